@@ -54,6 +54,11 @@ WORKLOADS = {
 # latency - are spread over it: config 3 at 2048 / 4096 / 8192 frames per batch runs 152 / 156 / 160 GS/s in the steady
 # state and 141 / 146 / 147 over a 20-step run, where the last batch's trip through the tail stages is in the timed region.
 DEFAULT_FRAMES = {"c2": 4096, "c3": 8192, "c5": 2048}
+# steps the measured bank takes between the clock run-in (on a bank of its own) and the warmup steps
+RUN_IN_STEPS = 16
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files together
+DUMP_SPECTRUM_FRAMES = 16      # frames of the last batch whose spectrum and psd rows are written
+DUMP_SEED = 20260
 WORKLOAD_TEXT = {
     "c2": "BASELINE config 2: one TCI-shaped IQ stream, 192 kS/s, 4096-pt FFT, 16 tracked peaks",
     "c3": "BASELINE config 3: wideband synthetic IQ, 2 MS/s, 16384-pt FFT, 256 concurrent CW peaks, one band per GPU "
@@ -85,7 +90,13 @@ def parse():
                          "--steps and --warmup are rounded up to whole replays")
     ap.add_argument("--no-delivery", action="store_true",
                     help="diagnostic: leave results in HBM (no sdr_poll in the timed loop), as round 1 measured")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's bands) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB in all; the same arguments give the same inputs in every run")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def f64_ops_per_sample(n, r32=False):
@@ -179,6 +190,53 @@ def cpu_baseline(rate, n, tones, free_last, seconds):
                   f"({block_frames}-frame block replayed {reps}x), {tones} listeners each, oracle/sdr_oracle.c "
                   f"(C restatement of the Go path, -O2 -ffp-contract=off); the Go binary itself cannot be built here",
     }
+
+
+def _columns(records: np.ndarray) -> np.ndarray:
+    """A record array as float64 [n, fields], a plain one as float64 [n] (every value is an integer below 2**53 or a
+    float)."""
+    if records.dtype.names is None:
+        return records.astype(np.float64)
+    return np.stack([records[f].astype(np.float64) for f in records.dtype.names], axis=-1).reshape(len(records), -1)
+
+
+def dump_outputs(out_dir: str, bank, delivery: bool, last_batch_index: int):
+    """--dump-outputs: what the last timed step computed, as a caller of the timed path receives it.
+
+    With delivery: the batch's records as sdr_poll handed them to the consumer thread - chunks, peaks, listeners,
+    edges, runes, rune_frames, and batch = (batch_index, first_frame, n_frames).  Always: the batch's frame records
+    (frame_records [frame, band, field]) and the spectrum and psd rows of a seeded sample of its frames (spectrum, psd
+    [k, band, N], spectrum_frames [k]).  Integers and records as float64, the float32 rows as they are.  An array over
+    its share of DUMP_LIMIT_BYTES keeps a seeded sample of its rows."""
+    arrays = {}
+    if delivery:
+        # the consumer's poll_counts lets the library fill the bank's reused record buffers without copying them out; after
+        # the timed region they still hold the last batch delivered (a poll that finds no batch writes nothing)
+        r = bank._res
+        assert r.batch_index == last_batch_index and r.n_frames == bank.last_batch_frames, (r.batch_index, last_batch_index)
+        arrays["batch"] = np.array([r.batch_index, r.first_frame, r.n_frames], np.float64)
+        for k, buf in bank._res_bufs.items():
+            arrays[k] = _columns(buf[:getattr(r, "n_" + k)])
+        arrays["rune_frames"] = bank._rune_frames[:r.n_runes].astype(np.float64)
+    frames = bank.last_batch_frames
+    recs = [bank.read_frame_records(b) for b in range(bank.n_bands)]
+    fields = [f for f in recs[0].dtype.names if f != "pad"]
+    arrays["frame_records"] = np.stack([_columns(r_[fields]) for r_ in recs], axis=1)
+    # (spectrum and psd take at most a sixteenth of the limit each: below any array's share, never sampled again below)
+    k = min(frames, DUMP_SPECTRUM_FRAMES, max(1, DUMP_LIMIT_BYTES // 16 // (4 * bank.n_bands * bank.n)))
+    sample = np.sort(np.random.default_rng(DUMP_SEED).choice(frames, size=k, replace=False))
+    rows = [[bank.read_spectrum(b, int(f)) for b in range(bank.n_bands)] for f in sample]
+    arrays["spectrum"] = np.array([[sp for sp, _ in row] for row in rows], np.float32)
+    arrays["psd"] = np.array([[psd for _, psd in row] for row in rows], np.float32)
+    arrays["spectrum_frames"] = sample.astype(np.float64)
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays) - 4096  # (room for each file's header)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            keep = np.random.default_rng(DUMP_SEED).choice(len(a), size=max(1, share // (a.nbytes // len(a))), replace=False)
+            a = a[np.sort(keep)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def spawn_ranks(n: int, deadline_s: float = 1500.0) -> int:
@@ -341,10 +399,13 @@ def main():
     my_bands = sharding.bands_of_rank(bands_per_gpu * world, world, rank)
     assert len(my_bands) == bands_per_gpu
 
-    bank = capi.Bank(shared.sample_rate, shared.block_size, n_bands=bands_per_gpu, edge_width=shared.edge_width,
-                     peak_threshold=shared.peak_threshold, signal_debounce=shared.signal_debounce,
-                     max_listeners=shared.max_listeners, max_batch_frames=frames, max_peaks=1024, find_peaks=True,
-                     trace=False, device_id=local_rank)
+    def make_bank():
+        return capi.Bank(shared.sample_rate, shared.block_size, n_bands=bands_per_gpu, edge_width=shared.edge_width,
+                         peak_threshold=shared.peak_threshold, signal_debounce=shared.signal_debounce,
+                         max_listeners=shared.max_listeners, max_batch_frames=frames, max_peaks=1024, find_peaks=True,
+                         trace=False, device_id=local_rank)
+
+    bank = make_bank()
     # the bank behind the job-wide setters (sharding.ShardedBank: rank 0's values, applied on every rank at the same batch
     # boundary) - one collective setter call before the timed region, as a host would make when the operator turns a knob
     sbank = sharding.ShardedBank(bank, shared, dist, coll_dev, n_bands_total=bands_per_gpu * world)
@@ -429,14 +490,27 @@ def main():
                 enqueued[0] += K
 
     # run-in (untimed, not counted as warmup): the clocks ramp up from idle over the first few hundred
-    # milliseconds of load; then the W warmup steps of the contract
-    t_settle = time.perf_counter()
-    k = 0
-    while (time.perf_counter() - t_settle) * 1e3 < args.settle_ms:
-        for _ in range(16):
-            step(k)
-            k += 1
-        torch.cuda.synchronize()
+    # milliseconds of load.  How many steps that takes varies from run to run, so it runs on a bank of its own (same
+    # configuration, listeners and inputs; created after the measured bank, whose streams keep the hardware queues they
+    # were dealt): the measured bank's history - and with it what the timed steps compute - is the same in every run.
+    # Then RUN_IN_STEPS on the measured bank and the W warmup steps of the contract
+    settler = None
+    if args.settle_ms > 0:
+        settler = make_bank()
+        settler.set_stream(stream.cuda_stream)
+        for bi in range(bands_per_gpu):
+            for b in bins_of_band[bi]:
+                settler.attach(bi, int(b))
+        t_settle = time.perf_counter()
+        k = 0
+        while (time.perf_counter() - t_settle) * 1e3 < args.settle_ms:
+            for _ in range(16):
+                settler.process_device(ring[k % len(ring)].data_ptr(), frames)
+                k += 1
+            torch.cuda.synchronize()
+    run_in = -(-RUN_IN_STEPS // K) * K if args.graph else RUN_IN_STEPS
+    for i in range(run_in):
+        step(i)
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
@@ -476,6 +550,10 @@ def main():
         every = [torch.zeros_like(own) for _ in range(world)]
         dist.all_gather(every, own)
         per_rank_s = [float(x.item()) for x in every]
+    if settler is not None:
+        settler.close()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bank, delivery, enqueued[0] - 1)
 
     samples_per_step_rank = frames * n * bands_per_gpu
     total_samples = samples_per_step_rank * args.steps * world

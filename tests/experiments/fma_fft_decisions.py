@@ -29,10 +29,12 @@ if ROOT not in sys.path:
 
 
 def _lib():
-    so = os.path.join(tempfile.gettempdir(), "libfma_fft_experiment.so")
-    src = os.path.join(ROOT, "tests", "experiments", "fma_fft.c")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-mfma", "-fPIC", "-shared", "-fvisibility=hidden", "-o", so, src, "-lm"])
-    L = C.CDLL(so)
+    # a directory of this process's own: a fixed name in the shared temp directory may belong to another user
+    with tempfile.TemporaryDirectory(prefix="fma_fft_experiment_") as d:
+        so = os.path.join(d, "libfma_fft_experiment.so")
+        src = os.path.join(ROOT, "tests", "experiments", "fma_fft.c")
+        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-mfma", "-fPIC", "-shared", "-fvisibility=hidden", "-o", so, src, "-lm"])
+        L = C.CDLL(so)  # (stays mapped after the file is removed)
     L.fma_iq_to_psd.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
