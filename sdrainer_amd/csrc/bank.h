@@ -94,6 +94,7 @@ struct BatchSet {
     DevBuf<float> tap;                // [band][max_batch][L] psd of each listener slot's bin
     DevBuf<float> tapw;               // [band][max_batch][L][4] psd at bin - 1, bin, bin + 1, 0 (k_fft_r32's wide tap; N = 16384 only)
     DevBuf<int32_t> tap_used;         // [band][L] the bins tapw was taken at (-1 = none)
+    DevBuf<uint32_t> fft_ctr;         // [band][2] k_fft_r32's frame counters (zeroed here; each launch leaves them zero)
     DevBuf<double> win_mean;          // [band][max_batch][10] (the chain kernels of SDR_NOISE_PATH=chains only)
     DevBuf<sdr_frame_rec> recs;       // [band][max_batch]
     DevBuf<uint64_t> raw_bits, bits;  // [band][L][bit_words] before / after the debouncer
@@ -115,6 +116,7 @@ struct BatchSet {
         tap.release();
         tapw.release();
         tap_used.release();
+        fft_ctr.release();
         win_mean.release();
         cum_part.release();
         recs.release();

@@ -78,6 +78,7 @@ hipError_t alloc_set(sdr_bank *b, BatchSet &S)
     if (b->logn == 14) {  // (the kernel that writes them serves this block size only)
         SET_ALLOC(S.tapw, B * F * 4 * std::max<size_t>(L, 1));
         SET_ALLOC(S.tap_used, B * std::max<size_t>(L, 1));
+        SET_ALLOC(S.fft_ctr, B * 2);
     }
     SET_ALLOC(S.win_mean, B * F * 10);
     SET_ALLOC(S.recs, B * F);

@@ -269,6 +269,7 @@ int process_device_body(sdr_bank *b, const float *iq_dev, int n_frames, int in_s
         sdr::FftTap tap{b->tap_bins.p, S.tap.p, max_slots, c.max_listeners};
         tap.wide = S.tapw.p;
         tap.used = S.tap_used.p;
+        tap.steal = S.fft_ctr.p;
         SDR_LAUNCH(sdr::K_FFT, sdr::launch_fft(b->logn, iq_dev, cur, b->tw.p, S.psd.p, n_frames, B, in_stride, stride, tap,
                                                stream_of(sdr::K_FFT)));
     }

@@ -1007,8 +1007,8 @@ static hipError_t launch_fft_t(const float *iq, const BatchCursor *cur, const ff
 }
 
 // N = 16384 has two kernels: this file's 16-point one and k_fft_r32.hip (512 threads x 32 points, the next frame
-// prefetched into registers), whose workgroups take several frames each.  SDR_FFT_R32 = 0 / 1 forces one of them (tests);
-// by default the 32-point kernel runs from 1024 frames per launch on (k_fft_r32.hip r32_fpw: measured by batch size).  The bank's
+// prefetched into registers), whose workgroups - one per CU - claim frames from a counter.  SDR_FFT_R32 = 0 / 1 forces one
+// of them (tests); by default the 32-point kernel runs from 1024 frames per launch on (measured by batch size).  The bank's
 // twiddle buffer holds both kernels' tables, the 32-point kernel's behind the other.
 static int r32_mode()
 {

@@ -6,8 +6,13 @@
 // wave of the CU parked (profiles/r04_fft_phase_order.txt) - and has neither the registers nor the LDS to fetch the next
 // frame meanwhile.  Here a workgroup is 512 threads x 32 points at two waves per SIMD: 256 VGPRs per thread, 128 for the
 // frame's complex128 state, 64 for the NEXT frame's complex64 samples, which are requested right after the current
-// frame's have been widened and have the whole frame to arrive.  A workgroup takes `fpw` consecutive frames; only its
-// first frame's input is waited for.
+// frame's have been widened and have the whole frame to arrive.
+//
+// Frames are claimed, not assigned: the grid is about one workgroup per CU, and each workgroup takes its next frame from
+// a per-band counter (one returning atomic add, one frame at a time) until the counter passes the batch.  A workgroup that
+// started late behind a tail kernel of another stream simply takes fewer frames; only a workgroup's first frame's input
+// is waited for, its twiddle block is loaded once per launch, and the launch ends at most one frame after its last
+// workgroup could have.  No workgroup ever waits on another: it claims, works and leaves.
 //
 // Frame schedule (per wave; B = workgroup barrier):
 //   widen the prefetched samples (f32 -> f64), request the next frame's
@@ -22,7 +27,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <mutex>
 
 #include "fft_r32.h"
@@ -152,7 +156,12 @@ enum PfPoint { PF_WIDENED = 0, PF_PASS0 = 1 /* +q */, PF_E0 = 6 /* +step */, PF_
 
 constexpr int kTw1LdsBytes = fft32::kTw1Entries * 16;
 constexpr int kSoftCounters = 4;
-constexpr int kLdsBytes = fft32::kExchangeBytes + kTw1LdsBytes + kSoftCounters * 4;
+// the band's frame counters' address and the grid's width, kept here rather than in SGPRs through the frame loop (the
+// frame has no scalar registers to spare: held there they pushed nine scalar registers out into vector-register lanes)
+constexpr int kStashWords = 4;
+// the frame claimed for the frame after next, one word per thread (only thread 0's is a claim: see claim_next)
+constexpr int kClaimBytes = fft32::T * 4;
+constexpr int kLdsBytes = fft32::kExchangeBytes + kTw1LdsBytes + (kSoftCounters + kStashWords) * 4 + kClaimBytes;
 // "Soft" barriers for the write-after-read hazards of the shared exchange area: a wave ARRIVES (one LDS add) when it has
 // read what it wanted and WAITS (polls the counter) right before it writes - a whole pass later, when everybody has long
 // arrived.  An s_barrier there would make the wave that is ahead sit out the other's pass: with two waves per SIMD the
@@ -228,9 +237,13 @@ __device__ __forceinline__ void ex_read(double (&x)[32], int t, const double *ar
         x[s] = area[base + fft32::map_addr_slot<E>(P, s)];
 }
 
+// The frame counters, [band][2] words: 0 = the next frame to claim, 1 = workgroups that have finished.  Zero between
+// launches: the workgroup that finishes last stores zero into both (launches on one pair are serialised by their stream,
+// and graph replay re-runs the same arguments: nothing on the host has to reset them).
+
 __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
                                                           const cplx *__restrict__ tw, float *__restrict__ psd, int in_stride,
-                                                          int out_stride, int n_frames, int fpw, const int *__restrict__ tap_bins,
+                                                          int out_stride, int n_frames, unsigned *__restrict__ steal, const int *__restrict__ tap_bins,
                                                           float *__restrict__ tap_out, int n_tap, int tap_stride,
                                                           float *__restrict__ tap_wide, int *__restrict__ tap_used)
 {
@@ -240,26 +253,45 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
     double *ex = reinterpret_cast<double *>(smem);
     const unsigned char *tw1_lds = smem + kExchangeBytes;
     const float *__restrict__ iq = cur ? cur->iq : iq_arg;  // graph replay: the batch's input pointer lives in device memory
-    const int frame0 = blockIdx.x * fpw;
-    const int frame_end = min(frame0 + fpw, n_frames);
-    const size_t in_band = (size_t)blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
+    const unsigned n_fr = (unsigned)n_frames;
+    constexpr unsigned kNoFrame = ~0u;  // (no frame: the row of `prev` in front of the first)
+    // this band's rows (four bases in eight SGPRs; with the bands' offsets kept beside the bases it was twelve)
+    const size_t out_band = (size_t)blockIdx.y * out_stride;
+    const float *const iq_b = iq + (size_t)blockIdx.y * in_stride * (size_t)N * 2;
+    float *const psd_b = psd + out_band * (size_t)N, *const tap_b = tap_out + out_band * (size_t)tap_stride;
+    float *const wide_b = tap_wide ? tap_wide + out_band * (size_t)(4 * tap_stride) : nullptr;
     const int tid = threadIdx.x;
     const rsrc_t twr = make_rsrc(tw, (unsigned)(kTwTotal * sizeof(cplx)));
 
     // setSamplesFromIQ's reads, one frame ahead: slot m <- sample tid + 512 * brev5(m) (fft_r32.h: pass 0's thread part of
     // the sample number is the thread id), 8 bytes per lane, 512 contiguous bytes per wave instruction
     u32x2 pf[R];
-    // slots [m0, m1) of `frame`; a frame past the workgroup's last one gets a descriptor of zero bytes: the loads return
-    // zeros without touching memory, and the frame's code stays free of branches
-    auto fetch = [&](int frame, int t, int m0, int m1) {
-        const rsrc_t xrs = make_rsrc(iq + (in_band + frame) * (size_t)N * 2, frame < frame_end ? N * 8u : 0u);
+    // slots [m0, m1) of `frame`; a claim past the batch gets a descriptor of zero bytes: the loads return zeros without
+    // touching memory, and the frame's code stays free of branches
+    auto fetch = [&](unsigned frame, int t, int m0, int m1) {
+        const bool live = frame < n_fr;
+        const rsrc_t xrs = make_rsrc(iq_b + (size_t)frame * N * 2, live ? N * 8u : 0u);
         const unsigned voff = (unsigned)thread_sample(t) * 8u;
 #pragma unroll
         for (int m = 0; m < R; m++)
             if (m >= m0 && m < m1)
                 pf[m] = __builtin_amdgcn_raw_buffer_load_b64(xrs, voff, slot_sample(m) * 8, SDR_R32_IN_AUX);
     };
-    fetch(frame0, tid, 0, R);
+    unsigned *stash = reinterpret_cast<unsigned *>(smem + kExchangeBytes + kTw1LdsBytes + kSoftCounters * 4);
+    unsigned *claim_lds = stash + kStashWords;
+    // the band's counters from the stash (see kStashWords)
+    auto band_ctr = [stash] {
+        const unsigned long long lo = (unsigned)__builtin_amdgcn_readfirstlane(stash[0]), hi = (unsigned)__builtin_amdgcn_readfirstlane(stash[1]);
+        return reinterpret_cast<unsigned *>((hi << 32) | lo);
+    };
+    // the first two frames, in one claim (the first one's input is the only one a workgroup waits for)
+    if (tid == 0) {
+        unsigned *const ctr = steal + 2 * blockIdx.y;
+        stash[0] = (unsigned)(unsigned long long)ctr;
+        stash[1] = (unsigned)((unsigned long long)ctr >> 32);
+        stash[2] = gridDim.x;
+        claim_lds[0] = __hip_atomic_fetch_add(ctr, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     // pass 1's twiddle block -> LDS, once per workgroup
     for (int i = tid; i < kTw1Entries; i += T) {
         const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(twr, (unsigned)i * 16u, kTw1 * 16, 0);
@@ -279,6 +311,9 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
     if (tid < kSoftCounters)
         soft[tid] = 0;
     __syncthreads();
+    // the frame this iteration computes, the one it prefetches and the one whose row it stores: wave-uniform (SGPRs)
+    unsigned frame = __builtin_amdgcn_readfirstlane(claim_lds[0]), next = frame + 1, prev = kNoFrame;
+    fetch(frame, tid, 0, R);
     R32Stamps st;
 #if defined(SDR_R32_PHASES)
     st.on = false;
@@ -293,15 +328,15 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
 #pragma unroll
     for (int j = 0; j < N / 4 / T; j++)
         sv[j] = u32x4{0u, 0u, 0u, 0u};
-    // (frame < frame0: descriptors of zero bytes, nothing is stored.  The run's offset goes into the VECTOR offset, the
+    // (prev = kNoFrame: descriptors of zero bytes, nothing is stored.  The run's offset goes into the VECTOR offset, the
     // scalar offset stays the literal 0: a 16-byte buffer store reads its data registers some cycles after it issues; with
     // an immediate scalar offset hipcc pads a following VALU write of those registers with wait states, with an SGPR
     // offset it assumes no hazard - and on gfx950 there is one: built that way, 0.3 % of the psd words of every launch
     // came out as the next run's LDS address, which the compiler had put into the first data register behind the store.)
     // stores [j0, j1) of the eight (tap: the tap value with the last one)
-    auto flush_row = [&](int frame, int t, int j0, int j1) {
-        const bool live = frame >= frame0;
-        const rsrc_t pdr = make_rsrc(psd + (out_band + (live ? frame : frame0)) * (size_t)N, live ? N * 4u : 0u);
+    auto flush_row = [&](unsigned frame, int t, int j0, int j1) {
+        const bool live = frame < n_fr;
+        const rsrc_t pdr = make_rsrc(psd_b + (size_t)frame * N, live ? N * 4u : 0u);
 #pragma unroll
         for (int j = 0; j < N / 4 / T; j++)
             if (j >= j0 && j < j1)
@@ -309,10 +344,19 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
         if (j1 == N / 4 / T) {
             // the tap (rx/receiver.go:393-394: spectrum[SignalBin] per listener and frame; the dB projection is applied
             // where it is consumed, k_listen.hip): slot l's value from thread l; lanes past n_tap fall outside the descriptor
-            const rsrc_t tpr = make_rsrc(tap_out + (out_band + (live ? frame : frame0)) * (size_t)tap_stride,
+            const rsrc_t tpr = make_rsrc(tap_b + (size_t)frame * tap_stride,
                                          (live && reg_tap) ? (unsigned)n_tap * 4u : 0u);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(tapv), tpr, (unsigned)t * 4u, 0, 0);
         }
+    };
+    // The claim for the frame after next, issued at the top of a frame and published to the workgroup (claim_lds, read
+    // behind the row's barrier) behind E0 - pass 0 later, when it has long returned: the prefetch of that frame starts
+    // at the top of the next one.  One returning atomic add by thread 0 - the other lanes aim past a descriptor of four
+    // bytes, which drops them (as C++ a one-lane branch would cut the frame into basic blocks); the value is live in one
+    // register through pass 0 only, while the prefetched samples have most of theirs still free.
+    auto claim_next = [&](int t) {
+        const rsrc_t crs = make_rsrc(band_ctr(), 4u);
+        return (unsigned)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, crs, (unsigned)t * 4u, 0, 0);
     };
 
 #if SDR_R32_PRIO
@@ -320,12 +364,12 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
 #endif
     int it = 0;  // frames this workgroup has finished (the soft barriers' targets count in it)
 #pragma nounroll
-    for (int frame = frame0; frame < frame_end; frame++, it++) {
+    while (frame < n_fr) {
         // (everything derived from the thread id is loop-invariant; hoisted, it would sit in registers the frame needs)
         int t = tid;
         asm volatile("" : "+v"(t));
 #if defined(SDR_R32_PHASES)
-        st.on = blockIdx.x == SDR_R32_PHASES && blockIdx.y == 0 && frame == frame0 + 1;
+        st.on = blockIdx.x == SDR_R32_PHASES && blockIdx.y == 0 && it == 1;
 #endif
         SDR_R32_STAMP(st, RS_TOP);
 #if defined(SDR_R32_PHASES)
@@ -350,20 +394,22 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
         auto pf_point = [&](int point) {
             __builtin_amdgcn_sched_barrier(0);
             if (point < kStorePoints)
-                flush_row(frame - 1, t, st_begin(point), st_begin(point + 1));
-            fetch(frame + 1, t, pf_begin(point), pf_begin(point + 1));
+                flush_row(prev, t, st_begin(point), st_begin(point + 1));
+            fetch(next, t, pf_begin(point), pf_begin(point + 1));
             __builtin_amdgcn_sched_barrier(0);
         };
 #if defined(SDR_R32_PHASES)  // (the first point taken apart for its stamps)
         SDR_R32_STAMP(st, RS_CVT);
         __builtin_amdgcn_sched_barrier(0);
-        flush_row(frame - 1, t, st_begin(PF_WIDENED), st_begin(PF_WIDENED + 1));
+        flush_row(prev, t, st_begin(PF_WIDENED), st_begin(PF_WIDENED + 1));
         SDR_R32_STAMP(st, RS_FLUSHED);
-        fetch(frame + 1, t, pf_begin(PF_WIDENED), pf_begin(PF_WIDENED + 1));
+        fetch(next, t, pf_begin(PF_WIDENED), pf_begin(PF_WIDENED + 1));
         __builtin_amdgcn_sched_barrier(0);
 #else
         pf_point(PF_WIDENED);
 #endif
+        const unsigned claimed = claim_next(t);
+        __builtin_amdgcn_sched_barrier(0);
         SDR_R32_STAMP(st, RS_WIDENED);
 
         // pass 0; behind its stage 3 everybody must be out of the previous frame's psd row (it shares the area with E0):
@@ -398,6 +444,8 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
         ex_read<0, 1>(xi, t, ex);
         pf_point(PF_E0 + 3);
         soft_arrive(soft + SOFT_E0);  // this wave has what it wanted from E0 (E1 writes blocks other waves read here)
+        // (every wave has read the previous claim: it did so in front of this frame's E0 barriers)
+        claim_lds[t] = claimed;
         SDR_R32_STAMP(st, RS_E0);
         pf_point(PF_PRE1);
 
@@ -491,8 +539,8 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
             // store costs the frame is its issue: as three dword stores by every wave this was 2.4 % of the kernel.  Lanes
             // without a slot aim past the descriptor (no per-lane branch).  A neighbour that does not exist (bin 0's left,
             // bin N - 1's right) wraps to a word nobody reads.
-            if (__builtin_amdgcn_readfirstlane(t) < n_tap && tap_wide) {  // (wave-uniform)
-                const rsrc_t wr = make_rsrc(tap_wide + (out_band + frame) * (size_t)(4 * tap_stride), reg_tap ? (unsigned)tap_stride * 16u : 0u);
+            if (__builtin_amdgcn_readfirstlane(t) < n_tap && wide_b) {  // (wave-uniform; frame < n_frames here)
+                const rsrc_t wr = make_rsrc(wide_b + (size_t)frame * (4 * tap_stride), reg_tap ? (unsigned)tap_stride * 16u : 0u);
                 u32x4 wv;
                 wv.x = __float_as_uint(row[row_word((my_bin - 1) & (N - 1))]);
                 wv.y = __float_as_uint(tv);
@@ -501,69 +549,79 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
                 __builtin_amdgcn_raw_buffer_store_b128(wv, wr, t < n_tap ? (unsigned)t * 16u : 0x7ffffff0u, 0, 0);
             }
         }
+        // the frame after next, published behind E0 and ordered before this read by the row's barrier
+        const unsigned after = __builtin_amdgcn_readfirstlane(claim_lds[0]);
         soft_arrive(soft + SOFT_ROW);  // this wave is out of the row
         SDR_R32_STAMP(st, RS_STORED);
 #if defined(SDR_R32_PHASES)
         if (st.on && (threadIdx.x & 63) < RS_COUNT)
             g_r32_phases[threadIdx.x >> 6][threadIdx.x & 63] = st.v;
 #endif
+        prev = frame;
+        frame = next;
+        next = after;
+        it++;
     }
-    flush_row(frame_end - 1, tid, 0, N / 4 / T);
+    // (the thread id afresh: the prologue's `tid == 0` held through the loop is two more scalar registers)
+    int t = tid;
+    asm volatile("" : "+v"(t));
+    flush_row(prev, t, 0, N / 4 / T);
+    // Every claim of this workgroup has returned (each was consumed); the workgroup that finishes last finds all others'
+    // claims done and puts the band's counters back to zero for the next launch.
+    if (t == 0) {
+        unsigned *const ctr = band_ctr();
+        const unsigned done = __hip_atomic_fetch_add(ctr + 1, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (done == stash[2] - 1) {
+            __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(ctr + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
 }  // namespace r32
 
-// Frames per workgroup of the R32 kernel (SDR_FFT_R32_FPW overrides).  A workgroup's first frame is not prefetched and
-// its twiddle block is loaded once, so more frames per workgroup are cheaper frames (standalone, 8192 frames: 0.517 ms at
-// four, 0.494 at eight, 0.481 at thirty-two) - but the tail stages hold CUs while a launch runs, and a launch that is two
-// or three rounds of workgroups over the CUs it gets ends on a round that is nearly empty: in the pipeline about a
-// thousand workgroups per launch is what measures best, four frames each at most (config 3, GS/s by frames per batch and
-// frames per workgroup: 8192 - 1: 170, 2: 189, 3: 190, 4: 195, 6: 189, 8: 187; 3072 - 3: 170, 4: 155; 2048 - 1: 154, 2: 173,
-// 3: 174, 4: 155; 1024 - 1: 141, 2: 163, the sixteen-point kernel 152; 512 - 1: 98, 2: 94, the sixteen-point kernel 104:
-// launch_fft sends batches of fewer than 1024 frames there).
-static int r32_fpw(long total_frames)
-{
-    static const int forced = [] {
-        const char *e = getenv("SDR_FFT_R32_FPW");
-        return e ? std::max(1, std::min(atoi(e), 1024)) : 0;
-    }();
-    if (forced)
-        return forced;
-    return total_frames >= 4096 ? 4 : total_frames >= 2560 ? 3 : 2;
-}
-
 int r32_twiddle_count() { return fft32::kTwTotal; }
 void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out) { fft32::build_twiddles(wre, wim, out); }
+
+// Workgroups per band: one per CU, less SDR_R32_RESERVE CUs left to the tail stages of the other streams (measured at
+// config 3, see HISTORY round 6), never more than there are frames.
+#if !defined(SDR_R32_RESERVE)
+#define SDR_R32_RESERVE 0
+#endif
 
 hipError_t launch_fft_r32(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
                           int in_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
     constexpr int kMaxDevices = 64;
-    static std::once_flag attr_once[kMaxDevices];
+    static std::once_flag setup_once[kMaxDevices];
+    static hipError_t setup_err[kMaxDevices];  // (kept: every later call reports why the first one failed)
+    static int cu_count[kMaxDevices];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess)
         return e;
     if (dev < 0 || dev >= kMaxDevices)
         return hipErrorInvalidDevice;
-    hipError_t attr_err = hipSuccess;
-    std::call_once(attr_once[dev], [&] {
-        attr_err = hipFuncSetAttribute(reinterpret_cast<const void *>(&r32::k_fft_r32), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       r32::kLdsBytes);
+    std::call_once(setup_once[dev], [dev] {
+        hipError_t se = hipFuncSetAttribute(reinterpret_cast<const void *>(&r32::k_fft_r32), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            r32::kLdsBytes);
+        if (se == hipSuccess)
+            se = hipDeviceGetAttribute(&cu_count[dev], hipDeviceAttributeMultiprocessorCount, dev);
+        setup_err[dev] = se;
     });
-    if (attr_err != hipSuccess)
-        return attr_err;
+    if (setup_err[dev] != hipSuccess)
+        return setup_err[dev];
     if (n_frames <= 0 || n_bands <= 0)
         return hipSuccess;
     if (tap.n > fft32::T)
         return hipErrorInvalidValue;  // (launch_fft never asks: one listener slot per thread)
-    // a workgroup's frames are consecutive; never fewer workgroups than the chip has CUs
-    int fpw = r32_fpw((long)n_frames * n_bands);
-    while (fpw > 1 && (long)((n_frames + fpw - 1) / fpw) * n_bands < 256)
-        fpw /= 2;
-    launch_kernel(r32::k_fft_r32, dim3((n_frames + fpw - 1) / fpw, n_bands), dim3(fft32::T), r32::kLdsBytes, stream, iq, cur, tw, psd,
-                  in_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used);
+    if (!tap.steal)
+        return hipErrorInvalidValue;  // the frame counters are the bank's (BatchSet::fft_ctr)
+    const int cus = std::max(1, cu_count[dev] - SDR_R32_RESERVE);
+    const int grid = std::min((cus + n_bands - 1) / n_bands, n_frames);
+    launch_kernel(r32::k_fft_r32, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, stream, iq, cur, tw, psd, in_stride, out_stride,
+                  n_frames, tap.steal, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used);
     return hipGetLastError();
 }
 

@@ -136,6 +136,8 @@ struct FftTap {
     // and the bins those rows were taken at, [band][stride] (-1 = none): what k_cum_refine reads instead of psd columns
     float *wide = nullptr;
     int32_t *used = nullptr;
+    // k_fft_r32 only: its frame counters, [band][2] uint32, zero between launches (BatchSet::fft_ctr)
+    uint32_t *steal = nullptr;
 };
 
 hipError_t launch_fft(int logn, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,

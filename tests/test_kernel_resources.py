@@ -1,0 +1,60 @@
+"""k_fft_r32's register budget, checked at compile time (no GPU): the kernel runs at two waves per SIMD with every vector
+register in use, and a toolchain or source change that pushes its prefetched samples out to scratch costs 20 - 30 % of
+the kernel without changing a single result.  The kernel is compiled device-only for gfx950 with the library's own
+flags (sdrainer_amd/csrc/build.py) and the compiler's resource report is read."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from sdrainer_amd.csrc import build as hip_build
+
+SRC = os.path.join(hip_build.HERE, "k_fft_r32.hip")
+
+
+@pytest.fixture(scope="module")
+def usage(tmp_path_factory):
+    try:
+        cc = hip_build.hipcc()
+    except RuntimeError as e:
+        pytest.fail(str(e))
+    out = tmp_path_factory.mktemp("res") / "k_fft_r32.o"
+    flags = hip_build.FLAGS + hip_build.EXTRA_FLAGS.get("k_fft_r32.hip", [])
+    cmd = [cc] + flags + ["--cuda-device-only", "-c", SRC, "-o", str(out), "-Rpass-analysis=kernel-resource-usage"]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-4000:]
+    # the remarks of the function whose name holds k_fft_r32, up to the next function's
+    m = re.search(r"Function Name: \S*k_fft_r32\S*(.*?)(?:Function Name:|\Z)", p.stderr, re.S)
+    assert m, "no resource report for k_fft_r32"
+    return {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", m.group(1))}
+
+
+def _int(usage, key):
+    assert key in usage, f"{key!r} missing from the report: {sorted(usage)}"
+    return int(usage[key])
+
+
+def test_no_spills(usage):
+    assert _int(usage, "VGPRs Spill") == 0
+    assert _int(usage, "SGPRs Spill") == 0
+
+
+def test_no_scratch(usage):
+    assert _int(usage, "ScratchSize [bytes/lane]") == 0
+
+
+def test_vgprs_and_occupancy(usage):
+    assert _int(usage, "VGPRs") <= 256
+    assert _int(usage, "Occupancy [waves/SIMD]") == 2
+
+
+def test_lds_fits():
+    """The LDS is dynamic (the report says 0): the kernel's own constant kLdsBytes, evaluated by the compiler."""
+    probe = ('#include "k_fft_r32.hip"\n'
+             'static_assert(sdr::r32::kLdsBytes <= 160 * 1024, "k_fft_r32 needs more LDS than a CU has");\n')
+    cc = hip_build.hipcc()
+    p = subprocess.run([cc] + hip_build.FLAGS + hip_build.EXTRA_FLAGS.get("k_fft_r32.hip", []) +
+                       ["--cuda-device-only", "-fsyntax-only", "-I", hip_build.HERE, "-x", "hip", "-"],
+                       input=probe, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-4000:]

@@ -76,6 +76,9 @@ int main(int argc, char **argv)
     CK(hipMalloc(&pd, total * N * 4));
     const int n_tap = getenv("SDR_TAP") ? atoi(getenv("SDR_TAP")) : 256;
     sdr::FftTap tap{nullptr, nullptr, n_tap, n_tap > 0 ? n_tap : 1};
+    // k_fft_r32's frame counters (N = 16384 from 1024 frames on), a zeroed pair per band
+    CK(hipMalloc(&tap.steal, (size_t)bands * 2 * sizeof(uint32_t)));
+    CK(hipMemset(tap.steal, 0, (size_t)bands * 2 * sizeof(uint32_t)));
     float *dout = nullptr;
     if (n_tap > 0) {
         std::vector<int32_t> bins((size_t)n_tap * bands);

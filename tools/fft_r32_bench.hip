@@ -4,7 +4,7 @@
 //     the oracle by the GPU tests)
 //   - timing of each: single launches (min / median of 30) and 100 launches back to back
 //   - -DSDR_R32_PHASES=<workgroup>: the phase timeline of that workgroup's second frame, every wave
-// usage: fft_r32_bench [frames [bands]]      env SDR_FFT_R32_FPW = frames per workgroup, SDR_TAP = listeners
+// usage: fft_r32_bench [frames [bands]]      env SDR_TAP = listeners
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,8 +50,6 @@ int main(int argc, char **argv)
     const int logn = 14, N = 1 << logn;
     printf("# fft_r32_bench: %d band(s) x %d frames of %d points\n# flags: %s\n# kernel sources sha256: %s\n", bands, frames, N,
            SDR_TOOL_FLAGS, SDR_SRC_HASH);
-    if (const char *e = getenv("SDR_FFT_R32_FPW"))
-        printf("# SDR_FFT_R32_FPW=%s\n", e);
     std::vector<double> wre, wim;
     fft64::radix2_factors(N, wre, wim);
     // (the library's table for N = 16384 holds both kernels' twiddles; the tool launches each kernel on its own)
@@ -98,6 +96,9 @@ int main(int argc, char **argv)
         }
         host_bins = bins;
     }
+    // k_fft_r32's frame counters, a zeroed pair per band (each launch leaves them zero)
+    CK(hipMalloc(&tap32.steal, (size_t)bands * 2 * sizeof(uint32_t)));
+    CK(hipMemset(tap32.steal, 0, (size_t)bands * 2 * sizeof(uint32_t)));
     {
         // wide dynamic range: a strong on-bin carrier, weak noise, a few zeros and subnormals
         std::vector<float> x(total * N * 2);

@@ -28,8 +28,8 @@ if [ "$PART" != pipeline ]; then
 # 1. the dominant kernel alone.  N = 16384 is served by k_fft_r32 (512 threads x 32 points); the 16-point-per-thread
 #    k_fft_psd<14> (SDR_FFT_R32=0) and k_fft_psd<13> on the same number of samples stand beside it (verdict r4 1a).
 {
-  for fpw in 4 8 32; do echo "== r32_prod 8192 frames FPW=$fpw"; SDR_FFT_R32_FPW=$fpw SDR_R32_ONLY=1 timeout -k 5 90 tools/bin/r32_prod 8192 1; done
-  echo "== r32_prod 2048 frames FPW=4"; SDR_R32_ONLY=1 timeout -k 5 90 tools/bin/r32_prod 2048 1
+  echo "== r32_prod 8192 frames"; SDR_R32_ONLY=1 timeout -k 5 90 tools/bin/r32_prod 8192 1
+  echo "== r32_prod 2048 frames"; SDR_R32_ONLY=1 timeout -k 5 90 tools/bin/r32_prod 2048 1
   echo "== r32_prod 8192 frames, word by word against k_fft_psd<14>"; timeout -k 5 120 tools/bin/r32_prod 8192 1
 } > $O/r32_standalone.txt 2>&1
 timeout -k 5 90 tools/bin/r32_phases 8192 1 > $O/r32_phases.txt 2>&1 || true
