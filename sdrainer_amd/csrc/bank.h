@@ -47,7 +47,7 @@ template <class T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
-    hipError_t alloc(size_t count)
+    hipError_t alloc(size_t count, int byte = 0)  // (every byte of the buffer set to `byte`)
     {
         n = count;
         if (count == 0)
@@ -55,7 +55,7 @@ struct DevBuf {
         hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T));
         if (e != hipSuccess)
             return e;
-        e = hipMemset(p, 0, count * sizeof(T));
+        e = hipMemset(p, byte, count * sizeof(T));
         if (e != hipSuccess)
             return e;
         // the memset runs on the null stream, which non-blocking streams (the bank's own, the copy stream) do not
@@ -218,6 +218,10 @@ struct sdr_bank {
         int64_t first_frame = 0, batch = 0;
     } pend;
     std::vector<int> late_attached;  // flattened slot indices bound by sdr_attach_at, not on the device yet
+    // k_put_slots launched on the listen stream and not yet known to be done: slots_put_ev is recorded behind the last of
+    // them, and every gather off the listen stream waits for it until a query (or sync_bank) finds it complete
+    bool slots_put = false;
+    hipEvent_t slots_put_ev = nullptr;
     // bulk delivery (host/delivery.h): sdr_poll may run on a consumer thread of its own beside the producer's process
     // calls (the reference's Reporter is called from other goroutines too); the bookkeeping - which finished batch sits in
     // which set's pinned block or in the parked queue, who takes it - is the Delivery's, under its mutex

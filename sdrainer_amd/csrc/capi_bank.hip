@@ -38,6 +38,7 @@ int sync_bank(sdr_bank *b)
     }
     for (int s = 0; s < N_STAGES; s++)
         HIP_TRY(hipStreamSynchronize(b->stream[s]));
+    b->slots_put = false;
     resolve_profile(b);
     return SDR_OK;
 }
@@ -77,7 +78,10 @@ hipError_t alloc_set(sdr_bank *b, BatchSet &S)
     SET_ALLOC(S.tap, B * F * std::max<size_t>(L, 1));
     if (b->logn == 14) {  // (the kernel that writes them serves this block size only)
         SET_ALLOC(S.tapw, B * F * 4 * std::max<size_t>(L, 1));
-        SET_ALLOC(S.tap_used, B * std::max<size_t>(L, 1));
+        // -1 = no bin: k_fft_r32 rewrites the first min(L, 512) entries per band at every launch; the rest are never
+        // written and, zeroed, would claim bin 0 (k_cum_refine reads only the first n_tap <= 512)
+        if (e == hipSuccess)
+            e = S.tap_used.alloc(B * std::max<size_t>(L, 1), 0xff);
         SET_ALLOC(S.fft_ctr, B * 2);
     }
     SET_ALLOC(S.win_mean, B * F * 10);
@@ -317,6 +321,8 @@ int sdr_destroy(sdr_bank *b)
         (void)hipStreamSynchronize(b->stream[s]);
     resolve_profile(b);
     drop_graphs(b);
+    if (b->slots_put_ev)
+        (void)hipEventDestroy(b->slots_put_ev);
     for (auto &ph : b->phase_done)
         for (auto &ev : ph)
             if (ev)

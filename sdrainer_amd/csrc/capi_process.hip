@@ -55,9 +55,10 @@ __global__ void k_put_bins(int32_t *bins, BinPack p)
         bins[p.index[i]] = p.bin[i];
 }
 
-// The listeners bound by sdr_attach_at since the last flush, to the device: their slots on the listen stream (the only
-// stream that touches slots), their tap bins on the FFT stream (read by the next FFT) - a handful of launches whatever
-// their number, and no synchronous copy.
+// The listeners bound by sdr_attach_at since the last flush, to the device: their slots on the listen stream (where the
+// decoder, which carries their state, runs; a gather on another stream waits for slots_put_ev - process_device_body),
+// their tap bins on the FFT stream (read by the next FFT) - a handful of launches whatever their
+// number, and no synchronous copy.
 int flush_late_attached(sdr_bank *b)
 {
     if (b->late_attached.empty())
@@ -73,6 +74,10 @@ int flush_late_attached(sdr_bank *b)
         hipLaunchKernelGGL(k_put_slots, dim3(1), dim3(256), 0, b->stream[S_LISTEN], b->slots.p, p);
         HIP_TRY(hipGetLastError());
     }
+    if (!b->slots_put_ev)
+        HIP_TRY(hipEventCreateWithFlags(&b->slots_put_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(b->slots_put_ev, b->stream[S_LISTEN]));  // (behind every earlier put too: one stream)
+    b->slots_put = true;
     for (size_t at = 0; at < v.size(); at += PUT_BINS) {
         BinPack p{};
         p.n = (int32_t)std::min<size_t>(PUT_BINS, v.size() - at);
@@ -159,6 +164,7 @@ int process_device_body(sdr_bank *b, const float *iq_dev, int n_frames, int in_s
     // from batch to batch and so may run on any stream, moves behind the thresholds it waits for anyway (config 2:
     // 0.206 -> 0.142 ms per 4096-frame step, 80 -> 118 GS/s; config 3 unchanged within a percent either way, config 5's
     // share 10 % SLOWER with it: its peaks stream is the full one).  Not under capture: a replay's graphs are cut by stream.
+    // (a gather there also waits for late-attached slots: see slots_put below)
     if (!cap && (long)B * N <= 8192)
         plan[sdr::K_LISTEN_GATHER] = S_PEAKS;
     // is kernel k part of the graph that is recording (always, outside a capture)?
@@ -336,6 +342,21 @@ int process_device_body(sdr_bank *b, const float *iq_dev, int n_frames, int in_s
     if (do_listen) {
     SDR_AFTER(sdr::K_LISTEN_GATHER, sdr::K_THRESHOLDS);
     SDR_AFTER(sdr::K_LISTEN_GATHER, sdr::K_FFT);
+    // Slots of listeners bound by sdr_attach_at: the gather reads a slot's active, bin, start_frame and tapped_from, and
+    // k_put_slots writes them word by word on the listen stream (flush_late_attached, this call's or an earlier one's).
+    // The waits above say nothing about that stream, and the listen stream of a small plan runs a batch or more behind
+    // the peaks stream, so a gather elsewhere waits for the last put until the host has seen it complete.  The other slot
+    // writers on the listen stream need no such wait: k_set_debounce writes deb.threshold, k_listener_stop dec /
+    // text_count / text_dropped, and k_listen_decode of the batch before moves start_frame and tapped_from of a listener
+    // that has started from a frame at or before that batch's first to this batch's first - old or new, the gather
+    // skips no frame and reads every one from the tap; sdr_attach and sdr_detach write slots only after sync_bank has
+    // drained every stream.
+    if (!cap && b->slots_put) {
+        if (hipEventQuery(b->slots_put_ev) == hipSuccess)
+            b->slots_put = false;
+        else if (plan[sdr::K_LISTEN_GATHER] != S_LISTEN)
+            HIP_TRY(hipStreamWaitEvent(stream_of(sdr::K_LISTEN_GATHER), b->slots_put_ev, 0));
+    }
     // (armed whether or not the stage launches: SDR_DONE records a stage event nobody took the ordinary way, and a
     // stage left out must still publish its event - the set-reuse wait reads the last stage of each stream)
     SDR_ARM(sdr::K_LISTEN_GATHER);

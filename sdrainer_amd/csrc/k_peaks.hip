@@ -372,6 +372,9 @@ __global__ __launch_bounds__(kRefineThreads) void k_cum_refine(float *__restrict
     for (int i = tid; i < kRefineSpan; i += T)
         s_tapidx[i] = 0xffffu;
     __syncthreads();
+    // (relies on l < n_tap <= 512: the process step passes the wide tap only when k_fft_r32 ran, which serves at most 512
+    // slots (fft_writes_wide_tap), and that kernel rewrites tap_used[0 .. min(tap_stride, 512)) at every launch - entries
+    // beyond are -1 from the allocation and never current)
     if (tap_wide) {
         for (int l = tid; l < n_tap; l += T) {
             const int b = tap_used[(size_t)band * tap_stride + l];

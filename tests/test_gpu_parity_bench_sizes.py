@@ -66,15 +66,20 @@ def _run_oracle(rate, n, edge, bins_per_band, iq_per_band, centers):
     return refs, outs
 
 
-def _check_batch_polled(res, outs, a, e, tones, text, n_bands):
-    """One polled batch (sdr_poll: what bench.py's consumer thread receives) against the oracle's whole-run output."""
+def _check_batch_polled(res, outs, a, e, tones, text, n_bands, live=None, gone=()):
+    """One polled batch (sdr_poll: what bench.py's consumer thread receives) against the oracle's whole-run output.
+    live[band]: the listener ids to check (default: 0 .. tones - 1); gone: (band, listener) pairs detached before the
+    batch, which must deliver nothing."""
     assert res["first_frame"] == a and res["n_frames"] == e - a
     assert res["runes_dropped"] == 0 and res["edges_dropped"] == 0
     by = {(int(r["band"]), int(r["listener"])): r for r in res["listeners"]}
+    for key in gone:
+        r = by.get(key)
+        assert r is None or (r["n_edges"] == 0 and r["n_runes"] == 0), f"band {key[0]} listener {key[1]}: delivers after its detach"
     n_edges = 0
     for band in range(n_bands):
         out = outs[band]
-        for lid in range(tones):
+        for lid in (range(tones) if live is None else live[band]):
             trans, states = _transitions(out["deb"][:, lid], a, e)
             r = by.get((band, lid))
             if r is None:
@@ -97,6 +102,36 @@ def _check_batch_polled(res, outs, a, e, tones, text, n_bands):
     want = {(band, gc) for band in range(n_bands) for gc, f in enumerate(outs[band]["peak_frames"]) if a <= f < e}
     assert seen == want
     return n_edges, n_peaks
+
+
+def _check_device_batch(bank, outs, a, e, n_bands, live, k, cumulations=True):
+    """What the last batch [a, e) left on the device against the oracle: frame records, the keying bits of the listeners
+    live[band], and (cumulations) every cumulation row it completed."""
+    for b in range(n_bands):
+        recs = bank.read_frame_records(b)
+        for f in REC_FIELDS:
+            assert _bits_equal(recs[f], outs[b]["frames"][f][a:e].copy()), f"band {b} batch {k} field {f}"
+        for lid in live[b]:
+            assert np.array_equal(bank.read_keying_bits(b, lid), outs[b]["deb"][a:e, lid]), f"band {b} listener {lid} batch {k}"
+        if not cumulations:
+            continue
+        for c in range(bank.last_batch_chunks):
+            _, _, fr = bank.read_peaks(b, c)
+            gc = list(outs[b]["peak_frames"]).index(a + fr)
+            exact = outs[b]["cumulation"][gc]
+            assert _bits_equal(bank.read_cumulation(b, c), exact), f"band {b} cumulation {gc}"
+            # the row as the pipeline keeps it (k_peaks.hip: exact where FindPeaks reads it, an upper bound elsewhere):
+            # never below the exact cumulation in any bin, equal to it in every bin of every peak and beside its maximum
+            os.environ["SDR_READ_CUM_RAW"] = "1"
+            try:
+                raw = bank.read_cumulation(b, c)
+            finally:
+                del os.environ["SDR_READ_CUM_RAW"]
+            assert np.all(raw >= exact), f"band {b} cumulation {gc}: the kept row is below the exact one somewhere"
+            pk, _, _ = bank.read_peaks(b, c)
+            for p in pk:
+                lo, hi = max(p[0], p[6] - 1), min(p[1], p[6] + 1)
+                assert _bits_equal(raw[p[0]:p[1] + 1], exact[p[0]:p[1] + 1]) and _bits_equal(raw[lo:hi + 1], exact[lo:hi + 1])
 
 
 def _eager_case(capi, rate, n, tones, n_bands, frames, n_batches, free_last, seed, tail_frames=0):
@@ -132,29 +167,7 @@ def _eager_case(capi, rate, n, tones, n_bands, frames, n_batches, free_last, see
         edges += ne
         peaks += npk
         # what stays on the device: frame records, keying bits, cumulations
-        for b in range(n_bands):
-            recs = bank.read_frame_records(b)
-            for f in REC_FIELDS:
-                assert _bits_equal(recs[f], outs[b]["frames"][f][a:e].copy()), f"band {b} batch {k} field {f}"
-            for lid in range(tones):
-                assert np.array_equal(bank.read_keying_bits(b, lid), outs[b]["deb"][a:e, lid]), f"band {b} listener {lid} batch {k}"
-            for c in range(bank.last_batch_chunks):
-                _, _, fr = bank.read_peaks(b, c)
-                gc = list(outs[b]["peak_frames"]).index(a + fr)
-                exact = outs[b]["cumulation"][gc]
-                assert _bits_equal(bank.read_cumulation(b, c), exact), f"band {b} cumulation {gc}"
-                # the row as the pipeline keeps it (k_peaks.hip: exact where FindPeaks reads it, an upper bound elsewhere):
-                # never below the exact cumulation in any bin, equal to it in every bin of every peak and beside its maximum
-                os.environ["SDR_READ_CUM_RAW"] = "1"
-                try:
-                    raw = bank.read_cumulation(b, c)
-                finally:
-                    del os.environ["SDR_READ_CUM_RAW"]
-                assert np.all(raw >= exact), f"band {b} cumulation {gc}: the kept row is below the exact one somewhere"
-                pk, _, _ = bank.read_peaks(b, c)
-                for p in pk:
-                    lo, hi = max(p[0], p[6] - 1), min(p[1], p[6] + 1)
-                    assert _bits_equal(raw[p[0]:p[1] + 1], exact[p[0]:p[1] + 1]) and _bits_equal(raw[lo:hi + 1], exact[lo:hi + 1])
+        _check_device_batch(bank, outs, a, e, n_bands, [range(tones)] * n_bands, k)
     for b in range(n_bands):
         for lid in range(tones):
             assert text[b][lid] == refs[b].text(lid), f"band {b} listener {lid} text"
