@@ -307,6 +307,51 @@ int sdr_graph_launch(sdr_bank *bank, const float *const *iq_dev);
  * goes with them - read it (sdr_read_*) before the release. */
 int sdr_graph_release(sdr_bank *bank);
 
+/* several GPUs, one process ------------------------------------------------------------------ */
+/* An sdr_group drives one sdr_bank per member - a member is a HIP device ordinal; the same ordinal may repeat (two banks
+ * on one device) - as ONE bank of cfg->n_bands bands: band b lives on member b % n_members as local band b / n_members
+ * (sharding.bands_of_rank).  Every member gets the rest of *cfg unchanged (geometry, listeners, capacities, find_peaks,
+ * trace); cfg->device_id is ignored; n_bands < n_members is SDR_ERR_BAD_ARG.  Semantics are the bank's unless stated:
+ *   - per-band calls (sdr_attach, sdr_attach_at, sdr_detach, sdr_listener_stop, sdr_set_center_frequency, sdr_read_*,
+ *     sdr_scope_*) go to the member bank and local band sdr_group_member names;
+ *   - sdr_group_process_staged(_limit) takes the minimum of staged frames over ALL the group's bands and every member
+ *     processes that many, so frame indices, cumulation boundaries and batch_index agree across the group;
+ *   - sdr_group_process_device takes one device pointer per member, each laid out as sdr_process_device's over the
+ *     member's local bands; every member is enqueued before the call waits for anything;
+ *   - the setters apply to every member before the next process call: every band changes at the same frame
+ *     (band = -1: every band);
+ *   - sdr_group_poll delivers batch k once every member has finished it, merged into one sdr_results with global band
+ *     numbers in exactly one bank's order (chunks by band, then chunk; listeners by band, then slot), first_peak /
+ *     first_edge / first_rune renumbered, drop counters summed.  A member batch already taken from its bank is kept by
+ *     the group through SDR_ERR_WOULD_BLOCK (another member is behind) and SDR_ERR_BAD_SIZE (n_* set, nothing
+ *     delivered); the next call delivers the same batch whole.  Members that disagree on batch_index, first_frame or
+ *     n_frames: SDR_ERR_STATE.  sdr_group_poll_peaks is the chunks / peaks half of the same merge.
+ * Threading is the bank's: one producer thread, plus one consumer thread in sdr_group_poll.  Every group call leaves the
+ * caller's current HIP device as it found it.  The processing calls check every member (listen half pending, graph
+ * captured, pointers) before any member is launched; a failure after that (SDR_ERR_HIP) marks the group failed and its
+ * processing calls return SDR_ERR_STATE from then on rather than run the members out of step.  Graph mode is not
+ * offered: a member captured through sdr_group_member makes the processing calls return SDR_ERR_STATE. */
+typedef struct sdr_group sdr_group;
+int sdr_group_create(const sdr_config *cfg, const int32_t *device_ids, int n_members, sdr_group **out);
+int sdr_group_destroy(sdr_group *group);
+int sdr_group_member(sdr_group *group, int band, sdr_bank **bank, int *local_band);
+int sdr_group_push_iq(sdr_group *group, int band, int sample_rate, const float *iq, size_t n_floats);
+int sdr_group_push_kiwi_snd(sdr_group *group, int band, int sample_rate, const uint8_t *payload, size_t n_bytes);
+int sdr_group_process_staged(sdr_group *group, int *n_frames_out);
+int sdr_group_process_staged_limit(sdr_group *group, int max_frames, int *n_frames_out);
+int sdr_group_process_device(sdr_group *group, const float *const *iq_dev, int n_frames);
+int sdr_group_sync(sdr_group *group);
+int sdr_group_set_peak_threshold(sdr_group *group, int band, float threshold);
+int sdr_group_set_signal_debounce(sdr_group *group, int band, int debounce);
+int sdr_group_set_edge_width(sdr_group *group, int edge_width);
+int sdr_group_set_find_peaks(sdr_group *group, int on);
+int sdr_group_enable_results(sdr_group *group, int on);
+int sdr_group_poll(sdr_group *group, sdr_results *results, int wait);
+int sdr_group_defer_listen(sdr_group *group, int on);
+int sdr_group_poll_peaks(sdr_group *group, sdr_results *results, int wait);
+int sdr_group_process_listen(sdr_group *group);
+int sdr_group_read_drop_counters(sdr_group *group, uint64_t *runes_dropped, uint64_t *edges_dropped);
+
 /* scope tap ---------------------------------------------------------------------------------- */
 /* The reference shows its inner workings through scope.Scope (scope/scope.go:33-37); NullScope is the default
  * and so is "no tap" here: the two reads below need a bank created with trace = 1 (that is scope.Active()).

@@ -92,6 +92,10 @@ SYMBOLS = (
     "sdr_last_batch_frames sdr_total_frames sdr_last_batch_chunks sdr_read_peaks sdr_read_cumulation sdr_read_text "
     "sdr_read_edges sdr_read_keying_bits sdr_read_frame_records sdr_read_trace sdr_read_spectrum "
     "sdr_read_decoder_state sdr_graph_batches sdr_graph_capture sdr_graph_launch sdr_graph_release sdr_scope_active sdr_scope_read_spectral sdr_scope_read_demod sdr_scope_read_decode sdr_enable_results sdr_poll sdr_defer_listen sdr_listen_pending sdr_poll_peaks sdr_attach_at sdr_process_listen sdr_results_pending sdr_read_drop_counters sdr_profile_enable sdr_profile_read sdr_profile_reset sdr_kernel_name sdr_audio_create "
+    "sdr_group_create sdr_group_destroy sdr_group_member sdr_group_push_iq sdr_group_push_kiwi_snd sdr_group_process_staged "
+    "sdr_group_process_staged_limit sdr_group_process_device sdr_group_sync sdr_group_set_peak_threshold "
+    "sdr_group_set_signal_debounce sdr_group_set_edge_width sdr_group_set_find_peaks sdr_group_enable_results sdr_group_poll "
+    "sdr_group_defer_listen sdr_group_poll_peaks sdr_group_process_listen sdr_group_read_drop_counters "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -188,6 +192,25 @@ def load():
     sig("sdr_audio_close", C.c_int, vp)
     sig("sdr_audio_read_text", C.c_int, vp, C.c_int, C.c_char_p, C.c_int, ip)
     sig("sdr_audio_read_trace", C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, ip)
+    sig("sdr_group_create", C.c_int, C.POINTER(Config), C.POINTER(C.c_int32), C.c_int, C.POINTER(vp))
+    sig("sdr_group_destroy", C.c_int, vp)
+    sig("sdr_group_member", C.c_int, vp, C.c_int, C.POINTER(vp), ip)
+    sig("sdr_group_push_iq", C.c_int, vp, C.c_int, C.c_int, fp, C.c_size_t)
+    sig("sdr_group_push_kiwi_snd", C.c_int, vp, C.c_int, C.c_int, C.c_char_p, C.c_size_t)
+    sig("sdr_group_process_staged", C.c_int, vp, ip)
+    sig("sdr_group_process_staged_limit", C.c_int, vp, C.c_int, ip)
+    sig("sdr_group_process_device", C.c_int, vp, C.POINTER(C.c_void_p), C.c_int)
+    sig("sdr_group_sync", C.c_int, vp)
+    sig("sdr_group_set_peak_threshold", C.c_int, vp, C.c_int, C.c_float)
+    sig("sdr_group_set_signal_debounce", C.c_int, vp, C.c_int, C.c_int)
+    sig("sdr_group_set_edge_width", C.c_int, vp, C.c_int)
+    sig("sdr_group_set_find_peaks", C.c_int, vp, C.c_int)
+    sig("sdr_group_enable_results", C.c_int, vp, C.c_int)
+    sig("sdr_group_poll", C.c_int, vp, C.POINTER(Results), C.c_int)
+    sig("sdr_group_defer_listen", C.c_int, vp, C.c_int)
+    sig("sdr_group_poll_peaks", C.c_int, vp, C.POINTER(Results), C.c_int)
+    sig("sdr_group_process_listen", C.c_int, vp)
+    sig("sdr_group_read_drop_counters", C.c_int, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
     _lib = L
     return L
 
@@ -199,6 +222,38 @@ def _check(rc: int):
 
 def _vp(a):
     return C.c_void_p(a.ctypes.data) if a is not None else None
+
+
+def _results_buffers(c: Config):
+    """Record arrays big enough for any batch of a bank (or group) of config `c`, and the sdr_results pointing at them."""
+    chunks = (c.max_batch_frames // CUMULATION_SIZE + 2) * c.n_bands
+    listeners = max(c.max_listeners * c.n_bands, 1)
+    bufs = {
+        "chunks": np.zeros(chunks, CHUNK_RESULT_DTYPE),
+        "peaks": np.zeros(chunks * c.max_peaks, PEAK_DTYPE),
+        "listeners": np.zeros(listeners, LISTENER_RESULT_DTYPE),
+        "edges": np.zeros(listeners * min(c.max_batch_frames, 8192), EDGE_DTYPE),
+        "runes": np.zeros(listeners * 2048, np.uint32),
+    }
+    rune_frames = np.zeros(listeners * 2048, np.uint32)
+    r = Results()
+    r.struct_size = C.sizeof(Results)
+    for k, a in bufs.items():
+        setattr(r, k, a.ctypes.data)
+        setattr(r, k + "_cap", len(a))
+    r.rune_frames = rune_frames.ctypes.data
+    return bufs, rune_frames, r
+
+
+def _results_dict(r: Results, bufs: dict, rune_frames: np.ndarray, copy: bool) -> dict:
+    out = {"batch_index": r.batch_index, "first_frame": r.first_frame, "n_frames": r.n_frames,
+           "runes_dropped": r.runes_dropped, "edges_dropped": r.edges_dropped}
+    for k, a in bufs.items():
+        v = a[:getattr(r, "n_" + k)]
+        out[k] = v.copy() if copy else v
+    v = rune_frames[:r.n_runes]
+    out["rune_frames"] = v.copy() if copy else v
+    return out
 
 
 class Bank:
@@ -221,9 +276,18 @@ class Bank:
         self._h = h
         self._L = L
 
+    @classmethod
+    def _view(cls, handle: C.c_void_p, cfg: Config) -> "Bank":
+        """A Bank over a bank owned by someone else (a Group member): close() leaves it alone."""
+        self = cls.__new__(cls)
+        self.cfg, self.n, self.n_bands = cfg, cfg.block_size, cfg.n_bands
+        self._h, self._L, self._owner = handle, load(), False
+        return self
+
     def close(self):
         if getattr(self, "_h", None):
-            self._L.sdr_destroy(self._h)
+            if getattr(self, "_owner", True):
+                self._L.sdr_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -446,24 +510,7 @@ class Bank:
     def enable_results(self, on: bool = True):
         _check(self._L.sdr_enable_results(self._h, int(on)))
         if on and not hasattr(self, "_res"):
-            c = self.cfg
-            chunks = (c.max_batch_frames // CUMULATION_SIZE + 2) * c.n_bands
-            listeners = max(c.max_listeners * c.n_bands, 1)
-            self._res_bufs = {
-                "chunks": np.zeros(chunks, CHUNK_RESULT_DTYPE),
-                "peaks": np.zeros(chunks * c.max_peaks, PEAK_DTYPE),
-                "listeners": np.zeros(listeners, LISTENER_RESULT_DTYPE),
-                "edges": np.zeros(listeners * min(c.max_batch_frames, 8192), EDGE_DTYPE),
-                "runes": np.zeros(listeners * 2048, np.uint32),
-            }
-            self._rune_frames = np.zeros(listeners * 2048, np.uint32)
-            r = Results()
-            r.struct_size = C.sizeof(Results)
-            for k, a in self._res_bufs.items():
-                setattr(r, k, a.ctypes.data)
-                setattr(r, k + "_cap", len(a))
-            r.rune_frames = self._rune_frames.ctypes.data
-            self._res = r
+            self._res_bufs, self._rune_frames, self._res = _results_buffers(self.cfg)
 
     def poll_peaks(self, wait: bool = True, copy: bool = True):
         """sdr_poll_peaks: chunks and peaks of the batch that waits for its listen half (it stays undelivered)."""
@@ -476,14 +523,7 @@ class Bank:
         if rc == ERR_WOULD_BLOCK:
             return None
         _check(rc)
-        out = {"batch_index": r.batch_index, "first_frame": r.first_frame, "n_frames": r.n_frames,
-               "runes_dropped": r.runes_dropped, "edges_dropped": r.edges_dropped}
-        for k, a in self._res_bufs.items():
-            v = a[:getattr(r, "n_" + k)]
-            out[k] = v.copy() if copy else v
-        v = self._rune_frames[:r.n_runes]
-        out["rune_frames"] = v.copy() if copy else v
-        return out
+        return _results_dict(r, self._res_bufs, self._rune_frames, copy)
 
     def poll_counts(self, wait: bool = False):
         """Like poll() but returns only the record counts (the bench's timed loop: no Python-side copies)."""
@@ -521,6 +561,126 @@ class Bank:
             _check(self._L.sdr_profile_read(self._h, k, C.byref(ms), C.byref(n)))
             out[name] = (ms.value, n.value)
         return out
+
+
+class Group:
+    """sdr_group: one bank per member device, driven as one bank of n_bands bands (band b on member b % n_members as
+    local band b // n_members).  Per-band calls go through member(band)."""
+
+    def __init__(self, device_ids, sample_rate: int, block_size: int, n_bands: int, edge_width: int | None = None,
+                 peak_threshold: float = 15.0, signal_debounce: int = 1, max_listeners: int = 30,
+                 max_batch_frames: int = 1024, max_peaks: int = 1024, find_peaks: bool = True, trace: bool = False):
+        L = load()
+        if edge_width is None:
+            edge_width = 70 * block_size // 512
+        self.cfg = Config(C.sizeof(Config), n_bands, sample_rate, block_size, edge_width, peak_threshold,
+                          signal_debounce, max_listeners, max_batch_frames, max_peaks, int(find_peaks), int(trace), 0, 0)
+        self.n, self.n_bands, self.n_members = block_size, n_bands, len(device_ids)
+        self.device_ids = list(device_ids)
+        ids = (C.c_int32 * max(len(device_ids), 1))(*device_ids)
+        h = C.c_void_p()
+        _check(L.sdr_group_create(C.byref(self.cfg), ids, len(device_ids), C.byref(h)))
+        self._h, self._L = h, L
+        self._members = {}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for m in self._members.values():  # (the views' banks go with the group)
+                m._h = None
+            self._L.sdr_group_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def member(self, band: int):
+        """(Bank view of the member that holds `band`, local band index)."""
+        bh, local = C.c_void_p(), C.c_int()
+        _check(self._L.sdr_group_member(self._h, band, C.byref(bh), C.byref(local)))
+        m = band % self.n_members
+        if m not in self._members:
+            c = Config.from_buffer_copy(self.cfg)
+            c.n_bands = (self.n_bands - m + self.n_members - 1) // self.n_members
+            c.device_id = self.device_ids[m]
+            self._members[m] = Bank._view(bh, c)
+        return self._members[m], local.value
+
+    # producer ---------------------------------------------------------------------------------
+    def push_iq(self, band: int, sample_rate: int, iq: np.ndarray) -> int:
+        iq = np.ascontiguousarray(iq, dtype=np.float32)
+        rc = self._L.sdr_group_push_iq(self._h, band, sample_rate, iq.ctypes.data_as(C.POINTER(C.c_float)), iq.size)
+        if rc not in (OK, ERR_BAD_RATE, ERR_BAD_SIZE, ERR_WOULD_DROP, ERR_STATE):
+            _check(rc)
+        return rc
+
+    def push_kiwi_snd(self, band: int, sample_rate: int, payload: bytes) -> int:
+        rc = self._L.sdr_group_push_kiwi_snd(self._h, band, sample_rate, payload, len(payload))
+        if rc not in (OK, ERR_BAD_RATE, ERR_BAD_SIZE, ERR_WOULD_DROP, ERR_STATE):
+            _check(rc)
+        return rc
+
+    def process_staged(self) -> int:
+        n = C.c_int()
+        _check(self._L.sdr_group_process_staged(self._h, C.byref(n)))
+        return n.value
+
+    def process_staged_limit(self, max_frames: int) -> int:
+        n = C.c_int()
+        _check(self._L.sdr_group_process_staged_limit(self._h, max_frames, C.byref(n)))
+        return n.value
+
+    def process_device(self, iq_dev_ptrs, n_frames: int):
+        """iq_dev_ptrs: one device pointer per member, each [local band][frame][2N] float32."""
+        arr = (C.c_void_p * len(iq_dev_ptrs))(*[C.c_void_p(int(p)) for p in iq_dev_ptrs])
+        _check(self._L.sdr_group_process_device(self._h, arr, n_frames))
+
+    def sync(self):
+        _check(self._L.sdr_group_sync(self._h))
+
+    # control ----------------------------------------------------------------------------------
+    def set_peak_threshold(self, band: int, t: float):
+        _check(self._L.sdr_group_set_peak_threshold(self._h, band, t))
+
+    def set_signal_debounce(self, band: int, d: int):
+        _check(self._L.sdr_group_set_signal_debounce(self._h, band, d))
+
+    def set_edge_width(self, e: int):
+        _check(self._L.sdr_group_set_edge_width(self._h, e))
+
+    def set_find_peaks(self, on: bool):
+        _check(self._L.sdr_group_set_find_peaks(self._h, int(on)))
+
+    # delivery ---------------------------------------------------------------------------------
+    def enable_results(self, on: bool = True):
+        _check(self._L.sdr_group_enable_results(self._h, int(on)))
+        if on and not hasattr(self, "_res"):
+            self._res_bufs, self._rune_frames, self._res = _results_buffers(self.cfg)
+
+    def poll(self, wait: bool = False, copy: bool = True, _entry=None):
+        """Oldest batch every member has finished, merged (as Bank.poll), or None."""
+        r = self._res
+        rc = (_entry or self._L.sdr_group_poll)(self._h, C.byref(r), int(wait))
+        if rc == ERR_WOULD_BLOCK:
+            return None
+        _check(rc)
+        return _results_dict(r, self._res_bufs, self._rune_frames, copy)
+
+    def poll_peaks(self, wait: bool = True, copy: bool = True):
+        return self.poll(wait, copy, _entry=self._L.sdr_group_poll_peaks)
+
+    def defer_listen(self, on: bool = True):
+        _check(self._L.sdr_group_defer_listen(self._h, int(on)))
+
+    def process_listen(self):
+        _check(self._L.sdr_group_process_listen(self._h))
+
+    def read_drop_counters(self):
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(self._L.sdr_group_read_drop_counters(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
 
 class AudioBank:

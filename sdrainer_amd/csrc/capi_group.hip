@@ -1,0 +1,399 @@
+// capi_group.hip — sdr_group (include/sdrainer_hip.h): one bank per member device, driven as one bank of n_bands bands
+// from one host process - the single-process counterpart of sharding.ShardedBank, reachable from a C or Go host.
+// Built on the public bank ABI only: every member is an ordinary sdr_bank, and there is no device work of the group's
+// own.  Routing, the frame count of a staged call and the merge / park logic of delivery are host/group.h (plain C++,
+// exercised without a GPU by tests/host/test_group.cpp); this file is the C ABI in front of it: the checks that keep the
+// members in step, the fan-out to the members, and the caller's current device.
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <vector>
+
+#include "../../include/sdrainer_hip.h"
+#include "host/group.h"
+
+namespace sdr {
+int set_error(int code, const char *msg);  // capi_bank.hip: the calling thread's sdr_last_error()
+}  // namespace sdr
+
+namespace {
+
+struct BankSource final : host::GroupSource {
+    std::vector<sdr_bank *> *banks;
+    explicit BankSource(std::vector<sdr_bank *> *b) : banks(b) {}
+    int poll(int m, sdr_results *r, bool wait) override { return sdr_poll((*banks)[(size_t)m], r, wait ? 1 : 0); }
+    int poll_peaks(int m, sdr_results *r, bool wait) override { return sdr_poll_peaks((*banks)[(size_t)m], r, wait ? 1 : 0); }
+    int report(int code, const char *msg) override { return sdr::set_error(code, msg); }
+};
+
+// Every group call leaves the caller's current HIP device as it found it (the members' calls select theirs).
+struct KeepDevice {
+    int dev = -1;
+    KeepDevice()
+    {
+        if (hipGetDevice(&dev) != hipSuccess)
+            dev = -1;
+    }
+    ~KeepDevice()
+    {
+        if (dev >= 0)
+            (void)hipSetDevice(dev);
+    }
+};
+
+// A 16-byte aligned address for a zero-frame sdr_process_device: the bank checks its state (failed, graph captured,
+// listen half pending) and returns before it reads or launches anything.
+alignas(16) float g_probe[4];
+
+}  // namespace
+
+struct sdr_group {
+    sdr_config cfg{};
+    host::GroupRouting rt;
+    std::vector<sdr_bank *> banks;
+    std::unique_ptr<BankSource> src;
+    std::unique_ptr<host::GroupDelivery> delivery;
+    bool failed = false;  // producer-owned: a member failed after another had run, the members are out of step
+};
+
+namespace {
+
+int fail(int code, const char *msg) { return sdr::set_error(code, msg); }
+
+int route(sdr_group *g, int band, sdr_bank **bank, int *local)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    if (band < 0 || band >= g->rt.n_bands)
+        return fail(SDR_ERR_BAD_ARG, "band out of range");
+    *bank = g->banks[(size_t)g->rt.member_of(band)];
+    *local = g->rt.local_of(band);
+    return SDR_OK;
+}
+
+// Before any member is launched: the group has not failed and every member may process a new batch.
+int check_members(sdr_group *g)
+{
+    if (g->failed)
+        return fail(SDR_ERR_STATE, "an earlier group call left the members out of step; destroy the group");
+    for (sdr_bank *b : g->banks) {
+        const int rc = sdr_process_device(b, g_probe, 0);
+        if (rc)
+            return rc;  // (SDR_ERR_STATE: graph captured, listen half pending, or the member failed on its own)
+    }
+    return SDR_OK;
+}
+
+// A member call failed: once another member has run this batch, or on a HIP failure, the members are out of step.
+int member_failed(sdr_group *g, int rc, int member)
+{
+    if (rc == SDR_ERR_HIP || member > 0)
+        g->failed = true;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+int sdr_group_create(const sdr_config *cfg, const int32_t *device_ids, int n_members, sdr_group **out)
+{
+    if (!cfg || !device_ids || !out)
+        return fail(SDR_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    if (cfg->struct_size != (int32_t)sizeof(sdr_config))
+        return fail(SDR_ERR_BAD_ARG, "sdr_config.struct_size mismatch (ABI)");
+    host::GroupRouting rt{cfg->n_bands, n_members};
+    if (!rt.valid())
+        return fail(SDR_ERR_BAD_ARG, "a group needs at least one member and at least one band per member");
+    KeepDevice keep;
+    std::unique_ptr<sdr_group> g(new sdr_group);
+    g->cfg = *cfg;
+    g->rt = rt;
+    for (int m = 0; m < n_members; m++) {
+        sdr_config mc = *cfg;
+        mc.n_bands = rt.bands_of(m);
+        mc.device_id = device_ids[m];
+        sdr_bank *b = nullptr;
+        const int rc = sdr_create(&mc, &b);
+        if (rc) {
+            for (sdr_bank *made : g->banks)
+                sdr_destroy(made);
+            return rc;
+        }
+        g->banks.push_back(b);
+    }
+    g->src.reset(new BankSource(&g->banks));
+    g->delivery.reset(new host::GroupDelivery(g->src.get(), rt));
+    *out = g.release();
+    return SDR_OK;
+}
+
+int sdr_group_destroy(sdr_group *g)
+{
+    if (!g)
+        return SDR_OK;
+    KeepDevice keep;
+    int rc = SDR_OK;
+    for (sdr_bank *b : g->banks) {
+        const int r = sdr_destroy(b);
+        rc = rc ? rc : r;
+    }
+    delete g;
+    return rc;
+}
+
+int sdr_group_member(sdr_group *g, int band, sdr_bank **bank, int *local_band)
+{
+    if (!bank || !local_band)
+        return fail(SDR_ERR_BAD_ARG, "null argument");
+    return route(g, band, bank, local_band);
+}
+
+int sdr_group_push_iq(sdr_group *g, int band, int sample_rate, const float *iq, size_t n_floats)
+{
+    sdr_bank *b = nullptr;
+    int local = 0;
+    int rc = route(g, band, &b, &local);
+    if (rc)
+        return rc;
+    KeepDevice keep;
+    return sdr_push_iq(b, local, sample_rate, iq, n_floats);
+}
+
+int sdr_group_push_kiwi_snd(sdr_group *g, int band, int sample_rate, const uint8_t *payload, size_t n_bytes)
+{
+    sdr_bank *b = nullptr;
+    int local = 0;
+    int rc = route(g, band, &b, &local);
+    if (rc)
+        return rc;
+    KeepDevice keep;
+    return sdr_push_kiwi_snd(b, local, sample_rate, payload, n_bytes);
+}
+
+int sdr_group_process_staged(sdr_group *g, int *n_frames_out)
+{
+    return sdr_group_process_staged_limit(g, g ? g->cfg.max_batch_frames : 0, n_frames_out);
+}
+
+int sdr_group_process_staged_limit(sdr_group *g, int max_frames, int *n_frames_out)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    if (n_frames_out)
+        *n_frames_out = 0;
+    KeepDevice keep;
+    int rc = check_members(g);
+    if (rc)
+        return rc;
+    std::vector<int> staged((size_t)g->rt.n_bands);
+    for (int band = 0; band < g->rt.n_bands; band++)
+        staged[(size_t)band] = sdr_staged_frames(g->banks[(size_t)g->rt.member_of(band)], g->rt.local_of(band));
+    const int n = host::group_frames(staged, max_frames, g->cfg.max_batch_frames);
+    if (n_frames_out)
+        *n_frames_out = n;
+    if (n == 0)
+        return SDR_OK;
+    for (int m = 0; m < g->rt.n_members; m++) {
+        int done = 0;
+        rc = sdr_process_staged_limit(g->banks[(size_t)m], n, &done);
+        if (rc)
+            return member_failed(g, rc, m);
+        if (done != n) {
+            g->failed = true;
+            return fail(SDR_ERR_STATE, "a member consumed another frame count than the group (out of step)");
+        }
+    }
+    return SDR_OK;
+}
+
+int sdr_group_process_device(sdr_group *g, const float *const *iq_dev, int n_frames)
+{
+    if (!g || !iq_dev)
+        return fail(SDR_ERR_BAD_ARG, "null argument");
+    for (int m = 0; m < g->rt.n_members; m++) {
+        if (!iq_dev[m])
+            return fail(SDR_ERR_BAD_ARG, "null iq_dev of a member");
+        if (reinterpret_cast<uintptr_t>(iq_dev[m]) & 15)
+            return fail(SDR_ERR_BAD_ARG, "iq_dev must be 16-byte aligned (frames are copied to LDS 16 bytes per lane)");
+    }
+    if (n_frames > g->cfg.max_batch_frames)
+        return fail(SDR_ERR_BAD_ARG, "n_frames exceeds max_batch_frames");
+    KeepDevice keep;
+    int rc = check_members(g);
+    if (rc)
+        return rc;
+    if (n_frames <= 0)
+        return SDR_OK;
+    // (sdr_process_device only enqueues: every member is launched before anything is waited for)
+    for (int m = 0; m < g->rt.n_members; m++)
+        if ((rc = sdr_process_device(g->banks[(size_t)m], iq_dev[m], n_frames)))
+            return member_failed(g, rc, m);
+    return SDR_OK;
+}
+
+int sdr_group_sync(sdr_group *g)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    KeepDevice keep;
+    for (sdr_bank *b : g->banks) {
+        const int rc = sdr_sync(b);
+        if (rc)
+            return rc;
+    }
+    return SDR_OK;
+}
+
+// Collective setters.  A bank applies a setter at its next process call; the group's next process call runs every
+// member, so every band changes at the same frame.  The members share one geometry: what the first accepts, all accept.
+int sdr_group_set_peak_threshold(sdr_group *g, int band, float threshold)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    if (band < -1 || band >= g->rt.n_bands)
+        return fail(SDR_ERR_BAD_ARG, "band out of range (-1: every band)");
+    KeepDevice keep;
+    for (int b = band < 0 ? 0 : band; b < (band < 0 ? g->rt.n_bands : band + 1); b++) {
+        const int rc = sdr_set_peak_threshold(g->banks[(size_t)g->rt.member_of(b)], g->rt.local_of(b), threshold);
+        if (rc)
+            return rc;
+    }
+    return SDR_OK;
+}
+
+int sdr_group_set_signal_debounce(sdr_group *g, int band, int debounce)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    if (band < -1 || band >= g->rt.n_bands)
+        return fail(SDR_ERR_BAD_ARG, "band out of range (-1: every band)");
+    KeepDevice keep;
+    for (int b = band < 0 ? 0 : band; b < (band < 0 ? g->rt.n_bands : band + 1); b++) {
+        const int rc = sdr_set_signal_debounce(g->banks[(size_t)g->rt.member_of(b)], g->rt.local_of(b), debounce);
+        if (rc)
+            return rc;
+    }
+    return SDR_OK;
+}
+
+int sdr_group_set_edge_width(sdr_group *g, int edge_width)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    KeepDevice keep;
+    for (sdr_bank *b : g->banks) {
+        const int rc = sdr_set_edge_width(b, edge_width);
+        if (rc)
+            return rc;
+    }
+    return SDR_OK;
+}
+
+int sdr_group_set_find_peaks(sdr_group *g, int on)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    KeepDevice keep;
+    for (sdr_bank *b : g->banks) {
+        const int rc = sdr_set_find_peaks(b, on);
+        if (rc)
+            return rc;
+    }
+    return SDR_OK;
+}
+
+int sdr_group_enable_results(sdr_group *g, int on)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    KeepDevice keep;
+    for (sdr_bank *b : g->banks) {
+        const int rc = sdr_enable_results(b, on);
+        if (rc)
+            return rc;
+    }
+    g->delivery->reset(on != 0);  // (undelivered batches are discarded with the mode, as every member discards its own)
+    return SDR_OK;
+}
+
+int sdr_group_poll(sdr_group *g, sdr_results *r, int wait)
+{
+    if (!g || !r)
+        return fail(SDR_ERR_BAD_ARG, "null argument");
+    if (r->struct_size != (int32_t)sizeof(sdr_results))
+        return fail(SDR_ERR_BAD_ARG, "sdr_results.struct_size mismatch (ABI)");
+    KeepDevice keep;
+    return g->delivery->poll(r, wait != 0);
+}
+
+int sdr_group_defer_listen(sdr_group *g, int on)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    for (sdr_bank *b : g->banks)
+        if (sdr_listen_pending(b))
+            return fail(SDR_ERR_STATE, "a batch waits for its listen half (sdr_group_process_listen)");
+    if (on && !g->delivery->on())
+        return fail(SDR_ERR_STATE, "deferred listening needs bulk delivery (sdr_group_enable_results)");
+    for (sdr_bank *b : g->banks) {
+        const int rc = sdr_defer_listen(b, on);
+        if (rc)
+            return rc;
+    }
+    return SDR_OK;
+}
+
+int sdr_group_poll_peaks(sdr_group *g, sdr_results *r, int wait)
+{
+    if (!g || !r)
+        return fail(SDR_ERR_BAD_ARG, "null argument");
+    if (r->struct_size != (int32_t)sizeof(sdr_results))
+        return fail(SDR_ERR_BAD_ARG, "sdr_results.struct_size mismatch (ABI)");
+    KeepDevice keep;
+    return g->delivery->poll_peaks(r, wait != 0);
+}
+
+int sdr_group_process_listen(sdr_group *g)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    if (g->failed)
+        return fail(SDR_ERR_STATE, "an earlier group call left the members out of step; destroy the group");
+    for (sdr_bank *b : g->banks)
+        if (!sdr_listen_pending(b))
+            return fail(SDR_ERR_STATE, "no group batch waits for its listen half");
+    KeepDevice keep;
+    for (int m = 0; m < g->rt.n_members; m++) {
+        const int rc = sdr_process_listen(g->banks[(size_t)m]);
+        if (rc)
+            return member_failed(g, rc, m);
+    }
+    return SDR_OK;
+}
+
+int sdr_group_read_drop_counters(sdr_group *g, uint64_t *runes_dropped, uint64_t *edges_dropped)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    KeepDevice keep;
+    uint64_t runes = 0, edges = 0;
+    for (sdr_bank *b : g->banks) {
+        uint64_t r = 0, e = 0;
+        const int rc = sdr_read_drop_counters(b, &r, &e);
+        if (rc)
+            return rc;
+        runes += r;
+        edges += e;
+    }
+    if (runes_dropped)
+        *runes_dropped = runes;
+    if (edges_dropped)
+        *edges_dropped = edges;
+    return SDR_OK;
+}
+
+#pragma GCC visibility pop
+}  // extern "C"
