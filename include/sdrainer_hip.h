@@ -26,6 +26,7 @@
  *   sdr_read_edges / _trace         what cw.SpectralDemodulator.Tick hands to Decoder.Tick  cw/spectral.go:48-54
  *   sdr_read_frame_records          locals of Receiver.run (noise floor, thresholds)  rx/receiver.go:381-385
  *   sdr_push_kiwi_snd               decodeIQMessage + kiwi.Process.IQData       kiwi/client.go:284-308, kiwi/kiwi.go:94-105
+ *   sdr_push_iq_sc16, *_sc16        Receiver.IQData fed by decodeIQBytes' complex int16 samples  kiwi/client.go:298-308
  *   sdr_audio_*                     cw.AudioDemodulator (Goertzel audio path)   cw/audio.go:37-211
  *   sdr_enable_results / sdr_poll   the consumer side in bulk: what Receiver.run hands to its listeners'
  *                                   io.Writer (rx/receiver.go:123, ChannelWriter :508-539) and to the
@@ -169,6 +170,15 @@ int sdr_process_staged_limit(sdr_bank *bank, int max_frames, int *n_frames_out);
  * float32 (band stride = n_frames*2*block_size floats), 16-byte aligned (SDR_ERR_BAD_ARG otherwise).
  * Asynchronous on the bank's stream. */
 int sdr_process_device(sdr_bank *bank, const float *iq_dev, int n_frames);
+/* Complex int16 input ("sc16": int16 I, then int16 Q, little-endian), the format of IQ sources and capture hardware.  A
+ * sample's value is float32(x) / 32767, correctly rounded (kiwi/client.go:298-308): every result is bit-identical to the
+ * float32 calls fed with those values.  n_values counts int16 values (2 per sample); statuses are the float32 calls'.
+ *   sdr_push_iq_sc16: as sdr_push_iq; the int16 values are staged and uploaded as they are (half the bytes) and converted
+ *     on the device.  A band's batch must not mix it with sdr_push_iq or sdr_push_kiwi_snd (SDR_ERR_STATE).
+ *   sdr_process_device_sc16: as sdr_process_device, layout [band][frame][block_size][2] int16, 16-byte aligned; the FFT
+ *     kernels read the int16 values themselves (no float32 copy). */
+int sdr_push_iq_sc16(sdr_bank *bank, int band, int sample_rate, const int16_t *iq, size_t n_values);
+int sdr_process_device_sc16(sdr_bank *bank, const int16_t *iq_dev, int n_frames);
 /* Blocks until everything queued on the bank's stream has finished. */
 int sdr_sync(sdr_bank *bank);
 
@@ -302,6 +312,10 @@ int sdr_graph_batches(sdr_bank *bank);
 int sdr_graph_capture(sdr_bank *bank, int n_frames);
 /* iq_dev: sdr_graph_batches() device pointers, one batch each, layout and alignment as sdr_process_device. */
 int sdr_graph_launch(sdr_bank *bank, const float *const *iq_dev);
+/* The same for sc16 input (sdr_process_device_sc16's layout).  A graph runs the format it was captured for: launching it
+ * with the other call returns SDR_ERR_STATE. */
+int sdr_graph_capture_sc16(sdr_bank *bank, int n_frames);
+int sdr_graph_launch_sc16(sdr_bank *bank, const int16_t *const *iq_dev);
 /* Back to sdr_process_*: drains the pipeline, moves what was not polled yet to the host-side queue (sdr_poll keeps
  * delivering it, oldest first) and frees the replays' buffer sets; what the last replay's last batch left on the device
  * goes with them - read it (sdr_read_*) before the release. */
@@ -340,6 +354,9 @@ int sdr_group_push_kiwi_snd(sdr_group *group, int band, int sample_rate, const u
 int sdr_group_process_staged(sdr_group *group, int *n_frames_out);
 int sdr_group_process_staged_limit(sdr_group *group, int max_frames, int *n_frames_out);
 int sdr_group_process_device(sdr_group *group, const float *const *iq_dev, int n_frames);
+/* sc16 input (sdr_push_iq_sc16 / sdr_process_device_sc16), routed exactly like the float32 calls. */
+int sdr_group_push_iq_sc16(sdr_group *group, int band, int sample_rate, const int16_t *iq, size_t n_values);
+int sdr_group_process_device_sc16(sdr_group *group, const int16_t *const *iq_dev, int n_frames);
 int sdr_group_sync(sdr_group *group);
 int sdr_group_set_peak_threshold(sdr_group *group, int band, float threshold);
 int sdr_group_set_signal_debounce(sdr_group *group, int band, int debounce);

@@ -96,6 +96,8 @@ SYMBOLS = (
     "sdr_group_process_staged_limit sdr_group_process_device sdr_group_sync sdr_group_set_peak_threshold "
     "sdr_group_set_signal_debounce sdr_group_set_edge_width sdr_group_set_find_peaks sdr_group_enable_results sdr_group_poll "
     "sdr_group_defer_listen sdr_group_poll_peaks sdr_group_process_listen sdr_group_read_drop_counters "
+    "sdr_push_iq_sc16 sdr_process_device_sc16 sdr_graph_capture_sc16 sdr_graph_launch_sc16 "
+    "sdr_group_push_iq_sc16 sdr_group_process_device_sc16 "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -139,6 +141,8 @@ def load():
     sig("sdr_process_staged", C.c_int, vp, ip)
     sig("sdr_process_staged_limit", C.c_int, vp, C.c_int, ip)
     sig("sdr_process_device", C.c_int, vp, vp, C.c_int)
+    sig("sdr_push_iq_sc16", C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_int16), C.c_size_t)
+    sig("sdr_process_device_sc16", C.c_int, vp, vp, C.c_int)
     sig("sdr_sync", C.c_int, vp)
     sig("sdr_attach", C.c_int, vp, C.c_int, C.c_int, ip)
     sig("sdr_detach", C.c_int, vp, C.c_int, C.c_int)
@@ -164,6 +168,8 @@ def load():
     sig("sdr_graph_batches", C.c_int, vp)
     sig("sdr_graph_capture", C.c_int, vp, C.c_int)
     sig("sdr_graph_launch", C.c_int, vp, C.POINTER(C.c_void_p))
+    sig("sdr_graph_capture_sc16", C.c_int, vp, C.c_int)
+    sig("sdr_graph_launch_sc16", C.c_int, vp, C.POINTER(C.c_void_p))
     sig("sdr_graph_release", C.c_int, vp)
     sig("sdr_scope_active", C.c_int, vp)
     sig("sdr_scope_read_spectral", C.c_int, vp, C.c_int, C.c_int, C.POINTER(ScopeSpectralFrame), C.POINTER(C.c_double), C.c_int)
@@ -200,6 +206,8 @@ def load():
     sig("sdr_group_process_staged", C.c_int, vp, ip)
     sig("sdr_group_process_staged_limit", C.c_int, vp, C.c_int, ip)
     sig("sdr_group_process_device", C.c_int, vp, C.POINTER(C.c_void_p), C.c_int)
+    sig("sdr_group_push_iq_sc16", C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_int16), C.c_size_t)
+    sig("sdr_group_process_device_sc16", C.c_int, vp, C.POINTER(C.c_void_p), C.c_int)
     sig("sdr_group_sync", C.c_int, vp)
     sig("sdr_group_set_peak_threshold", C.c_int, vp, C.c_int, C.c_float)
     sig("sdr_group_set_signal_debounce", C.c_int, vp, C.c_int, C.c_int)
@@ -308,6 +316,14 @@ class Bank:
             _check(rc)
         return rc
 
+    def push_iq_sc16(self, band: int, sample_rate: int, iq: np.ndarray) -> int:
+        """iq: int16 I,Q pairs (sc16); value = float32(x) / 32767.  Status code as push_iq."""
+        iq = np.ascontiguousarray(iq, dtype=np.int16)
+        rc = self._L.sdr_push_iq_sc16(self._h, band, sample_rate, iq.ctypes.data_as(C.POINTER(C.c_int16)), iq.size)
+        if rc not in (OK, ERR_BAD_RATE, ERR_BAD_SIZE, ERR_WOULD_DROP, ERR_STATE):
+            _check(rc)
+        return rc
+
     def push_kiwi_snd(self, band: int, sample_rate: int, payload: bytes) -> int:
         """payload: body of one KiwiSDR SND message (17-byte header + big-endian int16 IQ)."""
         rc = self._L.sdr_push_kiwi_snd(self._h, band, sample_rate, payload, len(payload))
@@ -330,6 +346,10 @@ class Bank:
 
     def process_device(self, iq_dev_ptr: int, n_frames: int):
         _check(self._L.sdr_process_device(self._h, C.c_void_p(iq_dev_ptr), n_frames))
+
+    def process_device_sc16(self, iq_dev_ptr: int, n_frames: int):
+        """iq_dev_ptr: device memory [band][frame][2N] int16 (sc16), 16-byte aligned."""
+        _check(self._L.sdr_process_device_sc16(self._h, C.c_void_p(iq_dev_ptr), n_frames))
 
     def process_host(self, iq: np.ndarray) -> int:
         """iq: float32 [n_bands, n_frames, 2N] (or [n_frames, 2N] for one band) from host memory."""
@@ -471,6 +491,14 @@ class Bank:
         arr = (C.c_void_p * len(iq_dev_ptrs))(*[C.c_void_p(int(p)) for p in iq_dev_ptrs])
         assert len(iq_dev_ptrs) == self.graph_batches
         _check(self._L.sdr_graph_launch(self._h, arr))
+
+    def graph_capture_sc16(self, n_frames: int):
+        _check(self._L.sdr_graph_capture_sc16(self._h, n_frames))
+
+    def graph_launch_sc16(self, iq_dev_ptrs):
+        arr = (C.c_void_p * len(iq_dev_ptrs))(*[C.c_void_p(int(p)) for p in iq_dev_ptrs])
+        assert len(iq_dev_ptrs) == self.graph_batches
+        _check(self._L.sdr_graph_launch_sc16(self._h, arr))
 
     def graph_release(self):
         _check(self._L.sdr_graph_release(self._h))
@@ -616,6 +644,13 @@ class Group:
             _check(rc)
         return rc
 
+    def push_iq_sc16(self, band: int, sample_rate: int, iq: np.ndarray) -> int:
+        iq = np.ascontiguousarray(iq, dtype=np.int16)
+        rc = self._L.sdr_group_push_iq_sc16(self._h, band, sample_rate, iq.ctypes.data_as(C.POINTER(C.c_int16)), iq.size)
+        if rc not in (OK, ERR_BAD_RATE, ERR_BAD_SIZE, ERR_WOULD_DROP, ERR_STATE):
+            _check(rc)
+        return rc
+
     def push_kiwi_snd(self, band: int, sample_rate: int, payload: bytes) -> int:
         rc = self._L.sdr_group_push_kiwi_snd(self._h, band, sample_rate, payload, len(payload))
         if rc not in (OK, ERR_BAD_RATE, ERR_BAD_SIZE, ERR_WOULD_DROP, ERR_STATE):
@@ -636,6 +671,11 @@ class Group:
         """iq_dev_ptrs: one device pointer per member, each [local band][frame][2N] float32."""
         arr = (C.c_void_p * len(iq_dev_ptrs))(*[C.c_void_p(int(p)) for p in iq_dev_ptrs])
         _check(self._L.sdr_group_process_device(self._h, arr, n_frames))
+
+    def process_device_sc16(self, iq_dev_ptrs, n_frames: int):
+        """iq_dev_ptrs: one device pointer per member, each [local band][frame][2N] int16 (sc16)."""
+        arr = (C.c_void_p * len(iq_dev_ptrs))(*[C.c_void_p(int(p)) for p in iq_dev_ptrs])
+        _check(self._L.sdr_group_process_device_sc16(self._h, arr, n_frames))
 
     def sync(self):
         _check(self._L.sdr_group_sync(self._h))

@@ -206,6 +206,7 @@ struct sdr_bank {
     int64_t graph_replays = 0;  // launches since the capture
     bool graph_ready = false;
     int graph_frames = 0, graph_slots = 0;
+    sdr::InFormat graph_fmt = sdr::InFormat::F32;  // the input format the graphs were captured for (sdr_graph_capture / _sc16)
     uint64_t attach_gen = 0, graph_attach_gen = 0;  // sdr_attach / sdr_detach calls so far; as of the capture
     // what the captured graphs have baked in besides the listeners: the packing kernels exist only if results were on, the
     // refinement / peak-scan nodes only if find_peaks was
@@ -236,9 +237,9 @@ struct sdr_bank {
     // nothing on this path waits for the device unless the ring has wrapped around onto work still in flight.
     struct Staging {
         float *h_f32 = nullptr;        // pinned [band][max_batch][2N] float32 frames
-        uint8_t *h_raw = nullptr;      // pinned [band][max_batch][2N] big-endian int16 (KiwiSDR payloads), on demand
+        uint8_t *h_raw = nullptr;      // pinned [band][max_batch][2N] int16: big-endian (KiwiSDR payloads) or sc16, on demand
         DevBuf<float> d_f32;           // [band][n][2N]: what the FFT kernel reads
-        DevBuf<uint8_t> d_raw;         // raw payload bytes, unpacked on the device (k_unpack.hip)
+        DevBuf<uint8_t> d_raw;         // raw int16 bytes, unpacked on the device (k_unpack.hip)
         hipEvent_t uploaded = nullptr;  // the upload has left the pinned buffers (they may be overwritten)
         hipEvent_t consumed = nullptr;  // the FFT has read d_f32 (it may be overwritten)
     };
@@ -247,7 +248,7 @@ struct sdr_bank {
     int stage_cur = 0;  // the set sdr_push_* currently fills
     hipStream_t copy_stream = nullptr;
     std::vector<int> staged;
-    std::vector<int> staged_kind;  // per band: 0 nothing staged, 1 float32 frames, 2 int16be frames
+    std::vector<int> staged_kind;  // per band: 0 nothing staged, 1 float32 frames, 2 int16be frames, 3 sc16 frames
 
     bool profiling = false;
     double prof_ms[sdr::K_COUNT] = {};
@@ -299,9 +300,10 @@ int check_listener(sdr_bank *b, int band, int lid);
 hipError_t alloc_set(sdr_bank *b, BatchSet &S);
 // (capi_process.hip)
 int flush_late_attached(sdr_bank *b);
-int process_device_body(sdr_bank *b, const float *iq_dev, int n_frames, int in_stride, int capture_k = -1, int capture_stage = -1,
-                        int parts = PART_ALL);
-int process_device_impl(sdr_bank *b, const float *iq_dev, int n_frames, int in_stride);
+// iq_dev: float32 frames, or sc16 frames with fmt = SC16 (only the FFT reads the input)
+int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_stride, int capture_k = -1, int capture_stage = -1,
+                        int parts = PART_ALL, sdr::InFormat fmt = sdr::InFormat::F32);
+int process_device_impl(sdr_bank *b, const void *iq_dev, int n_frames, int in_stride, sdr::InFormat fmt = sdr::InFormat::F32);
 // (capi_results.hip)
 sdr::ResultsLayout make_results_layout(const sdr_bank *b);
 int results_attach_set(sdr_bank *b, int set_idx);  // the set's pinned block and events, once bulk delivery is on

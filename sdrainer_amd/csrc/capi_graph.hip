@@ -115,7 +115,8 @@ int sdr_graph_release(sdr_bank *b)
     return graph_release(b, false);
 }
 
-int sdr_graph_capture(sdr_bank *b, int n_frames)
+namespace {
+static int graph_capture(sdr_bank *b, int n_frames, sdr::InFormat fmt)
 {
     if (!b)
         return fail(SDR_ERR_BAD_ARG, "null bank");
@@ -180,7 +181,7 @@ int sdr_graph_capture(sdr_bank *b, int n_frames)
                 break;
             }
             for (int k = 0; k < RING && rc == SDR_OK; k++)
-                rc = process_device_body(b, nullptr, n_frames, n_frames, ph * RING + k, st);
+                rc = process_device_body(b, nullptr, n_frames, n_frames, ph * RING + k, st, PART_ALL, fmt);
             e = hipStreamEndCapture(cs, &b->graph[ph][st]);
             if ((e != hipSuccess || !b->graph[ph][st]) && rc == SDR_OK)
                 rc = fail(SDR_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -227,6 +228,7 @@ int sdr_graph_capture(sdr_bank *b, int n_frames)
     b->results->graph_begin(b->batch_index);
     b->graph_replays = 0;
     b->graph_frames = n_frames;
+    b->graph_fmt = fmt;
     b->graph_slots = max_slots;
     b->graph_attach_gen = b->attach_gen;
     b->graph_results_on = b->results_on;
@@ -234,12 +236,16 @@ int sdr_graph_capture(sdr_bank *b, int n_frames)
     return SDR_OK;
 }
 
-int sdr_graph_launch(sdr_bank *b, const float *const *iq_dev)
+// iq_dev: RING pointers to frames of format fmt
+static int graph_launch(sdr_bank *b, const void *const *iq_dev, sdr::InFormat fmt)
 {
     if (!b || !iq_dev)
         return fail(SDR_ERR_BAD_ARG, "null argument");
     if (!b->graph_ready)
         return fail(SDR_ERR_STATE, "no graph captured (sdr_graph_capture)");
+    if (fmt != b->graph_fmt)
+        return fail(SDR_ERR_STATE, fmt == sdr::InFormat::SC16 ? "the graph was captured for float32 input (sdr_graph_launch)"
+                                                               : "the graph was captured for sc16 input (sdr_graph_launch_sc16)");
     if (b->failed)
         return fail(SDR_ERR_STATE, "an earlier process call failed half way; destroy the bank");
     int max_slots = 0;
@@ -275,7 +281,10 @@ int sdr_graph_launch(sdr_bank *b, const float *const *iq_dev)
         if (!iq_dev[k] || (reinterpret_cast<uintptr_t>(iq_dev[k]) & 15))
             return fail(SDR_ERR_BAD_ARG, "every input pointer must be non-null and 16-byte aligned");
         cursor[k] = sdr::BatchCursor{};
-        cursor[k].iq = iq_dev[k];
+        if (fmt == sdr::InFormat::SC16)
+            cursor[k].iq_sc16 = static_cast<const int16_t *>(iq_dev[k]);
+        else
+            cursor[k].iq = static_cast<const float *>(iq_dev[k]);
         cursor[k].frame_base = (uint32_t)total;
         cursor[k].count0 = count;
         cursor[k].carry_in = carry;
@@ -383,6 +392,20 @@ int sdr_graph_launch(sdr_bank *b, const float *const *iq_dev)
     b->total_frames = total;
     b->graph_replays++;
     return SDR_OK;
+}
+}  // namespace
+
+int sdr_graph_capture(sdr_bank *b, int n_frames) { return graph_capture(b, n_frames, sdr::InFormat::F32); }
+int sdr_graph_capture_sc16(sdr_bank *b, int n_frames) { return graph_capture(b, n_frames, sdr::InFormat::SC16); }
+
+int sdr_graph_launch(sdr_bank *b, const float *const *iq_dev)
+{
+    return graph_launch(b, reinterpret_cast<const void *const *>(iq_dev), sdr::InFormat::F32);
+}
+
+int sdr_graph_launch_sc16(sdr_bank *b, const int16_t *const *iq_dev)
+{
+    return graph_launch(b, reinterpret_cast<const void *const *>(iq_dev), sdr::InFormat::SC16);
 }
 
 #pragma GCC visibility pop

@@ -162,6 +162,17 @@ int sdr_group_push_iq(sdr_group *g, int band, int sample_rate, const float *iq, 
     return sdr_push_iq(b, local, sample_rate, iq, n_floats);
 }
 
+int sdr_group_push_iq_sc16(sdr_group *g, int band, int sample_rate, const int16_t *iq, size_t n_values)
+{
+    sdr_bank *b = nullptr;
+    int local = 0;
+    int rc = route(g, band, &b, &local);
+    if (rc)
+        return rc;
+    KeepDevice keep;
+    return sdr_push_iq_sc16(b, local, sample_rate, iq, n_values);
+}
+
 int sdr_group_push_kiwi_snd(sdr_group *g, int band, int sample_rate, const uint8_t *payload, size_t n_bytes)
 {
     sdr_bank *b = nullptr;
@@ -209,7 +220,9 @@ int sdr_group_process_staged_limit(sdr_group *g, int max_frames, int *n_frames_o
     return SDR_OK;
 }
 
-int sdr_group_process_device(sdr_group *g, const float *const *iq_dev, int n_frames)
+namespace {
+// iq_dev: one pointer per member, float32 frames or (sc16) complex int16 frames
+static int group_process_device(sdr_group *g, const void *const *iq_dev, int n_frames, bool sc16)
 {
     if (!g || !iq_dev)
         return fail(SDR_ERR_BAD_ARG, "null argument");
@@ -228,10 +241,25 @@ int sdr_group_process_device(sdr_group *g, const float *const *iq_dev, int n_fra
     if (n_frames <= 0)
         return SDR_OK;
     // (sdr_process_device only enqueues: every member is launched before anything is waited for)
-    for (int m = 0; m < g->rt.n_members; m++)
-        if ((rc = sdr_process_device(g->banks[(size_t)m], iq_dev[m], n_frames)))
+    for (int m = 0; m < g->rt.n_members; m++) {
+        sdr_bank *b = g->banks[(size_t)m];
+        rc = sc16 ? sdr_process_device_sc16(b, static_cast<const int16_t *>(iq_dev[m]), n_frames)
+                  : sdr_process_device(b, static_cast<const float *>(iq_dev[m]), n_frames);
+        if (rc)
             return member_failed(g, rc, m);
+    }
     return SDR_OK;
+}
+}  // namespace
+
+int sdr_group_process_device(sdr_group *g, const float *const *iq_dev, int n_frames)
+{
+    return group_process_device(g, reinterpret_cast<const void *const *>(iq_dev), n_frames, false);
+}
+
+int sdr_group_process_device_sc16(sdr_group *g, const int16_t *const *iq_dev, int n_frames)
+{
+    return group_process_device(g, reinterpret_cast<const void *const *>(iq_dev), n_frames, true);
 }
 
 int sdr_group_sync(sdr_group *g)

@@ -95,7 +95,7 @@ int flush_late_attached(sdr_bank *b)
 
 // A failure after the first launch leaves the pipeline half enqueued (some stages of this batch ran, the
 // carried state of others did not advance): no later batch can be trusted, so the bank refuses further work.
-int process_device_impl(sdr_bank *b, const float *iq_dev, int n_frames, int in_stride)
+int process_device_impl(sdr_bank *b, const void *iq_dev, int n_frames, int in_stride, sdr::InFormat fmt)
 {
     if (b->failed)
         return fail(SDR_ERR_STATE, "an earlier process call failed half way; destroy the bank");
@@ -103,7 +103,7 @@ int process_device_impl(sdr_bank *b, const float *iq_dev, int n_frames, int in_s
         return fail(SDR_ERR_STATE, "a graph is captured: process through sdr_graph_launch, or sdr_graph_release first");
     if (b->listen_pending)
         return fail(SDR_ERR_STATE, "the previous batch still waits for its listen half (sdr_process_listen)");
-    const int rc = process_device_body(b, iq_dev, n_frames, in_stride, -1, -1, b->defer_listen ? PART_SPECTRA : PART_ALL);
+    const int rc = process_device_body(b, iq_dev, n_frames, in_stride, -1, -1, b->defer_listen ? PART_SPECTRA : PART_ALL, fmt);
     if (rc == SDR_ERR_HIP)
         b->failed = true;
     return rc;
@@ -127,7 +127,8 @@ constexpr int kDefaultPlan[sdr::K_COUNT] = {
 // parts: PART_SPECTRA leaves the batch's listeners for a later PART_LISTEN call (sdr_defer_listen / sdr_process_listen:
 // the host binds listeners to peaks of this very batch in between, rx/receiver.go:409-426); the later call takes the
 // batch's set, length and first frame from b->pend.
-int process_device_body(sdr_bank *b, const float *iq_dev, int n_frames, int in_stride, int capture_k, int capture_stage, int parts)
+int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_stride, int capture_k, int capture_stage, int parts,
+                        sdr::InFormat fmt)
 {
     const bool cap = capture_k >= 0;
     const bool do_spectra = (parts & PART_SPECTRA) != 0, do_listen = (parts & PART_LISTEN) != 0;
@@ -276,7 +277,7 @@ int process_device_body(sdr_bank *b, const float *iq_dev, int n_frames, int in_s
         tap.wide = S.tapw.p;
         tap.used = S.tap_used.p;
         tap.steal = S.fft_ctr.p;
-        SDR_LAUNCH(sdr::K_FFT, sdr::launch_fft(b->logn, iq_dev, cur, b->tw.p, S.psd.p, n_frames, B, in_stride, stride, tap,
+        SDR_LAUNCH(sdr::K_FFT, sdr::launch_fft(b->logn, fmt, iq_dev, cur, b->tw.p, S.psd.p, n_frames, B, in_stride, stride, tap,
                                                stream_of(sdr::K_FFT)));
     }
     SDR_DONE(sdr::K_FFT);
@@ -564,7 +565,7 @@ int sdr_push_iq(sdr_bank *b, int band, int sample_rate, const float *iq, size_t 
     if ((size_t)b->staged[band] + nf > (size_t)c.max_batch_frames)  // rx/receiver.go:328-333
         return fail(SDR_ERR_WOULD_DROP, "IQ data skipped: staging queue full");
     if (b->staged[band] > 0 && b->staged_kind[band] != 1)
-        return fail(SDR_ERR_STATE, "band already holds raw KiwiSDR frames in this batch");
+        return fail(SDR_ERR_STATE, "band already holds int16 frames (KiwiSDR or sc16) in this batch");
     rc = staging_ready(b, false);
     if (rc)
         return rc;
@@ -593,13 +594,43 @@ int sdr_push_kiwi_snd(sdr_bank *b, int band, int sample_rate, const uint8_t *pay
     if ((size_t)b->staged[band] + nf > (size_t)c.max_batch_frames)
         return fail(SDR_ERR_WOULD_DROP, "IQ data skipped: staging queue full");
     if (b->staged[band] > 0 && b->staged_kind[band] != 2)
-        return fail(SDR_ERR_STATE, "band already holds float32 frames in this batch");
+        return fail(SDR_ERR_STATE, "band already holds float32 or sc16 frames in this batch");
     rc = staging_ready(b, true);
     if (rc)
         return rc;
     b->staged_kind[band] = 2;
     staging_copy(b->stage[b->stage_cur].h_raw + ((size_t)band * c.max_batch_frames + (size_t)b->staged[band]) * per,
                  payload + kHeader, n_bytes - kHeader);
+    b->staged[band] += (int)nf;
+    return SDR_OK;
+}
+
+// sc16 frames from the host: staged raw like a KiwiSDR payload (half the bytes of float32 go over PCIe) and converted on
+// the device by k_unpack_sc16 into the float32 staging buffer the FFT reads
+int sdr_push_iq_sc16(sdr_bank *b, int band, int sample_rate, const int16_t *iq, size_t n_values)
+{
+    int rc = check_band(b, band);
+    if (rc)
+        return rc;
+    if (!iq)
+        return fail(SDR_ERR_BAD_ARG, "null iq");
+    const sdr_config &c = b->cfg;
+    if (sample_rate != c.sample_rate)  // rx/receiver.go:319-322
+        return fail(SDR_ERR_BAD_RATE, "wrong incoming sample rate");
+    const size_t per = 2 * (size_t)c.block_size;  // int16 values per frame
+    if (n_values == 0 || n_values % per != 0)  // rx/receiver.go:323-326
+        return fail(SDR_ERR_BAD_SIZE, "wrong incoming block size");
+    const size_t nf = n_values / per;
+    if ((size_t)b->staged[band] + nf > (size_t)c.max_batch_frames)  // rx/receiver.go:328-333
+        return fail(SDR_ERR_WOULD_DROP, "IQ data skipped: staging queue full");
+    if (b->staged[band] > 0 && b->staged_kind[band] != 3)
+        return fail(SDR_ERR_STATE, "band already holds float32 or KiwiSDR frames in this batch");
+    rc = staging_ready(b, true);
+    if (rc)
+        return rc;
+    b->staged_kind[band] = 3;
+    staging_copy(b->stage[b->stage_cur].h_raw + ((size_t)band * c.max_batch_frames + (size_t)b->staged[band]) * per * 2, iq,
+                 sizeof(int16_t) * n_values);
     b->staged[band] += (int)nf;
     return SDR_OK;
 }
@@ -641,8 +672,8 @@ int sdr_process_staged_limit(sdr_bank *b, int max_frames, int *n_frames_out)
     HIP_TRY(hipStreamWaitEvent(b->copy_stream, st.consumed, 0));
     for (int band = 0; band < c.n_bands; band++) {
         float *dst = st.d_f32.p + (size_t)band * n * per;
-        if (b->staged_kind[band] == 2) {
-            // raw int16be payload: upload half the bytes, unpack in HBM (k_unpack.hip)
+        if (b->staged_kind[band] >= 2) {
+            // raw int16 (KiwiSDR big-endian, or sc16): upload half the bytes, unpack in HBM (k_unpack.hip)
             if (!st.d_raw.p) {
                 hipError_t e = st.d_raw.alloc(2 * per * F * (size_t)c.n_bands);
                 if (e != hipSuccess)
@@ -651,7 +682,10 @@ int sdr_process_staged_limit(sdr_bank *b, int max_frames, int *n_frames_out)
             uint8_t *rdst = st.d_raw.p + (size_t)band * F * per * 2;
             HIP_TRY(hipMemcpyAsync(rdst, st.h_raw + (size_t)band * F * per * 2, 2 * per * (size_t)n, hipMemcpyHostToDevice,
                                    b->copy_stream));
-            HIP_TRY(sdr::launch_unpack_be16(rdst, dst, per * (size_t)n, b->copy_stream));
+            if (b->staged_kind[band] == 2)
+                HIP_TRY(sdr::launch_unpack_be16(rdst, dst, per * (size_t)n, b->copy_stream));
+            else
+                HIP_TRY(sdr::launch_unpack_sc16(reinterpret_cast<const int16_t *>(rdst), dst, per * (size_t)n, b->copy_stream));
         } else {
             HIP_TRY(hipMemcpyAsync(dst, st.h_f32 + (size_t)band * F * per, sizeof(float) * per * (size_t)n, hipMemcpyHostToDevice,
                                    b->copy_stream));
@@ -674,7 +708,7 @@ int sdr_process_staged_limit(sdr_bank *b, int max_frames, int *n_frames_out)
         bool raw = false, f32 = false;
         for (int band = 0; band < c.n_bands; band++)
             if (b->staged[band] > n)
-                (b->staged_kind[band] == 2 ? raw : f32) = true;
+                (b->staged_kind[band] >= 2 ? raw : f32) = true;
         if (f32 && (rc = staging_ready(b, false)))
             return rc;
         if (raw && (rc = staging_ready(b, true)))
@@ -686,7 +720,7 @@ int sdr_process_staged_limit(sdr_bank *b, int max_frames, int *n_frames_out)
     for (int band = 0; band < c.n_bands; band++) {
         const int left = b->staged[band] - n;
         if (left > 0) {
-            if (b->staged_kind[band] == 2)
+            if (b->staged_kind[band] >= 2)
                 memcpy(b->stage[next].h_raw + (size_t)band * F * per * 2, b->stage[prev].h_raw + ((size_t)band * F + (size_t)n) * per * 2,
                        per * 2 * (size_t)left);
             else
@@ -707,6 +741,15 @@ int sdr_process_device(sdr_bank *b, const float *iq_dev, int n_frames)
     if (reinterpret_cast<uintptr_t>(iq_dev) & 15)
         return fail(SDR_ERR_BAD_ARG, "iq_dev must be 16-byte aligned (frames are copied to LDS 16 bytes per lane)");
     return process_device_impl(b, iq_dev, n_frames, n_frames);
+}
+
+int sdr_process_device_sc16(sdr_bank *b, const int16_t *iq_dev, int n_frames)
+{
+    if (!b || !iq_dev)
+        return fail(SDR_ERR_BAD_ARG, "null argument");
+    if (reinterpret_cast<uintptr_t>(iq_dev) & 15)
+        return fail(SDR_ERR_BAD_ARG, "iq_dev must be 16-byte aligned (frames are copied to LDS 16 bytes per lane)");
+    return process_device_impl(b, iq_dev, n_frames, n_frames, sdr::InFormat::SC16);
 }
 
 

@@ -14,6 +14,7 @@
 #include "fft_f64.h"
 #include "fft_r32.h"
 #include "gomath.h"
+#include "sc16.h"
 #include "sdr_device.h"
 
 #if !defined(SDR_FFT_PSD_AUX)
@@ -666,6 +667,96 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
+// k_fft_psd for sc16 input (sc16.h: int16 I, int16 Q per sample): the one-frame workgroup of k_fft_psd<LOGN, false> with
+// half the input bytes.  Its LDS-DMA moves 4 bytes per sample - 256 samples per 1 KB row, R / 4 rows per wave - into
+// sc16.h's staging image, pass 0 reads one ds_read_b32 per register slot and converts where the float32 kernel widens.
+// From the first butterfly on everything is the float32 kernel's (run_passes, store_psd, the LDS tap), so the results
+// are the float32 path's bits for the converted values.  Only this one form exists for sc16: the multi-frame workgroup,
+// layout B, wave-private staging and the timing-only builds stay float32-only (launch_fft_t).
+template <int LOGN>
+__global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 ? 4 : 1)) void k_fft_psd_sc16(const int16_t *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
+                                                                       const fft64::cplx *__restrict__ tw, float *__restrict__ psd,
+                                                                       int in_stride, int out_stride, const int *__restrict__ tap_bins,
+                                                                       float *__restrict__ tap_out, int n_tap, int tap_stride)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    using PL = fft64::Plan<LOGN>;
+    static_assert(!PL::LB, "sc16 input has no layout B kernel");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double *lds = reinterpret_cast<double *>(smem);
+    Stamps st;
+#if defined(SDR_FFT_PHASES)
+    st.on = false;
+#endif
+    const int16_t *__restrict__ iq = cur ? cur->iq_sc16 : iq_arg;  // graph replay: the batch's input pointer lives in device memory
+    const int frame = blockIdx.x;
+    const size_t in_band = (size_t)blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
+    const int t = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    {
+        // frame -> LDS: row r = wave * R/4 + j; lane p fetches granule sc16::granule(p, r) of the row (the swizzle lives in
+        // the source address, the DMA writes lane p's 16 bytes at row base + 16 p)
+        constexpr int ROWS_PER_WAVE = PL::R / 4;
+        const int lane = t & 63;
+        const rsrc_t xrs = make_rsrc(iq + (in_band + frame) * PL::N * 2, PL::N * 4u);
+#pragma unroll
+        for (int j = 0; j < ROWS_PER_WAVE; j++) {
+            const int r = wave * ROWS_PER_WAVE + j;
+            const int g = sc16::granule<LOGN>(lane, r);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void *)(smem + r * 1024), 16,
+                                                     (unsigned)g * 16u, r * 1024, 0, SDR_FFT_DMA_AUX);
+        }
+    }
+    // the listeners' bins into LDS (behind the exchange area) while the frame is on its way
+    int *lds_bins = reinterpret_cast<int *>(smem + fft64::kLdsBytes<LOGN>);
+    const bool lds_tap = n_tap > 0 && n_tap <= kMaxLdsTap;
+    if (lds_tap)
+        for (int l = threadIdx.x; l < n_tap; l += PL::T)
+            lds_bins[l] = tap_bins[(size_t)blockIdx.y * tap_stride + l];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    double xr[PL::R], xi[PL::R];
+    {
+        // dsp/fft.go:59-69 setSamplesFromIQ: slot m <- sample input_sample(t, m), the image address linear over GF(2)
+        const int thread_byte = sc16::lds_byte<LOGN>(fft64::input_sample<LOGN>(t, 0));
+#pragma unroll
+        for (int m = 0; m < PL::R; m++) {
+            const int slot_byte = sc16::lds_byte<LOGN>(fft64::input_sample<LOGN>(0, m));
+            const uint32_t w = *reinterpret_cast<const uint32_t *>(smem + (thread_byte ^ slot_byte));
+            xr[m] = (double)sc16::re_of(w);
+            xi[m] = (double)sc16::im_of(w);
+        }
+    }
+    __syncthreads();  // everyone has its samples: the exchange area may be written again
+    const fft64::cplx no_pre[kTwPreMax] = {};
+    run_passes<LOGN, 0, true>(xr, xi, t, make_rsrc(tw, (unsigned)(PL::TW_TOTAL * sizeof(fft64::cplx))), tw, lds, [] {}, no_pre, st);
+    if constexpr (!last_lds_exchange_is_cross<LOGN>())
+        if (lds_tap)
+            __syncthreads();  // a wave-local last exchange fences only its own wave; the row goes everywhere
+    store_psd<LOGN, true>(xr, xi, t, psd + (out_band + frame) * PL::N, smem, lds_tap);
+    if (lds_tap) {
+        __syncthreads();  // the row is in LDS
+        const float *row = reinterpret_cast<const float *>(smem);
+        float *out = tap_out + (out_band + frame) * (size_t)tap_stride;
+        for (int l = threadIdx.x; l < n_tap; l += PL::T) {
+            const int bin = lds_bins[l];
+            out[l] = bin >= 0 ? row[bin] : 0.0f;
+        }
+    } else if (n_tap > 0) {
+        // more listeners than the LDS tap holds: re-read the stored row once it has reached memory
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        const float *row = psd + (out_band + frame) * PL::N;
+        float *out = tap_out + (out_band + frame) * (size_t)tap_stride;
+        const int *bins = tap_bins + (size_t)blockIdx.y * tap_stride;
+        for (int l = threadIdx.x; l < n_tap; l += PL::T) {
+            const int bin = bins[l];
+            out[l] = bin >= 0 ? row[bin] : 0.0f;
+        }
+    }
+#endif  // __HIP_DEVICE_COMPILE__
+}
+
 // Epilogue of layout B (dsp/fft.go:54-57 fftshift, :71-73 PSD[float32]).  Wave w holds the bins = w (mod 16): stored
 // from the registers, a wave instruction would put 64 four-byte words into 64 different 64-byte segments of the row
 // (measured: 0.087 of the kernel's 0.21 ms).  So the row goes through a 32 KB tile of LDS - the part the next frame's
@@ -939,11 +1030,14 @@ static int fft_fpw_b()
 }
 
 template <int LOGN>
-static hipError_t launch_fft_t(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
+static hipError_t launch_fft_t(InFormat fmt, const void *iq_in, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
                                int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
     using PL = fft64::Plan<LOGN>;
+    const float *iq = static_cast<const float *>(iq_in);
     if constexpr (PL::LB) {
+        if (fmt != InFormat::F32)
+            return hipErrorNotSupported;  // (layout B builds: sc16 input has no kernel at this size)
         static std::once_flag b_attr_once[kMaxDevices];
         int dev = 0;
         hipError_t e = hipGetDevice(&dev);
@@ -980,7 +1074,8 @@ static hipError_t launch_fft_t(const float *iq, const BatchCursor *cur, const ff
     hipError_t attr_err = hipSuccess;
     std::call_once(attr_once[dev], [&] {
         for (const void *k : {reinterpret_cast<const void *>(&k_fft_psd<LOGN, false>),
-                              reinterpret_cast<const void *>(&k_fft_psd<LOGN, true>)}) {
+                              reinterpret_cast<const void *>(&k_fft_psd<LOGN, true>),
+                              reinterpret_cast<const void *>(&k_fft_psd_sc16<LOGN>)}) {
             const hipError_t ae = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, fft64::kLdsBytes<LOGN> + kMaxLdsTap * 4 + kPfSinkBytes);
             if (ae != hipSuccess)
                 attr_err = ae;
@@ -990,6 +1085,13 @@ static hipError_t launch_fft_t(const float *iq, const BatchCursor *cur, const ff
         return attr_err;
     if (n_frames <= 0 || n_bands <= 0)
         return hipSuccess;
+    const unsigned tap_lds = tap.n > 0 && tap.n <= kMaxLdsTap ? ((tap.n * 4 + 255) & ~255) : 0;
+    if (fmt == InFormat::SC16) {
+        // one frame per workgroup, always (SDR_FFT_FPW is the float32 kernel's)
+        launch_kernel((k_fft_psd_sc16<LOGN>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, stream,
+                      static_cast<const int16_t *>(iq_in), cur, tw, psd, in_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride);
+        return hipGetLastError();
+    }
     // a workgroup's frames are consecutive; never fewer workgroups than CUs can take (a short batch keeps one
     // frame per workgroup)
     int fpw = fft_fpw();
@@ -1000,7 +1102,7 @@ static hipError_t launch_fft_t(const float *iq, const BatchCursor *cur, const ff
                            iq, cur, tw, psd, in_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride);
     else
         launch_kernel((k_fft_psd<LOGN, false>), dim3(n_frames, n_bands), dim3(PL::T),
-                           fft64::kLdsBytes<LOGN> + (tap.n > 0 && tap.n <= kMaxLdsTap ? ((tap.n * 4 + 255) & ~255) : 0) + kPfSinkBytes, stream, iq, cur, tw, psd, in_stride,
+                           fft64::kLdsBytes<LOGN> + tap_lds + kPfSinkBytes, stream, iq, cur, tw, psd, in_stride,
                            out_stride, n_frames, 1, tap.bins, tap.out, tap.n, tap.stride);
     return hipGetLastError();
     }
@@ -1009,7 +1111,8 @@ static hipError_t launch_fft_t(const float *iq, const BatchCursor *cur, const ff
 // N = 16384 has two kernels: this file's 16-point one and k_fft_r32.hip (512 threads x 32 points, the next frame
 // prefetched into registers), whose workgroups - one per CU - claim frames from a counter.  SDR_FFT_R32 = 0 / 1 forces one
 // of them (tests); by default the 32-point kernel runs from 1024 frames per launch on (measured by batch size).  The bank's
-// twiddle buffer holds both kernels' tables, the 32-point kernel's behind the other.
+// twiddle buffer holds both kernels' tables, the 32-point kernel's behind the other.  sc16 input takes the same choice
+// (k_fft_r32_sc16 or k_fft_psd_sc16<14>): the switch and SDR_FFT_R32 do not look at the format.
 static int r32_mode()
 {
     static const int v = [] {
@@ -1027,22 +1130,33 @@ static bool use_r32(int logn, int n_frames, int n_bands, int tap_n)
 }
 bool fft_writes_wide_tap(int logn, int n_frames, int n_bands, int tap_n) { return tap_n > 0 && use_r32(logn, n_frames, n_bands, tap_n); }
 
+hipError_t launch_fft(int logn, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
+                      int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+{
+    if (fmt != InFormat::F32 && fmt != InFormat::SC16)
+        return hipErrorInvalidValue;
+    if (logn == 14) {
+        if (use_r32(logn, n_frames, n_bands, tap.n)) {
+            const fft64::cplx *tw32 = tw + fft64::Plan<14>::TW_TOTAL;
+            if (fmt == InFormat::SC16)
+                return launch_fft_r32_sc16(static_cast<const int16_t *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+            return launch_fft_r32(static_cast<const float *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+        }
+    }
+    switch (logn) {
+    case 9: return launch_fft_t<9>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 10: return launch_fft_t<10>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 11: return launch_fft_t<11>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 12: return launch_fft_t<12>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 13: return launch_fft_t<13>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 14: return launch_fft_t<14>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
 hipError_t launch_fft(int logn, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
                       int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
-    if (logn == 14) {
-        if (use_r32(logn, n_frames, n_bands, tap.n))
-            return launch_fft_r32(iq, cur, tw + fft64::Plan<14>::TW_TOTAL, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    }
-    switch (logn) {
-    case 9: return launch_fft_t<9>(iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 10: return launch_fft_t<10>(iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 11: return launch_fft_t<11>(iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 12: return launch_fft_t<12>(iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 13: return launch_fft_t<13>(iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 14: return launch_fft_t<14>(iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return launch_fft(logn, InFormat::F32, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
 }
 
 int twiddle_count(int logn)

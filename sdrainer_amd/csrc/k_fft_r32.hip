@@ -24,6 +24,12 @@
 //   psd = f32(re^2 + im^2) -> LDS row (fft-shifted, swizzled) B -> 16-byte runs per lane -> global (1 KB per wave
 //   instruction) + the listeners' tap straight from the row
 // Compiled with -ffp-contract=off: the butterflies are the reference's ten float64 operations, no FMA.
+//
+// sc16 input.  k_fft_r32_sc16.hip compiles this file again with SDR_R32_SC16 = 1: the kernel k_fft_r32_sc16 reads complex
+// int16 frames (sc16.h).  Its next frame waits in 32 registers instead of 64 (one 4-byte word per slot), the same 32
+// loads per thread are dealt over the frame by the same plan - 4 bytes per lane, 256 contiguous bytes per wave instruction
+// - and the samples are converted (sc16::to_f32) where the float32 kernel widens.  Everything else is the float32
+// kernel's.  Its own translation unit keeps the float32 kernel's source, and so its code, exactly as it was.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +37,18 @@
 
 #include "fft_r32.h"
 #include "sdr_device.h"
+
+#if !defined(SDR_R32_SC16)
+#define SDR_R32_SC16 0
+#endif
+#if SDR_R32_SC16
+#include "sc16.h"
+#define SDR_R32_KERNEL k_fft_r32_sc16
+#define SDR_R32_IN int16_t
+#else
+#define SDR_R32_KERNEL k_fft_r32
+#define SDR_R32_IN float
+#endif
 
 #if !defined(SDR_R32_IN_AUX)
 #define SDR_R32_IN_AUX 0  // cache policy bits of the input loads (2 = nt)
@@ -241,7 +259,7 @@ __device__ __forceinline__ void ex_read(double (&x)[32], int t, const double *ar
 // launches: the workgroup that finishes last stores zero into both (launches on one pair are serialised by their stream,
 // and graph replay re-runs the same arguments: nothing on the host has to reset them).
 
-__global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
+__global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
                                                           const cplx *__restrict__ tw, float *__restrict__ psd, int in_stride,
                                                           int out_stride, int n_frames, unsigned *__restrict__ steal, const int *__restrict__ tap_bins,
                                                           float *__restrict__ tap_out, int n_tap, int tap_stride,
@@ -252,12 +270,16 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *ex = reinterpret_cast<double *>(smem);
     const unsigned char *tw1_lds = smem + kExchangeBytes;
+#if SDR_R32_SC16
+    const int16_t *__restrict__ iq = cur ? cur->iq_sc16 : iq_arg;  // graph replay: the batch's input pointer lives in device memory
+#else
     const float *__restrict__ iq = cur ? cur->iq : iq_arg;  // graph replay: the batch's input pointer lives in device memory
+#endif
     const unsigned n_fr = (unsigned)n_frames;
     constexpr unsigned kNoFrame = ~0u;  // (no frame: the row of `prev` in front of the first)
     // this band's rows (four bases in eight SGPRs; with the bands' offsets kept beside the bases it was twelve)
     const size_t out_band = (size_t)blockIdx.y * out_stride;
-    const float *const iq_b = iq + (size_t)blockIdx.y * in_stride * (size_t)N * 2;
+    const SDR_R32_IN *const iq_b = iq + (size_t)blockIdx.y * in_stride * (size_t)N * 2;
     float *const psd_b = psd + out_band * (size_t)N, *const tap_b = tap_out + out_band * (size_t)tap_stride;
     float *const wide_b = tap_wide ? tap_wide + out_band * (size_t)(4 * tap_stride) : nullptr;
     const int tid = threadIdx.x;
@@ -265,17 +287,31 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
 
     // setSamplesFromIQ's reads, one frame ahead: slot m <- sample tid + 512 * brev5(m) (fft_r32.h: pass 0's thread part of
     // the sample number is the thread id), 8 bytes per lane, 512 contiguous bytes per wave instruction
+#if SDR_R32_SC16
+    unsigned pf[R];  // (sc16: one word per sample, 256 contiguous bytes per wave instruction)
+    constexpr unsigned kSampleBytes = 4;
+#else
     u32x2 pf[R];
+#endif
     // slots [m0, m1) of `frame`; a claim past the batch gets a descriptor of zero bytes: the loads return zeros without
     // touching memory, and the frame's code stays free of branches
     auto fetch = [&](unsigned frame, int t, int m0, int m1) {
         const bool live = frame < n_fr;
+#if SDR_R32_SC16
+        const rsrc_t xrs = make_rsrc(iq_b + (size_t)frame * N * 2, live ? N * kSampleBytes : 0u);
+        const unsigned voff = (unsigned)thread_sample(t) * kSampleBytes;
+#pragma unroll
+        for (int m = 0; m < R; m++)
+            if (m >= m0 && m < m1)
+                pf[m] = __builtin_amdgcn_raw_buffer_load_b32(xrs, voff, slot_sample(m) * (int)kSampleBytes, SDR_R32_IN_AUX);
+#else
         const rsrc_t xrs = make_rsrc(iq_b + (size_t)frame * N * 2, live ? N * 8u : 0u);
         const unsigned voff = (unsigned)thread_sample(t) * 8u;
 #pragma unroll
         for (int m = 0; m < R; m++)
             if (m >= m0 && m < m1)
                 pf[m] = __builtin_amdgcn_raw_buffer_load_b64(xrs, voff, slot_sample(m) * 8, SDR_R32_IN_AUX);
+#endif
     };
     unsigned *stash = reinterpret_cast<unsigned *>(smem + kExchangeBytes + kTw1LdsBytes + kSoftCounters * 4);
     unsigned *claim_lds = stash + kStashWords;
@@ -379,8 +415,13 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
         double xr[R], xi[R];
 #pragma unroll
         for (int m = 0; m < R; m++) {  // dsp/fft.go:59-69 setSamplesFromIQ: widen, exact
+#if SDR_R32_SC16
+            xr[m] = (double)sc16::re_of(pf[m]);  // (sc16: converted first, float32(x) / 32767 rounded once)
+            xi[m] = (double)sc16::im_of(pf[m]);
+#else
             xr[m] = (double)__uint_as_float(pf[m].x);
             xi[m] = (double)__uint_as_float(pf[m].y);
+#endif
         }
         // (the next frame's requests go out BEHIND the conversions: hoisted above them - they depend on nothing - both
         // frames' samples would be live at once, 64 registers more than there are; the pins keep the conversions from
@@ -581,8 +622,10 @@ __global__ __launch_bounds__(fft32::T, 2) void k_fft_r32(const float *__restrict
 
 }  // namespace r32
 
+#if !SDR_R32_SC16
 int r32_twiddle_count() { return fft32::kTwTotal; }
 void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out) { fft32::build_twiddles(wre, wim, out); }
+#endif
 
 // Workgroups per band: one per CU, less SDR_R32_RESERVE CUs left to the tail stages of the other streams (measured at
 // config 3, see HISTORY round 6), never more than there are frames.
@@ -590,8 +633,13 @@ void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out) 
 #define SDR_R32_RESERVE 0
 #endif
 
+#if SDR_R32_SC16
+hipError_t launch_fft_r32_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+                               int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+#else
 hipError_t launch_fft_r32(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
                           int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+#endif
 {
     constexpr int kMaxDevices = 64;
     static std::once_flag setup_once[kMaxDevices];
@@ -604,7 +652,7 @@ hipError_t launch_fft_r32(const float *iq, const BatchCursor *cur, const fft64::
     if (dev < 0 || dev >= kMaxDevices)
         return hipErrorInvalidDevice;
     std::call_once(setup_once[dev], [dev] {
-        hipError_t se = hipFuncSetAttribute(reinterpret_cast<const void *>(&r32::k_fft_r32), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t se = hipFuncSetAttribute(reinterpret_cast<const void *>(&r32::SDR_R32_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             r32::kLdsBytes);
         if (se == hipSuccess)
             se = hipDeviceGetAttribute(&cu_count[dev], hipDeviceAttributeMultiprocessorCount, dev);
@@ -620,7 +668,7 @@ hipError_t launch_fft_r32(const float *iq, const BatchCursor *cur, const fft64::
         return hipErrorInvalidValue;  // the frame counters are the bank's (BatchSet::fft_ctr)
     const int cus = std::max(1, cu_count[dev] - SDR_R32_RESERVE);
     const int grid = std::min((cus + n_bands - 1) / n_bands, n_frames);
-    launch_kernel(r32::k_fft_r32, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, stream, iq, cur, tw, psd, in_stride, out_stride,
+    launch_kernel(r32::SDR_R32_KERNEL, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, stream, iq, cur, tw, psd, in_stride, out_stride,
                   n_frames, tap.steal, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used);
     return hipGetLastError();
 }

@@ -4,6 +4,7 @@
 // source: the raw payload is what gets uploaded.
 #include <hip/hip_runtime.h>
 
+#include "sc16.h"
 #include "sdr_device.h"
 
 namespace sdr {
@@ -43,6 +44,37 @@ hipError_t launch_unpack_be16(const uint8_t *raw, float *out, size_t n_values, h
         return hipSuccess;
     const size_t threads = (n_values + 3) / 4;
     hipLaunchKernelGGL(k_unpack_be16, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, raw, out, n_values);
+    return hipGetLastError();
+}
+
+// sdr_push_iq_sc16: little-endian int16 values (sc16) -> float32, 4 values per thread (8-byte loads, 16-byte stores);
+// the conversion is the one the sc16 FFT kernels use (sc16.h)
+__global__ __launch_bounds__(256) void k_unpack_sc16(const int16_t *__restrict__ raw, float *__restrict__ out, size_t n_values)
+{
+    const size_t i4 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t i = i4 * 4;
+    if (i >= n_values)
+        return;
+    if (i + 4 <= n_values) {
+        const uint2 w = *reinterpret_cast<const uint2 *>(raw + i);  // staging buffers are 8-byte aligned
+        float4 f;
+        f.x = sc16::re_of(w.x);
+        f.y = sc16::im_of(w.x);
+        f.z = sc16::re_of(w.y);
+        f.w = sc16::im_of(w.y);
+        *reinterpret_cast<float4 *>(out + i) = f;
+    } else {
+        for (size_t k = i; k < n_values; k++)
+            out[k] = sc16::to_f32(raw[k]);
+    }
+}
+
+hipError_t launch_unpack_sc16(const int16_t *raw, float *out, size_t n_values, hipStream_t stream)
+{
+    if (n_values == 0)
+        return hipSuccess;
+    const size_t threads = (n_values + 3) / 4;
+    hipLaunchKernelGGL(k_unpack_sc16, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, raw, out, n_values);
     return hipGetLastError();
 }
 

@@ -63,12 +63,16 @@ struct NoiseGeom {
 // writes the cursors of the batches of one replay into pinned memory and the graph's first node uploads them.
 // A null cursor pointer means "use the launch parameters" (the eager path).
 struct BatchCursor {
-    const float *iq;      // this batch's input frames
+    const float *iq;      // this batch's input frames (float32 graphs)
     uint32_t frame_base;  // bank frame index of its first frame
     int32_t count0;       // cumulationCount before its first frame
     int32_t carry_in;     // which of the two carry buffers holds the cumulation carried in (0 / 1)
     int32_t reserved;
+    const int16_t *iq_sc16;  // this batch's input frames (sc16 graphs: sdr_graph_capture_sc16)
 };
+
+// What the FFT kernels read: interleaved float32 I,Q or complex int16 (sc16.h)
+enum class InFormat { F32 = 0, SC16 = 1 };
 
 struct ListenGeom {
     int n, stride, max_listeners, text_cap, edge_cap, bit_words, trace;
@@ -140,13 +144,19 @@ struct FftTap {
     uint32_t *steal = nullptr;
 };
 
-hipError_t launch_fft(int logn, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
+// iq: [band][in_stride frames][N] samples of format fmt (float32 pairs or sc16 words)
+hipError_t launch_fft(int logn, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
                       int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream);
+hipError_t launch_fft(int logn, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
+                      int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream);  // (float32)
 int twiddle_count(int logn);
 void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx *out);
 // k_fft_r32.hip: N = 16384 as 512 threads x 32 points with the next frame prefetched into registers (own twiddle layout)
 hipError_t launch_fft_r32(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
                           int in_stride, int out_stride, FftTap tap, hipStream_t stream);
+// k_fft_r32_sc16.hip: the same kernel reading sc16 frames
+hipError_t launch_fft_r32_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+                               int in_stride, int out_stride, FftTap tap, hipStream_t stream);
 int r32_twiddle_count();
 void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out);
 hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, int n_frames, int n_bands, int stride,
@@ -191,6 +201,7 @@ __host__ __device__ inline int chunks_completed(int count0, int n_frames)
     return n_frames >= first_len ? 1 + (n_frames - first_len) / SDR_CUMULATION_SIZE : 0;
 }
 hipError_t launch_unpack_be16(const uint8_t *raw, float *out, size_t n_values, hipStream_t stream);
+hipError_t launch_unpack_sc16(const int16_t *raw, float *out, size_t n_values, hipStream_t stream);  // little-endian int16 values
 hipError_t launch_find_peaks(float *cum, const float *psd, const void *db_tab, const float *carry0, const float *carry1, int carry_in,
                              const sdr_frame_rec *recs, DevPeak *peaks, int *counts, const BatchCursor *cur, PeakGeom g, int n_frames,
                              int n_chunks, int n_bands, FftTap tap, hipStream_t stream);  // tap: .wide / .used / .n / .stride of this batch's FFT (or null)

@@ -1,0 +1,52 @@
+"""k_fft_r32_sc16's register budget, checked at compile time (no GPU), as tests/test_kernel_resources.py checks the
+float32 kernel: k_fft_r32.hip compiled again with SDR_R32_SC16 = 1 (k_fft_r32_sc16.hip), device-only for gfx950 with the
+library's own flags, and the compiler's resource report read.  The sc16 kernel must run at two waves per SIMD with
+nothing in scratch, like the float32 one; its prefetched frame is 32 registers instead of 64."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from sdrainer_amd.csrc import build as hip_build
+
+SRC = os.path.join(hip_build.HERE, "k_fft_r32_sc16.hip")
+
+
+@pytest.fixture(scope="module")
+def usage(tmp_path_factory):
+    try:
+        cc = hip_build.hipcc()
+    except RuntimeError as e:
+        pytest.fail(str(e))
+    assert "k_fft_r32_sc16.hip" in hip_build.SOURCES
+    out = tmp_path_factory.mktemp("res") / "k_fft_r32_sc16.o"
+    flags = hip_build.FLAGS + hip_build.EXTRA_FLAGS["k_fft_r32_sc16.hip"]
+    assert hip_build.EXTRA_FLAGS["k_fft_r32_sc16.hip"] == hip_build.EXTRA_FLAGS["k_fft_r32.hip"]
+    cmd = [cc] + flags + ["--cuda-device-only", "-c", SRC, "-o", str(out), "-Rpass-analysis=kernel-resource-usage"]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-4000:]
+    names = re.findall(r"Function Name: (\S+)", p.stderr)
+    assert not any("k_fft_r32E" in n or ("k_fft_r32" in n and "sc16" not in n) for n in names), names
+    m = re.search(r"Function Name: \S*k_fft_r32_sc16\S*(.*?)(?:Function Name:|\Z)", p.stderr, re.S)
+    assert m, "no resource report for k_fft_r32_sc16"
+    return {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", m.group(1))}
+
+
+def _int(usage, key):
+    assert key in usage, f"{key!r} missing from the report: {sorted(usage)}"
+    return int(usage[key])
+
+
+def test_no_spills(usage):
+    assert _int(usage, "VGPRs Spill") == 0
+    assert _int(usage, "SGPRs Spill") == 0
+
+
+def test_no_scratch(usage):
+    assert _int(usage, "ScratchSize [bytes/lane]") == 0
+
+
+def test_vgprs_and_occupancy(usage):
+    assert _int(usage, "VGPRs") <= 256
+    assert _int(usage, "Occupancy [waves/SIMD]") == 2

@@ -34,6 +34,15 @@ __device__ unsigned long long g_fft_wg[2048][4];
 #include "../sdrainer_amd/csrc/k_fft_r32.hip"  // (launch_fft routes N = 16384 to it; SDR_FFT_R32=0 keeps the 16-point kernel)
 #include "../sdrainer_amd/csrc/twiddles.h"
 
+namespace sdr {
+// (this tool times float32 input only: launch_fft's sc16 branch is linked to nothing - k_fft_r32_sc16.hip is k_fft_r32.hip
+// compiled again and cannot share this translation unit)
+hipError_t launch_fft_r32_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, int, int, FftTap, hipStream_t)
+{
+    return hipErrorNotSupported;
+}
+}  // namespace sdr
+
 static unsigned long long fnv(const void *p, size_t n)
 {
     const unsigned char *b = static_cast<const unsigned char *>(p);

@@ -25,6 +25,15 @@ __device__ unsigned g_r32_phases[8][16];
 #include "../sdrainer_amd/csrc/k_fft_r32.hip"
 #include "../sdrainer_amd/csrc/twiddles.h"
 
+namespace sdr {
+// (this tool times float32 input only: launch_fft's sc16 branch is linked to nothing - k_fft_r32_sc16.hip is k_fft_r32.hip
+// compiled again and cannot share this translation unit)
+hipError_t launch_fft_r32_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, int, int, FftTap, hipStream_t)
+{
+    return hipErrorNotSupported;
+}
+}  // namespace sdr
+
 static unsigned long long fnv(const void *p, size_t n)
 {
     const unsigned char *b = static_cast<const unsigned char *>(p);
