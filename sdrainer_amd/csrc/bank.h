@@ -86,7 +86,7 @@ inline const char *const kKernelNames[sdr::K_COUNT] = {"k_fft_psd",       "k_win
 constexpr int G_THRESHOLDS = 4, N_GRAPHS = 5;
 constexpr int GRAPH_PHASES = 4;  // graph mode: replays in flight, each with RING buffer sets of its own (sdr_graph_capture)
 constexpr int RING = 6;  // per-batch buffer sets in flight (a batch lives about four FFT launches from its FFT to its last result)
-enum Stage { S_FFT = 0, S_NOISE, S_LISTEN, S_PEAKS, N_STAGES };  // the bank's streams: four = the hardware queues HIP gives a process; with six streams created (two unused!) the step was 0.49 ms instead of 0.25, with GPU_MAX_HW_QUEUES=8 and five or six in use 0.29-0.60
+using sdr::S_FFT, sdr::S_NOISE, sdr::S_LISTEN, sdr::S_PEAKS, sdr::N_STAGES;  // the bank's streams (host/batch_plan.h)
 
 // Everything one batch produces.
 struct BatchSet {
@@ -158,6 +158,7 @@ struct sdr_bank {
     static constexpr int N_STAGES = sdrcapi::N_STAGES, GRAPH_PHASES = sdrcapi::GRAPH_PHASES, N_GRAPHS = sdrcapi::N_GRAPHS, RING = sdrcapi::RING;
 
     sdr_config cfg{};
+    sdr::Switches sw;  // the environment's switches, read at creation (host/batch_plan.h)
     int logn = 0;
     int device = 0;
     hipStream_t stream[N_STAGES] = {};  // stream[S_FFT] is the caller's (or the null stream)

@@ -197,6 +197,7 @@ int sdr_create(const sdr_config *cfg, sdr_bank **out)
 
     sdr_bank *b = new sdr_bank();
     b->cfg = *cfg;
+    b->sw = sdr::read_switches();
     b->device = cfg->device_id;
     b->logn = ilog2(N);
     b->edge_width = cfg->edge_width;
@@ -216,8 +217,7 @@ int sdr_create(const sdr_config *cfg, sdr_bank **out)
     } while (0)
 
     // SDR_NO_OVERLAP=1 runs every stage on the caller's stream (kernel-by-kernel profiling)
-    const char *no_overlap = getenv("SDR_NO_OVERLAP");
-    for (int s = 1; s < N_STAGES && !(no_overlap && no_overlap[0] == '1'); s++) {
+    for (int s = 1; s < N_STAGES && !b->sw.no_overlap; s++) {
         hipError_t e = hipStreamCreateWithFlags(&b->stream[s], hipStreamNonBlocking);
         if (e != hipSuccess) {
             sdr_destroy(b);
@@ -231,7 +231,7 @@ int sdr_create(const sdr_config *cfg, sdr_bank **out)
     // replays overlap stream against stream, ran at 101 instead of 156 GS/s (config 3; round 4, found by bisection).
     // Only the chain kernels (SDR_NOISE_PATH=chains) need it: the default noise path (k_noise_scan.hip) does not use the
     // matrix pipe, so a bank on it depends on no undocumented behaviour and is not probed.
-    if (getenv("SDR_NOISE_PATH") && std::string(getenv("SDR_NOISE_PATH")) == "chains") {
+    if (!b->sw.noise_scan) {
         const int sc = self_check_once(cfg->device_id);
         if (sc != SDR_OK) {
             sdr_destroy(b);

@@ -258,7 +258,7 @@ static int graph_launch(sdr_bank *b, const void *const *iq_dev, sdr::InFormat fm
     if (b->results_on != b->graph_results_on || b->find_peaks != b->graph_find_peaks)
         return fail(SDR_ERR_STATE, "sdr_enable_results / sdr_set_find_peaks changed since the capture: capture again");
     HIP_TRY(hipSetDevice(b->device));
-    static const bool dbg = getenv("SDR_GRAPH_DEBUG") != nullptr;
+    const bool dbg = b->sw.graph_debug;
     double tdbg[8] = {};
     int ndbg = 0;
     auto stamp = [&] {

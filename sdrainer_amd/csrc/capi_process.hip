@@ -109,14 +109,6 @@ int process_device_impl(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
     return rc;
 }
 
-// Which of the bank's four streams each kernel runs on (index = sdr::KernelId).  The step is as long as the
-// longest stream, and kernels that carry state from batch to batch (thresholds, decode, cumulate) must keep their
-// stream so that the stream orders the batches.  SDR_DIAG builds read an override from SDR_DIAG_PLAN (eight
-// digits) to try other plans.
-constexpr int kDefaultPlan[sdr::K_COUNT] = {
-    /* fft */ S_FFT, /* window means */ S_NOISE, /* noise stats */ S_NOISE, /* thresholds */ S_PEAKS,
-    /* gather */ S_LISTEN, /* cumulate */ S_PEAKS, /* find peaks */ S_PEAKS, /* decode */ S_LISTEN};
-
 // capture_stage: while capturing, ONE stream records at a time (sdr_graph_capture walks the batches once per stream):
 // only the kernels of that stream are issued, everything else of the batch is skipped in that walk, and NO event is
 // recorded or waited for - what orders the streams of a replay are events around whole graphs (sdr_graph_launch).
@@ -157,29 +149,21 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
     const int64_t first_frame = do_spectra ? b->total_frames : b->pend.first_frame;
     BatchSet &S = b->set[si];
     host::ResultSet &RS = b->results->set(si);  // (its block and events exist once bulk delivery is on)
-    int plan[sdr::K_COUNT];
-    for (int k = 0; k < sdr::K_COUNT; k++)
-        plan[k] = kDefaultPlan[k];
-    // Small geometries (one band of N <= 8192, two of 4096 ...): the FFT of a batch is shorter than its decoders, whose time
-    // goes with the frames, not the samples - the listen stream is the longest, and the gather, which carries no state
-    // from batch to batch and so may run on any stream, moves behind the thresholds it waits for anyway (config 2:
-    // 0.206 -> 0.142 ms per 4096-frame step, 80 -> 118 GS/s; config 3 unchanged within a percent either way, config 5's
-    // share 10 % SLOWER with it: its peaks stream is the full one).  Not under capture: a replay's graphs are cut by stream.
-    // (a gather there also waits for late-attached slots: see slots_put below)
-    if (!cap && (long)B * N <= 8192)
-        plan[sdr::K_LISTEN_GATHER] = S_PEAKS;
+    int max_slots = 0;
+    for (int i = 0; i < B; i++)
+        max_slots = std::max(max_slots, b->n_slots[i]);
+    // every choice of this batch (host/batch_plan.h); a gather moved off the listen stream also waits for late-attached
+    // slots: see slots_put below
+    const int count0 = b->cum_count;
+    const sdr::BatchPlan P = sdr::plan_batch(b->sw, sdr::BatchGeometry{B, N, stride, b->max_chunks}, n_frames, count0, cap, max_slots);
+    const int *plan = P.stream;
+    const sdr::CumGeom cg{N, stride, n_frames, count0, b->max_chunks};
     // is kernel k part of the graph that is recording (always, outside a capture)?
 #define SDR_ON(k) (!cap || (capture_stage == G_THRESHOLDS ? (k) == sdr::K_THRESHOLDS : (plan[k] == capture_stage && (k) != sdr::K_THRESHOLDS)))
 #if defined(SDR_DIAG)
-    // diagnostic builds only (tools/abl): SDR_DIAG_SKIP = bit mask of kernel ids not to launch, to see
-    // which stage holds the pipelined step up (results are wrong by construction); SDR_DIAG_PLAN = stream plan.
-    static const int diag_skip = getenv("SDR_DIAG_SKIP") ? atoi(getenv("SDR_DIAG_SKIP")) : 0;
-    if (const char *e = getenv("SDR_DIAG_PLAN"))
-        for (int k = 0; k < sdr::K_COUNT && e[k] >= '0' && e[k] < '0' + N_STAGES; k++)
-            plan[k] = e[k] - '0';
 #define SDR_LAUNCH(id, call) \
     do {                     \
-        if (!(diag_skip >> (id) & 1) && SDR_ON(id)) \
+        if (!(b->sw.diag_skip >> (id) & 1) && SDR_ON(id)) \
             HIP_TRY(call);   \
     } while (0)
 #else
@@ -203,13 +187,12 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
             return _rc;            \
     } while (0)
     // A stage's event is recorded by its kernel's own dispatch (sdr::launch_kernel, sdr_device.h): SDR_ARM hands the
-    // event to the next launch, SDR_DONE records it the ordinary way if no launch took it (stage left out, capture)
-    static const bool stop_events = !(getenv("SDR_STOP_EVENTS") && atoi(getenv("SDR_STOP_EVENTS")) == 0);
-    const bool ride = stop_events && !cap;
-#define SDR_ARM(k) (sdr::t_done_event = ride ? S.done[k] : nullptr)
+    // event to the next launch, SDR_DONE records it the ordinary way if no launch took it (stage left out).  Under
+    // capture no event is recorded at all.
+#define SDR_ARM(k) (sdr::t_done_event = cap ? nullptr : S.done[k])
 #define SDR_DONE(k)                                                                                   \
     do {                                                                                              \
-        if ((!ride || sdr::t_done_event) && !cap) {                                                   \
+        if (sdr::t_done_event && !cap) {                                                              \
             sdr::t_done_event = nullptr;                                                              \
             HIP_TRY(hipEventRecord(S.done[k], stream_of(k)));                                         \
         }                                                                                             \
@@ -222,20 +205,15 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
     // A caller that enqueues faster than the GPU works is soon more than RING batches ahead; then these events have
     // not happened yet at enqueue time and the FFT queue gets barrier packets: one per other stream (its last stage
     // stands for the stream), not one per stage - with nothing else running that was 0.200 -> 0.177 ms per step for a
-    // 0.166 ms kernel.  SDR_HOST_THROTTLE=1 (development) makes the HOST wait instead (the call blocks until the
-    // set is free, the FFT queue holds kernels only): 0.161 ms with nothing else running, but 0.237 against 0.234
-    // with the whole pipeline, where the FFT launches are spaced by the CUs the tail holds, not by their queue.
-    static const bool host_waits = getenv("SDR_HOST_THROTTLE") && atoi(getenv("SDR_HOST_THROTTLE")) != 0;
-    int max_slots = 0;
-    for (int i = 0; i < B; i++)
-        max_slots = std::max(max_slots, b->n_slots[i]);
+    // 0.166 ms kernel.  (The host waiting instead - the call blocking until the set is free, the FFT queue holding
+    // kernels only - was 0.161 ms with nothing else running, but 0.237 against 0.234 with the whole pipeline, where the
+    // FFT launches are spaced by the CUs the tail holds, not by their queue.)
     if (do_spectra) {
     // With bulk delivery on, the set's previous batch must have been delivered (or be parked) before its block is
     // written again - and a delivered batch is a finished one: every reader of the set is done, the queries below
     // succeed and the FFT queue gets no barrier packets at all (each costs the command processor microseconds between
     // two FFT kernels, and the FFT queue is the one that bounds the step).
-    static const bool park_first = !(getenv("SDR_PARK_FIRST") && atoi(getenv("SDR_PARK_FIRST")) == 0);
-    if (b->results_on && !cap && park_first) {
+    if (b->results_on && !cap) {
         const int prc = b->results->park(si);
         if (prc)
             return prc;
@@ -257,16 +235,8 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
                 continue;
             if (hipEventQuery(S.done[k]) == hipSuccess)
                 continue;
-            if (host_waits)
-                HIP_TRY(hipEventSynchronize(S.done[k]));
-            else
-                HIP_TRY(hipStreamWaitEvent(stream_of(sdr::K_FFT), S.done[k], 0));
+            HIP_TRY(hipStreamWaitEvent(stream_of(sdr::K_FFT), S.done[k], 0));
         }
-    }
-    if (b->results_on && !cap && !park_first) {
-        const int prc = b->results->park(si);
-        if (prc)
-            return prc;
     }
     if (cap && SDR_ON(sdr::K_FFT) && capture_k % RING == 0)  // the replay's cursors, in front of its first FFT
         HIP_TRY(launch_set_cursors(b->cursors.p + capture_k, CursorPack{}, stream_of(sdr::K_FFT)));
@@ -277,36 +247,25 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
         tap.wide = S.tapw.p;
         tap.used = S.tap_used.p;
         tap.steal = S.fft_ctr.p;
-        SDR_LAUNCH(sdr::K_FFT, sdr::launch_fft(b->logn, fmt, iq_dev, cur, b->tw.p, S.psd.p, n_frames, B, in_stride, stride, tap,
+        SDR_LAUNCH(sdr::K_FFT, sdr::launch_fft(b->logn, P.fft, fmt, iq_dev, cur, b->tw.p, S.psd.p, n_frames, B, in_stride, stride, tap,
                                                stream_of(sdr::K_FFT)));
     }
     SDR_DONE(sdr::K_FFT);
 
-    // noise floor (stateless per batch), then the rolling means -> thresholds, in batch order.
-    // Two ways (SDR_NOISE_PATH = scan | chains; scan unless told otherwise):
+    // noise floor (stateless per batch), then the rolling means -> thresholds, in batch order.  Two ways:
     //   scan    k_noise_scan.hip: ONE pass over the psd for FindNoiseFloor's sums and - where it pays - the bounds of the
     //           cumulations the batch completes; the reference's values where they are consumed (noise_cert.h), the
     //           literal loops for the few frames that cannot be certified;
     //   chains  k_noise.hip: the ordered float64 chains of rounds 1-4 (and k_cum_bound on the peaks stream).
-    static const bool scan_path = !(getenv("SDR_NOISE_PATH") && std::string(getenv("SDR_NOISE_PATH")) == "chains");
-    static const int force_exact = getenv("SDR_NOISE_FORCE_EXACT") ? atoi(getenv("SDR_NOISE_FORCE_EXACT")) : 0;  // (tests)
-    const int scan_count0 = b->cum_count;
-    int scan_slots = 1;
-    if (n_frames >= SDR_CUMULATION_SIZE - scan_count0)
-        scan_slots = 1 + (n_frames - (SDR_CUMULATION_SIZE - scan_count0) + SDR_CUMULATION_SIZE - 1) / SDR_CUMULATION_SIZE;  // (the last one may stay open)
-    if (cap)  // whatever cumulationCount the replayed batch starts at
-        scan_slots = sdr::chunks_completed(SDR_CUMULATION_SIZE - 1, n_frames) + 1;
-    const bool scan_bound = scan_path && sdr::cum_bound_pays(n_frames, B, N);
     SDR_AFTER(sdr::K_WINDOW_MEANS, sdr::K_FFT);
     {
         ProfScope ps(b, sdr::K_WINDOW_MEANS, stream_of(sdr::K_WINDOW_MEANS));
         SDR_ARM(sdr::K_WINDOW_MEANS);
-        if (scan_path) {
-            const sdr::CumGeom scg{N, stride, n_frames, scan_count0, b->max_chunks};
-            SDR_LAUNCH(sdr::K_WINDOW_MEANS, sdr::launch_psd_scan(S.psd.p, S.recs.p, S.cum_out.p, S.cum_part.p, cur, ng, scg, scan_slots, B, scan_bound,
-                                                                 force_exact, stream_of(sdr::K_WINDOW_MEANS)));
+        if (P.noise_scan) {
+            SDR_LAUNCH(sdr::K_WINDOW_MEANS, sdr::launch_psd_scan(S.psd.p, S.recs.p, S.cum_out.p, S.cum_part.p, cur, ng, cg, P.n_slots, B, P.bound_done,
+                                                                 P.scan_parts, P.force_exact, stream_of(sdr::K_WINDOW_MEANS)));
         } else {
-            SDR_LAUNCH(sdr::K_WINDOW_MEANS, sdr::launch_window_means(S.psd.p, S.win_mean.p, ng, n_frames, B, stride,
+            SDR_LAUNCH(sdr::K_WINDOW_MEANS, sdr::launch_window_means(S.psd.p, S.win_mean.p, ng, n_frames, B, stride, P.wm_wpb,
                                                                      stream_of(sdr::K_WINDOW_MEANS)));
         }
     }
@@ -315,8 +274,8 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
     {
         ProfScope ps(b, sdr::K_NOISE_STATS, stream_of(sdr::K_NOISE_STATS));
         SDR_ARM(sdr::K_NOISE_STATS);
-        if (!scan_path)  // (the scan kernel has finished the records itself: this stage launches nothing, its event is recorded below)
-            SDR_LAUNCH(sdr::K_NOISE_STATS, sdr::launch_noise_stats(S.psd.p, S.win_mean.p, S.recs.p, ng, n_frames, B, stride,
+        if (!P.noise_scan)  // (the scan kernel has finished the records itself: this stage launches nothing, its event is recorded below)
+            SDR_LAUNCH(sdr::K_NOISE_STATS, sdr::launch_noise_stats(S.psd.p, S.win_mean.p, S.recs.p, ng, n_frames, B, stride, P.var_mfma,
                                                                    stream_of(sdr::K_NOISE_STATS)));
     }
     SDR_DONE(sdr::K_NOISE_STATS);
@@ -399,33 +358,18 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
     }
 
     // dB projection + cumulation, peak scan (rx/receiver.go:404-409,459-460)
-    const int count0 = b->cum_count;
-    const int first_len = SDR_CUMULATION_SIZE - count0;
-    int n_slots_c = 1, n_chunks = 0;
-    if (n_frames >= first_len) {
-        n_chunks = 1 + (n_frames - first_len) / SDR_CUMULATION_SIZE;
-        const int rem = (n_frames - first_len) % SDR_CUMULATION_SIZE;
-        n_slots_c = n_chunks + (rem > 0 ? 1 : 0);
-    }
-    if (cap) {  // whatever cumulationCount the replayed batch starts at
-        n_chunks = sdr::chunks_completed(SDR_CUMULATION_SIZE - 1, n_frames);
-        n_slots_c = n_chunks + 1;
-    }
+    const int n_chunks = P.n_chunks;
     // (the scan wrote the bounds of the completed cumulations on the noise stream: the carry is added to slot 0's here)
-    static const bool scan_path_c = !(getenv("SDR_NOISE_PATH") && std::string(getenv("SDR_NOISE_PATH")) == "chains");
-    const bool scan_bound_done = scan_path_c && sdr::cum_bound_pays(n_frames, B, N);
     SDR_AFTER(sdr::K_CUMULATE, sdr::K_FFT);
-    if (scan_bound_done)
+    if (P.bound_done)
         SDR_AFTER(sdr::K_CUMULATE, sdr::K_WINDOW_MEANS);
     {
         ProfScope ps(b, sdr::K_CUMULATE, stream_of(sdr::K_CUMULATE));
         SDR_ARM(sdr::K_CUMULATE);
-        sdr::CumGeom cg{N, stride, n_frames, count0, b->max_chunks};
-        SDR_LAUNCH(sdr::K_CUMULATE, sdr::launch_cumulate(S.psd.p, b->db_tab.p, b->carry[0].p, b->carry[1].p, b->carry_cur,
-                                                         S.cum_out.p, S.cum_part.p, cur, cg, n_slots_c, B, scan_bound_done, stream_of(sdr::K_CUMULATE)));
+        SDR_LAUNCH(sdr::K_CUMULATE, sdr::launch_cumulate(S.psd.p, b->db_tab.p, b->carry[0].p, b->carry[1].p, b->carry_cur, S.cum_out.p, S.cum_part.p,
+                                                         cur, cg, P.n_slots, B, P.bound, P.bound_done, P.scan_parts, stream_of(sdr::K_CUMULATE)));
     }
     SDR_DONE(sdr::K_CUMULATE);
-    const int new_count = (count0 + n_frames) % SDR_CUMULATION_SIZE;
     SDR_AFTER(sdr::K_FIND_PEAKS, sdr::K_CUMULATE);
     if (!b->results_on)
         SDR_ARM(sdr::K_FIND_PEAKS);
@@ -437,12 +381,12 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
         // buffer, follows on the same stream)
         // the wide tap this batch's FFT left, if it was the kernel that leaves one (k_cum_refine reads the signals' columns there)
         sdr::FftTap wide_tap{nullptr, nullptr, max_slots, c.max_listeners};
-        if (S.tapw.p && sdr::fft_writes_wide_tap(b->logn, n_frames, B, max_slots)) {
+        if (P.fft.wide_tap) {
             wide_tap.wide = S.tapw.p;
             wide_tap.used = S.tap_used.p;
         }
         SDR_LAUNCH(sdr::K_FIND_PEAKS, sdr::launch_find_peaks(S.cum_out.p, S.psd.p, b->db_tab.p, b->carry[0].p, b->carry[1].p, b->carry_cur, S.recs.p,
-                                                             S.dev_peaks.p, S.peak_counts.p, cur, pg, n_frames, n_chunks, B, wide_tap,
+                                                             S.dev_peaks.p, S.peak_counts.p, cur, pg, n_frames, n_chunks, B, P.refine, wide_tap,
                                                              stream_of(sdr::K_FIND_PEAKS)));
     }
     if (b->results_on && SDR_ON(sdr::K_FIND_PEAKS)) {
@@ -478,9 +422,9 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
     // The carry buffer flips only when this batch wrote a new partial cumulation; if the batch ended
     // exactly on a chunk boundary the next batch starts from zero (count0 == 0 ignores the carry)
     b->last_carry_in = b->carry_cur;
-    if (new_count != 0)
+    if (P.new_count != 0)
         b->carry_cur ^= 1;
-    b->cum_count = new_count;
+    b->cum_count = P.new_count;
     b->last_set = si;
     b->last_frames = n_frames;
     b->last_chunks = n_chunks;

@@ -1,0 +1,195 @@
+// host/batch_plan.h — every choice the scheduler makes for one batch (process_device_body, capi_process.hip), made in one
+// place: which stream each kernel runs on, which FFT kernel runs, which noise-floor path, whether the cumulations are
+// bounded and refined, the slot and chunk counts.  The launchers receive these decisions as arguments and decide nothing.
+//
+// The environment switches that steer the pipeline are read here too, by read_switches(), once per bank (sdr_create).
+// They select a second implementation of a stage for the tests (tests/test_forced_paths.py) or are measurement knobs;
+// with none of them set every choice follows the batch's geometry.  Two test hooks stay outside, read at each call
+// because tests toggle them within one process: SDR_READ_CUM_RAW (sdr_read_cumulation) and SDR_SELF_CHECK_ORDER
+// (sdr_self_check, which has no bank).
+//
+// Pure C++: tests/host/test_batch_plan.cpp pins every rule at the boundaries where it switches, without a GPU.
+#pragma once
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+
+#include "../../../include/sdrainer_hip.h"
+
+namespace sdr {
+
+enum KernelId {
+    K_FFT = 0, K_WINDOW_MEANS, K_NOISE_STATS, K_THRESHOLDS, K_LISTEN_GATHER, K_CUMULATE, K_FIND_PEAKS, K_LISTEN_DECODE,
+    K_COUNT
+};
+// the bank's streams: four = the hardware queues HIP gives a process; with six streams created (two unused!) the step was
+// 0.49 ms instead of 0.25, with GPU_MAX_HW_QUEUES=8 and five or six in use 0.29-0.60
+enum Stage { S_FFT = 0, S_NOISE, S_LISTEN, S_PEAKS, N_STAGES };
+
+// k_fft_r32 serves at most this many listener slots: one per thread (fft_r32.h fft32::T)
+constexpr int kR32MaxTap = 512;
+
+struct Switches {
+    bool noise_scan = true;  // SDR_NOISE_PATH=chains: FindNoiseFloor by the ordered float64 chains of rounds 1-4 (k_noise.hip)
+    int force_exact = 0;     // SDR_NOISE_FORCE_EXACT=k: the scan's literal fallback for every frame (1) or every k-th one (tests)
+    int fft_r32 = -1;        // SDR_FFT_R32=0 / 1: N = 16384 never / always on k_fft_r32 (-1: by batch size)
+    int fft_fpw = 0;         // SDR_FFT_FPW: frames per workgroup of the 16-point kernels, 1 - 64 (0: the kernel's default)
+    int cum_bound = -1;      // SDR_CUM_BOUND=0 / 1: bound-and-refine never / always (-1: by batch size)
+    int refine_wide = -1;    // SDR_REFINE_WIDE=0 / 1: the refinement's workgroup shape (-1: by cumulations per batch)
+    int var_mfma = -1;       // SDR_VAR_MFMA=0 / 1: the chains' variance kernel (-1: by batch length)
+    int wm_wpb = 0;          // SDR_WM_WPB: windows per workgroup of the chains' window sums (0: launch_window_means' rule)
+    bool no_overlap = false;   // SDR_NO_OVERLAP=1: every stage on the caller's stream (kernel-by-kernel profiling)
+    bool graph_debug = false;  // SDR_GRAPH_DEBUG: host-side timings of every sdr_graph_launch on stderr
+    // -DSDR_DIAG builds only (tools/abl): SDR_DIAG_SKIP = bit mask of kernel ids not to launch, to see which stage holds the
+    // pipelined step up (results are wrong by construction); SDR_DIAG_PLAN = the stream of each kernel, one digit each
+    int diag_skip = 0;
+    int diag_plan[K_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1};  // (-1: the plan's own)
+};
+
+// a forced 0 / 1 (any value >= 0: on unless 0), or -1 when unset or negative
+inline int tri_state(const char *e)
+{
+    if (!e)
+        return -1;
+    const int v = atoi(e);
+    return v >= 0 ? (v != 0 ? 1 : 0) : -1;
+}
+
+inline Switches read_switches()
+{
+    Switches s;
+    const char *e;
+    if ((e = getenv("SDR_NOISE_PATH")))
+        s.noise_scan = strcmp(e, "chains") != 0;
+    if ((e = getenv("SDR_NOISE_FORCE_EXACT")))
+        s.force_exact = atoi(e);
+    if ((e = getenv("SDR_FFT_R32")))
+        s.fft_r32 = atoi(e) ? 1 : 0;
+    if ((e = getenv("SDR_FFT_FPW"))) {
+        const int v = atoi(e);
+        s.fft_fpw = v < 1 ? 1 : (v > 64 ? 64 : v);
+    }
+    s.cum_bound = tri_state(getenv("SDR_CUM_BOUND"));
+    s.refine_wide = tri_state(getenv("SDR_REFINE_WIDE"));
+    s.var_mfma = tri_state(getenv("SDR_VAR_MFMA"));
+    if ((e = getenv("SDR_WM_WPB")))
+        s.wm_wpb = atoi(e) > 0 ? atoi(e) : 0;  // (development)
+    e = getenv("SDR_NO_OVERLAP");
+    s.no_overlap = e && e[0] == '1';
+    s.graph_debug = getenv("SDR_GRAPH_DEBUG") != nullptr;
+#if defined(SDR_DIAG)
+    if ((e = getenv("SDR_DIAG_SKIP")))
+        s.diag_skip = atoi(e);
+    if ((e = getenv("SDR_DIAG_PLAN")))
+        for (int k = 0; k < K_COUNT && e[k] >= '0' && e[k] < '0' + N_STAGES; k++)
+            s.diag_plan[k] = e[k] - '0';
+#endif
+    return s;
+}
+
+// Which FFT kernel runs a batch, and how.
+struct FftChoice {
+    bool r32 = false;       // N = 16384 on k_fft_r32 instead of the 16-point k_fft_psd<14>
+    int fpw = 0;            // the 16-point kernels: frames per workgroup asked for (0: the kernel's default, launch_fft_t)
+    bool wide_tap = false;  // the kernel leaves the wide tap (psd at bin - 1, bin, bin + 1 of every listener: k_cum_refine reads it)
+};
+
+// N = 16384 has two kernels: k_fft_psd.hip's 16-point one and k_fft_r32.hip (512 threads x 32 points, the next frame
+// prefetched into registers), whose workgroups - one per CU - claim frames from a counter.  By default the 32-point kernel
+// runs from 1024 frames per launch on (measured by batch size) and while the listener slots fit its tap (one per thread).
+// sc16 input takes the same choice (k_fft_r32_sc16 or k_fft_psd_sc16<14>): the rule does not look at the format.
+// (bench.py restates the frame-count rule to name the kernel in its report.)
+inline FftChoice fft_choice(const Switches &sw, int n, int n_frames, int n_bands, int tap_n)
+{
+    FftChoice c;
+    c.r32 = n == 16384 && tap_n <= kR32MaxTap && (sw.fft_r32 == 1 || (sw.fft_r32 < 0 && (long)n_frames * n_bands >= 1024));
+    c.fpw = sw.fft_fpw;
+    c.wide_tap = c.r32 && tap_n > 0;
+    return c;
+}
+
+enum class Refine { NONE, NARROW, WIDE };
+
+struct BatchGeometry {
+    int n_bands, n, max_batch_frames, max_chunks;
+};
+
+struct BatchPlan {
+    int stream[K_COUNT];  // Stage of each KernelId
+    FftChoice fft;
+    bool noise_scan;   // k_psd_scan (else the chains: k_window_means -> k_noise_stats)
+    int force_exact;   // k_psd_scan's literal fallback (tests)
+    bool var_mfma;     // the chains' variance kernel: the matrix pipe (else two vector-ALU chain groups per workgroup)
+    int wm_wpb;        // the chains' window sums: windows per workgroup (0: launch_window_means' rule)
+    bool bound;        // the completed cumulations are bounded, and refined where FindPeaks looks (else every slot exact)
+    bool bound_done;   // ... and k_psd_scan forms the bound's unit counts (k_bound_finish finishes them)
+    int scan_parts;    // workgroups a slot's frames are dealt over by k_psd_scan; k_bound_finish adds as many partial counts
+    int n_slots;       // cumulation slots the batch touches: grid of k_psd_scan and k_cumulate
+    int n_chunks;      // cumulations the batch completes
+    int new_count;     // cumulationCount after the batch
+    Refine refine;     // the refinement's workgroup shape (NONE: no bound)
+};
+
+// One batch of n_frames frames that starts at cumulationCount count0, max_slots listener slots in use.  capturing: the
+// batch is being recorded into a graph (sdr_graph_capture), replayed later at whatever count0 and without stream changes.
+inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_frames, int count0, bool capturing, int max_slots)
+{
+    BatchPlan p;
+    // Which of the bank's four streams each kernel runs on.  The step is as long as the longest stream, and kernels that
+    // carry state from batch to batch (thresholds, decode, cumulate) must keep their stream so that the stream orders the
+    // batches.
+    const int plan[K_COUNT] = {/* fft */ S_FFT,        /* window means */ S_NOISE, /* noise stats */ S_NOISE, /* thresholds */ S_PEAKS,
+                               /* gather */ S_LISTEN,  /* cumulate */ S_PEAKS,     /* find peaks */ S_PEAKS,  /* decode */ S_LISTEN};
+    for (int k = 0; k < K_COUNT; k++)
+        p.stream[k] = plan[k];
+    // Small geometries (one band of N <= 8192, two of 4096 ...): the FFT of a batch is shorter than its decoders, whose time
+    // goes with the frames, not the samples - the listen stream is the longest, and the gather, which carries no state
+    // from batch to batch and so may run on any stream, moves behind the thresholds it waits for anyway (config 2:
+    // 0.206 -> 0.142 ms per 4096-frame step, 80 -> 118 GS/s; config 3 unchanged within a percent either way, config 5's
+    // share 10 % SLOWER with it: its peaks stream is the full one).  Not under capture: a replay's graphs are cut by stream.
+    if (!capturing && (long)g.n_bands * g.n <= 8192)
+        p.stream[K_LISTEN_GATHER] = S_PEAKS;
+    for (int k = 0; k < K_COUNT; k++)
+        if (sw.diag_plan[k] >= 0)
+            p.stream[k] = sw.diag_plan[k];
+
+    p.fft = fft_choice(sw, g.n, n_frames, g.n_bands, max_slots);
+
+    // noise floor: the one-pass scan (k_noise_scan.hip) unless the chains are asked for
+    p.noise_scan = sw.noise_scan;
+    p.force_exact = sw.force_exact;
+    // the chains' variance: two vector-ALU chain groups per workgroup for long batches (less CU time), the matrix-pipe
+    // kernel for short ones (less latency) - see k_noise.hip NS_GROUPS_VALU
+    p.var_mfma = sw.var_mfma >= 0 ? sw.var_mfma != 0 : n_frames < 4096;
+    p.wm_wpb = sw.wm_wpb;
+
+    // Bound-and-refine replaces the exact kernel's work with three launches on the peaks stream; on a short batch their fixed
+    // latencies (a refinement is a chain of a hundred scattered sector reads per candidate, whatever the batch) make that
+    // stream the longest of the four: config 3 at 2048 frames per batch 135-143 GS/s against 150 with every slot exact.  From
+    // 64 M samples per batch on it pays (config 3 at 8192 frames, config 5's share of 8 x 2048 x 8192).
+    p.bound = sw.cum_bound >= 0 ? sw.cum_bound != 0 : (double)n_frames * (double)g.n_bands * (double)g.n >= 64.0 * 1024.0 * 1024.0;
+    p.bound_done = p.noise_scan && p.bound;
+
+    // cumulations: the batch completes n_chunks and touches one more slot when it leaves one open.  A captured batch is
+    // replayed at any cumulationCount: its grids cover the most chunks a batch of this length can complete, plus the open one.
+    p.n_chunks = (count0 + n_frames) / SDR_CUMULATION_SIZE;
+    p.new_count = (count0 + n_frames) % SDR_CUMULATION_SIZE;
+    p.n_slots = p.n_chunks + (p.new_count != 0 ? 1 : 0);
+    if (capturing) {
+        p.n_chunks = (SDR_CUMULATION_SIZE - 1 + n_frames) / SDR_CUMULATION_SIZE;
+        p.n_slots = p.n_chunks + 1;
+    }
+    // two parts while the slots alone are fewer than a quarter of the CUs; from there on whole slots: with 16-byte loads a
+    // workgroup walks a frame in 1.6 us, and 83 fat workgroups hold less CU time than 166 - config 3: 205.5 -> 209.7 GS/s
+    p.scan_parts = (long)p.n_slots * g.n_bands < 64 ? 2 : 1;
+
+    // Spans of 4096 bins x 256 threads keep a cumulation's refinement - a latency chain of a hundred scattered sector reads -
+    // short where the peaks stream's length bounds the step (few cumulations per batch).  With many cumulations per batch
+    // what counts is the CU time the kernel HOLDS: four waves of a small workgroup hold a whole CU against the FFT's
+    // workgroups just as sixteen do, so a workgroup takes the whole row (10.9 -> CU-ms per 8192-frame step).
+    const bool wide = sw.refine_wide >= 0 ? sw.refine_wide != 0 : (g.n >= 4096 && (long)p.n_chunks * g.n_bands >= 64);
+    p.refine = !p.bound ? Refine::NONE : wide ? Refine::WIDE : Refine::NARROW;
+    return p;
+}
+
+}  // namespace sdr

@@ -997,19 +997,11 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, 4) void k_fft_psd_b(const flo
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-// Tuning knob, read once per process: SDR_FFT_FPW = frames per workgroup.
+// frames per workgroup when the plan asks for none (FftChoice::fpw, SDR_FFT_FPW)
 // (LDS behind the exchange area: the one-frame workgroup's copy of its listeners' bins)
 constexpr int kDefaultFpw = 1;  // in the pipeline short-lived workgroups win: 0.250 (1) / 0.253 (2) / 0.291 (4) / 0.294 ms (8) per step, standalone the other way round (0.174 / 0.166 / 0.165 / 0.164 ms)
-constexpr int kMaxDevices = 64;
-static int fft_fpw()
-{
-    static const int v = [] {
-        if (const char *e = getenv("SDR_FFT_FPW"))
-            return std::max(1, std::min(atoi(e), 64));
-        return kDefaultFpw;
-    }();
-    return v;
-}
+constexpr int kDefaultFpwB = 8;  // (the layout B kernel)
+static_assert(fft32::T == kR32MaxTap, "host/batch_plan.h: k_fft_r32 serves one listener slot per thread");
 
 // LDS of the layout B kernel: the cross-wave exchange's (padded) area, or the staging image plus the epilogue's tile
 template <int LOGN>
@@ -1017,84 +1009,49 @@ inline constexpr int kLdsBytesB = fft64::kLdsBytes<LOGN> > fft64::Plan<LOGN>::N 
                                       ? fft64::kLdsBytes<LOGN>
                                       : fft64::Plan<LOGN>::N * 8 + fft64::Plan<LOGN>::N * 2;
 
-// frames per workgroup of the layout B kernel: SDR_FFT_FPW overrides
-constexpr int kDefaultFpwB = 8;
-static int fft_fpw_b()
-{
-    static const int v = [] {
-        if (const char *e = getenv("SDR_FFT_FPW"))
-            return std::max(1, std::min(atoi(e), 64));
-        return kDefaultFpwB;
-    }();
-    return v;
-}
-
 template <int LOGN>
-static hipError_t launch_fft_t(InFormat fmt, const void *iq_in, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
-                               int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
+                               int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
     using PL = fft64::Plan<LOGN>;
     const float *iq = static_cast<const float *>(iq_in);
     if constexpr (PL::LB) {
         if (fmt != InFormat::F32)
             return hipErrorNotSupported;  // (layout B builds: sc16 input has no kernel at this size)
-        static std::once_flag b_attr_once[kMaxDevices];
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess)
-            return e;
-        if (dev < 0 || dev >= kMaxDevices)
-            return hipErrorInvalidDevice;
-        hipError_t attr_err = hipSuccess;
-        std::call_once(b_attr_once[dev], [&] {
-            attr_err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fft_psd_b<LOGN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           kLdsBytesB<LOGN>);
-        });
+        static LdsLimitOnce lds_once;
+        const hipError_t attr_err = raise_lds_limit_once(lds_once, {reinterpret_cast<const void *>(&k_fft_psd_b<LOGN>)}, kLdsBytesB<LOGN>);
         if (attr_err != hipSuccess)
             return attr_err;
         if (n_frames <= 0 || n_bands <= 0)
             return hipSuccess;
         // a workgroup's frames are consecutive (the next one is prefetched under the current one's first passes);
         // never fewer workgroups than the chip has CUs
-        int fpw = fft_fpw_b();
+        int fpw = fpw_asked > 0 ? fpw_asked : kDefaultFpwB;
         while (fpw > 1 && (long)((n_frames + fpw - 1) / fpw) * n_bands < 256)
             fpw /= 2;
         launch_kernel((k_fft_psd_b<LOGN>), dim3((n_frames + fpw - 1) / fpw, n_bands), dim3(PL::T), kLdsBytesB<LOGN>, stream, iq, cur, tw, psd,
                       in_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride);
         return hipGetLastError();
     } else {
-    // the > 64 KB dynamic LDS attribute is per device: set it once on each device a bank launches on
-    static std::once_flag attr_once[kMaxDevices];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess)
-        return e;
-    if (dev < 0 || dev >= kMaxDevices)
-        return hipErrorInvalidDevice;
-    hipError_t attr_err = hipSuccess;
-    std::call_once(attr_once[dev], [&] {
-        for (const void *k : {reinterpret_cast<const void *>(&k_fft_psd<LOGN, false>),
-                              reinterpret_cast<const void *>(&k_fft_psd<LOGN, true>),
-                              reinterpret_cast<const void *>(&k_fft_psd_sc16<LOGN>)}) {
-            const hipError_t ae = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, fft64::kLdsBytes<LOGN> + kMaxLdsTap * 4 + kPfSinkBytes);
-            if (ae != hipSuccess)
-                attr_err = ae;
-        }
-    });
+    static LdsLimitOnce lds_once;
+    const hipError_t attr_err = raise_lds_limit_once(lds_once,
+                                                     {reinterpret_cast<const void *>(&k_fft_psd<LOGN, false>), reinterpret_cast<const void *>(&k_fft_psd<LOGN, true>),
+                                                      reinterpret_cast<const void *>(&k_fft_psd_sc16<LOGN>)},
+                                                     fft64::kLdsBytes<LOGN> + kMaxLdsTap * 4 + kPfSinkBytes);
     if (attr_err != hipSuccess)
         return attr_err;
     if (n_frames <= 0 || n_bands <= 0)
         return hipSuccess;
     const unsigned tap_lds = tap.n > 0 && tap.n <= kMaxLdsTap ? ((tap.n * 4 + 255) & ~255) : 0;
     if (fmt == InFormat::SC16) {
-        // one frame per workgroup, always (SDR_FFT_FPW is the float32 kernel's)
+        // one frame per workgroup, always (FftChoice::fpw is the float32 kernel's)
         launch_kernel((k_fft_psd_sc16<LOGN>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, stream,
                       static_cast<const int16_t *>(iq_in), cur, tw, psd, in_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride);
         return hipGetLastError();
     }
     // a workgroup's frames are consecutive; never fewer workgroups than CUs can take (a short batch keeps one
     // frame per workgroup)
-    int fpw = fft_fpw();
+    int fpw = fpw_asked > 0 ? fpw_asked : kDefaultFpw;
     while (fpw > 1 && (long)((n_frames + fpw - 1) / fpw) * n_bands < 256)
         fpw /= 2;
     if (fpw > 1)
@@ -1108,55 +1065,34 @@ static hipError_t launch_fft_t(InFormat fmt, const void *iq_in, const BatchCurso
     }
 }
 
-// N = 16384 has two kernels: this file's 16-point one and k_fft_r32.hip (512 threads x 32 points, the next frame
-// prefetched into registers), whose workgroups - one per CU - claim frames from a counter.  SDR_FFT_R32 = 0 / 1 forces one
-// of them (tests); by default the 32-point kernel runs from 1024 frames per launch on (measured by batch size).  The bank's
-// twiddle buffer holds both kernels' tables, the 32-point kernel's behind the other.  sc16 input takes the same choice
-// (k_fft_r32_sc16 or k_fft_psd_sc16<14>): the switch and SDR_FFT_R32 do not look at the format.
-static int r32_mode()
-{
-    static const int v = [] {
-        if (const char *e = getenv("SDR_FFT_R32"))
-            return atoi(e) ? 1 : 0;
-        return -1;
-    }();
-    return v;
-}
-
-static bool use_r32(int logn, int n_frames, int n_bands, int tap_n)
-{
-    const int mode = r32_mode();
-    return logn == 14 && tap_n <= fft32::T && (mode == 1 || (mode < 0 && (long)n_frames * n_bands >= 1024));
-}
-bool fft_writes_wide_tap(int logn, int n_frames, int n_bands, int tap_n) { return tap_n > 0 && use_r32(logn, n_frames, n_bands, tap_n); }
-
-hipError_t launch_fft(int logn, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
-                      int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+// The bank's twiddle buffer for N = 16384 holds both kernels' tables, the 32-point kernel's behind the other.
+hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
+                      int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
     if (fmt != InFormat::F32 && fmt != InFormat::SC16)
         return hipErrorInvalidValue;
-    if (logn == 14) {
-        if (use_r32(logn, n_frames, n_bands, tap.n)) {
-            const fft64::cplx *tw32 = tw + fft64::Plan<14>::TW_TOTAL;
-            if (fmt == InFormat::SC16)
-                return launch_fft_r32_sc16(static_cast<const int16_t *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-            return launch_fft_r32(static_cast<const float *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-        }
+    if (fft.r32) {
+        if (logn != 14)
+            return hipErrorInvalidValue;
+        const fft64::cplx *tw32 = tw + fft64::Plan<14>::TW_TOTAL;
+        if (fmt == InFormat::SC16)
+            return launch_fft_r32_sc16(static_cast<const int16_t *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+        return launch_fft_r32(static_cast<const float *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
     }
     switch (logn) {
-    case 9: return launch_fft_t<9>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 10: return launch_fft_t<10>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 11: return launch_fft_t<11>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 12: return launch_fft_t<12>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 13: return launch_fft_t<13>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 14: return launch_fft_t<14>(fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 9: return launch_fft_t<9>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 10: return launch_fft_t<10>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 11: return launch_fft_t<11>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 12: return launch_fft_t<12>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 13: return launch_fft_t<13>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 14: return launch_fft_t<14>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
     default: return hipErrorInvalidValue;
     }
 }
-hipError_t launch_fft(int logn, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
+hipError_t launch_fft(int logn, FftChoice fft, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
                       int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
-    return launch_fft(logn, InFormat::F32, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    return launch_fft(logn, fft, InFormat::F32, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
 }
 
 int twiddle_count(int logn)

@@ -1015,7 +1015,7 @@ hipError_t launch_mfma_order_probe(unsigned *mismatches, int order, hipStream_t 
     return hipGetLastError();
 }
 
-hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, int n_frames, int n_bands, int stride,
+hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, int n_frames, int n_bands, int stride, int wpb_forced,
                                hipStream_t stream)
 {
     // (rounds 2 - 3, 2048-frame batches: config 3's 160 workgroups of one window each; two windows back to back per
@@ -1034,9 +1034,8 @@ hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, 
     if (!half && wpb < 4)
         wpb = 1;
     wpb = wpb < 1 ? 1 : (wpb > g.n_windows ? g.n_windows : wpb);
-    static const int wpb_env = getenv("SDR_WM_WPB") ? atoi(getenv("SDR_WM_WPB")) : 0;  // (development)
-    if (wpb_env > 0)
-        wpb = wpb_env > g.n_windows ? g.n_windows : wpb_env;
+    if (wpb_forced > 0)  // (SDR_WM_WPB, development)
+        wpb = wpb_forced > g.n_windows ? g.n_windows : wpb_forced;
 
     const dim3 grid(per_band, (g.n_windows + wpb - 1) / wpb, n_bands);
     if (half)
@@ -1047,13 +1046,11 @@ hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, 
     return hipGetLastError();
 }
 
+// mfma: the matrix-pipe kernel (less latency) rather than two vector-ALU chain groups per workgroup (less CU time): the plan
+// picks it for short batches (host/batch_plan.h)
 hipError_t launch_noise_stats(const float *psd, const double *win_mean, sdr_frame_rec *recs, NoiseGeom g, int n_frames,
-                              int n_bands, int stride, hipStream_t stream)
+                              int n_bands, int stride, bool mfma, hipStream_t stream)
 {
-    // long batches: two vector-ALU chain groups per workgroup (less CU time); short ones: the matrix-pipe kernel (less
-    // latency) - see NS_GROUPS_VALU
-    static const int force = getenv("SDR_VAR_MFMA") ? atoi(getenv("SDR_VAR_MFMA")) : -1;  // (development)
-    const bool mfma = force >= 0 ? force != 0 : n_frames < 4096;
     const int groups_of_64 = (n_frames + TILE - 1) / TILE;
     if (mfma)
         launch_kernel(k_noise_stats<true>, dim3(groups_of_64, n_bands), dim3(CHAIN_THREADS), 0, stream, psd, win_mean, recs, g, n_frames, stride);

@@ -404,17 +404,6 @@ hipError_t launch_noise_exact_check(const float *psd_band, sdr_frame_rec *recs_b
     return hipGetLastError();
 }
 
-// parts a slot's frames are dealt over (k_peaks.hip's k_bound_finish must add as many)
-int scan_parts(int n_slots, int n_bands)
-{
-    static const int forced = getenv("SDR_SCAN_PARTS") ? atoi(getenv("SDR_SCAN_PARTS")) : 0;  // (experiments: 1 or 2)
-    if (forced == 1 || forced == 2)
-        return forced;
-    // (two parts while the slots alone are fewer than a quarter of the CUs; from there on whole slots: with 16-byte loads a
-    // workgroup walks a frame in 1.6 us, and 83 fat workgroups hold less CU time than 166 - config 3: 205.5 -> 209.7 GS/s)
-    return (long)n_slots * n_bands < 64 ? 2 : 1;
-}
-
 static int scan_jmax(int window)
 {
     const int j = (window + 63) / 64;
@@ -422,10 +411,11 @@ static int scan_jmax(int window)
 }
 
 // One batch's noise floor: the FindNoiseFloor fields of every frame's record and (do_bound) the unit counts of every
-// cumulation the batch completes.  force_exact: see k_psd_scan (tests).  (A stage event armed by the caller rides on
+// cumulation the batch completes, a slot's frames dealt over `parts` workgroups (k_bound_finish adds as many partial counts:
+// both take the value from the batch's plan, host/batch_plan.h).  force_exact: see k_psd_scan (tests).  (A stage event armed by the caller rides on
 // the launch.)
 hipError_t launch_psd_scan(const float *psd, sdr_frame_rec *recs, float *cum_out, float *cum_part, const BatchCursor *cur, NoiseGeom ng,
-                           CumGeom cg, int n_slots, int n_bands, bool do_bound, int force_exact, hipStream_t stream)
+                           CumGeom cg, int n_slots, int n_bands, bool do_bound, int parts, int force_exact, hipStream_t stream)
 {
     if (cg.n_frames <= 0 || n_bands <= 0)
         return hipSuccess;
@@ -446,7 +436,7 @@ hipError_t launch_psd_scan(const float *psd, sdr_frame_rec *recs, float *cum_out
     const int edge_hi = g.edge + g.n_windows * g.window;
     const int n_items = g.n_windows + (do_bound ? (g.edge + g.piece - 1) / g.piece + (g.n - edge_hi + g.piece - 1) / g.piece : 0);
     const int waves = n_items < kScanMaxWaves ? n_items : kScanMaxWaves;
-    g.parts = scan_parts(n_slots, n_bands);
+    g.parts = parts;
     // without bounds: as many frames per workgroup as leave the chip about two workgroups per CU, at least eight
     g.fpw = 0;
     if (!do_bound) {
@@ -456,24 +446,12 @@ hipError_t launch_psd_scan(const float *psd, sdr_frame_rec *recs, float *cum_out
     }
     const unsigned lds = (unsigned)scan_lds_bytes(ng.n);
     // more than 64 KB of dynamic LDS needs the attribute, once per device and instantiation
-    static std::once_flag attr_once[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess)
-        return e;
-    if (dev < 0 || dev >= 64)
-        return hipErrorInvalidDevice;
-    hipError_t attr_err = hipSuccess;
-    std::call_once(attr_once[dev], [&] {
-        const int max_lds = scan_lds_bytes(16384);
-        for (const void *k : {reinterpret_cast<const void *>(&k_psd_scan<2>), reinterpret_cast<const void *>(&k_psd_scan<5>),
-                              reinterpret_cast<const void *>(&k_psd_scan<10>), reinterpret_cast<const void *>(&k_psd_scan<19>),
-                              reinterpret_cast<const void *>(&k_psd_scan<26>)}) {
-            const hipError_t ae = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-            if (ae != hipSuccess)
-                attr_err = ae;
-        }
-    });
+    static LdsLimitOnce lds_once;
+    const hipError_t attr_err = raise_lds_limit_once(lds_once,
+                                                     {reinterpret_cast<const void *>(&k_psd_scan<2>), reinterpret_cast<const void *>(&k_psd_scan<5>),
+                                                      reinterpret_cast<const void *>(&k_psd_scan<10>), reinterpret_cast<const void *>(&k_psd_scan<19>),
+                                                      reinterpret_cast<const void *>(&k_psd_scan<26>)},
+                                                     scan_lds_bytes(16384));
     if (attr_err != hipSuccess)
         return attr_err;
     // (graph mode: the grid must cover the slots of any cumulation phase - the kernel returns for slots beyond the batch)

@@ -190,9 +190,6 @@ __global__ __launch_bounds__(SDR_CUM_THREADS) __attribute__((amdgpu_num_vgpr(SDR
 #if !defined(SDR_BOUND_U)
 #define SDR_BOUND_U 8
 #endif
-#if !defined(SDR_BOUND_WGS)
-#define SDR_BOUND_WGS 64
-#endif
 constexpr int kBoundThreads = 1024;
 constexpr int kBoundLdsBytes = 96 * 1024;  // (reserved, not used: one workgroup per CU)
 typedef unsigned bound_u4 __attribute__((ext_vector_type(4)));
@@ -373,7 +370,7 @@ __global__ __launch_bounds__(kRefineThreads) void k_cum_refine(float *__restrict
         s_tapidx[i] = 0xffffu;
     __syncthreads();
     // (relies on l < n_tap <= 512: the process step passes the wide tap only when k_fft_r32 ran, which serves at most 512
-    // slots (fft_writes_wide_tap), and that kernel rewrites tap_used[0 .. min(tap_stride, 512)) at every launch - entries
+    // slots (FftChoice::wide_tap, host/batch_plan.h), and that kernel rewrites tap_used[0 .. min(tap_stride, 512)) at every launch - entries
     // beyond are -1 from the allocation and never current)
     if (tap_wide) {
         for (int l = tid; l < n_tap; l += T) {
@@ -639,19 +636,6 @@ __global__ __launch_bounds__(kPeakThreadsMax) void k_find_peaks(const float *__r
     }
 }
 
-// Bound-and-refine replaces the exact kernel's work with three launches on the peaks stream; on a short batch their fixed
-// latencies (a refinement is a chain of a hundred scattered sector reads per candidate, whatever the batch) make that
-// stream the longest of the four: config 3 at 2048 frames per batch 135-143 GS/s against 150 with every slot exact.  From
-// 64 M samples per batch on it pays (config 3 at 8192 frames, config 5's share of 8 x 2048 x 8192).  SDR_CUM_BOUND=0 / 1
-// forces one (development).
-bool cum_bound_pays(int n_frames, int n_bands, int n)
-{
-    static const int force = getenv("SDR_CUM_BOUND") ? atoi(getenv("SDR_CUM_BOUND")) : -1;
-    if (force >= 0)
-        return force != 0;
-    return (double)n_frames * (double)n_bands * (double)n >= 64.0 * 1024.0 * 1024.0;
-}
-
 // k_bound_finish - the bounds of the cumulations a batch completes from the unit counts k_psd_scan left in their rows
 // (one or two partial counts per bin: a slot's frames may have been dealt over two workgroups) and, for the first one -
 // slot 0 continues the cumulation carried in - the carry: gomath::cum_bound, as k_cum_bound forms it.
@@ -688,11 +672,12 @@ __global__ __launch_bounds__(256) void k_bound_finish(float *__restrict__ cum_ou
 // One batch's cumulation work, on `stream`: bounds of the cumulations it completes, the exact carry of the one it leaves
 // open.  (A stage event armed by the caller rides on the last launch.)
 hipError_t launch_cumulate(const float *psd, const void *db_tab, float *carry0, float *carry1, int carry_in, float *cum_out,
-                           const float *cum_part, const BatchCursor *cur, CumGeom g, int n_slots, int n_bands, bool bound_done, hipStream_t stream)
+                           const float *cum_part, const BatchCursor *cur, CumGeom g, int n_slots, int n_bands, bool bound, bool bound_done,
+                           int parts, hipStream_t stream)
 {
     const double inv_n2 = 1.0 / ((double)g.n * (double)g.n);
     const int threads = g.n < SDR_CUM_THREADS ? g.n : SDR_CUM_THREADS;
-    if (!cum_bound_pays(g.n_frames, n_bands, g.n)) {  // short batches: every slot exact, one launch (as rounds 1-3)
+    if (!bound) {  // short batches: every slot exact, one launch (as rounds 1-3)
         launch_kernel(k_cumulate, dim3((g.n + threads - 1) / threads, n_slots, n_bands), dim3(threads), 0, stream, psd, db_tab, carry0, carry1,
                       carry_in, cum_out, static_cast<float *>(nullptr), cur, g, 0, 0, inv_n2);
         return hipGetLastError();
@@ -703,22 +688,12 @@ hipError_t launch_cumulate(const float *psd, const void *db_tab, float *carry0, 
     t_done_event = nullptr;
     if (bound_done) {
         hipLaunchKernelGGL(k_bound_finish, dim3((g.n + 255) / 256, n_slots, n_bands), dim3(256), 0, stream, cum_out, cum_part,
-                           scan_parts(n_slots, n_bands), carry0, carry1, carry_in, cur, g, a128, per_frame);
+                           parts, carry0, carry1, carry_in, cur, g, a128, per_frame);
     } else {
-        static std::once_flag attr_once[64];
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess)
-            return e;
-        if (dev < 0 || dev >= 64)
-            return hipErrorInvalidDevice;
-        hipError_t attr_err = hipSuccess;
-        std::call_once(attr_once[dev], [&] {
-            attr_err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cum_bound), hipFuncAttributeMaxDynamicSharedMemorySize, kBoundLdsBytes);
-        });
+        static LdsLimitOnce lds_once;
+        const hipError_t attr_err = raise_lds_limit_once(lds_once, {reinterpret_cast<const void *>(&k_cum_bound)}, kBoundLdsBytes);
         if (attr_err != hipSuccess)
             return attr_err;
-        static const int wgs_env = getenv("SDR_BOUND_WGS") ? atoi(getenv("SDR_BOUND_WGS")) : SDR_BOUND_WGS;  // (development)
         const int threads = (g.n / 4) < kBoundThreads ? g.n / 4 : kBoundThreads;
         const int blocks = (g.n / 4 + threads - 1) / threads, items = n_bands * n_slots * blocks;
         // as few workgroups as keep the kernel a fraction of the batch's FFT time (the peaks stream must not become the
@@ -728,8 +703,6 @@ hipError_t launch_cumulate(const float *psd, const void *db_tab, float *carry0, 
         int rounds = (int)(batch_samples / (2048.0 * 16384.0) + 0.5);
         rounds = rounds < 1 ? 1 : (rounds > 5 ? 5 : rounds);
         int wgs = (items + rounds - 1) / rounds;
-        if (getenv("SDR_BOUND_WGS"))
-            wgs = wgs_env;
         wgs = wgs < 1 ? 1 : (wgs > items ? items : wgs);
         hipLaunchKernelGGL(k_cum_bound, dim3(wgs), dim3(threads), kBoundLdsBytes, stream, psd, carry0, carry1, carry_in, cum_out, cur, g, n_slots,
                            n_bands, a128, per_frame);
@@ -761,48 +734,29 @@ hipError_t launch_spectrum_row(const float *psd_row, float *out, int n, hipStrea
 
 hipError_t launch_find_peaks(float *cum, const float *psd, const void *db_tab, const float *carry0, const float *carry1, int carry_in,
                              const sdr_frame_rec *recs, DevPeak *peaks, int *counts, const BatchCursor *cur, PeakGeom g, int n_frames,
-                             int n_chunks, int n_bands, FftTap tap, hipStream_t stream)
+                             int n_chunks, int n_bands, Refine refine, FftTap tap, hipStream_t stream)
 {
     if (n_chunks == 0)
         return hipSuccess;
     const int words = g.n >> 6;
     const unsigned lds = (unsigned)((size_t)g.n * 4 + (size_t)words * 16 + (size_t)(words + 1) * 4);
     // more than 64 KB of dynamic LDS needs the attribute, once per device
-    static std::once_flag attr_once[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess)
-        return e;
-    if (dev < 0 || dev >= 64)
-        return hipErrorInvalidDevice;
-    hipError_t attr_err = hipSuccess;
-    std::call_once(attr_once[dev], [&] {
-        attr_err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_find_peaks), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       16384 * 4 + 256 * 16 + 257 * 4);
-    });
+    static LdsLimitOnce lds_once;
+    const hipError_t attr_err = raise_lds_limit_once(lds_once, {reinterpret_cast<const void *>(&k_find_peaks)}, 16384 * 4 + 256 * 16 + 257 * 4);
     if (attr_err != hipSuccess)
         return attr_err;
     // the exact cumulation where the scan will look, then the scan (a stage event armed by the caller rides on the scan)
     const hipEvent_t done = t_done_event;
     t_done_event = nullptr;
     const double inv_n2 = 1.0 / ((double)g.n * (double)g.n);
-    if (cum_bound_pays(n_frames, n_bands, g.n))  // (otherwise k_cumulate left every row exact)
-    {
-        // Spans of 4096 bins x 256 threads keep a cumulation's refinement - a latency chain of a hundred scattered sector
-        // reads - short where the peaks stream's length bounds the step (few cumulations per batch).  With many
-        // cumulations per batch what counts is the CU time the kernel HOLDS: four waves of a small workgroup hold a whole
-        // CU against the FFT's workgroups just as sixteen do, so a workgroup takes the whole row (10.9 -> CU-ms per
-        // 8192-frame step; SDR_REFINE_WIDE = 0 / 1 forces one).
-        static const int wide_env = getenv("SDR_REFINE_WIDE") ? atoi(getenv("SDR_REFINE_WIDE")) : -1;
-        const bool wide = wide_env >= 0 ? wide_env != 0 : (g.n >= 4096 && (long)n_chunks * n_bands >= 64);
-        if (wide)
-            hipLaunchKernelGGL((k_cum_refine<16384, 1024>), dim3(n_chunks, (g.n + 16383) / 16384, n_bands), dim3(1024), 0, stream, cum, psd, db_tab,
-                               carry0, carry1, carry_in, recs, cur, g, n_frames, inv_n2, tap.wide, tap.used, tap.n, tap.stride);
-        else
-            hipLaunchKernelGGL((k_cum_refine<kRefineSpan, kRefineThreads>), dim3(n_chunks, (g.n + kRefineSpan - 1) / kRefineSpan, n_bands),
-                               dim3(kRefineThreads), 0, stream, cum, psd, db_tab, carry0, carry1, carry_in, recs, cur, g, n_frames, inv_n2, tap.wide,
-                               tap.used, tap.n, tap.stride);
-    }
+    // (Refine::NONE: k_cumulate left every row exact)
+    if (refine == Refine::WIDE)
+        hipLaunchKernelGGL((k_cum_refine<16384, 1024>), dim3(n_chunks, (g.n + 16383) / 16384, n_bands), dim3(1024), 0, stream, cum, psd, db_tab,
+                           carry0, carry1, carry_in, recs, cur, g, n_frames, inv_n2, tap.wide, tap.used, tap.n, tap.stride);
+    else if (refine == Refine::NARROW)
+        hipLaunchKernelGGL((k_cum_refine<kRefineSpan, kRefineThreads>), dim3(n_chunks, (g.n + kRefineSpan - 1) / kRefineSpan, n_bands),
+                           dim3(kRefineThreads), 0, stream, cum, psd, db_tab, carry0, carry1, carry_in, recs, cur, g, n_frames, inv_n2, tap.wide,
+                           tap.used, tap.n, tap.stride);
     t_done_event = done;
     const int threads = g.n < kPeakThreadsMax ? g.n : kPeakThreadsMax;
     launch_kernel(k_find_peaks, dim3(n_chunks, n_bands), dim3(threads), lds, stream, static_cast<const float *>(cum), recs, peaks, counts, cur, g,

@@ -4,10 +4,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <initializer_list>
+#include <mutex>
 
 #include "../../include/sdrainer_hip.h"
 #include "cw_decoder.h"
 #include "fft_f64.h"
+#include "host/batch_plan.h"
 
 namespace sdr {
 
@@ -108,11 +111,6 @@ struct ResultsLayout {
     size_t off_peak_counts, off_peaks, off_edge_counts, off_edges, off_text_counts, off_text, off_text_frames, off_drops, bytes;
 };
 
-enum KernelId {
-    K_FFT = 0, K_WINDOW_MEANS, K_NOISE_STATS, K_THRESHOLDS, K_LISTEN_GATHER, K_CUMULATE, K_FIND_PEAKS, K_LISTEN_DECODE,
-    K_COUNT
-};
-
 // A stage's completion event can ride on the kernel's own dispatch packet (hipExtLaunchKernelGGL's stopEvent)
 // instead of a hipEventRecord behind the kernel.  The record is a barrier packet of its own: the queue's next kernel
 // waits for the command processor to retire it, which on the FFT queue was 27-36 us per batch with nothing running
@@ -130,6 +128,32 @@ inline void launch_kernel(F kernel, dim3 grid, dim3 block, unsigned lds_bytes, h
         hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
 }
 
+// More than 64 KB of dynamic LDS needs the kernel attribute, which is per device: set it once on each device a bank
+// launches on, for every kernel of one launcher.  `once` is that launcher's (a function-local static); the call that
+// sets it returns what hipFuncSetAttribute said (the last failure), later calls on that device return hipSuccess.
+struct LdsLimitOnce {
+    static constexpr int kMaxDevices = 64;
+    std::once_flag dev[kMaxDevices];
+};
+inline hipError_t raise_lds_limit_once(LdsLimitOnce &once, std::initializer_list<const void *> kernels, int bytes)
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess)
+        return e;
+    if (dev < 0 || dev >= LdsLimitOnce::kMaxDevices)
+        return hipErrorInvalidDevice;
+    hipError_t attr_err = hipSuccess;
+    std::call_once(once.dev[dev], [&] {
+        for (const void *k : kernels) {
+            const hipError_t ae = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+            if (ae != hipSuccess)
+                attr_err = ae;
+        }
+    });
+    return attr_err;
+}
+
 // The listeners' bins of every band and where their psd values go (k_fft_psd.hip "The tap").
 struct FftTap {
     const int32_t *bins;  // [band][stride], -1 = free slot
@@ -144,10 +168,10 @@ struct FftTap {
     uint32_t *steal = nullptr;
 };
 
-// iq: [band][in_stride frames][N] samples of format fmt (float32 pairs or sc16 words)
-hipError_t launch_fft(int logn, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
-                      int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream);
-hipError_t launch_fft(int logn, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
+// iq: [band][in_stride frames][N] samples of format fmt (float32 pairs or sc16 words); `fft` picks the kernel (host/batch_plan.h)
+hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
+                      int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream);
+hipError_t launch_fft(int logn, FftChoice fft, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
                       int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream);  // (float32)
 int twiddle_count(int logn);
 void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx *out);
@@ -159,10 +183,11 @@ hipError_t launch_fft_r32_sc16(const int16_t *iq, const BatchCursor *cur, const 
                                int in_stride, int out_stride, FftTap tap, hipStream_t stream);
 int r32_twiddle_count();
 void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out);
-hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, int n_frames, int n_bands, int stride,
+// wpb_forced: windows per workgroup (0: the launcher's rule); mfma: the matrix-pipe variance kernel (host/batch_plan.h)
+hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, int n_frames, int n_bands, int stride, int wpb_forced,
                                hipStream_t stream);
 hipError_t launch_noise_stats(const float *psd, const double *win_mean, sdr_frame_rec *recs, NoiseGeom g, int n_frames,
-                              int n_bands, int stride, hipStream_t stream);
+                              int n_bands, int stride, bool mfma, hipStream_t stream);
 hipError_t launch_mfma_order_probe(unsigned *mismatches, int order, hipStream_t stream);  // k_noise.hip: sdr_self_check
 hipError_t launch_thresholds(sdr_frame_rec *recs, BandState *st, int n_frames, int n_bands, int stride,
                              hipStream_t stream);
@@ -176,16 +201,15 @@ hipError_t launch_listen_decode(ListenerSlot *slots, const uint16_t *morse, cons
 hipError_t launch_listener_stop(ListenerSlot *slot, const uint16_t *morse, uint32_t *text, uint32_t *text_frames, int text_cap,
                                 uint32_t frame, DropCounters *drops, hipStream_t stream);
 hipError_t launch_set_debounce(ListenerSlot *slots, int n, int threshold, hipStream_t stream);
-// bound_done: k_psd_scan has written the bounds of the completed cumulations (slot 0's as its raw unit count: the carry
-// is added here, on the stream the carry is produced on)
+// bound: the completed cumulations are bounded (else every slot exact); bound_done: k_psd_scan has written their unit counts
+// in `parts` partial rows (slot 0's without the carry: it is added here, on the stream the carry is produced on)
 hipError_t launch_cumulate(const float *psd, const void *db_tab, float *carry0, float *carry1, int carry_in, float *cum_out,
-                           const float *cum_part, const BatchCursor *cur, CumGeom g, int n_slots, int n_bands, bool bound_done, hipStream_t stream);
-int scan_parts(int n_slots, int n_bands);
-bool cum_bound_pays(int n_frames, int n_bands, int n);
+                           const float *cum_part, const BatchCursor *cur, CumGeom g, int n_slots, int n_bands, bool bound, bool bound_done,
+                           int parts, hipStream_t stream);
 // k_noise_scan.hip: the FindNoiseFloor fields of every frame's record, certified or literal, and (do_bound) the unit counts
-// of the completed cumulations - one kernel
+// of the completed cumulations, a slot's frames dealt over `parts` workgroups - one kernel
 hipError_t launch_psd_scan(const float *psd, sdr_frame_rec *recs, float *cum_out, float *cum_part, const BatchCursor *cur, NoiseGeom ng,
-                           CumGeom cg, int n_slots, int n_bands, bool do_bound, int force_exact, hipStream_t stream);
+                           CumGeom cg, int n_slots, int n_bands, bool do_bound, int parts, int force_exact, hipStream_t stream);
 hipError_t launch_noise_exact_check(const float *psd_band, sdr_frame_rec *recs_band, NoiseGeom ng, int n_frames, unsigned *mismatches,
                                     hipStream_t stream);
 hipError_t launch_spectrum_row(const float *psd_row, float *out, int n, hipStream_t stream);
@@ -204,9 +228,7 @@ hipError_t launch_unpack_be16(const uint8_t *raw, float *out, size_t n_values, h
 hipError_t launch_unpack_sc16(const int16_t *raw, float *out, size_t n_values, hipStream_t stream);  // little-endian int16 values
 hipError_t launch_find_peaks(float *cum, const float *psd, const void *db_tab, const float *carry0, const float *carry1, int carry_in,
                              const sdr_frame_rec *recs, DevPeak *peaks, int *counts, const BatchCursor *cur, PeakGeom g, int n_frames,
-                             int n_chunks, int n_bands, FftTap tap, hipStream_t stream);  // tap: .wide / .used / .n / .stride of this batch's FFT (or null)
-// does launch_fft, called like this, leave the wide tap (k_fft_r32 does; the sixteen-point kernels do not)?
-bool fft_writes_wide_tap(int logn, int n_frames, int n_bands, int tap_n);
+                             int n_chunks, int n_bands, Refine refine, FftTap tap, hipStream_t stream);  // tap: .wide / .used / .n / .stride of this batch's FFT (or null)
 hipError_t launch_cumulation_row(const float *psd_band, const void *db_tab, const float *carry_in_band, float *row_out, CumGeom g, int slot,
                                  hipStream_t stream);
 

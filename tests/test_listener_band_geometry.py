@@ -240,9 +240,9 @@ class Case:
 @pytest.mark.parametrize("slots", [512, 513])
 def test_fft_r32_slot_limit(capi, slots):
     """N = 16384, 256 keyed carriers and `slots` listeners, two 1024-frame batches (n_frames * n_bands >= 1024, so the
-    frame count alone would pick k_fft_r32).  use_r32 (k_fft_psd.hip:1026, `tap_n <= fft32::T`) selects k_fft_r32 at
+    frame count alone would pick k_fft_r32).  fft_choice (host/batch_plan.h, `tap_n <= kR32MaxTap`) selects k_fft_r32 at
     512 slots - register tap, wide tap and tap_used written, and k_cum_refine reading them (capi_process.hip:439,
-    fft_writes_wide_tap) - and the one-frame k_fft_psd<14> with its LDS tap at 513, where k_cum_refine reads the psd.
+    FftChoice::wide_tap) - and the one-frame k_fft_psd<14> with its LDS tap at 513, where k_cum_refine reads the psd.
     max_listeners is 600 in both, so tap_stride > 512 and the tap_used entries past 512 exist.  513 slots also need a
     ninth gather row (k_listen.hip:709, grid.y = (n_slots + 63) / 64)."""
     c = Case(16384, 1, 256, slots, [("batch", 1024), ("batch", 1024)], seed=6100 + slots, max_listeners=600)
@@ -252,7 +252,7 @@ def test_fft_r32_slot_limit(capi, slots):
 # -- 2. crossing 512 slots inside a stream ---------------------------------------------------------------------------------
 
 def test_crossing_512_slots_by_attach_then_holes(capi):
-    """N = 16384: a 1024-frame batch at 512 slots (k_fft_r32, k_fft_psd.hip:1026 use_r32), sdr_attach of a 513th
+    """N = 16384: a 1024-frame batch at 512 slots (k_fft_r32, host/batch_plan.h fft_choice), sdr_attach of a 513th
     listener, a batch at 513 slots (k_fft_psd<14>: the pool is a high-water mark, capi_bank.hip:421), then three listeners
     detached - holes under the high-water mark, still 513 slots and still k_fft_psd<14> - and a third batch.  The
     cumulation and every decoder run across both switches."""
@@ -266,7 +266,7 @@ def test_crossing_512_slots_inside_a_deferred_batch(capi):
     """N = 16384: a deferred 1024-frame batch whose FFT runs at 512 slots (k_fft_r32, wide tap), then sdr_attach_at
     binds listeners 513 and 514 at the cumulation boundaries 300 and 700 inside it, so its listen half gathers 514 slots
     (k_listen.hip:709, a ninth gather row; k_listen.hip:67, frames before tapped_from from the retained psd rows); the
-    next deferred batch runs k_fft_psd<14> (k_fft_psd.hip:1026 use_r32: tap_n > fft32::T) with every listener on the tap."""
+    next deferred batch runs k_fft_psd<14> (host/batch_plan.h fft_choice: tap_n > kR32MaxTap) with every listener on the tap."""
     steps = [("defer", 1024, [(0, 4000, 300), (0, 9001, 700)]), ("defer", 1024, [])]
     c = Case(16384, 1, 256, 512, steps, seed=6300, max_listeners=600)
     c.run(capi).close()
@@ -280,7 +280,7 @@ def test_lds_tap_capacity(capi, n, listeners):
     n_tap <= kMaxLdsTap (k_fft_psd.hip:519 `lds_tap`, and the dynamic LDS size at :1003) and drains the tap from the
     stored psd row past it (:635, tap_frame).  4096 and 4097 listeners on one band of N = 8192 in two 512-frame batches,
     and 4100 at N = 16384 in two 1024-frame batches: the frame count would select k_fft_r32 there, and it is the slot
-    count (:1026 use_r32, tap_n > fft32::T) that puts the tap on k_fft_psd<14> instead.  64 or 65 gather rows."""
+    count (fft_choice, tap_n > kR32MaxTap) that puts the tap on k_fft_psd<14> instead.  64 or 65 gather rows."""
     frames = 1024 if n == 16384 else 512
     c = Case(n, 1, 256, listeners, [("batch", frames), ("batch", frames)], seed=6400 + listeners)
     c.run(capi).close()
@@ -328,7 +328,7 @@ def test_config5_whole_on_one_gpu(capi):
 
 
 def test_fft_r32_claim_counters_beyond_8_bands(capi):
-    """k_fft_r32 on 24 bands x N = 16384 x 64-frame batches (k_fft_psd.hip:1026 use_r32: 64 * 24 >= 1024 frames per
+    """k_fft_r32 on 24 bands x N = 16384 x 64-frame batches (host/batch_plan.h fft_choice: 64 * 24 >= 1024 frames per
     launch, 16 slots): a claim counter pair per band (k_fft_r32.hip:289 `steal + 2 * blockIdx.y`), put back to zero by
     each band's last workgroup (:574), over two launches."""
     c = Case(16384, 24, 16, 16, [("batch", 64), ("batch", 64)], seed=6600, free_last=False)

@@ -110,7 +110,9 @@ int main(int argc, char **argv)
         }
         CK(hipMemcpy(iq, x.data(), x.size() * 4, hipMemcpyHostToDevice));
     }
-    auto launch = [&](hipStream_t st) { return sdr::launch_fft(logn, iq, nullptr, tw, pd, frames, bands, frames, frames, tap, st); };
+    // the library's choice for this batch (SDR_FFT_R32 / SDR_FFT_FPW honoured as in the pipeline)
+    const sdr::FftChoice choice = sdr::fft_choice(sdr::read_switches(), N, frames, bands, n_tap);
+    auto launch = [&](hipStream_t st) { return sdr::launch_fft(logn, choice, iq, nullptr, tw, pd, frames, bands, frames, frames, tap, st); };
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));

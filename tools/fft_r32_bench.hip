@@ -65,7 +65,6 @@ int main(int argc, char **argv)
     std::vector<fft64::cplx> h16((size_t)sdr::twiddle_count(logn)), h32((size_t)sdr::r32_twiddle_count());
     sdr::build_twiddles(logn, wre.data(), wim.data(), h16.data());
     sdr::r32_build_twiddles(wre.data(), wim.data(), h32.data());
-    setenv("SDR_FFT_R32", "0", 1);  // sdr::launch_fft below = the 16-point kernel
     fft64::cplx *tw16, *tw32;
     float *iq, *pd16, *pd32;
     const size_t total = (size_t)frames * bands;
@@ -125,7 +124,9 @@ int main(int argc, char **argv)
         }
         CK(hipMemcpy(iq, x.data(), x.size() * 4, hipMemcpyHostToDevice));
     }
-    auto launch16 = [&](hipStream_t st) { return sdr::launch_fft(logn, iq, nullptr, tw16, pd16, frames, bands, frames, frames, tap16, st); };
+    sdr::FftChoice c16;  // the 16-point kernel (SDR_FFT_FPW honoured as in the pipeline)
+    c16.fpw = sdr::read_switches().fft_fpw;
+    auto launch16 = [&](hipStream_t st) { return sdr::launch_fft(logn, c16, iq, nullptr, tw16, pd16, frames, bands, frames, frames, tap16, st); };
     auto launch32 = [&](hipStream_t st) { return sdr::launch_fft_r32(iq, nullptr, tw32, pd32, frames, bands, frames, frames, tap32, st); };
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
