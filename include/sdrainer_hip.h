@@ -87,7 +87,7 @@ typedef struct sdr_config {
     int32_t struct_size;      /* = sizeof(sdr_config), ABI guard                                  */
     int32_t n_bands;          /* independent receivers in this bank                               */
     int32_t sample_rate;      /* Receiver.Start(sampleRate, blockSize)                            */
-    int32_t block_size;       /* complex samples per frame; power of two in [512, 16384]          */
+    int32_t block_size;       /* complex samples per frame; power of two in [512, 65536]          */
     int32_t edge_width;       /* bins ignored at both spectrum edges (default 70)                 */
     float peak_threshold;     /* dB over the noise floor for the peak scan (default 15)           */
     int32_t signal_debounce;  /* BoolDebouncer threshold of new listeners (default 1)             */

@@ -95,6 +95,7 @@ struct BatchSet {
     DevBuf<float> tapw;               // [band][max_batch][L][4] psd at bin - 1, bin, bin + 1, 0 (k_fft_r32's wide tap; N = 16384 only)
     DevBuf<int32_t> tap_used;         // [band][L] the bins tapw was taken at (-1 = none)
     DevBuf<uint32_t> fft_ctr;         // [band][2] k_fft_r32's frame counters (zeroed here; each launch leaves them zero)
+    DevBuf<fft64::cplx> fft_scratch;  // [band][group frames][N] k_fft_2p's intermediate (N = 32768 / 65536 only)
     DevBuf<double> win_mean;          // [band][max_batch][10] (the chain kernels of SDR_NOISE_PATH=chains only)
     DevBuf<sdr_frame_rec> recs;       // [band][max_batch]
     DevBuf<uint64_t> raw_bits, bits;  // [band][L][bit_words] before / after the debouncer
@@ -117,6 +118,7 @@ struct BatchSet {
         tapw.release();
         tap_used.release();
         fft_ctr.release();
+        fft_scratch.release();
         win_mean.release();
         cum_part.release();
         recs.release();

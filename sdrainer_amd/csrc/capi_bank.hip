@@ -84,6 +84,9 @@ hipError_t alloc_set(sdr_bank *b, BatchSet &S)
             e = S.tap_used.alloc(B * std::max<size_t>(L, 1), 0xff);
         SET_ALLOC(S.fft_ctr, B * 2);
     }
+    // N = 32768 / 65536 (k_fft_2p.hip): one frame group's float64 intermediate of every band.  Per set, so that the FFT
+    // launches of replays in flight at the same time (graph mode) never share it.
+    SET_ALLOC(S.fft_scratch, B * (size_t)sdr::fft2p_group_frames(b->sw, c.block_size, c.n_bands, c.max_batch_frames) * N);
     SET_ALLOC(S.win_mean, B * F * 10);
     SET_ALLOC(S.recs, B * F);
     SET_ALLOC(S.raw_bits, B * L * (size_t)b->bit_words);
@@ -182,8 +185,8 @@ int sdr_create(const sdr_config *cfg, sdr_bank **out)
     if (cfg->struct_size != (int32_t)sizeof(sdr_config))
         return fail(SDR_ERR_BAD_ARG, "sdr_config.struct_size mismatch (ABI)");
     const int N = cfg->block_size;
-    if (N < 512 || N > 16384 || (N & (N - 1)))
-        return fail(SDR_ERR_BAD_SIZE, "block_size must be a power of two in [512, 16384]");
+    if (N < 512 || N > 65536 || (N & (N - 1)))
+        return fail(SDR_ERR_BAD_SIZE, "block_size must be a power of two in [512, 65536]");
     if (cfg->n_bands < 1 || cfg->sample_rate < 1 || cfg->max_batch_frames < 1 || cfg->max_listeners < 0 ||
         cfg->max_peaks < 1)
         return fail(SDR_ERR_BAD_ARG, "non-positive geometry");
@@ -230,8 +233,9 @@ int sdr_create(const sdr_config *cfg, sdr_bank **out)
     // exist took the queue one of them was to get - two of the bank's streams then shared a queue and graph mode, whose
     // replays overlap stream against stream, ran at 101 instead of 156 GS/s (config 3; round 4, found by bisection).
     // Only the chain kernels (SDR_NOISE_PATH=chains) need it: the default noise path (k_noise_scan.hip) does not use the
-    // matrix pipe, so a bank on it depends on no undocumented behaviour and is not probed.
-    if (!b->sw.noise_scan) {
+    // matrix pipe, so a bank on it depends on no undocumented behaviour and is not probed; nor is a bank of N > 16384, whose
+    // default chains keep their variance on the vector ALU (host/batch_plan.h var_mfma_at).
+    if (sdr::may_use_matrix_pipe(b->sw, N)) {
         const int sc = self_check_once(cfg->device_id);
         if (sc != SDR_OK) {
             sdr_destroy(b);

@@ -247,6 +247,7 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
         tap.wide = S.tapw.p;
         tap.used = S.tap_used.p;
         tap.steal = S.fft_ctr.p;
+        tap.scratch = S.fft_scratch.p;
         SDR_LAUNCH(sdr::K_FFT, sdr::launch_fft(b->logn, P.fft, fmt, iq_dev, cur, b->tw.p, S.psd.p, n_frames, B, in_stride, stride, tap,
                                                stream_of(sdr::K_FFT)));
     }

@@ -201,7 +201,7 @@ int sdr_read_frame_records(sdr_bank *b, int band, sdr_frame_rec *out, int max)
         // The hot path (k_noise_scan.hip) produces FindNoiseFloor's CONSUMED values and only brackets the float64 variance,
         // which nothing consumes.  A read gets the reference's variance - the literal loops run here, for every frame of
         // the batch - and the same pass compares the consumed values with the literal ones: a difference is an error.
-        if (b->sw.noise_scan) {
+        if (sdr::noise_scan_at(b->sw, b->cfg.block_size)) {
             unsigned *mism = nullptr, h = 0;
             HIP_TRY(hipMalloc(&mism, sizeof(unsigned)));
             hipError_t e = hipMemset(mism, 0, sizeof(unsigned));

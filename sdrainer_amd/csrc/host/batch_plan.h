@@ -38,6 +38,7 @@ struct Switches {
     int refine_wide = -1;    // SDR_REFINE_WIDE=0 / 1: the refinement's workgroup shape (-1: by cumulations per batch)
     int var_mfma = -1;       // SDR_VAR_MFMA=0 / 1: the chains' variance kernel (-1: by batch length)
     int wm_wpb = 0;          // SDR_WM_WPB: windows per workgroup of the chains' window sums (0: launch_window_means' rule)
+    int fft2p_group_mb = -1;  // SDR_FFT2P_GROUP_MB: N > 16384, MiB of float64 intermediate per frame group (0: the whole batch; -1: kFft2pGroupMiB)
     bool no_overlap = false;   // SDR_NO_OVERLAP=1: every stage on the caller's stream (kernel-by-kernel profiling)
     bool graph_debug = false;  // SDR_GRAPH_DEBUG: host-side timings of every sdr_graph_launch on stderr
     // -DSDR_DIAG builds only (tools/abl): SDR_DIAG_SKIP = bit mask of kernel ids not to launch, to see which stage holds the
@@ -72,6 +73,8 @@ inline Switches read_switches()
     s.cum_bound = tri_state(getenv("SDR_CUM_BOUND"));
     s.refine_wide = tri_state(getenv("SDR_REFINE_WIDE"));
     s.var_mfma = tri_state(getenv("SDR_VAR_MFMA"));
+    if ((e = getenv("SDR_FFT2P_GROUP_MB")))
+        s.fft2p_group_mb = atoi(e) >= 0 ? atoi(e) : -1;  // (measurement: tools/fft2p_bench.py)
     if ((e = getenv("SDR_WM_WPB")))
         s.wm_wpb = atoi(e) > 0 ? atoi(e) : 0;  // (development)
     e = getenv("SDR_NO_OVERLAP");
@@ -87,12 +90,46 @@ inline Switches read_switches()
     return s;
 }
 
+// The noise-floor path of a bank of block size n: the one-pass scan (k_noise_scan.hip) unless the chains are asked for.
+// Above N = 16384 a window holds more than the 64 JMAX = 1664 values one scan wave owns: the chains (k_noise.hip), which
+// take any window, compute the noise floor there.
+inline bool noise_scan_at(const Switches &sw, int n) { return sw.noise_scan && n <= 16384; }
+// The chains' variance on the matrix pipe relies on the order in which it accumulates (sdr_self_check probes it at
+// sdr_create).  Only banks that ASKED for the chains (SDR_NOISE_PATH=chains, SDR_VAR_MFMA=1) may take it: at N > 16384,
+// where the chains are the default noise path, the variance runs on the vector ALU unless SDR_VAR_MFMA=1.
+inline bool var_mfma_at(const Switches &sw, int n, int n_frames)
+{
+    if (sw.var_mfma >= 0)
+        return sw.var_mfma != 0;
+    return n <= 16384 && n_frames < 4096;
+}
+// may a bank of block size n launch the matrix-pipe variance kernel (then sdr_create probes it)?
+inline bool may_use_matrix_pipe(const Switches &sw, int n) { return !noise_scan_at(sw, n) && (sw.var_mfma == 1 || (sw.var_mfma < 0 && n <= 16384)); }
+
 // Which FFT kernel runs a batch, and how.
 struct FftChoice {
     bool r32 = false;       // N = 16384 on k_fft_r32 instead of the 16-point k_fft_psd<14>
     int fpw = 0;            // the 16-point kernels: frames per workgroup asked for (0: the kernel's default, launch_fft_t)
     bool wide_tap = false;  // the kernel leaves the wide tap (psd at bin - 1, bin, bin + 1 of every listener: k_cum_refine reads it)
+    bool two_phase = false;  // N = 32768 / 65536: the two kernels of k_fft_2p.hip, frame group by frame group
+    int group_frames = 0;    // ... frames per group (the batch set's scratch holds one group's intermediate of every band)
 };
+
+// N = 32768 and 65536 (k_fft_2p.hip): frames per group of the two phases.  A group's float64 intermediate is 16 bytes per
+// sample of every band.  Groups that fit the 256 MiB Infinity Cache were the first design; measured, phase B does not gain
+// from them (0.99 ms per 4096-frame batch of 32768 points in 64 MiB groups, 0.92 ms as one whole-batch group) and every
+// group costs two launches, so a group is 128 MiB: within 3 % of whole batches at an eighth of their scratch.
+constexpr int kFft2pGroupMiB = 128;  // measured end to end: 64 MiB groups 67, 128 MiB 74, whole batches 76 GS/s
+// frames per group of a bank of n_bands bands of N = n whose batches hold at most max_frames frames (0 below N = 32768)
+inline int fft2p_group_frames(const Switches &sw, int n, int n_bands, int max_frames)
+{
+    if (n <= 16384 || n_bands <= 0 || max_frames <= 0)
+        return 0;
+    const int mib = sw.fft2p_group_mb >= 0 ? sw.fft2p_group_mb : kFft2pGroupMiB;
+    const long per_frame = (long)n_bands * n * 16;
+    const long f = mib == 0 ? max_frames : ((long)mib << 20) / per_frame;
+    return (int)(f < 1 ? 1 : (f > max_frames ? max_frames : f));
+}
 
 // N = 16384 has two kernels: k_fft_psd.hip's 16-point one and k_fft_r32.hip (512 threads x 32 points, the next frame
 // prefetched into registers), whose workgroups - one per CU - claim frames from a counter.  By default the 32-point kernel
@@ -104,7 +141,8 @@ inline FftChoice fft_choice(const Switches &sw, int n, int n_frames, int n_bands
     FftChoice c;
     c.r32 = n == 16384 && tap_n <= kR32MaxTap && (sw.fft_r32 == 1 || (sw.fft_r32 < 0 && (long)n_frames * n_bands >= 1024));
     c.fpw = sw.fft_fpw;
-    c.wide_tap = c.r32 && tap_n > 0;
+    c.wide_tap = c.r32 && tap_n > 0;  // (never at N > 16384: k_cum_refine reads psd columns there)
+    c.two_phase = n > 16384;
     return c;
 }
 
@@ -154,13 +192,14 @@ inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_fr
             p.stream[k] = sw.diag_plan[k];
 
     p.fft = fft_choice(sw, g.n, n_frames, g.n_bands, max_slots);
+    p.fft.group_frames = fft2p_group_frames(sw, g.n, g.n_bands, g.max_batch_frames);
 
-    // noise floor: the one-pass scan (k_noise_scan.hip) unless the chains are asked for
-    p.noise_scan = sw.noise_scan;
+    // noise floor: the one-pass scan unless the chains are asked for or the windows are too wide for it (noise_scan_at)
+    p.noise_scan = noise_scan_at(sw, g.n);
     p.force_exact = sw.force_exact;
     // the chains' variance: two vector-ALU chain groups per workgroup for long batches (less CU time), the matrix-pipe
-    // kernel for short ones (less latency) - see k_noise.hip NS_GROUPS_VALU
-    p.var_mfma = sw.var_mfma >= 0 ? sw.var_mfma != 0 : n_frames < 4096;
+    // kernel for short ones (less latency) - see k_noise.hip NS_GROUPS_VALU; never by default above N = 16384 (var_mfma_at)
+    p.var_mfma = var_mfma_at(sw, g.n, n_frames);
     p.wm_wpb = sw.wm_wpb;
 
     // Bound-and-refine replaces the exact kernel's work with three launches on the peaks stream; on a short batch their fixed

@@ -1,0 +1,194 @@
+// k_fft_2p.hip — IQ frame -> float64 radix-2 DIT FFT -> fftshift -> PSD (float32) and the listener tap for N = 32768 and
+// 65536, whose float64 frame (512 KB / 1 MB) fits neither the registers (512 KB) nor the LDS (160 KB) of one CU: two
+// kernels over the two phases of fft_2p.h, the intermediate in a scratch buffer of the batch's set.
+//
+// A batch is run in frame groups: phase A of a group, then phase B of the same group, in stream order on the FFT stream
+// (no workgroup waits for another).  The scratch holds one group's intermediate (16 bytes per sample); the group's size is
+// the plan's (host/batch_plan.h fft2p_group_frames).
+// Compiled with -ffp-contract=off (gomath.h).
+#include <hip/hip_runtime.h>
+
+#include "../../include/sdrainer_hip.h"
+#include "fft_2p.h"
+#include "sc16.h"
+#include "sdr_device.h"
+
+namespace sdr {
+
+__device__ __forceinline__ fft64::cplx tw_load(const fft64::cplx *__restrict__ tw, int i)
+{
+    return tw[i];
+}
+
+// Phase A of frames [frame0, frame0 + group) of band blockIdx.y: workgroup x = frame_local * WG_A + w takes the sub-FFTs
+// p = w G .. w G + G - 1 (blocks k = brev_B(p)).  Y: [band][group frames][N].
+template <int LOGN, InFormat FMT>
+__global__ __launch_bounds__(fft2p::T) void k_fft2p_a(const void *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
+                                                      const fft64::cplx *__restrict__ tw, fft64::cplx *__restrict__ y, int in_stride,
+                                                      int frame0, int group)
+{
+    using PH = fft2p::Phases<LOGN>;
+    using S = typename PH::SA;
+    constexpr int N = PH::N, MB = PH::A;
+    __shared__ double lr[S::G * S::LDS_ROW], li[S::G * S::LDS_ROW];
+    const int fl = blockIdx.x / PH::WG_A, w = blockIdx.x % PH::WG_A, band = blockIdx.y, t = threadIdx.x;
+    const size_t frame_row = (size_t)band * in_stride + frame0 + fl;
+    const auto W = [tw](int i) { return tw_load(tw, i); };
+    double xr[fft2p::R], xi[fft2p::R];
+    {
+        const int gl = fft2p::p0_sub<MB>(t), p = w * S::G + gl;
+        if constexpr (FMT == InFormat::F32) {
+            const float2 *__restrict__ iq = reinterpret_cast<const float2 *>(cur ? cur->iq : static_cast<const float *>(iq_arg)) + frame_row * N;
+#pragma unroll
+            for (int s = 0; s < fft2p::R; s++) {
+                const float2 v = iq[fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s))];
+                xr[s] = (double)v.x;
+                xi[s] = (double)v.y;
+            }
+        } else {
+            const uint32_t *__restrict__ iq = reinterpret_cast<const uint32_t *>(cur ? cur->iq_sc16 : static_cast<const int16_t *>(iq_arg)) + frame_row * N;
+#pragma unroll
+            for (int s = 0; s < fft2p::R; s++) {
+                const uint32_t v = iq[fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s))];
+                xr[s] = (double)sc16::re_of(v);
+                xi[s] = (double)sc16::im_of(v);
+            }
+        }
+        fft2p::pass0<MB>(xr, xi, LOGN, 0, 0, t, W);
+#pragma unroll
+        for (int s = 0; s < fft2p::R; s++) {
+            const int at = gl * S::LDS_ROW + fft2p::p0_index<MB>(t, s);
+            lr[at] = xr[s];
+            li[at] = xi[s];
+        }
+    }
+    __syncthreads();
+    const int gl = fft2p::p1_sub<MB, true>(t);
+#pragma unroll
+    for (int s = 0; s < fft2p::R; s++) {
+        const int at = gl * S::LDS_ROW + fft2p::p1_index<MB, true>(t, s);
+        xr[s] = lr[at];
+        xi[s] = li[at];
+    }
+    fft2p::pass1<MB, true>(xr, xi, LOGN, 0, 0, t, W);
+    const int k = fft2p::a_block<LOGN>(w * S::G + gl);
+    fft64::cplx *__restrict__ out = y + ((size_t)band * group + fl) * N + ((size_t)k << PH::A);
+#pragma unroll
+    for (int s = 0; s < fft2p::R; s++)
+        out[fft2p::p1_index<MB, true>(t, s)] = fft64::cplx{xr[s], xi[s]};
+}
+
+// Phase B of the same group: workgroup x = frame_local * WG_B + w takes the residues c = w G .. w G + G - 1, writes their
+// bins' psd (fft-shifted) and the tap of the listeners whose bins are among them (k_fft_psd.hip "The tap"): the row's
+// values of those residues go to LDS first, the tap reads them there.
+template <int LOGN>
+__global__ __launch_bounds__(fft2p::T) void k_fft2p_b(const fft64::cplx *__restrict__ y, const fft64::cplx *__restrict__ tw,
+                                                      float *__restrict__ psd, int out_stride, int frame0, int group,
+                                                      const int *__restrict__ tap_bins, float *__restrict__ tap_out, int n_tap, int tap_stride)
+{
+    using PH = fft2p::Phases<LOGN>;
+    using S = typename PH::SB;
+    constexpr int N = PH::N, MB = PH::B, A = PH::A;
+    __shared__ double lr[S::G * S::LDS_ROW], li[S::G * S::LDS_ROW];
+    const int fl = blockIdx.x / PH::WG_B, w = blockIdx.x % PH::WG_B, band = blockIdx.y, t = threadIdx.x;
+    const int c0 = w * S::G;
+    const auto W = [tw](int i) { return tw_load(tw, i); };
+    double xr[fft2p::R], xi[fft2p::R];
+    {
+        const int gl = fft2p::p0_sub<MB>(t), c = c0 + gl;
+        const fft64::cplx *__restrict__ in = y + ((size_t)band * group + fl) * N + c;
+#pragma unroll
+        for (int s = 0; s < fft2p::R; s++) {
+            const fft64::cplx v = in[(size_t)fft2p::p0_index<MB>(t, s) << A];
+            xr[s] = v.x;
+            xi[s] = v.y;
+        }
+        fft2p::pass0<MB>(xr, xi, LOGN, A, c, t, W);
+#pragma unroll
+        for (int s = 0; s < fft2p::R; s++) {
+            const int at = gl * S::LDS_ROW + fft2p::p0_index<MB>(t, s);
+            lr[at] = xr[s];
+            li[at] = xi[s];
+        }
+    }
+    __syncthreads();
+    const int gl = fft2p::p1_sub<MB, false>(t), c = c0 + gl;
+#pragma unroll
+    for (int s = 0; s < fft2p::R; s++) {
+        const int at = gl * S::LDS_ROW + fft2p::p1_index<MB, false>(t, s);
+        xr[s] = lr[at];
+        xi[s] = li[at];
+    }
+    fft2p::pass1<MB, false>(xr, xi, LOGN, A, c, t, W);
+    const int frame = frame0 + fl;
+    float *__restrict__ row = psd + ((size_t)band * out_stride + frame) * N;
+    float p[fft2p::R];
+#pragma unroll
+    for (int s = 0; s < fft2p::R; s++) {
+        p[s] = fft2p::psd_of(xr[s], xi[s]);
+        row[(c + (fft2p::p1_index<MB, false>(t, s) << A)) ^ (N / 2)] = p[s];
+    }
+    if (n_tap <= 0)
+        return;  // (uniform)
+    __syncthreads();  // every thread is done reading the exchange area
+    float *prow = reinterpret_cast<float *>(lr);  // [residue of the workgroup][q]
+#pragma unroll
+    for (int s = 0; s < fft2p::R; s++)
+        prow[gl * (1 << MB) + fft2p::p1_index<MB, false>(t, s)] = p[s];
+    __syncthreads();
+    const int *__restrict__ bins = tap_bins + (size_t)band * tap_stride;
+    float *__restrict__ out = tap_out + ((size_t)band * out_stride + frame) * tap_stride;
+    for (int l = t; l < n_tap; l += fft2p::T) {
+        const int bin = bins[l];
+        if (bin < 0) {
+            if (w == 0)
+                out[l] = 0.0f;
+            continue;
+        }
+        const int idx = bin ^ (N / 2), cl = (idx & ((1 << A) - 1)) - c0;
+        if (cl >= 0 && cl < S::G)
+            out[l] = prow[cl * (1 << MB) + (idx >> A)];
+    }
+}
+
+template <int LOGN>
+static hipError_t launch_fft2p_t(FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
+                                 int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+{
+    using PH = fft2p::Phases<LOGN>;
+    if (n_frames <= 0 || n_bands <= 0)
+        return hipSuccess;
+    if (!tap.scratch || fft.group_frames <= 0)
+        return hipErrorInvalidValue;
+    const int group = fft.group_frames;
+    // (a stage event armed by the caller rides on the last launch)
+    const hipEvent_t done = t_done_event;
+    t_done_event = nullptr;
+    for (int f0 = 0; f0 < n_frames; f0 += group) {
+        const int g = n_frames - f0 < group ? n_frames - f0 : group;
+        if (fmt == InFormat::SC16)
+            hipLaunchKernelGGL((k_fft2p_a<LOGN, InFormat::SC16>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
+                               tap.scratch, in_stride, f0, group);
+        else
+            hipLaunchKernelGGL((k_fft2p_a<LOGN, InFormat::F32>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
+                               tap.scratch, in_stride, f0, group);
+        if (f0 + group >= n_frames)
+            t_done_event = done;
+        launch_kernel((k_fft2p_b<LOGN>), dim3(g * PH::WG_B, n_bands), dim3(fft2p::T), 0, stream, static_cast<const fft64::cplx *>(tap.scratch),
+                      tw, psd, out_stride, f0, group, tap.bins, tap.out, tap.n, tap.stride);
+    }
+    t_done_event = nullptr;
+    return hipGetLastError();
+}
+
+hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
+                         int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+{
+    switch (logn) {
+    case 15: return launch_fft2p_t<15>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 16: return launch_fft2p_t<16>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace sdr

@@ -1071,6 +1071,8 @@ hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, con
 {
     if (fmt != InFormat::F32 && fmt != InFormat::SC16)
         return hipErrorInvalidValue;
+    if (fft.two_phase)
+        return launch_fft_2p(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
     if (fft.r32) {
         if (logn != 14)
             return hipErrorInvalidValue;
@@ -1104,6 +1106,8 @@ int twiddle_count(int logn)
     case 12: return fft64::Plan<12>::TW_TOTAL;
     case 13: return fft64::Plan<13>::TW_TOTAL;
     case 14: return fft64::Plan<14>::TW_TOTAL + r32_twiddle_count();
+    case 15: return 1 << 14;  // k_fft_2p: go-dsp's table as it is, the N / 2 entries a radix-2 FFT reads
+    case 16: return 1 << 15;
     default: return 0;
     }
 }
@@ -1119,6 +1123,11 @@ void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx 
     case 14:
         fft64::build_pass_twiddles<14>(wre, wim, out);
         r32_build_twiddles(wre, wim, out + fft64::Plan<14>::TW_TOTAL);
+        break;
+    case 15:
+    case 16:
+        for (int i = 0; i < 1 << (logn - 1); i++)
+            out[i] = fft64::cplx{wre[i], wim[i]};
         break;
     default: break;
     }

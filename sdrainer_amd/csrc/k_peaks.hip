@@ -636,6 +636,106 @@ __global__ __launch_bounds__(kPeakThreadsMax) void k_find_peaks(const float *__r
     }
 }
 
+// k_find_peaks for N > 16384, whose row does not fit the LDS (256 KB at N = 65536): the same three steps, the values of
+// step 3's runs divided again from the row in memory (the same float32 division: the same values)
+__global__ __launch_bounds__(kPeakThreadsMax) void k_find_peaks_wide(const float *__restrict__ cum, const sdr_frame_rec *__restrict__ recs,
+                                                                 DevPeak *__restrict__ peaks, int *__restrict__ counts,
+                                                                 const BatchCursor *__restrict__ cur, PeakGeom g, int n_frames)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_peaks[];
+    const int chunk = blockIdx.x, band = blockIdx.y, tid = threadIdx.x, lane = threadIdx.x & 63;
+    if (cur) {
+        g.count0 = cur->count0;
+        if (chunk >= chunks_completed(g.count0, n_frames))
+            return;
+    }
+    const int n = g.n, words = peak_words(n), T = blockDim.x;
+    unsigned long long *flags = reinterpret_cast<unsigned long long *>(smem_peaks);          // [words]
+    unsigned long long *starts = flags + words;                                              // [words]
+    int *offs = reinterpret_cast<int *>(starts + words);                                     // [words + 1]
+    const int first_len = SDR_CUMULATION_SIZE - g.count0;
+    const int end_frame = first_len + chunk * SDR_CUMULATION_SIZE - 1;  // frame that completes this chunk
+    const float thr = recs[(size_t)band * g.stride + end_frame].peak_thr;
+    const float *c = cum + ((size_t)band * g.max_chunks + chunk) * n;
+    const float size = (float)SDR_CUMULATION_SIZE;
+    // 1. values and flag words (n is a multiple of T, T a multiple of 64: every wave instruction covers 64 whole bins)
+#pragma unroll 8
+    for (int b = tid; b < n; b += T) {
+        const float v = __fdiv_rn(c[b], size);
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(v > thr);
+        if (lane == 0)
+            flags[b >> 6] = m;
+    }
+    __syncthreads();
+    // 2. run starts per word, numbered by a prefix sum
+    for (int w = tid; w < words; w += T) {
+        const unsigned long long f = flags[w];
+        const unsigned long long before = (f << 1) | (w > 0 ? flags[w - 1] >> 63 : 0ull);
+        starts[w] = f & ~before;
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const int total = word_prefix(starts, offs, words, tid);
+        if (tid == 63)
+            counts[(size_t)band * g.max_chunks + chunk] = total;
+    }
+    __syncthreads();
+    // 3. the runs that start in word w
+    for (int w = tid; w < words; w += T) {
+        unsigned long long st = starts[w];
+        int idx = offs[w];
+        while (st) {
+            const int k = __builtin_ctzll(st);
+            st &= st - 1;
+            const int from = (w << 6) + k;
+            // end of the run: first clear bit at or after `from`
+            int to;
+            {
+                int ww = w;
+                unsigned long long inv = ~flags[ww] >> k;  // bit j = bin from + j is NOT flagged (zeros shifted in at the top: handled below)
+                int base = from;
+                int room = 64 - k;  // valid bits in `inv`
+                for (;;) {
+                    const int z = inv ? __builtin_ctzll(inv) : 64;
+                    if (z < room) {
+                        to = base + z - 1;
+                        break;
+                    }
+                    ww++;
+                    base += room;
+                    if (ww >= words) {
+                        to = n - 1;
+                        break;
+                    }
+                    inv = ~flags[ww];
+                    room = 64;
+                }
+            }
+            if (idx < g.max_peaks) {
+                float best = __fdiv_rn(c[from], size);
+                int best_bin = from;
+                for (int j = from + 1; j <= to; j++) {
+                    const float vj = __fdiv_rn(c[j], size);
+                    if (best < vj) {
+                        best = vj;
+                        best_bin = j;
+                    }
+                }
+                DevPeak p;
+                p.from = from;
+                p.to = to;
+                p.signal_bin = best_bin;
+                p.signal_value = best;
+                p.y1 = best_bin > 0 ? c[best_bin - 1] : 0.f;  // (exact: neighbours of a flagged bin were refined)
+                p.y2 = c[best_bin];
+                p.y3 = best_bin < n - 1 ? c[best_bin + 1] : 0.f;
+                peaks[((size_t)band * g.max_chunks + chunk) * g.max_peaks + idx] = p;
+            }
+            idx++;
+        }
+    }
+}
+
 // k_bound_finish - the bounds of the cumulations a batch completes from the unit counts k_psd_scan left in their rows
 // (one or two partial counts per bin: a slot's frames may have been dealt over two workgroups) and, for the first one -
 // slot 0 continues the cumulation carried in - the carry: gomath::cum_bound, as k_cum_bound forms it.
@@ -739,7 +839,8 @@ hipError_t launch_find_peaks(float *cum, const float *psd, const void *db_tab, c
     if (n_chunks == 0)
         return hipSuccess;
     const int words = g.n >> 6;
-    const unsigned lds = (unsigned)((size_t)g.n * 4 + (size_t)words * 16 + (size_t)(words + 1) * 4);
+    const bool wide = g.n > 16384;  // (k_find_peaks_wide: no row in LDS)
+    const unsigned lds = (unsigned)((wide ? 0 : (size_t)g.n * 4) + (size_t)words * 16 + (size_t)(words + 1) * 4);
     // more than 64 KB of dynamic LDS needs the attribute, once per device
     static LdsLimitOnce lds_once;
     const hipError_t attr_err = raise_lds_limit_once(lds_once, {reinterpret_cast<const void *>(&k_find_peaks)}, 16384 * 4 + 256 * 16 + 257 * 4);
@@ -759,8 +860,12 @@ hipError_t launch_find_peaks(float *cum, const float *psd, const void *db_tab, c
                            tap.used, tap.n, tap.stride);
     t_done_event = done;
     const int threads = g.n < kPeakThreadsMax ? g.n : kPeakThreadsMax;
-    launch_kernel(k_find_peaks, dim3(n_chunks, n_bands), dim3(threads), lds, stream, static_cast<const float *>(cum), recs, peaks, counts, cur, g,
-                  n_frames);
+    if (wide)
+        launch_kernel(k_find_peaks_wide, dim3(n_chunks, n_bands), dim3(threads), lds, stream, static_cast<const float *>(cum), recs, peaks, counts,
+                      cur, g, n_frames);
+    else
+        launch_kernel(k_find_peaks, dim3(n_chunks, n_bands), dim3(threads), lds, stream, static_cast<const float *>(cum), recs, peaks, counts, cur, g,
+                      n_frames);
     return hipGetLastError();
 }
 

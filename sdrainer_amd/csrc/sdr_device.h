@@ -166,6 +166,8 @@ struct FftTap {
     int32_t *used = nullptr;
     // k_fft_r32 only: its frame counters, [band][2] uint32, zero between launches (BatchSet::fft_ctr)
     uint32_t *steal = nullptr;
+    // k_fft_2p only: one frame group's float64 intermediate, [band][FftChoice::group_frames][N] (BatchSet::fft_scratch)
+    fft64::cplx *scratch = nullptr;
 };
 
 // iq: [band][in_stride frames][N] samples of format fmt (float32 pairs or sc16 words); `fft` picks the kernel (host/batch_plan.h)
@@ -173,6 +175,9 @@ hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, con
                       int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream);
 hipError_t launch_fft(int logn, FftChoice fft, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
                       int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream);  // (float32)
+// k_fft_2p.hip: N = 32768 / 65536 as two phases over a scratch buffer (fft_2p.h), frame group by frame group
+hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
+                         int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream);
 int twiddle_count(int logn);
 void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx *out);
 // k_fft_r32.hip: N = 16384 as 512 threads x 32 points with the next frame prefetched into registers (own twiddle layout)
