@@ -93,6 +93,20 @@ __device__ __forceinline__ double wave_sum_to_lane63(double x)
     return x;
 }
 
+// noise_cert.h kScanTerms bounds (in units of u) the relative error of every sum certify() works from.  The sequential
+// float64 additions a psd value can pass through on its way into one of those sums, for a k_psd_scan<JMAX>:
+//   * the lane chain: a lane adds its 4 Q4MAX values of the 16-byte loads and its R1MAX values of the dword loads one after
+//     the other, from s1 = 0.0 (k_psd_scan below; loads beyond the segment add 0.0 and are counted all the same);
+//   * the DPP ladder: wave_sum_to_lane63, six additions deep (row_shr 1 / 2 / 4 / 8, row_bcast 15 / 31);
+//   * segments: none - a window is one segment, summed by one wave (the edge pieces feed the bound's unit counts only);
+//   * certify(): the variance's S1 / S2 add up to kMaxWindows window sums from 0.0 and then psd[resultTo], one more.
+constexpr int kScanLadderAdds = 6;
+constexpr int kCertifyAdds = noise::kMaxWindows + 1;
+template <int JMAX>
+constexpr int scan_lane_adds() { return 4 * (JMAX / 4) + (JMAX < 4 ? JMAX : 4); }  // (k_psd_scan's Q4MAX and R1MAX)
+template <int JMAX>
+constexpr int scan_sequential_adds() { return scan_lane_adds<JMAX>() + kScanLadderAdds + kCertifyAdds; }
+
 // LDS of a scan workgroup: the run's sums [frame][window][S1, S2], the list of frames for the literal loops, and - used
 // by those only - a staged psd row and the double buffer of the variance chain's terms
 struct ScanLds {
@@ -220,6 +234,8 @@ __global__ __launch_bounds__(64 * kScanMaxWaves) void k_psd_scan(const float *__
         // per-lane offset.  (As global loads under per-lane predicates the loop was 38 instructions per value, five of them
         // the arithmetic.)  What such a value adds is harmless: nothing to S1 / S2, something to a unit count never stored.
         constexpr int Q4MAX = JMAX / 4, R1MAX = JMAX < 4 ? JMAX : 4, Q4A = Q4MAX ? Q4MAX : 1;
+        static_assert(4 * Q4MAX + R1MAX == scan_lane_adds<JMAX>(), "scan_lane_adds must count this lane chain");
+        static_assert(scan_sequential_adds<JMAX>() <= noise::kScanTerms, "noise::kScanTerms no longer bounds the scan's sums");
         const int q4 = len >> 8, rem = len - (q4 << 8);  // (wave-uniform; q4 <= Q4MAX as len <= 64 JMAX)
         unsigned u4[Q4A][4], u1[R1MAX], hw_max = 0u;
 #pragma unroll
@@ -403,6 +419,12 @@ hipError_t launch_noise_exact_check(const float *psd_band, sdr_frame_rec *recs_b
                        mismatches);
     return hipGetLastError();
 }
+
+// every instantiation of k_psd_scan (launch_psd_scan, scan_jmax) within noise::kScanTerms
+static_assert(scan_sequential_adds<2>() <= noise::kScanTerms && scan_sequential_adds<5>() <= noise::kScanTerms &&
+                  scan_sequential_adds<10>() <= noise::kScanTerms && scan_sequential_adds<19>() <= noise::kScanTerms &&
+                  scan_sequential_adds<26>() <= noise::kScanTerms,
+              "noise::kScanTerms no longer bounds the scan's sums");
 
 static int scan_jmax(int window)
 {

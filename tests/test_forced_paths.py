@@ -16,11 +16,14 @@ import sys
 
 import pytest
 
+import fuzz_paths_gen
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ("test_receiver_run_bit_exact or test_nine_window_geometry or test_config5_geometry or test_batch_split_invariance_and_carry"
          " or test_scan_segment_geometries")
+FUZZ_PATHS = "test_random_paths and (" + " or ".join(f"seed{s:03d}-" for s in fuzz_paths_gen.forced_selection()) + ")"
 
 
 @pytest.mark.parametrize("env, files, sel", [
@@ -44,6 +47,11 @@ SMALL = ("test_receiver_run_bit_exact or test_nine_window_geometry or test_confi
     ({"SDR_CUM_BOUND": "1"}, ["tests/test_gpu_parity_bench_sizes.py"], "config3"),
     ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "1"}, ["tests/test_gpu_fuzz.py"], "random_streams"),
     ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "0", "SDR_NOISE_PATH": "chains", "SDR_VAR_MFMA": "0"}, ["tests/test_gpu_fuzz.py"], "random_streams"),
+    # seeds of the path fuzz that between them reach every FFT kernel family, input path and adversarial kind
+    # (fuzz_paths_gen.forced_selection), through bound-and-refine in both refinement shapes and through the chains
+    ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "0"}, ["tests/test_gpu_fuzz_paths.py"], FUZZ_PATHS),
+    ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "1"}, ["tests/test_gpu_fuzz_paths.py"], FUZZ_PATHS),
+    ({"SDR_NOISE_PATH": "chains"}, ["tests/test_gpu_fuzz_paths.py"], FUZZ_PATHS),
 ])
 def test_parity_with_the_other_implementation_forced(env, files, sel):
     p = subprocess.run([sys.executable, "-m", "pytest", *[os.path.join(ROOT, f) for f in files], "-q", "-x", "-m", "gpu", "-k", sel,

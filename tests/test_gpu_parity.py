@@ -45,7 +45,8 @@ def _peak_tuple_equal(g, r):
 
 
 @pytest.mark.parametrize("n,rate,tones", [(512, 48000, 4), (1024, 96000, 6), (2048, 192000, 8), (4096, 192000, 16),
-                                          (8192, 2000000, 16), (16384, 2000000, 32)])
+                                          (8192, 2000000, 16), (16384, 2000000, 32), (32768, 2000000, 32),
+                                          (65536, 4000000, 32)])
 def test_spectrum_psd_bit_exact(capi, n, rate, tones):
     frames = 6
     iq, bins, _ = synth.make_band(frames, rate, n, tones, seed=100 + n)

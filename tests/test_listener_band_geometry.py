@@ -18,18 +18,11 @@ one stream per band (a listener's keying column is zero before it is attached) a
 delivers and what stays on the device: frame records, keying bits, edges, runes, decoder state, the exact cumulation
 rows (and the kept row: never below the exact one, equal at and beside every peak) and peaks.
 """
-from concurrent.futures import ThreadPoolExecutor
-
-import numpy as np
 import pytest
 
-from oracle import oracle as orc
-from sdrainer_amd import synth
-from test_gpu_parity_bench_sizes import _check_batch_polled, _check_device_batch
+from parity_case import RATE, Case
 
 pytestmark = pytest.mark.gpu
-
-RATE = 2_000_000
 
 
 @pytest.fixture(scope="module")
@@ -37,202 +30,6 @@ def capi():
     from sdrainer_amd import capi as c
     c.load()
     return c
-
-
-def _extra_bins(n, carriers, count, seed):
-    """`count` listener bins besides the keyed carriers: 0 and N - 1, a carrier twice, both neighbours of every fourth
-    carrier, then noise bins (seeded)."""
-    carriers = [int(c) for c in carriers]
-    out = [0, n - 1, carriers[0]]
-    for c in carriers[::4]:
-        out += [c - 1, c + 1]
-    taken = set(carriers) | set(out)
-    rng = np.random.default_rng(seed)
-    noise = rng.permutation([b for b in range(n) if b not in taken])
-    out += [int(b) for b in noise[:max(0, count - len(out))]]
-    assert len(out) >= count, "not enough bins"
-    return out[:count]
-
-
-class Case:
-    """One bank's stream: bands of keyed carriers, the listeners attached before the first frame, then a list of steps
-       ("batch", frames)                      an eager batch
-       ("defer", frames, [(band, bin, s)])    a deferred batch; after its peaks, sdr_attach_at(band, bin, s) in order
-       ("attach", band, bin) / ("detach", band, lid)   between batches
-    (steps may also be a function of the carriers' bins per band, which exist once the input does)
-    """
-
-    def __init__(self, n, n_bands, carriers, listeners, steps, seed, rate=RATE, free_last=True, max_listeners=None, total_frames=None):
-        self.n, self.n_bands, self.rate = n, n_bands, rate
-        self.edge = synth.default_edge_width(n)
-        self.total = total_frames or sum(s[1] for s in steps if s[0] in ("batch", "defer"))
-        self.centers = [14000000 + 100000 * b for b in range(n_bands)]
-        self.dev_iq, self.carriers, self.init_bins = [], [], []
-        for b in range(n_bands):
-            iq, bins, _ = synth.make_band_torch(self.total, rate, n, carriers, seed=seed + 17 * b, device="cuda", free_last_window=free_last)
-            self.dev_iq.append(iq)
-            self.carriers.append([int(x) for x in bins])
-            self.init_bins.append((self.carriers[b] + _extra_bins(n, bins, max(0, listeners - carriers), seed + 17 * b))[:listeners])
-        self.steps = steps = steps(self.carriers) if callable(steps) else steps
-        assert self.total == sum(s[1] for s in steps if s[0] in ("batch", "defer"))
-        self.max_frames = max(s[1] for s in steps if s[0] in ("batch", "defer"))
-        late = sum(1 for s in steps if s[0] == "attach") + sum(len(s[2]) for s in steps if s[0] == "defer")
-        self.max_listeners = max_listeners or listeners + late
-        # every listener of every band: (attached at frame, detached at frame or None)
-        self.life = [[(0, None) for _ in bins] for bins in self.init_bins]
-        self.bins = [list(bins) for bins in self.init_bins]
-        pos = 0
-        for s in steps:
-            if s[0] == "attach":
-                self.bins[s[1]].append(s[2])
-                self.life[s[1]].append((pos, None))
-            elif s[0] == "detach":
-                self.life[s[1]][s[2]] = (self.life[s[1]][s[2]][0], pos)
-            else:
-                for band, bn, at in s[2] if s[0] == "defer" else []:
-                    assert pos <= at < pos + s[1]
-                    self.bins[band].append(bn)
-                    self.life[band].append((at, None))
-                pos += s[1]
-
-    def run_oracle(self):
-        """One oracle receiver per band, attached and detached at the bank's frames, bands on threads of their own."""
-        def band_events(b):
-            ev, pos = [], 0  # (frame, "attach", bin) / (frame, "detach", lid), in the bank's call order
-            for s in self.steps:
-                if s[0] == "attach" and s[1] == b:
-                    ev.append((pos, "attach", s[2]))
-                elif s[0] == "detach" and s[1] == b:
-                    ev.append((pos, "detach", s[2]))
-                elif s[0] == "defer":
-                    ev += [(at, "attach", bn) for band, bn, at in s[2] if band == b]
-                if s[0] in ("batch", "defer"):
-                    pos += s[1]
-            return ev
-
-        def run(b):
-            host = self.dev_iq[b].cpu().numpy()
-            r = orc.Receiver(self.rate, self.n, self.edge, 15.0, 1, center_frequency=self.centers[b])
-            for bn in self.init_bins[b]:
-                r.attach(int(bn))
-            L = len(self.bins[b])
-            st = {"frames": [], "deb": np.zeros((self.total, L), np.uint8), "peaks": [], "peak_frames": [], "cumulation": []}
-            pos = 0
-            for at, kind, arg in band_events(b) + [(self.total, None, None)]:
-                if at > pos:
-                    out = r.process(host[pos:at])
-                    st["frames"].append(out["frames"])
-                    st["deb"][pos:at, :out["deb"].shape[1]] = out["deb"]
-                    st["peaks"] += out["peaks"]
-                    st["peak_frames"] += [pos + int(f) for f in out["peak_frames"]]
-                    st["cumulation"] += list(out["cumulation"])
-                    pos = at
-                if kind == "attach":
-                    r.attach(int(arg))
-                elif kind == "detach":
-                    r.detach(int(arg))
-            st["frames"] = np.concatenate(st["frames"])
-            st["peak_frames"] = np.array(st["peak_frames"], np.int64)
-            return r, st
-
-        with ThreadPoolExecutor(max(1, min(self.n_bands, 16))) as ex:
-            res = list(ex.map(run, range(self.n_bands)))
-        self.refs = [r for r, _ in res]
-        self.outs = [o for _, o in res]
-
-    def live(self, b, a, e):
-        """Listeners of band b that listen during [a, e) and are not detached at its end."""
-        return [lid for lid, (s, d) in enumerate(self.life[b]) if s < e and (d is None or d >= e)]
-
-    def new_bank(self, capi, stream=None):
-        """stream: the bank's own (graph capture needs one); None: the current stream, which orders the input for it."""
-        import torch
-
-        bank = capi.Bank(self.rate, self.n, n_bands=self.n_bands, edge_width=self.edge, max_batch_frames=self.max_frames,
-                         max_listeners=self.max_listeners, max_peaks=1024)
-        bank.set_stream((stream or torch.cuda.current_stream()).cuda_stream)
-        for b in range(self.n_bands):
-            bank.set_center_frequency(b, self.centers[b])
-            for i, bn in enumerate(self.init_bins[b]):
-                assert bank.attach(b, int(bn)) == i
-        bank.enable_results(True)
-        self.text = [["" for _ in bins] for bins in self.bins]
-        self.edges = self.peaks = 0
-        return bank
-
-    def gone(self, a):
-        """(band, listener) pairs detached before frame a."""
-        return [(b, lid) for b in range(self.n_bands) for lid, (_, d) in enumerate(self.life[b]) if d is not None and d <= a]
-
-    def check_polled(self, res, a, e):
-        """One delivered batch against the stitched oracle stream, for the listeners live in it; detached ones deliver nothing."""
-        ne, npk = _check_batch_polled(res, self.outs, a, e, None, self.text, self.n_bands,
-                                      live=[self.live(b, a, e) for b in range(self.n_bands)], gone=self.gone(a))
-        self.edges += ne
-        self.peaks += npk
-
-    def check_device(self, bank, a, e, k, cumulations=True):
-        """What the last batch left on the device: frame records, keying bits, cumulation rows."""
-        _check_device_batch(bank, self.outs, a, e, self.n_bands, [self.live(b, a, e) for b in range(self.n_bands)], k, cumulations)
-
-    def check_end(self, bank, min_edges):
-        for b in range(self.n_bands):
-            for lid in range(len(self.bins[b])):
-                assert self.text[b][lid] == self.refs[b].text(lid), f"band {b} listener {lid} text"
-                assert np.array_equal(bank.read_decoder_state(b, lid), self.refs[b].decoder_state(lid)), f"band {b} listener {lid} state"
-        assert bank.read_drop_counters() == (0, 0)
-        n_carriers = sum(len(c) for c in self.carriers)
-        assert self.edges > min_edges * n_carriers and self.peaks > 0 and any(len(t) > 0 for row in self.text for t in row)
-
-    def run(self, capi, min_edges=20, lag=False):
-        """Every step on one bank, each batch checked when it is delivered.  lag: a batch is polled only once the next one
-        is enqueued (the listen stream may then still run one batch while the next batch's spectral stages start), and
-        what stays on the device is checked for the last batch only."""
-        import torch
-
-        self.run_oracle()
-        bank = self.new_bank(capi)
-        pos, k = 0, 0
-        pending = []  # (first frame, end, batch index, input) enqueued and not yet polled
-
-        def deliver(last):
-            a, e, i, _ = pending.pop(0)
-            res = bank.poll(wait=True)
-            assert res["batch_index"] == i
-            self.check_polled(res, a, e)
-            if last:
-                self.check_device(bank, a, e, i)
-        slots = [len(bins) for bins in self.init_bins]  # (no attach follows a detach here: ids are the oracle's)
-        for s in self.steps:
-            if s[0] == "attach":
-                assert bank.attach(s[1], int(s[2])) == slots[s[1]]
-                slots[s[1]] += 1
-                continue
-            if s[0] == "detach":
-                bank.detach(s[1], s[2])
-                continue
-            a, e = pos, pos + s[1]
-            batch = torch.stack([iq[a:e] for iq in self.dev_iq]).contiguous()  # [band][frame][2N]
-            if s[0] == "defer":
-                bank.defer_listen(True)
-                bank.process_device(batch.data_ptr(), e - a)
-                pk = bank.poll_peaks(wait=True)
-                assert pk["first_frame"] == a
-                for band, bn, at in s[2]:
-                    assert bank.attach_at(band, int(bn), at) == slots[band]
-                    slots[band] += 1
-                bank.process_listen()
-                bank.defer_listen(False)
-            else:
-                bank.process_device(batch.data_ptr(), e - a)
-            pending.append((a, e, k, batch))
-            if len(pending) > lag:
-                deliver(not lag)
-            pos, k = e, k + 1
-        while pending:
-            deliver(len(pending) == 1)
-        self.check_end(bank, min_edges)
-        return bank
 
 
 # -- 1. N = 16384 at 512 and 513 slots -----------------------------------------------------------------------------------

@@ -51,7 +51,7 @@ def test_go_sincos_matches_libm():
     assert worst <= 2.3e-16  # within ~1 ulp at |value| <= 1
 
 
-@pytest.mark.parametrize("n", [4, 8, 512, 4096, 16384])
+@pytest.mark.parametrize("n", [4, 8, 512, 4096, 16384, 32768, 65536])
 def test_radix2_factors(n):
     w = orc.radix2_factors(n)
     k = np.arange(n)
@@ -60,7 +60,7 @@ def test_radix2_factors(n):
     assert w[0] == 1 and w[n // 4] == -1j and w[n // 2] == -1 and w[3 * n // 4] == 1j  # literal size-4 table
 
 
-@pytest.mark.parametrize("n", [2, 8, 512, 4096, 8192, 16384])
+@pytest.mark.parametrize("n", [2, 8, 512, 4096, 8192, 16384, 32768, 65536])
 def test_fft_against_numpy(n):
     rng = np.random.default_rng(n)
     iq = rng.standard_normal(2 * n).astype(np.float32)
