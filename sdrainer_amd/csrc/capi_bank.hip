@@ -192,6 +192,8 @@ int sdr_create(const sdr_config *cfg, sdr_bank **out)
         return fail(SDR_ERR_BAD_ARG, "non-positive geometry");
     if (cfg->edge_width < 0 || N - 2 * cfg->edge_width < 10)
         return fail(SDR_ERR_BAD_ARG, "edge_width leaves fewer than 10 bins: the reference's windowSize would be 0 (NaN)");
+    if (!sdr::hop_valid(cfg->hop, N))
+        return fail(SDR_ERR_BAD_ARG, "hop must be 0 (= block_size) or a power of two with block_size / 16 <= hop <= block_size and hop >= 32");
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (cfg->device_id < 0 || cfg->device_id >= ndev)
@@ -200,6 +202,7 @@ int sdr_create(const sdr_config *cfg, sdr_bank **out)
 
     sdr_bank *b = new sdr_bank();
     b->cfg = *cfg;
+    b->hop = sdr::effective_hop(cfg->hop, N);
     b->sw = sdr::read_switches();
     b->device = cfg->device_id;
     b->logn = ilog2(N);
@@ -310,7 +313,7 @@ int sdr_create(const sdr_config *cfg, sdr_bank **out)
     b->h_slots.assign(B * L, sdr::ListenerSlot{});
     b->n_slots.assign(B, 0);
     b->center_frequency.assign(B, 0);
-    b->staged.assign(B, 0);
+    b->staged.assign(B, sdr::StreamStage{N, b->hop, 0, 0});
     b->staged_kind.assign(B, 0);
     *out = b;
     return SDR_OK;
@@ -428,7 +431,7 @@ int sdr_attach(sdr_bank *b, int band, int bin, int *listener_id)
     s.active = 1;
     s.bin = bin;
     cw::debouncer_init(s.deb, c.signal_debounce);          // NewSpectralDemodulator, cw/spectral.go:25-33
-    cw::decoder_init(s.dec, c.sample_rate, c.block_size);  // NewDecoder, cw/decode.go:131-147
+    cw::decoder_init(s.dec, c.sample_rate, sdr::effective_hop(c.hop, c.block_size));  // NewDecoder, cw/decode.go:131-147
     cw::decoder_reset(s.dec);                              // Listener.Attach -> demodulator.Reset, listener.go:88
     s.start_frame = s.tapped_from = (uint32_t)b->total_frames;  // listens from the next frame processed
     rc = sync_bank(b);
@@ -494,7 +497,7 @@ int sdr_attach_at(sdr_bank *b, int band, int bin, int64_t start_frame, int *list
     s.active = 1;
     s.bin = bin;
     cw::debouncer_init(s.deb, c.signal_debounce);
-    cw::decoder_init(s.dec, c.sample_rate, c.block_size);
+    cw::decoder_init(s.dec, c.sample_rate, sdr::effective_hop(c.hop, c.block_size));
     cw::decoder_reset(s.dec);
     s.start_frame = (uint32_t)start_frame;
     s.tapped_from = (uint32_t)b->total_frames;  // the FFT of every frame before that has run without this listener

@@ -120,6 +120,8 @@ static int graph_capture(sdr_bank *b, int n_frames, sdr::InFormat fmt)
 {
     if (!b)
         return fail(SDR_ERR_BAD_ARG, "null bank");
+    if (b->hop != b->cfg.block_size)  // (the replays' cursors carry [band][frame] batches)
+        return fail(SDR_ERR_STATE, "graph mode is not offered on a bank with hop < block_size (overlapped frames)");
     if (n_frames <= 0 || n_frames > b->cfg.max_batch_frames)
         return fail(SDR_ERR_BAD_ARG, "n_frames out of range");
     if (b->failed)
@@ -181,7 +183,7 @@ static int graph_capture(sdr_bank *b, int n_frames, sdr::InFormat fmt)
                 break;
             }
             for (int k = 0; k < RING && rc == SDR_OK; k++)
-                rc = process_device_body(b, nullptr, n_frames, n_frames, ph * RING + k, st, PART_ALL, fmt);
+                rc = process_device_body(b, nullptr, n_frames, (size_t)n_frames * (size_t)b->cfg.block_size, ph * RING + k, st, PART_ALL, fmt);
             e = hipStreamEndCapture(cs, &b->graph[ph][st]);
             if ((e != hipSuccess || !b->graph[ph][st]) && rc == SDR_OK)
                 rc = fail(SDR_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));

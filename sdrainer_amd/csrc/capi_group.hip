@@ -104,6 +104,8 @@ int sdr_group_create(const sdr_config *cfg, const int32_t *device_ids, int n_mem
     *out = nullptr;
     if (cfg->struct_size != (int32_t)sizeof(sdr_config))
         return fail(SDR_ERR_BAD_ARG, "sdr_config.struct_size mismatch (ABI)");
+    if (cfg->hop != 0 && cfg->hop != cfg->block_size)  // (the group's device call takes [band][frame] batches per member)
+        return fail(SDR_ERR_BAD_ARG, "a group is not offered with hop < block_size (overlapped frames)");
     host::GroupRouting rt{cfg->n_bands, n_members};
     if (!rt.valid())
         return fail(SDR_ERR_BAD_ARG, "a group needs at least one member and at least one band per member");

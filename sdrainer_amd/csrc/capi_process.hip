@@ -95,7 +95,7 @@ int flush_late_attached(sdr_bank *b)
 
 // A failure after the first launch leaves the pipeline half enqueued (some stages of this batch ran, the
 // carried state of others did not advance): no later batch can be trusted, so the bank refuses further work.
-int process_device_impl(sdr_bank *b, const void *iq_dev, int n_frames, int in_stride, sdr::InFormat fmt)
+int process_device_impl(sdr_bank *b, const void *iq_dev, int n_frames, size_t in_stride, sdr::InFormat fmt)
 {
     if (b->failed)
         return fail(SDR_ERR_STATE, "an earlier process call failed half way; destroy the bank");
@@ -119,7 +119,7 @@ int process_device_impl(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
 // parts: PART_SPECTRA leaves the batch's listeners for a later PART_LISTEN call (sdr_defer_listen / sdr_process_listen:
 // the host binds listeners to peaks of this very batch in between, rx/receiver.go:409-426); the later call takes the
 // batch's set, length and first frame from b->pend.
-int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_stride, int capture_k, int capture_stage, int parts,
+int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in_stride, int capture_k, int capture_stage, int parts,
                         sdr::InFormat fmt)
 {
     const bool cap = capture_k >= 0;
@@ -248,7 +248,7 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, int in_st
         tap.used = S.tap_used.p;
         tap.steal = S.fft_ctr.p;
         tap.scratch = S.fft_scratch.p;
-        SDR_LAUNCH(sdr::K_FFT, sdr::launch_fft(b->logn, P.fft, fmt, iq_dev, cur, b->tw.p, S.psd.p, n_frames, B, in_stride, stride, tap,
+        SDR_LAUNCH(sdr::K_FFT, sdr::launch_fft(b->logn, P.fft, fmt, iq_dev, cur, b->tw.p, S.psd.p, n_frames, B, in_stride, b->hop, stride, tap,
                                                stream_of(sdr::K_FFT)));
     }
     SDR_DONE(sdr::K_FFT);
@@ -476,8 +476,7 @@ static int staging_ready(sdr_bank *b, bool raw)
 {
     const sdr_config &c = b->cfg;
     sdr_bank::Staging &st = b->stage[b->stage_cur];
-    const size_t per = 2 * (size_t)c.block_size;
-    const size_t frames = (size_t)c.max_batch_frames * (size_t)c.n_bands;
+    const size_t samples = b->stage_cap() * (size_t)c.n_bands;
     HIP_TRY(hipSetDevice(b->device));
     if (!b->copy_stream)
         HIP_TRY(hipStreamCreateWithFlags(&b->copy_stream, hipStreamNonBlocking));
@@ -486,14 +485,17 @@ static int staging_ready(sdr_bank *b, bool raw)
         HIP_TRY(hipEventCreateWithFlags(&st.consumed, hipEventDisableTiming));
     }
     if (!raw && !st.h_f32)
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&st.h_f32), sizeof(float) * per * frames, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&st.h_f32), sizeof(float) * 2 * samples, hipHostMallocDefault));
     if (raw && !st.h_raw)
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&st.h_raw), 2 * per * frames, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&st.h_raw), sizeof(int16_t) * 2 * samples, hipHostMallocDefault));
     return SDR_OK;
 }
-}  // namespace
 
-int sdr_push_iq(sdr_bank *b, int band, int sample_rate, const float *iq, size_t n_floats)
+// One push of `n_values` values (two per sample, `value_bytes` bytes each) of kind `kind` (sdr_bank::staged_kind) behind
+// what the band has staged.  The stream arrives in whole hops: at hop = block_size that is the reference's whole frames
+// (rx/receiver.go:323-326), below it a piece is any whole number of hops (host/overlap.h StreamStage).
+static int push_samples(sdr_bank *b, int band, int sample_rate, const void *iq, size_t n_values, int kind, size_t value_bytes,
+                        const char *mixed)
 {
     int rc = check_band(b, band);
     if (rc)
@@ -503,22 +505,31 @@ int sdr_push_iq(sdr_bank *b, int band, int sample_rate, const float *iq, size_t 
     const sdr_config &c = b->cfg;
     if (sample_rate != c.sample_rate)  // rx/receiver.go:319-322
         return fail(SDR_ERR_BAD_RATE, "wrong incoming sample rate");
-    const size_t per = 2 * (size_t)c.block_size;
-    if (n_floats == 0 || n_floats % per != 0)  // rx/receiver.go:323-326
-        return fail(SDR_ERR_BAD_SIZE, "wrong incoming block size");
-    const size_t nf = n_floats / per;
-    if ((size_t)b->staged[band] + nf > (size_t)c.max_batch_frames)  // rx/receiver.go:328-333
+    const size_t per = 2 * (size_t)b->hop;
+    if (n_values == 0 || n_values % per != 0)  // rx/receiver.go:323-326
+        return fail(SDR_ERR_BAD_SIZE, b->hop == c.block_size ? "wrong incoming block size" : "a push must hold a whole number of hops");
+    const size_t ns = n_values / 2;
+    sdr::StreamStage &ss = b->staged[band];
+    if (ss.would_drop(ns, c.max_batch_frames))  // rx/receiver.go:328-333
         return fail(SDR_ERR_WOULD_DROP, "IQ data skipped: staging queue full");
-    if (b->staged[band] > 0 && b->staged_kind[band] != 1)
-        return fail(SDR_ERR_STATE, "band already holds int16 frames (KiwiSDR or sc16) in this batch");
-    rc = staging_ready(b, false);
+    if (ss.staged > 0 && b->staged_kind[band] != kind)
+        return fail(SDR_ERR_STATE, mixed);
+    rc = staging_ready(b, kind != 1);
     if (rc)
         return rc;
-    b->staged_kind[band] = 1;
-    float *dst = b->stage[b->stage_cur].h_f32 + ((size_t)band * c.max_batch_frames + (size_t)b->staged[band]) * per;
-    staging_copy(dst, iq, sizeof(float) * n_floats);  // copy on push: the caller may reuse its buffer (kiwi/client.go:203)
-    b->staged[band] += (int)nf;
+    b->staged_kind[band] = kind;
+    sdr_bank::Staging &st = b->stage[b->stage_cur];
+    unsigned char *row = kind == 1 ? reinterpret_cast<unsigned char *>(st.h_f32) : st.h_raw;
+    staging_copy(row + ((size_t)band * b->stage_cap() + ss.staged) * 2 * value_bytes, iq,
+                 n_values * value_bytes);  // copy on push: the caller may reuse its buffer (kiwi/client.go:203)
+    ss.push(ns);
     return SDR_OK;
+}
+}  // namespace
+
+int sdr_push_iq(sdr_bank *b, int band, int sample_rate, const float *iq, size_t n_floats)
+{
+    return push_samples(b, band, sample_rate, iq, n_floats, 1, sizeof(float), "band already holds int16 frames (KiwiSDR or sc16) in this batch");
 }
 
 int sdr_push_kiwi_snd(sdr_bank *b, int band, int sample_rate, const uint8_t *payload, size_t n_bytes)
@@ -526,65 +537,32 @@ int sdr_push_kiwi_snd(sdr_bank *b, int band, int sample_rate, const uint8_t *pay
     int rc = check_band(b, band);
     if (rc)
         return rc;
+    if (b->hop != b->cfg.block_size)
+        return fail(SDR_ERR_STATE, "sdr_push_kiwi_snd is not offered on a bank with hop < block_size (overlapped frames)");
     if (!payload)
         return fail(SDR_ERR_BAD_ARG, "null payload");
-    const sdr_config &c = b->cfg;
-    if (sample_rate != c.sample_rate)
+    if (sample_rate != b->cfg.sample_rate)
         return fail(SDR_ERR_BAD_RATE, "wrong incoming sample rate");
     constexpr size_t kHeader = 17;  // flags, sequence, S-meter, GPS (kiwi/client.go:285-290)
-    const size_t per = 2 * (size_t)c.block_size * 2;  // bytes per frame: 2N int16
+    const size_t per = 2 * (size_t)b->cfg.block_size * 2;  // bytes per frame: 2N int16
     if (n_bytes <= kHeader || (n_bytes - kHeader) % per != 0)  // kiwi/kiwi.go:96-98 panics on a partial block
         return fail(SDR_ERR_BAD_SIZE, "SND payload does not hold whole frames");
-    const size_t nf = (n_bytes - kHeader) / per;
-    if ((size_t)b->staged[band] + nf > (size_t)c.max_batch_frames)
-        return fail(SDR_ERR_WOULD_DROP, "IQ data skipped: staging queue full");
-    if (b->staged[band] > 0 && b->staged_kind[band] != 2)
-        return fail(SDR_ERR_STATE, "band already holds float32 or sc16 frames in this batch");
-    rc = staging_ready(b, true);
-    if (rc)
-        return rc;
-    b->staged_kind[band] = 2;
-    staging_copy(b->stage[b->stage_cur].h_raw + ((size_t)band * c.max_batch_frames + (size_t)b->staged[band]) * per,
-                 payload + kHeader, n_bytes - kHeader);
-    b->staged[band] += (int)nf;
-    return SDR_OK;
+    return push_samples(b, band, sample_rate, payload + kHeader, (n_bytes - kHeader) / 2, 2, sizeof(int16_t),
+                        "band already holds float32 or sc16 frames in this batch");
 }
 
 // sc16 frames from the host: staged raw like a KiwiSDR payload (half the bytes of float32 go over PCIe) and converted on
 // the device by k_unpack_sc16 into the float32 staging buffer the FFT reads
 int sdr_push_iq_sc16(sdr_bank *b, int band, int sample_rate, const int16_t *iq, size_t n_values)
 {
-    int rc = check_band(b, band);
-    if (rc)
-        return rc;
-    if (!iq)
-        return fail(SDR_ERR_BAD_ARG, "null iq");
-    const sdr_config &c = b->cfg;
-    if (sample_rate != c.sample_rate)  // rx/receiver.go:319-322
-        return fail(SDR_ERR_BAD_RATE, "wrong incoming sample rate");
-    const size_t per = 2 * (size_t)c.block_size;  // int16 values per frame
-    if (n_values == 0 || n_values % per != 0)  // rx/receiver.go:323-326
-        return fail(SDR_ERR_BAD_SIZE, "wrong incoming block size");
-    const size_t nf = n_values / per;
-    if ((size_t)b->staged[band] + nf > (size_t)c.max_batch_frames)  // rx/receiver.go:328-333
-        return fail(SDR_ERR_WOULD_DROP, "IQ data skipped: staging queue full");
-    if (b->staged[band] > 0 && b->staged_kind[band] != 3)
-        return fail(SDR_ERR_STATE, "band already holds float32 or KiwiSDR frames in this batch");
-    rc = staging_ready(b, true);
-    if (rc)
-        return rc;
-    b->staged_kind[band] = 3;
-    staging_copy(b->stage[b->stage_cur].h_raw + ((size_t)band * c.max_batch_frames + (size_t)b->staged[band]) * per * 2, iq,
-                 sizeof(int16_t) * n_values);
-    b->staged[band] += (int)nf;
-    return SDR_OK;
+    return push_samples(b, band, sample_rate, iq, n_values, 3, sizeof(int16_t), "band already holds float32 or KiwiSDR frames in this batch");
 }
 
 int sdr_staged_frames(sdr_bank *b, int band)
 {
     if (check_band(b, band))
         return -1;
-    return b->staged[band];
+    return b->staged[band].frames();
 }
 
 int sdr_process_staged(sdr_bank *b, int *n_frames_out)
@@ -598,104 +576,147 @@ int sdr_process_staged_limit(sdr_bank *b, int max_frames, int *n_frames_out)
         return fail(SDR_ERR_BAD_ARG, "null bank");
     const sdr_config &c = b->cfg;
     int n = std::min(c.max_batch_frames, std::max(max_frames, 0));
-    for (int v : b->staged)
-        n = std::min(n, v);
+    for (const sdr::StreamStage &ss : b->staged)
+        n = std::min(n, ss.frames());
     if (n_frames_out)
         *n_frames_out = n;
     if (n == 0)
         return SDR_OK;
     HIP_TRY(hipSetDevice(b->device));
-    const size_t per = 2 * (size_t)c.block_size;
-    const size_t F = (size_t)c.max_batch_frames;
+    const size_t cap = b->stage_cap();  // samples per band row, pinned and device alike
+    const size_t overlap = (size_t)(c.block_size - b->hop);
     sdr_bank::Staging &st = b->stage[b->stage_cur];
     if (!st.d_f32.p) {
-        hipError_t e = st.d_f32.alloc(per * F * (size_t)c.n_bands);
+        hipError_t e = st.d_f32.alloc(2 * cap * (size_t)c.n_bands);
         if (e != hipSuccess)
             return fail(SDR_ERR_HIP, "hipMalloc iq staging failed");
     }
-    // upload on the copy stream, once the FFT of this set's previous batch has read the device buffer
+    // upload on the copy stream, once the FFT of this set's previous batch has read the device buffer.  Only what was
+    // pushed goes up: the first `history` samples of a band's device row are already there (the batch before left them)
     HIP_TRY(hipStreamWaitEvent(b->copy_stream, st.consumed, 0));
     for (int band = 0; band < c.n_bands; band++) {
-        float *dst = st.d_f32.p + (size_t)band * n * per;
+        const sdr::StreamStage &ss = b->staged[band];
+        const size_t up = sdr::span_samples(n, b->hop, c.block_size) - ss.history;  // samples
+        float *dst = st.d_f32.p + ((size_t)band * cap + ss.history) * 2;
         if (b->staged_kind[band] >= 2) {
             // raw int16 (KiwiSDR big-endian, or sc16): upload half the bytes, unpack in HBM (k_unpack.hip)
             if (!st.d_raw.p) {
-                hipError_t e = st.d_raw.alloc(2 * per * F * (size_t)c.n_bands);
+                hipError_t e = st.d_raw.alloc(4 * cap * (size_t)c.n_bands);
                 if (e != hipSuccess)
                     return fail(SDR_ERR_HIP, "hipMalloc raw staging failed");
             }
-            uint8_t *rdst = st.d_raw.p + (size_t)band * F * per * 2;
-            HIP_TRY(hipMemcpyAsync(rdst, st.h_raw + (size_t)band * F * per * 2, 2 * per * (size_t)n, hipMemcpyHostToDevice,
-                                   b->copy_stream));
+            uint8_t *rdst = st.d_raw.p + (size_t)band * cap * 4;
+            HIP_TRY(hipMemcpyAsync(rdst, st.h_raw + (size_t)band * cap * 4, 4 * up, hipMemcpyHostToDevice, b->copy_stream));
             if (b->staged_kind[band] == 2)
-                HIP_TRY(sdr::launch_unpack_be16(rdst, dst, per * (size_t)n, b->copy_stream));
+                HIP_TRY(sdr::launch_unpack_be16(rdst, dst, 2 * up, b->copy_stream));
             else
-                HIP_TRY(sdr::launch_unpack_sc16(reinterpret_cast<const int16_t *>(rdst), dst, per * (size_t)n, b->copy_stream));
+                HIP_TRY(sdr::launch_unpack_sc16(reinterpret_cast<const int16_t *>(rdst), dst, 2 * up, b->copy_stream));
         } else {
-            HIP_TRY(hipMemcpyAsync(dst, st.h_f32 + (size_t)band * F * per, sizeof(float) * per * (size_t)n, hipMemcpyHostToDevice,
-                                   b->copy_stream));
+            HIP_TRY(hipMemcpyAsync(dst, st.h_f32 + (size_t)band * cap * 2, sizeof(float) * 2 * up, hipMemcpyHostToDevice, b->copy_stream));
         }
     }
     HIP_TRY(hipEventRecord(st.uploaded, b->copy_stream));
     HIP_TRY(hipStreamWaitEvent(b->stream[S_FFT], st.uploaded, 0));
-    int rc = process_device_impl(b, st.d_f32.p, n, n);
+    int rc = process_device_impl(b, st.d_f32.p, n, cap);
     if (rc)
         return rc;
-    HIP_TRY(hipEventRecord(st.consumed, b->stream[S_FFT]));  // (behind the FFT launch: the only reader of d_f32)
-    // the caller goes on filling the next set; what this batch did not take moves to its front
     const int next = (b->stage_cur + 1) % sdr_bank::STAGE_RING;
     const int prev = b->stage_cur;
-    b->stage_cur = next;
-    bool any_left = false;
-    for (int band = 0; band < c.n_bands; band++)
-        any_left = any_left || b->staged[band] > n;
-    if (any_left) {
-        bool raw = false, f32 = false;
-        for (int band = 0; band < c.n_bands; band++)
-            if (b->staged[band] > n)
-                (b->staged_kind[band] >= 2 ? raw : f32) = true;
-        if (f32 && (rc = staging_ready(b, false)))
-            return rc;
-        if (raw && (rc = staging_ready(b, true)))
-            return rc;
+    if (overlap > 0) {
+        // The next batch's history: the last block_size - hop samples of the frames just consumed, from sample n * hop of
+        // every band's row to the front of the next set's - on the FFT stream, behind this batch's FFT (which reads this
+        // set) and behind the next set's last FFT (which read the rows written here; its later uploads write behind the
+        // history only).
+        sdr_bank::Staging &nx = b->stage[next];
+        if (!nx.d_f32.p) {
+            hipError_t e = nx.d_f32.alloc(2 * cap * (size_t)c.n_bands);
+            if (e != hipSuccess)
+                return fail(SDR_ERR_HIP, "hipMalloc iq staging failed");
+        }
+        HIP_TRY(hipMemcpy2DAsync(nx.d_f32.p, cap * 2 * sizeof(float), st.d_f32.p + (size_t)n * (size_t)b->hop * 2, cap * 2 * sizeof(float),
+                                 overlap * 2 * sizeof(float), (size_t)c.n_bands, hipMemcpyDeviceToDevice, b->stream[S_FFT]));
     }
+    HIP_TRY(hipEventRecord(st.consumed, b->stream[S_FFT]));  // (behind the FFT launch and the history copy: the only readers of d_f32)
+    // the caller goes on filling the next set; what this batch did not take moves to its front
+    b->stage_cur = next;
+    std::vector<sdr::StreamStage::Consumed> took((size_t)c.n_bands);
+    bool raw = false, f32 = false;
+    for (int band = 0; band < c.n_bands; band++) {
+        took[(size_t)band] = b->staged[band].consume(n);
+        if (took[(size_t)band].left > 0)
+            (b->staged_kind[band] >= 2 ? raw : f32) = true;
+    }
+    if (f32 && (rc = staging_ready(b, false)))
+        return rc;
+    if (raw && (rc = staging_ready(b, true)))
+        return rc;
     // the pinned buffers of the next set are free once ITS last upload has completed (two batches ago: a formality)
     if (b->stage[next].uploaded)
         HIP_TRY(hipEventSynchronize(b->stage[next].uploaded));
     for (int band = 0; band < c.n_bands; band++) {
-        const int left = b->staged[band] - n;
-        if (left > 0) {
+        const sdr::StreamStage::Consumed &t = took[(size_t)band];
+        if (t.left > 0) {
             if (b->staged_kind[band] >= 2)
-                memcpy(b->stage[next].h_raw + (size_t)band * F * per * 2, b->stage[prev].h_raw + ((size_t)band * F + (size_t)n) * per * 2,
-                       per * 2 * (size_t)left);
+                memcpy(b->stage[next].h_raw + (size_t)band * cap * 4, b->stage[prev].h_raw + ((size_t)band * cap + t.left_from) * 4, 4 * t.left);
             else
-                memcpy(b->stage[next].h_f32 + (size_t)band * F * per, b->stage[prev].h_f32 + ((size_t)band * F + (size_t)n) * per,
-                       sizeof(float) * per * (size_t)left);
+                memcpy(b->stage[next].h_f32 + (size_t)band * cap * 2, b->stage[prev].h_f32 + ((size_t)band * cap + t.left_from) * 2,
+                       sizeof(float) * 2 * t.left);
         } else {
             b->staged_kind[band] = 0;
         }
-        b->staged[band] = std::max(left, 0);
     }
     return SDR_OK;
 }
 
-int sdr_process_device(sdr_bank *b, const float *iq_dev, int n_frames)
+namespace {
+static int check_device_input(sdr_bank *b, const void *iq_dev)
 {
     if (!b || !iq_dev)
         return fail(SDR_ERR_BAD_ARG, "null argument");
     if (reinterpret_cast<uintptr_t>(iq_dev) & 15)
         return fail(SDR_ERR_BAD_ARG, "iq_dev must be 16-byte aligned (frames are copied to LDS 16 bytes per lane)");
-    return process_device_impl(b, iq_dev, n_frames, n_frames);
+    return SDR_OK;
 }
+static int process_device_dense(sdr_bank *b, const void *iq_dev, int n_frames, sdr::InFormat fmt)
+{
+    const int rc = check_device_input(b, iq_dev);
+    if (rc)
+        return rc;
+    if (b->hop != b->cfg.block_size)
+        return fail(SDR_ERR_STATE, "the bank's frames overlap (hop < block_size): [band][frame] input has no meaning, use sdr_process_device_stream");
+    return process_device_impl(b, iq_dev, n_frames, (size_t)std::max(n_frames, 0) * (size_t)b->cfg.block_size, fmt);
+}
+static int process_device_stream(sdr_bank *b, const void *iq_dev, int n_frames, size_t band_stride_samples, sdr::InFormat fmt)
+{
+    const int rc = check_device_input(b, iq_dev);
+    if (rc)
+        return rc;
+    if (band_stride_samples % 4 != 0)
+        return fail(SDR_ERR_BAD_ARG, "band_stride_samples must be a multiple of 4 samples (every band's stream 16-byte aligned)");
+    if (band_stride_samples < sdr::span_samples(n_frames, b->hop, b->cfg.block_size) || band_stride_samples > 0xffffffffu)
+        return fail(SDR_ERR_BAD_ARG, "band_stride_samples is smaller than (n_frames - 1) * hop + block_size (or beyond 2^32 - 1)");
+    return process_device_impl(b, iq_dev, n_frames, band_stride_samples, fmt);
+}
+}  // namespace
+
+int sdr_process_device(sdr_bank *b, const float *iq_dev, int n_frames) { return process_device_dense(b, iq_dev, n_frames, sdr::InFormat::F32); }
 
 int sdr_process_device_sc16(sdr_bank *b, const int16_t *iq_dev, int n_frames)
 {
-    if (!b || !iq_dev)
-        return fail(SDR_ERR_BAD_ARG, "null argument");
-    if (reinterpret_cast<uintptr_t>(iq_dev) & 15)
-        return fail(SDR_ERR_BAD_ARG, "iq_dev must be 16-byte aligned (frames are copied to LDS 16 bytes per lane)");
-    return process_device_impl(b, iq_dev, n_frames, n_frames, sdr::InFormat::SC16);
+    return process_device_dense(b, iq_dev, n_frames, sdr::InFormat::SC16);
 }
+
+int sdr_process_device_stream(sdr_bank *b, const float *iq_dev, int n_frames, size_t band_stride_samples)
+{
+    return process_device_stream(b, iq_dev, n_frames, band_stride_samples, sdr::InFormat::F32);
+}
+
+int sdr_process_device_stream_sc16(sdr_bank *b, const int16_t *iq_dev, int n_frames, size_t band_stride_samples)
+{
+    return process_device_stream(b, iq_dev, n_frames, band_stride_samples, sdr::InFormat::SC16);
+}
+
+int sdr_hop(sdr_bank *b) { return b ? b->hop : -1; }
 
 
 // ---- deferred listen half: strain-mode discovery without a host round trip per cumulation -----------------------
@@ -727,7 +748,7 @@ int sdr_process_listen(sdr_bank *b)
         return fail(SDR_ERR_STATE, "an earlier process call failed half way; destroy the bank");
     if (!b->listen_pending)
         return fail(SDR_ERR_STATE, "no batch waits for its listen half");
-    const int rc = process_device_body(b, nullptr, b->pend.frames, b->pend.frames, -1, -1, PART_LISTEN);
+    const int rc = process_device_body(b, nullptr, b->pend.frames, 0, -1, -1, PART_LISTEN);  // (no FFT: no input)
     if (rc == SDR_ERR_HIP)
         b->failed = true;
     return rc;

@@ -132,9 +132,11 @@ SDR_HD inline double dit_to_wpm(double tickSeconds, double ditTicks)  // :197-20
 }
 SDR_HD inline double dit_to_wpm(const DecoderState &d, double ditTicks) { return dit_to_wpm(d.tickSeconds, ditTicks); }
 
-SDR_HD inline void decoder_init(DecoderState &d, int sampleRate, int blockSize)  // NewDecoder :131-147
+// tickSamples: samples between two ticks - the reference's blockSize; with overlapped frames the bank's hop (a tick is
+// time, not a frame's length)
+SDR_HD inline void decoder_init(DecoderState &d, int sampleRate, int tickSamples)  // NewDecoder :131-147
 {
-    d.tickSeconds = (double)blockSize / (double)sampleRate;
+    d.tickSeconds = (double)tickSamples / (double)sampleRate;
     d.ticks = 0;
     d.onStart = 0;
     d.offStart = 0;

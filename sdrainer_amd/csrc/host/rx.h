@@ -387,6 +387,33 @@ private:
     std::vector<Deferred> deferred_;
 };
 
+// The time of a frame on the stream clock.  One frame advances the clock by tickSamples / sampleRate: the reference's
+// blockSize / sampleRate, and with overlapped frames (sdr_config.hop) the hop - time, not a frame's length.  Attachment and
+// silence time-outs, segmentLimit and the ageing of the PeaksTable all read the clock this sets.
+struct FrameTiming {
+    int sampleRate = 1, tickSamples = 1;
+    double tick() const { return (double)tickSamples / (double)sampleRate; }
+    double frameTime(int64_t f) const { return (double)(f + 1) * (double)tickSamples / (double)sampleRate; }
+    bool firesAt(const Listener &l, int64_t f) const  // Listener.TimeoutExceeded with the clock at frame f
+    {
+        const double now = frameTime(f);
+        return (now - l.LastAttach() > l.AttachmentTimeout()) || (now - l.LastWrite() > l.SilenceTimeout());
+    }
+    // first frame >= from at which the listener's time-out fires if it writes nothing more
+    int64_t earliestExpiry(const Listener &l, int64_t from) const
+    {
+        const double T = tick();
+        const double due = std::min(l.LastAttach() + l.AttachmentTimeout(), l.LastWrite() + l.SilenceTimeout());
+        if (!(due < 1e18))
+            return INT64_MAX;
+        int64_t f = (int64_t)std::floor(due / T);  // (f + 1) * T > due  <=>  f + 1 > due / T
+        f = std::max(f - 2, from);                 // settle rounding with the predicate itself
+        while (!firesAt(l, f))
+            f++;
+        return f;
+    }
+};
+
 class ListenerPool {  // :180-270
 public:
     using Factory = std::function<std::shared_ptr<Listener>(const std::string &id)>;
@@ -606,7 +633,8 @@ public:
             peaks_->SetRand(rand_);
     }
 
-    int Start(int sampleRate, int blockSize, int maxBatchFrames = 256, int deviceId = 0)  // :130-146
+    // hop: samples from one frame's start to the next (sdr_config.hop; 0 = blockSize: the reference's frames)
+    int Start(int sampleRate, int blockSize, int maxBatchFrames = 256, int deviceId = 0, int hop = 0)  // :130-146
     {
         if (bank_)
             return SDR_OK;
@@ -623,11 +651,14 @@ public:
         cfg.max_peaks = blockSize / 2;
         cfg.find_peaks = mode_ == StrainMode;
         cfg.device_id = deviceId;
+        cfg.hop = hop;
         int rc = sdr_create(&cfg, &bank_);
         if (rc != SDR_OK)
             return rc;
         sampleRate_ = sampleRate;
         blockSize_ = blockSize;
+        hop_ = sdr_hop(bank_);
+        timing_ = FrameTiming{sampleRate, hop_};
         maxBatchFrames_ = maxBatchFrames;
         sdr_set_center_frequency(bank_, 0, centerFrequency_);
         // results arrive in bulk, one sdr_poll per processed segment (no per-listener reads, no pipeline drain)
@@ -693,13 +724,14 @@ public:
     }
 
     // The frame case of run() (:353-463) for everything staged so far (IQData), or for `n_frames` frames already
-    // in device memory ([frame][2 * blockSize] float32, 16-byte aligned).  The stream is processed in segments;
+    // in device memory ([frame][2 * blockSize] float32, 16-byte aligned; a receiver started with a hop: one stream of
+    // (n_frames - 1) * hop + blockSize samples, frame f from sample f * hop on).  The stream is processed in segments;
     // where a segment ends is what keeps the per-frame semantics of the reference (:388-426) although the
     // device works on many frames per call:
     //  * strain mode with a free listener: at every cumulation boundary, where the reference binds a new
     //    listener that must start listening with the very next frame (:409-426);
     //  * any listener: at the earliest frame its attachment or silence time-out can fire (:396-400).  With the
-    //    stream clock (frame f happens at (f + 1) * blockSize / sampleRate) that frame is known: the attachment
+    //    stream clock (frame f happens at (f + 1) * hop / sampleRate: FrameTiming) that frame is known: the attachment
     //    expiry exactly, the silence expiry as "no rune from now on" - runes only postpone it, and every rune
     //    comes back stamped with the frame of its Write (text_processor.go:208-209), so the check after the
     //    segment is the reference's check at exactly that frame.  With a caller-supplied clock the time of a
@@ -738,7 +770,9 @@ public:
             const int n = segmentLimit(n_frames - done);
             int rc = sdr_defer_listen(bank_, speculative_ ? 1 : 0);
             if (rc == SDR_OK)
-                rc = sdr_process_device(bank_, iq_dev + (size_t)done * 2 * (size_t)blockSize_, n);
+                rc = hop_ == blockSize_ ? sdr_process_device(bank_, iq_dev + (size_t)done * 2 * (size_t)blockSize_, n)
+                                        : sdr_process_device_stream(bank_, iq_dev + (size_t)done * 2 * (size_t)hop_, n,
+                                                                    (size_t)(n - 1) * (size_t)hop_ + (size_t)blockSize_);
             if (rc != SDR_OK)
                 return rc;
             rc = segmentLaunched(n);
@@ -840,25 +874,9 @@ private:
         listener->Attach(peak, dev);
         return SDR_OK;
     }
-    double frameTime(int64_t f) const { return (double)(f + 1) * (double)blockSize_ / (double)sampleRate_; }
-    bool firesAt(const Listener &l, int64_t f) const  // Listener.TimeoutExceeded with the clock at frame f
-    {
-        const double now = frameTime(f);
-        return (now - l.LastAttach() > l.AttachmentTimeout()) || (now - l.LastWrite() > l.SilenceTimeout());
-    }
-    // first frame >= from at which the listener's time-out fires if it writes nothing more
-    int64_t earliestExpiry(const Listener &l, int64_t from) const
-    {
-        const double T = (double)blockSize_ / (double)sampleRate_;
-        const double due = std::min(l.LastAttach() + l.AttachmentTimeout(), l.LastWrite() + l.SilenceTimeout());
-        if (!(due < 1e18))
-            return INT64_MAX;
-        int64_t f = (int64_t)std::floor(due / T);  // (f + 1) * T > due  <=>  f + 1 > due / T
-        f = std::max(f - 2, from);                 // settle rounding with the predicate itself
-        while (!firesAt(l, f))
-            f++;
-        return f;
-    }
+    // (the stream clock's arithmetic is FrameTiming's: a frame advances it by hop / sampleRate)
+    double frameTime(int64_t f) const { return timing_.frameTime(f); }
+    int64_t earliestExpiry(const Listener &l, int64_t from) const { return timing_.earliestExpiry(l, from); }
     // how many of `available` frames the next device call may take
     int segmentLimit(int available)
     {
@@ -877,7 +895,7 @@ private:
         if (hunting && !speculative_)
             limit = std::min(limit, until_boundary);
         if (speculative_) {
-            const double T = (double)blockSize_ / (double)sampleRate_;
+            const double T = timing_.tick();
             const double shortest = std::min(attachmentTimeout_, silenceTimeout_);
             if (shortest < 1e17) {
                 // bound at frame b (clock frameTime(b)), it fires at the first f with (f - b) * T > shortest
@@ -1115,7 +1133,8 @@ private:
     Fanout fanout_;
     float peakThreshold_ = SDR_DEFAULT_PEAK_THRESHOLD;
     int edgeWidth_ = SDR_DEFAULT_EDGE_WIDTH;
-    int sampleRate_ = 0, blockSize_ = 0;
+    int sampleRate_ = 0, blockSize_ = 0, hop_ = 0;
+    FrameTiming timing_;
     int64_t centerFrequency_ = 0, vfoOffset_ = 0;
     double silenceTimeout_ = kDefaultSilenceTimeout, attachmentTimeout_ = kDefaultAttachmentTimeout;
     sdr_bank *bank_ = nullptr;

@@ -24,21 +24,21 @@ __device__ __forceinline__ fft64::cplx tw_load(const fft64::cplx *__restrict__ t
 // p = w G .. w G + G - 1 (blocks k = brev_B(p)).  Y: [band][group frames][N].
 template <int LOGN, InFormat FMT>
 __global__ __launch_bounds__(fft2p::T) void k_fft2p_a(const void *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
-                                                      const fft64::cplx *__restrict__ tw, fft64::cplx *__restrict__ y, int in_stride,
-                                                      int frame0, int group)
+                                                      const fft64::cplx *__restrict__ tw, fft64::cplx *__restrict__ y, size_t in_stride,
+                                                      int frame_stride, int frame0, int group)
 {
     using PH = fft2p::Phases<LOGN>;
     using S = typename PH::SA;
     constexpr int N = PH::N, MB = PH::A;
     __shared__ double lr[S::G * S::LDS_ROW], li[S::G * S::LDS_ROW];
     const int fl = blockIdx.x / PH::WG_A, w = blockIdx.x % PH::WG_A, band = blockIdx.y, t = threadIdx.x;
-    const size_t frame_row = (size_t)band * in_stride + frame0 + fl;
+    const size_t frame_at = input_sample_offset(band * in_stride, (unsigned)(frame0 + fl), frame_stride);  // (samples)
     const auto W = [tw](int i) { return tw_load(tw, i); };
     double xr[fft2p::R], xi[fft2p::R];
     {
         const int gl = fft2p::p0_sub<MB>(t), p = w * S::G + gl;
         if constexpr (FMT == InFormat::F32) {
-            const float2 *__restrict__ iq = reinterpret_cast<const float2 *>(cur ? cur->iq : static_cast<const float *>(iq_arg)) + frame_row * N;
+            const float2 *__restrict__ iq = reinterpret_cast<const float2 *>(cur ? cur->iq : static_cast<const float *>(iq_arg)) + frame_at;
 #pragma unroll
             for (int s = 0; s < fft2p::R; s++) {
                 const float2 v = iq[fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s))];
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(fft2p::T) void k_fft2p_a(const void *__restrict__ i
                 xi[s] = (double)v.y;
             }
         } else {
-            const uint32_t *__restrict__ iq = reinterpret_cast<const uint32_t *>(cur ? cur->iq_sc16 : static_cast<const int16_t *>(iq_arg)) + frame_row * N;
+            const uint32_t *__restrict__ iq = reinterpret_cast<const uint32_t *>(cur ? cur->iq_sc16 : static_cast<const int16_t *>(iq_arg)) + frame_at;
 #pragma unroll
             for (int s = 0; s < fft2p::R; s++) {
                 const uint32_t v = iq[fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s))];
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(fft2p::T) void k_fft2p_b(const fft64::cplx *__restr
 
 template <int LOGN>
 static hipError_t launch_fft2p_t(FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                                 int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+                                 int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
     using PH = fft2p::Phases<LOGN>;
     if (n_frames <= 0 || n_bands <= 0)
@@ -168,10 +168,10 @@ static hipError_t launch_fft2p_t(FftChoice fft, InFormat fmt, const void *iq, co
         const int g = n_frames - f0 < group ? n_frames - f0 : group;
         if (fmt == InFormat::SC16)
             hipLaunchKernelGGL((k_fft2p_a<LOGN, InFormat::SC16>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
-                               tap.scratch, in_stride, f0, group);
+                               tap.scratch, in_stride, frame_stride, f0, group);
         else
             hipLaunchKernelGGL((k_fft2p_a<LOGN, InFormat::F32>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
-                               tap.scratch, in_stride, f0, group);
+                               tap.scratch, in_stride, frame_stride, f0, group);
         if (f0 + group >= n_frames)
             t_done_event = done;
         launch_kernel((k_fft2p_b<LOGN>), dim3(g * PH::WG_B, n_bands), dim3(fft2p::T), 0, stream, static_cast<const fft64::cplx *>(tap.scratch),
@@ -182,11 +182,11 @@ static hipError_t launch_fft2p_t(FftChoice fft, InFormat fmt, const void *iq, co
 }
 
 hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                         int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+                         int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
     switch (logn) {
-    case 15: return launch_fft2p_t<15>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 16: return launch_fft2p_t<16>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 15: return launch_fft2p_t<15>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+    case 16: return launch_fft2p_t<16>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
     default: return hipErrorInvalidValue;
     }
 }

@@ -432,7 +432,7 @@ constexpr int kPfSinkBytes = SDR_FFT_PF_DIST > 0 ? 4096 : 0;
 template <int LOGN, bool MULTI>
 __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 ? 4 : 1)) void k_fft_psd(const float *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
                                                                   const fft64::cplx *__restrict__ tw,
-                                                                  float *__restrict__ psd, int in_stride, int out_stride,
+                                                                  float *__restrict__ psd, size_t in_stride, int frame_stride, int out_stride,
                                                                   int n_frames, int fpw, const int *__restrict__ tap_bins,
                                                                   float *__restrict__ tap_out, int n_tap, int tap_stride)
 {
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
     const float *__restrict__ iq = cur ? cur->iq : iq_arg;  // graph replay: the batch's input pointer lives in device memory
     const int frame0 = MULTI ? blockIdx.x * fpw : blockIdx.x;
     const int frame_end = MULTI ? min(frame0 + fpw, n_frames) : frame0 + 1;
-    const size_t in_band = (size_t)blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
+    const size_t in_band = blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
     constexpr bool PRIV = private_stage<LOGN>();
     const int ltid = logical_thread<LOGN>((int)threadIdx.x);
     const int wave = __builtin_amdgcn_readfirstlane(ltid >> 6);
@@ -474,12 +474,12 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
         constexpr int ROWS_PER_WAVE = PL::R / 2;
         const int lane = tid & 63;
 #if defined(SDR_ABLATE) && (SDR_ABLATE == 8)
-        const size_t fr = (in_band + frame) & 15;  // timing-only: 16 frames, L2-resident
+        const size_t fr = (size_t)((blockIdx.y * (in_stride / PL::N) + frame) & 15) * PL::N;  // timing-only: 16 frames, L2-resident
 #else
-        const size_t fr = in_band + frame;
+        const size_t fr = input_sample_offset(in_band, frame, frame_stride);
 #endif
         // buffer form: row in the scalar offset, granule in one 32-bit VGPR - no 64-bit per-lane addresses
-        const rsrc_t xrs = make_rsrc(iq + fr * PL::N * 2, PL::N * 8u);
+        const rsrc_t xrs = make_rsrc(iq + fr * 2, PL::N * 8u);
         if constexpr (PRIV) {
             const unsigned voff = (unsigned)(fft64::input_sample<LOGN>((tid & ~63) | (2 * (lane & 31)), 0) +
                                              ((lane >> 5) ? fft64::input_slot_sample<LOGN>(1) : 0)) * 8u;
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
         if constexpr (REGS) {
             // dsp/fft.go:59-69 setSamplesFromIQ: slot m <- sample input_sample(t, m): the thread's part of the sample
             // number in the per-lane offset, the slot's in the scalar offset; 8 bytes per lane, four lanes per 32-byte run
-            const rsrc_t xrs = make_rsrc(iq + (in_band + frame) * PL::N * 2, PL::N * 8u);
+            const rsrc_t xrs = make_rsrc(iq + input_sample_offset(in_band, frame, frame_stride) * 2, PL::N * 8u);
             const unsigned voff = (unsigned)fft64::input_sample<LOGN>(t, 0) * 8u;
             u32x2 raw[PL::R];
 #pragma unroll
@@ -676,7 +676,7 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
 template <int LOGN>
 __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 ? 4 : 1)) void k_fft_psd_sc16(const int16_t *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
                                                                        const fft64::cplx *__restrict__ tw, float *__restrict__ psd,
-                                                                       int in_stride, int out_stride, const int *__restrict__ tap_bins,
+                                                                       size_t in_stride, int frame_stride, int out_stride, const int *__restrict__ tap_bins,
                                                                        float *__restrict__ tap_out, int n_tap, int tap_stride)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -690,7 +690,7 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
 #endif
     const int16_t *__restrict__ iq = cur ? cur->iq_sc16 : iq_arg;  // graph replay: the batch's input pointer lives in device memory
     const int frame = blockIdx.x;
-    const size_t in_band = (size_t)blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
+    const size_t in_band = blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
     const int t = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     {
@@ -698,7 +698,7 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
         // the source address, the DMA writes lane p's 16 bytes at row base + 16 p)
         constexpr int ROWS_PER_WAVE = PL::R / 4;
         const int lane = t & 63;
-        const rsrc_t xrs = make_rsrc(iq + (in_band + frame) * PL::N * 2, PL::N * 4u);
+        const rsrc_t xrs = make_rsrc(iq + input_sample_offset(in_band, frame, frame_stride) * 2, PL::N * 4u);
 #pragma unroll
         for (int j = 0; j < ROWS_PER_WAVE; j++) {
             const int r = wave * ROWS_PER_WAVE + j;
@@ -837,7 +837,7 @@ __device__ __forceinline__ void store_psd_b(const double (&xr)[fft64::Plan<LOGN>
 template <int LOGN>
 __global__ __launch_bounds__(fft64::Plan<LOGN>::T, 4) void k_fft_psd_b(const float *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
                                                                         const fft64::cplx *__restrict__ tw, float *__restrict__ psd,
-                                                                        int in_stride, int out_stride, int n_frames, int fpw,
+                                                                        size_t in_stride, int frame_stride, int out_stride, int n_frames, int fpw,
                                                                         const int *__restrict__ tap_bins, float *__restrict__ tap_out,
                                                                         int n_tap, int tap_stride)
 {
@@ -863,7 +863,7 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, 4) void k_fft_psd_b(const flo
     const float *__restrict__ iq = cur ? cur->iq : iq_arg;
     const int frame0 = blockIdx.x * fpw;
     const int frame_end = min(frame0 + fpw, n_frames);
-    const size_t in_band = (size_t)blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
+    const size_t in_band = blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int kBlock = PL::R * 64 * 8;  // bytes of staging per wave: its 16 slots x 64 samples
@@ -876,11 +876,11 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, 4) void k_fft_psd_b(const flo
             return;
 #endif
 #if defined(SDR_ABLATE) && (SDR_ABLATE == 8)
-        const size_t fr = (in_band + frame) & 15;  // timing-only: 16 frames, L2-resident
+        const size_t fr = (size_t)((blockIdx.y * (in_stride / PL::N) + frame) & 15) * PL::N;  // timing-only: 16 frames, L2-resident
 #else
-        const size_t fr = in_band + frame;
+        const size_t fr = input_sample_offset(in_band, frame, frame_stride);
 #endif
-        const rsrc_t xrs = make_rsrc(iq + fr * PL::N * 2, PL::N * 8u);
+        const rsrc_t xrs = make_rsrc(iq + fr * 2, PL::N * 8u);
         const int lane = tid & 63;
         // sample of (lane 2g, this wave, slot h): the slot's odd bit h = lane >> 5 selects sample bit 13
         const unsigned voff = (unsigned)(fft64::input_sample<LOGN>((tid & ~63) | (2 * (lane & 31)), 0) + ((lane >> 5) ? fft64::input_slot_sample<LOGN>(1) : 0)) * 8u;
@@ -1011,7 +1011,7 @@ inline constexpr int kLdsBytesB = fft64::kLdsBytes<LOGN> > fft64::Plan<LOGN>::N 
 
 template <int LOGN>
 static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                               int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+                               int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
     using PL = fft64::Plan<LOGN>;
     const float *iq = static_cast<const float *>(iq_in);
@@ -1030,7 +1030,7 @@ static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, c
         while (fpw > 1 && (long)((n_frames + fpw - 1) / fpw) * n_bands < 256)
             fpw /= 2;
         launch_kernel((k_fft_psd_b<LOGN>), dim3((n_frames + fpw - 1) / fpw, n_bands), dim3(PL::T), kLdsBytesB<LOGN>, stream, iq, cur, tw, psd,
-                      in_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride);
+                      in_stride, frame_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride);
         return hipGetLastError();
     } else {
     static LdsLimitOnce lds_once;
@@ -1046,7 +1046,7 @@ static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, c
     if (fmt == InFormat::SC16) {
         // one frame per workgroup, always (FftChoice::fpw is the float32 kernel's)
         launch_kernel((k_fft_psd_sc16<LOGN>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, stream,
-                      static_cast<const int16_t *>(iq_in), cur, tw, psd, in_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride);
+                      static_cast<const int16_t *>(iq_in), cur, tw, psd, in_stride, frame_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride);
         return hipGetLastError();
     }
     // a workgroup's frames are consecutive; never fewer workgroups than CUs can take (a short batch keeps one
@@ -1056,45 +1056,45 @@ static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, c
         fpw /= 2;
     if (fpw > 1)
         launch_kernel((k_fft_psd<LOGN, true>), dim3((n_frames + fpw - 1) / fpw, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN>, stream,
-                           iq, cur, tw, psd, in_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride);
+                           iq, cur, tw, psd, in_stride, frame_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride);
     else
         launch_kernel((k_fft_psd<LOGN, false>), dim3(n_frames, n_bands), dim3(PL::T),
                            fft64::kLdsBytes<LOGN> + tap_lds + kPfSinkBytes, stream, iq, cur, tw, psd, in_stride,
-                           out_stride, n_frames, 1, tap.bins, tap.out, tap.n, tap.stride);
+                           frame_stride, out_stride, n_frames, 1, tap.bins, tap.out, tap.n, tap.stride);
     return hipGetLastError();
     }
 }
 
 // The bank's twiddle buffer for N = 16384 holds both kernels' tables, the 32-point kernel's behind the other.
 hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                      int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+                      int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
     if (fmt != InFormat::F32 && fmt != InFormat::SC16)
         return hipErrorInvalidValue;
     if (fft.two_phase)
-        return launch_fft_2p(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+        return launch_fft_2p(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
     if (fft.r32) {
         if (logn != 14)
             return hipErrorInvalidValue;
         const fft64::cplx *tw32 = tw + fft64::Plan<14>::TW_TOTAL;
         if (fmt == InFormat::SC16)
-            return launch_fft_r32_sc16(static_cast<const int16_t *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-        return launch_fft_r32(static_cast<const float *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+            return launch_fft_r32_sc16(static_cast<const int16_t *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+        return launch_fft_r32(static_cast<const float *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
     }
     switch (logn) {
-    case 9: return launch_fft_t<9>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 10: return launch_fft_t<10>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 11: return launch_fft_t<11>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 12: return launch_fft_t<12>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 13: return launch_fft_t<13>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
-    case 14: return launch_fft_t<14>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    case 9: return launch_fft_t<9>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+    case 10: return launch_fft_t<10>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+    case 11: return launch_fft_t<11>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+    case 12: return launch_fft_t<12>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+    case 13: return launch_fft_t<13>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+    case 14: return launch_fft_t<14>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
     default: return hipErrorInvalidValue;
     }
 }
 hipError_t launch_fft(int logn, FftChoice fft, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
-                      int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream)
+                      int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
-    return launch_fft(logn, fft, InFormat::F32, iq, cur, tw, psd, n_frames, n_bands, in_stride, out_stride, tap, stream);
+    return launch_fft(logn, fft, InFormat::F32, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
 }
 
 int twiddle_count(int logn)

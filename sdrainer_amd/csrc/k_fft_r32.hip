@@ -30,6 +30,14 @@
 // loads per thread are dealt over the frame by the same plan - 4 bytes per lane, 256 contiguous bytes per wave instruction
 // - and the samples are converted (sc16::to_f32) where the float32 kernel widens.  Everything else is the float32
 // kernel's.  Its own translation unit keeps the float32 kernel's source, and so its code, exactly as it was.
+//
+// Overlapped frames (a frame stride below N: host/overlap.h).  The frame loop has no scalar register left for a stride:
+// one more live SGPR, even packed into the word that holds the frame count, is one SGPR spilled.  So the kernels above
+// keep their dense frames (frame f at sample f * N of the band, a constant shift) and k_fft_r32_hop.hip /
+// k_fft_r32_hop_sc16.hip compile this file again with SDR_R32_HOP = 1: k_fft_r32_hop(_sc16) take the stride as a shift
+// (every hop is a power of two) beside the frame count, fold it into the scalar base of the frame's buffer descriptor
+// and pay that one spilled SGPR (into a vector register's lane: no scratch).  launch_fft_r32(_sc16) hand a launch with
+// frame_stride != N on to them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,13 +49,27 @@
 #if !defined(SDR_R32_SC16)
 #define SDR_R32_SC16 0
 #endif
+#if !defined(SDR_R32_HOP)
+#define SDR_R32_HOP 0
+#endif
 #if SDR_R32_SC16
 #include "sc16.h"
-#define SDR_R32_KERNEL k_fft_r32_sc16
 #define SDR_R32_IN int16_t
 #else
-#define SDR_R32_KERNEL k_fft_r32
 #define SDR_R32_IN float
+#endif
+#if SDR_R32_HOP && SDR_R32_SC16
+#define SDR_R32_KERNEL k_fft_r32_hop_sc16
+#define SDR_R32_LAUNCH launch_fft_r32_hop_sc16
+#elif SDR_R32_HOP
+#define SDR_R32_KERNEL k_fft_r32_hop
+#define SDR_R32_LAUNCH launch_fft_r32_hop
+#elif SDR_R32_SC16
+#define SDR_R32_KERNEL k_fft_r32_sc16
+#define SDR_R32_LAUNCH launch_fft_r32_sc16
+#else
+#define SDR_R32_KERNEL k_fft_r32
+#define SDR_R32_LAUNCH launch_fft_r32
 #endif
 
 #if !defined(SDR_R32_IN_AUX)
@@ -177,6 +199,8 @@ constexpr int kSoftCounters = 4;
 // the band's frame counters' address and the grid's width, kept here rather than in SGPRs through the frame loop (the
 // frame has no scalar registers to spare: held there they pushed nine scalar registers out into vector-register lanes)
 constexpr int kStashWords = 4;
+// k_fft_r32's frames_and_shift argument: frames of the launch in the low kFrameBits bits, log2 of the frame stride above
+constexpr int kFrameBits = 26;
 // the frame claimed for the frame after next, one word per thread (only thread 0's is a claim: see claim_next)
 constexpr int kClaimBytes = fft32::T * 4;
 constexpr int kLdsBytes = fft32::kExchangeBytes + kTw1LdsBytes + (kSoftCounters + kStashWords) * 4 + kClaimBytes;
@@ -260,8 +284,9 @@ __device__ __forceinline__ void ex_read(double (&x)[32], int t, const double *ar
 // and graph replay re-runs the same arguments: nothing on the host has to reset them).
 
 __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
-                                                          const cplx *__restrict__ tw, float *__restrict__ psd, int in_stride,
-                                                          int out_stride, int n_frames, unsigned *__restrict__ steal, const int *__restrict__ tap_bins,
+                                                          const cplx *__restrict__ tw, float *__restrict__ psd, unsigned in_stride,
+                                                          int out_stride, unsigned frames_and_shift /* (dense: the frame count alone) */,
+                                                          unsigned *__restrict__ steal, const int *__restrict__ tap_bins,
                                                           float *__restrict__ tap_out, int n_tap, int tap_stride,
                                                           float *__restrict__ tap_wide, int *__restrict__ tap_used)
 {
@@ -275,11 +300,21 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
 #else
     const float *__restrict__ iq = cur ? cur->iq : iq_arg;  // graph replay: the batch's input pointer lives in device memory
 #endif
-    const unsigned n_fr = (unsigned)n_frames;
+#if SDR_R32_HOP
+    // Frame f starts at sample f << shift of the band (log2 hop).  The shift rides in the top bits of the word that holds
+    // the frame count; both are taken out of it with scalar temporaries where a frame is claimed or fetched (kFrameBits).
+    const unsigned fr_sh = frames_and_shift;
+    auto n_fr = [fr_sh] { return fr_sh & ((1u << kFrameBits) - 1); };
+    auto frame_at = [fr_sh](unsigned frame) { return ((size_t)frame << (fr_sh >> kFrameBits)) << 1; };  // (in floats / int16 values)
+#else
+    const unsigned n_frames_u = frames_and_shift;
+    auto n_fr = [n_frames_u] { return n_frames_u; };
+    auto frame_at = [](unsigned frame) { return (size_t)frame * N * 2; };
+#endif
     constexpr unsigned kNoFrame = ~0u;  // (no frame: the row of `prev` in front of the first)
     // this band's rows (four bases in eight SGPRs; with the bands' offsets kept beside the bases it was twelve)
     const size_t out_band = (size_t)blockIdx.y * out_stride;
-    const SDR_R32_IN *const iq_b = iq + (size_t)blockIdx.y * in_stride * (size_t)N * 2;
+    const SDR_R32_IN *const iq_b = iq + (size_t)blockIdx.y * in_stride * 2;
     float *const psd_b = psd + out_band * (size_t)N, *const tap_b = tap_out + out_band * (size_t)tap_stride;
     float *const wide_b = tap_wide ? tap_wide + out_band * (size_t)(4 * tap_stride) : nullptr;
     const int tid = threadIdx.x;
@@ -296,16 +331,16 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
     // slots [m0, m1) of `frame`; a claim past the batch gets a descriptor of zero bytes: the loads return zeros without
     // touching memory, and the frame's code stays free of branches
     auto fetch = [&](unsigned frame, int t, int m0, int m1) {
-        const bool live = frame < n_fr;
+        const bool live = frame < n_fr();
 #if SDR_R32_SC16
-        const rsrc_t xrs = make_rsrc(iq_b + (size_t)frame * N * 2, live ? N * kSampleBytes : 0u);
+        const rsrc_t xrs = make_rsrc(iq_b + frame_at(frame), live ? N * kSampleBytes : 0u);
         const unsigned voff = (unsigned)thread_sample(t) * kSampleBytes;
 #pragma unroll
         for (int m = 0; m < R; m++)
             if (m >= m0 && m < m1)
                 pf[m] = __builtin_amdgcn_raw_buffer_load_b32(xrs, voff, slot_sample(m) * (int)kSampleBytes, SDR_R32_IN_AUX);
 #else
-        const rsrc_t xrs = make_rsrc(iq_b + (size_t)frame * N * 2, live ? N * 8u : 0u);
+        const rsrc_t xrs = make_rsrc(iq_b + frame_at(frame), live ? N * 8u : 0u);
         const unsigned voff = (unsigned)thread_sample(t) * 8u;
 #pragma unroll
         for (int m = 0; m < R; m++)
@@ -371,7 +406,7 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
     // came out as the next run's LDS address, which the compiler had put into the first data register behind the store.)
     // stores [j0, j1) of the eight (tap: the tap value with the last one)
     auto flush_row = [&](unsigned frame, int t, int j0, int j1) {
-        const bool live = frame < n_fr;
+        const bool live = frame < n_fr();
         const rsrc_t pdr = make_rsrc(psd_b + (size_t)frame * N, live ? N * 4u : 0u);
 #pragma unroll
         for (int j = 0; j < N / 4 / T; j++)
@@ -400,7 +435,7 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
 #endif
     int it = 0;  // frames this workgroup has finished (the soft barriers' targets count in it)
 #pragma nounroll
-    while (frame < n_fr) {
+    while (frame < n_fr()) {
         // (everything derived from the thread id is loop-invariant; hoisted, it would sit in registers the frame needs)
         int t = tid;
         asm volatile("" : "+v"(t));
@@ -622,7 +657,7 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
 
 }  // namespace r32
 
-#if !SDR_R32_SC16
+#if !SDR_R32_SC16 && !SDR_R32_HOP
 int r32_twiddle_count() { return fft32::kTwTotal; }
 void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out) { fft32::build_twiddles(wre, wim, out); }
 #endif
@@ -633,13 +668,8 @@ void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out) 
 #define SDR_R32_RESERVE 0
 #endif
 
-#if SDR_R32_SC16
-hipError_t launch_fft_r32_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                               int in_stride, int out_stride, FftTap tap, hipStream_t stream)
-#else
-hipError_t launch_fft_r32(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                          int in_stride, int out_stride, FftTap tap, hipStream_t stream)
-#endif
+hipError_t SDR_R32_LAUNCH(const SDR_R32_IN *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
     constexpr int kMaxDevices = 64;
     static std::once_flag setup_once[kMaxDevices];
@@ -666,10 +696,29 @@ hipError_t launch_fft_r32(const float *iq, const BatchCursor *cur, const fft64::
         return hipErrorInvalidValue;  // (launch_fft never asks: one listener slot per thread)
     if (!tap.steal)
         return hipErrorInvalidValue;  // the frame counters are the bank's (BatchSet::fft_ctr)
+    if (in_stride > 0xffffffffu)
+        return hipErrorInvalidValue;
+#if SDR_R32_HOP
+    // the frame stride travels as a shift beside the frame count (see the kernel): a power of two, as every hop is
+    int shift = 0;
+    while ((1 << shift) < frame_stride)
+        shift++;
+    if (frame_stride <= 0 || (1 << shift) != frame_stride || n_frames >= (1 << r32::kFrameBits))
+        return hipErrorInvalidValue;
+    const unsigned frames_and_shift = (unsigned)n_frames | (unsigned)shift << r32::kFrameBits;
+#else
+    if (frame_stride != fft32::N)  // overlapped frames: the strided kernel (k_fft_r32_hop.hip)
+#if SDR_R32_SC16
+        return launch_fft_r32_hop_sc16(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+#else
+        return launch_fft_r32_hop(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+#endif
+    const unsigned frames_and_shift = (unsigned)n_frames;
+#endif
     const int cus = std::max(1, cu_count[dev] - SDR_R32_RESERVE);
     const int grid = std::min((cus + n_bands - 1) / n_bands, n_frames);
-    launch_kernel(r32::SDR_R32_KERNEL, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, stream, iq, cur, tw, psd, in_stride, out_stride,
-                  n_frames, tap.steal, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used);
+    launch_kernel(r32::SDR_R32_KERNEL, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, stream, iq, cur, tw, psd, (unsigned)in_stride, out_stride,
+                  frames_and_shift, tap.steal, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used);
     return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@
 #include "cw_decoder.h"
 #include "fft_f64.h"
 #include "host/batch_plan.h"
+#include "host/overlap.h"
 
 namespace sdr {
 
@@ -170,22 +171,30 @@ struct FftTap {
     fft64::cplx *scratch = nullptr;
 };
 
-// iq: [band][in_stride frames][N] samples of format fmt (float32 pairs or sc16 words); `fft` picks the kernel (host/batch_plan.h)
+// iq: samples of format fmt (float32 pairs or sc16 words); band b's frame f is the N samples from sample b * in_stride +
+// f * frame_stride on (host/overlap.h input_sample_offset; dense frames: frame_stride = N, in_stride = n_frames * N; overlapped
+// frames: frame_stride = hop < N); `fft` picks the kernel (host/batch_plan.h)
 hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                      int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream);
+                      int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
 hipError_t launch_fft(int logn, FftChoice fft, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
-                      int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream);  // (float32)
+                      int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);  // (float32)
 // k_fft_2p.hip: N = 32768 / 65536 as two phases over a scratch buffer (fft_2p.h), frame group by frame group
 hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                         int n_frames, int n_bands, int in_stride, int out_stride, FftTap tap, hipStream_t stream);
+                         int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
 int twiddle_count(int logn);
 void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx *out);
 // k_fft_r32.hip: N = 16384 as 512 threads x 32 points with the next frame prefetched into registers (own twiddle layout)
 hipError_t launch_fft_r32(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                          int in_stride, int out_stride, FftTap tap, hipStream_t stream);
+                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
 // k_fft_r32_sc16.hip: the same kernel reading sc16 frames
 hipError_t launch_fft_r32_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                               int in_stride, int out_stride, FftTap tap, hipStream_t stream);
+                               size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
+// k_fft_r32_hop.hip / k_fft_r32_hop_sc16.hip: the same kernels for frame_stride < N (a power of two); the two launchers
+// above hand such a launch on themselves
+hipError_t launch_fft_r32_hop(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+                              size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
+hipError_t launch_fft_r32_hop_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+                                   size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
 int r32_twiddle_count();
 void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out);
 // wpb_forced: windows per workgroup (0: the launcher's rule); mfma: the matrix-pipe variance kernel (host/batch_plan.h)
