@@ -224,6 +224,23 @@ int sdr_set_edge_width(sdr_bank *bank, int edge_width);
 int sdr_set_signal_debounce(sdr_bank *bank, int band, int debounce);
 int sdr_set_center_frequency(sdr_bank *bank, int band, int64_t frequency);
 int sdr_set_find_peaks(sdr_bank *bank, int on);
+/* A window on the frames (the third semantic extension).  window[i] multiplies sample i of every
+ * frame of every band before the transform: re' = float32(re * window[i]), im' = float32(im * window[i]), one correctly
+ * rounded float32 multiplication each; for sc16 input the operand is the converted value, so sc16 stays bit-identical to
+ * float32 input holding those values.  Everything behind the multiplication is the reference's arithmetic on those
+ * float32 values: the results equal the reference fed with frames multiplied so.  The FFT kernels multiply while they
+ * read the input, for every input path (host pushes, KiwiSDR payloads, device frames and streams), with any hop.
+ *   window: host pointer to n == block_size float32 values, copied (borrowed for the call only).  NULL with n == 0
+ *     removes the window; a bank that never had one, or had it removed, runs the kernels it ran without this call.
+ *   Takes effect from the first frame of the next process call; batches already enqueued keep the window they were
+ *     enqueued with (the call drains the bank: it is a rare control call, not one for the sample path).
+ *   SDR_ERR_BAD_ARG: n != block_size, or a null table with n != 0.  SDR_ERR_STATE: the listen half of a deferred batch is
+ *     pending, or a graph is captured (set the window, then capture: the capture records it and replays with it).
+ * Nothing is normalised: absolute levels fall by the window's gains - a periodic Hann window takes 6.02 dB off a carrier
+ * (coherent gain 0.5) and 4.26 dB off noise (power gain 0.375).  Thresholds are relative to the measured noise floor and
+ * need no change; a caller who wants calibrated levels scales the table (Hann: by 2 for carriers).
+ * N = 16384: k_fft_r32 has no windowed form, a windowed bank runs the 16-point kernel at every batch length. */
+int sdr_set_window(sdr_bank *bank, const float *window, int n);
 
 /* consumer side (all synchronise with the stream first) --------------------------------------- */
 /* Frames per band consumed by the last process call / since bank creation. */
@@ -391,6 +408,9 @@ int sdr_group_set_peak_threshold(sdr_group *group, int band, float threshold);
 int sdr_group_set_signal_debounce(sdr_group *group, int band, int debounce);
 int sdr_group_set_edge_width(sdr_group *group, int edge_width);
 int sdr_group_set_find_peaks(sdr_group *group, int on);
+/* sdr_set_window on every member, before the group's next process call: every band changes at the same frame, and the
+ * members cannot come to disagree (what one would refuse is refused before any member's table changes). */
+int sdr_group_set_window(sdr_group *group, const float *window, int n);
 int sdr_group_enable_results(sdr_group *group, int on);
 int sdr_group_poll(sdr_group *group, sdr_results *results, int wait);
 int sdr_group_defer_listen(sdr_group *group, int on);

@@ -96,6 +96,13 @@ class Results(C.Structure):
 
 _lib = None
 
+
+def _set_window(fn, handle, w):
+    if w is None:
+        return fn(handle, None, 0)
+    w = np.ascontiguousarray(w, np.float32).reshape(-1)
+    return fn(handle, w.ctypes.data_as(C.POINTER(C.c_float)), int(w.size))
+
 # every symbol include/sdrainer_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 SYMBOLS = (
     "sdr_last_error sdr_abi_version sdr_create sdr_destroy sdr_self_check sdr_set_stream sdr_push_iq sdr_push_kiwi_snd sdr_staged_frames "
@@ -111,6 +118,7 @@ SYMBOLS = (
     "sdr_push_iq_sc16 sdr_process_device_sc16 sdr_graph_capture_sc16 sdr_graph_launch_sc16 "
     "sdr_group_push_iq_sc16 sdr_group_process_device_sc16 "
     "sdr_hop sdr_process_device_stream sdr_process_device_stream_sc16 "
+    "sdr_set_window sdr_group_set_window "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -169,6 +177,7 @@ def load():
     sig("sdr_set_signal_debounce", C.c_int, vp, C.c_int, C.c_int)
     sig("sdr_set_center_frequency", C.c_int, vp, C.c_int, C.c_int64)
     sig("sdr_set_find_peaks", C.c_int, vp, C.c_int)
+    sig("sdr_set_window", C.c_int, vp, C.POINTER(C.c_float), C.c_int)
     sig("sdr_last_batch_frames", C.c_int, vp)
     sig("sdr_total_frames", C.c_int64, vp)
     sig("sdr_last_batch_chunks", C.c_int, vp)
@@ -229,6 +238,7 @@ def load():
     sig("sdr_group_set_signal_debounce", C.c_int, vp, C.c_int, C.c_int)
     sig("sdr_group_set_edge_width", C.c_int, vp, C.c_int)
     sig("sdr_group_set_find_peaks", C.c_int, vp, C.c_int)
+    sig("sdr_group_set_window", C.c_int, vp, C.POINTER(C.c_float), C.c_int)
     sig("sdr_group_enable_results", C.c_int, vp, C.c_int)
     sig("sdr_group_poll", C.c_int, vp, C.POINTER(Results), C.c_int)
     sig("sdr_group_defer_listen", C.c_int, vp, C.c_int)
@@ -439,6 +449,10 @@ class Bank:
 
     def set_find_peaks(self, on: bool):
         _check(self._L.sdr_set_find_peaks(self._h, int(on)))
+
+    def set_window(self, w):
+        """A window on the frames: block_size float32 values (copied), None removes it (sdr_set_window)."""
+        _check(_set_window(self._L.sdr_set_window, self._h, w))
 
     # consumer ---------------------------------------------------------------------------------
     @property
@@ -724,6 +738,10 @@ class Group:
 
     def set_find_peaks(self, on: bool):
         _check(self._L.sdr_group_set_find_peaks(self._h, int(on)))
+
+    def set_window(self, w):
+        """sdr_group_set_window: the same window on every member, None removes it."""
+        _check(_set_window(self._L.sdr_group_set_window, self._h, w))
 
     # delivery ---------------------------------------------------------------------------------
     def enable_results(self, on: bool = True):

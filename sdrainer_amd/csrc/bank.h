@@ -175,6 +175,8 @@ struct sdr_bank {
     DevBuf<fft64::cplx> tw;
     DevBuf<unsigned char> db_tab;   // gomath.h tables of the certified dB shortcut (k_cumulate)
     DevBuf<int32_t> tap_bins;       // [band][L] bin of every listener slot, -1 = free (k_fft_psd tap)
+    DevBuf<float> window;           // [N] the window table in sdr::window_layout's order (sdr_set_window), allocated at the first call that sets one
+    bool windowed = false;          // the batches run the windowed FFT kernels with `window` (captured graphs hold its pointer)
     DevBuf<float> spectrum_row;     // scratch of sdr_read_spectrum
     std::vector<BatchSet> set;  // RING sets; graph mode adds its own (sdr_graph_capture); capacity reserved at creation: references stay valid
     DevBuf<sdr::BandState> band_state;

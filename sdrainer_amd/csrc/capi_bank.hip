@@ -339,6 +339,7 @@ int sdr_destroy(sdr_bank *b)
     b->cursors.release();
     b->db_tab.release();
     b->tap_bins.release();
+    b->window.release();
     b->spectrum_row.release();
     for (auto &S : b->set)
         S.release();
@@ -553,6 +554,36 @@ int sdr_set_edge_width(sdr_bank *b, int edge_width)
     if (edge_width < 0 || b->cfg.block_size - 2 * edge_width < 10)
         return fail(SDR_ERR_BAD_ARG, "edge_width leaves fewer than 10 bins");
     b->edge_width = edge_width;  // a launch parameter: picked up by the next batch
+    return SDR_OK;
+}
+
+// The table is read by the FFT kernels of batches that may still be queued: drain them, then overwrite it.  A captured
+// graph holds the table's pointer and the kernels the plan picked with or without a window, hence SDR_ERR_STATE there.
+int sdr_set_window(sdr_bank *b, const float *window, int n)
+{
+    if (!b)
+        return fail(SDR_ERR_BAD_ARG, "null bank");
+    if (!window && n != 0)
+        return fail(SDR_ERR_BAD_ARG, "null window table with n != 0 (NULL, 0 removes the window)");
+    if (window && n != b->cfg.block_size)
+        return fail(SDR_ERR_BAD_ARG, "the window table must hold block_size values");
+    if (b->listen_pending)
+        return fail(SDR_ERR_STATE, "the listen half of a deferred batch is pending (sdr_process_listen first)");
+    if (b->graph_ready)
+        return fail(SDR_ERR_STATE, "a graph is captured (sdr_graph_release first; set the window, then capture)");
+    const int rc = sync_bank(b);
+    if (rc)
+        return rc;
+    if (!window) {
+        b->windowed = false;
+        return SDR_OK;
+    }
+    if (!b->window.p)
+        HIP_TRY(b->window.alloc((size_t)n));
+    std::vector<float> image((size_t)n);  // the values in the order the bank's FFT kernel reads them
+    sdr::window_layout(b->logn, window, image.data());
+    HIP_TRY(hipMemcpy(b->window.p, image.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    b->windowed = true;
     return SDR_OK;
 }
 

@@ -322,6 +322,25 @@ int sdr_group_set_edge_width(sdr_group *g, int edge_width)
     return SDR_OK;
 }
 
+int sdr_group_set_window(sdr_group *g, const float *window, int n)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    // What a member could refuse is checked for all of them before any table changes: the arguments are judged against
+    // the one geometry they share by the first member, a listen half is pending on every member or on none, and the
+    // group offers no graph capture.
+    for (sdr_bank *b : g->banks)
+        if (sdr_listen_pending(b))
+            return fail(SDR_ERR_STATE, "a batch waits for its listen half (sdr_group_process_listen)");
+    KeepDevice keep;
+    for (sdr_bank *b : g->banks) {
+        const int rc = sdr_set_window(b, window, n);
+        if (rc)
+            return rc;
+    }
+    return SDR_OK;
+}
+
 int sdr_group_set_find_peaks(sdr_group *g, int on)
 {
     if (!g)

@@ -155,7 +155,7 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
     // every choice of this batch (host/batch_plan.h); a gather moved off the listen stream also waits for late-attached
     // slots: see slots_put below
     const int count0 = b->cum_count;
-    const sdr::BatchPlan P = sdr::plan_batch(b->sw, sdr::BatchGeometry{B, N, stride, b->max_chunks}, n_frames, count0, cap, max_slots);
+    const sdr::BatchPlan P = sdr::plan_batch(b->sw, sdr::BatchGeometry{B, N, stride, b->max_chunks}, n_frames, count0, cap, max_slots, b->windowed);
     const int *plan = P.stream;
     const sdr::CumGeom cg{N, stride, n_frames, count0, b->max_chunks};
     // is kernel k part of the graph that is recording (always, outside a capture)?
@@ -248,6 +248,7 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
         tap.used = S.tap_used.p;
         tap.steal = S.fft_ctr.p;
         tap.scratch = S.fft_scratch.p;
+        tap.window = b->windowed ? b->window.p : nullptr;
         SDR_LAUNCH(sdr::K_FFT, sdr::launch_fft(b->logn, P.fft, fmt, iq_dev, cur, b->tw.p, S.psd.p, n_frames, B, in_stride, b->hop, stride, tap,
                                                stream_of(sdr::K_FFT)));
     }

@@ -136,10 +136,13 @@ inline int fft2p_group_frames(const Switches &sw, int n, int n_bands, int max_fr
 // runs from 1024 frames per launch on (measured by batch size) and while the listener slots fit its tap (one per thread).
 // sc16 input takes the same choice (k_fft_r32_sc16 or k_fft_psd_sc16<14>): the rule does not look at the format.
 // (bench.py restates the frame-count rule to name the kernel in its report.)
-inline FftChoice fft_choice(const Switches &sw, int n, int n_frames, int n_bands, int tap_n)
+// windowed: the bank has a window (sdr_set_window).  k_fft_r32 has no windowed form - it has no register left for a
+// thread's 32 window values beside its prefetched frame - so a windowed batch never takes it, SDR_FFT_R32=1 or not: N =
+// 16384 runs the 16-point kernel at every batch length, and k_cum_refine reads psd columns (no wide tap).
+inline FftChoice fft_choice(const Switches &sw, int n, int n_frames, int n_bands, int tap_n, bool windowed = false)
 {
     FftChoice c;
-    c.r32 = n == 16384 && tap_n <= kR32MaxTap && (sw.fft_r32 == 1 || (sw.fft_r32 < 0 && (long)n_frames * n_bands >= 1024));
+    c.r32 = !windowed && n == 16384 && tap_n <= kR32MaxTap && (sw.fft_r32 == 1 || (sw.fft_r32 < 0 && (long)n_frames * n_bands >= 1024));
     c.fpw = sw.fft_fpw;
     c.wide_tap = c.r32 && tap_n > 0;  // (never at N > 16384: k_cum_refine reads psd columns there)
     c.two_phase = n > 16384;
@@ -170,7 +173,9 @@ struct BatchPlan {
 
 // One batch of n_frames frames that starts at cumulationCount count0, max_slots listener slots in use.  capturing: the
 // batch is being recorded into a graph (sdr_graph_capture), replayed later at whatever count0 and without stream changes.
-inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_frames, int count0, bool capturing, int max_slots)
+// windowed: the bank has a window (fft_choice).
+inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_frames, int count0, bool capturing, int max_slots,
+                            bool windowed = false)
 {
     BatchPlan p;
     // Which of the bank's four streams each kernel runs on.  The step is as long as the longest stream, and kernels that
@@ -191,7 +196,7 @@ inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_fr
         if (sw.diag_plan[k] >= 0)
             p.stream[k] = sw.diag_plan[k];
 
-    p.fft = fft_choice(sw, g.n, n_frames, g.n_bands, max_slots);
+    p.fft = fft_choice(sw, g.n, n_frames, g.n_bands, max_slots, windowed);
     p.fft.group_frames = fft2p_group_frames(sw, g.n, g.n_bands, g.max_batch_frames);
 
     // noise floor: the one-pass scan unless the chains are asked for or the windows are too wide for it (noise_scan_at)

@@ -20,63 +20,13 @@ __device__ __forceinline__ fft64::cplx tw_load(const fft64::cplx *__restrict__ t
     return tw[i];
 }
 
-// Phase A of frames [frame0, frame0 + group) of band blockIdx.y: workgroup x = frame_local * WG_A + w takes the sub-FFTs
-// p = w G .. w G + G - 1 (blocks k = brev_B(p)).  Y: [band][group frames][N].
-template <int LOGN, InFormat FMT>
-__global__ __launch_bounds__(fft2p::T) void k_fft2p_a(const void *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
-                                                      const fft64::cplx *__restrict__ tw, fft64::cplx *__restrict__ y, size_t in_stride,
-                                                      int frame_stride, int frame0, int group)
-{
-    using PH = fft2p::Phases<LOGN>;
-    using S = typename PH::SA;
-    constexpr int N = PH::N, MB = PH::A;
-    __shared__ double lr[S::G * S::LDS_ROW], li[S::G * S::LDS_ROW];
-    const int fl = blockIdx.x / PH::WG_A, w = blockIdx.x % PH::WG_A, band = blockIdx.y, t = threadIdx.x;
-    const size_t frame_at = input_sample_offset(band * in_stride, (unsigned)(frame0 + fl), frame_stride);  // (samples)
-    const auto W = [tw](int i) { return tw_load(tw, i); };
-    double xr[fft2p::R], xi[fft2p::R];
-    {
-        const int gl = fft2p::p0_sub<MB>(t), p = w * S::G + gl;
-        if constexpr (FMT == InFormat::F32) {
-            const float2 *__restrict__ iq = reinterpret_cast<const float2 *>(cur ? cur->iq : static_cast<const float *>(iq_arg)) + frame_at;
-#pragma unroll
-            for (int s = 0; s < fft2p::R; s++) {
-                const float2 v = iq[fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s))];
-                xr[s] = (double)v.x;
-                xi[s] = (double)v.y;
-            }
-        } else {
-            const uint32_t *__restrict__ iq = reinterpret_cast<const uint32_t *>(cur ? cur->iq_sc16 : static_cast<const int16_t *>(iq_arg)) + frame_at;
-#pragma unroll
-            for (int s = 0; s < fft2p::R; s++) {
-                const uint32_t v = iq[fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s))];
-                xr[s] = (double)sc16::re_of(v);
-                xi[s] = (double)sc16::im_of(v);
-            }
-        }
-        fft2p::pass0<MB>(xr, xi, LOGN, 0, 0, t, W);
-#pragma unroll
-        for (int s = 0; s < fft2p::R; s++) {
-            const int at = gl * S::LDS_ROW + fft2p::p0_index<MB>(t, s);
-            lr[at] = xr[s];
-            li[at] = xi[s];
-        }
-    }
-    __syncthreads();
-    const int gl = fft2p::p1_sub<MB, true>(t);
-#pragma unroll
-    for (int s = 0; s < fft2p::R; s++) {
-        const int at = gl * S::LDS_ROW + fft2p::p1_index<MB, true>(t, s);
-        xr[s] = lr[at];
-        xi[s] = li[at];
-    }
-    fft2p::pass1<MB, true>(xr, xi, LOGN, 0, 0, t, W);
-    const int k = fft2p::a_block<LOGN>(w * S::G + gl);
-    fft64::cplx *__restrict__ out = y + ((size_t)band * group + fl) * N + ((size_t)k << PH::A);
-#pragma unroll
-    for (int s = 0; s < fft2p::R; s++)
-        out[fft2p::p1_index<MB, true>(t, s)] = fft64::cplx{xr[s], xi[s]};
-}
+// Phase A (k_fft_2p_a.h): k_fft2p_a, and k_fft2p_win_a for a bank with a window
+#define SDR_FFT2P_WIN 0
+#include "k_fft_2p_a.h"
+#undef SDR_FFT2P_WIN
+#define SDR_FFT2P_WIN 1
+#include "k_fft_2p_a.h"
+#undef SDR_FFT2P_WIN
 
 // Phase B of the same group: workgroup x = frame_local * WG_B + w takes the residues c = w G .. w G + G - 1, writes their
 // bins' psd (fft-shifted) and the tap of the listeners whose bins are among them (k_fft_psd.hip "The tap"): the row's
@@ -166,7 +116,13 @@ static hipError_t launch_fft2p_t(FftChoice fft, InFormat fmt, const void *iq, co
     t_done_event = nullptr;
     for (int f0 = 0; f0 < n_frames; f0 += group) {
         const int g = n_frames - f0 < group ? n_frames - f0 : group;
-        if (fmt == InFormat::SC16)
+        if (tap.window && fmt == InFormat::SC16)
+            hipLaunchKernelGGL((k_fft2p_win_a<LOGN, InFormat::SC16>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
+                               tap.scratch, in_stride, frame_stride, f0, group, tap.window);
+        else if (tap.window)
+            hipLaunchKernelGGL((k_fft2p_win_a<LOGN, InFormat::F32>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
+                               tap.scratch, in_stride, frame_stride, f0, group, tap.window);
+        else if (fmt == InFormat::SC16)
             hipLaunchKernelGGL((k_fft2p_a<LOGN, InFormat::SC16>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
                                tap.scratch, in_stride, frame_stride, f0, group);
         else

@@ -17,6 +17,26 @@
 #include "sc16.h"
 #include "sdr_device.h"
 
+// A window on the frames.  k_fft_psd_win.hip compiles this file again with SDR_FFT_WIN = 1: the kernels k_fft_psd_win and
+// k_fft_psd_sc16_win take the bank's window table (N float32 in device memory, in the order load_window reads it) and
+// multiply sample i of every frame by its value - one correctly rounded float32 multiplication per component, where
+// the plain kernels widen the sample to float64 - and launch_fft_win launches them.  Everything behind the
+// multiplication is the plain kernels'.  A translation unit of its own keeps the plain kernels' code exactly what it was.
+#if !defined(SDR_FFT_WIN)
+#define SDR_FFT_WIN 0
+#endif
+#if SDR_FFT_WIN
+#define SDR_K_FFT_PSD k_fft_psd_win
+#define SDR_K_FFT_PSD_SC16 k_fft_psd_sc16_win
+#define SDR_WIN_PARAM , const float *__restrict__ win
+#define SDR_WIN_ARG , win
+#else
+#define SDR_K_FFT_PSD k_fft_psd
+#define SDR_K_FFT_PSD_SC16 k_fft_psd_sc16
+#define SDR_WIN_PARAM
+#define SDR_WIN_ARG
+#endif
+
 #if !defined(SDR_FFT_PSD_AUX)
 #define SDR_FFT_PSD_AUX 0  // cache policy bits of the psd stores (2 = nt)
 #endif
@@ -302,6 +322,44 @@ __device__ __forceinline__ void run_passes(double (&xr)[fft64::Plan<LOGN>::R], d
     }
 }
 
+#if SDR_FFT_WIN
+// The window values of thread t's register slots (slot m holds sample input_sample(t, m)).  In sample order a wave's
+// lanes would read them 32 bytes and more apart - what the frame itself avoids by going through LDS; measured, sixteen
+// such dword loads per thread made the kernel 13 % slower per launch.  So the bank keeps the table in THIS kernel's order
+// (window_layout below, applied once by sdr_set_window): [m / 4][t][m % 4], a thread's four values of a slot group in one
+// 16-byte load, a wave instruction reading 1 KB contiguous - R / 4 loads per thread.  Called before the wait for the
+// frame's LDS-DMA: the loads ride under it (the table is L2-resident like the twiddles).
+template <int LOGN>
+SDR_HD constexpr int window_slot(int t, int m)
+{
+    return ((m >> 2) * fft64::Plan<LOGN>::T + t) * 4 + (m & 3);
+}
+template <int LOGN>
+__device__ __forceinline__ void load_window(float (&wv)[fft64::Plan<LOGN>::R], int t, const float *__restrict__ win)
+{
+    using PL = fft64::Plan<LOGN>;
+    static_assert(PL::R % 4 == 0 && PL::R * PL::T == PL::N, "the table holds R values per thread, four per load");
+    const rsrc_t wrs = make_rsrc(win, PL::N * 4u);
+    const unsigned woff = (unsigned)window_slot<LOGN>(t, 0) * 4u;
+#pragma unroll
+    for (int j = 0; j < PL::R / 4; j++) {
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrs, woff, window_slot<LOGN>(0, 4 * j) * 4, 0);
+        wv[4 * j + 0] = __uint_as_float(v.x);
+        wv[4 * j + 1] = __uint_as_float(v.y);
+        wv[4 * j + 2] = __uint_as_float(v.z);
+        wv[4 * j + 3] = __uint_as_float(v.w);
+    }
+}
+template <int LOGN>
+static void window_layout_t(const float *w, float *out)
+{
+    using PL = fft64::Plan<LOGN>;
+    for (int t = 0; t < PL::T; t++)
+        for (int m = 0; m < PL::R; m++)
+            out[window_slot<LOGN>(t, m)] = w[fft64::input_sample<LOGN>(t, m)];
+}
+#endif
+
 // Epilogue (dsp/fft.go:54-57 fftshift, :71-73 PSD[float32]): psd[k] = float32(re^2 + im^2), two multiplies and an
 // add in float64, no FMA, rounded once.
 // LDS_COPY: the row also goes to LDS (float32 at byte 4 k), where the one-frame workgroup's tap picks its bins up.
@@ -430,11 +488,11 @@ constexpr int kPfSinkBytes = SDR_FFT_PF_DIST > 0 ? 4096 : 0;
 // (second launch bound = waves per SIMD the register allocation must leave room for: four, i.e. one 1024-thread
 // workgroup or two 512-thread ones per CU)
 template <int LOGN, bool MULTI>
-__global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 ? 4 : 1)) void k_fft_psd(const float *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
+__global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 ? 4 : 1)) void SDR_K_FFT_PSD(const float *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
                                                                   const fft64::cplx *__restrict__ tw,
                                                                   float *__restrict__ psd, size_t in_stride, int frame_stride, int out_stride,
                                                                   int n_frames, int fpw, const int *__restrict__ tap_bins,
-                                                                  float *__restrict__ tap_out, int n_tap, int tap_stride)
+                                                                  float *__restrict__ tap_out, int n_tap, int tap_stride SDR_WIN_PARAM)
 {
 #if defined(__HIP_DEVICE_COMPILE__)  // (the host pass needs the signature only; with the body it drops the stub without a diagnostic)
     using PL = fft64::Plan<LOGN>;
@@ -513,6 +571,9 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
         }
     };
     constexpr bool REGS = PRIV && !MULTI && SDR_FFT_PRIVATE_STAGE == 2;  // one-frame workgroup: straight into the registers pass 0 starts from
+#if SDR_FFT_WIN
+    static_assert(!REGS, "the windowed kernels read their samples from the LDS image");
+#endif
     if constexpr (!REGS)
         stage_frame(frame0, ltid);
     // one-frame workgroup: its listeners' bins into LDS (behind the exchange area) while the frame is on its way
@@ -552,6 +613,12 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
             }
             SDR_STAMP(st, ST_LANDED);
         } else {
+#if SDR_FFT_WIN
+        // (a later frame of a multi-frame workgroup: these loads are the youngest, so the counted wait below covers the
+        // previous frame's stores as well as the DMA)
+        float wv[PL::R];
+        load_window<LOGN>(wv, t, win);
+#endif
         if (!MULTI || frame == frame0)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else
@@ -573,8 +640,13 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
             const int slot_byte = PRIV ? m * 512 : fft64::in_lds_byte<LOGN>(fft64::input_sample<LOGN>(0, m));
             const float2 v = *reinterpret_cast<const float2 *>(smem + (PRIV ? thread_byte + slot_byte : (thread_byte ^ slot_byte)));
 #endif
+#if SDR_FFT_WIN
+            xr[m] = (double)__fmul_rn(v.x, wv[m]);
+            xi[m] = (double)__fmul_rn(v.y, wv[m]);
+#else
             xr[m] = (double)v.x;
             xi[m] = (double)v.y;
+#endif
         }
         if constexpr (PRIV)
             wave_sync();  // the wave has its samples: its block belongs to its first exchange now
@@ -674,10 +746,10 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
 // are the float32 path's bits for the converted values.  Only this one form exists for sc16: the multi-frame workgroup,
 // layout B, wave-private staging and the timing-only builds stay float32-only (launch_fft_t).
 template <int LOGN>
-__global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 ? 4 : 1)) void k_fft_psd_sc16(const int16_t *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
+__global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 ? 4 : 1)) void SDR_K_FFT_PSD_SC16(const int16_t *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
                                                                        const fft64::cplx *__restrict__ tw, float *__restrict__ psd,
                                                                        size_t in_stride, int frame_stride, int out_stride, const int *__restrict__ tap_bins,
-                                                                       float *__restrict__ tap_out, int n_tap, int tap_stride)
+                                                                       float *__restrict__ tap_out, int n_tap, int tap_stride SDR_WIN_PARAM)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     using PL = fft64::Plan<LOGN>;
@@ -713,6 +785,10 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
     if (lds_tap)
         for (int l = threadIdx.x; l < n_tap; l += PL::T)
             lds_bins[l] = tap_bins[(size_t)blockIdx.y * tap_stride + l];
+#if SDR_FFT_WIN
+    float wv[PL::R];
+    load_window<LOGN>(wv, t, win);
+#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     double xr[PL::R], xi[PL::R];
@@ -723,8 +799,13 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
         for (int m = 0; m < PL::R; m++) {
             const int slot_byte = sc16::lds_byte<LOGN>(fft64::input_sample<LOGN>(0, m));
             const uint32_t w = *reinterpret_cast<const uint32_t *>(smem + (thread_byte ^ slot_byte));
+#if SDR_FFT_WIN
+            xr[m] = (double)__fmul_rn(sc16::re_of(w), wv[m]);
+            xi[m] = (double)__fmul_rn(sc16::im_of(w), wv[m]);
+#else
             xr[m] = (double)sc16::re_of(w);
             xi[m] = (double)sc16::im_of(w);
+#endif
         }
     }
     __syncthreads();  // everyone has its samples: the exchange area may be written again
@@ -1015,6 +1096,12 @@ static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, c
 {
     using PL = fft64::Plan<LOGN>;
     const float *iq = static_cast<const float *>(iq_in);
+#if SDR_FFT_WIN
+    const float *win = tap.window;
+    if constexpr (PL::LB) {
+        return hipErrorNotSupported;  // (layout B builds: no windowed kernel at this size)
+    } else {
+#else
     if constexpr (PL::LB) {
         if (fmt != InFormat::F32)
             return hipErrorNotSupported;  // (layout B builds: sc16 input has no kernel at this size)
@@ -1033,10 +1120,11 @@ static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, c
                       in_stride, frame_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride);
         return hipGetLastError();
     } else {
+#endif
     static LdsLimitOnce lds_once;
     const hipError_t attr_err = raise_lds_limit_once(lds_once,
-                                                     {reinterpret_cast<const void *>(&k_fft_psd<LOGN, false>), reinterpret_cast<const void *>(&k_fft_psd<LOGN, true>),
-                                                      reinterpret_cast<const void *>(&k_fft_psd_sc16<LOGN>)},
+                                                     {reinterpret_cast<const void *>(&SDR_K_FFT_PSD<LOGN, false>), reinterpret_cast<const void *>(&SDR_K_FFT_PSD<LOGN, true>),
+                                                      reinterpret_cast<const void *>(&SDR_K_FFT_PSD_SC16<LOGN>)},
                                                      fft64::kLdsBytes<LOGN> + kMaxLdsTap * 4 + kPfSinkBytes);
     if (attr_err != hipSuccess)
         return attr_err;
@@ -1045,8 +1133,8 @@ static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, c
     const unsigned tap_lds = tap.n > 0 && tap.n <= kMaxLdsTap ? ((tap.n * 4 + 255) & ~255) : 0;
     if (fmt == InFormat::SC16) {
         // one frame per workgroup, always (FftChoice::fpw is the float32 kernel's)
-        launch_kernel((k_fft_psd_sc16<LOGN>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, stream,
-                      static_cast<const int16_t *>(iq_in), cur, tw, psd, in_stride, frame_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride);
+        launch_kernel((SDR_K_FFT_PSD_SC16<LOGN>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, stream,
+                      static_cast<const int16_t *>(iq_in), cur, tw, psd, in_stride, frame_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_ARG);
         return hipGetLastError();
     }
     // a workgroup's frames are consecutive; never fewer workgroups than CUs can take (a short batch keeps one
@@ -1055,24 +1143,52 @@ static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, c
     while (fpw > 1 && (long)((n_frames + fpw - 1) / fpw) * n_bands < 256)
         fpw /= 2;
     if (fpw > 1)
-        launch_kernel((k_fft_psd<LOGN, true>), dim3((n_frames + fpw - 1) / fpw, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN>, stream,
-                           iq, cur, tw, psd, in_stride, frame_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride);
+        launch_kernel((SDR_K_FFT_PSD<LOGN, true>), dim3((n_frames + fpw - 1) / fpw, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN>, stream,
+                           iq, cur, tw, psd, in_stride, frame_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_ARG);
     else
-        launch_kernel((k_fft_psd<LOGN, false>), dim3(n_frames, n_bands), dim3(PL::T),
+        launch_kernel((SDR_K_FFT_PSD<LOGN, false>), dim3(n_frames, n_bands), dim3(PL::T),
                            fft64::kLdsBytes<LOGN> + tap_lds + kPfSinkBytes, stream, iq, cur, tw, psd, in_stride,
-                           frame_stride, out_stride, n_frames, 1, tap.bins, tap.out, tap.n, tap.stride);
+                           frame_stride, out_stride, n_frames, 1, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_ARG);
     return hipGetLastError();
     }
 }
 
+#if SDR_FFT_WIN
+// The device image of a window table w[N] (sample order): the order the windowed kernel of that size reads it in (N = 512
+// - 16384: load_window above; N = 32768 / 65536: k_fft2p_win_a reads it in sample order beside the samples themselves).
+void window_layout(int logn, const float *w, float *out)
+{
+    switch (logn) {
+    case 9: window_layout_t<9>(w, out); break;
+    case 10: window_layout_t<10>(w, out); break;
+    case 11: window_layout_t<11>(w, out); break;
+    case 12: window_layout_t<12>(w, out); break;
+    case 13: window_layout_t<13>(w, out); break;
+    case 14: window_layout_t<14>(w, out); break;
+    default:
+        for (int i = 0; i < 1 << logn; i++)
+            out[i] = w[i];
+        break;
+    }
+}
+
+// N = 512 - 16384 with the window table tap.window, in window_layout's order (launch_fft hands such a launch on)
+hipError_t launch_fft_win(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
+                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
+{
+    if (!tap.window || fft.r32 || fft.two_phase)
+        return hipErrorInvalidValue;  // (host/batch_plan.h: a windowed batch is never planned onto k_fft_r32)
+#else
 // The bank's twiddle buffer for N = 16384 holds both kernels' tables, the 32-point kernel's behind the other.
 hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
                       int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
     if (fmt != InFormat::F32 && fmt != InFormat::SC16)
         return hipErrorInvalidValue;
-    if (fft.two_phase)
+    if (fft.two_phase)  // (with tap.window: k_fft2p_win_a)
         return launch_fft_2p(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+    if (tap.window)
+        return launch_fft_win(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
     if (fft.r32) {
         if (logn != 14)
             return hipErrorInvalidValue;
@@ -1081,6 +1197,7 @@ hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, con
             return launch_fft_r32_sc16(static_cast<const int16_t *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
         return launch_fft_r32(static_cast<const float *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
     }
+#endif
     switch (logn) {
     case 9: return launch_fft_t<9>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
     case 10: return launch_fft_t<10>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
@@ -1091,6 +1208,7 @@ hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, con
     default: return hipErrorInvalidValue;
     }
 }
+#if !SDR_FFT_WIN
 hipError_t launch_fft(int logn, FftChoice fft, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
                       int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
 {
@@ -1132,5 +1250,6 @@ void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx 
     default: break;
     }
 }
+#endif  // !SDR_FFT_WIN
 
 }  // namespace sdr

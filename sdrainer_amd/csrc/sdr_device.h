@@ -169,6 +169,10 @@ struct FftTap {
     uint32_t *steal = nullptr;
     // k_fft_2p only: one frame group's float64 intermediate, [band][FftChoice::group_frames][N] (BatchSet::fft_scratch)
     fft64::cplx *scratch = nullptr;
+    // the bank's window table, [N] float32 in window_layout's order (sdr_set_window), null = none: sample i of every frame
+    // is multiplied by its value in float32 before it is widened, by the windowed forms of the kernels (k_fft_psd_win.hip,
+    // k_fft2p_win_a)
+    const float *window = nullptr;
 };
 
 // iq: samples of format fmt (float32 pairs or sc16 words); band b's frame f is the N samples from sample b * in_stride +
@@ -178,6 +182,11 @@ hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, con
                       int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
 hipError_t launch_fft(int logn, FftChoice fft, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
                       int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);  // (float32)
+// k_fft_psd_win.hip: N = 512 - 16384 with tap.window set (launch_fft hands such a launch on; never k_fft_r32)
+hipError_t launch_fft_win(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
+                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
+// ... and the order its kernels read the table in: out[N] from the caller's w[N] (sample order)
+void window_layout(int logn, const float *w, float *out);
 // k_fft_2p.hip: N = 32768 / 65536 as two phases over a scratch buffer (fft_2p.h), frame group by frame group
 hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);

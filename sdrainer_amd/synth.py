@@ -48,6 +48,12 @@ def keying_pattern(text: str, dit_frames: int) -> np.ndarray:
     return np.array(out, np.uint8)
 
 
+def hann(n: int) -> np.ndarray:
+    """The periodic Hann window of n points, 0.5 - 0.5 cos(2 pi i / n) in float64, rounded once to float32
+    (capi.Bank.set_window): hann(n)[0] == 0, hann(n)[n // 2] == 1."""
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n, dtype=np.float64) / n)).astype(np.float32)
+
+
 def dit_frames(sample_rate: int, block_size: int) -> int:
     return max(2, math.ceil(0.060 / (block_size / sample_rate)))
 

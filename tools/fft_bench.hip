@@ -50,6 +50,12 @@ hipError_t launch_fft_r32_hop_sc16(const int16_t *, const BatchCursor *, const f
 {
     return hipErrorNotSupported;
 }
+// (nor the windowed kernels, k_fft_psd_win.hip: this tool sets no window)
+hipError_t launch_fft_win(int, FftChoice, InFormat, const void *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap,
+                          hipStream_t)
+{
+    return hipErrorNotSupported;
+}
 }  // namespace sdr
 
 static unsigned long long fnv(const void *p, size_t n)
