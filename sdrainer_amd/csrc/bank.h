@@ -166,6 +166,7 @@ struct sdr_bank {
     int device = 0;
     hipStream_t stream[N_STAGES] = {};  // stream[S_FFT] is the caller's (or the null stream)
     bool own_stream[N_STAGES] = {};
+    bool fft_queue_alone = true;  // no stream of the bank's own shares stream[S_FFT]'s hardware queue (probe_fft_queue, capi_bank.hip)
 
     int max_chunks = 0;
     int text_cap = 2048;

@@ -43,6 +43,78 @@ int sync_bank(sdr_bank *b)
     return SDR_OK;
 }
 
+// Does the FFT's stream (the caller's) run on a hardware queue that none of the bank's own streams uses?  The runtime deals
+// its few hardware queues to streams as they are first used and tells nobody which; kernels of two streams on one queue run
+// one after the other, and the CUs k_fft_r32's grid would leave to the tail (host/batch_plan.h fft_reserve_cus) then only
+// make its launch longer.  So the bank looks: a kernel that spins for kProbeSpinUs on the FFT's stream, an empty kernel
+// on each of its own streams; an empty kernel that ends while the spin still runs was not behind it in its queue.  An
+// answer that comes late (the host thread descheduled) reads as "shared", which costs the reserve's gain and nothing else.
+// Only banks whose plan could reserve are probed (N = 16384, the stages on streams of their own, no forced reserve).
+constexpr int kProbeSpinUs = 300;
+__global__ void k_queue_probe_spin(unsigned ticks, unsigned *sink)
+{
+    // wall_clock64 counts at 100 MHz; the loop is bounded so that it ends whatever the clock does
+    const unsigned long long t0 = wall_clock64();
+    unsigned n = 0;
+    for (int i = 0; i < (1 << 20) && wall_clock64() - t0 < ticks; i++) {
+        __builtin_amdgcn_s_sleep(32);
+        n++;
+    }
+    if (n == 0xffffffffu)
+        *sink = n;
+}
+__global__ void k_queue_probe_nop() {}
+
+int probe_fft_queue(sdr_bank *b)
+{
+    b->fft_queue_alone = true;
+    if (b->cfg.block_size != 16384 || b->sw.no_overlap || b->sw.fft_reserve >= 0)
+        return SDR_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    hipEvent_t spin_done = nullptr, nop_done[N_STAGES] = {};
+    auto cleanup = [&] {
+        if (spin_done)
+            (void)hipEventDestroy(spin_done);
+        for (hipEvent_t e : nop_done)
+            if (e)
+                (void)hipEventDestroy(e);
+    };
+    hipError_t e = hipEventCreateWithFlags(&spin_done, hipEventDisableTiming);
+    for (int s = 1; s < N_STAGES && e == hipSuccess; s++)
+        e = hipEventCreateWithFlags(&nop_done[s], hipEventDisableTiming);
+    // every stream's queue is dealt by now: an empty kernel on each, finished, before the probe proper
+    for (int s = 0; s < N_STAGES && e == hipSuccess; s++) {
+        hipLaunchKernelGGL(k_queue_probe_nop, dim3(1), dim3(1), 0, b->stream[s]);
+        e = hipStreamSynchronize(b->stream[s]);
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_queue_probe_spin, dim3(1), dim3(1), 0, b->stream[S_FFT], (unsigned)kProbeSpinUs * 100u, reinterpret_cast<unsigned *>(b->drops.p));
+        e = hipEventRecord(spin_done, b->stream[S_FFT]);
+    }
+    for (int s = 1; s < N_STAGES && e == hipSuccess; s++) {
+        hipLaunchKernelGGL(k_queue_probe_nop, dim3(1), dim3(1), 0, b->stream[s]);
+        e = hipEventRecord(nop_done[s], b->stream[s]);
+    }
+    bool shared[N_STAGES] = {};
+    for (int s = 1; s < N_STAGES && e == hipSuccess; s++) {
+        e = hipEventSynchronize(nop_done[s]);
+        // (the spin's event is behind the spin in its queue: done already = the empty kernel waited for the spin, or the answer is late)
+        shared[s] = b->stream[s] == b->stream[S_FFT] || hipEventQuery(spin_done) == hipSuccess;
+        if (shared[s])
+            b->fft_queue_alone = false;
+    }
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(b->stream[S_FFT]);
+    cleanup();
+    if (e != hipSuccess)
+        return fail(SDR_ERR_HIP, std::string("hardware queue probe: ") + hipGetErrorString(e));
+    if (b->sw.queue_debug)
+        fprintf(stderr, "sdr: FFT stream %s (noise %d listen %d peaks %d share its hardware queue)\n",
+                b->fft_queue_alone ? "has a hardware queue to itself" : "SHARES a hardware queue: no CUs reserved", (int)shared[S_NOISE], (int)shared[S_LISTEN],
+                (int)shared[S_PEAKS]);
+    return SDR_OK;
+}
+
 int check_band(sdr_bank *b, int band)
 {
     if (!b)
@@ -315,6 +387,13 @@ int sdr_create(const sdr_config *cfg, sdr_bank **out)
     b->center_frequency.assign(B, 0);
     b->staged.assign(B, sdr::StreamStage{N, b->hop, 0, 0});
     b->staged_kind.assign(B, 0);
+    {
+        const int prc = probe_fft_queue(b);  // (the null stream's queue against the bank's; sdr_set_stream looks again)
+        if (prc) {
+            sdr_destroy(b);
+            return prc;
+        }
+    }
     *out = b;
     return SDR_OK;
 }
@@ -395,7 +474,7 @@ int sdr_set_stream(sdr_bank *b, void *hip_stream)
         if (!b->own_stream[s])
             b->stream[s] = reinterpret_cast<hipStream_t>(hip_stream);  // SDR_NO_OVERLAP: one stream for all
     b->stream[S_FFT] = reinterpret_cast<hipStream_t>(hip_stream);
-    return SDR_OK;
+    return probe_fft_queue(b);
 }
 
 int sdr_sync(sdr_bank *b)

@@ -155,7 +155,7 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
     // every choice of this batch (host/batch_plan.h); a gather moved off the listen stream also waits for late-attached
     // slots: see slots_put below
     const int count0 = b->cum_count;
-    const sdr::BatchPlan P = sdr::plan_batch(b->sw, sdr::BatchGeometry{B, N, stride, b->max_chunks}, n_frames, count0, cap, max_slots, b->windowed);
+    const sdr::BatchPlan P = sdr::plan_batch(b->sw, sdr::BatchGeometry{B, N, stride, b->max_chunks, b->fft_queue_alone}, n_frames, count0, cap, max_slots, b->windowed);
     const int *plan = P.stream;
     const sdr::CumGeom cg{N, stride, n_frames, count0, b->max_chunks};
     // is kernel k part of the graph that is recording (always, outside a capture)?

@@ -36,11 +36,13 @@ struct Switches {
     int fft_fpw = 0;         // SDR_FFT_FPW: frames per workgroup of the 16-point kernels, 1 - 64 (0: the kernel's default)
     int cum_bound = -1;      // SDR_CUM_BOUND=0 / 1: bound-and-refine never / always (-1: by batch size)
     int refine_wide = -1;    // SDR_REFINE_WIDE=0 / 1: the refinement's workgroup shape (-1: by cumulations per batch)
+    int fft_reserve = -1;    // SDR_FFT_RESERVE=k: CUs k_fft_r32's grid leaves free (-1: fft_reserve_cus' rule; measurement and tests)
     int var_mfma = -1;       // SDR_VAR_MFMA=0 / 1: the chains' variance kernel (-1: by batch length)
     int wm_wpb = 0;          // SDR_WM_WPB: windows per workgroup of the chains' window sums (0: launch_window_means' rule)
     int fft2p_group_mb = -1;  // SDR_FFT2P_GROUP_MB: N > 16384, MiB of float64 intermediate per frame group (0: the whole batch; -1: kFft2pGroupMiB)
     bool no_overlap = false;   // SDR_NO_OVERLAP=1: every stage on the caller's stream (kernel-by-kernel profiling)
     bool graph_debug = false;  // SDR_GRAPH_DEBUG: host-side timings of every sdr_graph_launch on stderr
+    bool queue_debug = false;  // SDR_QUEUE_DEBUG: what the bank's hardware queue probe found (sdr_create, sdr_set_stream) on stderr
     // -DSDR_DIAG builds only (tools/abl): SDR_DIAG_SKIP = bit mask of kernel ids not to launch, to see which stage holds the
     // pipelined step up (results are wrong by construction); SDR_DIAG_PLAN = the stream of each kernel, one digit each
     int diag_skip = 0;
@@ -73,6 +75,8 @@ inline Switches read_switches()
     s.cum_bound = tri_state(getenv("SDR_CUM_BOUND"));
     s.refine_wide = tri_state(getenv("SDR_REFINE_WIDE"));
     s.var_mfma = tri_state(getenv("SDR_VAR_MFMA"));
+    if ((e = getenv("SDR_FFT_RESERVE")))
+        s.fft_reserve = atoi(e) >= 0 ? atoi(e) : -1;
     if ((e = getenv("SDR_FFT2P_GROUP_MB")))
         s.fft2p_group_mb = atoi(e) >= 0 ? atoi(e) : -1;  // (measurement: tools/fft2p_bench.py)
     if ((e = getenv("SDR_WM_WPB")))
@@ -80,6 +84,7 @@ inline Switches read_switches()
     e = getenv("SDR_NO_OVERLAP");
     s.no_overlap = e && e[0] == '1';
     s.graph_debug = getenv("SDR_GRAPH_DEBUG") != nullptr;
+    s.queue_debug = getenv("SDR_QUEUE_DEBUG") != nullptr;
 #if defined(SDR_DIAG)
     if ((e = getenv("SDR_DIAG_SKIP")))
         s.diag_skip = atoi(e);
@@ -113,6 +118,8 @@ struct FftChoice {
     bool wide_tap = false;  // the kernel leaves the wide tap (psd at bin - 1, bin, bin + 1 of every listener: k_cum_refine reads it)
     bool two_phase = false;  // N = 32768 / 65536: the two kernels of k_fft_2p.hip, frame group by frame group
     int group_frames = 0;    // ... frames per group (the batch set's scratch holds one group's intermediate of every band)
+    int reserve_cus = 0;     // k_fft_r32: CUs its grid leaves to the other streams' kernels (fft_reserve_cus; 0 for every other kernel)
+    bool reserve_forced = false;  // ... as SDR_FFT_RESERVE gave it (the launcher caps the rule's value at kReserveDeviceShare of the device, not a forced one)
 };
 
 // N = 32768 and 65536 (k_fft_2p.hip): frames per group of the two phases.  A group's float64 intermediate is 16 bytes per
@@ -149,10 +156,58 @@ inline FftChoice fft_choice(const Switches &sw, int n, int n_frames, int n_bands
     return c;
 }
 
+// k_fft_r32's grid is one persistent workgroup per CU: 254 VGPRs at two waves per SIMD and about 160 KB of LDS, so nothing
+// else fits on a CU it holds, and it holds it until the launch ends.  With every CU taken, the other streams' kernels - the
+// scan, then the chain of thresholds, gather, decode, cumulate, refine, find-peaks and the pack kernels - find a CU only
+// between two FFT launches, one dependent stage per boundary: a batch's latency grows until every set of the ring is in
+// flight, the caller waits for a set, and the FFT queue idles 0.21 - 0.23 ms of a 0.72 ms config-3 step.  So the grid
+// leaves CUs free: enough for the scan's workgroups (each holds a whole CU: 115 KB of LDS) in kReserveRounds rounds, plus
+// kReserveExtra for the chain kernels (k_cum_refine's 1024-thread workgroups among them), at most kReserveMax - a quarter
+// of the 256-CU device the rule was measured on; on a smaller device or a partition the launcher caps the rule's value at
+// CUs / kReserveDeviceShare.  The FFT launch grows by CUs / (CUs - reserve), the launches follow each other 6 - 8 us apart
+// and the step is the launch.  Measured on one MI355X, GS/s of the 2000-step line, one band, 256 listeners, by reserve
+// forced with SDR_FFT_RESERVE, ONE run per figure (profiles/reserve_sweep.jsonl; HISTORY has the 20-step line and a
+// second box).  This box's other runs at reserve 0 gave 201.5 - 202.7, so read the row against 194 - 203, not 194:
+//   8192 frames   0: 194   48: 205   56: 210   60: 212   64: 220   68: 218   72: 216   80: 211
+//   4096 frames   0: 178   32: 197   48: 194   64: 210   72: 210
+//   2048 frames   0: 159   16: 162   32: 183   43: 182   64: 185
+// Interleaved pairs against the parent commit, the figure to quote: 1.09 (2000 steps), 1.11 (20 steps) at 8192 frames
+// (profiles/reserve_bench_pairs.json).  64 wins at 8192 frames and loses nowhere; between 60 and 64 the gain doubles (64
+// free CUs are eight on each of the eight XCDs), so the constants put every batch of 4096 frames and more at the clamp:
+// 82 - 84 scan workgroups / 2 + 24 > 64.  Every measurement is one band with 256 listeners: batches of several bands on
+// k_fft_r32 (24 bands: 48 or 64 CUs by the same formula) and banks with few listeners take the rule unmeasured.
+// The reserve helps only where the other stages can run BESIDE an FFT launch: the runtime deals its hardware queues to
+// streams as it likes, and where the FFT's stream (the caller's) shares a queue with one of the bank's streams the
+// launches only get longer - 0.91 of the parent commit in those runs of tools/sc16_rate.py.  The bank probes that
+// (sdr_bank::fft_queue_alone, capi_bank.hip probe_fft_queue) and the rule reserves nothing on a shared queue.
+// No reserve where the batch does not run k_fft_r32, where the chains compute the noise floor (their many small workgroups
+// are not what the rule was measured with), and below kReserveMinFrames frames per launch, the shortest batch measured.
+// scan_wgs: workgroups of k_psd_scan (n_slots x scan_parts x n_bands).  SDR_FFT_RESERVE=k forces k CUs for every k_fft_r32
+// launch (the launcher keeps at least one workgroup).
+constexpr int kReserveRounds = 2;
+constexpr int kReserveExtra = 24;
+constexpr int kReserveMax = 64;
+constexpr int kReserveDeviceShare = 4;  // the launcher caps the rule's value at CUs / 4 (a forced one it takes as it is)
+constexpr int kReserveMinFrames = 2048;
+inline int fft_reserve_cus(const Switches &sw, const FftChoice &c, bool noise_scan, int n_frames, int n_bands, int scan_wgs, bool fft_queue_alone = true)
+{
+    if (!c.r32)
+        return 0;
+    if (sw.fft_reserve >= 0)
+        return sw.fft_reserve;
+    if (!noise_scan || !fft_queue_alone || (long)n_frames * n_bands < kReserveMinFrames)
+        return 0;
+    const int r = (scan_wgs + kReserveRounds - 1) / kReserveRounds + kReserveExtra;
+    return r > kReserveMax ? kReserveMax : r;
+}
+
 enum class Refine { NONE, NARROW, WIDE };
 
 struct BatchGeometry {
     int n_bands, n, max_batch_frames, max_chunks;
+    // the FFT's stream was found on a hardware queue that none of the bank's other streams uses (sdr_bank::fft_queue_alone,
+    // probed at sdr_create and sdr_set_stream): only then can the other stages run beside an FFT launch
+    bool fft_queue_alone = true;
 };
 
 struct BatchPlan {
@@ -224,13 +279,19 @@ inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_fr
         p.n_slots = p.n_chunks + 1;
     }
     // two parts while the slots alone are fewer than a quarter of the CUs; from there on whole slots: with 16-byte loads a
-    // workgroup walks a frame in 1.6 us, and 83 fat workgroups hold less CU time than 166 - config 3: 205.5 -> 209.7 GS/s
+    // workgroup walks a frame in 1.6 us, and 83 fat workgroups hold less CU time than 166 - config 3: 205.5 -> 209.7 GS/s.
+    // Measured again beside the FFT grid's reserve (64 free CUs): two parts at every batch length 220.9 / 220.9 GS/s, this
+    // rule 221.7 / 220.4 - no difference, the rule stays (profiles/reserve_plan_rules.jsonl)
     p.scan_parts = (long)p.n_slots * g.n_bands < 64 ? 2 : 1;
+    p.fft.reserve_cus = fft_reserve_cus(sw, p.fft, p.noise_scan, n_frames, g.n_bands, p.n_slots * p.scan_parts * g.n_bands, g.fft_queue_alone);
+    p.fft.reserve_forced = p.fft.r32 && sw.fft_reserve >= 0;
 
     // Spans of 4096 bins x 256 threads keep a cumulation's refinement - a latency chain of a hundred scattered sector reads -
     // short where the peaks stream's length bounds the step (few cumulations per batch).  With many cumulations per batch
     // what counts is the CU time the kernel HOLDS: four waves of a small workgroup hold a whole CU against the FFT's
-    // workgroups just as sixteen do, so a workgroup takes the whole row (10.9 -> CU-ms per 8192-frame step).
+    // workgroups just as sixteen do, so a workgroup takes the whole row (10.9 -> CU-ms per 8192-frame step).  With CUs
+    // left free beside the FFT (fft_reserve_cus) that reason is gone, and so is the difference: SDR_REFINE_WIDE=0 220.9 /
+    // 221.1 GS/s against 221.7 / 220.4 with the whole row at config 3 - the rule stays (profiles/reserve_plan_rules.jsonl).
     const bool wide = sw.refine_wide >= 0 ? sw.refine_wide != 0 : (g.n >= 4096 && (long)p.n_chunks * g.n_bands >= 64);
     p.refine = !p.bound ? Refine::NONE : wide ? Refine::WIDE : Refine::NARROW;
     return p;

@@ -1194,8 +1194,8 @@ hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, con
             return hipErrorInvalidValue;
         const fft64::cplx *tw32 = tw + fft64::Plan<14>::TW_TOTAL;
         if (fmt == InFormat::SC16)
-            return launch_fft_r32_sc16(static_cast<const int16_t *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
-        return launch_fft_r32(static_cast<const float *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+            return launch_fft_r32_sc16(static_cast<const int16_t *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, fft.reserve_cus, fft.reserve_forced, stream);
+        return launch_fft_r32(static_cast<const float *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, fft.reserve_cus, fft.reserve_forced, stream);
     }
 #endif
     switch (logn) {

@@ -662,14 +662,11 @@ int r32_twiddle_count() { return fft32::kTwTotal; }
 void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out) { fft32::build_twiddles(wre, wim, out); }
 #endif
 
-// Workgroups per band: one per CU, less SDR_R32_RESERVE CUs left to the tail stages of the other streams (measured at
-// config 3, see HISTORY round 6), never more than there are frames.
-#if !defined(SDR_R32_RESERVE)
-#define SDR_R32_RESERVE 0
-#endif
-
+// Workgroups per band: one per CU, less the reserve_cus CUs the batch plan leaves to the other streams' kernels
+// (host/batch_plan.h fft_reserve_cus; the rule's value capped at a quarter of the device, a forced one taken as it is),
+// at least one, never more than there are frames.
 hipError_t SDR_R32_LAUNCH(const SDR_R32_IN *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
+                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, hipStream_t stream)
 {
     constexpr int kMaxDevices = 64;
     static std::once_flag setup_once[kMaxDevices];
@@ -709,13 +706,15 @@ hipError_t SDR_R32_LAUNCH(const SDR_R32_IN *iq, const BatchCursor *cur, const ff
 #else
     if (frame_stride != fft32::N)  // overlapped frames: the strided kernel (k_fft_r32_hop.hip)
 #if SDR_R32_SC16
-        return launch_fft_r32_hop_sc16(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+        return launch_fft_r32_hop_sc16(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, stream);
 #else
-        return launch_fft_r32_hop(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+        return launch_fft_r32_hop(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, stream);
 #endif
     const unsigned frames_and_shift = (unsigned)n_frames;
 #endif
-    const int cus = std::max(1, cu_count[dev] - SDR_R32_RESERVE);
+    // the rule's value is sized on a 256-CU device: on a smaller one (or a partition) never more than a quarter of it
+    const int reserve = reserve_forced ? reserve_cus : std::min(reserve_cus, cu_count[dev] / kReserveDeviceShare);
+    const int cus = std::max(1, cu_count[dev] - std::max(0, reserve));
     const int grid = std::min((cus + n_bands - 1) / n_bands, n_frames);
     launch_kernel(r32::SDR_R32_KERNEL, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, stream, iq, cur, tw, psd, (unsigned)in_stride, out_stride,
                   frames_and_shift, tap.steal, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used);

@@ -192,18 +192,20 @@ hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, 
                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
 int twiddle_count(int logn);
 void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx *out);
-// k_fft_r32.hip: N = 16384 as 512 threads x 32 points with the next frame prefetched into registers (own twiddle layout)
+// k_fft_r32.hip: N = 16384 as 512 threads x 32 points with the next frame prefetched into registers (own twiddle layout);
+// reserve_cus: CUs the grid leaves free (FftChoice::reserve_cus; unless reserve_forced at most CUs / kReserveDeviceShare) -
+// workgroups per band = max(1, ceil((CUs - reserve_cus) / n_bands)), at most n_frames
 hipError_t launch_fft_r32(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
+                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, hipStream_t stream);
 // k_fft_r32_sc16.hip: the same kernel reading sc16 frames
 hipError_t launch_fft_r32_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                               size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
+                               size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, hipStream_t stream);
 // k_fft_r32_hop.hip / k_fft_r32_hop_sc16.hip: the same kernels for frame_stride < N (a power of two); the two launchers
 // above hand such a launch on themselves
 hipError_t launch_fft_r32_hop(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                              size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
+                              size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, hipStream_t stream);
 hipError_t launch_fft_r32_hop_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                                   size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
+                                   size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, hipStream_t stream);
 int r32_twiddle_count();
 void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out);
 // wpb_forced: windows per workgroup (0: the launcher's rule); mfma: the matrix-pipe variance kernel (host/batch_plan.h)

@@ -37,16 +37,22 @@ __device__ unsigned long long g_fft_wg[2048][4];
 namespace sdr {
 // (this tool times float32 input only: launch_fft's sc16 branch is linked to nothing - k_fft_r32_sc16.hip is k_fft_r32.hip
 // compiled again and cannot share this translation unit)
-hipError_t launch_fft_r32_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, hipStream_t)
+hipError_t launch_fft_r32_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, hipStream_t)
 {
     return hipErrorNotSupported;
 }
 // (nor dense input's strided twins, k_fft_r32_hop.hip / k_fft_r32_hop_sc16.hip: this tool's frames do not overlap)
-hipError_t launch_fft_r32_hop(const float *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, hipStream_t)
+hipError_t launch_fft_r32_hop(const float *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, hipStream_t)
 {
     return hipErrorNotSupported;
 }
-hipError_t launch_fft_r32_hop_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, hipStream_t)
+hipError_t launch_fft_r32_hop_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, hipStream_t)
+{
+    return hipErrorNotSupported;
+}
+// (nor the two-phase kernels of N = 32768 / 65536, k_fft_2p.hip)
+hipError_t launch_fft_2p(int, FftChoice, InFormat, const void *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap,
+                         hipStream_t)
 {
     return hipErrorNotSupported;
 }
