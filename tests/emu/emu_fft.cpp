@@ -4,6 +4,7 @@
 // oracle's stage-by-stage radix-2 FFT (oracle/sdr_oracle.c: orc_fft_radix2).
 //
 // usage: emu_fft <liborc.so>     (exit code 0 = all sizes bit-identical)
+//        emu_fft <liborc.so> nonfinite     the psd classes of frames with one non-finite sample (nonfinite_classes.h)
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 
 #include "../../sdrainer_amd/csrc/fft_f64.h"
 #include "../../sdrainer_amd/csrc/twiddles.h"
+#include "nonfinite_classes.h"
 
 using namespace fft64;
 
@@ -238,6 +240,60 @@ static int audit_tw_rows()
     return 0;
 }
 
+// One frame through the kernel's phase functions: load, every pass and exchange, the bins in natural order.
+template <int LOGN>
+static int transform(const std::vector<float> &iq, const std::vector<cplx> &tw, std::vector<double> &yre, std::vector<double> &yim)
+{
+    using PL = Plan<LOGN>;
+    const int N = PL::N;
+    std::vector<double> xr((size_t)N), xi((size_t)N), lre((size_t)exchange_words<LOGN>()), lim((size_t)exchange_words<LOGN>());
+    for (int t = 0; t < PL::T; t++)
+        load_input<LOGN>(iq.data(), t, &xr[(size_t)t * PL::R], &xi[(size_t)t * PL::R]);
+    Passes<LOGN, 0>::run(xr, xi, tw.data(), lre, lim);
+    std::vector<char> seen((size_t)N, 0);
+    for (int t = 0; t < PL::T; t++)
+        for (int s = 0; s < PL::R; s++) {
+            const int b = output_bin<LOGN>(t, s);
+            if (b < 0 || b >= N || seen[b]) {
+                printf("LOGN=%d: output_bin not a bijection (t=%d s=%d -> %d)\n", LOGN, t, s, b);
+                return 1;
+            }
+            seen[b] = 1;
+            yre[b] = xr[(size_t)t * PL::R + s];
+            yim[b] = xi[(size_t)t * PL::R + s];
+        }
+    return 0;
+}
+
+// A frame with ONE non-finite sample component ("Inf / NaN inputs"): the class of every psd word, kernel and
+// oracle.  The kernels skip the multiplications by the literal twiddles 1 and -i that the reference carries out, and
+// (Inf + bi) * (1 + 0i) = (Inf, NaN) where the skipped form keeps (Inf, b): the classes may differ, and this prints where.
+
+template <int LOGN>
+static int nonfinite(orc_iq_fft_t orc_fft)
+{
+    using PL = Plan<LOGN>;
+    const int N = PL::N;
+    std::vector<double> wre, wim;
+    radix2_factors(N, wre, wim);
+    std::vector<cplx> tw((size_t)PL::TW_TOTAL);
+    build_pass_twiddles<LOGN>(wre.data(), wim.data(), tw.data());
+    return nonfinite_cases(N, [&](const std::vector<float> &iq, std::vector<float> &psd) {
+        std::vector<double> yre((size_t)N), yim((size_t)N);
+        if (transform<LOGN>(iq, tw, yre, yim))
+            return 1;
+        for (int i = 0; i < N; i++)
+            psd[i] = (float)(yre[i] * yre[i] + yim[i] * yim[i]);
+        return 0;
+    }, [&](const std::vector<float> &iq, std::vector<float> &psd) {
+        std::vector<double> rre((size_t)N), rim((size_t)N);
+        orc_fft(N, iq.data(), rre.data(), rim.data());
+        for (int i = 0; i < N; i++)
+            psd[i] = (float)(rre[i] * rre[i] + rim[i] * rim[i]);
+        return 0;
+    });
+}
+
 template <int LOGN>
 static int check(orc_iq_fft_t orc_fft, orc_factors_t orc_fac, unsigned seed)
 {
@@ -264,23 +320,9 @@ static int check(orc_iq_fft_t orc_fft, orc_factors_t orc_fac, unsigned seed)
     std::vector<cplx> tw((size_t)PL::TW_TOTAL);
     build_pass_twiddles<LOGN>(wre.data(), wim.data(), tw.data());
 
-    std::vector<double> xr((size_t)N), xi((size_t)N), lre((size_t)exchange_words<LOGN>()), lim((size_t)exchange_words<LOGN>());
-    for (int t = 0; t < PL::T; t++)
-        load_input<LOGN>(iq.data(), t, &xr[(size_t)t * PL::R], &xi[(size_t)t * PL::R]);
-    Passes<LOGN, 0>::run(xr, xi, tw.data(), lre, lim);
-
-    std::vector<double> yre((size_t)N), yim((size_t)N), seen((size_t)N, 0.0);
-    for (int t = 0; t < PL::T; t++)
-        for (int s = 0; s < PL::R; s++) {
-            const int b = output_bin<LOGN>(t, s);
-            if (b < 0 || b >= N || seen[b] != 0.0) {
-                printf("LOGN=%d: output_bin not a bijection (t=%d s=%d -> %d)\n", LOGN, t, s, b);
-                return 1;
-            }
-            seen[b] = 1.0;
-            yre[b] = xr[(size_t)t * PL::R + s];
-            yim[b] = xi[(size_t)t * PL::R + s];
-        }
+    std::vector<double> yre((size_t)N), yim((size_t)N);
+    if (transform<LOGN>(iq, tw, yre, yim))
+        return 1;
     std::vector<double> rre((size_t)N), rim((size_t)N);
     orc_fft(N, iq.data(), rre.data(), rim.data());
     long bad = 0;
@@ -319,6 +361,8 @@ int main(int argc, char **argv)
     }
     auto orc_fft = (orc_iq_fft_t)dlsym(h, "orc_iq_fft");
     auto orc_fac = (orc_factors_t)dlsym(h, "orc_radix2_factors");
+    if (argc > 2 && !strcmp(argv[2], "nonfinite"))  // (the table only: one size with an LDS exchange only, one of layout B)
+        return nonfinite<9>(orc_fft) | nonfinite<14>(orc_fft);
     int rc = 0;
     rc |= check<9>(orc_fft, orc_fac, 1);
     rc |= check<10>(orc_fft, orc_fac, 2);

@@ -5,6 +5,7 @@
 // (oracle/sdr_oracle.c: orc_iq_to_spectrum_and_psd), at N = 32768 and 65536, float32 and sc16 input (the latter through
 // sc16.h's conversion, as the kernel reads it), random, full-scale and zero frames.
 //   usage: emu_fft_2p <liborc.so>        prints "<case>: <k> mismatches" per case
+//          emu_fft_2p <liborc.so> nonfinite     the psd classes of frames with one non-finite sample (nonfinite_classes.h)
 #include <dlfcn.h>
 
 #include <cmath>
@@ -16,6 +17,7 @@
 
 #include "../../sdrainer_amd/csrc/fft_2p.h"
 #include "../../sdrainer_amd/csrc/twiddles.h"
+#include "nonfinite_classes.h"
 
 typedef void (*orc_psd_t)(int, const float *, float *, float *);
 
@@ -189,6 +191,26 @@ static int run(orc_psd_t orc, const char *kind, bool sc16in, unsigned seed)
     return bad || tap_bad;
 }
 
+// the psd classes of frames with one non-finite sample component, both phases and oracle (nonfinite_classes.h)
+template <int LOGN>
+static int nonfinite(orc_psd_t orc)
+{
+    Emu<LOGN> emu;
+    constexpr int N = 1 << LOGN;
+    return nonfinite_cases(N, [&](const std::vector<float> &iq, std::vector<float> &psd) {
+        std::vector<cplx> y(N);
+        std::vector<int> bins;
+        std::vector<float> tap;
+        emu.phase_a([&](int i, double &re, double &im) { re = (double)iq[2 * i]; im = (double)iq[2 * i + 1]; }, y);
+        emu.phase_b(y, psd, bins, tap);
+        return 0;
+    }, [&](const std::vector<float> &iq, std::vector<float> &psd) {
+        std::vector<float> spec(N);
+        orc(N, iq.data(), spec.data(), psd.data());
+        return 0;
+    });
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) {
@@ -203,6 +225,8 @@ int main(int argc, char **argv)
     auto orc = (orc_psd_t)dlsym(h, "orc_iq_to_spectrum_and_psd");
     if (!orc)
         return 2;
+    if (argc > 2 && !strcmp(argv[2], "nonfinite"))
+        return nonfinite<15>(orc) | nonfinite<16>(orc);
     int rc = 0;
     for (const char *kind : {"random", "fullscale", "zero"})
         for (bool s : {false, true}) {

@@ -4,6 +4,7 @@
 // Compared bit for bit with the oracle's stage-by-stage radix-2 FFT (oracle/sdr_oracle.c: orc_iq_fft).
 //
 // usage: emu_fft_r32 <liborc.so>     (exit code 0 = bit-identical and conflict-free)
+//        emu_fft_r32 <liborc.so> nonfinite     the psd classes of frames with one non-finite sample (nonfinite_classes.h)
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 
 #include "../../sdrainer_amd/csrc/fft_r32.h"
 #include "../../sdrainer_amd/csrc/twiddles.h"
+#include "nonfinite_classes.h"
 
 using namespace fft32;
 
@@ -150,22 +152,9 @@ static int audit_maps()
     return rc;
 }
 
-static int check(orc_iq_fft_t orc_fft, unsigned seed)
+// One frame through the plan's passes and exchanges, the bins in natural order.
+static int transform(const std::vector<float> &iq, const std::vector<cplx> &tw, std::vector<double> &yre, std::vector<double> &yim)
 {
-    std::mt19937 rng(seed);
-    std::normal_distribution<float> nd(0.f, 1.f);
-    std::vector<float> iq(2 * (size_t)N);
-    for (auto &v : iq)
-        v = nd(rng);
-    for (int n = 0; n < N; n++) {
-        iq[2 * n] += 100.f * (float)cos(2 * M_PI * 37.0 * n / N);
-        iq[2 * n + 1] += 100.f * (float)sin(2 * M_PI * 37.0 * n / N);
-    }
-    std::vector<double> wre, wim;
-    fft64::radix2_factors(N, wre, wim);
-    std::vector<cplx> tw((size_t)kTwTotal);
-    build_twiddles(wre.data(), wim.data(), tw.data());
-
     std::vector<double> xr((size_t)N), xi((size_t)N), lre((size_t)kExchangeBytes / 8), lim((size_t)kExchangeBytes / 8);
     // setSamplesFromIQ (dsp/fft.go:59-69)
     for (int t = 0; t < T; t++)
@@ -221,7 +210,6 @@ static int check(orc_iq_fft_t orc_fft, unsigned seed)
         first_chunks2<4, false, 4>(tw2, first);
         run_pass2_with<4, false, 4>(&xr[(size_t)t * R], &xi[(size_t)t * R], first, tw2);
     }
-    std::vector<double> yre((size_t)N), yim((size_t)N);
     std::vector<char> seen((size_t)N, 0);
     for (int t = 0; t < T; t++)
         for (int s = 0; s < R; s++) {
@@ -234,6 +222,53 @@ static int check(orc_iq_fft_t orc_fft, unsigned seed)
             yre[b] = xr[(size_t)t * R + s];
             yim[b] = xi[(size_t)t * R + s];
         }
+    return 0;
+}
+
+static std::vector<cplx> twiddles()
+{
+    std::vector<double> wre, wim;
+    fft64::radix2_factors(N, wre, wim);
+    std::vector<cplx> tw((size_t)kTwTotal);
+    build_twiddles(wre.data(), wim.data(), tw.data());
+    return tw;
+}
+
+// the psd classes of frames with one non-finite sample component, plan and oracle (nonfinite_classes.h)
+static int nonfinite(orc_iq_fft_t orc_fft)
+{
+    const std::vector<cplx> tw = twiddles();
+    return nonfinite_cases(N, [&](const std::vector<float> &iq, std::vector<float> &psd) {
+        std::vector<double> yre((size_t)N), yim((size_t)N);
+        if (transform(iq, tw, yre, yim))
+            return 1;
+        for (int i = 0; i < N; i++)
+            psd[i] = (float)(yre[i] * yre[i] + yim[i] * yim[i]);
+        return 0;
+    }, [&](const std::vector<float> &iq, std::vector<float> &psd) {
+        std::vector<double> rre((size_t)N), rim((size_t)N);
+        orc_fft(N, iq.data(), rre.data(), rim.data());
+        for (int i = 0; i < N; i++)
+            psd[i] = (float)(rre[i] * rre[i] + rim[i] * rim[i]);
+        return 0;
+    });
+}
+
+static int check(orc_iq_fft_t orc_fft, unsigned seed)
+{
+    std::mt19937 rng(seed);
+    std::normal_distribution<float> nd(0.f, 1.f);
+    std::vector<float> iq(2 * (size_t)N);
+    for (auto &v : iq)
+        v = nd(rng);
+    for (int n = 0; n < N; n++) {
+        iq[2 * n] += 100.f * (float)cos(2 * M_PI * 37.0 * n / N);
+        iq[2 * n + 1] += 100.f * (float)sin(2 * M_PI * 37.0 * n / N);
+    }
+    const std::vector<cplx> tw = twiddles();
+    std::vector<double> yre((size_t)N), yim((size_t)N);
+    if (transform(iq, tw, yre, yim))
+        return 1;
     std::vector<double> rre((size_t)N), rim((size_t)N);
     orc_fft(N, iq.data(), rre.data(), rim.data());
     long bad = 0;
@@ -259,6 +294,8 @@ int main(int argc, char **argv)
         return 2;
     }
     auto orc_fft = (orc_iq_fft_t)dlsym(h, "orc_iq_fft");
+    if (argc > 2 && !strcmp(argv[2], "nonfinite"))
+        return nonfinite(orc_fft);
     int rc = audit_maps();
     rc |= check(orc_fft, 6);
     rc |= check(orc_fft, 7);

@@ -11,12 +11,14 @@ the same parity tests here; and the scan is run with its literal fallback FORCED
 (SDR_NOISE_FORCE_EXACT), so that the list of flagged frames, the exact kernel behind it and the mix of both are exercised
 (a frame is flagged by itself about three times in 10^5)."""
 import os
+import re
 import subprocess
 import sys
 
 import pytest
 
 import fuzz_paths_gen
+import value_range_gen
 
 pytestmark = pytest.mark.gpu
 
@@ -24,6 +26,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ("test_receiver_run_bit_exact or test_nine_window_geometry or test_config5_geometry or test_batch_split_invariance_and_carry"
          " or test_scan_segment_geometries")
 FUZZ_PATHS = "test_random_paths and (" + " or ".join(f"seed{s:03d}-" for s in fuzz_paths_gen.forced_selection()) + ")"
+# the N = 512 cases of every value-range regime and k_fft_r32's floor and carrier_inf cases (tests/value_range_gen.py), by
+# node id: a -k expression matches substrings, of the module's name and of other tests' ids too
+VALUE_RANGE_FILES = [f"tests/test_value_range_gpu.py::test_value_range[{i}]" for i in value_range_gen.FORCED]
+VALUE_RANGE = ""
 
 
 @pytest.mark.parametrize("env, files, sel", [
@@ -52,9 +58,20 @@ FUZZ_PATHS = "test_random_paths and (" + " or ".join(f"seed{s:03d}-" for s in fu
     ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "0"}, ["tests/test_gpu_fuzz_paths.py"], FUZZ_PATHS),
     ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "1"}, ["tests/test_gpu_fuzz_paths.py"], FUZZ_PATHS),
     ({"SDR_NOISE_PATH": "chains"}, ["tests/test_gpu_fuzz_paths.py"], FUZZ_PATHS),
+    # psd words across the whole float32 range (subnormal, zero among subnormals, +Inf at carriers, in the noise, everywhere,
+    # 670 dB within a cumulation): the scan's literal fallback on these rows, the chains with both variance kernels, and the
+    # bound kernels on their floor_hw and `special` branches in both refinement shapes
+    ({"SDR_NOISE_FORCE_EXACT": "1"}, VALUE_RANGE_FILES, VALUE_RANGE),
+    ({"SDR_NOISE_FORCE_EXACT": "3"}, VALUE_RANGE_FILES, VALUE_RANGE),
+    ({"SDR_NOISE_PATH": "chains"}, VALUE_RANGE_FILES, VALUE_RANGE),
+    ({"SDR_NOISE_PATH": "chains", "SDR_VAR_MFMA": "1"}, VALUE_RANGE_FILES, VALUE_RANGE),
+    ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "0"}, VALUE_RANGE_FILES, VALUE_RANGE),
+    ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "1"}, VALUE_RANGE_FILES, VALUE_RANGE),
 ])
 def test_parity_with_the_other_implementation_forced(env, files, sel):
     p = subprocess.run([sys.executable, "-m", "pytest", *[os.path.join(ROOT, f) for f in files], "-q", "-x", "-m", "gpu", "-k", sel,
                         "-p", "no:cacheprovider"], env=dict(os.environ, **env), cwd=ROOT, capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-2000:]
     assert " passed" in p.stdout and "failed" not in p.stdout
+    if files is VALUE_RANGE_FILES:  # exactly the cases named, none deselected and none besides
+        assert len(files) == 10 and re.search(r"(^|\s)10 passed", p.stdout) and "deselected" not in p.stdout, p.stdout[-3000:]
