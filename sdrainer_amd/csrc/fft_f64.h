@@ -6,10 +6,14 @@
 // over a bit-reversed copy of the input.  Any schedule that evaluates that same graph with the same
 // IEEE operations (complex multiply as (ac-bd, ad+bc), no FMA contraction) and the same twiddle
 // VALUES produces the same bits.  So each thread keeps R = 16 (8 for N=512) points in VGPRs and runs
-// LOGR consecutive stages on them (a "pass"), then the data is exchanged for the next pass - inside a
-// wave's own block of LDS, across waves through LDS (once), or in registers (make_layout, make_swap_plan).  Twiddles are never recomputed on the device: the host builds go-dsp's table (radix2 factors
-// via math.Sincos, even entries copied from the half-size table) and uploads it re-laid-out per pass
-// so a wave reads them with coalesced 16-byte loads.
+// LOGR consecutive stages on them (a "pass"), then the data is exchanged for the next pass.  One
+// assignment of index bits to (register slot, lane, wave) per pass (make_layout) decides how: inside a
+// wave's own block of LDS, across waves through LDS (once, behind pass 1), or - where only lane bits 4
+// and 5 trade places with slot bits - in registers (make_swap_plan).  The frame itself is staged
+// through LDS by LDS-DMA and read from there in pass 0's layout ("Input staging" below).  Twiddles are
+// never recomputed on the device: the host builds go-dsp's table (radix2 factors via math.Sincos, even
+// entries copied from the half-size table) and uploads it re-laid-out per pass so a wave reads them
+// with coalesced 16-byte loads.
 //
 // Everything here is `SDR_HD` and free of HIP intrinsics so tests/emu can run the very same phase
 // functions thread-by-thread on the CPU to validate the index math without a GPU.
@@ -27,26 +31,6 @@ namespace fft64 {
 struct cplx {
     double x, y;
 };
-
-// Two assignments of index bits to (register slot, lane, wave) - make_layout below:
-//  A  passes 0,1 share their wave bits, the cross-wave exchange sits after pass 1; the frame is staged through LDS
-//     (LDS-DMA) and read in the pass-0 layout.  All sizes below SDR_FFT_LAYOUT_B_FROM.
-//  B  the cross-wave exchange sits after pass 0; from then on wave w owns the sub-problem "index bits 0-3 = w".
-//     Pass 0's lanes are the six lowest sample-number bits, so a wave loads 512 contiguous bytes per register slot
-//     straight from memory - no LDS staging, the next frame is prefetched into registers - and pass 1's twiddles depend
-//     on the wave only (scalar loads).  Needs the wave id to cover a whole pass's worth of bits (WB == LOGR): N = 16384.
-//     MEASURED (round 3, tools/fft_bench, 2048 frames of 16384): bit-identical, but no faster - 0.168 ms per launch
-//     against layout A's 0.165.  What it gains (the next frame's LDS-DMA under passes 1-2: A loses 0.050 ms to the input
-//     wait, B 0.032) it pays back: the register-only exchanges (+128 v_permlane, 128 ds_bpermute per wave), a
-//     transposed epilogue through LDS (wave w holds the bins = w mod 16; stored from registers they cost 0.087 ms)
-//     and waves that drift apart over the long barrier-free stretch.  And its workgroups must take several frames
-//     each, which starves the tail stages of CUs inside the pipeline (0.273 ms per step against 0.216).  So it is
-//     OFF by default (SDR_FFT_LAYOUT_B_FROM = 15 selects no size); -DSDR_FFT_LAYOUT_B_FROM=14 builds it, tests/emu
-//     checks both layouts on the CPU.
-#if !defined(SDR_FFT_LAYOUT_B_FROM)
-#define SDR_FFT_LAYOUT_B_FROM 15
-#endif
-SDR_HD constexpr bool layout_b(int logn) { return logn >= SDR_FFT_LAYOUT_B_FROM; }
 
 template <int LOGN>
 struct Plan {
@@ -75,12 +59,10 @@ struct Plan {
         return o;
     }
     static constexpr int TW_TOTAL = tw_offset(NPASS);
-    static constexpr bool LB = layout_b(LOGN);
-    static_assert(!LB || WB == LOGR, "layout B needs the wave id to hold exactly one pass's bits");
     // Exchange e (between pass e and e+1) moves data between waves only when the set of index bits
-    // held in the wave id changes; that happens once: after pass 1 in layout A, after pass 0 in layout B
-    // (see make_layout).  Every other exchange stays inside a wave and needs no workgroup barrier.
-    SDR_HD static constexpr bool cross_wave(int e) { return WB > 0 && e == (LB ? 0 : 1); }
+    // held in the wave id changes; that happens once, after pass 1 (see make_layout).  Every other
+    // exchange stays inside a wave and needs no workgroup barrier.
+    SDR_HD static constexpr bool cross_wave(int e) { return WB > 0 && e == 1; }
 };
 
 SDR_HD inline unsigned brev_bits(unsigned v, int bits)
@@ -106,7 +88,9 @@ SDR_HD inline unsigned brev_bits(unsigned v, int bits)
 //          upwards (lane bits 0-3 = index bits 0-3: coalesced twiddle loads and output stores).
 //
 // With that choice passes 0 and 1 share their wave bits, and so do passes 2 and 3: only the exchange
-// after pass 1 crosses waves.
+// after pass 1 crosses waves (Plan::cross_wave).  The exchanges that turn out to move nothing but lane
+// bits 4 / 5 against slot bits need no LDS (make_swap_plan): exchange 1 at N = 1024 (no wave bits
+// there), exchange 2 at N = 8192 and 16384.
 // ---------------------------------------------------------------------------------------------
 struct Layout {
     int sbit[4];   // index bit held by slot bit j
@@ -126,22 +110,13 @@ SDR_HD constexpr Layout make_layout(int P)
         used[L.sbit[j]] = true;
     }
     const int wz_hi = (PL::NPASS == 3) ? 2 * PL::LOGR - (PL::LOGR - PL::LAST_LOG) : 2 * PL::LOGR;
-    // layout B: pass 0 keeps pass 1's slot bits in the wave id, every later pass the bits of pass 0's slots
-    const int wlo = PL::LB ? (P == 0 ? PL::LOGR : 0) : (P <= 1) ? 2 * PL::LOGR : wz_hi - PL::WB;
+    const int wlo = (P <= 1) ? 2 * PL::LOGR : wz_hi - PL::WB;
     for (int j = 0; j < PL::WB; j++) {
         L.tbit[PL::LOGL + j] = wlo + j;
         used[wlo + j] = true;
     }
     int k = 0;
-    if (PL::LB && P >= 1) {
-        // Layout B keeps LDS for the one cross-wave exchange (and the next frame's samples): behind it index bits
-        // move between slots and lanes in registers only - v_permlane16/32_swap trade a slot bit for lane bit 4 / 5,
-        // ds_bpermute (the LDS crossbar, no LDS memory) rotates other lane bits into those two positions
-        // (make_reg_plan).  The lane orders below are the ones those steps produce.
-        constexpr int kLanesB[4][6] = {{0, 0, 0, 0, 0, 0}, {10, 11, 12, 13, 8, 9}, {4, 5, 12, 13, 6, 7}, {4, 5, 6, 7, 8, 9}};
-        for (int j = 0; j < PL::LOGL; j++)
-            L.tbit[j] = kLanesB[P][j];
-    } else if (P == 0) {
+    if (P == 0) {
         for (int b = LOGN - 1; b >= 0; b--)
             if (!used[b])
                 L.tbit[k++] = b;
@@ -474,144 +449,6 @@ inline void exchange_swap_wave(double (*x)[Plan<LOGN>::R])
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Register exchanges in general: a short sequence of steps on a wave's x[lane][slot],
-//   SWAP(a, b)  slot bit a <-> lane bit 4 and slot bit b <-> lane bit 5 (either may be -1: left alone)
-//   ROT(p)      lane positions (p, p+1) <-> (4, 5): every register moves to the lane with those bits exchanged
-// make_reg_plan(E).n == 0: exchange E goes through LDS.
-// ---------------------------------------------------------------------------------------------
-struct RegStep {
-    int rot;   // 0: SWAP, 1: ROT
-    int a, b;  // SWAP: slot bits for lane bits 4 / 5; ROT: a = p
-};
-struct RegPlan {
-    int n;
-    RegStep st[3];
-};
-
-template <int LOGN>
-SDR_HD constexpr RegPlan make_reg_plan(int E)
-{
-    using PL = Plan<LOGN>;
-    RegPlan R{0, {}};
-#if defined(SDR_FFT_B_LDS_EXCH)
-    // (experiment, round 4: layout B with its two wave-local exchanges through the wave's own LDS block instead of
-    // v_permlane / ds_bpermute.  VALID FOR ONE-FRAME WORKGROUPS ONLY (SDR_FFT_FPW=1): the blocks overlap the next frame's
-    // staging image.  Measured, 2048 x 16384 standalone: 0.169 ms (registers: 0.185 at one frame per workgroup, 0.168 at
-    // eight) against layout A's 0.162 - the cross-wave exchange right behind pass 0 still waits for the last wave's
-    // samples, and the transposed epilogue costs what the barrier-free second half gains.  With the next frame's DMA
-    // issued as if LDS were free (wrong results, timing only) 0.155: the price of that LDS is what separates the two.)
-    if (PL::LB)
-        return R;
-#endif
-    if (PL::LB) {
-        if (E == 1) {
-            R.n = 3;
-            R.st[0] = RegStep{0, 0, 1};
-            R.st[1] = RegStep{1, 0, 0};
-            R.st[2] = RegStep{0, 2, 3};
-        } else if (E == 2) {
-            R.n = 2;
-            R.st[0] = RegStep{1, 2, 0};
-            R.st[1] = RegStep{0, 0, 1};
-        }
-        return R;
-    }
-    const SwapPlan S = make_swap_plan<LOGN>(E);
-    if (S.ok) {
-        R.n = 1;
-        R.st[0] = RegStep{0, S.slot_bit_lane4, S.slot_bit_lane5};
-    }
-    return R;
-}
-
-// does the plan turn pass E's layout into pass E+1's?  (bit bookkeeping only)
-template <int LOGN>
-SDR_HD constexpr bool reg_plan_valid(int E)
-{
-    using PL = Plan<LOGN>;
-    const RegPlan R = make_reg_plan<LOGN>(E);
-    if (R.n == 0)
-        return true;
-    Layout A = make_layout<LOGN>(E);
-    const Layout B = make_layout<LOGN>(E + 1);
-    for (int i = 0; i < R.n; i++) {
-        const RegStep &st = R.st[i];
-        if (st.rot) {
-            for (int j = 0; j < 2; j++) {
-                const int t = A.tbit[st.a + j];
-                A.tbit[st.a + j] = A.tbit[4 + j];
-                A.tbit[4 + j] = t;
-            }
-        } else {
-            if (st.a >= 0) {
-                const int t = A.sbit[st.a];
-                A.sbit[st.a] = A.tbit[4];
-                A.tbit[4] = t;
-            }
-            if (st.b >= 0) {
-                const int t = A.sbit[st.b];
-                A.sbit[st.b] = A.tbit[5];
-                A.tbit[5] = t;
-            }
-        }
-    }
-    for (int j = 0; j < PL::LOGR; j++)
-        if (A.sbit[j] != B.sbit[j])
-            return false;
-    for (int j = 0; j < PL::LOGT; j++)
-        if (A.tbit[j] != B.tbit[j])
-            return false;
-    return true;
-}
-
-// lane a register comes from in ROT(p): the lane number with bit positions (p, p+1) and (4, 5) exchanged
-SDR_HD constexpr int rot_source_lane(int lane, int p)
-{
-    const int lo = (lane >> p) & 3, hi = (lane >> 4) & 3;
-    return (lane & ~((3 << p) | (3 << 4))) | (hi << p) | (lo << 4);
-}
-
-// Host-side model of a register exchange for one wave (x[lane][slot]); tests/emu uses it.
-template <int LOGN, int E>
-inline void exchange_regs_wave(double (*x)[Plan<LOGN>::R])
-{
-    constexpr RegPlan P = make_reg_plan<LOGN>(E);
-    static_assert(P.n > 0 && reg_plan_valid<LOGN>(E), "exchange is not a valid register plan");
-    constexpr int R = Plan<LOGN>::R;
-    for (int i = 0; i < P.n; i++) {
-        const RegStep st = P.st[i];
-        if (st.rot) {
-            double tmp[64][R];
-            for (int l = 0; l < 64; l++)
-                for (int s = 0; s < R; s++)
-                    tmp[l][s] = x[rot_source_lane(l, st.a)][s];
-            for (int l = 0; l < 64; l++)
-                for (int s = 0; s < R; s++)
-                    x[l][s] = tmp[l][s];
-            continue;
-        }
-        for (int round = 0; round < 2; round++) {
-            const int sb = round == 0 ? st.a : st.b;
-            const int half = round == 0 ? 16 : 32;
-            if (sb < 0)
-                continue;
-            for (int a = 0; a < R; a++) {
-                if ((a >> sb) & 1)
-                    continue;
-                const int b = a | (1 << sb);
-                // v_permlaneNN_swap A, B: A's lanes with the bit set <-> B's lanes with the bit clear
-                for (int l = 0; l < 64; l++)
-                    if (!(l & half)) {
-                        const double t = x[l + half][a];
-                        x[l + half][a] = x[l][b];
-                        x[l][b] = t;
-                    }
-            }
-        }
-    }
-}
-
 #if defined(__HIPCC__)
 __device__ __forceinline__ void swap_halves(double &a, double &b, bool rows16)
 {
@@ -645,51 +482,6 @@ __device__ __forceinline__ void exchange_swap(double (&x)[Plan<LOGN>::R])
             swap_halves(x[a], x[a | (1 << P.slot_bit_lane5)], false);
 }
 #endif
-
-#if defined(__HIPCC__)
-// Device: the register exchange of plan E on one array of R doubles (called once for the real, once for the
-// imaginary parts).
-template <int LOGN, int E>
-__device__ __forceinline__ void exchange_regs(double (&x)[Plan<LOGN>::R])
-{
-    constexpr RegPlan P = make_reg_plan<LOGN>(E);
-    static_assert(P.n > 0 && reg_plan_valid<LOGN>(E), "exchange is not a valid register plan");
-    constexpr int R = Plan<LOGN>::R;
-#pragma unroll
-    for (int i = 0; i < P.n; i++) {
-        if (P.st[i].rot) {
-            const int lane = (int)(threadIdx.x & 63);
-            const int src = rot_source_lane(lane, P.st[i].a) * 4;
-#pragma unroll
-            for (int a = 0; a < R; a++) {
-                const int lo = __builtin_amdgcn_ds_bpermute(src, __double2loint(x[a]));
-                const int hi = __builtin_amdgcn_ds_bpermute(src, __double2hiint(x[a]));
-                x[a] = __hiloint2double(hi, lo);
-            }
-        } else {
-#pragma unroll
-            for (int a = 0; a < R; a++)
-                if (P.st[i].a >= 0 && !((a >> P.st[i].a) & 1))
-                    swap_halves(x[a], x[a | (1 << P.st[i].a)], true);
-#pragma unroll
-            for (int a = 0; a < R; a++)
-                if (P.st[i].b >= 0 && !((a >> P.st[i].b) & 1))
-                    swap_halves(x[a], x[a | (1 << P.st[i].b)], false);
-        }
-    }
-}
-#endif
-
-// sample-number part contributed by register slot m at the start of pass 0 (the thread's part is input_sample(t, 0))
-template <int LOGN>
-SDR_HD constexpr int input_slot_sample(int m)
-{
-    const int i = slot_part<LOGN, 0>(m);
-    int r = 0;
-    for (int b = 0; b < LOGN; b++)
-        r |= ((i >> b) & 1) << (LOGN - 1 - b);
-    return r;
-}
 
 // Sample number (natural order) held in slot m of thread t at the start of pass 0.
 template <int LOGN>
@@ -793,20 +585,9 @@ SDR_HD inline void load_input(const float *iq, int t, double *xr, double *xi)
 // Pass P: pass_log(P) radix-2 stages on the thread's registers.  `tw_at(c, lo)` returns twiddle table
 // entry c + lo, where c (the row) is a compile-time constant and lo = tw_pos(t, u) the only per-thread part (the
 // kernel turns that split into a buffer load with c in the scalar offset; the emulator indexes an array).
-// CHUNK > 0 (device, layout B): at most CHUNK twiddle rows are requested at a time and a scheduling fence behind
-// their butterflies keeps the compiler from pulling the next rows' loads forward - the register-staged kernel has 16
-// registers for twiddles (the next frame's samples occupy 32), not the 60 a whole pass's rows take when they are all
-// in flight at once.
-#if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
-#define SDR_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define SDR_SCHED_FENCE() \
-    do {                  \
-    } while (0)
-#endif
 // stage Q of pass P on register group u (compile-time loop over the stages: every bound below is a constant
 // expression, so the twiddle arrays and the data stay in registers)
-template <int LOGN, int P, int CHUNK, int Q, class TW>
+template <int LOGN, int P, int Q, class TW>
 SDR_HD inline void butterfly_stages(double *xr, double *xi, int u, int lo, TW &tw_at)
 {
     using PL = Plan<LOGN>;
@@ -816,74 +597,64 @@ SDR_HD inline void butterfly_stages(double *xr, double *xi, int u, int lo, TW &t
         constexpr int S = 1 << (P * PL::LOGR);
         constexpr int OFF = PL::tw_offset(P);
         constexpr int ROWS = 1 << Q;
-        constexpr int CH = (CHUNK > 0 && CHUNK < ROWS) ? CHUNK : ROWS;
+        double wr[ROWS], wi[ROWS];
 #if defined(__HIPCC__)
 #pragma unroll
 #endif
-        for (int c = 0; c < ROWS / CH; c++) {
-            double wr[CH], wi[CH];
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-            for (int j = 0; j < CH; j++) {
-                const int mm = c * CH + j;
-                // pass 0 has thread-independent twiddles; W[0] = 1 and W[N/4] = -i are the literal
-                // entries of go-dsp's size-4 table, multiplying by them is exact (up to the sign of a
-                // zero, which cannot reach |X|^2), so the multiply is skipped.
-                const bool one = (P == 0 && mm == 0);
-                const bool minus_i = (P == 0 && Q >= 1 && mm == (ROWS >> 1));
-                wr[j] = 1.0;
-                wi[j] = 0.0;
-                if (!one && !minus_i) {
+        for (int mm = 0; mm < ROWS; mm++) {
+            // pass 0 has thread-independent twiddles; W[0] = 1 and W[N/4] = -i are the literal
+            // entries of go-dsp's size-4 table, multiplying by them is exact (up to the sign of a
+            // zero, which cannot reach |X|^2), so the multiply is skipped.
+            const bool one = (P == 0 && mm == 0);
+            const bool minus_i = (P == 0 && Q >= 1 && mm == (ROWS >> 1));
+            wr[mm] = 1.0;
+            wi[mm] = 0.0;
+            if (!one && !minus_i) {
 #if defined(SDR_ABLATE) && (SDR_ABLATE == 3)
-                    wr[j] = 0.5 + 1e-9 * lo;  // timing-only build: no twiddle loads
-                    wi[j] = 0.25;
+                wr[mm] = 0.5 + 1e-9 * lo;  // timing-only build: no twiddle loads
+                wi[mm] = 0.25;
 #else
-                    const cplx w = tw_at(OFF + (ROWS - 1 + mm) * S, lo);
-                    wr[j] = w.x;
-                    wi[j] = w.y;
+                const cplx w = tw_at(OFF + (ROWS - 1 + mm) * S, lo);
+                wr[mm] = w.x;
+                wi[mm] = w.y;
 #endif
-                }
             }
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-            for (int j = 0; j < CH; j++) {
-                const int mm = c * CH + j;
-                const bool one = (P == 0 && mm == 0);
-                const bool minus_i = (P == 0 && Q >= 1 && mm == (ROWS >> 1));
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-                for (int k = 0; k < (RP >> (Q + 1)); k++) {
-                    const int a = u * RP + mm + (k << (Q + 1));
-                    const int b = a + ROWS;
-                    double tr, ti;
-                    if (one) {
-                        tr = xr[b];
-                        ti = xi[b];
-                    } else if (minus_i) {
-                        tr = xi[b];
-                        ti = -xr[b];
-                    } else {
-                        tr = xr[b] * wr[j] - xi[b] * wi[j];  // Go complex128 multiply, amd64: no FMA
-                        ti = xr[b] * wi[j] + xi[b] * wr[j];
-                    }
-                    const double ar = xr[a], ai = xi[a];
-                    xr[a] = ar + tr;
-                    xi[a] = ai + ti;
-                    xr[b] = ar - tr;
-                    xi[b] = ai - ti;
-                }
-            }
-            if (CHUNK > 0)
-                SDR_SCHED_FENCE();
         }
-        butterfly_stages<LOGN, P, CHUNK, Q + 1>(xr, xi, u, lo, tw_at);
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int mm = 0; mm < ROWS; mm++) {
+            const bool one = (P == 0 && mm == 0);
+            const bool minus_i = (P == 0 && Q >= 1 && mm == (ROWS >> 1));
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int k = 0; k < (RP >> (Q + 1)); k++) {
+                const int a = u * RP + mm + (k << (Q + 1));
+                const int b = a + ROWS;
+                double tr, ti;
+                if (one) {
+                    tr = xr[b];
+                    ti = xi[b];
+                } else if (minus_i) {
+                    tr = xi[b];
+                    ti = -xr[b];
+                } else {
+                    tr = xr[b] * wr[mm] - xi[b] * wi[mm];  // Go complex128 multiply, amd64: no FMA
+                    ti = xr[b] * wi[mm] + xi[b] * wr[mm];
+                }
+                const double ar = xr[a], ai = xi[a];
+                xr[a] = ar + tr;
+                xi[a] = ai + ti;
+                xr[b] = ar - tr;
+                xi[b] = ai - ti;
+            }
+        }
+        butterfly_stages<LOGN, P, Q + 1>(xr, xi, u, lo, tw_at);
     }
 }
 
-template <int LOGN, int P, int CHUNK = 0, class TW>
+template <int LOGN, int P, class TW>
 SDR_HD inline void butterfly_pass(double *xr, double *xi, int t, TW tw_at)
 {
     using PL = Plan<LOGN>;
@@ -893,7 +664,7 @@ SDR_HD inline void butterfly_pass(double *xr, double *xi, int t, TW tw_at)
 #endif
     for (int u = 0; u < G; u++) {
         const int lo = (P == 0) ? 0 : tw_pos<LOGN, P>(t, u);  // position inside the row, see make_tw_perm
-        butterfly_stages<LOGN, P, CHUNK, 0>(xr, xi, u, lo, tw_at);
+        butterfly_stages<LOGN, P, 0>(xr, xi, u, lo, tw_at);
     }
 }
 

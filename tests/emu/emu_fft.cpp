@@ -35,11 +35,11 @@ struct Passes {
                                     [tw](int c, int lo) { return tw[c + lo]; });
         if (P < PL::NPASS - 1) {
             constexpr int E = (P < PL::NPASS - 1 ? P : 0);
-            if constexpr (make_reg_plan<LOGN>(E).n > 0) {
-                // register exchange (v_permlane16/32_swap and ds_bpermute on the GPU): modelled wave by wave
+            if constexpr (make_swap_plan<LOGN>(E).ok) {
+                // register exchange (v_permlane16/32_swap on the GPU): modelled wave by wave
                 for (int t0 = 0; t0 < PL::T; t0 += 64) {
-                    exchange_regs_wave<LOGN, E>(reinterpret_cast<double (*)[PL::R]>(&xr[(size_t)t0 * PL::R]));
-                    exchange_regs_wave<LOGN, E>(reinterpret_cast<double (*)[PL::R]>(&xi[(size_t)t0 * PL::R]));
+                    exchange_swap_wave<LOGN, E>(reinterpret_cast<double (*)[PL::R]>(&xr[(size_t)t0 * PL::R]));
+                    exchange_swap_wave<LOGN, E>(reinterpret_cast<double (*)[PL::R]>(&xi[(size_t)t0 * PL::R]));
                 }
             } else {
             // LDS starts each exchange poisoned, so a read of a word nobody wrote yet cannot pass
@@ -112,18 +112,11 @@ struct Audit {
     {
         int w, r, rc = 0;
         audit<LOGN, E>(&w, &r);
-        if (make_reg_plan<LOGN>(E).n > 0) {
-            printf("LOGN=%d exchange %d: in registers:", LOGN, E);
-            for (int i = 0; i < make_reg_plan<LOGN>(E).n; i++) {
-                const RegStep st = make_reg_plan<LOGN>(E).st[i];
-                if (st.rot)
-                    printf(" rotate lane bits (%d,%d)<->(4,5);", st.a, st.a + 1);
-                else
-                    printf(" swap slot bit %d<->lane bit 4, slot bit %d<->lane bit 5;", st.a, st.b);
-            }
-            printf(" plan %s\n", reg_plan_valid<LOGN>(E) ? "valid" : "INVALID");
-            if (!reg_plan_valid<LOGN>(E))
-                rc = 1;
+        if (make_swap_plan<LOGN>(E).ok) {
+            // (-1: the lane bit keeps its index bit.  That the swap turns pass E's layout into pass E+1's is what
+            // make_swap_plan decides, and what the bit-for-bit comparison then depends on)
+            printf("LOGN=%d exchange %d: in registers: swap slot bit %d<->lane bit 4, slot bit %d<->lane bit 5\n", LOGN, E,
+                   make_swap_plan<LOGN>(E).slot_bit_lane4, make_swap_plan<LOGN>(E).slot_bit_lane5);
         } else {
             printf("LOGN=%d exchange %d (%s): worst write %d-way, worst read %d-way\n", LOGN, E,
                    Plan<LOGN>::cross_wave(E) ? "cross-wave" : "wave-local", w, r);
@@ -141,19 +134,6 @@ template <int LOGN>
 static int audit_loads()
 {
     using PL = Plan<LOGN>;
-    if (PL::LB) {
-        // layout B loads the frame straight from memory: the 64 lanes of a wave must read 64 consecutive samples
-        // (512 contiguous bytes per wave instruction) for every register slot
-        for (int m = 0; m < PL::R; m++)
-            for (int t0 = 0; t0 < PL::T; t0 += 64)
-                for (int t = t0; t < t0 + 64; t++)
-                    if (input_sample<LOGN>(t, m) != input_sample<LOGN>(t0, m) + (t - t0)) {
-                        printf("LOGN=%d (layout B): wave %d slot %d does not load 64 consecutive samples\n", LOGN, t0 / 64, m);
-                        return 1;
-                    }
-        printf("LOGN=%d (layout B): every wave loads 512 contiguous bytes per slot\n", LOGN);
-        return 0;
-    }
     for (int m = 0; m < PL::R; m++)
         for (int t0 = 0; t0 < PL::T; t0 += 4)
             for (int t = t0; t < t0 + 4; t++)
@@ -341,8 +321,7 @@ static int check(orc_iq_fft_t orc_fft, orc_factors_t orc_fac, unsigned seed)
     int rc = bad != 0;
     rc |= Audit<LOGN, 0>::run();
     rc |= audit_loads<LOGN>();
-    if (!PL::LB)
-        rc |= audit_staging<LOGN>();
+    rc |= audit_staging<LOGN>();
     // twiddle rows: the positions the threads of a pass read must be a permutation of the row
     rc |= audit_tw_rows<LOGN, 1>();
     return rc;
@@ -361,7 +340,7 @@ int main(int argc, char **argv)
     }
     auto orc_fft = (orc_iq_fft_t)dlsym(h, "orc_iq_fft");
     auto orc_fac = (orc_factors_t)dlsym(h, "orc_radix2_factors");
-    if (argc > 2 && !strcmp(argv[2], "nonfinite"))  // (the table only: one size with an LDS exchange only, one of layout B)
+    if (argc > 2 && !strcmp(argv[2], "nonfinite"))  // (the table only: one size whose only exchange goes through LDS, one with all three kinds)
         return nonfinite<9>(orc_fft) | nonfinite<14>(orc_fft);
     int rc = 0;
     rc |= check<9>(orc_fft, orc_fac, 1);

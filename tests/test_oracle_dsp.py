@@ -357,23 +357,27 @@ def test_cumulation_bound_is_an_upper_bound(tmp_path):
     assert out.returncode == 0 and " 0 violations" in out.stdout, out.stdout + out.stderr
 
 
-@pytest.mark.parametrize("layout_b_from", [15, 14])
-def test_fft_phase_functions_match_oracle_bit_for_bit(tmp_path, layout_b_from):
+def test_fft_phase_functions_match_oracle_bit_for_bit(tmp_path):
     """The register/LDS index math and per-pass twiddle layout of the FFT kernel (fft_f64.h), emulated
     thread by thread on the CPU, against the oracle's stage-by-stage radix-2 FFT for every block size: LDS exchanges
-    (padded additive address maps, bank-conflict audit), register exchanges (permlane swaps, lane rotations), twiddle
-    rows in thread order, input staging.  Both layouts: A (shipped, all sizes) and B (experimental, N = 16384:
-    cross-wave exchange first, registers only behind it)."""
+    (padded additive address maps, bank-conflict audit), register exchanges (permlane swaps), twiddle rows in thread
+    order, input staging.  The layout has exactly three exchanges that stay in registers."""
     import os
+    import re
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = str(tmp_path / "emu_fft")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", f"-DSDR_FFT_LAYOUT_B_FROM={layout_b_from}", "-o", exe,
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-o", exe,
                            os.path.join(root, "tests", "emu", "emu_fft.cpp"), "-ldl"])
     out = subprocess.run([exe, orc.build()], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert out.stdout.count(": 0 mismatches") == 6
-    assert ("layout B" in out.stdout) == (layout_b_from <= 14)
+    # (LOGN, exchange, slot bit that trades places with lane bit 4, with lane bit 5; -1: the lane bit keeps its index bit)
+    swaps = re.findall(r"^LOGN=(\d+) exchange (\d+): in registers: swap slot bit (-?\d+)<->lane bit 4, slot bit (-?\d+)<->lane bit 5$",
+                       out.stdout, re.M)
+    assert [tuple(map(int, m)) for m in swaps] == [(10, 1, 0, 1), (13, 2, -1, 0), (14, 2, 0, 1)], out.stdout
+    assert out.stdout.count("in registers") == 3, out.stdout
+    assert "layout B" not in out.stdout and "rotate" not in out.stdout, out.stdout
 
 
 def test_noise_floor_certification_against_the_literal_algorithm(tmp_path):

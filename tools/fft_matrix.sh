@@ -20,7 +20,7 @@ names = {"fb_prod": "production build", "fb_clock": "production + per-workgroup 
          "fb_abl5": "no butterflies at all", "fb_abl6": "(almost) no psd stores", "fb_abl7": "no input, no stores",
          "fb_abl8": "input L2-resident (16 frames cycled)", "fb_abl10": "cross-wave exchange without its LDS traffic",
          "fb_abl11": "cross-wave exchange without its barriers", "fb_abl12": "cross-wave exchange without either",
-         "fb_abl13": "no wave-local LDS exchange", "fb_abl14": "no register exchanges (layout B; layout A: unchanged kernel, slow outlier = different code)",
+         "fb_abl13": "no wave-local LDS exchange", "fb_abl14": "no register exchange (the last one at N = 16384: v_permlane swaps)",
          "fb_abl15": "no input DMA at all (what a perfectly hidden input would leave)", "fb_abl16": "no input DMA, no stores"}
 cur, rows = None, []
 for line in open(sys.argv[1]):
