@@ -1,5 +1,5 @@
-"""One bank's stream against the CPU oracle, bit for bit: the `Case` driver that test_listener_band_geometry.py and
-test_gpu_fuzz_paths.py share (a plain helper module, not a test file).
+"""One bank's stream against the CPU oracle, bit for bit: the `Case` driver every GPU parity test shares (a plain helper
+module, not a test file; what it is built from is in tests/parity_tools.py).
 
 A Case holds n_bands bands of keyed carriers and a list of steps; it runs one oracle receiver per band, attached and
 detached at the bank's frames and stitched into one stream per band (a listener's keying column is zero before it is
@@ -16,6 +16,11 @@ The input reaches the bank by one of the paths of include/sdrainer_hip.h:
   "graph"        hipGraph replays of float32 batches (sdr_graph_capture / sdr_graph_launch)
   "graph_sc16"   the same for sc16 (sdr_graph_capture_sc16 / sdr_graph_launch_sc16)
 The oracle always reads the float32 values the bank was given: for sc16 and KiwiSDR input float32(x) / 32767.
+
+With a hop below the block size frame f of a band is stream[f * hop : f * hop + N]: the oracle is fed the materialised
+frames, the device paths go through sdr_process_device_stream(_sc16) with the pointer advanced by frames * hop, the staged
+paths push the samples each batch adds, and what means time follows the hop (parity_tools.decode).  With a window per
+batch the oracle is fed the frames times the window in float32 (parity_tools.windowed).
 """
 from concurrent.futures import ThreadPoolExecutor
 
@@ -23,27 +28,13 @@ import numpy as np
 
 from oracle import oracle as orc
 from sdrainer_amd import synth
-from test_gpu_parity_bench_sizes import _check_batch_polled, _check_device_batch
+from parity_tools import (RATES, bits_equal, check_batch_polled, check_device_batch, decode, frames_of, listener_bins, make_stream,
+                          nan_equal_bits, sc16_to_float32, windowed)
 
 RATE = 2_000_000
 PATHS = ("device", "device_sc16", "staged", "staged_sc16", "kiwi", "graph", "graph_sc16")
 SC16_PATHS = ("device_sc16", "staged_sc16", "kiwi", "graph_sc16")
 KIWI_HEADER = bytes([0x01] + [7] * 16)  # the 17 bytes in front of an SND message's samples (flags, sequence, smeter)
-
-
-def nan_equal_bits(a, b):
-    """Bit for bit, except that two NaNs are equal whatever their sign and payload (which are not part of the contract)."""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    both_nan = np.isnan(a) & np.isnan(b)
-    u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
-    return np.array_equal(np.where(both_nan, 0, a.view(u)), np.where(both_nan, 0, b.view(u)))
-
-
-def sc16_to_float32(q):
-    """The float32 values an sc16 sample stands for (include/sdrainer_hip.h: float32(x) / 32767, one rounding)."""
-    return np.asarray(q, np.int16).astype(np.float32) / np.float32(32767.0)
 
 
 def _extra_bins(n, carriers, count, seed):
@@ -76,43 +67,75 @@ class Case:
     and the debounce are the bank's (sdr_config), one for all of its bands: sdr_set_signal_debounce reaches only the
     listeners attached at the time, as the reference's Receiver.SetSignalDebounce does, and every later listener starts
     from the bank's value.  `bands` replaces the synthetic carriers: one
-    (float32 [total, 2N] host array, int16 [total, 2N] or None, carrier bins) per band - the int16 array is what the sc16
-    and KiwiSDR paths send, and the float32 one must then be its value (sc16_to_float32).  Graph paths take batches of one
-    length, sdr_graph_batches() of them per replay, with attach / detach only between replays (each one is followed by a
-    release and a new capture); no deferred batches.  nan_ok: the oracle's stream holds NaN (a silent run: -Inf and then
-    NaN in the rolling means and thresholds), and NaN compares by class in the float fields."""
+    (float32 stream [samples, 2] or its dense frames [total, 2N], int16 of the same shape or None, carrier bins) per band -
+    the int16 array is what the sc16 and KiwiSDR paths send, and the float32 one must then be its value (sc16_to_float32).
+    Graph paths take batches of one length, sdr_graph_batches() of them per replay, with attach, detach and a new window
+    only between replays (each one is followed by a release and a new capture); no deferred batches.  nan_ok: the oracle's
+    stream holds NaN (a silent run: -Inf and then NaN in the rolling means and thresholds), and NaN compares by class in
+    the float fields.
+
+    hop: samples between frame starts (None or 0: dense frames); KiwiSDR and graph input take no hop below N, as the
+    library refuses it.  pad: samples behind every band's stream in device memory (the band stride of the stream calls).
+    windows: one table or None per batch; the bank is told only when it changes.  trace: the bank is created with
+    trace=True, and every checked batch is also held to the oracle's traced values, raw and debounced bits
+    (sdr_read_trace) and to the psd and dB rows of the frames spectrum_frames() names.  With a hop or with trace the
+    expected text, decoder state and rune frames are the hop-timed decoder's over the oracle's debounced bits, and every
+    step is a batch.
+
+    Not run by any test yet, so not to be trusted before the first row that uses them: the staged paths with a hop below N
+    (the sample range of _enqueue) and run_graph with windows (a window set before the capture, release and a new capture
+    when the next replay's window differs)."""
 
     def __init__(self, n, n_bands, carriers, listeners, steps, seed, rate=RATE, free_last=True, max_listeners=None, total_frames=None,
                  *, edge=None, debounce=1, threshold=15.0, centers=None, path="device", bands=None, init_bins=None, max_peaks=1024,
-                 nan_ok=False):
+                 nan_ok=False, hop=None, pad=0, windows=None, trace=False):
         assert path in PATHS, path
         self.n, self.n_bands, self.rate, self.path, self.nan_ok = n, n_bands, rate, path, nan_ok
+        self.hop, self.step, self.pad, self.trace = hop or 0, hop or n, pad, trace
+        assert self.step == n or path in ("device", "device_sc16", "staged", "staged_sc16"), f"{path} input takes no hop below N"
+        assert not pad or (self.hop and path.startswith("device")), "a padded band stride is the device stream calls'"
+        self.timed = bool(self.hop or trace)
         self.edge = synth.default_edge_width(n) if edge is None else edge
         self.debounce, self.threshold = debounce, _per_band(threshold, n_bands)
         self.total = total_frames or sum(s[1] for s in steps if s[0] in ("batch", "defer"))
         self.centers = [14000000 + 100000 * b for b in range(n_bands)] if centers is None else _per_band(centers, n_bands)
         self.max_peaks = max_peaks
-        self.dev_iq, self.host_iq, self.q, self.carriers, self.init_bins = [], [], [], [], []
+        samples = (self.total - 1) * self.step + n
+        self.stream, self.q, self.carriers, self.init_bins, made = [], [], [], [], []
         for b in range(n_bands):
             if bands is None:
                 iq, bins, _ = synth.make_band_torch(self.total, rate, n, carriers, seed=seed + 17 * b, device="cuda", free_last_window=free_last)
-                self.dev_iq.append(iq)
+                made.append(iq.view(-1, 2))
+                self.stream.append(iq.cpu().numpy().reshape(-1, 2))
                 self.q.append(None)
             else:
                 f32, q, bins = bands[b]
-                assert f32.shape == (self.total, 2 * n) and f32.dtype == np.float32
+                assert f32.size == 2 * samples and f32.dtype == np.float32, f"band {b}: not {self.total} frames of float32"
                 if path in SC16_PATHS:
-                    assert q is not None and np.array_equal(sc16_to_float32(q).view(np.uint32), f32.view(np.uint32))
-                self.host_iq.append(f32)
-                self.q.append(q)
+                    assert q is not None and bits_equal(sc16_to_float32(q), f32), f"band {b}: the float32 input is not its int16's value"
+                self.stream.append(f32.reshape(-1, 2))
+                self.q.append(None if q is None else q.reshape(-1, 2))
             self.carriers.append([int(x) for x in bins])
             if init_bins is not None:
                 self.init_bins.append([int(x) for x in init_bins[b]])
             else:
                 self.init_bins.append((self.carriers[b] + _extra_bins(n, bins, max(0, listeners - len(bins)), seed + 17 * b))[:listeners])
+        if made:
+            import torch
+
+            self._dev = torch.stack(made)  # (twice the input on the device until `made` goes)
+            del made
         self.steps = steps = steps(self.carriers) if callable(steps) else steps
-        assert self.total == sum(s[1] for s in steps if s[0] in ("batch", "defer"))
-        self.max_frames = max(s[1] for s in steps if s[0] in ("batch", "defer"))
+        self.spans, pos = [], 0  # the batches' frames [a, e)
+        for s in steps:
+            if s[0] in ("batch", "defer"):
+                self.spans.append((pos, pos + s[1]))
+                pos += s[1]
+        assert self.total == pos, f"the steps hold {pos} frames, not {self.total}"
+        assert not self.timed or len(self.spans) == len(steps), "with a hop or with trace every step is a batch"
+        self.windows = [None] * len(self.spans) if windows is None else list(windows)
+        assert len(self.windows) == len(self.spans), "one window (or None) per batch"
+        self.max_frames = max(e - a for a, e in self.spans)
         late = sum(1 for s in steps if s[0] == "attach") + sum(len(s[2]) for s in steps if s[0] == "defer")
         self.max_listeners = max_listeners or max(1, max(len(b) for b in self.init_bins) + late)
         # every listener of every band: (attached at frame, detached at frame or None)
@@ -127,17 +150,46 @@ class Case:
                 self.life[s[1]][s[2]] = (self.life[s[1]][s[2]][0], pos)
             else:
                 for band, bn, at in s[2] if s[0] == "defer" else []:
-                    assert pos <= at < pos + s[1]
+                    assert pos <= at < pos + s[1], f"band {band}: attach_at frame {at} outside its batch"
                     self.bins[band].append(bn)
                     self.life[band].append((at, None))
                 pos += s[1]
 
+    @classmethod
+    def of_streams(cls, n, hop, calls, n_bands, tones, listeners, sc16, seed, windows=None, pad=0):
+        """Device-resident streams of keyed carriers (parity_tools.make_stream) in calls of `calls` frames, the listeners on
+        the carriers and beside them (listener_bins), on a bank with trace."""
+        made = [make_stream(n, hop or n, sum(calls), RATES[n], tones, seed + 17 * b, sc16) for b in range(n_bands)]
+        return cls(n, n_bands, None, 0, [("batch", x) for x in calls], seed, rate=RATES[n], max_listeners=listeners,
+                   path="device_sc16" if sc16 else "device", bands=made, init_bins=[listener_bins(n, m[2], listeners) for m in made],
+                   hop=hop, pad=pad, windows=windows, trace=True)
+
+    def frames(self, b, a, e):
+        """Frames [a, e) of band b as the oracle is fed them: float32 [frames, 2N], each batch's times that batch's window."""
+        n = self.n
+        f = frames_of(self.stream[b], n, self.hop, a, e) if self.hop else self.stream[b][a * n:e * n].reshape(-1, 2 * n)
+        out = None
+        for (lo, hi), w in zip(self.spans, self.windows):
+            lo, hi = max(a, lo), min(e, hi)
+            if w is not None and lo < hi:
+                out = np.array(f) if out is None else out
+                out[lo - a:hi - a] = windowed(f[lo - a:hi - a], w, n)
+        return f if out is None else out
+
     def oracle_input(self, b):
-        """The float32 values band b is given, host side."""
-        return self.host_iq[b] if self.host_iq else self.dev_iq[b].cpu().numpy()
+        """The float32 frames band b is given, host side."""
+        return self.frames(b, 0, self.total)
+
+    def spectrum_frames(self, frames):
+        """The frames of a batch of `frames` frames whose psd and dB rows are read back (trace): first, last, around a
+        cumulation boundary, a few inside."""
+        return sorted({0, min(1, frames - 1), frames - 1, frames // 2, min(99, frames - 1), min(100, frames - 1), frames // 3})
 
     def run_oracle(self):
         """One oracle receiver per band, attached and detached at the bank's frames, bands on threads of their own."""
+        if hasattr(self, "outs"):
+            return
+
         def band_events(b):
             ev, pos = [], 0  # (frame, "attach", bin) / (frame, "detach", lid), in the bank's call order
             for s in self.steps:
@@ -152,18 +204,19 @@ class Case:
             return ev
 
         def run(b):
-            host = self.oracle_input(b)
             r = orc.Receiver(self.rate, self.n, self.edge, self.threshold[b], self.debounce, center_frequency=self.centers[b])
             for bn in self.init_bins[b]:
                 r.attach(int(bn))
             L = len(self.bins[b])
-            st = {"frames": [], "deb": np.zeros((self.total, L), np.uint8), "peaks": [], "peak_frames": [], "cumulation": []}
+            st = {"frames": [], "deb": np.zeros((self.total, L), np.uint8), "raw": np.zeros((self.total, L), np.uint8),
+                  "values": np.zeros((self.total, L), np.float32), "peaks": [], "peak_frames": [], "cumulation": []}
             pos = 0
             for at, kind, arg in band_events(b) + [(self.total, None, None)]:
                 if at > pos:
-                    out = r.process(host[pos:at], max_peaks=max(4096, self.max_peaks))
+                    out = r.process(self.frames(b, pos, at), max_peaks=max(4096, self.max_peaks))
                     st["frames"].append(out["frames"])
-                    st["deb"][pos:at, :out["deb"].shape[1]] = out["deb"]
+                    for f in ("deb", "raw", "values"):
+                        st[f][pos:at, :out[f].shape[1]] = out[f]
                     st["peaks"] += out["peaks"]
                     st["peak_frames"] += [pos + int(f) for f in out["peak_frames"]]
                     st["cumulation"] += list(out["cumulation"])
@@ -180,6 +233,15 @@ class Case:
             res = list(ex.map(run, range(self.n_bands)))
         self.refs = [r for r, _ in res]
         self.outs = [o for _, o in res]
+        if self.timed:  # (text, 12-value state, the tick that wrote each rune) of every listener
+            self.decs = [[decode(out["deb"][:, lid], self.rate, self.step) for lid in range(out["deb"].shape[1])] for out in self.outs]
+
+    def oracle_counts(self):
+        """(edges, peaks) the oracle sees over the run: a row with none of either proves nothing."""
+        self.run_oracle()
+        edges = sum(int(np.count_nonzero(np.diff(np.concatenate([[0], out["deb"][:, lid].astype(np.int8)])))) for out in self.outs
+                    for lid in range(out["deb"].shape[1]))
+        return edges, sum(len(p) for out in self.outs for p in out["peaks"])
 
     def live(self, b, a, e):
         """Listeners of band b that listen during [a, e) and are not detached at its end."""
@@ -190,18 +252,28 @@ class Case:
         import torch
 
         bank = capi.Bank(self.rate, self.n, n_bands=self.n_bands, edge_width=self.edge, max_batch_frames=self.max_frames,
-                         max_listeners=self.max_listeners, max_peaks=self.max_peaks, signal_debounce=self.debounce)
+                         max_listeners=self.max_listeners, max_peaks=self.max_peaks, signal_debounce=self.debounce, trace=self.trace,
+                         hop=self.hop)
+        assert bank.hop == self.step, f"the bank's hop is {bank.hop}, not {self.step}"
         bank.set_stream((stream or torch.cuda.current_stream()).cuda_stream)
         for b in range(self.n_bands):
             bank.set_center_frequency(b, self.centers[b])
             if self.threshold[b] != 15.0:
                 bank.set_peak_threshold(b, self.threshold[b])
             for i, bn in enumerate(self.init_bins[b]):
-                assert bank.attach(b, int(bn)) == i
+                assert bank.attach(b, int(bn)) == i, f"band {b}: listener {i} got another id"
         bank.enable_results(True)
         self.text = [["" for _ in bins] for bins in self.bins]
+        self.rune_at = [[[] for _ in bins] for bins in self.bins]
         self.edges = self.peaks = 0
+        self.window = None  # (a bank that never had a window is never told about one)
         return bank
+
+    def set_window(self, bank, k):
+        """Batch k's window, if it is not the one the bank has."""
+        if self.windows[k] is not self.window:
+            self.window = self.windows[k]
+            bank.set_window(self.window)
 
     def gone(self, a):
         """(band, listener) pairs detached before frame a."""
@@ -209,61 +281,94 @@ class Case:
 
     def check_polled(self, res, a, e):
         """One delivered batch against the stitched oracle stream, for the listeners live in it; detached ones deliver nothing."""
-        ne, npk = _check_batch_polled(res, self.outs, a, e, None, self.text, self.n_bands,
-                                      live=[self.live(b, a, e) for b in range(self.n_bands)], gone=self.gone(a))
+        ne, npk = check_batch_polled(res, self.outs, a, e, None, self.text, self.n_bands,
+                                     live=[self.live(b, a, e) for b in range(self.n_bands)], gone=self.gone(a), rune_at=self.rune_at)
         self.edges += ne
         self.peaks += npk
 
     def check_device(self, bank, a, e, k, cumulations=True):
-        """What the last batch left on the device: frame records, keying bits, cumulation rows."""
-        _check_device_batch(bank, self.outs, a, e, self.n_bands, [self.live(b, a, e) for b in range(self.n_bands)], k, cumulations,
-                            same=nan_equal_bits if self.nan_ok else None)
+        """What the last batch left on the device: frame records, keying bits, cumulation rows; with trace, the tap."""
+        check_device_batch(bank, self.outs, a, e, self.n_bands, [self.live(b, a, e) for b in range(self.n_bands)], k, cumulations,
+                           same=nan_equal_bits if self.nan_ok else None)
+        if self.trace:
+            self.check_trace(bank, a, e, k)
+
+    def check_trace(self, bank, a, e, k):
+        """The tap of the last batch: the value handed to Listen, raw and debounced state of every listener, frame by frame;
+        psd and dB spectrum of the sampled frames."""
+        same = nan_equal_bits if self.nan_ok else bits_equal
+        for b in range(self.n_bands):
+            out = self.outs[b]
+            for lid in self.live(b, a, e):
+                v, raw, deb = bank.read_trace(b, lid)
+                assert same(v, out["values"][a:e, lid].copy()), f"band {b} listener {lid} batch {k} tap values"
+                assert np.array_equal(raw, out["raw"][a:e, lid]), f"band {b} listener {lid} batch {k} raw bits"
+                assert np.array_equal(deb, out["deb"][a:e, lid]), f"band {b} listener {lid} batch {k} debounced bits"
+            for f in self.spectrum_frames(e - a):
+                sp, psd = bank.read_spectrum(b, f)
+                want_sp, want_psd = orc.iq_to_spectrum_and_psd(self.frames(b, a + f, a + f + 1))
+                assert same(psd, want_psd), f"band {b} batch {k} frame {a + f} psd"
+                assert same(sp, want_sp), f"band {b} batch {k} frame {a + f} spectrum"
 
     def check_end(self, bank, min_edges, activity=True):
         for b in range(self.n_bands):
             for lid in range(len(self.bins[b])):
-                assert self.text[b][lid] == self.refs[b].text(lid), f"band {b} listener {lid} text"
-                assert np.array_equal(bank.read_decoder_state(b, lid), self.refs[b].decoder_state(lid)), f"band {b} listener {lid} state"
-        assert bank.read_drop_counters() == (0, 0)
+                text, state = self.decs[b][lid][:2] if self.timed else (self.refs[b].text(lid), self.refs[b].decoder_state(lid))
+                assert self.text[b][lid] == text, f"band {b} listener {lid} text"
+                assert np.array_equal(bank.read_decoder_state(b, lid), state), f"band {b} listener {lid} state"
+                if self.timed:
+                    assert np.array_equal(np.array(self.rune_at[b][lid], np.int64), self.decs[b][lid][2]), f"band {b} listener {lid} rune frames"
+        assert bank.read_drop_counters() == (0, 0), "runes or edges dropped"
         if activity:
             n_carriers = sum(len(c) for c in self.carriers)
-            assert self.edges > min_edges * n_carriers and self.peaks > 0 and any(len(t) > 0 for row in self.text for t in row)
+            assert self.edges > min_edges * n_carriers and self.peaks > 0 and any(len(t) > 0 for row in self.text for t in row), \
+                f"{self.edges} edges, {self.peaks} peaks: the run shows too little"
 
     # -- input -------------------------------------------------------------------------------------------------------------
     def _device_input(self):
-        """The whole stream of every band in device memory, [band][frame][2N] per band (float32 or int16 by the path)."""
+        """The whole stream of every band in device memory, [band][sample][2] (float32 or int16 by the path), `pad` samples
+        of zeros behind each."""
         import torch
 
-        if self.dev_iq:
-            return self.dev_iq
         if not hasattr(self, "_dev"):
-            src = self.q if self.path in SC16_PATHS else self.host_iq
-            self._dev = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in src]
+            src = self.q if self.path in SC16_PATHS else self.stream
+            host = np.zeros((self.n_bands, src[0].shape[0] + self.pad, 2), src[0].dtype)
+            for b in range(self.n_bands):
+                host[b, :src[b].shape[0]] = src[b]
+            self._dev = torch.from_numpy(host).cuda()
         return self._dev
 
-    def _device_batch(self, a, e):
-        import torch
-
-        return torch.stack([iq[a:e] for iq in self._device_input()]).contiguous()
+    def device_batch(self, a, e):
+        """Dense frames [a, e) of every band in device memory, [band][frame][2N]."""
+        return self._device_input()[:, a * self.n:e * self.n].contiguous()
 
     def _enqueue(self, bank, a, e):
         """One batch [a, e) through the case's input path (not the graph paths); returns what must outlive the call."""
-        if self.path in ("device", "device_sc16"):
-            batch = self._device_batch(a, e)
-            (bank.process_device_sc16 if self.path == "device_sc16" else bank.process_device)(batch.data_ptr(), e - a)
+        sc16 = self.path in SC16_PATHS
+        if self.path.startswith("device") and self.hop:
+            dev = self._device_input()
+            ptr = dev.data_ptr() + a * self.hop * 2 * dev.element_size()
+            (bank.process_device_stream_sc16 if sc16 else bank.process_device_stream)(ptr, e - a, dev.shape[1])
+            return dev
+        if self.path.startswith("device"):
+            batch = self.device_batch(a, e)
+            (bank.process_device_sc16 if sc16 else bank.process_device)(batch.data_ptr(), e - a)
             return batch
+        lo, hi = (a - 1) * self.step + self.n if a else 0, (e - 1) * self.step + self.n  # the samples the batch adds
         for b in range(self.n_bands):
             if self.path == "staged":
-                assert bank.push_iq(b, self.rate, self.host_iq[b][a:e].reshape(-1)) == 0
+                assert bank.push_iq(b, self.rate, self.stream[b][lo:hi].reshape(-1)) == 0, f"band {b}: push refused"
             elif self.path == "staged_sc16":
-                assert bank.push_iq_sc16(b, self.rate, self.q[b][a:e].reshape(-1)) == 0
+                assert bank.push_iq_sc16(b, self.rate, self.q[b][lo:hi].reshape(-1)) == 0, f"band {b}: push refused"
             else:  # KiwiSDR: the batch's frames in messages of up to 1, 2, 5, 12 ... frames, as the websocket delivers them
-                f, sizes = a, (1, 2, 5, 12, 40)
+                f, sizes, n = a, (1, 2, 5, 12, 40), self.n
                 while f < e:
                     k = min(sizes[(f - a) % len(sizes)], e - f)
-                    assert bank.push_kiwi_snd(b, self.rate, KIWI_HEADER + self.q[b][f:f + k].astype(">i2").tobytes()) == 0
+                    assert bank.push_kiwi_snd(b, self.rate, KIWI_HEADER + self.q[b][f * n:(f + k) * n].astype(">i2").tobytes()) == 0, \
+                        f"band {b}: message refused"
                     f += k
-        assert bank.process_staged() == e - a
+        got = bank.process_staged()
+        assert got == e - a, f"{got} staged frames, not {e - a}"
         return None
 
     # -- runs --------------------------------------------------------------------------------------------------------------
@@ -281,27 +386,30 @@ class Case:
         def deliver(last):
             a, e, i, _ = pending.pop(0)
             res = bank.poll(wait=True)
-            assert res["batch_index"] == i
+            assert res["batch_index"] == i, f"batch {i} delivered as {res['batch_index']}"
             self.check_polled(res, a, e)
             if last:
                 self.check_device(bank, a, e, i)
         slots = [len(bins) for bins in self.init_bins]  # (no attach follows a detach on a band: ids are the oracle's)
         for s in self.steps:
             if s[0] == "attach":
-                assert bank.attach(s[1], int(s[2])) == slots[s[1]]
+                got = bank.attach(s[1], int(s[2]))
+                assert got == slots[s[1]], f"band {s[1]}: attach gave listener {got}"
                 slots[s[1]] += 1
                 continue
             if s[0] == "detach":
                 bank.detach(s[1], s[2])
                 continue
             a, e = pos, pos + s[1]
+            self.set_window(bank, k)
             if s[0] == "defer":
                 bank.defer_listen(True)
                 batch = self._enqueue(bank, a, e)
                 pk = bank.poll_peaks(wait=True)
-                assert pk["first_frame"] == a
+                assert pk["first_frame"] == a, f"batch {k}: peaks of frame {pk['first_frame']}"
                 for band, bn, at in s[2]:
-                    assert bank.attach_at(band, int(bn), at) == slots[band]
+                    got = bank.attach_at(band, int(bn), at)
+                    assert got == slots[band], f"band {band}: attach_at gave listener {got}"
                     slots[band] += 1
                 bank.process_listen()
                 bank.defer_listen(False)
@@ -318,7 +426,8 @@ class Case:
 
     def run_graph(self, capi, min_edges=20, activity=True):
         """The graph paths: replays of sdr_graph_batches() batches of one length, a release and a new capture after every
-        listener change.  Each delivered batch is checked; what stays on the device after the last batch of every replay."""
+        listener change and before a replay with another window.  Each delivered batch is checked; what stays on the
+        device after the last batch of every replay."""
         import torch
 
         assert all(s[0] in ("batch", "attach", "detach") for s in self.steps), "graph mode takes no deferred batch"
@@ -337,19 +446,24 @@ class Case:
                 pos += per
                 if len(run) < K:
                     continue
+                assert all(w is self.windows[k] for w in self.windows[k:k + K]), "graph mode: one window per replay"
+                if captured and self.windows[k] is not self.window:
+                    bank.graph_release()
+                    captured = False
+                self.set_window(bank, k)
                 if not captured:
                     (bank.graph_capture_sc16 if sc16 else bank.graph_capture)(per)
                     captured = True
-                batches = [self._device_batch(a, e) for a, e in run]
+                batches = [self.device_batch(a, e) for a, e in run]
                 torch.cuda.synchronize()  # (the input is written on torch's stream, the bank reads it on its own)
                 (bank.graph_launch_sc16 if sc16 else bank.graph_launch)([x.data_ptr() for x in batches])
                 for a, e in run:
                     res = bank.poll(wait=True)
-                    assert res["batch_index"] == k
+                    assert res["batch_index"] == k, f"batch {k} delivered as {res['batch_index']}"
                     self.check_polled(res, a, e)
                     k += 1
                 bank.sync()
-                assert bank.total_frames == pos
+                assert bank.total_frames == pos, f"{bank.total_frames} frames after {pos}"
                 self.check_device(bank, run[-1][0], run[-1][1], k - 1, cumulations=False)
                 run = []
                 continue
@@ -360,7 +474,8 @@ class Case:
                 bank.graph_release()
                 captured = False
             if s[0] == "attach":
-                assert bank.attach(s[1], int(s[2])) == slots[s[1]]
+                got = bank.attach(s[1], int(s[2]))
+                assert got == slots[s[1]], f"band {s[1]}: attach gave listener {got}"
                 slots[s[1]] += 1
             else:
                 bank.detach(s[1], s[2])

@@ -12,15 +12,15 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from sdrainer_amd import capi  # noqa: E402
-from test_fft_r32_stealing import N, _bank, _batch, _pool  # noqa: E402
+from parity_tools import POOL_N as N, pool_bank, pool_batch, pool_frames  # noqa: E402
 
 capi.load()
 frames = 2048
-iq, want = _pool(7700)
-bank = _bank(capi, 1, frames)
+iq, want = pool_frames(7700)
+bank = pool_bank(capi, 1, frames)
 stream = torch.cuda.Stream()
 bank.set_stream(stream.cuda_stream)
-dev = _batch(torch.from_numpy(iq).cuda(), frames)
+dev = pool_batch(torch.from_numpy(iq).cuda(), frames)
 torch.cuda.synchronize()
 for _ in range(2):
     bank.process_device(dev.data_ptr(), frames)

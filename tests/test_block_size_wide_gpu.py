@@ -13,8 +13,9 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from parity_case import Case
+from parity_tools import REC_FIELDS, bits_equal, capi, check_batch_polled, run_oracle  # noqa: F401 (capi: the fixture)
 from sdrainer_amd import synth
-import test_gpu_parity_bench_sizes as base
 
 pytestmark = pytest.mark.gpu
 
@@ -24,21 +25,14 @@ RATE = {32768: 2_000_000, 65536: 4_000_000}
 FRAMES = {32768: 1024, 65536: 512}  # per batch; two of them, then a shorter batch
 
 
-@pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd import capi as c
-    c.load()
-    return c
-
-
 @pytest.mark.parametrize("n", [32768, 65536])
 def test_wide_block_one_band(capi, n):
-    base._eager_case(capi, RATE[n], n, 256, 1, FRAMES[n], 2, True, seed=7000 + n % 1000, tail_frames=333)
+    Case(n, 1, 256, 256, [("batch", FRAMES[n])] * 2 + [("batch", 333)], seed=7000 + n % 1000, rate=RATE[n]).run(capi).close()
 
 
 @pytest.mark.parametrize("n", [32768, 65536])
 def test_wide_block_three_bands(capi, n):
-    base._eager_case(capi, RATE[n], n, 256, 3, FRAMES[n] // 2, 2, True, seed=7100 + n % 1000, tail_frames=211)
+    Case(n, 3, 256, 256, [("batch", FRAMES[n] // 2)] * 2 + [("batch", 211)], seed=7100 + n % 1000, rate=RATE[n]).run(capi).close()
 
 
 @pytest.mark.parametrize("env", [{"SDR_CUM_BOUND": "0"}, {"SDR_CUM_BOUND": "1"}, {"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "0"},
@@ -146,7 +140,7 @@ def test_wide_block_graph_mode(capi, n):
     K = bank.graph_batches
     total = 2 * K * per
     iq, bins, _ = synth.make_band_torch(total, rate, n, tones, seed=8200 + n % 1000, device="cuda")
-    refs, outs = base._run_oracle(rate, n, edge, [bins], [iq.cpu().numpy()], [14000000])
+    refs, outs, _ = run_oracle(rate, n, edge, [bins], [iq.cpu().numpy()], [14000000])
     stream = torch.cuda.Stream()
     bank.set_stream(stream.cuda_stream)
     bank.set_center_frequency(0, 14000000)
@@ -164,12 +158,12 @@ def test_wide_block_graph_mode(capi, n):
             res = bank.poll(wait=True)
             a = (rep * K + k) * per
             assert res["batch_index"] == delivered
-            base._check_batch_polled(res, outs, a, a + per, tones, text, n_bands)
+            check_batch_polled(res, outs, a, a + per, tones, text, n_bands)
             delivered += 1
     bank.sync()
     recs = bank.read_frame_records(0)
-    for f in base.REC_FIELDS:
-        assert base._bits_equal(recs[f], outs[0]["frames"][f][total - per:].copy()), f"field {f}"
+    for f in REC_FIELDS:
+        assert bits_equal(recs[f], outs[0]["frames"][f][total - per:].copy()), f"field {f}"
     for lid in range(tones):
         assert text[0][lid] == refs[0].text(lid), f"listener {lid}"
         assert np.array_equal(bank.read_decoder_state(0, lid), refs[0].decoder_state(lid))

@@ -8,71 +8,25 @@ The input is cheap to check: frame f of a batch is frame f % P of a pool of P ra
 batch, so that a row left from an earlier batch or taken from another frame cannot pass), and the oracle computes the
 pool only.  Every row is read back with sdr_read_spectrum.
 """
-import ctypes as C
-
-import numpy as np
 import pytest
 
-from oracle import oracle as orc
+from parity_tools import capi, check_pool_rows, pool_bank, pool_batch, pool_frames  # noqa: F401 (capi: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-N = 16384
-RATE = 2_000_000
-POOL = 61
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd import capi as c
-    c.load()
-    return c
-
-
-def _pool(seed):
-    """P frames of noise and a tone at a random bin (float32 [P, 2N]) and the oracle's psd of each (uint32 [P, N])."""
-    rng = np.random.default_rng(seed)
-    n = np.arange(N)
-    iq = np.empty((POOL, 2 * N), np.float32)
-    for p in range(POOL):
-        k = rng.integers(N)
-        iq[p, 0::2] = 0.2 * np.cos(2 * np.pi * k * n / N) + rng.normal(0, 1e-2, N)
-        iq[p, 1::2] = 0.2 * np.sin(2 * np.pi * k * n / N) + rng.normal(0, 1e-2, N)
-    psd = np.stack([orc.iq_to_spectrum_and_psd(iq[p])[1] for p in range(POOL)]).view(np.uint32)
-    return iq, psd
-
-
-def _batch(pool_dev, n_frames):
-    """[n_frames, 2N] on the GPU: frame f = pool frame f % P."""
-    import torch
-    idx = torch.arange(n_frames, device=pool_dev.device) % POOL
-    return pool_dev[idx].contiguous()
-
-
-def _check_rows(bank, band, n_frames, want):
-    psd = np.empty(N, np.float32)
-    for f in range(n_frames):
-        rc = bank._L.sdr_read_spectrum(bank._h, band, f, None, C.c_void_p(psd.ctypes.data))
-        assert rc == 0, bank._L.sdr_last_error().decode()
-        assert np.array_equal(psd.view(np.uint32), want[f % POOL]), f"band {band} frame {f}: psd row differs from the oracle"
-
-
-def _bank(capi, n_bands, max_frames):
-    return capi.Bank(RATE, N, n_bands=n_bands, max_batch_frames=max_frames, max_listeners=4, max_peaks=64)
 
 
 def test_batch_sizes_and_consecutive_batches(capi):
     """1024, 1031 (not a multiple of the grid), 3000 and 8192 frames, one after the other on one bank: each batch's
     launch finds the counter its predecessor left at zero."""
     import torch
-    bank = _bank(capi, 1, 8192)
+    bank = pool_bank(capi, 1, 8192)
     for i, frames in enumerate([1024, 1031, 3000, 8192, 1031]):
-        iq, want = _pool(7000 + i)
-        dev = _batch(torch.from_numpy(iq).cuda(), frames)
+        iq, want = pool_frames(7000 + i)
+        dev = pool_batch(torch.from_numpy(iq).cuda(), frames)
         torch.cuda.synchronize()
         bank.process_device(dev.data_ptr(), frames)
         bank.sync()
-        _check_rows(bank, 0, frames, want)
+        check_pool_rows(bank, 0, frames, want)
     bank.close()
 
 
@@ -80,35 +34,35 @@ def test_two_bands(capi):
     """Two bands in one launch: each band claims from a counter of its own."""
     import torch
     frames = 2048
-    bank = _bank(capi, 2, frames)
+    bank = pool_bank(capi, 2, frames)
     for rep in range(2):
-        pools = [_pool(7100 + 2 * rep + b) for b in range(2)]
-        dev = torch.stack([_batch(torch.from_numpy(p[0]).cuda(), frames) for p in pools]).contiguous()
+        pools = [pool_frames(7100 + 2 * rep + b) for b in range(2)]
+        dev = torch.stack([pool_batch(torch.from_numpy(p[0]).cuda(), frames) for p in pools]).contiguous()
         torch.cuda.synchronize()
         bank.process_device(dev.data_ptr(), frames)
         bank.sync()
         for b in range(2):
-            _check_rows(bank, b, frames, pools[b][1])
+            check_pool_rows(bank, b, frames, pools[b][1])
     bank.close()
 
 
 def test_two_banks_at_once(capi):
     """Two banks on device 0, their FFTs in flight together on streams of their own: counters per bank."""
     import torch
-    banks = [_bank(capi, 1, 4096) for _ in range(2)]
+    banks = [pool_bank(capi, 1, 4096) for _ in range(2)]
     streams = [torch.cuda.Stream() for _ in banks]
     for bank, s in zip(banks, streams):
         bank.set_stream(s.cuda_stream)
     for rep in range(2):
-        pools = [_pool(7200 + 2 * rep + k) for k in range(2)]
-        devs = [_batch(torch.from_numpy(p[0]).cuda(), 4096 - 5 * k) for k, p in enumerate(pools)]
+        pools = [pool_frames(7200 + 2 * rep + k) for k in range(2)]
+        devs = [pool_batch(torch.from_numpy(p[0]).cuda(), 4096 - 5 * k) for k, p in enumerate(pools)]
         torch.cuda.synchronize()
         for k, bank in enumerate(banks):
             bank.process_device(devs[k].data_ptr(), 4096 - 5 * k)
         for bank in banks:
             bank.sync()
         for k, bank in enumerate(banks):
-            _check_rows(bank, 0, 4096 - 5 * k, pools[k][1])
+            check_pool_rows(bank, 0, 4096 - 5 * k, pools[k][1])
     for bank in banks:
         bank.close()
 
@@ -117,17 +71,17 @@ def test_graph_replays(capi):
     """Three replays of the captured steady state (1024-frame batches): the counters' reset needs no host step."""
     import torch
     per = 1024
-    bank = _bank(capi, 1, per)
+    bank = pool_bank(capi, 1, per)
     stream = torch.cuda.Stream()
     bank.set_stream(stream.cuda_stream)
     K = bank.graph_batches
     bank.graph_capture(per)
     for rep in range(3):
-        pools = [_pool(7300 + rep * K + k) for k in range(K)]
-        devs = [_batch(torch.from_numpy(p[0]).cuda(), per) for p in pools]
+        pools = [pool_frames(7300 + rep * K + k) for k in range(K)]
+        devs = [pool_batch(torch.from_numpy(p[0]).cuda(), per) for p in pools]
         torch.cuda.synchronize()
         bank.graph_launch([d.data_ptr() for d in devs])
         bank.sync()
-        _check_rows(bank, 0, per, pools[-1][1])  # (the read calls see the replay's last batch)
+        check_pool_rows(bank, 0, per, pools[-1][1])  # (the read calls see the replay's last batch)
     bank.graph_release()
     bank.close()

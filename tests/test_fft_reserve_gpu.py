@@ -17,8 +17,8 @@ import re
 
 import pytest
 
-from test_fft_r32_stealing import _bank, _batch, _check_rows, _pool
-from test_gpu_parity_bench_sizes import _eager_case
+from parity_case import Case
+from parity_tools import capi, check_pool_rows, pool_bank, pool_batch, pool_frames  # noqa: F401 (capi: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -42,13 +42,6 @@ def rule_reserve(n_frames, n_bands=1):
 
 
 @pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd import capi as c
-    c.load()
-    return c
-
-
-@pytest.fixture(scope="module")
 def cus():
     import torch
     return torch.cuda.get_device_properties(0).multi_processor_count
@@ -57,7 +50,7 @@ def cus():
 @pytest.fixture(scope="module")
 def pools():
     """The pools every case shares: (iq, oracle psd) by index."""
-    return [_pool(7600 + i) for i in range(3)]
+    return [pool_frames(7600 + i) for i in range(3)]
 
 
 @pytest.mark.parametrize("which", ["one", "rule", "all_but_one", "beyond"])
@@ -66,14 +59,14 @@ def test_forced_reserve(capi, cus, pools, monkeypatch, which):
     reserve = {"one": 1, "rule": rule_reserve(8192), "all_but_one": cus - 1, "beyond": cus + 40}[which]
     assert reserve > 0
     monkeypatch.setenv("SDR_FFT_RESERVE", str(reserve))
-    bank = _bank(capi, 1, 1031)
+    bank = pool_bank(capi, 1, 1031)
     for i, frames in enumerate([1024, 1031]):
         iq, want = pools[i]
-        dev = _batch(torch.from_numpy(iq).cuda(), frames)
+        dev = pool_batch(torch.from_numpy(iq).cuda(), frames)
         torch.cuda.synchronize()
         bank.process_device(dev.data_ptr(), frames)
         bank.sync()
-        _check_rows(bank, 0, frames, want)
+        check_pool_rows(bank, 0, frames, want)
     bank.close()
 
 
@@ -84,13 +77,13 @@ def test_three_bands(capi, cus, pools, monkeypatch):
     assert (cus - reserve) % 3 != 0
     monkeypatch.setenv("SDR_FFT_RESERVE", str(reserve))
     frames = 350
-    bank = _bank(capi, 3, frames)
-    dev = torch.stack([_batch(torch.from_numpy(pools[b][0]).cuda(), frames) for b in range(3)]).contiguous()
+    bank = pool_bank(capi, 3, frames)
+    dev = torch.stack([pool_batch(torch.from_numpy(pools[b][0]).cuda(), frames) for b in range(3)]).contiguous()
     torch.cuda.synchronize()
     bank.process_device(dev.data_ptr(), frames)
     bank.sync()
     for b in range(3):
-        _check_rows(bank, b, frames, pools[b][1])
+        check_pool_rows(bank, b, frames, pools[b][1])
     bank.close()
 
 
@@ -99,18 +92,18 @@ def test_graph_replays(capi, pools, monkeypatch):
     import torch
     monkeypatch.setenv("SDR_FFT_RESERVE", "48")
     per = 1024
-    bank = _bank(capi, 1, per)
+    bank = pool_bank(capi, 1, per)
     stream = torch.cuda.Stream()
     bank.set_stream(stream.cuda_stream)
     K = bank.graph_batches
     bank.graph_capture(per)
     for rep in range(2):
         use = [pools[(rep + k) % len(pools)] for k in range(K)]
-        devs = [_batch(torch.from_numpy(p[0]).cuda(), per) for p in use]
+        devs = [pool_batch(torch.from_numpy(p[0]).cuda(), per) for p in use]
         torch.cuda.synchronize()
         bank.graph_launch([d.data_ptr() for d in devs])
         bank.sync()
-        _check_rows(bank, 0, per, use[-1][1])  # (the read calls see the replay's last batch)
+        check_pool_rows(bank, 0, per, use[-1][1])  # (the read calls see the replay's last batch)
     bank.graph_release()
     bank.close()
 
@@ -120,7 +113,7 @@ def test_default_rule_end_to_end(capi, monkeypatch):
     monkeypatch.delenv("SDR_FFT_RESERVE", raising=False)
     frames = _const("kReserveMinFrames")
     assert rule_reserve(frames) > 0 and rule_reserve(frames - 1) == 0
-    _eager_case(capi, 2_000_000, 16384, 8, 1, frames, 1, True, seed=3700)
+    Case(16384, 1, 8, 8, [("batch", frames)], seed=3700).run(capi).close()
 
 
 def _probe_case(extra_env):

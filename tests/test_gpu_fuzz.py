@@ -9,21 +9,10 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from parity_tools import REC_FIELDS, bits_equal, capi  # noqa: F401 (capi: the fixture)
 from sdrainer_amd import synth
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd import capi as c
-    c.load()
-    return c
-
-
-def _bits_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("SDR_FUZZ_SEEDS", "10"))))  # (a longer soak: SDR_FUZZ_SEEDS=300)
@@ -74,8 +63,8 @@ def test_random_streams_and_cuts(capi, seed):
             assert cnt == len(p)
             peaks.append((a + fr, p))
     got = np.concatenate(recs)
-    for f in ["min_mean", "variance", "dev_in", "nf_in", "noise_dev", "noise_floor", "peak_thr", "listen_thr"]:
-        assert _bits_equal(got[f], out["frames"][f]), (seed, f)
+    for f in REC_FIELDS:
+        assert bits_equal(got[f], out["frames"][f]), (seed, f)
     for lid in lids:
         deb = out["deb"][:, lid]
         assert np.array_equal(np.concatenate(debs[lid]), deb), (seed, lid)

@@ -14,17 +14,11 @@ import pytest
 import fuzz_paths_gen as gen
 from oracle import oracle as orc
 from parity_case import Case
+from parity_tools import capi  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 N_SEEDS = int(os.environ.get("SDR_FUZZ_PATHS_SEEDS", str(gen.DEFAULT_SEEDS)))
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd import capi as c
-    c.load()
-    return c
 
 
 def _assert_adversarial(s, case, bands):

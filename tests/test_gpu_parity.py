@@ -13,31 +13,10 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from parity_tools import REC_FIELDS, assert_records_equal, bits_equal, capi, nan_equal_bits  # noqa: F401 (capi: the fixture)
 from sdrainer_amd import synth
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd import capi as c
-    c.load()
-    return c
-
-
-def _bits_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.dtype == b.dtype and a.shape == b.shape
-    u = {4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize]
-    return np.array_equal(a.view(u), b.view(u))
-
-
-REC_FIELDS = ["min_mean", "variance", "dev_in", "nf_in", "noise_dev", "noise_floor", "peak_thr", "listen_thr"]
-
-
-def _assert_records_equal(got, ref, what=""):
-    for f in REC_FIELDS:
-        assert _bits_equal(got[f], ref[f]), f"{what} frame record field {f} differs"
 
 
 def _peak_tuple_equal(g, r):
@@ -56,8 +35,8 @@ def test_spectrum_psd_bit_exact(capi, n, rate, tones):
     for f in range(frames):
         sp, psd = bank.read_spectrum(0, f)
         sp_ref, psd_ref = orc.iq_to_spectrum_and_psd(iq[f])
-        assert _bits_equal(psd, psd_ref), f"psd frame {f}"
-        assert _bits_equal(sp, sp_ref), f"spectrum frame {f}"
+        assert bits_equal(psd, psd_ref), f"psd frame {f}"
+        assert bits_equal(sp, sp_ref), f"spectrum frame {f}"
         # north-star bound: magnitudes within 1e-5 relative of the mathematical DFT
         mag_ref = np.abs(np.fft.fftshift(np.fft.fft(x[f])))
         mag = np.sqrt(psd.astype(np.float64))
@@ -79,10 +58,10 @@ def test_receiver_run_bit_exact(capi, n, rate, tones, frames):
     assert lids == rids
     out = ref.process(iq)
     assert bank.process_host(iq) == frames
-    _assert_records_equal(bank.read_frame_records(0), out["frames"])
+    assert_records_equal(bank.read_frame_records(0), out["frames"])
     for lid in lids:
         v, r, d = bank.read_trace(0, lid)
-        assert _bits_equal(v, out["values"][:, lid].copy())
+        assert bits_equal(v, out["values"][:, lid].copy())
         assert np.array_equal(r, out["raw"][:, lid]) and np.array_equal(d, out["deb"][:, lid])
         assert np.array_equal(bank.read_keying_bits(0, lid), out["deb"][:, lid])
         # edges = transitions of the debounced stream (the input of Decoder.Tick)
@@ -94,7 +73,7 @@ def test_receiver_run_bit_exact(capi, n, rate, tones, frames):
         assert bank.read_text(0, lid) == ref.text(lid)
     assert bank.last_batch_chunks == out["n_chunks"] == frames // 100
     for c in range(out["n_chunks"]):
-        assert _bits_equal(bank.read_cumulation(0, c), out["cumulation"][c])
+        assert bits_equal(bank.read_cumulation(0, c), out["cumulation"][c])
         peaks, count, fr = bank.read_peaks(0, c)
         assert fr == out["peak_frames"][c] and count == len(out["peaks"][c])
         assert peaks == out["peaks"][c]
@@ -124,7 +103,7 @@ def test_batch_split_invariance_and_carry(capi):
         for c in range(bank.last_batch_chunks):
             p, cnt, fr = bank.read_peaks(0, c)
             peaks.append((a + fr, p))
-    _assert_records_equal(np.concatenate(recs), out["frames"])
+    assert_records_equal(np.concatenate(recs), out["frames"])
     for lid in lids:
         assert np.array_equal(np.concatenate(debs[lid]), out["deb"][:, lid])
         assert text[lid] == ref.text(lid)
@@ -148,7 +127,7 @@ def test_multi_band_independent(capi):
     assert bank.process_host(allq) == frames
     for b in range(B):
         out = refs[b].process(bands[b][0])
-        _assert_records_equal(bank.read_frame_records(b), out["frames"], f"band {b}")
+        assert_records_equal(bank.read_frame_records(b), out["frames"], f"band {b}")
         for lid in range(b + 1):
             assert np.array_equal(bank.read_keying_bits(b, lid), out["deb"][:, lid])
             assert bank.read_text(b, lid) == refs[b].text(lid)
@@ -230,7 +209,7 @@ def test_listener_pool_and_controls(capi):
     bank.set_peak_threshold(0, 9.0)
     out = ref.process(iq)
     bank.process_host(iq)
-    _assert_records_equal(bank.read_frame_records(0), out["frames"])
+    assert_records_equal(bank.read_frame_records(0), out["frames"])
     p, _, _ = bank.read_peaks(0, 1)
     assert p == out["peaks"][1]
     bank.close()
@@ -296,7 +275,7 @@ def test_device_resident_input_and_profile(capi):
     assert prof["k_fft_psd"][1] == 1 and prof["k_fft_psd"][0] > 0
     ref = orc.Receiver(rate, n, synth.default_edge_width(n))
     out = ref.process(iq)
-    _assert_records_equal(bank.read_frame_records(0), out["frames"])
+    assert_records_equal(bank.read_frame_records(0), out["frames"])
     # the device pointer must be 16-byte aligned (frames are staged into LDS 16 bytes per lane)
     with pytest.raises(capi.SdrError) as e:
         bank.process_device(t.data_ptr() + 8, 1)
@@ -330,7 +309,7 @@ def test_audio_path_bit_exact(capi):
         rm, rr, rd = ref.write(sig)
         ref.close()
         ab.close()
-        assert _bits_equal(np.concatenate(mags), rm)
+        assert bits_equal(np.concatenate(mags), rm)
         assert np.array_equal(np.concatenate(raws), rr) and np.array_equal(np.concatenate(debs), rd)
         assert ab.read_text(0) == ref.text() == "cq de dl1abc"
         assert ab.read_text(1) == ""
@@ -361,7 +340,7 @@ def test_full_size_properties(capi):
         bank.close()
     bits, peaks, recs = results[0]
     assert np.array_equal(bits, results[1][0]) and peaks == results[1][1]
-    assert _bits_equal(recs["listen_thr"], results[1][2]["listen_thr"])
+    assert bits_equal(recs["listen_thr"], results[1][2]["listen_thr"])
     # after the 60-frame warm-up of the rolling means the detected keying IS the transmitted keying
     # (a noise-only bin crosses listen_thr with probability ~1e-7 per frame: allow a couple of blips)
     assert np.count_nonzero(bits[64:] != key[64:]) <= 2
@@ -385,11 +364,11 @@ def test_receiver_run_bit_exact_large_blocks(capi, n, rate, tones, frames, liste
         bank.attach(0, int(b))
     out = ref.process(iq)
     assert bank.process_host(iq) == frames
-    _assert_records_equal(bank.read_frame_records(0), out["frames"])
+    assert_records_equal(bank.read_frame_records(0), out["frames"])
     for lid in range(listeners):
         assert np.array_equal(bank.read_keying_bits(0, lid), out["deb"][:, lid])
         assert bank.read_text(0, lid) == ref.text(lid)
-    assert _bits_equal(bank.read_cumulation(0, 0), out["cumulation"][0])
+    assert bits_equal(bank.read_cumulation(0, 0), out["cumulation"][0])
     assert bank.read_peaks(0, 0)[0] == out["peaks"][0]
     bank.close()
 
@@ -405,7 +384,7 @@ def test_nine_window_geometry(capi):
         bank.attach(0, int(b))
     out = ref.process(iq)
     bank.process_host(iq)
-    _assert_records_equal(bank.read_frame_records(0), out["frames"])
+    assert_records_equal(bank.read_frame_records(0), out["frames"])
     assert bank.read_peaks(0, 0)[0] == out["peaks"][0]
     bank.close()
 
@@ -428,19 +407,12 @@ def test_scan_segment_geometries(capi, n, edge):
         bank.attach(0, int(b))
     out = ref.process(iq)
     bank.process_host(iq)
-    _assert_records_equal(bank.read_frame_records(0), out["frames"])
+    assert_records_equal(bank.read_frame_records(0), out["frames"])
     assert len(out["peaks"]) >= 1
     for c in range(len(out["peaks"])):
         assert bank.read_peaks(0, c)[0] == out["peaks"][c], c
-        assert _bits_equal(bank.read_cumulation(0, c), out["cumulation"][c]), c
+        assert bits_equal(bank.read_cumulation(0, c), out["cumulation"][c]), c
     bank.close()
-
-
-def _nan_equal_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    both_nan = np.isnan(a) & np.isnan(b)  # the sign / payload of a NaN is not part of the contract
-    u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
-    return np.array_equal(np.where(both_nan, 0, a.view(u)), np.where(both_nan, 0, b.view(u)))
 
 
 def test_degenerate_inputs_follow_the_reference(capi):
@@ -459,7 +431,7 @@ def test_degenerate_inputs_follow_the_reference(capi):
     bank.process_host(iq)
     got = bank.read_frame_records(0)
     for f in REC_FIELDS:
-        assert _nan_equal_bits(got[f], out["frames"][f]), f
+        assert nan_equal_bits(got[f], out["frames"][f]), f
     assert np.isfinite(got["listen_thr"][:70]).all()
     assert np.isneginf(got["listen_thr"][70:130]).all() and np.isnan(got["listen_thr"][130:]).all()
     sp, psd = bank.read_spectrum(0, 70)
@@ -525,8 +497,8 @@ def test_kiwi_snd_payload_unpacked_on_device(capi):
     out = ref.process(np.concatenate(ref_iq), want_spectrum=True)
     for fr in (0, 57, frames - 1):
         sp, psd = bank.read_spectrum(0, fr)
-        assert _bits_equal(sp, out["spectrum"][fr]) and _bits_equal(psd, out["psd"][fr])
-    _assert_records_equal(bank.read_frame_records(0), out["frames"])
+        assert bits_equal(sp, out["spectrum"][fr]) and bits_equal(psd, out["psd"][fr])
+    assert_records_equal(bank.read_frame_records(0), out["frames"])
     assert np.array_equal(bank.read_keying_bits(0, 0), out["deb"][:, 0])
     # afterwards the band accepts float frames again
     assert bank.push_iq(0, rate, np.zeros(2 * n, np.float32) + 1e-3) == capi.OK
@@ -562,7 +534,7 @@ def test_config5_geometry(capi):
             out = outs[b]
             recs = bank.read_frame_records(b)
             for f in REC_FIELDS:
-                assert _bits_equal(recs[f], out["frames"][f][a:e].copy()), f"band {b} frames {a}:{e} field {f}"
+                assert bits_equal(recs[f], out["frames"][f][a:e].copy()), f"band {b} frames {a}:{e} field {f}"
             for lid in range(tones):
                 assert np.array_equal(bank.read_keying_bits(b, lid), out["deb"][a:e, lid]), f"band {b} listener {lid}"
                 deb = out["deb"][:, lid].astype(np.int8)
@@ -574,7 +546,7 @@ def test_config5_geometry(capi):
             for c in range(bank.last_batch_chunks):
                 peaks, count, fr = bank.read_peaks(b, c)
                 gc = list(out["peak_frames"]).index(a + fr)
-                assert _bits_equal(bank.read_cumulation(b, c), out["cumulation"][gc])
+                assert bits_equal(bank.read_cumulation(b, c), out["cumulation"][gc])
                 assert peaks == out["peaks"][gc] and count == len(peaks)
                 n_peaks += len(peaks)
     for b in range(B):
@@ -775,7 +747,7 @@ def test_graph_mode_bit_exact(capi):
             delivered += 1
     bank.sync()
     assert bank.total_frames == frames and bank.last_batch_frames == per
-    _assert_records_equal(bank.read_frame_records(0), out["frames"][frames - per:])
+    assert_records_equal(bank.read_frame_records(0), out["frames"][frames - per:])
     for lid in range(tones):
         assert text[lid] == ref.text(lid) and len(text[lid]) > 0
         assert np.array_equal(bank.read_keying_bits(0, lid), out["deb"][frames - per:, lid])
@@ -1001,8 +973,8 @@ def test_short_batches_without_sync_keep_the_ring_sets_safe(capi, find_peaks):
     assert bank.last_batch_chunks == 1  # frames 1440..1499 complete the cumulation that ends at frame 1499
     last = len(out["cumulation"]) - 1
     assert out["peak_frames"][last] == frames - 1
-    assert _bits_equal(bank.read_cumulation(0, 0), out["cumulation"][last])
-    _assert_records_equal(bank.read_frame_records(0), out["frames"][frames - per:])
+    assert bits_equal(bank.read_cumulation(0, 0), out["cumulation"][last])
+    assert_records_equal(bank.read_frame_records(0), out["frames"][frames - per:])
     if find_peaks:
         assert bank.read_peaks(0, 0)[0] == out["peaks"][last]
     bank.close()

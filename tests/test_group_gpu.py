@@ -13,88 +13,13 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from oracle import oracle as orc  # noqa: E402
+from parity_tools import (GROUP_BANDS as BANDS, GROUP_CENTER as CENTER, Pair, assert_records_equal, capi, group_bands as _bands,  # noqa: E402, F401
+                          same_delivery as _same)
 from sdrainer_amd import synth  # noqa: E402
 
-BANDS = 5
-CENTER = [7_000_000 + 250_000 * b for b in range(BANDS)]
 DEVICE_SETS = [pytest.param((0, 0), id="dev00"),
                pytest.param((0, 1), id="dev01", marks=pytest.mark.skipif(
                    not torch.cuda.is_available() or torch.cuda.device_count() < 2, reason="needs two visible GPUs"))]
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd.csrc import build
-    build.build()
-    from sdrainer_amd import capi as c
-    return c
-
-
-def _bands(frames, rate, n, tones, seed):
-    out = [synth.make_band(frames, rate, n, tones, seed=seed + b) for b in range(BANDS)]
-    return np.stack([o[0] for o in out]), [o[1] for o in out]
-
-
-def _same(a, b):
-    """Two deliveries (capi poll dicts), field by field, floats by their bits."""
-    assert a is not None and b is not None
-    for k in ("batch_index", "first_frame", "n_frames", "runes_dropped", "edges_dropped"):
-        assert a[k] == b[k], k
-    for k in ("chunks", "peaks", "listeners", "edges", "runes", "rune_frames"):
-        assert a[k].shape == b[k].shape, k
-        assert a[k].tobytes() == b[k].tobytes(), k
-
-
-class Pair:
-    """One bank of BANDS bands and a group of the same bands, fed the same input."""
-
-    def __init__(self, capi, devices, rate, n, **kw):
-        self.capi, self.devices, self.n = capi, devices, n
-        self.bank = capi.Bank(rate, n, n_bands=BANDS, device_id=0, **kw)
-        self.group = capi.Group(devices, rate, n, BANDS, **kw)
-        self.M = len(devices)
-        for b in range(BANDS):
-            self.bank.set_center_frequency(b, CENTER[b])
-            m, lb = self.group.member(b)
-            m.set_center_frequency(lb, CENTER[b])
-        self.dev = torch.cuda.current_device()
-
-    def member_input(self, iq):
-        """iq [BANDS, frames, 2N] -> one device tensor per member, [local band][frame][2N]."""
-        return [torch.from_numpy(np.ascontiguousarray(iq[m::self.M])).to(f"cuda:{d}") for m, d in enumerate(self.devices)]
-
-    def process(self, iq):
-        nf = iq.shape[1]
-        t = torch.from_numpy(np.ascontiguousarray(iq)).to("cuda:0")
-        ts = self.member_input(iq)
-        self.bank.process_device(t.data_ptr(), nf)
-        self.group.process_device([x.data_ptr() for x in ts], nf)
-        self.check_device()
-        self.group.sync()
-        self.bank.sync()
-        self.check_device()
-
-    def attach(self, band, bin_):
-        lid = self.bank.attach(band, int(bin_))
-        m, lb = self.group.member(band)
-        assert m.attach(lb, int(bin_)) == lid
-        return lid
-
-    def polls(self, wait=True):
-        a, b = self.bank.poll(wait=wait), self.group.poll(wait=wait)
-        self.check_device()
-        if a is None:
-            assert b is None
-            return None
-        _same(b, a)
-        return b
-
-    def check_device(self):
-        assert torch.cuda.current_device() == self.dev
-
-    def close(self):
-        self.group.close()
-        self.bank.close()
 
 
 def _text(res, band, texts):
@@ -102,12 +27,6 @@ def _text(res, band, texts):
         if int(r["band"]) == band:
             lid = int(r["listener"])
             texts[lid] = texts.get(lid, "") + "".join(chr(int(x)) for x in res["runes"][r["first_rune"]:r["first_rune"] + r["n_runes"]])
-
-
-def _recs_equal(got, want):
-    for f in ("min_mean", "dev_in", "variance", "nf_in", "noise_dev", "noise_floor", "peak_thr", "listen_thr"):
-        assert np.array_equal(got[f].view(np.uint32 if got[f].dtype == np.float32 else np.uint64),
-                              want[f].view(np.uint32 if want[f].dtype == np.float32 else np.uint64)), f
 
 
 @pytest.mark.parametrize("devices", DEVICE_SETS)
@@ -132,7 +51,7 @@ def test_group_delivers_what_one_bank_delivers(capi, devices, n, rate, batches):
         delivered += 1
         _text(res, band, texts)
         m, lb = p.group.member(band)
-        _recs_equal(m.read_frame_records(lb), want["frames"])
+        assert_records_equal(m.read_frame_records(lb), want["frames"])
         if last:
             _, psd = m.read_spectrum(lb, nf - 1)
             assert np.array_equal(psd.view(np.uint32), want["psd"][-1].view(np.uint32))

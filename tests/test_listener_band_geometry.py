@@ -21,15 +21,9 @@ rows (and the kept row: never below the exact one, equal at and beside every pea
 import pytest
 
 from parity_case import RATE, Case
+from parity_tools import capi  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd import capi as c
-    c.load()
-    return c
 
 
 # -- 1. N = 16384 at 512 and 513 slots -----------------------------------------------------------------------------------
@@ -101,7 +95,7 @@ def test_config5_whole_on_one_gpu(capi):
     assert K * per * 2 == c.total
     for k in range(K):
         a, e = k * per, (k + 1) * per
-        batch = torch.stack([iq[a:e] for iq in c.dev_iq]).contiguous()
+        batch = c.device_batch(a, e)
         torch.cuda.synchronize()  # (the input is written on torch's stream, the bank reads it on its own)
         bank.process_device(batch.data_ptr(), per)
         res = bank.poll(wait=True)
@@ -109,7 +103,7 @@ def test_config5_whole_on_one_gpu(capi):
         c.check_polled(res, a, e)
         c.check_device(bank, a, e, k)
     bank.graph_capture(per)
-    batches = [torch.stack([iq[(K + k) * per:(K + k + 1) * per] for iq in c.dev_iq]).contiguous() for k in range(K)]
+    batches = [c.device_batch((K + k) * per, (K + k + 1) * per) for k in range(K)]
     torch.cuda.synchronize()
     bank.graph_launch([x.data_ptr() for x in batches])
     for k in range(K):

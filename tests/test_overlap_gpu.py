@@ -1,9 +1,8 @@
 """Overlapped frames on the GPU (sdr_config.hop < block_size; include/sdrainer_hip.h sdr_process_device_stream), bit for bit
 against the CPU oracle fed with the materialised frames: frame f of a band is stream[f * hop : f * hop + N].
 
-Inputs are continuous streams of keyed carriers over noise with one noise window left carrier-free.  synth.make_band
-builds one frame per row, so make_band(n_hops, rate, hop, ...) flattened is such a stream: every tone makes whole cycles per
-hop (phase-continuous), is keyed per hop, and bin i of the short transform is bin i * N / hop of the long one.
+Inputs are continuous streams of keyed carriers over noise with one noise window left carrier-free
+(parity_tools.make_stream); the driver is parity_case.Case with a hop.
 
 What means time follows the hop: the listeners' decoder is cw.NewDecoder(sampleRate, hop).  The oracle's receiver builds
 its decoders from the block size, so each listener's debounced bits from the oracle receiver go through
@@ -13,175 +12,20 @@ import ctypes as C
 
 import numpy as np
 import pytest
-from numpy.lib.stride_tricks import sliding_window_view
 
 from oracle import oracle as orc
+from parity_case import Case
+from parity_tools import (GEOMETRY, RATES as RATE, REC_FIELDS, bits_equal, capi, check_device_batch, decode, frames_of,  # noqa: F401
+                          make_stream, run_oracle)
 from sdrainer_amd import synth
-from test_gpu_parity_bench_sizes import REC_FIELDS, _bits_equal, _check_batch_polled, _check_device_batch
 
 pytestmark = pytest.mark.gpu
-
-RATE = {512: 48_000, 4096: 192_000, 8192: 2_000_000, 16384: 2_000_000, 32768: 2_000_000, 65536: 2_000_000}
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd import capi as c
-    c.load()
-    return c
-
-
-def to_f32(q):
-    return np.asarray(q, np.int16).astype(np.float32) / np.float32(32767.0)
-
-
-def make_stream(n, hop, frames, rate, tones, seed, sc16=False):
-    """(float32 [samples, 2], int16 [samples, 2] or None, the carriers' bins of the N-point spectrum) of a stream that
-    holds `frames` frames."""
-    n_hops = frames - 1 + n // hop
-    iq, bins, _ = synth.make_band(n_hops, rate, hop, tones, seed=seed, free_last_window=True)
-    s = iq.reshape(-1, 2)
-    q = None
-    if sc16:
-        q = np.rint(s.astype(np.float64) * (30000.0 / float(np.abs(s).max()))).astype(np.int16)
-        s = to_f32(q)
-    return s, q, [int(b) * (n // hop) for b in bins]
-
-
-def frames_of(s, n, hop, a=0, e=None):
-    """Frames [a, e) of stream s [samples, 2], materialised: float32 [frames, 2N]."""
-    w = sliding_window_view(s, n, axis=0)[::hop][a:e]  # [frames, 2, N]
-    return np.ascontiguousarray(w.transpose(0, 2, 1)).reshape(-1, 2 * n)
-
-
-def decode(deb_col, rate, hop):
-    """oracle.Decoder(rate, hop) over one listener's debounced bits: text, state, and the tick that wrote each rune."""
-    d = orc.Decoder(rate, hop)
-    d.reset()
-    L, col = orc.lib(), np.ascontiguousarray(deb_col, np.uint8)
-    at, have = [], 0
-    for f in range(len(col)):
-        L.orc_decoder_tick(d._h, int(col[f]))
-        now = L.orc_decoder_out_len(d._h)
-        at += [f] * (now - have)
-        have = now
-    return d.text(), d.state(), np.array(at, np.int64)
-
-
-def run_oracle(streams, bins, n, hop, rate, edge, centers):
-    """One oracle receiver per band over the materialised frames, plus the hop-timed decoders of every listener."""
-    outs, decs = [], []
-    for s, bn, cf in zip(streams, bins, centers):
-        r = orc.Receiver(rate, n, edge, 15.0, 1, center_frequency=cf)
-        for b in bn:
-            r.attach(int(b))
-        out = r.process(frames_of(s, n, hop), max_peaks=4096)
-        outs.append(out)
-        decs.append([decode(out["deb"][:, lid], rate, hop) for lid in range(len(bn))])
-    return outs, decs
-
-
-def listener_bins(n, carriers, count):
-    """The carriers, then both neighbours of each, then bins 0 and N - 1, up to `count` listeners."""
-    out = list(carriers)
-    for c in carriers:
-        out += [c - 1, c + 1]
-    out += [0, n - 1]
-    return out[:count]
-
-
-class Run:
-    """One overlapped bank over device-resident streams: calls of sdr_process_device_stream with the pointer advanced by
-    frames * hop, every delivery and what stays on the device checked against the oracle."""
-
-    def __init__(self, capi, n, hop, calls, n_bands, tones, listeners, sc16, seed, pad=0):
-        import torch
-
-        self.capi, self.n, self.hop, self.sc16, self.n_bands = capi, n, hop, sc16, n_bands
-        self.rate, self.edge = RATE[n], synth.default_edge_width(n)
-        self.total = sum(calls)
-        made = [make_stream(n, hop, self.total, self.rate, tones, seed + 17 * b, sc16) for b in range(n_bands)]
-        self.streams = [m[0] for m in made]
-        self.bins = [listener_bins(n, m[2], listeners) for m in made]
-        self.centers = [14_000_000 + 100_000 * b for b in range(n_bands)]
-        self.outs, self.decs = run_oracle(self.streams, self.bins, n, hop, self.rate, self.edge, self.centers)
-        self.stride = self.streams[0].shape[0] + pad  # samples
-        host = np.zeros((n_bands, self.stride, 2), np.int16 if sc16 else np.float32)
-        for b in range(n_bands):
-            host[b, :self.stride - pad] = made[b][1] if sc16 else made[b][0]
-        self.dev = torch.from_numpy(host).cuda()
-        self.bank = capi.Bank(self.rate, n, n_bands=n_bands, edge_width=self.edge, max_batch_frames=max(calls), max_listeners=listeners,
-                              max_peaks=1024, trace=True, hop=hop)
-        self.bank.set_stream(torch.cuda.current_stream().cuda_stream)
-        for b in range(n_bands):
-            self.bank.set_center_frequency(b, self.centers[b])
-            for i, bn in enumerate(self.bins[b]):
-                assert self.bank.attach(b, int(bn)) == i
-        self.bank.enable_results(True)
-        self.calls = calls
-
-    def go(self):
-        bank, n, hop = self.bank, self.n, self.hop
-        assert bank.hop == hop
-        L = len(self.bins[0])
-        text = [["" for _ in bn] for bn in self.bins]
-        rune_at = [[[] for _ in bn] for bn in self.bins]
-        pos, edges, peaks = 0, 0, 0
-        for k, frames in enumerate(self.calls):
-            ptr = self.dev.data_ptr() + pos * hop * 2 * self.dev.element_size()
-            (bank.process_device_stream_sc16 if self.sc16 else bank.process_device_stream)(ptr, frames, self.stride)
-            res = bank.poll(wait=True)
-            assert res["batch_index"] == k
-            a, e = pos, pos + frames
-            ne, npk = _check_batch_polled(res, self.outs, a, e, L, text, self.n_bands)
-            edges, peaks = edges + ne, peaks + npk
-            for r in res["listeners"]:
-                rune_at[int(r["band"])][int(r["listener"])] += [int(x) for x in res["rune_frames"][r["first_rune"]:r["first_rune"] + r["n_runes"]]]
-            _check_device_batch(bank, self.outs, a, e, self.n_bands, [range(L)] * self.n_bands, k)
-            for b in range(self.n_bands):
-                out = self.outs[b]
-                # the tap: the value handed to Listen, raw and debounced state of every listener, frame by frame
-                for lid in range(L):
-                    v, raw, deb = bank.read_trace(b, lid)
-                    assert _bits_equal(v, out["values"][a:e, lid].copy()), f"band {b} listener {lid} tap values"
-                    assert np.array_equal(raw, out["raw"][a:e, lid]) and np.array_equal(deb, out["deb"][a:e, lid])
-                # psd and spectrum of sampled frames (first, last, around a cumulation boundary, a few inside)
-                for f in sorted({0, 1, frames - 1, frames // 2, min(99, frames - 1), min(100, frames - 1), frames // 3}):
-                    sp, psd = bank.read_spectrum(b, f)
-                    want_sp, want_psd = orc.iq_to_spectrum_and_psd(frames_of(self.streams[b], n, hop, a + f, a + f + 1))
-                    assert _bits_equal(psd, want_psd), f"band {b} frame {a + f} psd"
-                    assert _bits_equal(sp, want_sp), f"band {b} frame {a + f} spectrum"
-            pos = e
-        for b in range(self.n_bands):
-            for lid in range(L):
-                want_text, want_state, want_at = self.decs[b][lid]
-                assert text[b][lid] == want_text, f"band {b} listener {lid} text"
-                assert np.array_equal(bank.read_decoder_state(b, lid), want_state), f"band {b} listener {lid} decoder state"
-                assert np.array_equal(np.array(rune_at[b][lid], np.int64), want_at), f"band {b} listener {lid} rune frames"
-        assert bank.read_drop_counters() == (0, 0)
-        assert edges > 0 and peaks > 0
-        bank.close()
-
-
-# (N, hop, frames per call and a shorter call behind it for everything that is carried, bands, carriers, listeners): chosen
-# so that every FFT input path runs strided - k_fft_psd<LOGN> one frame per workgroup and its sc16 twin, k_fft_psd<14>,
-# k_fft_r32 (1024 frames of N = 16384 and more) with the plain and, at 256 listeners, the wide tap, and k_fft2p_a
-GEOMETRY = [
-    (512, 128, (300, 130), 1, 6, 12),
-    (4096, 1024, (700, 130), 1, 16, 24),
-    (8192, 4096, (2048, 130), 8, 16, 16),
-    (16384, 2048, (256, 130), 1, 16, 24),
-    (16384, 4096, (1024, 130), 1, 16, 24),
-    (16384, 4096, (2048, 130), 1, 256, 256),
-    (32768, 8192, (256, 130), 1, 16, 24),
-    (65536, 8192, (160, 130), 1, 16, 24),
-]
 
 
 @pytest.mark.parametrize("sc16", [False, True], ids=["f32", "sc16"])
 @pytest.mark.parametrize("n,hop,calls,n_bands,tones,listeners", GEOMETRY, ids=[f"N{g[0]}-hop{g[1]}-{g[2][0]}x{g[3]}-L{g[5]}" for g in GEOMETRY])
 def test_geometry(capi, n, hop, calls, n_bands, tones, listeners, sc16):
-    Run(capi, n, hop, calls, n_bands, tones, listeners, sc16, seed=7000 + n // 64 + hop // 32).go()
+    Case.of_streams(n, hop, calls, n_bands, tones, listeners, sc16, seed=7000 + n // 64 + hop // 32).run(capi, min_edges=0).close()
 
 
 def _collect(bank, n_bands, L):
@@ -206,7 +50,7 @@ def test_split_invariance(capi, sc16):
     n, hop, rate, frames, L = 512, 128, 48_000, 437, 5
     s, q, carriers = make_stream(n, hop, frames, rate, 4, seed=99, sc16=sc16)
     bins = carriers + [carriers[0] + 1]
-    (out,), (decs,) = run_oracle([s], [bins], n, hop, rate, 70, [0])
+    _, (out,), (decs,) = run_oracle(rate, n, 70, [bins], [s], [0], hop)
     dev = torch.from_numpy(np.ascontiguousarray(q if sc16 else s)).cuda()
     size = dev.element_size()
 
@@ -219,7 +63,7 @@ def test_split_invariance(capi, sc16):
         """pieces: per processed batch what _collect returned, in order."""
         recs = np.concatenate([p[0][0] for p in pieces])
         for f in REC_FIELDS:
-            assert _bits_equal(recs[f], out["frames"][f]), f
+            assert bits_equal(recs[f], out["frames"][f]), f
         at, peaks, cums = 0, [], []
         for p in pieces:
             peaks += [(at + fr, pk) for fr, pk, _ in p[0][3]]
@@ -227,7 +71,7 @@ def test_split_invariance(capi, sc16):
             at += len(p[0][0])
         assert at == frames
         assert [f for f, _ in peaks] == list(out["peak_frames"]) and [p for _, p in peaks] == out["peaks"]
-        assert all(_bits_equal(c, w) for c, w in zip(cums, out["cumulation"])) and len(cums) == len(out["cumulation"])
+        assert all(bits_equal(c, w) for c, w in zip(cums, out["cumulation"])) and len(cums) == len(out["cumulation"])
         for lid in range(L):
             assert np.array_equal(np.concatenate([p[0][1][lid] for p in pieces]), out["deb"][:, lid])
             assert "".join(p[0][2][lid] for p in pieces) == decs[lid][0]
@@ -350,13 +194,13 @@ def test_band_stride_and_shared_buffer(capi, sc16):
     import torch
 
     n, hop = 4096, 1024
-    Run(capi, n, hop, (300, 130), 3, 8, 12, sc16, seed=5200, pad=52).go()
+    Case.of_streams(n, hop, (300, 130), 3, 8, 12, sc16, seed=5200, pad=52).run(capi, min_edges=0).close()
     rate, edge, frames = RATE[n], synth.default_edge_width(n), 200
     stride = (frames - 1) * hop + n + 36
     s, q, carriers = make_stream(n, hop, frames + (stride + hop - 1) // hop, rate, 8, seed=5300, sc16=sc16)
     streams = [s[:stride + 4000], s[stride:]]
     bins = [carriers, carriers]
-    outs, decs = run_oracle([x[:(frames - 1) * hop + n] for x in streams], bins, n, hop, rate, edge, [0, 0])
+    _, outs, decs = run_oracle(rate, n, edge, bins, [x[:(frames - 1) * hop + n] for x in streams], [0, 0], hop)
     dev = torch.from_numpy(np.ascontiguousarray(q if sc16 else s)).cuda()
     bank = capi.Bank(rate, n, n_bands=2, edge_width=edge, max_batch_frames=frames, max_listeners=8, hop=hop)
     bank.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -365,7 +209,7 @@ def test_band_stride_and_shared_buffer(capi, sc16):
             bank.attach(b, int(bn))
     (bank.process_device_stream_sc16 if sc16 else bank.process_device_stream)(dev.data_ptr(), frames, stride)
     bank.sync()
-    _check_device_batch(bank, outs, 0, frames, 2, [range(8)] * 2, 0)
+    check_device_batch(bank, outs, 0, frames, 2, [range(8)] * 2, 0)
     for b in range(2):
         for lid in range(8):
             assert bank.read_text(b, lid) == decs[b][lid][0]

@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from oracle import oracle as orc  # noqa: E402
+from parity_tools import capi, sc16_to_float32 as to_f32  # noqa: E402, F401 (capi: the fixture)
 from sdrainer_amd import synth  # noqa: E402
 
 POOL = 13
@@ -31,18 +32,6 @@ def multiply_wrong():
 
 
 SPECIAL = np.concatenate([np.array([32767, -32768, -32767, 0, 1, -1], np.int16), multiply_wrong()[::97]])
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd.csrc import build
-    build.build()
-    from sdrainer_amd import capi as c
-    return c
-
-
-def to_f32(q):
-    return q.astype(np.float32) / np.float32(32767.0)
 
 
 def pool(n, tones, seed):

@@ -17,18 +17,10 @@ import pytest
 
 import value_range_gen as gen
 from oracle import oracle as orc
-from parity_case import Case, nan_equal_bits
-from test_gpu_parity_bench_sizes import _bits_equal, _check_device_batch
-from test_window_gpu import WRun, environment
+from parity_case import Case
+from parity_tools import bits_equal, capi, check_device_batch, environment, nan_equal_bits  # noqa: F401 (capi: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd import capi as c
-    c.load()
-    return c
 
 
 def mixed(regime, psd):
@@ -77,8 +69,8 @@ def test_value_range(capi, spec):
     bank.close()
 
 
-class VRun(WRun):
-    """test_window_gpu's driver (dense frames, one band), reading back at least 8 rows of every call that has as many."""
+class VCase(Case):
+    """Dense frames of one band on a bank with trace, reading back at least 8 rows of every batch that has as many."""
 
     def spectrum_frames(self, frames):
         return sorted(set(super().spectrum_frames(frames)) | {int(x) for x in np.linspace(0, frames - 1, 8)})
@@ -89,13 +81,14 @@ def test_value_range_windowed(capi, spec):
     """The windowed code objects have an input step of their own: float32 samples and table each carrying half of the
     exponent, and int16 samples whose table carries all of it (the only way the sc16 kernels reach these levels)."""
     s, q, w, carriers = gen.windowed_input(spec)
-    run = VRun.from_streams(spec.n, spec.batches, spec.sc16, [w] * len(spec.batches), gen.RATES[spec.n], [(s, q, carriers)],
-                            [gen.listeners(spec.n, carriers)])
+    run = VCase(spec.n, 1, None, 0, [("batch", x) for x in spec.batches], seed=0, rate=gen.RATES[spec.n],
+                path="device_sc16" if spec.sc16 else "device", bands=[(s, q, carriers)], init_bins=[gen.listeners(spec.n, carriers)],
+                windows=[w] * len(spec.batches), trace=True)
     assert len(run.spectrum_frames(spec.batches[-1])) >= 8
     edges, peaks = run.oracle_counts()
     if spec.regime in gen.ACTIVE:
         assert edges > 0 and peaks > 0
-    run.go(capi, activity=spec.regime in gen.ACTIVE)
+    run.run(capi, min_edges=0, activity=spec.regime in gen.ACTIVE).close()
 
 
 # -- non-finite samples -------------------------------------------------------------------------------------------------
@@ -132,14 +125,14 @@ class PoisonedCase(Case):
 
     def check_device(self, bank, a, e, k, cumulations=True):
         P = POISONED
-        _check_device_batch(_OneBand(bank, 1), [self.outs[1]], a, e, 1, [self.live(1, a, e)], k)
+        check_device_batch(_OneBand(bank, 1), [self.outs[1]], a, e, 1, [self.live(1, a, e)], k)
         out = self.outs[0]
         recs, want = bank.read_frame_records(0), out["frames"][a:e]
         at = np.arange(a, e)
         for f in PER_FRAME:
-            assert _bits_equal(recs[f][at != P], want[f][at != P].copy()), f"band 0 batch {k} field {f} beside the poisoned frame"
+            assert bits_equal(recs[f][at != P], want[f][at != P].copy()), f"band 0 batch {k} field {f} beside the poisoned frame"
         for f in THRESHOLDS:
-            assert _bits_equal(recs[f][at < P], want[f][at < P].copy()), f"band 0 batch {k} field {f} before the poisoned frame"
+            assert bits_equal(recs[f][at < P], want[f][at < P].copy()), f"band 0 batch {k} field {f} before the poisoned frame"
             assert not np.any(np.isfinite(recs[f][at >= P])) and not np.any(np.isfinite(want[f][at >= P])), f"band 0 field {f}: finite behind the poisoned frame"
             assert np.all(np.isnan(recs[f][at >= P + 60])) and np.all(np.isnan(want[f][at >= P + 60])), f"band 0 field {f}: not NaN 60 frames on"
         for lid in self.live(0, a, e):
@@ -153,14 +146,14 @@ class PoisonedCase(Case):
                 assert not np.any(np.isfinite(got)) and not np.any(np.isfinite(exact)), "the poisoned cumulation holds a finite bin"
                 assert pk == []
             else:
-                assert _bits_equal(got, exact), f"band 0 cumulation {gc}"
+                assert bits_equal(got, exact), f"band 0 cumulation {gc}"
         if a <= P < e:
             self.saw_frame = True
             for f in ({P - 1, P + 1} & set(range(a, e))) | {P}:
                 sp, psd = bank.read_spectrum(0, f - a)
-                want_sp, want_psd = orc.iq_to_spectrum_and_psd(self.host_iq[0][f])
+                want_sp, want_psd = orc.iq_to_spectrum_and_psd(self.frames(0, f, f + 1))
                 if f != P:
-                    assert _bits_equal(psd, want_psd) and _bits_equal(sp, want_sp), f"band 0 frame {f}: the poisoned frame's neighbour"
+                    assert bits_equal(psd, want_psd) and bits_equal(sp, want_sp), f"band 0 frame {f}: the poisoned frame's neighbour"
                     continue
                 assert not np.any(np.isfinite(psd)) and not np.any(np.isfinite(want_psd))
                 assert not np.any(np.isfinite(recs["min_mean"][P - a])) and not np.any(np.isfinite(want["min_mean"][P - a]))
@@ -169,12 +162,12 @@ class PoisonedCase(Case):
                 else:
                     assert nan_equal_bits(psd, want_psd) and nan_equal_bits(sp, want_sp)
             sp, psd = bank.read_spectrum(1, P - a)
-            want_sp, want_psd = orc.iq_to_spectrum_and_psd(self.host_iq[1][P])
-            assert _bits_equal(psd, want_psd) and _bits_equal(sp, want_sp), "band 1 at the poisoned frame"
+            want_sp, want_psd = orc.iq_to_spectrum_and_psd(self.frames(1, P, P + 1))
+            assert bits_equal(psd, want_psd) and bits_equal(sp, want_sp), "band 1 at the poisoned frame"
 
 
 class _OneBand:
-    """A bank seen as its band `band` alone (band 0 of the view), for _check_device_batch."""
+    """A bank seen as its band `band` alone (band 0 of the view), for check_device_batch."""
 
     def __init__(self, bank, band):
         self._bank, self._band = bank, band

@@ -2,171 +2,23 @@
 
 The specification is one line: the reference fed frame f, sample i = float32(x[i] * w[i]), real and imaginary part each.
 So the oracle side of every comparison here is the oracle AS IT STANDS fed with the materialised frames multiplied by numpy
-in float32 (test_window_host.windowed); everything the bank delivers and keeps must be the oracle's bits.  The tables of the
+in float32 (parity_tools.windowed); everything the bank delivers and keeps must be the oracle's bits.  The tables of the
 parity tests are random and asymmetric (0.25 - 1): a Hann table is symmetric and positive and would let a reversed or
-shifted index through.  The hop-timed decoders are test_overlap_gpu.decode's."""
-import contextlib
+shifted index through.  The driver is parity_case.Case with a window per batch; the hop-timed decoders are
+parity_tools.decode's."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from parity_case import Case
+from parity_tools import (DEMO, GEOMETRY, GROUP_BANDS as BANDS, GROUP_CENTER as CENTER, RATES as RATE, REC_FIELDS, Pair, assert_records_equal,  # noqa: F401
+                          bits_equal, capi, check_batch_polled, check_demo_oracle, check_device_batch, decode, demo_oracle, demo_stream,
+                          environment, frames_of, group_bands, make_stream, random_window, run_oracle, windowed)
 from sdrainer_amd import synth
-from test_gpu_parity_bench_sizes import REC_FIELDS, _bits_equal, _check_batch_polled, _check_device_batch, _run_oracle
-from test_overlap_gpu import GEOMETRY, RATE, decode, frames_of, listener_bins, make_stream
-from test_window_host import DEMO, check_demo_oracle, demo_oracle, demo_stream, windowed
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from sdrainer_amd import capi as c
-    c.load()
-    return c
-
-
-def random_window(n, seed):
-    """float32 in [0.25, 1): random and asymmetric, and large enough for the carriers to stand out as they did."""
-    return (np.float32(0.25) + np.float32(0.75) * np.random.default_rng(seed).random(n, dtype=np.float32)).astype(np.float32)
-
-
-@contextlib.contextmanager
-def environment(**kw):
-    """Switches the library reads when a bank is created (host/batch_plan.h read_switches)."""
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update({k: str(v) for k, v in kw.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-class WRun:
-    """test_overlap_gpu.Run with a window per call (None: none): one bank over device-resident streams - overlapped
-    (sdr_process_device_stream, the pointer advanced by frames * hop) or, with hop = 0, dense (sdr_process_device) - every
-    delivery and what stays on the device checked against the oracle fed with the windowed frames."""
-
-    def __init__(self, n, hop, calls, n_bands, tones, listeners, sc16, seed, windows):
-        made = [make_stream(n, hop or n, sum(calls), RATE[n], tones, seed + 17 * b, sc16) for b in range(n_bands)]
-        self._init(n, hop, calls, sc16, windows, RATE[n], made, [listener_bins(n, m[2], listeners) for m in made])
-
-    @classmethod
-    def from_streams(cls, n, calls, sc16, windows, rate, made, bins):
-        """Dense frames (hop = 0) of ready streams: made[band] = (float32 [samples, 2], int16 [samples, 2] or None, the
-        carriers' bins) as make_stream returns it, bins[band] the listeners' bins (as many in every band)."""
-        self = cls.__new__(cls)
-        self._init(n, 0, calls, sc16, windows, rate, made, bins)
-        return self
-
-    def _init(self, n, hop, calls, sc16, windows, rate, made, bins):
-        assert len(windows) == len(calls)
-        self.n, self.hop, self.step, self.sc16, self.n_bands = n, hop, hop or n, sc16, len(made)
-        self.calls, self.windows, self.listeners = calls, windows, len(bins[0])
-        self.rate, self.edge = rate, synth.default_edge_width(n)
-        self.total = sum(calls)
-        self.made, self.bins = made, bins
-        self.streams = [m[0] for m in self.made]
-        self.centers = [14_000_000 + 100_000 * b for b in range(self.n_bands)]
-        self.outs, self.decs = [], []
-        for s, bn, cf in zip(self.streams, self.bins, self.centers):
-            r = orc.Receiver(self.rate, n, self.edge, 15.0, 1, center_frequency=cf)
-            for b in bn:
-                r.attach(int(b))
-            out = r.process(self.frames(s, 0, self.total), max_peaks=4096)
-            self.outs.append(out)
-            self.decs.append([decode(out["deb"][:, lid], self.rate, self.step) for lid in range(len(bn))])
-
-    def spectrum_frames(self, frames):
-        """The frames of a call of `frames` frames whose psd and dB rows are read back."""
-        return sorted({0, min(1, frames - 1), frames - 1, frames // 2, min(99, frames - 1), min(100, frames - 1), frames // 3})
-
-    def frames(self, s, a, e):
-        """Frames [a, e) of stream s as the reference is fed them: each call's frames times that call's window."""
-        f = frames_of(s, self.n, self.step, a, e)
-        if not f.flags.writeable:  # (one frame, or dense frames: a view of the stream)
-            f = f.copy()
-        pos = 0
-        for frames, w in zip(self.calls, self.windows):
-            lo, hi = max(a, pos), min(e, pos + frames)
-            if w is not None and lo < hi:
-                f[lo - a:hi - a] = windowed(f[lo - a:hi - a], w, self.n)
-            pos += frames
-        return f
-
-    def oracle_counts(self):
-        """(edges, peaks) the oracle sees over the run: a row with none of either proves nothing."""
-        edges = sum(int(np.count_nonzero(np.diff(np.concatenate([[0], out["deb"][:, lid].astype(np.int8)])))) for out in self.outs
-                    for lid in range(out["deb"].shape[1]))
-        return edges, sum(len(p) for out in self.outs for p in out["peaks"])
-
-    def go(self, capi, activity=True):
-        """activity=False: a stream in which the oracle keys nothing or finds no peak (test_value_range_gpu.py's floor)."""
-        import torch
-
-        n, step, n_bands, L = self.n, self.step, self.n_bands, self.listeners
-        samples = self.streams[0].shape[0]
-        host = np.zeros((n_bands, samples, 2), np.int16 if self.sc16 else np.float32)
-        for b in range(n_bands):
-            host[b] = self.made[b][1] if self.sc16 else self.made[b][0]
-        dev = torch.from_numpy(host).cuda()
-        bank = capi.Bank(self.rate, n, n_bands=n_bands, edge_width=self.edge, max_batch_frames=max(self.calls), max_listeners=L,
-                         max_peaks=1024, trace=True, hop=self.hop)
-        bank.set_stream(torch.cuda.current_stream().cuda_stream)
-        for b in range(n_bands):
-            bank.set_center_frequency(b, self.centers[b])
-            for i, bn in enumerate(self.bins[b]):
-                assert bank.attach(b, int(bn)) == i
-        bank.enable_results(True)
-        assert bank.hop == step
-        text = [["" for _ in bn] for bn in self.bins]
-        rune_at = [[[] for _ in bn] for bn in self.bins]
-        pos, edges, peaks, current = 0, 0, 0, None
-        for k, frames in enumerate(self.calls):
-            if self.windows[k] is not current:  # (a bank that never had a window is never told about one)
-                current = self.windows[k]
-                bank.set_window(current)
-            if self.hop:
-                ptr = dev.data_ptr() + pos * step * 2 * dev.element_size()
-                (bank.process_device_stream_sc16 if self.sc16 else bank.process_device_stream)(ptr, frames, samples)
-            else:
-                batch = dev[:, pos * n:(pos + frames) * n].contiguous()  # [band][frame][N][2]
-                (bank.process_device_sc16 if self.sc16 else bank.process_device)(batch.data_ptr(), frames)
-            res = bank.poll(wait=True)
-            assert res["batch_index"] == k
-            a, e = pos, pos + frames
-            ne, npk = _check_batch_polled(res, self.outs, a, e, L, text, n_bands)
-            edges, peaks = edges + ne, peaks + npk
-            for r in res["listeners"]:
-                rune_at[int(r["band"])][int(r["listener"])] += [int(x) for x in res["rune_frames"][r["first_rune"]:r["first_rune"] + r["n_runes"]]]
-            _check_device_batch(bank, self.outs, a, e, n_bands, [range(L)] * n_bands, k)
-            for b in range(n_bands):
-                out = self.outs[b]
-                for lid in range(L):
-                    v, raw, deb = bank.read_trace(b, lid)
-                    assert _bits_equal(v, out["values"][a:e, lid].copy()), f"band {b} listener {lid} tap values"
-                    assert np.array_equal(raw, out["raw"][a:e, lid]) and np.array_equal(deb, out["deb"][a:e, lid])
-                for f in self.spectrum_frames(frames):
-                    sp, psd = bank.read_spectrum(b, f)
-                    want_sp, want_psd = orc.iq_to_spectrum_and_psd(self.frames(self.streams[b], a + f, a + f + 1))
-                    assert _bits_equal(psd, want_psd), f"band {b} frame {a + f} psd"
-                    assert _bits_equal(sp, want_sp), f"band {b} frame {a + f} spectrum"
-            pos = e
-        for b in range(n_bands):
-            for lid in range(L):
-                want_text, want_state, want_at = self.decs[b][lid]
-                assert text[b][lid] == want_text, f"band {b} listener {lid} text"
-                assert np.array_equal(bank.read_decoder_state(b, lid), want_state), f"band {b} listener {lid} decoder state"
-                assert np.array_equal(np.array(rune_at[b][lid], np.int64), want_at), f"band {b} listener {lid} rune frames"
-        assert bank.read_drop_counters() == (0, 0)
-        assert not activity or (edges > 0 and peaks > 0)
-        bank.close()
 
 
 # 1. Every input path ---------------------------------------------------------------------------------------------------
@@ -188,7 +40,7 @@ def row_id(g):
 def row_run(g, sc16):
     n, hop, calls, n_bands, tones, listeners, _ = g
     seed = 7000 + n // 64 + hop // 32
-    return WRun(n, hop, calls, n_bands, tones, listeners, sc16, seed, [random_window(n, seed + 1)] * len(calls))
+    return Case.of_streams(n, hop, calls, n_bands, tones, listeners, sc16, seed, [random_window(n, seed + 1)] * len(calls))
 
 
 @pytest.mark.parametrize("sc16", [False, True], ids=["f32", "sc16"])
@@ -198,7 +50,7 @@ def test_every_input_path(capi, g, sc16):
     edges, peaks = run.oracle_counts()
     assert edges > 0 and peaks > 0, "the row's input shows the oracle no edge or no peak"
     with environment(**({"SDR_FFT_FPW": g[6]} if g[6] else {})):
-        run.go(capi)
+        run.run(capi, min_edges=0).close()
 
 
 # 2. All ones is no window ----------------------------------------------------------------------------------------------
@@ -275,10 +127,10 @@ def test_window_changes_between_batches(capi, sc16):
     """One stream in three calls, the window changed between them (none -> random -> Hann): the oracle fed the three frame
     ranges multiplied accordingly; rolling means, the open cumulation (250, 130 and 170 frames) and the decoders carry across."""
     n, hop = 4096, 1024
-    run = WRun(n, hop, (250, 130, 170), 2, 12, 16, sc16, 8300, [None, random_window(n, 8301), synth.hann(n)])
+    run = Case.of_streams(n, hop, (250, 130, 170), 2, 12, 16, sc16, 8300, [None, random_window(n, 8301), synth.hann(n)])
     edges, peaks = run.oracle_counts()
     assert edges > 0 and peaks > 0
-    run.go(capi)
+    run.run(capi, min_edges=0).close()
 
 
 # 4. Staged, Kiwi, group, graph -----------------------------------------------------------------------------------------
@@ -317,7 +169,7 @@ def test_staged_pushes_with_a_hop(capi, sc16):
     assert at == frames
     recs = np.concatenate(recs)
     for f in REC_FIELDS:
-        assert _bits_equal(recs[f], out["frames"][f]), f
+        assert bits_equal(recs[f], out["frames"][f]), f
     for lid in range(L):
         assert np.array_equal(np.concatenate(debs[lid]), out["deb"][:, lid])
         assert text[lid] == decs[lid][0] and np.array_equal(bank.read_decoder_state(0, lid), decs[lid][1])
@@ -351,12 +203,12 @@ def test_kiwi_payloads(capi):
     out = ref.process(windowed(np.concatenate(ref_iq), w, n), want_spectrum=True)
     for fr in (0, 57, frames - 1):
         sp, psd = bank.read_spectrum(0, fr)
-        assert _bits_equal(sp, out["spectrum"][fr]) and _bits_equal(psd, out["psd"][fr])
+        assert bits_equal(sp, out["spectrum"][fr]) and bits_equal(psd, out["psd"][fr])
     recs = bank.read_frame_records(0)
     for fld in REC_FIELDS:
-        assert _bits_equal(recs[fld], out["frames"][fld]), fld
+        assert bits_equal(recs[fld], out["frames"][fld]), fld
     v, raw, deb = bank.read_trace(0, 0)
-    assert _bits_equal(v, out["values"][:, 0].copy()) and np.array_equal(raw, out["raw"][:, 0]) and np.array_equal(deb, out["deb"][:, 0])
+    assert bits_equal(v, out["values"][:, 0].copy()) and np.array_equal(raw, out["raw"][:, 0]) and np.array_equal(deb, out["deb"][:, 0])
     assert np.array_equal(bank.read_keying_bits(0, 0), out["deb"][:, 0])
     bank.close()
 
@@ -365,11 +217,9 @@ def test_group_window(capi):
     """A two-member group on one GPU through sdr_group_set_window against ONE bank with the same window (every merged
     delivery equal, field by field), one band of each member against the oracle; the window changes between the batches
     (random -> none -> Hann), for every member at the same frame."""
-    from test_group_gpu import BANDS, CENTER, Pair, _bands, _recs_equal
-
     n, rate, tones, batches = 1024, 96000, 4, (250, 150, 200)
     edge = synth.default_edge_width(n)
-    iq, bins = _bands(sum(batches), rate, n, tones, seed=8600)
+    iq, bins = group_bands(sum(batches), rate, n, tones, seed=8600)
     p = Pair(capi, (0, 0), rate, n, edge_width=edge, max_listeners=8, max_batch_frames=max(batches), max_peaks=64)
     p.bank.enable_results(True)
     p.group.enable_results(True)
@@ -393,10 +243,10 @@ def test_group_window(capi):
         for b in watched:
             want = refs[b].process(seg[b] if windows[k] is None else windowed(seg[b], windows[k], n), want_spectrum=True)
             m, lb = p.group.member(b)
-            _recs_equal(m.read_frame_records(lb), want["frames"])
-            _recs_equal(p.bank.read_frame_records(b), want["frames"])
+            assert_records_equal(m.read_frame_records(lb), want["frames"], f"band {b} (group)")
+            assert_records_equal(p.bank.read_frame_records(b), want["frames"], f"band {b} (bank)")
             _, psd = m.read_spectrum(lb, nf - 1)
-            assert _bits_equal(psd, want["psd"][-1])
+            assert bits_equal(psd, want["psd"][-1])
             for lid in range(tones):
                 assert np.array_equal(m.read_keying_bits(lb, lid), want["deb"][:, lid])
         f0 += nf
@@ -427,7 +277,7 @@ def test_graph_capture_with_a_window(capi):
         bins_per_band.append(bins)
         host_iq.append(windowed(iq.cpu().numpy(), w, n))
     centers = [7000000 + 50000 * b for b in range(n_bands)]
-    refs, outs = _run_oracle(rate, n, edge, bins_per_band, host_iq, centers)
+    refs, outs, _ = run_oracle(rate, n, edge, bins_per_band, host_iq, centers)
     stream = torch.cuda.Stream()
     bank.set_stream(stream.cuda_stream)
     for b in range(n_bands):
@@ -447,14 +297,14 @@ def test_graph_capture_with_a_window(capi):
             res = bank.poll(wait=True)
             a = (rep * K + k) * per
             assert res["batch_index"] == delivered
-            ne, npk = _check_batch_polled(res, outs, a, a + per, tones, text, n_bands)
+            ne, npk = check_batch_polled(res, outs, a, a + per, tones, text, n_bands)
             edges, peaks, delivered = edges + ne, peaks + npk, delivered + 1
     bank.sync()
     assert bank.total_frames == total and edges > 0 and peaks > 0
     for b in range(n_bands):
         recs = bank.read_frame_records(b)
         for f in REC_FIELDS:
-            assert _bits_equal(recs[f], outs[b]["frames"][f][total - per:].copy()), f"band {b} field {f}"
+            assert bits_equal(recs[f], outs[b]["frames"][f][total - per:].copy()), f"band {b} field {f}"
         for lid in range(tones):
             assert text[b][lid] == refs[b].text(lid), f"band {b} listener {lid}"
             assert np.array_equal(bank.read_keying_bits(b, lid), outs[b]["deb"][total - per:, lid])
@@ -511,7 +361,7 @@ def test_statuses(capi):
     # ... and the refused calls changed nothing: the second batch still runs with w
     bank.process_device(dev[frames:].data_ptr(), frames)
     bank.poll(wait=True)
-    _check_device_batch(bank, [out], frames, 2 * frames, 1, [range(8)], 1)
+    check_device_batch(bank, [out], frames, 2 * frames, 1, [range(8)], 1)
     bank.set_window(None)
     bank.set_window(synth.hann(n))
     bank.close()
@@ -528,7 +378,7 @@ def test_statuses(capi):
     bank.set_window(w)  # (accepted again once the capture is gone)
     bank.process_device(dev.data_ptr(), frames)
     bank.sync()
-    _check_device_batch(bank, [out], 0, frames, 1, [range(8)], 0)
+    check_device_batch(bank, [out], 0, frames, 1, [range(8)], 0)
     bank.close()
 
 

@@ -13,101 +13,12 @@ import subprocess
 import numpy as np
 import pytest
 
-from oracle import oracle as orc
+from parity_tools import DEMO, check_demo_oracle, demo_oracle, demo_stream, merged_runs, windowed
 from sdrainer_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "tests", "host")
 NEW_SYMBOLS = ["sdr_set_window", "sdr_group_set_window"]
-
-DEMO = dict(rate=192_000, n=4096, hop=1024, edge=560, bin=2600, weak_amplitude=3e-4, weak_text="cq de dl1abc dl1abc dl1abc k",
-            weak_repeats=2, weak_wpm=20, strong_amplitude=0.1, strong_bin=2588.5, strong_text="test w1aw w1aw test", strong_wpm=27,
-            strong_edge_ms=5.0, sigma=1e-3, seed=5)
-
-
-def windowed(frames, w, n):
-    """Frames [F, 2N] float32 with sample i of each multiplied by w[i]: numpy's float32 product, one rounding per
-    component - the definition of what the bank computes with that window."""
-    w = np.asarray(w, np.float32)
-    return (frames.reshape(-1, n, 2) * w[None, :, None]).astype(np.float32).reshape(-1, 2 * n)
-
-
-def _carrier(bin_, n, a, e):
-    """cos and sin of the carrier at spectrum bin `bin_` (a multiple of 0.5) over samples [a, e): FFT index bin_ + N / 2
-    (the spectrum is fft-shifted), the phase reduced in integers."""
-    k2 = int(round(2 * bin_)) + n  # twice the FFT index
-    ph = np.pi * ((k2 * np.arange(a, e, dtype=np.int64)) % (2 * n)) / n
-    return np.cos(ph), np.sin(ph)
-
-
-def demo_stream(neighbour):
-    """float32 [samples, 2]: the weak keyed station on bin 2600, the strong neighbour ("carrier": unkeyed; "soft": keyed
-    with raised-cosine edges) and noise, I drawn before Q over the whole stream."""
-    d = DEMO
-    rate, n = d["rate"], d["n"]
-    dit = int(round(1.2 / d["weak_wpm"] * rate))
-    key = np.repeat(np.concatenate([np.zeros(30, np.uint8), np.tile(synth.keying_pattern(d["weak_text"], 1), d["weak_repeats"])]), dit)
-    samples = (len(key) + n + 8191) // 8192 * 8192
-    key = np.concatenate([key, np.zeros(samples - len(key), np.uint8)]).astype(np.float64)
-    if neighbour == "carrier":
-        strong = np.ones(samples)
-    else:
-        sdit = int(round(1.2 / d["strong_wpm"] * rate))
-        pat = np.repeat(np.concatenate([synth.keying_pattern(d["strong_text"], 1), np.zeros(7, np.uint8)]), sdit)
-        strong = np.tile(pat, samples // len(pat) + 1)[:samples].astype(np.float64)
-        kern = np.hanning(int(round(d["strong_edge_ms"] * 1e-3 * rate)) + 2)[1:-1]
-        strong = np.convolve(strong, kern / kern.sum(), mode="same")
-    rng = np.random.default_rng(d["seed"])
-    noise_i = d["sigma"] * rng.standard_normal(samples)
-    noise_q = d["sigma"] * rng.standard_normal(samples)
-    out = np.empty((samples, 2), np.float32)
-    step = 1 << 21
-    for a in range(0, samples, step):
-        e = min(samples, a + step)
-        wc, ws = _carrier(d["bin"], n, a, e)
-        sc, ss = _carrier(d["strong_bin"], n, a, e)
-        out[a:e, 0] = d["weak_amplitude"] * key[a:e] * wc + d["strong_amplitude"] * strong[a:e] * sc + noise_i[a:e]
-        out[a:e, 1] = d["weak_amplitude"] * key[a:e] * ws + d["strong_amplitude"] * strong[a:e] * ss + noise_q[a:e]
-    return out
-
-
-def demo_oracle(s, w, piece=1200):
-    """The oracle receiver (find_peaks on) over every frame of stream s with window w (None: rectangular), the frames
-    materialised `piece` at a time, and the hop-timed decoder over the listener's debounced bits.  Returns deb bits, text,
-    decoder state, and per completed cumulation its completing frame and peak list."""
-    from test_overlap_gpu import decode, frames_of
-
-    d = DEMO
-    rate, n, hop = d["rate"], d["n"], d["hop"]
-    r = orc.Receiver(rate, n, d["edge"])
-    r.attach(d["bin"])
-    frames = (s.shape[0] - n) // hop + 1
-    deb, peak_frames, peaks = [], [], []
-    for a in range(0, frames, piece):
-        f = frames_of(s, n, hop, a, min(a + piece, frames))
-        out = r.process(f if w is None else windowed(f, w, n))
-        deb.append(out["deb"][:, 0])
-        peak_frames += [a + int(x) for x in out["peak_frames"]]
-        peaks += out["peaks"]
-    deb = np.concatenate(deb)
-    text, state, _ = decode(deb, rate, hop)
-    return dict(deb=deb, text=text, state=state, peak_frames=peak_frames, peaks=peaks, frames=frames)
-
-
-def merged_runs(peaks, lo=2588, hi=2600):
-    """How many cumulations hold one peak run that contains both bins (the two stations are one peak), and the longest run."""
-    merged = sum(any(p[0] <= lo and p[1] >= hi for p in pk) for pk in peaks)
-    longest = max((p[1] - p[0] + 1 for pk in peaks for p in pk), default=0)
-    return merged, longest
-
-
-def check_demo_oracle(rect, hann):
-    """The assertions on the oracle alone: they come first, so that a weak input fails as an input."""
-    assert len(rect["peaks"]) == len(hann["peaks"]) >= 70
-    assert "dl1abc" not in rect["text"], rect["text"]
-    assert merged_runs(rect["peaks"])[0] * 2 >= len(rect["peaks"]), merged_runs(rect["peaks"])
-    assert hann["text"].count("dl1abc") >= 4, hann["text"]
-    assert merged_runs(hann["peaks"])[0] == 0, merged_runs(hann["peaks"])
 
 
 @pytest.fixture(scope="module")
