@@ -482,6 +482,9 @@ int sdr_audio_set_magnitude_threshold(sdr_audio *a, double t);    /* default 0.7
  * Goertzel blocks are processed, the remainder is kept for the next call (audio.go:175-179). */
 int sdr_audio_write(sdr_audio *a, const float *samples, int n_samples);
 int sdr_audio_close(sdr_audio *a);                                /* decoder.stop (audio.go:205-207)  */
+/* The text one stream decoded since the last read, as UTF-8; a rune is never split (the decoder emits two-byte
+ * runes, U+00A7 and U+00A6, for keying it cannot name).  What does not fit into max_bytes is kept, in order, for the
+ * next call.  A stream stores at most 4096 undelivered runes: those decoded while the store is full are dropped. */
 int sdr_audio_read_text(sdr_audio *a, int stream, char *out, int max_bytes, int *n_bytes);
 /* per-block normalised magnitude / raw / debounced state of the last write (parity) */
 int sdr_audio_read_trace(sdr_audio *a, int stream, double *magnitudes, uint8_t *raw, uint8_t *debounced, int max,

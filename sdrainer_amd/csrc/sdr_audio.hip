@@ -328,7 +328,9 @@ int sdr_audio_read_text(sdr_audio *a, int stream, char *out, int max_bytes, int 
         AHIP(hipMemcpy(runes.data(), a->d_text + (size_t)stream * a->text_cap, sizeof(uint32_t) * s.text_count,
                        hipMemcpyDeviceToHost));
     int n = 0;
-    for (uint32_t r : runes) {
+    uint32_t consumed = 0;
+    for (; consumed < s.text_count; consumed++) {
+        const uint32_t r = runes[consumed];
         char tmp[4];
         size_t k;
         if (r < 0x80) {
@@ -352,8 +354,12 @@ int sdr_audio_read_text(sdr_audio *a, int stream, char *out, int max_bytes, int 
     }
     if (n_bytes)
         *n_bytes = n;
-    const uint32_t zero = 0;
-    AHIP(hipMemcpy(&a->d_state[stream].text_count, &zero, sizeof zero, hipMemcpyHostToDevice));
+    // drop what was handed out, keep the rest at the front of the buffer (as sdr_read_text does)
+    const uint32_t left = s.text_count - consumed;
+    if (left && consumed)
+        AHIP(hipMemcpy(a->d_text + (size_t)stream * a->text_cap, runes.data() + consumed, sizeof(uint32_t) * left,
+                       hipMemcpyHostToDevice));
+    AHIP(hipMemcpy(&a->d_state[stream].text_count, &left, sizeof left, hipMemcpyHostToDevice));
     return SDR_OK;
 }
 
