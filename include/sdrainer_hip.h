@@ -249,7 +249,8 @@ int64_t sdr_total_frames(sdr_bank *bank);
 /* Number of 100-frame cumulations completed by the last process call. */
 int sdr_last_batch_chunks(sdr_bank *bank);
 /* Peaks of completed cumulation `chunk` (0-based within the last batch).  *frame_in_batch = index
- * of the frame that completed it. */
+ * of the frame that completed it.  *n_out = the runs FindPeaks found, which may exceed what was stored: the first
+ * min(*n_out, max_peaks, max) records of `out` are filled, in bin order (the peaks_found of sdr_chunk_result). */
 int sdr_read_peaks(sdr_bank *bank, int band, int chunk, sdr_peak *out, int max, int *n_out, int *frame_in_batch);
 /* Cumulated spectrum (sum over 100 frames, float32[block_size]) of that chunk (rx/receiver.go:404-407), every bin the
  * reference's ordered float32 sum.  The pipeline itself keeps a cumulation exact only where FindPeaks reads it; this call
@@ -257,7 +258,9 @@ int sdr_read_peaks(sdr_bank *bank, int band, int chunk, sdr_peak *out, int max, 
 int sdr_read_cumulation(sdr_bank *bank, int band, int chunk, float *out);
 /* Decoded text of a listener since the last read, UTF-8 (what the reference writes to io.Writer). */
 int sdr_read_text(sdr_bank *bank, int band, int listener_id, char *out, int max_bytes, int *n_bytes);
-/* Keying edges of a listener produced by the last process call. */
+/* Keying edges of a listener produced by the last process call.  *n_out = the edges of the batch, which may exceed the
+ * min(max_batch_frames, 8192) a batch stores per listener: the first min(*n_out, that capacity, max) records of `out` are
+ * filled, the rest are counted in edges_dropped.  The decoder takes every edge whatever was stored. */
 int sdr_read_edges(sdr_bank *bank, int band, int listener_id, sdr_edge *out, int max, int *n_out);
 /* Packed debounced on/off bits of the last batch: bit (f & 63) of word (f >> 6). */
 int sdr_read_keying_bits(sdr_bank *bank, int band, int listener_id, uint64_t *out, int max_words);

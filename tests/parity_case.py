@@ -5,7 +5,8 @@ A Case holds n_bands bands of keyed carriers and a list of steps; it runs one or
 detached at the bank's frames and stitched into one stream per band (a listener's keying column is zero before it is
 attached), and compares with what sdr_poll delivers and what stays on the device: frame records, keying bits, edges,
 runes, decoder state, the exact cumulation rows (and the kept row: never below the exact one, equal at and beside every
-peak), peaks with their frequencies, and drop counters of 0.
+peak, those beyond the bank's max_peaks included), peaks with their frequencies (the oracle's first max_peaks of a
+cumulation, and the number of runs it found), and drop counters of 0.
 
 The input reaches the bank by one of the paths of include/sdrainer_hip.h:
   "device"       float32 in device memory (sdr_process_device)
@@ -282,14 +283,15 @@ class Case:
     def check_polled(self, res, a, e):
         """One delivered batch against the stitched oracle stream, for the listeners live in it; detached ones deliver nothing."""
         ne, npk = check_batch_polled(res, self.outs, a, e, None, self.text, self.n_bands,
-                                     live=[self.live(b, a, e) for b in range(self.n_bands)], gone=self.gone(a), rune_at=self.rune_at)
+                                     live=[self.live(b, a, e) for b in range(self.n_bands)], gone=self.gone(a), rune_at=self.rune_at,
+                                     max_peaks=self.max_peaks)
         self.edges += ne
         self.peaks += npk
 
     def check_device(self, bank, a, e, k, cumulations=True):
         """What the last batch left on the device: frame records, keying bits, cumulation rows; with trace, the tap."""
         check_device_batch(bank, self.outs, a, e, self.n_bands, [self.live(b, a, e) for b in range(self.n_bands)], k, cumulations,
-                           same=nan_equal_bits if self.nan_ok else None)
+                           same=nan_equal_bits if self.nan_ok else None, max_peaks=self.max_peaks)
         if self.trace:
             self.check_trace(bank, a, e, k)
 

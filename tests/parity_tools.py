@@ -175,14 +175,16 @@ def peaks_of(res, ch):
             for p in res["peaks"][ch["first_peak"]:ch["first_peak"] + ch["n_peaks"]]]
 
 
-def check_batch_polled(res, outs, a, e, tones, text, n_bands, live=None, gone=(), rune_at=None):
+def check_batch_polled(res, outs, a, e, tones, text, n_bands, live=None, gone=(), rune_at=None, max_peaks=None, edges_dropped=0):
     """One polled batch (sdr_poll: what bench.py's consumer thread receives) against the oracle's whole-run output.
     live[band]: the listener ids to check (default: 0 .. tones - 1); gone: (band, listener) pairs detached before the
     batch, which must deliver nothing.  The runes go to text[band][listener], their frames to rune_at (if given).
-    Returns the edges and peaks delivered."""
+    max_peaks: the bank's (None: it holds every run) - a cumulation delivers the oracle's first max_peaks peaks and says in
+    peaks_found how many runs there were; every chunk's first_peak follows on the one before.  Returns the edges and peaks
+    delivered."""
     k = res["batch_index"]
     assert res["first_frame"] == a and res["n_frames"] == e - a, f"batch {k}: frames {res['first_frame']} + {res['n_frames']}, not [{a}, {e})"
-    assert res["runes_dropped"] == 0 and res["edges_dropped"] == 0, f"batch {k}: runes or edges dropped"
+    assert res["runes_dropped"] == 0 and res["edges_dropped"] == edges_dropped, f"batch {k}: runes or edges dropped"
     by = {(int(r["band"]), int(r["listener"])): r for r in res["listeners"]}
     for key in gone:
         r = by.get(key)
@@ -209,20 +211,27 @@ def check_batch_polled(res, outs, a, e, tones, text, n_bands, live=None, gone=()
         band = int(ch["band"])
         out = outs[band]
         gc = list(out["peak_frames"]).index(int(ch["frame"]))
-        got = peaks_of(res, ch)
-        assert got == out["peaks"][gc] and ch["peaks_found"] == len(got), f"band {band} batch {k} peaks of cumulation {gc}"
+        got, want = peaks_of(res, ch), out["peaks"][gc]
+        stored = len(want) if max_peaks is None else min(len(want), max_peaks)
+        assert ch["first_peak"] == n_peaks, f"band {band} batch {k} cumulation {gc}: first_peak {ch['first_peak']} after {n_peaks} peaks"
+        assert ch["n_peaks"] == stored and ch["peaks_found"] == len(want), \
+            f"band {band} batch {k} cumulation {gc}: {ch['n_peaks']} peaks of {ch['peaks_found']} found, not {stored} of {len(want)}"
+        assert got == want[:stored], f"band {band} batch {k} peaks of cumulation {gc}"
         n_peaks += len(got)
         seen.add((band, gc))
     want = {(band, gc) for band in range(n_bands) for gc, f in enumerate(outs[band]["peak_frames"]) if a <= f < e}
     assert seen == want, f"batch {k}: cumulations (band, index) delivered {sorted(seen)}, completed {sorted(want)}"
+    assert n_peaks == len(res["peaks"]), f"batch {k}: {len(res['peaks'])} peak records for {n_peaks} peaks"
     return n_edges, n_peaks
 
 
-def check_device_batch(bank, outs, a, e, n_bands, live, k, cumulations=True, same=None):
+def check_device_batch(bank, outs, a, e, n_bands, live, k, cumulations=True, same=None, max_peaks=None):
     """What the last batch [a, e) left on the device against the oracle: frame records, the keying bits of the listeners
-    live[band], and (cumulations) every cumulation row it completed.  same: how two float arrays compare (default: bit for
-    bit; streams that hold NaN pass one that lets NaN equal NaN)."""
+    live[band], and (cumulations) every cumulation row it completed with its peaks (max_peaks: the bank's, by default read
+    from it - sdr_read_peaks hands out the oracle's first max_peaks peaks and the number of runs found).  same: how two
+    float arrays compare (default: bit for bit; streams that hold NaN pass one that lets NaN equal NaN)."""
     same = same or bits_equal
+    max_peaks = bank.cfg.max_peaks if max_peaks is None else max_peaks
     for b in range(n_bands):
         recs = bank.read_frame_records(b)
         for f in REC_FIELDS:
@@ -232,17 +241,21 @@ def check_device_batch(bank, outs, a, e, n_bands, live, k, cumulations=True, sam
         if not cumulations:
             continue
         for c in range(bank.last_batch_chunks):
-            pk, _, fr = bank.read_peaks(b, c)
+            pk, found, fr = bank.read_peaks(b, c)
             gc = list(outs[b]["peak_frames"]).index(a + fr)
-            exact = outs[b]["cumulation"][gc]
+            exact, want = outs[b]["cumulation"][gc], outs[b]["peaks"][gc]
+            assert pk == want[:max_peaks] and found == len(want), \
+                f"band {b} batch {k} cumulation {gc}: {len(pk)} peaks read of {found} found, the oracle has {len(want)}"
             assert bits_equal(bank.read_cumulation(b, c), exact), f"band {b} batch {k} cumulation {gc}"
             # the row as the pipeline keeps it (k_peaks.hip: exact where FindPeaks reads it, an upper bound elsewhere):
             # never below the exact cumulation in any bin, equal to it in every bin of every peak and beside its maximum
             with environment(SDR_READ_CUM_RAW=1):
                 raw = bank.read_cumulation(b, c)
             assert np.all(raw >= exact), f"band {b} batch {k} cumulation {gc}: the kept row is below the exact one somewhere"
-            for p in pk:
-                lo, hi = max(p[0], p[6] - 1), min(p[1], p[6] + 1)
+            # (beside the maximum also where that is outside the run - PeakCenterCorrection reads those two bins whatever the run
+            # is, and a single-bin run has both outside; the refinement knows no max_peaks: exact at the truncated peaks too)
+            for p in pk + want[max_peaks:]:
+                lo, hi = max(0, p[6] - 1), min(len(exact) - 1, p[6] + 1)
                 assert bits_equal(raw[p[0]:p[1] + 1], exact[p[0]:p[1] + 1]) and bits_equal(raw[lo:hi + 1], exact[lo:hi + 1]), \
                     f"band {b} batch {k} cumulation {gc}: the kept row differs from the exact one in peak {p[0]} - {p[1]}"
 
@@ -308,23 +321,23 @@ def same_delivery(a, b):
 
 
 class Pair:
-    """One bank of GROUP_BANDS bands and a group of the same bands, fed the same input."""
+    """One bank of n_bands bands (GROUP_BANDS unless given) and a group of the same bands, fed the same input."""
 
-    def __init__(self, capi, devices, rate, n, **kw):
+    def __init__(self, capi, devices, rate, n, n_bands=GROUP_BANDS, **kw):
         import torch
 
         self.capi, self.devices, self.n = capi, devices, n
-        self.bank = capi.Bank(rate, n, n_bands=GROUP_BANDS, device_id=0, **kw)
-        self.group = capi.Group(devices, rate, n, GROUP_BANDS, **kw)
+        self.bank = capi.Bank(rate, n, n_bands=n_bands, device_id=0, **kw)
+        self.group = capi.Group(devices, rate, n, n_bands, **kw)
         self.M = len(devices)
-        for b in range(GROUP_BANDS):
+        for b in range(n_bands):
             self.bank.set_center_frequency(b, GROUP_CENTER[b])
             m, lb = self.group.member(b)
             m.set_center_frequency(lb, GROUP_CENTER[b])
         self.dev = torch.cuda.current_device()
 
     def member_input(self, iq):
-        """iq [GROUP_BANDS, frames, 2N] -> one device tensor per member, [local band][frame][2N]."""
+        """iq [bands, frames, 2N] -> one device tensor per member, [local band][frame][2N]."""
         import torch
 
         return [torch.from_numpy(np.ascontiguousarray(iq[m::self.M])).to(f"cuda:{d}") for m, d in enumerate(self.devices)]

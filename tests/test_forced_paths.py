@@ -18,6 +18,7 @@ import sys
 import pytest
 
 import fuzz_paths_gen
+import peak_shape_gen
 import value_range_gen
 
 pytestmark = pytest.mark.gpu
@@ -30,6 +31,10 @@ FUZZ_PATHS = "test_random_paths and (" + " or ".join(f"seed{s:03d}-" for s in fu
 # node id: a -k expression matches substrings, of the module's name and of other tests' ids too
 VALUE_RANGE_FILES = [f"tests/test_value_range_gpu.py::test_value_range[{i}]" for i in value_range_gen.FORCED]
 VALUE_RANGE = ""
+# the peak scan at word, span and row ends and at its capacities (tests/peak_shape_gen.py), by node id: the whole module, and
+# its N = 16384 rows
+PEAK_SHAPE_FILES = list(peak_shape_gen.NODE_IDS)
+PEAK_SHAPE_16384 = list(peak_shape_gen.NODE_IDS_16384)
 
 
 @pytest.mark.parametrize("env, files, sel", [
@@ -67,6 +72,13 @@ VALUE_RANGE = ""
     ({"SDR_NOISE_PATH": "chains", "SDR_VAR_MFMA": "1"}, VALUE_RANGE_FILES, VALUE_RANGE),
     ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "0"}, VALUE_RANGE_FILES, VALUE_RANGE),
     ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "1"}, VALUE_RANGE_FILES, VALUE_RANGE),
+    # runs at word, span and row ends, runs longer than a word, tied pairs across every word end and more runs than max_peaks:
+    # by default these short batches take Refine::NONE - here through k_cum_bound and k_cum_refine's halo terms in both
+    # refinement shapes, and at N = 16384 behind k_fft_r32, whose wide tap then serves the listener rows' columns
+    ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "0"}, PEAK_SHAPE_FILES, ""),
+    ({"SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "1"}, PEAK_SHAPE_FILES, ""),
+    ({"SDR_FFT_R32": "1", "SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "0"}, PEAK_SHAPE_16384, ""),
+    ({"SDR_FFT_R32": "1", "SDR_CUM_BOUND": "1", "SDR_REFINE_WIDE": "1"}, PEAK_SHAPE_16384, ""),
 ])
 def test_parity_with_the_other_implementation_forced(env, files, sel):
     p = subprocess.run([sys.executable, "-m", "pytest", *[os.path.join(ROOT, f) for f in files], "-q", "-x", "-m", "gpu", "-k", sel,
@@ -75,3 +87,6 @@ def test_parity_with_the_other_implementation_forced(env, files, sel):
     assert " passed" in p.stdout and "failed" not in p.stdout
     if files is VALUE_RANGE_FILES:  # exactly the cases named, none deselected and none besides
         assert len(files) == 10 and re.search(r"(^|\s)10 passed", p.stdout) and "deselected" not in p.stdout, p.stdout[-3000:]
+    if files is PEAK_SHAPE_FILES or files is PEAK_SHAPE_16384:
+        assert len(files) == (32 if files is PEAK_SHAPE_FILES else 5), len(files)
+        assert re.search(rf"(^|\s){len(files)} passed", p.stdout) and "deselected" not in p.stdout, p.stdout[-3000:]
