@@ -324,6 +324,35 @@ int sdr_enable_results(sdr_bank *bank, int on);
  * call blocks until the oldest undelivered batch has finished (WOULD_BLOCK only if nothing was processed). */
 int sdr_poll(sdr_bank *bank, sdr_results *r, int wait);
 
+/* Waterfall rows: the exact spectrum of every completed cumulation, reduced, travelling with its batch (what the reference
+ * hands to scope.ShowSpectralFrame once per cumulation, rx/receiver.go:428-457, for a display of a few hundred to a few
+ * thousand columns - without a bank created with trace = 1, without a synchronising read, and for every batch).
+ *   sdr_enable_rows(columns): 0 switches rows off (a new bank's state: it launches exactly the kernels it launched before
+ *     this call existed); else a power of two, 64 <= columns <= block_size (anything else: SDR_ERR_BAD_ARG).  From the next
+ *     process call on, a kernel behind the batch's cumulations forms every bin's exact cumulation - what
+ *     sdr_read_cumulation returns: the reference's ordered float32 sum of the 100 spectra, fft-shifted - and packs one row
+ *     of `columns` float32 values per completed cumulation beside the batch's peaks.  With G = block_size / columns,
+ *         row[j] = the result of  m = cum[j*G]; for k in 1 .. G-1: v = cum[j*G + k]; if (v > m) m = v;
+ *     a group whose first bin is NaN gives NaN, any other the maximum of its non-NaN values; G = 1 is the cumulation itself.
+ *     NOTHING IS DIVIDED BY 100: the values are sums over SDR_CUMULATION_SIZE frames of dB + SDR_DBM_SHIFT, the caller scales
+ *     (the reference shows cumulation / 100).  Needs sdr_enable_results (SDR_ERR_STATE without; switching results off
+ *     switches rows off); SDR_ERR_STATE while a listen half is pending.  Like sdr_enable_results it invalidates a captured
+ *     graph (sdr_graph_launch returns SDR_ERR_STATE until the next capture; a capture made with rows on records the rows
+ *     kernel).  The first call, and a call with another non-zero column count, allocates pinned memory and drains the bank;
+ *     the latter needs every batch delivered first (SDR_ERR_STATE otherwise).
+ *   sdr_row_columns: the current setting.
+ *   sdr_poll_rows: a peek, like sdr_poll_peaks: copies the rows of the oldest finished, undelivered batch - the batch the
+ *     next sdr_poll hands out, which stays undelivered - to `rows` (rows_cap counts rows of `columns` values) and sets
+ *     *batch_index.  Row i belongs to chunks[i] of that batch's sdr_results: by band, then chunk.  It waits for the device
+ *     exactly where sdr_poll would (wait != 0) and returns SDR_ERR_WOULD_BLOCK where sdr_poll would; SDR_ERR_BAD_SIZE with
+ *     *n_rows set to the rows needed and nothing copied if rows_cap is too small; SDR_OK with *n_rows = 0 for a batch that
+ *     completed no cumulation or was processed with rows off.  A batch parked on the host (a ring set about to be reused,
+ *     graph replays, sdr_graph_release) keeps its rows.  With the listen half deferred the rows belong to the spectral
+ *     half: sdr_poll_rows sees the waiting batch as soon as sdr_poll_peaks does.  One consumer thread, as for sdr_poll. */
+int sdr_enable_rows(sdr_bank *bank, int columns);
+int sdr_row_columns(sdr_bank *bank);
+int sdr_poll_rows(sdr_bank *bank, float *rows, int rows_cap, int *n_rows, int64_t *batch_index, int wait);
+
 /* Strain-mode discovery over a long batch (rx/receiver.go:404-426: one listener bound per completed cumulation, to a
  * peak of that cumulation, listening from the very next frame).  With deferral on (needs sdr_enable_results), a
  * sdr_process_* call runs the spectral half of the batch only - FFT, noise floor, thresholds, cumulations and FindPeaks
@@ -352,7 +381,7 @@ int sdr_read_drop_counters(sdr_bank *bank, uint64_t *runes_dropped, uint64_t *ed
  * their own (allocated at capture), so that consecutive replays overlap stage by stage like consecutive eager batches.
  * Needs a bank on a real stream (sdr_set_stream with a non-null stream) and, once captured, all processing to go
  * through sdr_graph_launch (sdr_process_* return SDR_ERR_STATE until sdr_graph_release).  Attaching or detaching a
- * listener, sdr_enable_results and sdr_set_find_peaks invalidate the capture (sdr_graph_launch returns SDR_ERR_STATE:
+ * listener, sdr_enable_results, sdr_enable_rows and sdr_set_find_peaks invalidate the capture (sdr_graph_launch returns SDR_ERR_STATE:
  * capture again).  Results are read / polled exactly as after sdr_process_device;
  * the "last batch" of the read calls is the last replay's last.  Not offered with overlapped frames yet:
  * sdr_graph_capture(_sc16) on a bank with hop < block_size returns SDR_ERR_STATE. */
@@ -416,6 +445,12 @@ int sdr_group_set_find_peaks(sdr_group *group, int on);
 int sdr_group_set_window(sdr_group *group, const float *window, int n);
 int sdr_group_enable_results(sdr_group *group, int on);
 int sdr_group_poll(sdr_group *group, sdr_results *results, int wait);
+/* sdr_enable_rows on every member, before the group's next process call (what a member would refuse is refused before any
+ * member changes; SDR_ERR_STATE also while a group batch is half delivered).  sdr_group_poll_rows: the rows of the oldest
+ * batch EVERY member has finished, merged into the order sdr_group_poll gives that batch's chunks (global band, then
+ * chunk); the following sdr_group_poll delivers the same batch.  Statuses as sdr_poll_rows / sdr_group_poll. */
+int sdr_group_enable_rows(sdr_group *group, int columns);
+int sdr_group_poll_rows(sdr_group *group, float *rows, int rows_cap, int *n_rows, int64_t *batch_index, int wait);
 int sdr_group_defer_listen(sdr_group *group, int on);
 int sdr_group_poll_peaks(sdr_group *group, sdr_results *results, int wait);
 int sdr_group_process_listen(sdr_group *group);
@@ -468,7 +503,8 @@ int sdr_scope_read_decode(sdr_bank *bank, int band, int listener_id, sdr_scope_d
 /* When enabled every kernel launch is bracketed by HIP events on the bank's stream. */
 int sdr_profile_enable(sdr_bank *bank, int on);
 /* kernel: 0 fft_project, 1 window_means, 2 noise_stats, 3 thresholds, 4 listen_gather,
- *         5 cumulate, 6 find_peaks, 7 listen_decode.  Returns accumulated milliseconds and launch count. */
+ *         5 cumulate, 6 find_peaks, 7 listen_decode, 8 cum_rows (sdr_enable_rows; no launch while rows are off).
+ * Returns accumulated milliseconds and launch count. */
 int sdr_profile_read(sdr_bank *bank, int kernel, double *total_ms, int *launches);
 int sdr_profile_reset(sdr_bank *bank);
 const char *sdr_kernel_name(int kernel);

@@ -18,6 +18,7 @@ OK, ERR_BAD_ARG, ERR_BAD_RATE, ERR_BAD_SIZE, ERR_WOULD_DROP, ERR_HIP, ERR_NO_SLO
 CUMULATION_SIZE = 100
 KERNELS = ("k_fft_psd", "k_window_means", "k_noise_stats", "k_thresholds", "k_listen_gather", "k_cumulate",
            "k_find_peaks", "k_listen_decode")
+ROWS_KERNEL = "k_cum_rows"  # profile slot 8, behind the eight stages (launched only while rows are on: Bank.enable_rows)
 
 
 class SdrError(RuntimeError):
@@ -119,6 +120,7 @@ SYMBOLS = (
     "sdr_group_push_iq_sc16 sdr_group_process_device_sc16 "
     "sdr_hop sdr_process_device_stream sdr_process_device_stream_sc16 "
     "sdr_set_window sdr_group_set_window "
+    "sdr_enable_rows sdr_row_columns sdr_poll_rows sdr_group_enable_rows sdr_group_poll_rows "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -245,6 +247,11 @@ def load():
     sig("sdr_group_poll_peaks", C.c_int, vp, C.POINTER(Results), C.c_int)
     sig("sdr_group_process_listen", C.c_int, vp)
     sig("sdr_group_read_drop_counters", C.c_int, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+    sig("sdr_enable_rows", C.c_int, vp, C.c_int)
+    sig("sdr_row_columns", C.c_int, vp)
+    sig("sdr_poll_rows", C.c_int, vp, fp, C.c_int, ip, C.POINTER(C.c_int64), C.c_int)
+    sig("sdr_group_enable_rows", C.c_int, vp, C.c_int)
+    sig("sdr_group_poll_rows", C.c_int, vp, fp, C.c_int, ip, C.POINTER(C.c_int64), C.c_int)
     _lib = L
     return L
 
@@ -277,6 +284,32 @@ def _results_buffers(c: Config):
         setattr(r, k + "_cap", len(a))
     r.rune_frames = rune_frames.ctypes.data
     return bufs, rune_frames, r
+
+
+def _poll_rows(entry, handle, state: dict, columns: int, wait: bool, rows_cap):
+    """sdr_poll_rows / sdr_group_poll_rows: (batch_index, ndarray[n_rows, columns]), or None where the call would block.
+    The buffer grows to what the call asks for; with a fixed rows_cap (in rows) ERR_BAD_SIZE is raised instead, the rows
+    needed in the exception's n_rows."""
+    n, batch = C.c_int(), C.c_int64()
+    cap = rows_cap if rows_cap is not None else state.get("cap", 0)
+    for _ in range(2):
+        buf = state.get("buf")
+        if buf is None or buf.size < cap * columns:
+            buf = state["buf"] = np.zeros(max(cap * columns, 1), np.float32)
+        rc = entry(handle, buf.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(n), C.byref(batch), int(wait))
+        if rc == ERR_WOULD_BLOCK:
+            return None
+        if rc == ERR_BAD_SIZE and rows_cap is None:
+            cap = state["cap"] = n.value
+            continue
+        break
+    if rc != OK:
+        try:
+            _check(rc)
+        except SdrError as e:
+            e.n_rows = n.value
+            raise
+    return batch.value, buf[:n.value * columns].reshape(n.value, columns).copy()
 
 
 def _results_dict(r: Results, bufs: dict, rune_frames: np.ndarray, copy: bool) -> dict:
@@ -584,6 +617,23 @@ class Bank:
         if on and not hasattr(self, "_res"):
             self._res_bufs, self._rune_frames, self._res = _results_buffers(self.cfg)
 
+    def enable_rows(self, columns: int):
+        """sdr_enable_rows: one row of `columns` group maxima of the exact cumulation per completed cumulation (0: off)."""
+        _check(self._L.sdr_enable_rows(self._h, int(columns)))
+        if columns:
+            self._rows_last = int(columns)  # (batches processed before rows were switched off keep their rows)
+
+    @property
+    def row_columns(self) -> int:
+        return self._L.sdr_row_columns(self._h)
+
+    def poll_rows(self, wait: bool = False, rows_cap: int | None = None):
+        """sdr_poll_rows: (batch_index, ndarray[n_rows, columns]) of the oldest undelivered batch, which stays undelivered,
+        or None.  Rows are in the order of that batch's chunks; nothing is divided by 100."""
+        if not hasattr(self, "_rows_state"):
+            self._rows_state = {}
+        return _poll_rows(self._L.sdr_poll_rows, self._h, self._rows_state, getattr(self, "_rows_last", 0) or 1, wait, rows_cap)
+
     def poll_peaks(self, wait: bool = True, copy: bool = True):
         """sdr_poll_peaks: chunks and peaks of the batch that waits for its listen half (it stays undelivered)."""
         return self.poll(wait, copy, _entry=self._L.sdr_poll_peaks)
@@ -628,7 +678,7 @@ class Bank:
 
     def profile_read(self) -> dict:
         out = {}
-        for k, name in enumerate(KERNELS):
+        for k, name in enumerate(KERNELS + (ROWS_KERNEL,)):
             ms, n = C.c_double(), C.c_int()
             _check(self._L.sdr_profile_read(self._h, k, C.byref(ms), C.byref(n)))
             out[name] = (ms.value, n.value)
@@ -760,6 +810,17 @@ class Group:
 
     def poll_peaks(self, wait: bool = True, copy: bool = True):
         return self.poll(wait, copy, _entry=self._L.sdr_group_poll_peaks)
+
+    def enable_rows(self, columns: int):
+        """sdr_group_enable_rows: Bank.enable_rows on every member."""
+        _check(self._L.sdr_group_enable_rows(self._h, int(columns)))
+        self._row_columns = int(columns) or getattr(self, "_row_columns", 0)
+
+    def poll_rows(self, wait: bool = False, rows_cap: int | None = None):
+        """sdr_group_poll_rows: as Bank.poll_rows, the members' rows merged into the order of Group.poll's chunks."""
+        if not hasattr(self, "_rows_state"):
+            self._rows_state = {}
+        return _poll_rows(self._L.sdr_group_poll_rows, self._h, self._rows_state, getattr(self, "_row_columns", 0) or 1, wait, rows_cap)
 
     def defer_listen(self, on: bool = True):
         _check(self._L.sdr_group_defer_listen(self._h, int(on)))

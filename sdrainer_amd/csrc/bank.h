@@ -78,8 +78,8 @@ inline int ilog2(int n)
     return s;
 }
 
-inline const char *const kKernelNames[sdr::K_COUNT] = {"k_fft_psd",       "k_window_means", "k_noise_stats", "k_thresholds",
-                                          "k_listen_gather", "k_cumulate",     "k_find_peaks",  "k_listen_decode"};
+inline const char *const kKernelNames[sdr::K_PROFILE_COUNT] = {"k_fft_psd",       "k_window_means", "k_noise_stats", "k_thresholds",
+                                          "k_listen_gather", "k_cumulate",     "k_find_peaks",  "k_listen_decode", "k_cum_rows"};
 
 // graph mode records the four streams' kernels plus, as a graph of its own in front of the peaks stream's, the thresholds
 // (the listen graph starts behind them, not behind the cumulations)
@@ -219,6 +219,7 @@ struct sdr_bank {
     // refinement / peak-scan nodes only if find_peaks was
     bool graph_results_on = false;
     int graph_find_peaks = 0;
+    int graph_rows = 0;  // ... and the rows kernel only if rows were on, with the column count of the capture
     // deferred listen half (sdr_defer_listen): the batch whose spectra exist and whose listeners have not run yet
     bool defer_listen = false, listen_pending = false;
     struct PendingListen {
@@ -234,6 +235,9 @@ struct sdr_bank {
     // calls (the reference's Reporter is called from other goroutines too); the bookkeeping - which finished batch sits in
     // which set's pinned block or in the parked queue, who takes it - is the Delivery's, under its mutex
     bool results_on = false;
+    // waterfall rows (sdr_enable_rows): columns per row, 0 = off; the sets' pinned row blocks (host::ResultSet::rows) hold
+    // max_chunks * n_bands rows of rows_alloc_columns values, allocated when rows are switched on
+    int row_columns = 0, rows_alloc_columns = 0;
     sdr::ResultsLayout res_layout{};
     std::unique_ptr<host::DeliveryBackend> res_backend;
     std::unique_ptr<host::Delivery> results;
@@ -262,8 +266,8 @@ struct sdr_bank {
     std::vector<int> staged_kind;  // per band: 0 nothing staged, 1 float32 frames, 2 int16be frames, 3 sc16 frames
 
     bool profiling = false;
-    double prof_ms[sdr::K_COUNT] = {};
-    int prof_n[sdr::K_COUNT] = {};
+    double prof_ms[sdr::K_PROFILE_COUNT] = {};
+    int prof_n[sdr::K_PROFILE_COUNT] = {};
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
 
     sdr::NoiseGeom noise_geom() const
@@ -318,7 +322,8 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
 int process_device_impl(sdr_bank *b, const void *iq_dev, int n_frames, size_t in_stride, sdr::InFormat fmt = sdr::InFormat::F32);
 // (capi_results.hip)
 sdr::ResultsLayout make_results_layout(const sdr_bank *b);
-int results_attach_set(sdr_bank *b, int set_idx);  // the set's pinned block and events, once bulk delivery is on
+int results_attach_set(sdr_bank *b, int set_idx);  // the set's pinned block and events, once bulk delivery is on; its row block, once rows are
+void results_release_set(sdr_bank *b, int set_idx);  // ... and all of them freed
 // (capi_graph.hip)
 void drop_graphs(sdr_bank *b);
 hipError_t launch_set_cursors(sdr::BatchCursor *dst, const CursorPack &pack, hipStream_t stream);

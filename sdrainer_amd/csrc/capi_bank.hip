@@ -192,7 +192,7 @@ extern "C" {
 
 const char *sdr_last_error(void) { return g_last_error.c_str(); }
 int sdr_abi_version(void) { return SDR_ABI_VERSION; }
-const char *sdr_kernel_name(int kernel) { return (kernel >= 0 && kernel < sdr::K_COUNT) ? kKernelNames[kernel] : ""; }
+const char *sdr_kernel_name(int kernel) { return (kernel >= 0 && kernel < sdr::K_PROFILE_COUNT) ? kKernelNames[kernel] : ""; }
 
 int sdr_self_check(int device_id)
 {
@@ -423,15 +423,8 @@ int sdr_destroy(sdr_bank *b)
     for (auto &S : b->set)
         S.release();
     if (b->results)
-        for (int i = 0; i < b->results->n_sets(); i++) {
-            host::ResultSet &rs = b->results->set(i);
-            if (rs.block)
-                (void)hipHostFree(rs.block);
-            if (rs.ev_listen)
-                (void)hipEventDestroy(static_cast<hipEvent_t>(rs.ev_listen));
-            if (rs.ev_peaks)
-                (void)hipEventDestroy(static_cast<hipEvent_t>(rs.ev_peaks));
-        }
+        for (int i = 0; i < b->results->n_sets(); i++)
+            results_release_set(b, i);
     b->band_state.release();
     b->slots.release();
     b->morse.release();
@@ -714,7 +707,7 @@ int sdr_profile_enable(sdr_bank *b, int on)
 
 int sdr_profile_read(sdr_bank *b, int kernel, double *total_ms, int *launches)
 {
-    if (!b || kernel < 0 || kernel >= sdr::K_COUNT)
+    if (!b || kernel < 0 || kernel >= sdr::K_PROFILE_COUNT)
         return fail(SDR_ERR_BAD_ARG, "bad kernel id");
     int rc = sync_bank(b);
     if (rc)
@@ -733,7 +726,7 @@ int sdr_profile_reset(sdr_bank *b)
     int rc = sync_bank(b);
     if (rc)
         return rc;
-    for (int i = 0; i < sdr::K_COUNT; i++) {
+    for (int i = 0; i < sdr::K_PROFILE_COUNT; i++) {
         b->prof_ms[i] = 0;
         b->prof_n[i] = 0;
     }

@@ -85,15 +85,7 @@ static int graph_release(sdr_bank *b, bool keep_sets)
         HIP_TRY(hipSetDevice(b->device));
         for (size_t i = RING; i < b->set.size(); i++) {
             b->set[i].release();
-            host::ResultSet &rs = b->results->set((int)i);
-            if (rs.block)
-                (void)hipHostFree(rs.block);
-            if (rs.ev_listen)
-                (void)hipEventDestroy(static_cast<hipEvent_t>(rs.ev_listen));
-            if (rs.ev_peaks)
-                (void)hipEventDestroy(static_cast<hipEvent_t>(rs.ev_peaks));
-            rs.block = nullptr;
-            rs.ev_listen = rs.ev_peaks = nullptr;
+            results_release_set(b, (int)i);
         }
         b->set.resize(RING);
         if (b->last_set >= RING) {
@@ -235,6 +227,7 @@ static int graph_capture(sdr_bank *b, int n_frames, sdr::InFormat fmt)
     b->graph_attach_gen = b->attach_gen;
     b->graph_results_on = b->results_on;
     b->graph_find_peaks = b->find_peaks;
+    b->graph_rows = b->row_columns;
     return SDR_OK;
 }
 
@@ -257,8 +250,8 @@ static int graph_launch(sdr_bank *b, const void *const *iq_dev, sdr::InFormat fm
         return fail(SDR_ERR_STATE, "listeners were attached or detached since the capture: capture again");
     // the kernels that pack results, refine the cumulation and scan for peaks are nodes of the captured graphs or they are
     // not: a replay after sdr_enable_results / sdr_set_find_peaks changed either would publish batches no kernel fills
-    if (b->results_on != b->graph_results_on || b->find_peaks != b->graph_find_peaks)
-        return fail(SDR_ERR_STATE, "sdr_enable_results / sdr_set_find_peaks changed since the capture: capture again");
+    if (b->results_on != b->graph_results_on || b->find_peaks != b->graph_find_peaks || b->row_columns != b->graph_rows)
+        return fail(SDR_ERR_STATE, "sdr_enable_results / sdr_set_find_peaks / sdr_enable_rows changed since the capture: capture again");
     HIP_TRY(hipSetDevice(b->device));
     const bool dbg = b->sw.graph_debug;
     double tdbg[8] = {};
@@ -374,6 +367,8 @@ static int graph_launch(sdr_bank *b, const void *const *iq_dev, sdr::InFormat fm
             m.chunks = meta[k].chunks;
             m.count0 = meta[k].count0;
             m.slots = max_slots;
+            m.row_columns = b->graph_rows;
+            m.rows = b->graph_rows ? meta[k].chunks * b->cfg.n_bands : 0;
             {
                 std::lock_guard<std::mutex> guard(b->center_mu);
                 m.center = b->center_frequency;

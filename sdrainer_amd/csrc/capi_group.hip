@@ -23,6 +23,10 @@ struct BankSource final : host::GroupSource {
     explicit BankSource(std::vector<sdr_bank *> *b) : banks(b) {}
     int poll(int m, sdr_results *r, bool wait) override { return sdr_poll((*banks)[(size_t)m], r, wait ? 1 : 0); }
     int poll_peaks(int m, sdr_results *r, bool wait) override { return sdr_poll_peaks((*banks)[(size_t)m], r, wait ? 1 : 0); }
+    int poll_rows(int m, float *rows, int rows_cap, int *n_rows, int64_t *batch_index, bool wait) override
+    {
+        return sdr_poll_rows((*banks)[(size_t)m], rows, rows_cap, n_rows, batch_index, wait ? 1 : 0);
+    }
     int report(int code, const char *msg) override { return sdr::set_error(code, msg); }
 };
 
@@ -365,7 +369,42 @@ int sdr_group_enable_results(sdr_group *g, int on)
             return rc;
     }
     g->delivery->reset(on != 0);  // (undelivered batches are discarded with the mode, as every member discards its own)
+    if (!on)
+        g->delivery->set_rows(0);  // (the members switched their rows off with the results)
     return SDR_OK;
+}
+
+int sdr_group_enable_rows(sdr_group *g, int columns)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    // what a member could refuse is checked for all of them first: they share one geometry and one delivery mode, and a
+    // listen half is pending on every member or on none
+    if (columns != 0 && (columns < 64 || columns > g->cfg.block_size || (columns & (columns - 1)) != 0))
+        return fail(SDR_ERR_BAD_ARG, "columns must be 0 or a power of two with 64 <= columns <= block_size");
+    if (!g->delivery->on())
+        return fail(SDR_ERR_STATE, "rows need bulk delivery (sdr_group_enable_results)");
+    for (sdr_bank *b : g->banks)
+        if (sdr_listen_pending(b))
+            return fail(SDR_ERR_STATE, "a batch waits for its listen half (sdr_group_process_listen)");
+    if (g->delivery->parked() > 0)  // (a member batch taken with the old setting's rows)
+        return fail(SDR_ERR_STATE, "a batch is half delivered: sdr_group_poll first");
+    KeepDevice keep;
+    for (sdr_bank *b : g->banks) {
+        const int rc = sdr_enable_rows(b, columns);
+        if (rc)
+            return rc;
+    }
+    g->delivery->set_rows(columns);
+    return SDR_OK;
+}
+
+int sdr_group_poll_rows(sdr_group *g, float *rows, int rows_cap, int *n_rows, int64_t *batch_index, int wait)
+{
+    if (!g || !n_rows || !batch_index || rows_cap < 0 || (!rows && rows_cap > 0))
+        return fail(SDR_ERR_BAD_ARG, "null argument");
+    KeepDevice keep;
+    return g->delivery->poll_rows(rows, rows_cap, n_rows, batch_index, wait != 0);
 }
 
 int sdr_group_poll(sdr_group *g, sdr_results *r, int wait)

@@ -155,7 +155,8 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
     // every choice of this batch (host/batch_plan.h); a gather moved off the listen stream also waits for late-attached
     // slots: see slots_put below
     const int count0 = b->cum_count;
-    const sdr::BatchPlan P = sdr::plan_batch(b->sw, sdr::BatchGeometry{B, N, stride, b->max_chunks, b->fft_queue_alone}, n_frames, count0, cap, max_slots, b->windowed);
+    const sdr::BatchPlan P = sdr::plan_batch(b->sw, sdr::BatchGeometry{B, N, stride, b->max_chunks, b->fft_queue_alone}, n_frames, count0, cap, max_slots, b->windowed,
+                                                 b->results_on ? b->row_columns : 0);
     const int *plan = P.stream;
     const sdr::CumGeom cg{N, stride, n_frames, count0, b->max_chunks};
     // is kernel k part of the graph that is recording (always, outside a capture)?
@@ -391,6 +392,13 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
                                                              S.dev_peaks.p, S.peak_counts.p, cur, pg, n_frames, n_chunks, B, P.refine, wide_tap,
                                                              stream_of(sdr::K_FIND_PEAKS)));
     }
+    // the waterfall rows of the completed cumulations, straight into the set's row block: behind the cumulate step on the
+    // find-peaks stage's stream, in front of the event sdr_poll looks at (recorded behind the pack kernel below)
+    if (P.rows && SDR_ON(sdr::K_FIND_PEAKS)) {
+        ProfScope ps(b, sdr::K_CUM_ROWS, b->stream[P.rows_stream]);
+        HIP_TRY(sdr::launch_cum_rows(S.psd.p, b->db_tab.p, b->carry[0].p, b->carry[1].p, b->carry_cur, cur, cg, b->row_columns, n_chunks, B, RS.rows,
+                                     b->stream[P.rows_stream]));
+    }
     if (b->results_on && SDR_ON(sdr::K_FIND_PEAKS)) {
         SDR_ARM(sdr::K_FIND_PEAKS);
         HIP_TRY(sdr::launch_pack_peaks(S.dev_peaks.p, S.peak_counts.p, cur, b->res_layout, b->find_peaks, n_frames, n_chunks, B,
@@ -404,6 +412,8 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
             m.chunks = n_chunks;
             m.count0 = count0;
             m.slots = do_listen ? max_slots : 0;  // (sdr_poll_peaks delivers the spectral half; the listen half fills this in)
+            m.row_columns = P.rows ? b->row_columns : 0;
+            m.rows = P.rows ? n_chunks * B : 0;
             {
                 std::lock_guard<std::mutex> guard(b->center_mu);
                 m.center = b->center_frequency;

@@ -196,7 +196,18 @@ std::unique_ptr<host::DeliveryBackend> make_results_backend(sdr_bank *b) { retur
 int results_attach_set(sdr_bank *b, int set_idx)
 {
     host::ResultSet &rs = b->results->set(set_idx);
-    if (!b->res_layout.bytes || (rs.block && rs.ev_listen && rs.ev_peaks))
+    if (!b->res_layout.bytes)
+        return SDR_OK;
+    // the row block: max_chunks rows per band of the column count rows were switched on with (sdr_enable_rows has parked
+    // whatever batch still had rows of another width in the set)
+    if (b->rows_alloc_columns > 0 && !rs.rows) {
+        float *rows = nullptr;
+        const size_t bytes = sizeof(float) * (size_t)b->max_chunks * (size_t)b->cfg.n_bands * (size_t)b->rows_alloc_columns;
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&rows), bytes, hipHostMallocDefault));
+        memset(rows, 0, bytes);
+        rs.rows = rows;
+    }
+    if (rs.block && rs.ev_listen && rs.ev_peaks)
         return SDR_OK;
     // (the events first, the block last: a set is "attached" only with all three - a failure half way leaves nothing a
     // later call would take for complete)
@@ -217,6 +228,22 @@ int results_attach_set(sdr_bank *b, int set_idx)
         rs.block = blk;
     }
     return SDR_OK;
+}
+
+void results_release_set(sdr_bank *b, int set_idx)
+{
+    host::ResultSet &rs = b->results->set(set_idx);
+    if (rs.block)
+        (void)hipHostFree(rs.block);
+    if (rs.rows)
+        (void)hipHostFree(rs.rows);
+    if (rs.ev_listen)
+        (void)hipEventDestroy(static_cast<hipEvent_t>(rs.ev_listen));
+    if (rs.ev_peaks)
+        (void)hipEventDestroy(static_cast<hipEvent_t>(rs.ev_peaks));
+    rs.block = nullptr;
+    rs.rows = nullptr;
+    rs.ev_listen = rs.ev_peaks = nullptr;
 }
 
 }  // namespace sdrcapi
@@ -241,8 +268,66 @@ int sdr_enable_results(sdr_bank *b, int on)
                 return rc;
     }
     b->results_on = on != 0;
+    if (!on)
+        b->row_columns = 0;  // (rows travel with the results)
     b->results->reset(on != 0, b->batch_index);  // (undelivered batches are discarded with the mode)
     return SDR_OK;
+}
+
+// Waterfall rows.  The row blocks are sized for one column count: switching to another drains the bank and replaces them,
+// which needs every batch delivered (SDR_ERR_STATE otherwise: an undelivered batch may hold rows of the old width).
+int sdr_enable_rows(sdr_bank *b, int columns)
+{
+    if (!b)
+        return fail(SDR_ERR_BAD_ARG, "null bank");
+    if (columns != 0 && (columns < 64 || columns > b->cfg.block_size || (columns & (columns - 1)) != 0))
+        return fail(SDR_ERR_BAD_ARG, "columns must be 0 or a power of two with 64 <= columns <= block_size");
+    if (!b->results_on)
+        return fail(SDR_ERR_STATE, "rows need bulk delivery (sdr_enable_results)");
+    if (b->listen_pending)
+        return fail(SDR_ERR_STATE, "a batch waits for its listen half (sdr_process_listen)");
+    if (columns != 0 && columns != b->rows_alloc_columns) {
+        int rc = sync_bank(b);
+        if (rc)
+            return rc;
+        HIP_TRY(hipSetDevice(b->device));
+        // (an undelivered batch may hold rows of the old width in the blocks about to be replaced)
+        if (b->rows_alloc_columns != 0 && b->results->pending() > 0)
+            return fail(SDR_ERR_STATE, "another column count: poll the undelivered batches first (their rows have the old width)");
+        for (int i = 0; i < b->results->n_sets(); i++) {
+            host::ResultSet &rs = b->results->set(i);
+            if (rs.rows)
+                (void)hipHostFree(rs.rows);
+            rs.rows = nullptr;
+        }
+        b->rows_alloc_columns = columns;
+        b->graph_rows = -1;  // (a captured graph holds the old blocks' addresses: it stays invalid whatever is set later)
+        for (int i = 0; i < (int)b->set.size(); i++)
+            if ((rc = results_attach_set(b, i)))
+                return rc;
+    }
+    b->row_columns = columns;  // (a captured graph notices: sdr_graph_launch compares it with the capture's)
+    return SDR_OK;
+}
+
+int sdr_row_columns(sdr_bank *b) { return b ? b->row_columns : 0; }
+
+int sdr_poll_rows(sdr_bank *b, float *rows, int rows_cap, int *n_rows, int64_t *batch_index, int wait)
+{
+    if (!b || !n_rows || !batch_index || rows_cap < 0 || (!rows && rows_cap > 0))
+        return fail(SDR_ERR_BAD_ARG, "null argument");
+    if (!b->results->on())
+        return fail(SDR_ERR_STATE, "bulk delivery is off (sdr_enable_results)");
+    HIP_TRY(hipSetDevice(b->device));
+    host::RowsOut out;
+    out.rows = rows;
+    out.rows_cap = rows_cap;
+    const int rc = b->results->peek_rows(&out, wait != 0);
+    if (rc == SDR_OK || rc == SDR_ERR_BAD_SIZE) {
+        *n_rows = out.n_rows;
+        *batch_index = out.batch;
+    }
+    return rc;
 }
 
 int sdr_results_pending(sdr_bank *b) { return (b && b->results_on) ? b->results->pending() : 0; }

@@ -22,6 +22,9 @@ enum KernelId {
     K_FFT = 0, K_WINDOW_MEANS, K_NOISE_STATS, K_THRESHOLDS, K_LISTEN_GATHER, K_CUMULATE, K_FIND_PEAKS, K_LISTEN_DECODE,
     K_COUNT
 };
+// k_cum_rows (the waterfall rows of sdr_enable_rows) is no stage of the plan's table - it rides on the find-peaks stage's
+// stream and events - but it has a profile slot, behind the eight stages' (sdr_profile_read / sdr_kernel_name)
+constexpr int K_CUM_ROWS = K_COUNT, K_PROFILE_COUNT = K_COUNT + 1;
 // the bank's streams: four = the hardware queues HIP gives a process; with six streams created (two unused!) the step was
 // 0.49 ms instead of 0.25, with GPU_MAX_HW_QUEUES=8 and five or six in use 0.29-0.60
 enum Stage { S_FFT = 0, S_NOISE, S_LISTEN, S_PEAKS, N_STAGES };
@@ -224,13 +227,17 @@ struct BatchPlan {
     int n_chunks;      // cumulations the batch completes
     int new_count;     // cumulationCount after the batch
     Refine refine;     // the refinement's workgroup shape (NONE: no bound)
+    // sdr_enable_rows: k_cum_rows reduces every completed cumulation to row_columns values, on rows_stream behind the
+    // cumulate step (the find-peaks stage's stream: its event, which sdr_poll looks at, follows).  Off: no launch at all.
+    bool rows;
+    int rows_stream;
 };
 
 // One batch of n_frames frames that starts at cumulationCount count0, max_slots listener slots in use.  capturing: the
 // batch is being recorded into a graph (sdr_graph_capture), replayed later at whatever count0 and without stream changes.
-// windowed: the bank has a window (fft_choice).
+// windowed: the bank has a window (fft_choice).  row_columns: sdr_enable_rows' setting (0: rows off).
 inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_frames, int count0, bool capturing, int max_slots,
-                            bool windowed = false)
+                            bool windowed = false, int row_columns = 0)
 {
     BatchPlan p;
     // Which of the bank's four streams each kernel runs on.  The step is as long as the longest stream, and kernels that
@@ -294,6 +301,9 @@ inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_fr
     // 221.1 GS/s against 221.7 / 220.4 with the whole row at config 3 - the rule stays (profiles/reserve_plan_rules.jsonl).
     const bool wide = sw.refine_wide >= 0 ? sw.refine_wide != 0 : (g.n >= 4096 && (long)p.n_chunks * g.n_bands >= 64);
     p.refine = !p.bound ? Refine::NONE : wide ? Refine::WIDE : Refine::NARROW;
+    // rows only where the batch completes a cumulation (a captured batch may at any replay: n_chunks is its maximum)
+    p.rows = row_columns > 0 && p.n_chunks > 0;
+    p.rows_stream = p.stream[K_FIND_PEAKS];
     return p;
 }
 

@@ -34,6 +34,9 @@ struct BatchMeta {
     int64_t first_frame = 0;
     int frames = 0, chunks = 0, count0 = 0, slots = 0;
     std::vector<int64_t> center;  // the bands' centre frequencies when the batch was enqueued (peak frequencies)
+    // waterfall rows (sdr_enable_rows): the batch's row block holds `rows` rows of `row_columns` float32 values, one per
+    // completed cumulation, by band, then chunk; 0 / 0: the batch completed none or was processed with rows off
+    int rows = 0, row_columns = 0;
 };
 
 // the delivery side of one buffer set
@@ -41,6 +44,15 @@ struct ResultSet {
     BatchMeta meta;                 // guarded by Delivery::mu
     unsigned char *block = nullptr;  // the set's pinned block (device kernels write it, the host reads it behind the events)
     void *ev_listen = nullptr, *ev_peaks = nullptr;  // recorded behind the kernels that fill the block
+    float *rows = nullptr;  // the set's pinned row block (k_cum_rows writes it in front of ev_peaks), once rows were switched on
+};
+
+// sdr_poll_rows: the caller's buffer (in), what was found (out)
+struct RowsOut {
+    float *rows = nullptr;
+    int rows_cap = 0;  // in rows
+    int n_rows = 0, columns = 0;
+    int64_t batch = -1;
 };
 
 struct DeliveryBackend {
@@ -59,6 +71,7 @@ public:
     struct Parked {
         BatchMeta meta;
         std::unique_ptr<unsigned char[]> block;
+        std::unique_ptr<float[]> rows;  // meta.rows x meta.row_columns values (null: none)
     };
 
     // ring: the eager pipeline's sets (batch i -> set i % ring); graph_span: the sets graph mode adds behind them
@@ -127,6 +140,10 @@ public:
         Parked p;
         p.meta = S.meta;
         p.block = be_->copy_used(S.block, S.meta);
+        if (const size_t nv = S.rows ? row_values(S.meta) : 0) {  // the batch takes its rows with it
+            p.rows.reset(new float[nv]);
+            std::copy_n(S.rows, nv, p.rows.get());
+        }
         // parked stays sorted by batch: whatever is parked is older than whatever still sits in a set, and the producer
         // parks in batch order - checked here because delivery silently stalls if it is ever violated
         if (!parked_.empty() && parked_.back().meta.batch >= p.meta.batch)
@@ -274,6 +291,50 @@ public:
         return be_->deliver(S.block, m, out);
     }
 
+    // sdr_poll_rows: the rows of the oldest undelivered batch into the caller's buffer; the batch stays undelivered (the
+    // next poll() hands it out).  A batch whose listen half is still to come (publish(complete = false)) is looked at as
+    // soon as its spectral half has finished, as poll_peaks looks at it; any other batch when poll() would deliver it.
+    int peek_rows(RowsOut *out, bool wait)
+    {
+        std::unique_lock<std::mutex> guard(mu_);
+        for (int attempt = 0; attempt < 64; attempt++) {
+            const int64_t want = deliver_next_;
+            if (!parked_.empty() && parked_.front().meta.batch == want)
+                return copy_rows(parked_.front().meta, parked_.front().rows.get(), out);
+            ResultSet &S = sets_[(size_t)set_index(want)];
+            if (S.meta.batch != want)
+                return want >= batches_enqueued_ ? be_->report(SDR_ERR_WOULD_BLOCK, "no batch waiting")
+                                                 : be_->report(SDR_ERR_STATE, "results of the next batch are not where they should be");
+            const bool whole = want < batches_enqueued_;  // (else only the spectral half is enqueued: ev_listen is an older batch's)
+            void *const events[2] = {S.ev_peaks, whole ? S.ev_listen : nullptr};
+            bool moved = false;
+            for (void *e : events) {
+                if (!e)
+                    continue;
+                if (wait) {
+                    guard.unlock();  // (never held across a wait for the device)
+                    const int rc = be_->wait(e);
+                    guard.lock();
+                    if (rc != SDR_OK)
+                        return rc;
+                    if (S.meta.batch != want || deliver_next_ != want) {  // parked or delivered meanwhile: look again
+                        moved = true;
+                        break;
+                    }
+                } else {
+                    const int rc = be_->query(e);
+                    if (rc == SDR_ERR_WOULD_BLOCK)
+                        return be_->report(SDR_ERR_WOULD_BLOCK, "the oldest undelivered batch has not finished");
+                    if (rc != SDR_OK)
+                        return rc;
+                }
+            }
+            if (!moved)
+                return copy_rows(S.meta, S.rows, out);
+        }
+        return be_->report(SDR_ERR_WOULD_BLOCK, "the batch went to another consumer; poll again");
+    }
+
     // (tests)
     int64_t deliver_next()
     {
@@ -287,6 +348,22 @@ public:
     }
 
 private:
+    static size_t row_values(const BatchMeta &m) { return (size_t)std::max(m.rows, 0) * (size_t)std::max(m.row_columns, 0); }
+    int copy_rows(const BatchMeta &m, const float *rows, RowsOut *out)  // mu_ held
+    {
+        out->batch = m.batch;
+        out->columns = m.row_columns;
+        out->n_rows = row_values(m) ? m.rows : 0;
+        if (out->n_rows == 0)
+            return SDR_OK;
+        if (out->n_rows > out->rows_cap || !out->rows)
+            return be_->report(SDR_ERR_BAD_SIZE, "sdr_poll_rows: rows_cap is too small (*n_rows says what is needed)");
+        if (!rows)
+            return be_->report(SDR_ERR_STATE, "internal: a batch with rows has no row block");
+        std::copy_n(rows, row_values(m), out->rows);
+        return SDR_OK;
+    }
+
     int poll_parked(void *out)  // mu_ held: the oldest undelivered batch sits at the front of the parked queue
     {
         if (parked_.empty() || parked_.front().meta.batch != deliver_next_)

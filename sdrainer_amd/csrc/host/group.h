@@ -51,6 +51,9 @@ struct MemberBatch {
     std::vector<sdr_edge> edges = std::vector<sdr_edge>(256);
     std::vector<uint32_t> runes = std::vector<uint32_t>(256), rune_frames = std::vector<uint32_t>(256);
     bool held = false;  // r describes a batch taken from the member's bank and not delivered yet
+    // the batch's waterfall rows (sdr_group_enable_rows), peeked from the bank right before the batch was taken from it
+    std::vector<float> rows;
+    int n_rows = 0;
 
     void bind()
     {
@@ -88,6 +91,13 @@ struct GroupSource {
     // a member's sdr_poll / sdr_poll_peaks into r
     virtual int poll(int member, sdr_results *r, bool wait) = 0;
     virtual int poll_peaks(int member, sdr_results *r, bool wait) = 0;
+    // a member's sdr_poll_rows (a source without rows delivers none)
+    virtual int poll_rows(int, float *, int, int *n_rows, int64_t *batch_index, bool)
+    {
+        *n_rows = 0;
+        *batch_index = -1;
+        return SDR_OK;
+    }
     virtual int report(int code, const char *msg) = 0;  // records the message for sdr_last_error(), returns code
 };
 
@@ -194,6 +204,12 @@ public:
         std::lock_guard<std::mutex> g(mu_);
         return on_;
     }
+    // sdr_group_enable_rows: from now on a member batch is taken together with its rows, `columns` values each (0: none)
+    void set_rows(int columns)
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        row_columns_ = columns;
+    }
 
     // The oldest batch every member has finished, merged.  A member batch taken from its bank stays parked here through
     // SDR_ERR_WOULD_BLOCK (another member is behind), SDR_ERR_BAD_SIZE (the caller's buffers) and SDR_ERR_STATE, and
@@ -217,6 +233,53 @@ public:
             for (auto &p : parked_)
                 p.held = false;
         return rc;
+    }
+
+    // sdr_group_poll_rows: the rows of the oldest batch every member has finished, in the order poll() gives its chunks
+    // (global band, then chunk).  A peek for the caller - the next poll() delivers the same batch - but the member batches
+    // ARE taken from their banks (rows first, then the batch) and parked here, as poll() parks them: a bank hands out the
+    // rows of its oldest undelivered batch only.
+    int poll_rows(float *rows, int rows_cap, int *n_rows, int64_t *batch_index, bool wait)
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        if (!on_)
+            return src_->report(SDR_ERR_STATE, "bulk delivery is off (sdr_group_enable_results)");
+        for (int m = 0; m < rt_.n_members; m++) {
+            MemberBatch &p = parked_[(size_t)m];
+            if (p.held)
+                continue;
+            const int rc = take(m, p, wait, false);
+            if (rc != SDR_OK)
+                return rc;
+            p.held = true;
+        }
+        // every member completed the same cumulations: rows per band, the same on all members that have any
+        int total = 0, per_band = -1, columns = 0;
+        for (int m = 0; m < rt_.n_members; m++) {
+            const MemberBatch &p = parked_[(size_t)m];
+            if (p.r.batch_index != parked_[0].r.batch_index)
+                return src_->report(SDR_ERR_STATE, "sdr_group_poll_rows: the members delivered different batches (out of step)");
+            const int bands = rt_.bands_of(m);
+            if (p.n_rows % bands != 0 || (per_band >= 0 && p.n_rows / bands != per_band))
+                return src_->report(SDR_ERR_STATE, "sdr_group_poll_rows: the members' row counts disagree");
+            per_band = p.n_rows / bands;
+            if (p.n_rows > 0)
+                columns = (int)(p.rows.size() / (size_t)p.n_rows);
+            total += p.n_rows;
+        }
+        *n_rows = total;
+        *batch_index = parked_[0].r.batch_index;
+        if (total == 0)
+            return SDR_OK;
+        if (total > rows_cap || !rows)
+            return src_->report(SDR_ERR_BAD_SIZE, "sdr_group_poll_rows: rows_cap is too small (*n_rows says what is needed)");
+        float *dst = rows;
+        for (int gb = 0; gb < rt_.n_bands; gb++) {
+            const MemberBatch &p = parked_[(size_t)rt_.member_of(gb)];
+            const float *src = p.rows.data() + (size_t)rt_.local_of(gb) * (size_t)per_band * (size_t)columns;
+            dst = std::copy_n(src, (size_t)per_band * (size_t)columns, dst);
+        }
+        return SDR_OK;
     }
 
     // sdr_group_poll_peaks: the chunks and peaks of the batch that waits for its listen half.  The banks keep that batch
@@ -246,6 +309,26 @@ public:
 private:
     int take(int m, MemberBatch &p, bool wait, bool peaks)
     {
+        // the rows go first: once the batch itself is taken the bank's oldest undelivered batch is the next one
+        if (!peaks) {
+            p.n_rows = 0;
+            p.rows.clear();
+            int64_t batch = -1;
+            for (int attempt = 0; row_columns_ > 0 && attempt < 2; attempt++) {
+                int n = 0;
+                const int cap = (int)(p.rows.size() / (size_t)row_columns_);
+                const int rc = src_->poll_rows(m, p.rows.data(), cap, &n, &batch, wait);
+                if (rc == SDR_ERR_BAD_SIZE && attempt == 0) {
+                    p.rows.resize((size_t)n * (size_t)row_columns_);
+                    continue;
+                }
+                if (rc != SDR_OK)
+                    return rc;
+                p.n_rows = n;
+                p.rows.resize((size_t)n * (size_t)row_columns_);
+                break;
+            }
+        }
         for (int attempt = 0; attempt < 4; attempt++) {
             p.bind();
             const int rc = peaks ? src_->poll_peaks(m, &p.r, wait) : src_->poll(m, &p.r, wait);
@@ -260,6 +343,7 @@ private:
     GroupRouting rt_;
     std::mutex mu_, peek_mu_;
     bool on_ = false;
+    int row_columns_ = 0;
     std::vector<MemberBatch> parked_, peeked_;
 };
 

@@ -769,6 +769,90 @@ __global__ __launch_bounds__(256) void k_bound_finish(float *__restrict__ cum_ou
     cum_out[at] = gomath::cum_bound(c0, units, len, a128, per_frame, special);
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_cum_rows — waterfall rows (sdr_enable_rows / sdr_poll_rows): every cumulation the batch completes, exact in EVERY bin,
+// reduced to `columns` values - per group of G = n / columns neighbouring bins the result of the literal loop
+//     m = cum[j G];  for k in 1 .. G - 1: v = cum[j G + k]; if (v > m) m = v;
+// (a group whose first bin is NaN gives that NaN, any other the first maximum of its non-NaN values) - and written straight
+// into the batch's row block of pinned host memory: row (band, chunk) at ((band * chunks completed) + chunk) * columns, the
+// order of sdr_results.chunks.  No n-wide row goes to memory.
+// A bin's cumulation is k_cumulate's: the carry the chunk started from, then cum_exact_column over its frames - one
+// thread per bin, lanes on neighbouring bins (a wave reads 256 contiguous bytes of one frame per instruction).  The group
+// maximum is the loop's in any grouping as long as a NaN counts as -inf everywhere but in the group's first bin and the
+// LEFT operand wins a tie (`other > m`, never `>=`): up to 64 bins it is a shuffle ladder inside the wave (lane i takes
+// lane i + o: the left operand is always the lower bins), above that the waves' results meet in LDS, and a group wider
+// than the workgroup's 256 bins (G = 512, 1024) has its workgroup walk G / 256 blocks of bins.
+// Work: one more pass over the batch's psd (4 bytes per sample) and the certified dB projection of every value.
+// ---------------------------------------------------------------------------------------------
+constexpr int kRowsThreads = 256, kRowsMaxGroup = 1024;
+__global__ __launch_bounds__(kRowsThreads) void k_cum_rows(const float *__restrict__ psd, const void *__restrict__ db_tab,
+                                                           const float *__restrict__ carry0, const float *__restrict__ carry1, int carry_in_arg,
+                                                           const BatchCursor *__restrict__ cur, CumGeom g, int columns, double inv_n2,
+                                                           float *__restrict__ rows)
+{
+    int carry_sel = carry_in_arg;
+    if (cur) {  // graph replay: this batch's cumulation phase comes from device memory
+        g.count0 = cur->count0;
+        carry_sel = cur->carry_in;
+    }
+    const int chunk = blockIdx.y, band = blockIdx.z, tid = threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n_done = chunks_completed(g.count0, g.n_frames);
+    if (chunk >= n_done || n_done > g.max_chunks)  // (workgroup-uniform; the row block holds max_chunks rows per band)
+        return;
+    __shared__ __attribute__((aligned(16))) unsigned char s_tab[gomath::kDbTabBytes];
+    __shared__ float s_max[kRowsMaxGroup / 64], s_first[kRowsMaxGroup / 64];  // per wave and block of bins: its maximum, its first bin
+    {
+        const uint4 *src = static_cast<const uint4 *>(db_tab);
+        uint4 *dst = reinterpret_cast<uint4 *>(s_tab);
+        for (int i = tid; i < gomath::kDbTabBytes / 16; i += kRowsThreads)
+            dst[i] = src[i];
+    }
+    __syncthreads();
+    const gomath::DbTables tab = gomath::db_tables(s_tab);
+    const int n = g.n, G = n / columns;
+    const int W = G > kRowsThreads ? G : kRowsThreads;  // bins of this workgroup: whole groups
+    int begin, len;
+    cum_slot_frames(chunk, g.count0, &begin, &len);
+    const float *__restrict__ carry_in = carry_sel ? carry1 : carry0;
+    const float *__restrict__ base = psd + (size_t)band * g.stride * n;
+    float *__restrict__ row = rows + ((size_t)band * n_done + chunk) * columns;
+    for (int blk = 0; blk < W / kRowsThreads; blk++) {
+        const int bin = blockIdx.x * W + blk * kRowsThreads + tid;
+        float acc = 0.f;
+        if (chunk == 0 && g.count0 > 0)
+            acc = carry_in[(size_t)band * n + bin];
+        acc = cum_exact_column(base, (unsigned)begin * (unsigned)n + (unsigned)bin, (unsigned)n, len, acc, tab, inv_n2);
+        float m = __builtin_isnan(acc) ? -__builtin_inff() : acc;
+        const int span = G < 64 ? G : 64;
+        for (int o = 1; o < span; o <<= 1) {  // (a group's first lane never reads beyond its group)
+            const float other = __shfl_down(m, o);
+            if (other > m)
+                m = other;
+        }
+        if (G <= 64) {
+            if ((lane & (G - 1)) == 0)
+                row[bin / G] = __builtin_isnan(acc) ? acc : m;
+        } else if (lane == 0) {
+            s_max[blk * (kRowsThreads / 64) + wave] = m;
+            s_first[blk * (kRowsThreads / 64) + wave] = acc;
+        }
+    }
+    if (G > 64) {
+        __syncthreads();
+        const int waves = G >> 6;  // wave results per group, in bin order
+        if (tid < W / G) {
+            const float first = s_first[tid * waves];
+            float m = s_max[tid * waves];
+            for (int k = 1; k < waves; k++) {
+                const float v = s_max[tid * waves + k];
+                if (v > m)
+                    m = v;
+            }
+            row[blockIdx.x * (W / G) + tid] = __builtin_isnan(first) ? first : m;
+        }
+    }
+}
+
 // One batch's cumulation work, on `stream`: bounds of the cumulations it completes, the exact carry of the one it leaves
 // open.  (A stage event armed by the caller rides on the last launch.)
 hipError_t launch_cumulate(const float *psd, const void *db_tab, float *carry0, float *carry1, int carry_in, float *cum_out,
@@ -810,6 +894,22 @@ hipError_t launch_cumulate(const float *psd, const void *db_tab, float *carry0, 
     t_done_event = done;
     launch_kernel(k_cumulate, dim3((g.n + threads - 1) / threads, 1, n_bands), dim3(threads), 0, stream, psd, db_tab, carry0, carry1, carry_in,
                   cum_out, static_cast<float *>(nullptr), cur, g, 1, 0, inv_n2);
+    return hipGetLastError();
+}
+
+// the waterfall rows of the cumulations a batch completes, `columns` values each, into `rows` (pinned host memory):
+// n_chunks = the most the launch can meet (a replay decides by its cursor)
+hipError_t launch_cum_rows(const float *psd, const void *db_tab, const float *carry0, const float *carry1, int carry_in, const BatchCursor *cur,
+                           CumGeom g, int columns, int n_chunks, int n_bands, float *rows, hipStream_t stream)
+{
+    if (n_chunks <= 0)
+        return hipSuccess;
+    if (columns < 64 || columns > g.n || (columns & (columns - 1)) || g.n / columns > kRowsMaxGroup || g.n % kRowsThreads)
+        return hipErrorInvalidValue;
+    const int G = g.n / columns, W = G > kRowsThreads ? G : kRowsThreads;
+    const double inv_n2 = 1.0 / ((double)g.n * (double)g.n);
+    hipLaunchKernelGGL(k_cum_rows, dim3(g.n / W, n_chunks, n_bands), dim3(kRowsThreads), 0, stream, psd, db_tab, carry0, carry1, carry_in, cur, g,
+                       columns, inv_n2, rows);
     return hipGetLastError();
 }
 

@@ -254,6 +254,9 @@ hipError_t launch_unpack_sc16(const int16_t *raw, float *out, size_t n_values, h
 hipError_t launch_find_peaks(float *cum, const float *psd, const void *db_tab, const float *carry0, const float *carry1, int carry_in,
                              const sdr_frame_rec *recs, DevPeak *peaks, int *counts, const BatchCursor *cur, PeakGeom g, int n_frames,
                              int n_chunks, int n_bands, Refine refine, FftTap tap, hipStream_t stream);  // tap: .wide / .used / .n / .stride of this batch's FFT (or null)
+// k_cum_rows: every cumulation the batch completes, exact and reduced to `columns` group maxima, into the row block
+hipError_t launch_cum_rows(const float *psd, const void *db_tab, const float *carry0, const float *carry1, int carry_in, const BatchCursor *cur,
+                           CumGeom g, int columns, int n_chunks, int n_bands, float *rows, hipStream_t stream);
 hipError_t launch_cumulation_row(const float *psd_band, const void *db_tab, const float *carry_in_band, float *row_out, CumGeom g, int slot,
                                  hipStream_t stream);
 
