@@ -81,9 +81,7 @@ inline int ilog2(int n)
 inline const char *const kKernelNames[sdr::K_PROFILE_COUNT] = {"k_fft_psd",       "k_window_means", "k_noise_stats", "k_thresholds",
                                           "k_listen_gather", "k_cumulate",     "k_find_peaks",  "k_listen_decode", "k_cum_rows"};
 
-// graph mode records the four streams' kernels plus, as a graph of its own in front of the peaks stream's, the thresholds
-// (the listen graph starts behind them, not behind the cumulations)
-constexpr int G_THRESHOLDS = 4, N_GRAPHS = 5;
+using sdr::G_THRESHOLDS, sdr::N_GRAPHS;  // graph mode's graphs: one per stream and the thresholds' (host/batch_plan.h in_graph)
 constexpr int GRAPH_PHASES = 4;  // graph mode: replays in flight, each with RING buffer sets of its own (sdr_graph_capture)
 constexpr int RING = 6;  // per-batch buffer sets in flight (a batch lives about four FFT launches from its FFT to its last result)
 using sdr::S_FFT, sdr::S_NOISE, sdr::S_LISTEN, sdr::S_PEAKS, sdr::N_STAGES;  // the bank's streams (host/batch_plan.h)

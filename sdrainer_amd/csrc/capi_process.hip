@@ -11,11 +11,18 @@
 //   listen  k_listen_gather(i) -> k_listen_decode(i) (-> k_pack_listen(i))
 //
 // Batch i's per-batch buffers (psd, tap, frame records, keying bits, peaks ...) live in set i % RING, and one event per
-// kernel orders the stages across streams (kDefaultPlan, process_device_body): window means and cumulate after the FFT;
-// thresholds after the noise statistics; gather after thresholds; find_peaks after cumulate and thresholds; fft(i) after
-// every reader of set i % RING from batch i - RING.  State that is carried from frame to frame is only ever touched by one
-// kernel, whose stream keeps it in batch order.  Results leave the device in bulk (capi_results.hip) or are read after
-// sdr_sync(), which drains every stream (capi_read.hip).
+// stage orders the stages across streams.  Which stream a stage runs on, who waits for whom, which stage stands for its
+// stream when fft(i) waits for every reader of set i % RING from batch i - RING, and which graph a kernel belongs to under
+// capture are the plan's (host/batch_plan.h: plan_batch, stage_deps, set_reuse_stages, in_graph); this file applies them.
+// State that is carried from frame to frame is only ever touched by one kernel, whose stream keeps it in batch order.
+// Results leave the device in bulk (capi_results.hip) or are read after sdr_sync(), which drains every stream
+// (capi_read.hip).
+//
+// process_device_body enqueues every batch: it prepares a BatchIssue (the bank, the batch's buffer set and plan, whether
+// and for which graph a capture is recording) and runs the parts asked for - the spectral half (issue_spectra), the listen
+// half (issue_listen), cumulation and peaks (issue_cumulation) - then commits the host's state (commit_batch).
+// BatchIssue::stage is the one place that launches a stage's kernel and publishes its event: the event is an argument of
+// the launcher (sdr::LaunchAt, sdr_device.h), which attaches it to its last kernel.
 //
 // The same body is driven three more ways: recorded into graphs (capi_graph.hip: capture_k / capture_stage), as the
 // deferred listen half (sdr_defer_listen ...: the spectral stages of a batch first, listeners bound to frames inside it,
@@ -56,7 +63,7 @@ __global__ void k_put_bins(int32_t *bins, BinPack p)
 }
 
 // The listeners bound by sdr_attach_at since the last flush, to the device: their slots on the listen stream (where the
-// decoder, which carries their state, runs; a gather on another stream waits for slots_put_ev - process_device_body),
+// decoder, which carries their state, runs; a gather on another stream waits for slots_put_ev - issue_listen),
 // their tap bins on the FFT stream (read by the next FFT) - a handful of launches whatever their
 // number, and no synchronous copy.
 int flush_late_attached(sdr_bank *b)
@@ -109,13 +116,361 @@ int process_device_impl(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
     return rc;
 }
 
-// capture_stage: while capturing, ONE stream records at a time (sdr_graph_capture walks the batches once per stream):
-// only the kernels of that stream are issued, everything else of the batch is skipped in that walk, and NO event is
-// recorded or waited for - what orders the streams of a replay are events around whole graphs (sdr_graph_launch).
-// capture_k >= 0: the call is being recorded into a graph as its batch number capture_k (sdr_graph_capture).  Then
-// the batch uses buffer set RING + capture_k, everything that differs from batch to batch comes from the device-side
-// cursor of that number instead of the launch parameters, grids cover the most chunks a batch of this length can
-// complete, nothing is asked of the host (no event queries, no profiling, no parking) and no host state changes.
+namespace {
+
+// One batch being enqueued: what it runs on (the bank, its buffer set, its plan), whether a capture is recording and which
+// graph, and the batch's numbers - built by prepare_batch, read by the parts of process_device_body.  Its methods are the
+// only place where a stage's waits, its kernel and its event are issued.
+struct BatchIssue {
+    sdr_bank *b;
+    BatchSet *S;
+    host::ResultSet *RS;  // (its block and events exist once bulk delivery is on)
+    sdr::BatchPlan P;     // every choice of this batch (host/batch_plan.h) ...
+    sdr::StageDeps deps;  // ... and who waits for whom
+    // cap: the call is being recorded into graph `graph` (a stream's, or G_THRESHOLDS) as one batch of a replay.  Only the
+    // kernels of that graph are issued, and NO event is recorded, waited for or queried - what orders the streams of a
+    // replay are events around whole graphs (sdr_graph_launch).  cur: that batch's device-side cursor (else null).
+    bool cap;
+    int graph;
+    int capture_k;
+    sdr::BatchCursor *cur;
+    int si, n_frames, max_slots, count0;
+    int64_t first_frame;
+    bool do_listen;
+    sdr::CumGeom cg;
+
+    // is kernel k part of the graph that is recording (always, outside a capture)?
+    bool on(int k) const { return !cap || sdr::in_graph(P, k, graph); }
+    hipStream_t stream(int k) const { return b->stream[P.stream[k]]; }
+    // where stage k's last kernel goes: its stream and, outside a capture, the stage's event on the kernel's own dispatch
+    sdr::LaunchAt at(int k) const { return sdr::LaunchAt(stream(k), cap ? nullptr : S->done[k]); }
+    // stage k of this batch may start once stage `dep` of this batch is done (nothing to do on the same stream: under
+    // SDR_NO_OVERLAP every stage's is the caller's)
+    int wait(int k, int dep) const
+    {
+        if (!cap && stream(k) != stream(dep))
+            HIP_TRY(hipStreamWaitEvent(stream(k), S->done[dep], 0));
+        return SDR_OK;
+    }
+    // ... once every stage the plan orders it behind is
+    int wait_deps(int k) const
+    {
+        for (int i = 0; i < deps.n; i++)
+            if (deps.d[i].k == k)
+                if (const int rc = wait(k, deps.d[i].dep))
+                    return rc;
+        return SDR_OK;
+    }
+    // stage k's event the ordinary way, where no kernel carries it
+    int record(int k) const
+    {
+        if (!cap)
+            HIP_TRY(hipEventRecord(S->done[k], stream(k)));
+        return SDR_OK;
+    }
+    bool skipped(int k) const
+    {
+#if defined(SDR_DIAG)
+        return (b->sw.diag_skip >> k & 1) != 0;
+#else
+        (void)k;
+        return false;
+#endif
+    }
+    // Stage k.  LAUNCH: `launch`, one launcher call, runs inside the stage's profile scope if the stage is on (and, in
+    // -DSDR_DIAG builds, not skipped).  SCOPE_ONLY: the stage has a scope but no kernel of its own.  LEFT_OUT: neither.
+    // carries: the launcher's last kernel takes the stage's event (else a plain launch: a kernel behind it, issued by the
+    // caller, carries the event).  A stage that carries and launched nothing records its event the ordinary way: a stage
+    // left out must still publish it - the set-reuse wait reads the last stage of each stream.
+    enum Run { LAUNCH, SCOPE_ONLY, LEFT_OUT };
+    template <class L>
+    int stage(int k, Run how, bool carries, L &&launch) const
+    {
+        bool taken = false;
+        if (how != LEFT_OUT) {
+            ProfScope ps(b, k, stream(k));
+            if (how == LAUNCH && on(k) && !skipped(k)) {
+                const hipError_t e = launch(carries ? at(k) : sdr::LaunchAt(stream(k)));
+                if (e != hipSuccess)
+                    return fail(SDR_ERR_HIP, std::string("launch of stage ") + kKernelNames[k] + ": " + hipGetErrorString(e));
+                taken = carries;
+            }
+        }
+        return carries && !taken ? record(k) : SDR_OK;
+    }
+};
+
+// capture_k >= 0: the batch is being recorded into a graph as its batch number capture_k (sdr_graph_capture).  Then it
+// uses buffer set RING + capture_k, everything that differs from batch to batch comes from the device-side cursor of that
+// number instead of the launch parameters and grids cover the most chunks a batch of this length can complete.
+// Without PART_SPECTRA (the later listen half) set and first frame are the pending batch's (b->pend).
+BatchIssue prepare_batch(sdr_bank *b, int n_frames, int capture_k, int capture_stage, bool do_spectra, bool do_listen)
+{
+    const sdr_config &c = b->cfg;
+    BatchIssue is;
+    is.b = b;
+    is.cap = capture_k >= 0;
+    is.graph = capture_stage;
+    is.capture_k = capture_k;
+    is.cur = is.cap ? b->cursors.p + capture_k : nullptr;
+    is.si = is.cap ? RING + capture_k : do_spectra ? (int)(b->batch_index % RING) : b->pend.set;  // (capture: the sets sdr_graph_capture added)
+    is.S = &b->set[is.si];
+    is.RS = &b->results->set(is.si);
+    is.n_frames = n_frames;
+    is.first_frame = do_spectra ? b->total_frames : b->pend.first_frame;
+    is.do_listen = do_listen;
+    is.max_slots = 0;
+    for (int i = 0; i < c.n_bands; i++)
+        is.max_slots = std::max(is.max_slots, b->n_slots[i]);
+    is.count0 = b->cum_count;
+    is.P = sdr::plan_batch(b->sw, sdr::BatchGeometry{c.n_bands, c.block_size, c.max_batch_frames, b->max_chunks, b->fft_queue_alone}, n_frames, is.count0,
+                           is.cap, is.max_slots, b->windowed, b->results_on ? b->row_columns : 0);
+    is.deps = sdr::stage_deps(is.P, b->find_peaks && is.P.n_chunks > 0);
+    is.cg = sdr::CumGeom{c.block_size, c.max_batch_frames, n_frames, is.count0, b->max_chunks};
+    return is;
+}
+
+// The spectral half: FFT + PSD + tap, noise floor, thresholds.
+int issue_spectra(const BatchIssue &is, const void *iq_dev, size_t in_stride, sdr::InFormat fmt)
+{
+    sdr_bank *b = is.b;
+    const sdr_config &c = b->cfg;
+    BatchSet &S = *is.S;
+    const sdr::BatchPlan &P = is.P;
+    const int B = c.n_bands, stride = c.max_batch_frames, n_frames = is.n_frames;
+    // The FFT writes the set once every reader of it (batch i - RING) is done with it.  Not under capture: inside a graph
+    // a set is used once per replay, and sdr_graph_launch waits for the earlier replay that used this phase's sets.
+    if (!is.cap) {
+        // With bulk delivery on, the set's previous batch must have been delivered (or be parked) before its block is
+        // written again - and a delivered batch is a finished one: every reader of the set is done, the queries below
+        // succeed and the FFT queue gets no barrier packets at all (each costs the command processor microseconds between
+        // two FFT kernels, and the FFT queue is the one that bounds the step).
+        if (b->results_on)
+            if (const int rc = b->results->park(is.si))
+                return rc;
+        // With RING sets the previous user is four batches back and has almost always finished: ask the host first, a
+        // barrier packet in the FFT queue costs the command processor tens of microseconds.
+        // A caller that enqueues faster than the GPU works is soon more than RING batches ahead; then these events have
+        // not happened yet at enqueue time and the FFT queue gets barrier packets: one per other stream (its last stage
+        // stands for the stream: set_reuse_stages), not one per stage - with nothing else running that was 0.200 -> 0.177
+        // ms per step for a 0.166 ms kernel.  (The host waiting instead - the call blocking until the set is free, the FFT
+        // queue holding kernels only - was 0.161 ms with nothing else running, but 0.237 against 0.234 with the whole
+        // pipeline, where the FFT launches are spaced by the CUs the tail holds, not by their queue.)
+        int stands_for[N_STAGES];
+        sdr::set_reuse_stages(P, stands_for);
+        for (int k : stands_for)
+            if (k >= 0 && hipEventQuery(S.done[k]) != hipSuccess)
+                HIP_TRY(hipStreamWaitEvent(is.stream(sdr::K_FFT), S.done[k], 0));
+    }
+    if (is.cap && is.on(sdr::K_FFT) && is.capture_k % RING == 0)  // the replay's cursors, in front of its first FFT
+        HIP_TRY(launch_set_cursors(is.cur, CursorPack{}, is.stream(sdr::K_FFT)));
+    sdr::FftTap tap{b->tap_bins.p, S.tap.p, is.max_slots, c.max_listeners};
+    tap.wide = S.tapw.p;
+    tap.used = S.tap_used.p;
+    tap.steal = S.fft_ctr.p;
+    tap.scratch = S.fft_scratch.p;
+    tap.window = b->windowed ? b->window.p : nullptr;
+    // (n_frames > 0, process_device_body: launch_fft and launch_psd_scan launch nothing for an empty batch and would leave
+    // the event they are given unrecorded)
+    int rc = is.stage(sdr::K_FFT, BatchIssue::LAUNCH, true, [&](sdr::LaunchAt at) {
+        return sdr::launch_fft(b->logn, P.fft, fmt, iq_dev, is.cur, b->tw.p, S.psd.p, n_frames, B, in_stride, b->hop, stride, tap, at);
+    });
+    if (rc)
+        return rc;
+
+    // noise floor (stateless per batch), then the rolling means -> thresholds, in batch order.  Two ways:
+    //   scan    k_noise_scan.hip: ONE pass over the psd for FindNoiseFloor's sums and - where it pays - the bounds of the
+    //           cumulations the batch completes; the reference's values where they are consumed (noise_cert.h), the
+    //           literal loops for the few frames that cannot be certified;
+    //   chains  k_noise.hip: the ordered float64 chains of rounds 1-4 (and k_cum_bound on the peaks stream).
+    const sdr::NoiseGeom ng = b->noise_geom();
+    if ((rc = is.wait_deps(sdr::K_WINDOW_MEANS)))
+        return rc;
+    rc = is.stage(sdr::K_WINDOW_MEANS, BatchIssue::LAUNCH, true, [&](sdr::LaunchAt at) {
+        if (P.noise_scan)
+            return sdr::launch_psd_scan(S.psd.p, S.recs.p, S.cum_out.p, S.cum_part.p, is.cur, ng, is.cg, P.n_slots, B, P.bound_done, P.scan_parts,
+                                        P.force_exact, at);
+        return sdr::launch_window_means(S.psd.p, S.win_mean.p, ng, n_frames, B, stride, P.wm_wpb, at);
+    });
+    if (rc || (rc = is.wait_deps(sdr::K_NOISE_STATS)))
+        return rc;
+    // (the scan kernel has finished the records itself: then this stage launches nothing and its event is recorded)
+    rc = is.stage(sdr::K_NOISE_STATS, P.noise_scan ? BatchIssue::SCOPE_ONLY : BatchIssue::LAUNCH, true, [&](sdr::LaunchAt at) {
+        return sdr::launch_noise_stats(S.psd.p, S.win_mean.p, S.recs.p, ng, n_frames, B, stride, P.var_mfma, at);
+    });
+    if (rc || (rc = is.wait_deps(sdr::K_THRESHOLDS)))
+        return rc;
+    return is.stage(sdr::K_THRESHOLDS, BatchIssue::LAUNCH, true,
+                    [&](sdr::LaunchAt at) { return sdr::launch_thresholds(S.recs.p, b->band_state.p, n_frames, B, stride, at); });
+}
+
+// The listen half: per-signal envelope + decoder, and their delivery.
+int issue_listen(const BatchIssue &is)
+{
+    sdr_bank *b = is.b;
+    const sdr_config &c = b->cfg;
+    BatchSet &S = *is.S;
+    const int B = c.n_bands, n_frames = is.n_frames, max_slots = is.max_slots;
+    const BatchIssue::Run run = max_slots > 0 ? BatchIssue::LAUNCH : BatchIssue::LEFT_OUT;
+    sdr::ListenGeom lg;
+    lg.n = c.block_size;
+    lg.stride = c.max_batch_frames;
+    lg.max_listeners = c.max_listeners;
+    lg.text_cap = b->text_cap;
+    lg.edge_cap = b->edge_cap;
+    lg.bit_words = b->bit_words;
+    lg.trace = c.trace;
+    lg.frame_base = (uint32_t)is.first_frame;
+    int rc = is.wait_deps(sdr::K_LISTEN_GATHER);
+    if (rc)
+        return rc;
+    // Slots of listeners bound by sdr_attach_at: the gather reads a slot's active, bin, start_frame and tapped_from, and
+    // k_put_slots writes them word by word on the listen stream (flush_late_attached, this call's or an earlier one's).
+    // The waits above say nothing about that stream, and the listen stream of a small plan runs a batch or more behind
+    // the peaks stream, so a gather elsewhere waits for the last put until the host has seen it complete.  The other slot
+    // writers on the listen stream need no such wait: k_set_debounce writes deb.threshold, k_listener_stop dec /
+    // text_count / text_dropped, and k_listen_decode of the batch before moves start_frame and tapped_from of a listener
+    // that has started from a frame at or before that batch's first to this batch's first - old or new, the gather
+    // skips no frame and reads every one from the tap; sdr_attach and sdr_detach write slots only after sync_bank has
+    // drained every stream.
+    if (!is.cap && b->slots_put) {
+        if (hipEventQuery(b->slots_put_ev) == hipSuccess)
+            b->slots_put = false;
+        else if (is.P.stream[sdr::K_LISTEN_GATHER] != S_LISTEN)
+            HIP_TRY(hipStreamWaitEvent(is.stream(sdr::K_LISTEN_GATHER), b->slots_put_ev, 0));
+    }
+    rc = is.stage(sdr::K_LISTEN_GATHER, run, true, [&](sdr::LaunchAt at) {
+        return sdr::launch_listen_gather(S.tap.p, S.psd.p, S.recs.p, b->slots.p, b->db_tab.p, S.raw_bits.p, S.tr_values.p, S.tr_raw.p, is.cur, lg, n_frames,
+                                         max_slots, B, at);
+    });
+    if (rc || (rc = is.wait_deps(sdr::K_LISTEN_DECODE)))
+        return rc;
+    if (c.trace && max_slots > 0 && is.on(sdr::K_LISTEN_DECODE))  // the decoders' state before this batch: the decoder scope replays from it
+        HIP_TRY(hipMemcpyAsync(S.slots_before.p, b->slots.p, sizeof(sdr::ListenerSlot) * (size_t)B * (size_t)c.max_listeners, hipMemcpyDeviceToDevice,
+                               is.stream(sdr::K_LISTEN_DECODE)));
+    // (with bulk delivery the stage's event rides on the pack kernel below, not on the decoder)
+    rc = is.stage(sdr::K_LISTEN_DECODE, run, !b->results_on, [&](sdr::LaunchAt at) {
+        return sdr::launch_listen_decode(b->slots.p, b->morse.p, S.raw_bits.p, S.bits.p, b->text.p, b->text_frames.p, S.edges.p, S.edge_counts.p, S.tr_deb.p,
+                                         b->drops.p, is.cur, lg, n_frames, B, b->edge_pos.p, c.max_batch_frames, at);
+    });
+    if (rc)
+        return rc;
+    if (b->results_on && is.on(sdr::K_LISTEN_DECODE)) {
+        // delivery of this batch's edges and runes, behind the decoder on its stream; the decoder's event is
+        // recorded behind it so that the set is not reused before the copy to the host has happened
+        HIP_TRY(sdr::launch_pack_listen(b->slots.p, S.edges.p, S.edge_counts.p, b->text.p, b->text_frames.p, b->drops.p, b->res_layout, max_slots, B,
+                                        is.RS->block, is.at(sdr::K_LISTEN_DECODE)));
+        if (!is.cap)  // (a replay records it behind the listen graph)
+            HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(is.RS->ev_listen), is.stream(sdr::K_LISTEN_DECODE)));
+    }
+    return SDR_OK;
+}
+
+// dB projection + cumulation, peak scan (rx/receiver.go:404-409,459-460), the waterfall rows and their delivery.
+int issue_cumulation(const BatchIssue &is)
+{
+    sdr_bank *b = is.b;
+    const sdr_config &c = b->cfg;
+    BatchSet &S = *is.S;
+    const sdr::BatchPlan &P = is.P;
+    const int B = c.n_bands, n_frames = is.n_frames, n_chunks = P.n_chunks;
+    // (the scan wrote the bounds of the completed cumulations on the noise stream: the carry is added to slot 0's here)
+    int rc = is.wait_deps(sdr::K_CUMULATE);
+    if (rc)
+        return rc;
+    rc = is.stage(sdr::K_CUMULATE, BatchIssue::LAUNCH, true, [&](sdr::LaunchAt at) {
+        return sdr::launch_cumulate(S.psd.p, b->db_tab.p, b->carry[0].p, b->carry[1].p, b->carry_cur, S.cum_out.p, S.cum_part.p, is.cur, is.cg, P.n_slots, B,
+                                    P.bound, P.bound_done, P.scan_parts, at);
+    });
+    if (rc || (rc = is.wait_deps(sdr::K_FIND_PEAKS)))
+        return rc;
+    // (n_chunks > 0: launch_find_peaks launches nothing without a completed cumulation and would leave its event unrecorded;
+    // with bulk delivery the stage's event rides on the pack kernel below)
+    const bool peak_scan = b->find_peaks && n_chunks > 0;
+    rc = is.stage(sdr::K_FIND_PEAKS, peak_scan ? BatchIssue::LAUNCH : BatchIssue::LEFT_OUT, !b->results_on, [&](sdr::LaunchAt at) {
+        sdr::PeakGeom pg{c.block_size, c.max_batch_frames, is.count0, b->max_chunks, c.max_peaks};
+        // (reads the carry buffer this batch's cumulation started from: the next batch's k_cumulate, which writes that
+        // buffer, follows on the same stream)
+        // the wide tap this batch's FFT left, if it was the kernel that leaves one (k_cum_refine reads the signals' columns there)
+        sdr::FftTap wide_tap{nullptr, nullptr, is.max_slots, c.max_listeners};
+        if (P.fft.wide_tap) {
+            wide_tap.wide = S.tapw.p;
+            wide_tap.used = S.tap_used.p;
+        }
+        return sdr::launch_find_peaks(S.cum_out.p, S.psd.p, b->db_tab.p, b->carry[0].p, b->carry[1].p, b->carry_cur, S.recs.p, S.dev_peaks.p,
+                                      S.peak_counts.p, is.cur, pg, n_frames, n_chunks, B, P.refine, wide_tap, at);
+    });
+    if (rc)
+        return rc;
+    if (!is.on(sdr::K_FIND_PEAKS))
+        return SDR_OK;
+    // the waterfall rows of the completed cumulations, straight into the set's row block: behind the cumulate step on the
+    // find-peaks stage's stream, in front of the event sdr_poll looks at (recorded behind the pack kernel below)
+    if (P.rows) {
+        ProfScope ps(b, sdr::K_CUM_ROWS, b->stream[P.rows_stream]);
+        HIP_TRY(sdr::launch_cum_rows(S.psd.p, b->db_tab.p, b->carry[0].p, b->carry[1].p, b->carry_cur, is.cur, is.cg, b->row_columns, n_chunks, B, is.RS->rows,
+                                     b->stream[P.rows_stream]));
+    }
+    if (!b->results_on)
+        return SDR_OK;
+    // delivery of this batch's peaks, with the stage's event.  launch_pack_peaks launches nothing for a batch that completes
+    // no cumulation: then the event is recorded the ordinary way, at the end
+    if (n_chunks > 0)
+        HIP_TRY(sdr::launch_pack_peaks(S.dev_peaks.p, S.peak_counts.p, is.cur, b->res_layout, b->find_peaks, n_frames, n_chunks, B, is.RS->block,
+                                       is.at(sdr::K_FIND_PEAKS)));
+    if (!is.cap) {
+        HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(is.RS->ev_peaks), is.stream(sdr::K_FIND_PEAKS)));
+        host::BatchMeta m;
+        m.batch = b->batch_index;
+        m.first_frame = b->total_frames;
+        m.frames = n_frames;
+        m.chunks = n_chunks;
+        m.count0 = is.count0;
+        m.slots = is.do_listen ? is.max_slots : 0;  // (sdr_poll_peaks delivers the spectral half; the listen half fills this in)
+        m.row_columns = P.rows ? b->row_columns : 0;
+        m.rows = P.rows ? n_chunks * B : 0;
+        {
+            std::lock_guard<std::mutex> guard(b->center_mu);
+            m.center = b->center_frequency;
+        }
+        b->results->publish(is.si, std::move(m), is.do_listen);
+    }
+    return n_chunks > 0 ? SDR_OK : is.record(sdr::K_FIND_PEAKS);
+}
+
+// Every launch of the batch is enqueued: commit the host's view of the carried state in one go.
+// The carry buffer flips only when this batch wrote a new partial cumulation; if the batch ended
+// exactly on a chunk boundary the next batch starts from zero (count0 == 0 ignores the carry)
+void commit_batch(const BatchIssue &is)
+{
+    sdr_bank *b = is.b;
+    b->last_carry_in = b->carry_cur;
+    if (is.P.new_count != 0)
+        b->carry_cur ^= 1;
+    b->cum_count = is.P.new_count;
+    b->last_set = is.si;
+    b->last_frames = is.n_frames;
+    b->last_chunks = is.P.n_chunks;
+    b->last_count0 = is.count0;
+    if (!is.do_listen) {
+        b->pend.set = is.si;
+        b->pend.frames = is.n_frames;
+        b->pend.first_frame = b->total_frames;
+        b->pend.batch = b->batch_index;
+        b->listen_pending = true;
+    }
+    b->total_frames += is.n_frames;
+    b->batch_index++;
+    if (!b->results_on)
+        b->results->note_enqueued(b->batch_index);
+}
+
+}  // namespace
+
+// One batch, or the parts of it that `parts` names.  capture_k >= 0 / capture_stage: the call is being recorded into the
+// graph of stream capture_stage (or G_THRESHOLDS) as batch capture_k of a replay (sdr_graph_capture walks the batches once
+// per graph; see BatchIssue::cap): nothing is asked of the host (no event queries, no profiling, no parking, no late-attach
+// flush) and no host state changes.
 // parts: PART_SPECTRA leaves the batch's listeners for a later PART_LISTEN call (sdr_defer_listen / sdr_process_listen:
 // the host binds listeners to peaks of this very batch in between, rx/receiver.go:409-426); the later call takes the
 // batch's set, length and first frame from b->pend.
@@ -126,332 +481,30 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
     const bool do_spectra = (parts & PART_SPECTRA) != 0, do_listen = (parts & PART_LISTEN) != 0;
     if (!do_spectra)
         n_frames = b->pend.frames;
-    const sdr::BatchCursor *cur = cap ? b->cursors.p + capture_k : nullptr;
-    const sdr_config &c = b->cfg;
-    if (n_frames <= 0)
+    if (n_frames <= 0)  // (no launcher is ever called for an empty batch)
         return SDR_OK;
-    // an armed stage event must never outlive this call (an error return between SDR_ARM and the launch would
-    // otherwise hand it to the next kernel this thread launches, possibly on another bank)
-    struct DisarmOnExit {
-        ~DisarmOnExit() { sdr::t_done_event = nullptr; }
-    } disarm_on_exit;
-    if (n_frames > c.max_batch_frames)
+    if (n_frames > b->cfg.max_batch_frames)
         return fail(SDR_ERR_BAD_ARG, "n_frames exceeds max_batch_frames");
     HIP_TRY(hipSetDevice(b->device));
-    if (!cap) {
-        const int frc = flush_late_attached(b);
-        if (frc)
-            return frc;
-    }
-    const int B = c.n_bands, N = c.block_size, stride = c.max_batch_frames;
-    const sdr::NoiseGeom ng = b->noise_geom();
-    const int si = cap ? RING + capture_k : do_spectra ? (int)(b->batch_index % RING) : b->pend.set;  // (capture: the sets sdr_graph_capture added)
-    const int64_t first_frame = do_spectra ? b->total_frames : b->pend.first_frame;
-    BatchSet &S = b->set[si];
-    host::ResultSet &RS = b->results->set(si);  // (its block and events exist once bulk delivery is on)
-    int max_slots = 0;
-    for (int i = 0; i < B; i++)
-        max_slots = std::max(max_slots, b->n_slots[i]);
-    // every choice of this batch (host/batch_plan.h); a gather moved off the listen stream also waits for late-attached
-    // slots: see slots_put below
-    const int count0 = b->cum_count;
-    const sdr::BatchPlan P = sdr::plan_batch(b->sw, sdr::BatchGeometry{B, N, stride, b->max_chunks, b->fft_queue_alone}, n_frames, count0, cap, max_slots, b->windowed,
-                                                 b->results_on ? b->row_columns : 0);
-    const int *plan = P.stream;
-    const sdr::CumGeom cg{N, stride, n_frames, count0, b->max_chunks};
-    // is kernel k part of the graph that is recording (always, outside a capture)?
-#define SDR_ON(k) (!cap || (capture_stage == G_THRESHOLDS ? (k) == sdr::K_THRESHOLDS : (plan[k] == capture_stage && (k) != sdr::K_THRESHOLDS)))
-#if defined(SDR_DIAG)
-#define SDR_LAUNCH(id, call) \
-    do {                     \
-        if (!(b->sw.diag_skip >> (id) & 1) && SDR_ON(id)) \
-            HIP_TRY(call);   \
-    } while (0)
-#else
-#define SDR_LAUNCH(id, call)  \
-    do {                      \
-        if (SDR_ON(id))       \
-            HIP_TRY(call);    \
-    } while (0)
-#endif
-    auto stream_of = [&](int k) { return b->stream[plan[k]]; };
-    // kernel k of this batch may start once kernel `dep` of this batch is done (nothing to do on the same stream)
-    auto after = [&](int k, int dep) -> int {
-        if (stream_of(k) != stream_of(dep) && !cap)
-            HIP_TRY(hipStreamWaitEvent(stream_of(k), S.done[dep], 0));
-        return SDR_OK;
-    };
-#define SDR_AFTER(k, dep)          \
-    do {                           \
-        int _rc = after((k), (dep)); \
-        if (_rc)                   \
-            return _rc;            \
-    } while (0)
-    // A stage's event is recorded by its kernel's own dispatch (sdr::launch_kernel, sdr_device.h): SDR_ARM hands the
-    // event to the next launch, SDR_DONE records it the ordinary way if no launch took it (stage left out).  Under
-    // capture no event is recorded at all.
-#define SDR_ARM(k) (sdr::t_done_event = cap ? nullptr : S.done[k])
-#define SDR_DONE(k)                                                                                   \
-    do {                                                                                              \
-        if (sdr::t_done_event && !cap) {                                                              \
-            sdr::t_done_event = nullptr;                                                              \
-            HIP_TRY(hipEventRecord(S.done[k], stream_of(k)));                                         \
-        }                                                                                             \
-    } while (0)
-
-    // FFT + PSD + tap, once every reader of this set (batch i - RING) is done with it (with RING sets the
-    // previous user is four batches back and has almost always finished: ask the host first, a barrier packet in
-    // the FFT queue costs the command processor tens of microseconds)
-    // (inside a graph a set is used once per replay and replays are serialised by their stream)
-    // A caller that enqueues faster than the GPU works is soon more than RING batches ahead; then these events have
-    // not happened yet at enqueue time and the FFT queue gets barrier packets: one per other stream (its last stage
-    // stands for the stream), not one per stage - with nothing else running that was 0.200 -> 0.177 ms per step for a
-    // 0.166 ms kernel.  (The host waiting instead - the call blocking until the set is free, the FFT queue holding
-    // kernels only - was 0.161 ms with nothing else running, but 0.237 against 0.234 with the whole pipeline, where the
-    // FFT launches are spaced by the CUs the tail holds, not by their queue.)
-    if (do_spectra) {
-    // With bulk delivery on, the set's previous batch must have been delivered (or be parked) before its block is
-    // written again - and a delivered batch is a finished one: every reader of the set is done, the queries below
-    // succeed and the FFT queue gets no barrier packets at all (each costs the command processor microseconds between
-    // two FFT kernels, and the FFT queue is the one that bounds the step).
-    if (b->results_on && !cap) {
-        const int prc = b->results->park(si);
-        if (prc)
-            return prc;
-    }
-    {
-        // the last stage launched on a stream stands for all of that stream's
-        static const int launch_order[] = {sdr::K_WINDOW_MEANS, sdr::K_NOISE_STATS, sdr::K_THRESHOLDS, sdr::K_LISTEN_GATHER,
-                                           sdr::K_LISTEN_DECODE, sdr::K_CUMULATE,   sdr::K_FIND_PEAKS};
-        int last_on[N_STAGES];
-        for (int &l : last_on)
-            l = -1;
-        for (int k : launch_order)
-            last_on[plan[k]] = k;
-        for (int st = 0; st < N_STAGES; st++) {
-            const int k = last_on[st];
-            if (k < 0 || st == plan[sdr::K_FFT])
-                continue;
-            if (cap)  // (sdr_graph_launch waits for the earlier replay that used this phase's sets)
-                continue;
-            if (hipEventQuery(S.done[k]) == hipSuccess)
-                continue;
-            HIP_TRY(hipStreamWaitEvent(stream_of(sdr::K_FFT), S.done[k], 0));
-        }
-    }
-    if (cap && SDR_ON(sdr::K_FFT) && capture_k % RING == 0)  // the replay's cursors, in front of its first FFT
-        HIP_TRY(launch_set_cursors(b->cursors.p + capture_k, CursorPack{}, stream_of(sdr::K_FFT)));
-    {
-        ProfScope ps(b, sdr::K_FFT, stream_of(sdr::K_FFT));
-        SDR_ARM(sdr::K_FFT);
-        sdr::FftTap tap{b->tap_bins.p, S.tap.p, max_slots, c.max_listeners};
-        tap.wide = S.tapw.p;
-        tap.used = S.tap_used.p;
-        tap.steal = S.fft_ctr.p;
-        tap.scratch = S.fft_scratch.p;
-        tap.window = b->windowed ? b->window.p : nullptr;
-        SDR_LAUNCH(sdr::K_FFT, sdr::launch_fft(b->logn, P.fft, fmt, iq_dev, cur, b->tw.p, S.psd.p, n_frames, B, in_stride, b->hop, stride, tap,
-                                               stream_of(sdr::K_FFT)));
-    }
-    SDR_DONE(sdr::K_FFT);
-
-    // noise floor (stateless per batch), then the rolling means -> thresholds, in batch order.  Two ways:
-    //   scan    k_noise_scan.hip: ONE pass over the psd for FindNoiseFloor's sums and - where it pays - the bounds of the
-    //           cumulations the batch completes; the reference's values where they are consumed (noise_cert.h), the
-    //           literal loops for the few frames that cannot be certified;
-    //   chains  k_noise.hip: the ordered float64 chains of rounds 1-4 (and k_cum_bound on the peaks stream).
-    SDR_AFTER(sdr::K_WINDOW_MEANS, sdr::K_FFT);
-    {
-        ProfScope ps(b, sdr::K_WINDOW_MEANS, stream_of(sdr::K_WINDOW_MEANS));
-        SDR_ARM(sdr::K_WINDOW_MEANS);
-        if (P.noise_scan) {
-            SDR_LAUNCH(sdr::K_WINDOW_MEANS, sdr::launch_psd_scan(S.psd.p, S.recs.p, S.cum_out.p, S.cum_part.p, cur, ng, cg, P.n_slots, B, P.bound_done,
-                                                                 P.scan_parts, P.force_exact, stream_of(sdr::K_WINDOW_MEANS)));
-        } else {
-            SDR_LAUNCH(sdr::K_WINDOW_MEANS, sdr::launch_window_means(S.psd.p, S.win_mean.p, ng, n_frames, B, stride, P.wm_wpb,
-                                                                     stream_of(sdr::K_WINDOW_MEANS)));
-        }
-    }
-    SDR_DONE(sdr::K_WINDOW_MEANS);
-    SDR_AFTER(sdr::K_NOISE_STATS, sdr::K_WINDOW_MEANS);
-    {
-        ProfScope ps(b, sdr::K_NOISE_STATS, stream_of(sdr::K_NOISE_STATS));
-        SDR_ARM(sdr::K_NOISE_STATS);
-        if (!P.noise_scan)  // (the scan kernel has finished the records itself: this stage launches nothing, its event is recorded below)
-            SDR_LAUNCH(sdr::K_NOISE_STATS, sdr::launch_noise_stats(S.psd.p, S.win_mean.p, S.recs.p, ng, n_frames, B, stride, P.var_mfma,
-                                                                   stream_of(sdr::K_NOISE_STATS)));
-    }
-    SDR_DONE(sdr::K_NOISE_STATS);
-    SDR_AFTER(sdr::K_THRESHOLDS, sdr::K_NOISE_STATS);
-    {
-        ProfScope ps(b, sdr::K_THRESHOLDS, stream_of(sdr::K_THRESHOLDS));
-        SDR_ARM(sdr::K_THRESHOLDS);
-        SDR_LAUNCH(sdr::K_THRESHOLDS, sdr::launch_thresholds(S.recs.p, b->band_state.p, n_frames, B, stride,
-                                                             stream_of(sdr::K_THRESHOLDS)));
-    }
-    SDR_DONE(sdr::K_THRESHOLDS);
-    }  // do_spectra
-
-    // per-signal envelope + decoder
-    sdr::ListenGeom lg;
-    lg.n = N;
-    lg.stride = stride;
-    lg.max_listeners = c.max_listeners;
-    lg.text_cap = b->text_cap;
-    lg.edge_cap = b->edge_cap;
-    lg.bit_words = b->bit_words;
-    lg.trace = c.trace;
-    lg.frame_base = (uint32_t)first_frame;
-    if (do_listen) {
-    SDR_AFTER(sdr::K_LISTEN_GATHER, sdr::K_THRESHOLDS);
-    SDR_AFTER(sdr::K_LISTEN_GATHER, sdr::K_FFT);
-    // Slots of listeners bound by sdr_attach_at: the gather reads a slot's active, bin, start_frame and tapped_from, and
-    // k_put_slots writes them word by word on the listen stream (flush_late_attached, this call's or an earlier one's).
-    // The waits above say nothing about that stream, and the listen stream of a small plan runs a batch or more behind
-    // the peaks stream, so a gather elsewhere waits for the last put until the host has seen it complete.  The other slot
-    // writers on the listen stream need no such wait: k_set_debounce writes deb.threshold, k_listener_stop dec /
-    // text_count / text_dropped, and k_listen_decode of the batch before moves start_frame and tapped_from of a listener
-    // that has started from a frame at or before that batch's first to this batch's first - old or new, the gather
-    // skips no frame and reads every one from the tap; sdr_attach and sdr_detach write slots only after sync_bank has
-    // drained every stream.
-    if (!cap && b->slots_put) {
-        if (hipEventQuery(b->slots_put_ev) == hipSuccess)
-            b->slots_put = false;
-        else if (plan[sdr::K_LISTEN_GATHER] != S_LISTEN)
-            HIP_TRY(hipStreamWaitEvent(stream_of(sdr::K_LISTEN_GATHER), b->slots_put_ev, 0));
-    }
-    // (armed whether or not the stage launches: SDR_DONE records a stage event nobody took the ordinary way, and a
-    // stage left out must still publish its event - the set-reuse wait reads the last stage of each stream)
-    SDR_ARM(sdr::K_LISTEN_GATHER);
-    if (max_slots > 0) {
-        ProfScope ps(b, sdr::K_LISTEN_GATHER, stream_of(sdr::K_LISTEN_GATHER));
-        SDR_LAUNCH(sdr::K_LISTEN_GATHER, sdr::launch_listen_gather(S.tap.p, S.psd.p, S.recs.p, b->slots.p, b->db_tab.p, S.raw_bits.p, S.tr_values.p,
-                                                                   S.tr_raw.p, cur, lg, n_frames, max_slots, B,
-                                                                   stream_of(sdr::K_LISTEN_GATHER)));
-    }
-    SDR_DONE(sdr::K_LISTEN_GATHER);
-    SDR_AFTER(sdr::K_LISTEN_DECODE, sdr::K_LISTEN_GATHER);
-    if (c.trace && max_slots > 0 && SDR_ON(sdr::K_LISTEN_DECODE))  // the decoders' state before this batch: the decoder scope replays from it
-        HIP_TRY(hipMemcpyAsync(S.slots_before.p, b->slots.p, sizeof(sdr::ListenerSlot) * (size_t)B * (size_t)c.max_listeners,
-                               hipMemcpyDeviceToDevice, stream_of(sdr::K_LISTEN_DECODE)));
-    if (!b->results_on)
-        SDR_ARM(sdr::K_LISTEN_DECODE);
-    if (max_slots > 0) {
-        ProfScope ps(b, sdr::K_LISTEN_DECODE, stream_of(sdr::K_LISTEN_DECODE));
-        SDR_LAUNCH(sdr::K_LISTEN_DECODE, sdr::launch_listen_decode(b->slots.p, b->morse.p, S.raw_bits.p, S.bits.p, b->text.p,
-                                                                   b->text_frames.p, S.edges.p, S.edge_counts.p, S.tr_deb.p, b->drops.p, cur,
-                                                                   lg, n_frames, B, b->edge_pos.p, c.max_batch_frames, stream_of(sdr::K_LISTEN_DECODE)));
-    }
-    if (b->results_on && SDR_ON(sdr::K_LISTEN_DECODE)) {
-        // delivery of this batch's edges and runes, behind the decoder on its stream; the decoder's event is
-        // recorded behind it so that the set is not reused before the copy to the host has happened
-        SDR_ARM(sdr::K_LISTEN_DECODE);
-        HIP_TRY(sdr::launch_pack_listen(b->slots.p, S.edges.p, S.edge_counts.p, b->text.p, b->text_frames.p, b->drops.p, b->res_layout, max_slots, B,
-                                        RS.block, stream_of(sdr::K_LISTEN_DECODE)));
-        if (!cap)  // (a replay records it behind the listen graph)
-            HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(RS.ev_listen), stream_of(sdr::K_LISTEN_DECODE)));
-    }
-    SDR_DONE(sdr::K_LISTEN_DECODE);
-    }  // do_listen
+    if (!cap)
+        if (const int rc = flush_late_attached(b))
+            return rc;
+    const BatchIssue is = prepare_batch(b, n_frames, capture_k, capture_stage, do_spectra, do_listen);
+    int rc;
+    if (do_spectra && (rc = issue_spectra(is, iq_dev, in_stride, fmt)))
+        return rc;
+    if (do_listen && (rc = issue_listen(is)))
+        return rc;
     if (!do_spectra) {
         // the batch is complete: sdr_poll may have it
-        b->results->complete(si, max_slots, b->pend.batch);
+        b->results->complete(is.si, is.max_slots, b->pend.batch);
         b->listen_pending = false;
         return SDR_OK;
     }
-
-    // dB projection + cumulation, peak scan (rx/receiver.go:404-409,459-460)
-    const int n_chunks = P.n_chunks;
-    // (the scan wrote the bounds of the completed cumulations on the noise stream: the carry is added to slot 0's here)
-    SDR_AFTER(sdr::K_CUMULATE, sdr::K_FFT);
-    if (P.bound_done)
-        SDR_AFTER(sdr::K_CUMULATE, sdr::K_WINDOW_MEANS);
-    {
-        ProfScope ps(b, sdr::K_CUMULATE, stream_of(sdr::K_CUMULATE));
-        SDR_ARM(sdr::K_CUMULATE);
-        SDR_LAUNCH(sdr::K_CUMULATE, sdr::launch_cumulate(S.psd.p, b->db_tab.p, b->carry[0].p, b->carry[1].p, b->carry_cur, S.cum_out.p, S.cum_part.p,
-                                                         cur, cg, P.n_slots, B, P.bound, P.bound_done, P.scan_parts, stream_of(sdr::K_CUMULATE)));
-    }
-    SDR_DONE(sdr::K_CUMULATE);
-    SDR_AFTER(sdr::K_FIND_PEAKS, sdr::K_CUMULATE);
-    if (!b->results_on)
-        SDR_ARM(sdr::K_FIND_PEAKS);
-    if (b->find_peaks && n_chunks > 0) {
-        SDR_AFTER(sdr::K_FIND_PEAKS, sdr::K_THRESHOLDS);  // needs the completing frame's peak threshold
-        ProfScope ps(b, sdr::K_FIND_PEAKS, stream_of(sdr::K_FIND_PEAKS));
-        sdr::PeakGeom pg{N, stride, count0, b->max_chunks, c.max_peaks};
-        // (reads the carry buffer this batch's cumulation started from: the next batch's k_cumulate, which writes that
-        // buffer, follows on the same stream)
-        // the wide tap this batch's FFT left, if it was the kernel that leaves one (k_cum_refine reads the signals' columns there)
-        sdr::FftTap wide_tap{nullptr, nullptr, max_slots, c.max_listeners};
-        if (P.fft.wide_tap) {
-            wide_tap.wide = S.tapw.p;
-            wide_tap.used = S.tap_used.p;
-        }
-        SDR_LAUNCH(sdr::K_FIND_PEAKS, sdr::launch_find_peaks(S.cum_out.p, S.psd.p, b->db_tab.p, b->carry[0].p, b->carry[1].p, b->carry_cur, S.recs.p,
-                                                             S.dev_peaks.p, S.peak_counts.p, cur, pg, n_frames, n_chunks, B, P.refine, wide_tap,
-                                                             stream_of(sdr::K_FIND_PEAKS)));
-    }
-    // the waterfall rows of the completed cumulations, straight into the set's row block: behind the cumulate step on the
-    // find-peaks stage's stream, in front of the event sdr_poll looks at (recorded behind the pack kernel below)
-    if (P.rows && SDR_ON(sdr::K_FIND_PEAKS)) {
-        ProfScope ps(b, sdr::K_CUM_ROWS, b->stream[P.rows_stream]);
-        HIP_TRY(sdr::launch_cum_rows(S.psd.p, b->db_tab.p, b->carry[0].p, b->carry[1].p, b->carry_cur, cur, cg, b->row_columns, n_chunks, B, RS.rows,
-                                     b->stream[P.rows_stream]));
-    }
-    if (b->results_on && SDR_ON(sdr::K_FIND_PEAKS)) {
-        SDR_ARM(sdr::K_FIND_PEAKS);
-        HIP_TRY(sdr::launch_pack_peaks(S.dev_peaks.p, S.peak_counts.p, cur, b->res_layout, b->find_peaks, n_frames, n_chunks, B,
-                                       RS.block, stream_of(sdr::K_FIND_PEAKS)));
-        if (!cap) {
-            HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(RS.ev_peaks), stream_of(sdr::K_FIND_PEAKS)));
-            host::BatchMeta m;
-            m.batch = b->batch_index;
-            m.first_frame = b->total_frames;
-            m.frames = n_frames;
-            m.chunks = n_chunks;
-            m.count0 = count0;
-            m.slots = do_listen ? max_slots : 0;  // (sdr_poll_peaks delivers the spectral half; the listen half fills this in)
-            m.row_columns = P.rows ? b->row_columns : 0;
-            m.rows = P.rows ? n_chunks * B : 0;
-            {
-                std::lock_guard<std::mutex> guard(b->center_mu);
-                m.center = b->center_frequency;
-            }
-            b->results->publish(si, std::move(m), do_listen);
-        }
-    }
-    SDR_DONE(sdr::K_FIND_PEAKS);
-#undef SDR_AFTER
-#undef SDR_DONE
-#undef SDR_ARM
-#undef SDR_LAUNCH
-#undef SDR_ON
-
-    if (cap)
-        return SDR_OK;
-    // every launch of the batch is enqueued: commit the host's view of the carried state in one go.
-    // The carry buffer flips only when this batch wrote a new partial cumulation; if the batch ended
-    // exactly on a chunk boundary the next batch starts from zero (count0 == 0 ignores the carry)
-    b->last_carry_in = b->carry_cur;
-    if (P.new_count != 0)
-        b->carry_cur ^= 1;
-    b->cum_count = P.new_count;
-    b->last_set = si;
-    b->last_frames = n_frames;
-    b->last_chunks = n_chunks;
-    b->last_count0 = count0;
-    if (!do_listen) {
-        b->pend.set = si;
-        b->pend.frames = n_frames;
-        b->pend.first_frame = b->total_frames;
-        b->pend.batch = b->batch_index;
-        b->listen_pending = true;
-    }
-    b->total_frames += n_frames;
-    b->batch_index++;
-    if (!b->results_on)
-        b->results->note_enqueued(b->batch_index);
+    if ((rc = issue_cumulation(is)))
+        return rc;
+    if (!cap)
+        commit_batch(is);
     return SDR_OK;
 }
 

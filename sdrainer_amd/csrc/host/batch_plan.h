@@ -1,6 +1,8 @@
 // host/batch_plan.h — every choice the scheduler makes for one batch (process_device_body, capi_process.hip), made in one
 // place: which stream each kernel runs on, which FFT kernel runs, which noise-floor path, whether the cumulations are
-// bounded and refined, the slot and chunk counts.  The launchers receive these decisions as arguments and decide nothing.
+// bounded and refined, the slot and chunk counts; and the order of its stages (stage_deps, set_reuse_stages, in_graph: who
+// waits for whom, which stage stands for its stream when a buffer set is reused, which graph a kernel belongs to under
+// capture).  The launchers receive these decisions as arguments and decide nothing.
 //
 // The environment switches that steer the pipeline are read here too, by read_switches(), once per bank (sdr_create).
 // They select a second implementation of a stage for the tests (tests/test_forced_paths.py) or are measurement knobs;
@@ -305,6 +307,61 @@ inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_fr
     p.rows = row_columns > 0 && p.n_chunks > 0;
     p.rows_stream = p.stream[K_FIND_PEAKS];
     return p;
+}
+
+// ---- the order of a batch's stages.  The scheduler issues them in this order: FFT, window means, noise stats, thresholds,
+// gather, decode, cumulate, find-peaks.  A stage publishes an event (BatchSet::done) whether or not it launches a kernel.
+
+// Who waits for whom, in issue order: stage k starts once stage `dep` of the same batch is done.  The scheduler turns an
+// entry into a wait only where the two stages run on different streams (a stream orders its own kernels).
+struct StageDep {
+    int k, dep;
+};
+struct StageDeps {
+    static constexpr int kMax = 10;
+    int n = 0;
+    StageDep d[kMax];
+};
+// peak_scan: the batch runs the peak scan (sdr_set_find_peaks on and the batch completes a cumulation)
+inline StageDeps stage_deps(const BatchPlan &p, bool peak_scan)
+{
+    StageDeps s;
+    auto add = [&s](int k, int dep) { s.d[s.n++] = StageDep{k, dep}; };
+    add(K_WINDOW_MEANS, K_FFT);
+    add(K_NOISE_STATS, K_WINDOW_MEANS);
+    add(K_THRESHOLDS, K_NOISE_STATS);
+    add(K_LISTEN_GATHER, K_THRESHOLDS);
+    add(K_LISTEN_GATHER, K_FFT);
+    add(K_LISTEN_DECODE, K_LISTEN_GATHER);
+    add(K_CUMULATE, K_FFT);
+    if (p.bound_done)  // k_psd_scan wrote the bounds of the completed cumulations: the carry is added to slot 0's by k_bound_finish
+        add(K_CUMULATE, K_WINDOW_MEANS);
+    add(K_FIND_PEAKS, K_CUMULATE);
+    if (peak_scan)  // needs the completing frame's peak threshold
+        add(K_FIND_PEAKS, K_THRESHOLDS);
+    return s;
+}
+
+// Set reuse: the FFT of batch i + RING writes the buffer set that batch i used, once every reader of the set is done.  One
+// stage stands for each stream - the last one issued on it, whose event follows all the stream's earlier ones - so the
+// FFT's queue gets one wait per other stream, not one per stage.  out[st]: that stage for stream st, -1 where the stream
+// runs none of them or is the FFT's own (which orders its batches itself).
+inline void set_reuse_stages(const BatchPlan &p, int out[N_STAGES])
+{
+    static constexpr int issue_order[] = {K_WINDOW_MEANS, K_NOISE_STATS, K_THRESHOLDS, K_LISTEN_GATHER, K_LISTEN_DECODE, K_CUMULATE, K_FIND_PEAKS};
+    for (int st = 0; st < N_STAGES; st++)
+        out[st] = -1;
+    for (int k : issue_order)
+        out[p.stream[k]] = k;
+    out[p.stream[K_FFT]] = -1;
+}
+
+// Graph mode records one graph per stream plus, as a graph of its own in front of the peaks stream's, the thresholds (the
+// listen graph starts behind them, not behind the cumulations).  Is kernel k part of graph `graph` (a Stage, or G_THRESHOLDS)?
+constexpr int G_THRESHOLDS = N_STAGES, N_GRAPHS = N_STAGES + 1;
+inline bool in_graph(const BatchPlan &p, int k, int graph)
+{
+    return graph == G_THRESHOLDS ? k == K_THRESHOLDS : (k != K_THRESHOLDS && p.stream[k] == graph);
 }
 
 }  // namespace sdr

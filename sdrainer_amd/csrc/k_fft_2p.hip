@@ -103,17 +103,16 @@ __global__ __launch_bounds__(fft2p::T) void k_fft2p_b(const fft64::cplx *__restr
 
 template <int LOGN>
 static hipError_t launch_fft2p_t(FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                                 int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
+                                 int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
 {
     using PH = fft2p::Phases<LOGN>;
+    const hipStream_t stream = at.stream;
     if (n_frames <= 0 || n_bands <= 0)
         return hipSuccess;
     if (!tap.scratch || fft.group_frames <= 0)
         return hipErrorInvalidValue;
     const int group = fft.group_frames;
-    // (a stage event armed by the caller rides on the last launch)
-    const hipEvent_t done = t_done_event;
-    t_done_event = nullptr;
+    // (at.done rides on the last frame group's phase B, the last launch)
     for (int f0 = 0; f0 < n_frames; f0 += group) {
         const int g = n_frames - f0 < group ? n_frames - f0 : group;
         if (tap.window && fmt == InFormat::SC16)
@@ -128,21 +127,19 @@ static hipError_t launch_fft2p_t(FftChoice fft, InFormat fmt, const void *iq, co
         else
             hipLaunchKernelGGL((k_fft2p_a<LOGN, InFormat::F32>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
                                tap.scratch, in_stride, frame_stride, f0, group);
-        if (f0 + group >= n_frames)
-            t_done_event = done;
-        launch_kernel((k_fft2p_b<LOGN>), dim3(g * PH::WG_B, n_bands), dim3(fft2p::T), 0, stream, static_cast<const fft64::cplx *>(tap.scratch),
-                      tw, psd, out_stride, f0, group, tap.bins, tap.out, tap.n, tap.stride);
+        const bool last = f0 + group >= n_frames;
+        launch_kernel((k_fft2p_b<LOGN>), dim3(g * PH::WG_B, n_bands), dim3(fft2p::T), 0, last ? at : LaunchAt(stream),
+                      static_cast<const fft64::cplx *>(tap.scratch), tw, psd, out_stride, f0, group, tap.bins, tap.out, tap.n, tap.stride);
     }
-    t_done_event = nullptr;
     return hipGetLastError();
 }
 
 hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                         int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
+                         int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
 {
     switch (logn) {
-    case 15: return launch_fft2p_t<15>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
-    case 16: return launch_fft2p_t<16>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+    case 15: return launch_fft2p_t<15>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 16: return launch_fft2p_t<16>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
     default: return hipErrorInvalidValue;
     }
 }

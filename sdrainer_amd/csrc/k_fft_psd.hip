@@ -654,7 +654,7 @@ static_assert(fft32::T == kR32MaxTap, "host/batch_plan.h: k_fft_r32 serves one l
 
 template <int LOGN>
 static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                               int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
+                               int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
 {
     using PL = fft64::Plan<LOGN>;
     const float *iq = static_cast<const float *>(iq_in);
@@ -673,7 +673,7 @@ static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, c
     const unsigned tap_lds = tap.n > 0 && tap.n <= kMaxLdsTap ? ((tap.n * 4 + 255) & ~255) : 0;
     if (fmt == InFormat::SC16) {
         // one frame per workgroup, always (FftChoice::fpw is the float32 kernel's)
-        launch_kernel((SDR_K_FFT_PSD_SC16<LOGN>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, stream,
+        launch_kernel((SDR_K_FFT_PSD_SC16<LOGN>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at,
                       static_cast<const int16_t *>(iq_in), cur, tw, psd, in_stride, frame_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_ARG);
         return hipGetLastError();
     }
@@ -683,11 +683,11 @@ static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, c
     while (fpw > 1 && (long)((n_frames + fpw - 1) / fpw) * n_bands < 256)
         fpw /= 2;
     if (fpw > 1)
-        launch_kernel((SDR_K_FFT_PSD<LOGN, true>), dim3((n_frames + fpw - 1) / fpw, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN>, stream,
+        launch_kernel((SDR_K_FFT_PSD<LOGN, true>), dim3((n_frames + fpw - 1) / fpw, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN>, at,
                            iq, cur, tw, psd, in_stride, frame_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_ARG);
     else
         launch_kernel((SDR_K_FFT_PSD<LOGN, false>), dim3(n_frames, n_bands), dim3(PL::T),
-                           fft64::kLdsBytes<LOGN> + tap_lds, stream, iq, cur, tw, psd, in_stride,
+                           fft64::kLdsBytes<LOGN> + tap_lds, at, iq, cur, tw, psd, in_stride,
                            frame_stride, out_stride, n_frames, 1, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_ARG);
     return hipGetLastError();
 }
@@ -713,47 +713,41 @@ void window_layout(int logn, const float *w, float *out)
 
 // N = 512 - 16384 with the window table tap.window, in window_layout's order (launch_fft hands such a launch on)
 hipError_t launch_fft_win(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
+                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
 {
     if (!tap.window || fft.r32 || fft.two_phase)
         return hipErrorInvalidValue;  // (host/batch_plan.h: a windowed batch is never planned onto k_fft_r32)
 #else
 // The bank's twiddle buffer for N = 16384 holds both kernels' tables, the 32-point kernel's behind the other.
 hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                      int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
+                      int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
 {
     if (fmt != InFormat::F32 && fmt != InFormat::SC16)
         return hipErrorInvalidValue;
     if (fft.two_phase)  // (with tap.window: k_fft2p_win_a)
-        return launch_fft_2p(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+        return launch_fft_2p(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
     if (tap.window)
-        return launch_fft_win(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+        return launch_fft_win(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
     if (fft.r32) {
         if (logn != 14)
             return hipErrorInvalidValue;
         const fft64::cplx *tw32 = tw + fft64::Plan<14>::TW_TOTAL;
         if (fmt == InFormat::SC16)
-            return launch_fft_r32_sc16(static_cast<const int16_t *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, fft.reserve_cus, fft.reserve_forced, stream);
-        return launch_fft_r32(static_cast<const float *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, fft.reserve_cus, fft.reserve_forced, stream);
+            return launch_fft_r32_sc16(static_cast<const int16_t *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, fft.reserve_cus, fft.reserve_forced, at);
+        return launch_fft_r32(static_cast<const float *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, fft.reserve_cus, fft.reserve_forced, at);
     }
 #endif
     switch (logn) {
-    case 9: return launch_fft_t<9>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
-    case 10: return launch_fft_t<10>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
-    case 11: return launch_fft_t<11>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
-    case 12: return launch_fft_t<12>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
-    case 13: return launch_fft_t<13>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
-    case 14: return launch_fft_t<14>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
+    case 9: return launch_fft_t<9>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 10: return launch_fft_t<10>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 11: return launch_fft_t<11>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 12: return launch_fft_t<12>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 13: return launch_fft_t<13>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 14: return launch_fft_t<14>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
     default: return hipErrorInvalidValue;
     }
 }
 #if !SDR_FFT_WIN
-hipError_t launch_fft(int logn, FftChoice fft, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
-                      int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream)
-{
-    return launch_fft(logn, fft, InFormat::F32, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, stream);
-}
-
 int twiddle_count(int logn)
 {
     switch (logn) {

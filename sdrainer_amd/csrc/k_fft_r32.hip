@@ -666,7 +666,7 @@ void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out) 
 // (host/batch_plan.h fft_reserve_cus; the rule's value capped at a quarter of the device, a forced one taken as it is),
 // at least one, never more than there are frames.
 hipError_t SDR_R32_LAUNCH(const SDR_R32_IN *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, hipStream_t stream)
+                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at)
 {
     constexpr int kMaxDevices = 64;
     static std::once_flag setup_once[kMaxDevices];
@@ -706,9 +706,9 @@ hipError_t SDR_R32_LAUNCH(const SDR_R32_IN *iq, const BatchCursor *cur, const ff
 #else
     if (frame_stride != fft32::N)  // overlapped frames: the strided kernel (k_fft_r32_hop.hip)
 #if SDR_R32_SC16
-        return launch_fft_r32_hop_sc16(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, stream);
+        return launch_fft_r32_hop_sc16(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, at);
 #else
-        return launch_fft_r32_hop(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, stream);
+        return launch_fft_r32_hop(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, at);
 #endif
     const unsigned frames_and_shift = (unsigned)n_frames;
 #endif
@@ -716,7 +716,7 @@ hipError_t SDR_R32_LAUNCH(const SDR_R32_IN *iq, const BatchCursor *cur, const ff
     const int reserve = reserve_forced ? reserve_cus : std::min(reserve_cus, cu_count[dev] / kReserveDeviceShare);
     const int cus = std::max(1, cu_count[dev] - std::max(0, reserve));
     const int grid = std::min((cus + n_bands - 1) / n_bands, n_frames);
-    launch_kernel(r32::SDR_R32_KERNEL, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, stream, iq, cur, tw, psd, (unsigned)in_stride, out_stride,
+    launch_kernel(r32::SDR_R32_KERNEL, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, at, iq, cur, tw, psd, (unsigned)in_stride, out_stride,
                   frames_and_shift, tap.steal, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used);
     return hipGetLastError();
 }

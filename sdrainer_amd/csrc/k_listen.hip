@@ -703,11 +703,11 @@ __global__ void k_set_debounce(ListenerSlot *slots, int n, int threshold)
 
 hipError_t launch_listen_gather(const float *tap, const float *psd, const sdr_frame_rec *recs, const ListenerSlot *slots, const void *db_tab,
                                 uint64_t *raw_bits, float *tr_values, uint8_t *tr_raw, const BatchCursor *cur, ListenGeom g, int n_frames,
-                                int n_slots, int n_bands, hipStream_t stream)
+                                int n_slots, int n_bands, LaunchAt at)
 {
     const double inv_n2 = 1.0 / ((double)g.n * (double)g.n);
     launch_kernel(k_listen_gather, dim3(((n_frames + 63) / 64 + GATHER_WAVES - 1) / GATHER_WAVES, (n_slots + 63) / 64, n_bands),
-                       dim3(64 * GATHER_WAVES), 0, stream, tap, psd, recs,
+                       dim3(64 * GATHER_WAVES), 0, at, tap, psd, recs,
                        slots, db_tab, raw_bits, tr_values, tr_raw, cur, g, n_frames, n_slots, inv_n2);
     return hipGetLastError();
 }
@@ -715,11 +715,11 @@ hipError_t launch_listen_gather(const float *tap, const float *psd, const sdr_fr
 hipError_t launch_listen_decode(ListenerSlot *slots, const uint16_t *morse, const uint64_t *raw_bits,
                                 uint64_t *deb_bits, uint32_t *text, uint32_t *text_frames, sdr_edge *edges,
                                 uint32_t *edge_counts, uint8_t *tr_deb, DropCounters *drops, const BatchCursor *cur, ListenGeom g,
-                                int n_frames, int n_bands, uint32_t *edge_pos, int pos_stride, hipStream_t stream)
+                                int n_frames, int n_bands, uint32_t *edge_pos, int pos_stride, LaunchAt at)
 {
     // edge_pos: [band][listener][pos_stride] scratch, pos_stride >= n_frames (an edge per tick at most)
     const int n_total = n_bands * g.max_listeners;
-    launch_kernel(k_listen_decode, dim3((n_total + DEC_GROUP - 1) / DEC_GROUP), dim3(64 * DEC_WAVES), 0, stream, slots, morse, raw_bits, deb_bits, text,
+    launch_kernel(k_listen_decode, dim3((n_total + DEC_GROUP - 1) / DEC_GROUP), dim3(64 * DEC_WAVES), 0, at, slots, morse, raw_bits, deb_bits, text,
                   text_frames, edges, edge_counts, tr_deb, drops, cur, g, n_frames, n_total, edge_pos, pos_stride);
     return hipGetLastError();
 }

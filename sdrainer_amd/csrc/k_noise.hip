@@ -1016,7 +1016,7 @@ hipError_t launch_mfma_order_probe(unsigned *mismatches, int order, hipStream_t 
 }
 
 hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, int n_frames, int n_bands, int stride, int wpb_forced,
-                               hipStream_t stream)
+                               LaunchAt at)
 {
     // (rounds 2 - 3, 2048-frame batches: config 3's 160 workgroups of one window each; two windows back to back per
     // workgroup, 80 workgroups: 0.050 instead of 0.030 ms standalone and 0.226 - 0.238 instead of 0.222 - 0.225 ms per
@@ -1039,31 +1039,31 @@ hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, 
 
     const dim3 grid(per_band, (g.n_windows + wpb - 1) / wpb, n_bands);
     if (half)
-        launch_kernel((k_window_means<WM_GROUPS_HALF, WindowRingHalf>), grid, dim3(64 * (MAX_WAVES / WM_GROUPS) * WM_GROUPS_HALF), 0, stream, psd, win_mean, g,
+        launch_kernel((k_window_means<WM_GROUPS_HALF, WindowRingHalf>), grid, dim3(64 * (MAX_WAVES / WM_GROUPS) * WM_GROUPS_HALF), 0, at, psd, win_mean, g,
                       n_frames, stride, wpb);
     else
-        launch_kernel((k_window_means<WM_GROUPS, WindowRing>), grid, dim3(CHAIN_THREADS), 0, stream, psd, win_mean, g, n_frames, stride, wpb);
+        launch_kernel((k_window_means<WM_GROUPS, WindowRing>), grid, dim3(CHAIN_THREADS), 0, at, psd, win_mean, g, n_frames, stride, wpb);
     return hipGetLastError();
 }
 
 // mfma: the matrix-pipe kernel (less latency) rather than two vector-ALU chain groups per workgroup (less CU time): the plan
 // picks it for short batches (host/batch_plan.h)
 hipError_t launch_noise_stats(const float *psd, const double *win_mean, sdr_frame_rec *recs, NoiseGeom g, int n_frames,
-                              int n_bands, int stride, bool mfma, hipStream_t stream)
+                              int n_bands, int stride, bool mfma, LaunchAt at)
 {
     const int groups_of_64 = (n_frames + TILE - 1) / TILE;
     if (mfma)
-        launch_kernel(k_noise_stats<true>, dim3(groups_of_64, n_bands), dim3(CHAIN_THREADS), 0, stream, psd, win_mean, recs, g, n_frames, stride);
+        launch_kernel(k_noise_stats<true>, dim3(groups_of_64, n_bands), dim3(CHAIN_THREADS), 0, at, psd, win_mean, recs, g, n_frames, stride);
     else
-        launch_kernel(k_noise_stats<false>, dim3((groups_of_64 + NS_GROUPS_VALU - 1) / NS_GROUPS_VALU, n_bands), dim3(CHAIN_THREADS), 0, stream, psd,
+        launch_kernel(k_noise_stats<false>, dim3((groups_of_64 + NS_GROUPS_VALU - 1) / NS_GROUPS_VALU, n_bands), dim3(CHAIN_THREADS), 0, at, psd,
                       win_mean, recs, g, n_frames, stride);
     return hipGetLastError();
 }
 
 hipError_t launch_thresholds(sdr_frame_rec *recs, BandState *st, int n_frames, int n_bands, int stride,
-                             hipStream_t stream)
+                             LaunchAt at)
 {
-    launch_kernel(k_thresholds, dim3(n_bands), dim3(256), 0, stream, recs, st, n_frames, stride);
+    launch_kernel(k_thresholds, dim3(n_bands), dim3(256), 0, at, recs, st, n_frames, stride);
     return hipGetLastError();
 }
 

@@ -434,10 +434,9 @@ static int scan_jmax(int window)
 
 // One batch's noise floor: the FindNoiseFloor fields of every frame's record and (do_bound) the unit counts of every
 // cumulation the batch completes, a slot's frames dealt over `parts` workgroups (k_bound_finish adds as many partial counts:
-// both take the value from the batch's plan, host/batch_plan.h).  force_exact: see k_psd_scan (tests).  (A stage event armed by the caller rides on
-// the launch.)
+// both take the value from the batch's plan, host/batch_plan.h).  force_exact: see k_psd_scan (tests).
 hipError_t launch_psd_scan(const float *psd, sdr_frame_rec *recs, float *cum_out, float *cum_part, const BatchCursor *cur, NoiseGeom ng,
-                           CumGeom cg, int n_slots, int n_bands, bool do_bound, int parts, int force_exact, hipStream_t stream)
+                           CumGeom cg, int n_slots, int n_bands, bool do_bound, int parts, int force_exact, LaunchAt at)
 {
     if (cg.n_frames <= 0 || n_bands <= 0)
         return hipSuccess;
@@ -479,11 +478,11 @@ hipError_t launch_psd_scan(const float *psd, sdr_frame_rec *recs, float *cum_out
     // (graph mode: the grid must cover the slots of any cumulation phase - the kernel returns for slots beyond the batch)
     const dim3 grid(do_bound ? n_slots * g.parts : (cg.n_frames + g.fpw - 1) / g.fpw, n_bands), block(64 * waves);
     switch (jmax) {
-    case 2: launch_kernel(k_psd_scan<2>, grid, block, lds, stream, psd, recs, cum_out, cum_part, cur, g, ng.inv_n2, force_exact); break;
-    case 5: launch_kernel(k_psd_scan<5>, grid, block, lds, stream, psd, recs, cum_out, cum_part, cur, g, ng.inv_n2, force_exact); break;
-    case 10: launch_kernel(k_psd_scan<10>, grid, block, lds, stream, psd, recs, cum_out, cum_part, cur, g, ng.inv_n2, force_exact); break;
-    case 19: launch_kernel(k_psd_scan<19>, grid, block, lds, stream, psd, recs, cum_out, cum_part, cur, g, ng.inv_n2, force_exact); break;
-    default: launch_kernel(k_psd_scan<26>, grid, block, lds, stream, psd, recs, cum_out, cum_part, cur, g, ng.inv_n2, force_exact); break;
+    case 2: launch_kernel(k_psd_scan<2>, grid, block, lds, at, psd, recs, cum_out, cum_part, cur, g, ng.inv_n2, force_exact); break;
+    case 5: launch_kernel(k_psd_scan<5>, grid, block, lds, at, psd, recs, cum_out, cum_part, cur, g, ng.inv_n2, force_exact); break;
+    case 10: launch_kernel(k_psd_scan<10>, grid, block, lds, at, psd, recs, cum_out, cum_part, cur, g, ng.inv_n2, force_exact); break;
+    case 19: launch_kernel(k_psd_scan<19>, grid, block, lds, at, psd, recs, cum_out, cum_part, cur, g, ng.inv_n2, force_exact); break;
+    default: launch_kernel(k_psd_scan<26>, grid, block, lds, at, psd, recs, cum_out, cum_part, cur, g, ng.inv_n2, force_exact); break;
     }
     return hipGetLastError();
 }

@@ -854,22 +854,21 @@ __global__ __launch_bounds__(kRowsThreads) void k_cum_rows(const float *__restri
 }
 
 // One batch's cumulation work, on `stream`: bounds of the cumulations it completes, the exact carry of the one it leaves
-// open.  (A stage event armed by the caller rides on the last launch.)
+// open.  (at.done rides on the last launch, k_cumulate.)
 hipError_t launch_cumulate(const float *psd, const void *db_tab, float *carry0, float *carry1, int carry_in, float *cum_out,
                            const float *cum_part, const BatchCursor *cur, CumGeom g, int n_slots, int n_bands, bool bound, bool bound_done,
-                           int parts, hipStream_t stream)
+                           int parts, LaunchAt at)
 {
+    const hipStream_t stream = at.stream;
     const double inv_n2 = 1.0 / ((double)g.n * (double)g.n);
     const int threads = g.n < SDR_CUM_THREADS ? g.n : SDR_CUM_THREADS;
     if (!bound) {  // short batches: every slot exact, one launch (as rounds 1-3)
-        launch_kernel(k_cumulate, dim3((g.n + threads - 1) / threads, n_slots, n_bands), dim3(threads), 0, stream, psd, db_tab, carry0, carry1,
+        launch_kernel(k_cumulate, dim3((g.n + threads - 1) / threads, n_slots, n_bands), dim3(threads), 0, at, psd, db_tab, carry0, carry1,
                       carry_in, cum_out, static_cast<float *>(nullptr), cur, g, 0, 0, inv_n2);
         return hipGetLastError();
     }
     double a128, per_frame;
     gomath::cum_bound_constants(g.n, &a128, &per_frame);
-    const hipEvent_t done = t_done_event;
-    t_done_event = nullptr;
     if (bound_done) {
         hipLaunchKernelGGL(k_bound_finish, dim3((g.n + 255) / 256, n_slots, n_bands), dim3(256), 0, stream, cum_out, cum_part,
                            parts, carry0, carry1, carry_in, cur, g, a128, per_frame);
@@ -891,8 +890,7 @@ hipError_t launch_cumulate(const float *psd, const void *db_tab, float *carry0, 
         hipLaunchKernelGGL(k_cum_bound, dim3(wgs), dim3(threads), kBoundLdsBytes, stream, psd, carry0, carry1, carry_in, cum_out, cur, g, n_slots,
                            n_bands, a128, per_frame);
     }
-    t_done_event = done;
-    launch_kernel(k_cumulate, dim3((g.n + threads - 1) / threads, 1, n_bands), dim3(threads), 0, stream, psd, db_tab, carry0, carry1, carry_in,
+    launch_kernel(k_cumulate, dim3((g.n + threads - 1) / threads, 1, n_bands), dim3(threads), 0, at, psd, db_tab, carry0, carry1, carry_in,
                   cum_out, static_cast<float *>(nullptr), cur, g, 1, 0, inv_n2);
     return hipGetLastError();
 }
@@ -934,10 +932,11 @@ hipError_t launch_spectrum_row(const float *psd_row, float *out, int n, hipStrea
 
 hipError_t launch_find_peaks(float *cum, const float *psd, const void *db_tab, const float *carry0, const float *carry1, int carry_in,
                              const sdr_frame_rec *recs, DevPeak *peaks, int *counts, const BatchCursor *cur, PeakGeom g, int n_frames,
-                             int n_chunks, int n_bands, Refine refine, FftTap tap, hipStream_t stream)
+                             int n_chunks, int n_bands, Refine refine, FftTap tap, LaunchAt at)
 {
-    if (n_chunks == 0)
+    if (n_chunks == 0)  // (nothing is launched and at.done stays unrecorded: the scheduler does not call with an event then)
         return hipSuccess;
+    const hipStream_t stream = at.stream;
     const int words = g.n >> 6;
     const bool wide = g.n > 16384;  // (k_find_peaks_wide: no row in LDS)
     const unsigned lds = (unsigned)((wide ? 0 : (size_t)g.n * 4) + (size_t)words * 16 + (size_t)(words + 1) * 4);
@@ -946,9 +945,7 @@ hipError_t launch_find_peaks(float *cum, const float *psd, const void *db_tab, c
     const hipError_t attr_err = raise_lds_limit_once(lds_once, {reinterpret_cast<const void *>(&k_find_peaks)}, 16384 * 4 + 256 * 16 + 257 * 4);
     if (attr_err != hipSuccess)
         return attr_err;
-    // the exact cumulation where the scan will look, then the scan (a stage event armed by the caller rides on the scan)
-    const hipEvent_t done = t_done_event;
-    t_done_event = nullptr;
+    // the exact cumulation where the scan will look, then the scan (at.done rides on the scan)
     const double inv_n2 = 1.0 / ((double)g.n * (double)g.n);
     // (Refine::NONE: k_cumulate left every row exact)
     if (refine == Refine::WIDE)
@@ -958,13 +955,12 @@ hipError_t launch_find_peaks(float *cum, const float *psd, const void *db_tab, c
         hipLaunchKernelGGL((k_cum_refine<kRefineSpan, kRefineThreads>), dim3(n_chunks, (g.n + kRefineSpan - 1) / kRefineSpan, n_bands),
                            dim3(kRefineThreads), 0, stream, cum, psd, db_tab, carry0, carry1, carry_in, recs, cur, g, n_frames, inv_n2, tap.wide,
                            tap.used, tap.n, tap.stride);
-    t_done_event = done;
     const int threads = g.n < kPeakThreadsMax ? g.n : kPeakThreadsMax;
     if (wide)
-        launch_kernel(k_find_peaks_wide, dim3(n_chunks, n_bands), dim3(threads), lds, stream, static_cast<const float *>(cum), recs, peaks, counts,
+        launch_kernel(k_find_peaks_wide, dim3(n_chunks, n_bands), dim3(threads), lds, at, static_cast<const float *>(cum), recs, peaks, counts,
                       cur, g, n_frames);
     else
-        launch_kernel(k_find_peaks, dim3(n_chunks, n_bands), dim3(threads), lds, stream, static_cast<const float *>(cum), recs, peaks, counts, cur, g,
+        launch_kernel(k_find_peaks, dim3(n_chunks, n_bands), dim3(threads), lds, at, static_cast<const float *>(cum), recs, peaks, counts, cur, g,
                       n_frames);
     return hipGetLastError();
 }

@@ -90,20 +90,20 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void k_pack_peaks(const DevPeak *_
 
 hipError_t launch_pack_listen(ListenerSlot *slots, const sdr_edge *edges, const uint32_t *edge_counts, const uint32_t *text,
                               const uint32_t *text_frames, const DropCounters *drops, ResultsLayout lay, int n_slots, int n_bands, unsigned char *host,
-                              hipStream_t stream)
+                              LaunchAt at)
 {
     // (at least one workgroup: it also delivers the drop counters)
     launch_kernel(k_pack_listen, dim3(n_slots > 0 ? (n_slots + PACK_WAVES - 1) / PACK_WAVES : 1, n_bands), dim3(64 * PACK_WAVES),
-                       0, stream, slots, edges, edge_counts, text, text_frames, drops, lay, n_slots, host);
+                       0, at, slots, edges, edge_counts, text, text_frames, drops, lay, n_slots, host);
     return hipGetLastError();
 }
 
 hipError_t launch_pack_peaks(const DevPeak *peaks, const int *counts, const BatchCursor *cur, ResultsLayout lay, int find_peaks,
-                             int n_frames, int n_chunks, int n_bands, unsigned char *host, hipStream_t stream)
+                             int n_frames, int n_chunks, int n_bands, unsigned char *host, LaunchAt at)
 {
     if (n_chunks <= 0)
         return hipSuccess;
-    launch_kernel(k_pack_peaks, dim3((n_chunks + PACK_WAVES - 1) / PACK_WAVES, n_bands), dim3(64 * PACK_WAVES), 0, stream, peaks,
+    launch_kernel(k_pack_peaks, dim3((n_chunks + PACK_WAVES - 1) / PACK_WAVES, n_bands), dim3(64 * PACK_WAVES), 0, at, peaks,
                        counts, cur, lay, find_peaks, n_frames, n_chunks, host);
     return hipGetLastError();
 }

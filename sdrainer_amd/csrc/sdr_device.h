@@ -115,18 +115,23 @@ struct ResultsLayout {
 // A stage's completion event can ride on the kernel's own dispatch packet (hipExtLaunchKernelGGL's stopEvent)
 // instead of a hipEventRecord behind the kernel.  The record is a barrier packet of its own: the queue's next kernel
 // waits for the command processor to retire it, which on the FFT queue was 27-36 us per batch with nothing running
-// (0.200 ms per step for a 0.166 ms kernel launched back to back).  The caller arms `t_done_event` right before a
-// launch_* call; the first kernel launched through launch_kernel takes it.
-inline thread_local hipEvent_t t_done_event = nullptr;
+// (0.200 ms per step for a 0.166 ms kernel launched back to back).  So where a launcher launches is a stream and,
+// optionally, the event its work is done at: the scheduler's launchers take a LaunchAt where the others take a stream.
+// The contract of every such launcher: given an event, it attaches it to the LAST kernel it launches and to no other
+// (its earlier kernels get the plain stream).  One that returns hipSuccess without launching anything - launch_find_peaks
+// at n_chunks == 0, the FFT launchers at n_frames <= 0 - leaves the event unrecorded: the caller must not ask for one there.
+struct LaunchAt {
+    hipStream_t stream;
+    hipEvent_t done = nullptr;
+    LaunchAt(hipStream_t s, hipEvent_t d = nullptr) : stream(s), done(d) {}  // (implicit: a plain stream is a launch without an event)
+};
 template <class F, class... A>
-inline void launch_kernel(F kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, A... args)
+inline void launch_kernel(F kernel, dim3 grid, dim3 block, unsigned lds_bytes, LaunchAt at, A... args)
 {
-    hipEvent_t done = t_done_event;
-    t_done_event = nullptr;
-    if (done)
-        hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, nullptr, done, 0, args...);
+    if (at.done)
+        hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, at.stream, nullptr, at.done, 0, args...);
     else
-        hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+        hipLaunchKernelGGL(kernel, grid, block, lds_bytes, at.stream, args...);
 }
 
 // More than 64 KB of dynamic LDS needs the kernel attribute, which is per device: set it once on each device a bank
@@ -179,50 +184,48 @@ struct FftTap {
 // f * frame_stride on (host/overlap.h input_sample_offset; dense frames: frame_stride = N, in_stride = n_frames * N; overlapped
 // frames: frame_stride = hop < N); `fft` picks the kernel (host/batch_plan.h)
 hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                      int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
-hipError_t launch_fft(int logn, FftChoice fft, const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames,
-                      int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);  // (float32)
+                      int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
 // k_fft_psd_win.hip: N = 512 - 16384 with tap.window set (launch_fft hands such a launch on; never k_fft_r32)
 hipError_t launch_fft_win(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
+                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
 // ... and the order its kernels read the table in: out[N] from the caller's w[N] (sample order)
 void window_layout(int logn, const float *w, float *out);
 // k_fft_2p.hip: N = 32768 / 65536 as two phases over a scratch buffer (fft_2p.h), frame group by frame group
 hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                         int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, hipStream_t stream);
+                         int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
 int twiddle_count(int logn);
 void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx *out);
 // k_fft_r32.hip: N = 16384 as 512 threads x 32 points with the next frame prefetched into registers (own twiddle layout);
 // reserve_cus: CUs the grid leaves free (FftChoice::reserve_cus; unless reserve_forced at most CUs / kReserveDeviceShare) -
 // workgroups per band = max(1, ceil((CUs - reserve_cus) / n_bands)), at most n_frames
 hipError_t launch_fft_r32(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, hipStream_t stream);
+                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
 // k_fft_r32_sc16.hip: the same kernel reading sc16 frames
 hipError_t launch_fft_r32_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                               size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, hipStream_t stream);
+                               size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
 // k_fft_r32_hop.hip / k_fft_r32_hop_sc16.hip: the same kernels for frame_stride < N (a power of two); the two launchers
 // above hand such a launch on themselves
 hipError_t launch_fft_r32_hop(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                              size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, hipStream_t stream);
+                              size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
 hipError_t launch_fft_r32_hop_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                                   size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, hipStream_t stream);
+                                   size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
 int r32_twiddle_count();
 void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out);
 // wpb_forced: windows per workgroup (0: the launcher's rule); mfma: the matrix-pipe variance kernel (host/batch_plan.h)
 hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, int n_frames, int n_bands, int stride, int wpb_forced,
-                               hipStream_t stream);
+                               LaunchAt at);
 hipError_t launch_noise_stats(const float *psd, const double *win_mean, sdr_frame_rec *recs, NoiseGeom g, int n_frames,
-                              int n_bands, int stride, bool mfma, hipStream_t stream);
+                              int n_bands, int stride, bool mfma, LaunchAt at);
 hipError_t launch_mfma_order_probe(unsigned *mismatches, int order, hipStream_t stream);  // k_noise.hip: sdr_self_check
 hipError_t launch_thresholds(sdr_frame_rec *recs, BandState *st, int n_frames, int n_bands, int stride,
-                             hipStream_t stream);
+                             LaunchAt at);
 hipError_t launch_listen_gather(const float *tap, const float *psd, const sdr_frame_rec *recs, const ListenerSlot *slots, const void *db_tab,
                                 uint64_t *raw_bits, float *tr_values, uint8_t *tr_raw, const BatchCursor *cur, ListenGeom g, int n_frames,
-                                int n_slots, int n_bands, hipStream_t stream);
+                                int n_slots, int n_bands, LaunchAt at);
 hipError_t launch_listen_decode(ListenerSlot *slots, const uint16_t *morse, const uint64_t *raw_bits,
                                 uint64_t *deb_bits, uint32_t *text, uint32_t *text_frames, sdr_edge *edges,
                                 uint32_t *edge_counts, uint8_t *tr_deb, DropCounters *drops, const BatchCursor *cur, ListenGeom g,
-                                int n_frames, int n_bands, uint32_t *edge_pos, int pos_stride, hipStream_t stream);
+                                int n_frames, int n_bands, uint32_t *edge_pos, int pos_stride, LaunchAt at);
 hipError_t launch_listener_stop(ListenerSlot *slot, const uint16_t *morse, uint32_t *text, uint32_t *text_frames, int text_cap,
                                 uint32_t frame, DropCounters *drops, hipStream_t stream);
 hipError_t launch_set_debounce(ListenerSlot *slots, int n, int threshold, hipStream_t stream);
@@ -230,19 +233,19 @@ hipError_t launch_set_debounce(ListenerSlot *slots, int n, int threshold, hipStr
 // in `parts` partial rows (slot 0's without the carry: it is added here, on the stream the carry is produced on)
 hipError_t launch_cumulate(const float *psd, const void *db_tab, float *carry0, float *carry1, int carry_in, float *cum_out,
                            const float *cum_part, const BatchCursor *cur, CumGeom g, int n_slots, int n_bands, bool bound, bool bound_done,
-                           int parts, hipStream_t stream);
+                           int parts, LaunchAt at);
 // k_noise_scan.hip: the FindNoiseFloor fields of every frame's record, certified or literal, and (do_bound) the unit counts
 // of the completed cumulations, a slot's frames dealt over `parts` workgroups - one kernel
 hipError_t launch_psd_scan(const float *psd, sdr_frame_rec *recs, float *cum_out, float *cum_part, const BatchCursor *cur, NoiseGeom ng,
-                           CumGeom cg, int n_slots, int n_bands, bool do_bound, int parts, int force_exact, hipStream_t stream);
+                           CumGeom cg, int n_slots, int n_bands, bool do_bound, int parts, int force_exact, LaunchAt at);
 hipError_t launch_noise_exact_check(const float *psd_band, sdr_frame_rec *recs_band, NoiseGeom ng, int n_frames, unsigned *mismatches,
                                     hipStream_t stream);
 hipError_t launch_spectrum_row(const float *psd_row, float *out, int n, hipStream_t stream);
 hipError_t launch_pack_listen(ListenerSlot *slots, const sdr_edge *edges, const uint32_t *edge_counts, const uint32_t *text,
                               const uint32_t *text_frames, const DropCounters *drops, ResultsLayout lay, int n_slots, int n_bands, unsigned char *host,
-                              hipStream_t stream);
+                              LaunchAt at);
 hipError_t launch_pack_peaks(const DevPeak *peaks, const int *counts, const BatchCursor *cur, ResultsLayout lay, int find_peaks,
-                             int n_frames, int n_chunks, int n_bands, unsigned char *host, hipStream_t stream);
+                             int n_frames, int n_chunks, int n_bands, unsigned char *host, LaunchAt at);
 // cumulations a batch of n_frames completes when it starts at cumulationCount count0
 __host__ __device__ inline int chunks_completed(int count0, int n_frames)
 {
@@ -253,7 +256,7 @@ hipError_t launch_unpack_be16(const uint8_t *raw, float *out, size_t n_values, h
 hipError_t launch_unpack_sc16(const int16_t *raw, float *out, size_t n_values, hipStream_t stream);  // little-endian int16 values
 hipError_t launch_find_peaks(float *cum, const float *psd, const void *db_tab, const float *carry0, const float *carry1, int carry_in,
                              const sdr_frame_rec *recs, DevPeak *peaks, int *counts, const BatchCursor *cur, PeakGeom g, int n_frames,
-                             int n_chunks, int n_bands, Refine refine, FftTap tap, hipStream_t stream);  // tap: .wide / .used / .n / .stride of this batch's FFT (or null)
+                             int n_chunks, int n_bands, Refine refine, FftTap tap, LaunchAt at);  // tap: .wide / .used / .n / .stride of this batch's FFT (or null)
 // k_cum_rows: every cumulation the batch completes, exact and reduced to `columns` group maxima, into the row block
 hipError_t launch_cum_rows(const float *psd, const void *db_tab, const float *carry0, const float *carry1, int carry_in, const BatchCursor *cur,
                            CumGeom g, int columns, int n_chunks, int n_bands, float *rows, hipStream_t stream);

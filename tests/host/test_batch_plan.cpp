@@ -372,6 +372,106 @@ void test_forced_rest()
     std::printf("forced ok\n");
 }
 
+// The order of a batch's stages: who waits for whom, which stage stands for its stream when a set is reused, which graph
+// a kernel belongs to - literal tables at the plans that differ.
+void test_order()
+{
+    using namespace sdr;
+    struct Dep { int k, dep; };
+    auto deps_are = [](const sdr::StageDeps &s, std::initializer_list<Dep> want) {
+        bool same = s.n == (int)want.size() && s.n <= sdr::StageDeps::kMax;
+        int i = 0;
+        for (const Dep &w : want) {
+            same = same && i < s.n && s.d[i].k == w.k && s.d[i].dep == w.dep;
+            i++;
+        }
+        return same;
+    };
+    // the dependency list in issue order: the default plan (no bound at this length), with and without the peak scan
+    const BatchPlan def = plan(1, 16384, 2048);
+    CHECK(!def.bound_done);
+    CHECK(deps_are(stage_deps(def, true), {{K_WINDOW_MEANS, K_FFT},
+                                           {K_NOISE_STATS, K_WINDOW_MEANS},
+                                           {K_THRESHOLDS, K_NOISE_STATS},
+                                           {K_LISTEN_GATHER, K_THRESHOLDS},
+                                           {K_LISTEN_GATHER, K_FFT},
+                                           {K_LISTEN_DECODE, K_LISTEN_GATHER},
+                                           {K_CUMULATE, K_FFT},
+                                           {K_FIND_PEAKS, K_CUMULATE},
+                                           {K_FIND_PEAKS, K_THRESHOLDS}}));
+    CHECK(deps_are(stage_deps(def, false), {{K_WINDOW_MEANS, K_FFT},
+                                            {K_NOISE_STATS, K_WINDOW_MEANS},
+                                            {K_THRESHOLDS, K_NOISE_STATS},
+                                            {K_LISTEN_GATHER, K_THRESHOLDS},
+                                            {K_LISTEN_GATHER, K_FFT},
+                                            {K_LISTEN_DECODE, K_LISTEN_GATHER},
+                                            {K_CUMULATE, K_FFT},
+                                            {K_FIND_PEAKS, K_CUMULATE}}));
+    // bound_done: the cumulation also waits for the scan (the window-means stage), behind its wait for the FFT
+    const BatchPlan bd = plan(1, 16384, 8192);
+    CHECK(bd.bound_done);
+    CHECK(deps_are(stage_deps(bd, true), {{K_WINDOW_MEANS, K_FFT},
+                                          {K_NOISE_STATS, K_WINDOW_MEANS},
+                                          {K_THRESHOLDS, K_NOISE_STATS},
+                                          {K_LISTEN_GATHER, K_THRESHOLDS},
+                                          {K_LISTEN_GATHER, K_FFT},
+                                          {K_LISTEN_DECODE, K_LISTEN_GATHER},
+                                          {K_CUMULATE, K_FFT},
+                                          {K_CUMULATE, K_WINDOW_MEANS},
+                                          {K_FIND_PEAKS, K_CUMULATE},
+                                          {K_FIND_PEAKS, K_THRESHOLDS}}));
+    Switches chains;
+    chains.noise_scan = false;
+    const BatchPlan ch = plan(1, 16384, 8192, 0, false, 16, chains);  // (bounded, but k_cum_bound forms the counts on the peaks stream)
+    CHECK(ch.bound && !ch.bound_done && stage_deps(ch, true).n == 9 && stage_deps(ch, false).n == 8);
+    // the list does not depend on the streams: the small-geometry plan has the default one
+    CHECK(stage_deps(plan(1, 512, 2048), true).n == 9 && stage_deps(plan(1, 512, 2048), true).d[3].k == K_LISTEN_GATHER);
+
+    // set reuse: the last stage issued on each stream stands for it; the FFT's stream is left out
+    int s[N_STAGES];
+    set_reuse_stages(def, s);
+    CHECK(s[S_FFT] == -1 && s[S_NOISE] == K_NOISE_STATS && s[S_LISTEN] == K_LISTEN_DECODE && s[S_PEAKS] == K_FIND_PEAKS);
+    set_reuse_stages(bd, s);
+    CHECK(s[S_FFT] == -1 && s[S_NOISE] == K_NOISE_STATS && s[S_LISTEN] == K_LISTEN_DECODE && s[S_PEAKS] == K_FIND_PEAKS);
+    // small geometry: the gather runs on S_PEAKS, decode alone stands for S_LISTEN
+    const BatchPlan small = plan(1, 4096, 2048);
+    CHECK(small.stream[K_LISTEN_GATHER] == S_PEAKS);
+    set_reuse_stages(small, s);
+    CHECK(s[S_FFT] == -1 && s[S_NOISE] == K_NOISE_STATS && s[S_LISTEN] == K_LISTEN_DECODE && s[S_PEAKS] == K_FIND_PEAKS);
+    // a plan that moves stages (SDR_DIAG_PLAN): a stream without a stage has none, a stage beside the FFT is left out
+    Switches moved;
+    moved.diag_plan[K_LISTEN_DECODE] = S_PEAKS;  // (the gather is on S_PEAKS at this geometry: nothing is left on S_LISTEN)
+    moved.diag_plan[K_NOISE_STATS] = S_FFT;
+    set_reuse_stages(plan(1, 4096, 2048, 0, false, 16, moved), s);
+    CHECK(s[S_FFT] == -1 && s[S_NOISE] == K_WINDOW_MEANS && s[S_LISTEN] == -1 && s[S_PEAKS] == K_FIND_PEAKS);
+    Switches one;  // SDR_NO_OVERLAP is not a plan matter (every stream IS the caller's), but a plan on one stream waits for nothing
+    for (int k = 0; k < K_COUNT; k++)
+        one.diag_plan[k] = S_FFT;
+    set_reuse_stages(plan(1, 4096, 2048, 0, false, 16, one), s);
+    CHECK(s[S_FFT] == -1 && s[S_NOISE] == -1 && s[S_LISTEN] == -1 && s[S_PEAKS] == -1);
+
+    // graph membership: every kernel against every graph, under capture (the gather stays on S_LISTEN there)
+    CHECK(G_THRESHOLDS == 4 && N_GRAPHS == 5);
+    const int graph_of[K_COUNT] = {/* fft */ S_FFT,       /* window means */ S_NOISE, /* noise stats */ S_NOISE, /* thresholds */ G_THRESHOLDS,
+                                   /* gather */ S_LISTEN, /* cumulate */ S_PEAKS,     /* find peaks */ S_PEAKS,  /* decode */ S_LISTEN};
+    for (int n : {512, 16384}) {
+        const BatchPlan cap = plan(1, n, 2048, 0, true);
+        for (int k = 0; k < K_COUNT; k++)
+            for (int g = 0; g < N_GRAPHS; g++)
+                CHECK(in_graph(cap, k, g) == (g == graph_of[k]));
+    }
+    // ... and by stream, not by a table: a moved stage follows its stream, the thresholds stay in their own graph
+    Switches mv;
+    mv.diag_plan[K_LISTEN_GATHER] = S_PEAKS;
+    mv.diag_plan[K_THRESHOLDS] = S_NOISE;
+    const BatchPlan mvp = plan(1, 16384, 2048, 0, true, 16, mv);
+    for (int g = 0; g < N_GRAPHS; g++) {
+        CHECK(in_graph(mvp, K_LISTEN_GATHER, g) == (g == S_PEAKS));
+        CHECK(in_graph(mvp, K_THRESHOLDS, g) == (g == G_THRESHOLDS));
+    }
+    std::printf("order ok\n");
+}
+
 // Invariants and the rules before the plan, over geometries, lengths, phases, listener counts and switch settings.
 void test_sweep()
 {
@@ -439,6 +539,7 @@ int main()
     test_refine();
     test_counts();
     test_forced_rest();
+    test_order();
     test_sweep();
     return g_failures ? 1 : 0;
 }

@@ -1,5 +1,5 @@
 """The batch plan (sdrainer_amd/csrc/host/batch_plan.h: the environment's switches, the stream of every kernel, the FFT
-kernel, the noise path, the bound and its refinement, the slot and chunk counts) driven without a GPU by
+kernel, the noise path, the bound and its refinement, the slot and chunk counts, the order of the stages) driven without a GPU by
 tests/host/test_batch_plan.cpp: every rule pinned where it switches, every switch forced, invariants over a sweep -
 under the sanitizers, and with the -DSDR_DIAG overrides compiled in."""
 import os
@@ -23,4 +23,4 @@ def test_batch_plan(tmp_path, sanitizer, defines):
     run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0 and "FAILED" not in run.stdout, run.stdout + run.stderr
     assert run.stdout.split() == ["switches", "ok", "fft", "ok", "bound", "ok", "parts", "ok", "gather", "ok", "refine", "ok", "counts", "ok",
-                                  "forced", "ok", "sweep", "ok"]
+                                  "forced", "ok", "order", "ok", "sweep", "ok"]

@@ -37,28 +37,28 @@ __device__ unsigned long long g_fft_wg[2048][4];
 namespace sdr {
 // (this tool times float32 input only: launch_fft's sc16 branch is linked to nothing - k_fft_r32_sc16.hip is k_fft_r32.hip
 // compiled again and cannot share this translation unit)
-hipError_t launch_fft_r32_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, hipStream_t)
+hipError_t launch_fft_r32_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
 {
     return hipErrorNotSupported;
 }
 // (nor dense input's strided twins, k_fft_r32_hop.hip / k_fft_r32_hop_sc16.hip: this tool's frames do not overlap)
-hipError_t launch_fft_r32_hop(const float *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, hipStream_t)
+hipError_t launch_fft_r32_hop(const float *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
 {
     return hipErrorNotSupported;
 }
-hipError_t launch_fft_r32_hop_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, hipStream_t)
+hipError_t launch_fft_r32_hop_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
 {
     return hipErrorNotSupported;
 }
 // (nor the two-phase kernels of N = 32768 / 65536, k_fft_2p.hip)
 hipError_t launch_fft_2p(int, FftChoice, InFormat, const void *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap,
-                         hipStream_t)
+                         LaunchAt)
 {
     return hipErrorNotSupported;
 }
 // (nor the windowed kernels, k_fft_psd_win.hip: this tool sets no window)
 hipError_t launch_fft_win(int, FftChoice, InFormat, const void *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap,
-                          hipStream_t)
+                          LaunchAt)
 {
     return hipErrorNotSupported;
 }
@@ -133,7 +133,7 @@ int main(int argc, char **argv)
     }
     // the library's choice for this batch (SDR_FFT_R32 / SDR_FFT_FPW honoured as in the pipeline)
     const sdr::FftChoice choice = sdr::fft_choice(sdr::read_switches(), N, frames, bands, n_tap);
-    auto launch = [&](hipStream_t st) { return sdr::launch_fft(logn, choice, iq, nullptr, tw, pd, frames, bands, (size_t)frames * N, N, frames, tap, st); };
+    auto launch = [&](hipStream_t st) { return sdr::launch_fft(logn, choice, sdr::InFormat::F32, iq, nullptr, tw, pd, frames, bands, (size_t)frames * N, N, frames, tap, st); };
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));

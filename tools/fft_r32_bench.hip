@@ -28,28 +28,28 @@ __device__ unsigned g_r32_phases[8][16];
 namespace sdr {
 // (this tool times float32 input only: launch_fft's sc16 branch is linked to nothing - k_fft_r32_sc16.hip is k_fft_r32.hip
 // compiled again and cannot share this translation unit)
-hipError_t launch_fft_r32_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, hipStream_t)
+hipError_t launch_fft_r32_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
 {
     return hipErrorNotSupported;
 }
 // (nor dense input's strided twins, k_fft_r32_hop.hip / k_fft_r32_hop_sc16.hip: this tool's frames do not overlap)
-hipError_t launch_fft_r32_hop(const float *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, hipStream_t)
+hipError_t launch_fft_r32_hop(const float *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
 {
     return hipErrorNotSupported;
 }
-hipError_t launch_fft_r32_hop_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, hipStream_t)
+hipError_t launch_fft_r32_hop_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
 {
     return hipErrorNotSupported;
 }
 // (nor the two-phase kernels of N = 32768 / 65536, k_fft_2p.hip)
 hipError_t launch_fft_2p(int, FftChoice, InFormat, const void *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap,
-                         hipStream_t)
+                         LaunchAt)
 {
     return hipErrorNotSupported;
 }
 // (nor the windowed kernels, k_fft_psd_win.hip: this tool sets no window)
 hipError_t launch_fft_win(int, FftChoice, InFormat, const void *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap,
-                          hipStream_t)
+                          LaunchAt)
 {
     return hipErrorNotSupported;
 }
@@ -147,7 +147,7 @@ int main(int argc, char **argv)
     }
     sdr::FftChoice c16;  // the 16-point kernel (SDR_FFT_FPW honoured as in the pipeline)
     c16.fpw = sdr::read_switches().fft_fpw;
-    auto launch16 = [&](hipStream_t st) { return sdr::launch_fft(logn, c16, iq, nullptr, tw16, pd16, frames, bands, (size_t)frames * N, N, frames, tap16, st); };
+    auto launch16 = [&](hipStream_t st) { return sdr::launch_fft(logn, c16, sdr::InFormat::F32, iq, nullptr, tw16, pd16, frames, bands, (size_t)frames * N, N, frames, tap16, st); };
     const int reserve = std::max(0, sdr::read_switches().fft_reserve);  // SDR_FFT_RESERVE: CUs the 32-point kernel's grid leaves free
     auto launch32 = [&](hipStream_t st) { return sdr::launch_fft_r32(iq, nullptr, tw32, pd32, frames, bands, (size_t)frames * N, N, frames, tap32, reserve, true, st); };
     hipEvent_t e0, e1;
