@@ -353,6 +353,52 @@ int sdr_enable_rows(sdr_bank *bank, int columns);
 int sdr_row_columns(sdr_bank *bank);
 int sdr_poll_rows(sdr_bank *bank, float *rows, int rows_cap, int *n_rows, int64_t *batch_index, int wait);
 
+/* Listener reports: how strong every listened signal was in a batch, and how fast it is keyed - the "dB over noise, WPM"
+ * of a skimmer's spot line - travelling with the batch, without a bank created with trace = 1 and without a
+ * synchronising read per listener.
+ * With reports on, every batch delivers one sdr_listener_report for each listener slot that was active in the batch's
+ * listen stage, ordered by band, then listener id.  For such a listener the ticks f run over the frames of the batch that
+ * reach it (from start_frame on for a listener bound with sdr_attach_at, every frame otherwise; a listener whose
+ * start_frame lies behind the batch reports ticks = 0).  Per tick
+ *     v[f]  = the float32 value the gather compares with the frame's threshold, dB + SDR_DBM_SHIFT (Listener.Listen's value),
+ *     d[f]  = the DEBOUNCED bit, what the decoder sees,
+ *     nf[f] = sdr_frame_rec.noise_floor of the frame;
+ * a tick is MEASURED if neither v[f] nor nf[f] is NaN.  Values are quantised to 1/256 dB,
+ *     q(x) = (int32) rint(clamp(x, -1024, 1024) * 256)
+ * in float32 with round-half-to-even (the product is exact; +-Inf clamps).  Every field but wpm is an integer function of
+ * exact float32 values and sums and maxima of integers have no order: any kernel schedule gives the same bits, and the
+ * reports of consecutive batches add up (sums and counts add, on_max_q takes the maximum, wpm the last value) - any cut of
+ * a stream into batches gives the same totals.  That is why the record holds fixed-point sums and not float means.
+ * The caller's SNR is (on_sum_q - floor_sum_q) / (256.0 * ticks_on): the mean key-down level over the band's noise floor
+ * in dB.  Nothing is divided on the device.  A band of zero samples clamps at q = -262144 (v and nf are -Inf). */
+typedef struct sdr_listener_report {      /* 64 bytes */
+    int32_t band, listener, bin;
+    int32_t ticks;        /* frames of this batch that reached the listener                      */
+    int32_t ticks_on;     /* measured ticks with d = 1                                           */
+    int32_t ticks_off;    /* measured ticks with d = 0   (ticks - on - off: unmeasured, NaN)     */
+    int32_t on_max_q;     /* max q(v) over the ticks_on ticks; INT32_MIN if there are none       */
+    int32_t reserved;     /* 0 */
+    int64_t on_sum_q;     /* sum q(v)  over the ticks_on ticks                                   */
+    int64_t off_sum_q;    /* sum q(v)  over the ticks_off ticks                                  */
+    int64_t floor_sum_q;  /* sum q(nf) over the ticks_on ticks                                   */
+    double  wpm;          /* Decoder.wpm behind the batch's last tick (out12[3] of sdr_read_decoder_state) */
+} sdr_listener_report;
+/*   sdr_enable_reports(on): off in a new bank (it launches exactly the kernels it launched before this call existed).
+ *     Needs sdr_enable_results (SDR_ERR_STATE without; switching results off switches reports off); SDR_ERR_STATE while a
+ *     listen half is pending.  The first call that switches reports on allocates pinned memory (n_bands * max_listeners
+ *     records per buffer set) and drains the bank.  It invalidates a captured graph (sdr_graph_launch returns SDR_ERR_STATE
+ *     until the next capture; a capture made with reports on records the report kernels).
+ *   sdr_reports_enabled: the current setting.
+ *   sdr_poll_reports: a peek at the batch the next sdr_poll hands out, which stays undelivered: its records to `out` (cap
+ *     counts records), *n_out and *batch_index set.  It waits for the device and returns SDR_ERR_WOULD_BLOCK exactly where
+ *     sdr_poll would: the reports belong to the listen half, so a batch whose listen half is deferred shows them only
+ *     after sdr_process_listen.  SDR_ERR_BAD_SIZE with *n_out set to the records needed and nothing copied if cap is too
+ *     small; SDR_OK with *n_out = 0 for a batch processed with reports off or without an active listener.  A batch parked
+ *     on the host keeps its reports.  One consumer thread, as for sdr_poll. */
+int sdr_enable_reports(sdr_bank *bank, int on);
+int sdr_reports_enabled(sdr_bank *bank);
+int sdr_poll_reports(sdr_bank *bank, sdr_listener_report *out, int cap, int *n_out, int64_t *batch_index, int wait);
+
 /* Strain-mode discovery over a long batch (rx/receiver.go:404-426: one listener bound per completed cumulation, to a
  * peak of that cumulation, listening from the very next frame).  With deferral on (needs sdr_enable_results), a
  * sdr_process_* call runs the spectral half of the batch only - FFT, noise floor, thresholds, cumulations and FindPeaks
@@ -381,7 +427,7 @@ int sdr_read_drop_counters(sdr_bank *bank, uint64_t *runes_dropped, uint64_t *ed
  * their own (allocated at capture), so that consecutive replays overlap stage by stage like consecutive eager batches.
  * Needs a bank on a real stream (sdr_set_stream with a non-null stream) and, once captured, all processing to go
  * through sdr_graph_launch (sdr_process_* return SDR_ERR_STATE until sdr_graph_release).  Attaching or detaching a
- * listener, sdr_enable_results, sdr_enable_rows and sdr_set_find_peaks invalidate the capture (sdr_graph_launch returns SDR_ERR_STATE:
+ * listener, sdr_enable_results, sdr_enable_rows, sdr_enable_reports and sdr_set_find_peaks invalidate the capture (sdr_graph_launch returns SDR_ERR_STATE:
  * capture again).  Results are read / polled exactly as after sdr_process_device;
  * the "last batch" of the read calls is the last replay's last.  Not offered with overlapped frames yet:
  * sdr_graph_capture(_sc16) on a bank with hop < block_size returns SDR_ERR_STATE. */
@@ -451,6 +497,11 @@ int sdr_group_poll(sdr_group *group, sdr_results *results, int wait);
  * chunk); the following sdr_group_poll delivers the same batch.  Statuses as sdr_poll_rows / sdr_group_poll. */
 int sdr_group_enable_rows(sdr_group *group, int columns);
 int sdr_group_poll_rows(sdr_group *group, float *rows, int rows_cap, int *n_rows, int64_t *batch_index, int wait);
+/* sdr_enable_reports on every member (refusals as sdr_group_enable_rows).  sdr_group_poll_reports: the reports of the oldest
+ * batch EVERY member has finished, merged into one bank's order (global band, then listener id) with global band numbers;
+ * the following sdr_group_poll delivers the same batch.  Statuses as sdr_poll_reports / sdr_group_poll. */
+int sdr_group_enable_reports(sdr_group *group, int on);
+int sdr_group_poll_reports(sdr_group *group, sdr_listener_report *out, int cap, int *n_out, int64_t *batch_index, int wait);
 int sdr_group_defer_listen(sdr_group *group, int on);
 int sdr_group_poll_peaks(sdr_group *group, sdr_results *results, int wait);
 int sdr_group_process_listen(sdr_group *group);
@@ -503,7 +554,8 @@ int sdr_scope_read_decode(sdr_bank *bank, int band, int listener_id, sdr_scope_d
 /* When enabled every kernel launch is bracketed by HIP events on the bank's stream. */
 int sdr_profile_enable(sdr_bank *bank, int on);
 /* kernel: 0 fft_project, 1 window_means, 2 noise_stats, 3 thresholds, 4 listen_gather,
- *         5 cumulate, 6 find_peaks, 7 listen_decode, 8 cum_rows (sdr_enable_rows; no launch while rows are off).
+ *         5 cumulate, 6 find_peaks, 7 listen_decode, 8 cum_rows (sdr_enable_rows; no launch while rows are off),
+ *         9 listen_report, 10 report_marks (sdr_enable_reports; no launch while reports are off).
  * Returns accumulated milliseconds and launch count. */
 int sdr_profile_read(sdr_bank *bank, int kernel, double *total_ms, int *launches);
 int sdr_profile_reset(sdr_bank *bank);

@@ -18,6 +18,7 @@ OK, ERR_BAD_ARG, ERR_BAD_RATE, ERR_BAD_SIZE, ERR_WOULD_DROP, ERR_HIP, ERR_NO_SLO
 CUMULATION_SIZE = 100
 KERNELS = ("k_fft_psd", "k_window_means", "k_noise_stats", "k_thresholds", "k_listen_gather", "k_cumulate",
            "k_find_peaks", "k_listen_decode")
+REPORT_KERNELS = ("k_listen_report", "k_report_marks")  # profile slots 9 and 10 (launched only while reports are on: Bank.enable_reports)
 ROWS_KERNEL = "k_cum_rows"  # profile slot 8, behind the eight stages (launched only while rows are on: Bank.enable_rows)
 
 
@@ -71,6 +72,22 @@ LISTENER_RESULT_DTYPE = np.dtype([("band", "<i4"), ("listener", "<i4"), ("first_
                                   ("first_rune", "<i4"), ("n_runes", "<i4")])
 
 
+# sdr_listener_report (64 bytes): one listener's level, noise floor and speed over one batch, as sums that add up
+REPORT_DTYPE = np.dtype([("band", "<i4"), ("listener", "<i4"), ("bin", "<i4"), ("ticks", "<i4"), ("ticks_on", "<i4"),
+                         ("ticks_off", "<i4"), ("on_max_q", "<i4"), ("reserved", "<i4"), ("on_sum_q", "<i8"), ("off_sum_q", "<i8"),
+                         ("floor_sum_q", "<i8"), ("wpm", "<f8")])
+assert REPORT_DTYPE.itemsize == 64
+
+
+def report_snr_db(reports) -> np.ndarray:
+    """The mean key-down level over the band's noise floor in dB, per record: (on_sum_q - floor_sum_q) / (256 ticks_on);
+    NaN where a listener had no measured key-down tick."""
+    reports = np.asarray(reports)
+    on = reports["ticks_on"].astype(np.float64)
+    diff = (reports["on_sum_q"] - reports["floor_sum_q"]).astype(np.float64)
+    return np.where(on > 0, diff / (256.0 * np.maximum(on, 1.0)), np.nan)
+
+
 class ScopeSpectralFrame(C.Structure):
     """sdr_scope_spectral_frame: scope.SpectralFrame without its Values (scope/scope.go:24-31)."""
     _fields_ = [("frame", C.c_int64), ("from_frequency", C.c_double), ("to_frequency", C.c_double),
@@ -121,6 +138,7 @@ SYMBOLS = (
     "sdr_hop sdr_process_device_stream sdr_process_device_stream_sc16 "
     "sdr_set_window sdr_group_set_window "
     "sdr_enable_rows sdr_row_columns sdr_poll_rows sdr_group_enable_rows sdr_group_poll_rows "
+    "sdr_enable_reports sdr_reports_enabled sdr_poll_reports sdr_group_enable_reports sdr_group_poll_reports "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -252,6 +270,11 @@ def load():
     sig("sdr_poll_rows", C.c_int, vp, fp, C.c_int, ip, C.POINTER(C.c_int64), C.c_int)
     sig("sdr_group_enable_rows", C.c_int, vp, C.c_int)
     sig("sdr_group_poll_rows", C.c_int, vp, fp, C.c_int, ip, C.POINTER(C.c_int64), C.c_int)
+    sig("sdr_enable_reports", C.c_int, vp, C.c_int)
+    sig("sdr_reports_enabled", C.c_int, vp)
+    sig("sdr_poll_reports", C.c_int, vp, vp, C.c_int, ip, C.POINTER(C.c_int64), C.c_int)
+    sig("sdr_group_enable_reports", C.c_int, vp, C.c_int)
+    sig("sdr_group_poll_reports", C.c_int, vp, vp, C.c_int, ip, C.POINTER(C.c_int64), C.c_int)
     _lib = L
     return L
 
@@ -310,6 +333,32 @@ def _poll_rows(entry, handle, state: dict, columns: int, wait: bool, rows_cap):
             e.n_rows = n.value
             raise
     return batch.value, buf[:n.value * columns].reshape(n.value, columns).copy()
+
+
+def _poll_reports(entry, handle, state: dict, wait: bool, cap):
+    """sdr_poll_reports / sdr_group_poll_reports: (batch_index, ndarray of REPORT_DTYPE), or None where the call would
+    block.  The buffer grows to what the call asks for; with a fixed cap (in records) ERR_BAD_SIZE is raised instead, the
+    records needed in the exception's n_out."""
+    n, batch = C.c_int(), C.c_int64()
+    want = cap if cap is not None else state.get("cap", 0)
+    for _ in range(2):
+        buf = state.get("buf")
+        if buf is None or buf.size < want:
+            buf = state["buf"] = np.zeros(max(want, 1), REPORT_DTYPE)
+        rc = entry(handle, C.c_void_p(buf.ctypes.data), want, C.byref(n), C.byref(batch), int(wait))
+        if rc == ERR_WOULD_BLOCK:
+            return None
+        if rc == ERR_BAD_SIZE and cap is None:
+            want = state["cap"] = n.value
+            continue
+        break
+    if rc != OK:
+        try:
+            _check(rc)
+        except SdrError as e:
+            e.n_out = n.value
+            raise
+    return batch.value, buf[:n.value].copy()
 
 
 def _results_dict(r: Results, bufs: dict, rune_frames: np.ndarray, copy: bool) -> dict:
@@ -634,6 +683,21 @@ class Bank:
             self._rows_state = {}
         return _poll_rows(self._L.sdr_poll_rows, self._h, self._rows_state, getattr(self, "_rows_last", 0) or 1, wait, rows_cap)
 
+    def enable_reports(self, on: bool = True):
+        """sdr_enable_reports: one sdr_listener_report per active listener with every batch."""
+        _check(self._L.sdr_enable_reports(self._h, int(on)))
+
+    @property
+    def reports_enabled(self) -> bool:
+        return bool(self._L.sdr_reports_enabled(self._h))
+
+    def poll_reports(self, wait: bool = False, cap: int | None = None):
+        """sdr_poll_reports: (batch_index, ndarray of REPORT_DTYPE) of the oldest undelivered batch, which stays undelivered,
+        or None.  Records are ordered by band, then listener id."""
+        if not hasattr(self, "_reports_state"):
+            self._reports_state = {}
+        return _poll_reports(self._L.sdr_poll_reports, self._h, self._reports_state, wait, cap)
+
     def poll_peaks(self, wait: bool = True, copy: bool = True):
         """sdr_poll_peaks: chunks and peaks of the batch that waits for its listen half (it stays undelivered)."""
         return self.poll(wait, copy, _entry=self._L.sdr_poll_peaks)
@@ -678,7 +742,7 @@ class Bank:
 
     def profile_read(self) -> dict:
         out = {}
-        for k, name in enumerate(KERNELS + (ROWS_KERNEL,)):
+        for k, name in enumerate(KERNELS + (ROWS_KERNEL,) + REPORT_KERNELS):
             ms, n = C.c_double(), C.c_int()
             _check(self._L.sdr_profile_read(self._h, k, C.byref(ms), C.byref(n)))
             out[name] = (ms.value, n.value)
@@ -821,6 +885,16 @@ class Group:
         if not hasattr(self, "_rows_state"):
             self._rows_state = {}
         return _poll_rows(self._L.sdr_group_poll_rows, self._h, self._rows_state, getattr(self, "_row_columns", 0) or 1, wait, rows_cap)
+
+    def enable_reports(self, on: bool = True):
+        """sdr_group_enable_reports: Bank.enable_reports on every member."""
+        _check(self._L.sdr_group_enable_reports(self._h, int(on)))
+
+    def poll_reports(self, wait: bool = False, cap: int | None = None):
+        """sdr_group_poll_reports: as Bank.poll_reports, the members' records merged with global band numbers."""
+        if not hasattr(self, "_reports_state"):
+            self._reports_state = {}
+        return _poll_reports(self._L.sdr_group_poll_reports, self._h, self._reports_state, wait, cap)
 
     def defer_listen(self, on: bool = True):
         _check(self._L.sdr_group_defer_listen(self._h, int(on)))

@@ -3,7 +3,7 @@
 //   capi_bank.hip     create / destroy / control calls (attach, detach, setters), profiling
 //   capi_process.hip  the scheduler: one batch's kernels over the bank's four streams (eager, captured, deferred listen
 //                     half), the staged host input
-//   capi_results.hip  bulk delivery (sdr_enable_results / sdr_poll / sdr_poll_peaks) over host/delivery.h
+//   capi_results.hip  bulk delivery (sdr_enable_results / sdr_poll / sdr_poll_peaks, rows, listener reports) over host/delivery.h
 //   capi_graph.hip    graph mode (sdr_graph_*)
 //   capi_read.hip     per-listener / per-batch reads and the scope tap (they synchronise)
 #pragma once
@@ -78,8 +78,9 @@ inline int ilog2(int n)
     return s;
 }
 
-inline const char *const kKernelNames[sdr::K_PROFILE_COUNT] = {"k_fft_psd",       "k_window_means", "k_noise_stats", "k_thresholds",
-                                          "k_listen_gather", "k_cumulate",     "k_find_peaks",  "k_listen_decode", "k_cum_rows"};
+inline const char *const kKernelNames[sdr::K_PROFILE_SLOTS] = {"k_fft_psd",       "k_window_means", "k_noise_stats", "k_thresholds",
+                                          "k_listen_gather", "k_cumulate",     "k_find_peaks",  "k_listen_decode", "k_cum_rows",
+                                          "k_listen_report", "k_report_marks"};
 
 using sdr::G_THRESHOLDS, sdr::N_GRAPHS;  // graph mode's graphs: one per stream and the thresholds' (host/batch_plan.h in_graph)
 constexpr int GRAPH_PHASES = 4;  // graph mode: replays in flight, each with RING buffer sets of its own (sdr_graph_capture)
@@ -99,6 +100,7 @@ struct BatchSet {
     DevBuf<uint64_t> raw_bits, bits;  // [band][L][bit_words] before / after the debouncer
     DevBuf<sdr_edge> edges;           // [band][L][edge_cap]
     DevBuf<uint32_t> edge_counts;     // [band][L] edges produced by this batch
+    DevBuf<int32_t> report_marks;     // [band][L][2] where each listener starts / is tapped from in this batch (k_report_marks; reports only)
     DevBuf<float> tr_values;          // [band][max_batch][L] (trace only)
     DevBuf<uint8_t> tr_raw, tr_deb;
     DevBuf<sdr::ListenerSlot> slots_before;  // [band][L] the slots as the batch's decoders found them (trace only: sdr_scope_read_decode)
@@ -124,6 +126,7 @@ struct BatchSet {
         bits.release();
         edges.release();
         edge_counts.release();
+        report_marks.release();
         tr_values.release();
         tr_raw.release();
         tr_deb.release();
@@ -218,6 +221,7 @@ struct sdr_bank {
     bool graph_results_on = false;
     int graph_find_peaks = 0;
     int graph_rows = 0;  // ... and the rows kernel only if rows were on, with the column count of the capture
+    int graph_reports = 0;  // ... and the report kernels only if reports were (-1: the capture holds report blocks that are gone)
     // deferred listen half (sdr_defer_listen): the batch whose spectra exist and whose listeners have not run yet
     bool defer_listen = false, listen_pending = false;
     struct PendingListen {
@@ -236,6 +240,9 @@ struct sdr_bank {
     // waterfall rows (sdr_enable_rows): columns per row, 0 = off; the sets' pinned row blocks (host::ResultSet::rows) hold
     // max_chunks * n_bands rows of rows_alloc_columns values, allocated when rows are switched on
     int row_columns = 0, rows_alloc_columns = 0;
+    // listener reports (sdr_enable_reports): the sets' pinned report blocks (host::ResultSet::reports) hold n_bands *
+    // max_listeners records, allocated when reports are first switched on
+    bool reports_on = false, reports_alloc = false;
     sdr::ResultsLayout res_layout{};
     std::unique_ptr<host::DeliveryBackend> res_backend;
     std::unique_ptr<host::Delivery> results;
@@ -264,8 +271,8 @@ struct sdr_bank {
     std::vector<int> staged_kind;  // per band: 0 nothing staged, 1 float32 frames, 2 int16be frames, 3 sc16 frames
 
     bool profiling = false;
-    double prof_ms[sdr::K_PROFILE_COUNT] = {};
-    int prof_n[sdr::K_PROFILE_COUNT] = {};
+    double prof_ms[sdr::K_PROFILE_SLOTS] = {};
+    int prof_n[sdr::K_PROFILE_SLOTS] = {};
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
 
     sdr::NoiseGeom noise_geom() const
@@ -320,7 +327,7 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
 int process_device_impl(sdr_bank *b, const void *iq_dev, int n_frames, size_t in_stride, sdr::InFormat fmt = sdr::InFormat::F32);
 // (capi_results.hip)
 sdr::ResultsLayout make_results_layout(const sdr_bank *b);
-int results_attach_set(sdr_bank *b, int set_idx);  // the set's pinned block and events, once bulk delivery is on; its row block, once rows are
+int results_attach_set(sdr_bank *b, int set_idx);  // the set's pinned block and events, once bulk delivery is on; its row block, once rows are; its report block, once reports are
 void results_release_set(sdr_bank *b, int set_idx);  // ... and all of them freed
 // (capi_graph.hip)
 void drop_graphs(sdr_bank *b);

@@ -165,6 +165,7 @@ hipError_t alloc_set(sdr_bank *b, BatchSet &S)
     SET_ALLOC(S.bits, B * L * (size_t)b->bit_words);
     SET_ALLOC(S.edges, B * L * (size_t)b->edge_cap);
     SET_ALLOC(S.edge_counts, B * L);
+    SET_ALLOC(S.report_marks, B * L * 2);
     if (c.trace) {
         SET_ALLOC(S.tr_values, B * F * L);
         SET_ALLOC(S.tr_raw, B * F * L);
@@ -192,7 +193,7 @@ extern "C" {
 
 const char *sdr_last_error(void) { return g_last_error.c_str(); }
 int sdr_abi_version(void) { return SDR_ABI_VERSION; }
-const char *sdr_kernel_name(int kernel) { return (kernel >= 0 && kernel < sdr::K_PROFILE_COUNT) ? kKernelNames[kernel] : ""; }
+const char *sdr_kernel_name(int kernel) { return (kernel >= 0 && kernel < sdr::K_PROFILE_SLOTS) ? kKernelNames[kernel] : ""; }
 
 int sdr_self_check(int device_id)
 {
@@ -707,7 +708,7 @@ int sdr_profile_enable(sdr_bank *b, int on)
 
 int sdr_profile_read(sdr_bank *b, int kernel, double *total_ms, int *launches)
 {
-    if (!b || kernel < 0 || kernel >= sdr::K_PROFILE_COUNT)
+    if (!b || kernel < 0 || kernel >= sdr::K_PROFILE_SLOTS)
         return fail(SDR_ERR_BAD_ARG, "bad kernel id");
     int rc = sync_bank(b);
     if (rc)
@@ -726,7 +727,7 @@ int sdr_profile_reset(sdr_bank *b)
     int rc = sync_bank(b);
     if (rc)
         return rc;
-    for (int i = 0; i < sdr::K_PROFILE_COUNT; i++) {
+    for (int i = 0; i < sdr::K_PROFILE_SLOTS; i++) {
         b->prof_ms[i] = 0;
         b->prof_n[i] = 0;
     }

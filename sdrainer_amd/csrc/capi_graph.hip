@@ -228,6 +228,7 @@ static int graph_capture(sdr_bank *b, int n_frames, sdr::InFormat fmt)
     b->graph_results_on = b->results_on;
     b->graph_find_peaks = b->find_peaks;
     b->graph_rows = b->row_columns;
+    b->graph_reports = b->reports_on ? 1 : 0;
     return SDR_OK;
 }
 
@@ -250,8 +251,9 @@ static int graph_launch(sdr_bank *b, const void *const *iq_dev, sdr::InFormat fm
         return fail(SDR_ERR_STATE, "listeners were attached or detached since the capture: capture again");
     // the kernels that pack results, refine the cumulation and scan for peaks are nodes of the captured graphs or they are
     // not: a replay after sdr_enable_results / sdr_set_find_peaks changed either would publish batches no kernel fills
-    if (b->results_on != b->graph_results_on || b->find_peaks != b->graph_find_peaks || b->row_columns != b->graph_rows)
-        return fail(SDR_ERR_STATE, "sdr_enable_results / sdr_set_find_peaks / sdr_enable_rows changed since the capture: capture again");
+    if (b->results_on != b->graph_results_on || b->find_peaks != b->graph_find_peaks || b->row_columns != b->graph_rows ||
+        (b->reports_on ? 1 : 0) != b->graph_reports)
+        return fail(SDR_ERR_STATE, "sdr_enable_results / sdr_set_find_peaks / sdr_enable_rows / sdr_enable_reports changed since the capture: capture again");
     HIP_TRY(hipSetDevice(b->device));
     const bool dbg = b->sw.graph_debug;
     double tdbg[8] = {};
@@ -369,6 +371,9 @@ static int graph_launch(sdr_bank *b, const void *const *iq_dev, sdr::InFormat fm
             m.slots = max_slots;
             m.row_columns = b->graph_rows;
             m.rows = b->graph_rows ? meta[k].chunks * b->cfg.n_bands : 0;
+            m.reports = b->graph_reports > 0 && max_slots > 0 ? 1 : 0;
+            m.report_bands = b->cfg.n_bands;
+            m.report_stride = b->cfg.max_listeners;
             {
                 std::lock_guard<std::mutex> guard(b->center_mu);
                 m.center = b->center_frequency;

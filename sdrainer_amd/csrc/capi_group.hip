@@ -27,6 +27,10 @@ struct BankSource final : host::GroupSource {
     {
         return sdr_poll_rows((*banks)[(size_t)m], rows, rows_cap, n_rows, batch_index, wait ? 1 : 0);
     }
+    int poll_reports(int m, sdr_listener_report *out, int cap, int *n_out, int64_t *batch_index, bool wait) override
+    {
+        return sdr_poll_reports((*banks)[(size_t)m], out, cap, n_out, batch_index, wait ? 1 : 0);
+    }
     int report(int code, const char *msg) override { return sdr::set_error(code, msg); }
 };
 
@@ -371,6 +375,8 @@ int sdr_group_enable_results(sdr_group *g, int on)
     g->delivery->reset(on != 0);  // (undelivered batches are discarded with the mode, as every member discards its own)
     if (!on)
         g->delivery->set_rows(0);  // (the members switched their rows off with the results)
+    if (!on)
+        g->delivery->set_reports(false);  // (... and their reports)
     return SDR_OK;
 }
 
@@ -405,6 +411,36 @@ int sdr_group_poll_rows(sdr_group *g, float *rows, int rows_cap, int *n_rows, in
         return fail(SDR_ERR_BAD_ARG, "null argument");
     KeepDevice keep;
     return g->delivery->poll_rows(rows, rows_cap, n_rows, batch_index, wait != 0);
+}
+
+int sdr_group_enable_reports(sdr_group *g, int on)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    // what a member could refuse is checked for all of them first (sdr_group_enable_rows)
+    if (!g->delivery->on())
+        return fail(SDR_ERR_STATE, "reports need bulk delivery (sdr_group_enable_results)");
+    for (sdr_bank *b : g->banks)
+        if (sdr_listen_pending(b))
+            return fail(SDR_ERR_STATE, "a batch waits for its listen half (sdr_group_process_listen)");
+    if (g->delivery->parked() > 0)  // (a member batch taken with the old setting)
+        return fail(SDR_ERR_STATE, "a batch is half delivered: sdr_group_poll first");
+    KeepDevice keep;
+    for (sdr_bank *b : g->banks) {
+        const int rc = sdr_enable_reports(b, on);
+        if (rc)
+            return rc;
+    }
+    g->delivery->set_reports(on != 0);
+    return SDR_OK;
+}
+
+int sdr_group_poll_reports(sdr_group *g, sdr_listener_report *out, int cap, int *n_out, int64_t *batch_index, int wait)
+{
+    if (!g || !n_out || !batch_index || cap < 0 || (!out && cap > 0))
+        return fail(SDR_ERR_BAD_ARG, "null argument");
+    KeepDevice keep;
+    return g->delivery->poll_reports(out, cap, n_out, batch_index, wait != 0);
 }
 
 int sdr_group_poll(sdr_group *g, sdr_results *r, int wait)

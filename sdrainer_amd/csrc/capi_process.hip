@@ -8,7 +8,7 @@
 //   fft     k_fft_psd(i)                                          (the caller's stream)
 //   noise   k_window_means(i) -> k_noise_stats(i)
 //   peaks   k_thresholds(i) -> k_cum_bound(i), k_cumulate(i) -> k_find_peaks(i) (-> k_pack_peaks(i))
-//   listen  k_listen_gather(i) -> k_listen_decode(i) (-> k_pack_listen(i))
+//   listen  k_listen_gather(i) -> (k_report_marks(i) ->) k_listen_decode(i) (-> k_listen_report(i)) (-> k_pack_listen(i))
 //
 // Batch i's per-batch buffers (psd, tap, frame records, keying bits, peaks ...) live in set i % RING, and one event per
 // stage orders the stages across streams.  Which stream a stage runs on, who waits for whom, which stage stands for its
@@ -224,7 +224,7 @@ BatchIssue prepare_batch(sdr_bank *b, int n_frames, int capture_k, int capture_s
         is.max_slots = std::max(is.max_slots, b->n_slots[i]);
     is.count0 = b->cum_count;
     is.P = sdr::plan_batch(b->sw, sdr::BatchGeometry{c.n_bands, c.block_size, c.max_batch_frames, b->max_chunks, b->fft_queue_alone}, n_frames, is.count0,
-                           is.cap, is.max_slots, b->windowed, b->results_on ? b->row_columns : 0);
+                           is.cap, is.max_slots, b->windowed, b->results_on ? b->row_columns : 0, b->results_on && b->reports_on);
     is.deps = sdr::stage_deps(is.P, b->find_peaks && is.P.n_chunks > 0);
     is.cg = sdr::CumGeom{c.block_size, c.max_batch_frames, n_frames, is.count0, b->max_chunks};
     return is;
@@ -348,6 +348,12 @@ int issue_listen(const BatchIssue &is)
     if (c.trace && max_slots > 0 && is.on(sdr::K_LISTEN_DECODE))  // the decoders' state before this batch: the decoder scope replays from it
         HIP_TRY(hipMemcpyAsync(S.slots_before.p, b->slots.p, sizeof(sdr::ListenerSlot) * (size_t)B * (size_t)c.max_listeners, hipMemcpyDeviceToDevice,
                                is.stream(sdr::K_LISTEN_DECODE)));
+    // listener reports: where every listener starts and is tapped from in this batch, before the decoder moves the marks
+    const bool reports = is.P.reports && run == BatchIssue::LAUNCH && is.on(sdr::K_LISTEN_DECODE) && !is.skipped(sdr::K_LISTEN_DECODE);
+    if (reports) {
+        ProfScope ps(b, sdr::K_REPORT_MARKS, b->stream[is.P.reports_stream]);
+        HIP_TRY(sdr::launch_report_marks(b->slots.p, is.cur, lg, n_frames, B, S.report_marks.p, b->stream[is.P.reports_stream]));
+    }
     // (with bulk delivery the stage's event rides on the pack kernel below, not on the decoder)
     rc = is.stage(sdr::K_LISTEN_DECODE, run, !b->results_on, [&](sdr::LaunchAt at) {
         return sdr::launch_listen_decode(b->slots.p, b->morse.p, S.raw_bits.p, S.bits.p, b->text.p, b->text_frames.p, S.edges.p, S.edge_counts.p, S.tr_deb.p,
@@ -355,6 +361,13 @@ int issue_listen(const BatchIssue &is)
     });
     if (rc)
         return rc;
+    // ... and the reports themselves, straight into the set's report block: behind the decoder, in front of the pack kernel
+    // and so in front of the event sdr_poll looks at
+    if (reports) {
+        ProfScope ps(b, sdr::K_LISTEN_REPORT, b->stream[is.P.reports_stream]);
+        HIP_TRY(sdr::launch_listen_report(S.tap.p, S.psd.p, S.recs.p, b->slots.p, b->db_tab.p, S.bits.p, S.report_marks.p, lg, n_frames, max_slots, B,
+                                          is.RS->reports, b->stream[is.P.reports_stream]));
+    }
     if (b->results_on && is.on(sdr::K_LISTEN_DECODE)) {
         // delivery of this batch's edges and runes, behind the decoder on its stream; the decoder's event is
         // recorded behind it so that the set is not reused before the copy to the host has happened
@@ -429,6 +442,9 @@ int issue_cumulation(const BatchIssue &is)
         m.slots = is.do_listen ? is.max_slots : 0;  // (sdr_poll_peaks delivers the spectral half; the listen half fills this in)
         m.row_columns = P.rows ? b->row_columns : 0;
         m.rows = P.rows ? n_chunks * B : 0;
+        m.reports = P.reports && is.do_listen ? 1 : 0;  // (a deferred listen half says so itself: Delivery::complete)
+        m.report_bands = B;
+        m.report_stride = c.max_listeners;
         {
             std::lock_guard<std::mutex> guard(b->center_mu);
             m.center = b->center_frequency;
@@ -497,7 +513,7 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
         return rc;
     if (!do_spectra) {
         // the batch is complete: sdr_poll may have it
-        b->results->complete(is.si, is.max_slots, b->pend.batch);
+        b->results->complete(is.si, is.max_slots, b->pend.batch, is.P.reports ? 1 : 0);
         b->listen_pending = false;
         return SDR_OK;
     }

@@ -1,6 +1,7 @@
 // capi_results.hip — bulk delivery: every batch ends with two small kernels (k_results.hip) that copy what the batch
 // produced - peaks of each completed cumulation, each listener's keying edges, its newly decoded runes with their frames,
-// the bank's drop counters - into the batch's block of pinned host memory, used entries only; sdr_poll hands the oldest
+// the bank's drop counters - into the batch's block of pinned host memory, used entries only (waterfall rows and listener
+// reports go into blocks of their own, written by the kernels that form them); sdr_poll hands the oldest
 // finished batch to caller-owned buffers without draining the pipeline (the consumer side of rx.Reporter and the
 // listeners' io.Writer: rx/rx.go:11-17, rx/receiver.go:123,508-539).  Which batch sits where, and who may take it, is
 // host/delivery.h (plain C++, exercised without a GPU by tests/host/test_delivery_model.cpp); this file is its HIP
@@ -207,6 +208,14 @@ int results_attach_set(sdr_bank *b, int set_idx)
         memset(rows, 0, bytes);
         rs.rows = rows;
     }
+    // the report block: one record per listener slot of every band (0xff: listener = -1, "no listener in this slot")
+    if (b->reports_alloc && !rs.reports) {
+        sdr_listener_report *rep = nullptr;
+        const size_t bytes = sizeof(sdr_listener_report) * std::max<size_t>((size_t)b->cfg.n_bands * (size_t)b->cfg.max_listeners, 1);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&rep), bytes, hipHostMallocDefault));
+        memset(rep, 0xff, bytes);
+        rs.reports = rep;
+    }
     if (rs.block && rs.ev_listen && rs.ev_peaks)
         return SDR_OK;
     // (the events first, the block last: a set is "attached" only with all three - a failure half way leaves nothing a
@@ -237,12 +246,15 @@ void results_release_set(sdr_bank *b, int set_idx)
         (void)hipHostFree(rs.block);
     if (rs.rows)
         (void)hipHostFree(rs.rows);
+    if (rs.reports)
+        (void)hipHostFree(rs.reports);
     if (rs.ev_listen)
         (void)hipEventDestroy(static_cast<hipEvent_t>(rs.ev_listen));
     if (rs.ev_peaks)
         (void)hipEventDestroy(static_cast<hipEvent_t>(rs.ev_peaks));
     rs.block = nullptr;
     rs.rows = nullptr;
+    rs.reports = nullptr;
     rs.ev_listen = rs.ev_peaks = nullptr;
 }
 
@@ -270,6 +282,8 @@ int sdr_enable_results(sdr_bank *b, int on)
     b->results_on = on != 0;
     if (!on)
         b->row_columns = 0;  // (rows travel with the results)
+    if (!on)
+        b->reports_on = false;  // (... and so do the listener reports)
     b->results->reset(on != 0, b->batch_index);  // (undelivered batches are discarded with the mode)
     return SDR_OK;
 }
@@ -326,6 +340,50 @@ int sdr_poll_rows(sdr_bank *b, float *rows, int rows_cap, int *n_rows, int64_t *
     if (rc == SDR_OK || rc == SDR_ERR_BAD_SIZE) {
         *n_rows = out.n_rows;
         *batch_index = out.batch;
+    }
+    return rc;
+}
+
+// Listener reports.  The report blocks are allocated once, at the first call that switches reports on, with the bank
+// drained: a graph captured before that holds no report kernels and stays invalid until the next capture.
+int sdr_enable_reports(sdr_bank *b, int on)
+{
+    if (!b)
+        return fail(SDR_ERR_BAD_ARG, "null bank");
+    if (!b->results_on)
+        return fail(SDR_ERR_STATE, "reports need bulk delivery (sdr_enable_results)");
+    if (b->listen_pending)
+        return fail(SDR_ERR_STATE, "a batch waits for its listen half (sdr_process_listen)");
+    if (on && !b->reports_alloc) {
+        int rc = sync_bank(b);
+        if (rc)
+            return rc;
+        HIP_TRY(hipSetDevice(b->device));
+        b->reports_alloc = true;
+        for (int i = 0; i < (int)b->set.size(); i++)
+            if ((rc = results_attach_set(b, i)))
+                return rc;
+    }
+    b->reports_on = on != 0;  // (a captured graph notices: sdr_graph_launch compares it with the capture's)
+    return SDR_OK;
+}
+
+int sdr_reports_enabled(sdr_bank *b) { return b && b->reports_on ? 1 : 0; }
+
+int sdr_poll_reports(sdr_bank *b, sdr_listener_report *out, int cap, int *n_out, int64_t *batch_index, int wait)
+{
+    if (!b || !n_out || !batch_index || cap < 0 || (!out && cap > 0))
+        return fail(SDR_ERR_BAD_ARG, "null argument");
+    if (!b->results->on())
+        return fail(SDR_ERR_STATE, "bulk delivery is off (sdr_enable_results)");
+    HIP_TRY(hipSetDevice(b->device));
+    host::ReportsOut ro;
+    ro.out = out;
+    ro.cap = cap;
+    const int rc = b->results->peek_reports(&ro, wait != 0);
+    if (rc == SDR_OK || rc == SDR_ERR_BAD_SIZE) {
+        *n_out = ro.n;
+        *batch_index = ro.batch;
     }
     return rc;
 }

@@ -27,6 +27,9 @@ enum KernelId {
 // k_cum_rows (the waterfall rows of sdr_enable_rows) is no stage of the plan's table - it rides on the find-peaks stage's
 // stream and events - but it has a profile slot, behind the eight stages' (sdr_profile_read / sdr_kernel_name)
 constexpr int K_CUM_ROWS = K_COUNT, K_PROFILE_COUNT = K_COUNT + 1;
+// ... and so have the two kernels of sdr_enable_reports, which ride on the decode stage's stream and events (k_report.hip):
+// slots behind the rows kernel's.  K_PROFILE_SLOTS counts every profile slot.
+constexpr int K_LISTEN_REPORT = K_PROFILE_COUNT, K_REPORT_MARKS = K_PROFILE_COUNT + 1, K_PROFILE_SLOTS = K_PROFILE_COUNT + 2;
 // the bank's streams: four = the hardware queues HIP gives a process; with six streams created (two unused!) the step was
 // 0.49 ms instead of 0.25, with GPU_MAX_HW_QUEUES=8 and five or six in use 0.29-0.60
 enum Stage { S_FFT = 0, S_NOISE, S_LISTEN, S_PEAKS, N_STAGES };
@@ -233,13 +236,19 @@ struct BatchPlan {
     // cumulate step (the find-peaks stage's stream: its event, which sdr_poll looks at, follows).  Off: no launch at all.
     bool rows;
     int rows_stream;
+    // sdr_enable_reports: k_report_marks in front of the decoder and k_listen_report behind it, both on reports_stream
+    // (the decode stage's stream: its event, which sdr_poll looks at, follows the pack kernel behind them).  Only where the
+    // batch has listener slots; off: no launch at all.
+    bool reports;
+    int reports_stream;
 };
 
 // One batch of n_frames frames that starts at cumulationCount count0, max_slots listener slots in use.  capturing: the
 // batch is being recorded into a graph (sdr_graph_capture), replayed later at whatever count0 and without stream changes.
-// windowed: the bank has a window (fft_choice).  row_columns: sdr_enable_rows' setting (0: rows off).
+// windowed: the bank has a window (fft_choice).  row_columns: sdr_enable_rows' setting (0: rows off).  reports:
+// sdr_enable_reports' setting.
 inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_frames, int count0, bool capturing, int max_slots,
-                            bool windowed = false, int row_columns = 0)
+                            bool windowed = false, int row_columns = 0, bool reports = false)
 {
     BatchPlan p;
     // Which of the bank's four streams each kernel runs on.  The step is as long as the longest stream, and kernels that
@@ -306,6 +315,9 @@ inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_fr
     // rows only where the batch completes a cumulation (a captured batch may at any replay: n_chunks is its maximum)
     p.rows = row_columns > 0 && p.n_chunks > 0;
     p.rows_stream = p.stream[K_FIND_PEAKS];
+    // reports only where the listen stages run (issue_listen leaves them out without a listener slot)
+    p.reports = reports && max_slots > 0;
+    p.reports_stream = p.stream[K_LISTEN_DECODE];
     return p;
 }
 

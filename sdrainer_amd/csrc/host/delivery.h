@@ -37,6 +37,10 @@ struct BatchMeta {
     // waterfall rows (sdr_enable_rows): the batch's row block holds `rows` rows of `row_columns` float32 values, one per
     // completed cumulation, by band, then chunk; 0 / 0: the batch completed none or was processed with rows off
     int rows = 0, row_columns = 0;
+    // listener reports (sdr_enable_reports): reports != 0: the batch's report block holds one record per listener slot,
+    // [report_bands][report_stride], of which the first `slots` per band were written (listener = -1: the slot was not
+    // active); 0: the batch was processed with reports off or without a listener slot
+    int reports = 0, report_bands = 0, report_stride = 0;
 };
 
 // the delivery side of one buffer set
@@ -45,6 +49,8 @@ struct ResultSet {
     unsigned char *block = nullptr;  // the set's pinned block (device kernels write it, the host reads it behind the events)
     void *ev_listen = nullptr, *ev_peaks = nullptr;  // recorded behind the kernels that fill the block
     float *rows = nullptr;  // the set's pinned row block (k_cum_rows writes it in front of ev_peaks), once rows were switched on
+    // the set's pinned report block (k_listen_report writes it in front of ev_listen), once reports were switched on
+    sdr_listener_report *reports = nullptr;
 };
 
 // sdr_poll_rows: the caller's buffer (in), what was found (out)
@@ -52,6 +58,14 @@ struct RowsOut {
     float *rows = nullptr;
     int rows_cap = 0;  // in rows
     int n_rows = 0, columns = 0;
+    int64_t batch = -1;
+};
+
+// sdr_poll_reports: the caller's buffer (in), what was found (out)
+struct ReportsOut {
+    sdr_listener_report *out = nullptr;
+    int cap = 0;  // in records
+    int n = 0;
     int64_t batch = -1;
 };
 
@@ -72,6 +86,7 @@ public:
         BatchMeta meta;
         std::unique_ptr<unsigned char[]> block;
         std::unique_ptr<float[]> rows;  // meta.rows x meta.row_columns values (null: none)
+        std::vector<sdr_listener_report> reports;  // the active slots' records, in delivery order
     };
 
     // ring: the eager pipeline's sets (batch i -> set i % ring); graph_span: the sets graph mode adds behind them
@@ -144,6 +159,8 @@ public:
             p.rows.reset(new float[nv]);
             std::copy_n(S.rows, nv, p.rows.get());
         }
+        if (S.reports && S.meta.reports)  // ... and its reports, the active slots' only
+            walk_reports(S.meta, S.reports, [&p](const sdr_listener_report &r) { p.reports.push_back(r); });
         // parked stays sorted by batch: whatever is parked is older than whatever still sits in a set, and the producer
         // parks in batch order - checked here because delivery silently stalls if it is ever violated
         if (!parked_.empty() && parked_.back().meta.batch >= p.meta.batch)
@@ -163,11 +180,14 @@ public:
         if (complete)
             batches_enqueued_ = batch + 1;
     }
-    // the deferred listen half of `batch` has been enqueued
-    void complete(int set_idx, int slots, int64_t batch)
+    // the deferred listen half of `batch` has been enqueued (reports >= 0: whether it ran the report kernels - the
+    // listeners it ran for were bound after the spectral half was published)
+    void complete(int set_idx, int slots, int64_t batch, int reports = -1)
     {
         std::lock_guard<std::mutex> g(mu_);
         sets_[(size_t)set_idx].meta.slots = slots;
+        if (reports >= 0)
+            sets_[(size_t)set_idx].meta.reports = reports;
         batches_enqueued_ = batch + 1;
     }
     // no bulk delivery: only the count moves
@@ -335,6 +355,47 @@ public:
         return be_->report(SDR_ERR_WOULD_BLOCK, "the batch went to another consumer; poll again");
     }
 
+    // sdr_poll_reports: the reports of the oldest undelivered batch into the caller's buffer; the batch stays undelivered.
+    // The reports belong to the listen half: the call looks at a batch exactly when poll() would hand it out - a batch
+    // whose listen half is still to come is "no batch waiting".
+    int peek_reports(ReportsOut *out, bool wait)
+    {
+        std::unique_lock<std::mutex> guard(mu_);
+        for (int attempt = 0; attempt < 64; attempt++) {
+            const int64_t want = deliver_next_;
+            if (want >= batches_enqueued_)
+                return be_->report(SDR_ERR_WOULD_BLOCK, "no batch waiting");
+            if (!parked_.empty() && parked_.front().meta.batch == want)
+                return copy_reports(parked_.front().meta, nullptr, &parked_.front().reports, out);
+            ResultSet &S = sets_[(size_t)set_index(want)];
+            if (S.meta.batch != want)
+                return be_->report(SDR_ERR_STATE, "results of the next batch are not where they should be");
+            bool moved = false;
+            for (void *e : {S.ev_listen, S.ev_peaks}) {
+                if (wait) {
+                    guard.unlock();  // (never held across a wait for the device)
+                    const int rc = be_->wait(e);
+                    guard.lock();
+                    if (rc != SDR_OK)
+                        return rc;
+                    if (S.meta.batch != want || deliver_next_ != want) {  // parked or delivered meanwhile: look again
+                        moved = true;
+                        break;
+                    }
+                } else {
+                    const int rc = be_->query(e);
+                    if (rc == SDR_ERR_WOULD_BLOCK)
+                        return be_->report(SDR_ERR_WOULD_BLOCK, "the oldest undelivered batch has not finished");
+                    if (rc != SDR_OK)
+                        return rc;
+                }
+            }
+            if (!moved)
+                return copy_reports(S.meta, S.reports, nullptr, out);
+        }
+        return be_->report(SDR_ERR_WOULD_BLOCK, "the batch went to another consumer; poll again");
+    }
+
     // (tests)
     int64_t deliver_next()
     {
@@ -361,6 +422,44 @@ private:
         if (!rows)
             return be_->report(SDR_ERR_STATE, "internal: a batch with rows has no row block");
         std::copy_n(rows, row_values(m), out->rows);
+        return SDR_OK;
+    }
+
+    // the records of a report block's active slots, by band, then listener id
+    template <class F>
+    static void walk_reports(const BatchMeta &m, const sdr_listener_report *block, F &&take)
+    {
+        const int per_band = std::min(std::max(m.slots, 0), m.report_stride);
+        for (int band = 0; band < m.report_bands; band++)
+            for (int l = 0; l < per_band; l++) {
+                const sdr_listener_report &r = block[(size_t)band * (size_t)m.report_stride + (size_t)l];
+                if (r.listener >= 0)
+                    take(r);
+            }
+    }
+    // block: a set's report block (one record per slot), or parked: a parked batch's records
+    int copy_reports(const BatchMeta &m, const sdr_listener_report *block, const std::vector<sdr_listener_report> *parked, ReportsOut *out)  // mu_ held
+    {
+        out->batch = m.batch;
+        out->n = 0;
+        if (!m.reports)
+            return SDR_OK;
+        if (!block && !parked)
+            return be_->report(SDR_ERR_STATE, "internal: a batch with reports has no report block");
+        if (parked)
+            out->n = (int)parked->size();
+        else
+            walk_reports(m, block, [out](const sdr_listener_report &) { out->n++; });
+        if (out->n == 0)
+            return SDR_OK;
+        if (out->n > out->cap || !out->out)
+            return be_->report(SDR_ERR_BAD_SIZE, "sdr_poll_reports: cap is too small (*n_out says what is needed)");
+        if (parked) {
+            std::copy(parked->begin(), parked->end(), out->out);
+        } else {
+            sdr_listener_report *dst = out->out;
+            walk_reports(m, block, [&dst](const sdr_listener_report &r) { *dst++ = r; });
+        }
         return SDR_OK;
     }
 

@@ -54,6 +54,9 @@ struct MemberBatch {
     // the batch's waterfall rows (sdr_group_enable_rows), peeked from the bank right before the batch was taken from it
     std::vector<float> rows;
     int n_rows = 0;
+    // ... and its listener reports (sdr_group_enable_reports), peeked the same way; bands are the member's local ones
+    std::vector<sdr_listener_report> reports;
+    int n_reports = 0;
 
     void bind()
     {
@@ -95,6 +98,13 @@ struct GroupSource {
     virtual int poll_rows(int, float *, int, int *n_rows, int64_t *batch_index, bool)
     {
         *n_rows = 0;
+        *batch_index = -1;
+        return SDR_OK;
+    }
+    // a member's sdr_poll_reports (a source without reports delivers none)
+    virtual int poll_reports(int, sdr_listener_report *, int, int *n_out, int64_t *batch_index, bool)
+    {
+        *n_out = 0;
         *batch_index = -1;
         return SDR_OK;
     }
@@ -210,6 +220,12 @@ public:
         std::lock_guard<std::mutex> g(mu_);
         row_columns_ = columns;
     }
+    // sdr_group_enable_reports: from now on a member batch is taken together with its listener reports
+    void set_reports(bool on)
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        reports_on_ = on;
+    }
 
     // The oldest batch every member has finished, merged.  A member batch taken from its bank stays parked here through
     // SDR_ERR_WOULD_BLOCK (another member is behind), SDR_ERR_BAD_SIZE (the caller's buffers) and SDR_ERR_STATE, and
@@ -282,6 +298,50 @@ public:
         return SDR_OK;
     }
 
+    // sdr_group_poll_reports: the listener reports of the oldest batch every member has finished, in one bank's order
+    // (global band, then listener id) with global band numbers.  A peek for the caller, with the member batches taken and
+    // parked here as poll_rows takes them.
+    int poll_reports(sdr_listener_report *out, int cap, int *n_out, int64_t *batch_index, bool wait)
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        if (!on_)
+            return src_->report(SDR_ERR_STATE, "bulk delivery is off (sdr_group_enable_results)");
+        for (int m = 0; m < rt_.n_members; m++) {
+            MemberBatch &p = parked_[(size_t)m];
+            if (p.held)
+                continue;
+            const int rc = take(m, p, wait, false);
+            if (rc != SDR_OK)
+                return rc;
+            p.held = true;
+        }
+        int total = 0;
+        for (int m = 0; m < rt_.n_members; m++) {
+            if (parked_[(size_t)m].r.batch_index != parked_[0].r.batch_index)
+                return src_->report(SDR_ERR_STATE, "sdr_group_poll_reports: the members delivered different batches (out of step)");
+            total += parked_[(size_t)m].n_reports;
+        }
+        *n_out = total;
+        *batch_index = parked_[0].r.batch_index;
+        if (total == 0)
+            return SDR_OK;
+        if (total > cap || !out)
+            return src_->report(SDR_ERR_BAD_SIZE, "sdr_group_poll_reports: cap is too small (*n_out says what is needed)");
+        // a member's records are sorted by local band, then listener: global band gb's are one run of them
+        sdr_listener_report *dst = out;
+        for (int gb = 0; gb < rt_.n_bands; gb++) {
+            const MemberBatch &p = parked_[(size_t)rt_.member_of(gb)];
+            const int local = rt_.local_of(gb);
+            for (int i = 0; i < p.n_reports; i++)
+                if (p.reports[(size_t)i].band == local) {
+                    *dst = p.reports[(size_t)i];
+                    dst->band = gb;
+                    dst++;
+                }
+        }
+        return SDR_OK;
+    }
+
     // sdr_group_poll_peaks: the chunks and peaks of the batch that waits for its listen half.  The banks keep that batch
     // undelivered, so nothing is parked: the members are read into scratch buffers of their own (the producer's, not the
     // consumer's).
@@ -329,6 +389,22 @@ private:
                 break;
             }
         }
+        if (!peaks) {
+            p.n_reports = 0;
+            int64_t batch = -1;
+            for (int attempt = 0; reports_on_ && attempt < 2; attempt++) {
+                int n = 0;
+                const int rc = src_->poll_reports(m, p.reports.data(), (int)p.reports.size(), &n, &batch, wait);
+                if (rc == SDR_ERR_BAD_SIZE && attempt == 0) {
+                    p.reports.resize((size_t)n);
+                    continue;
+                }
+                if (rc != SDR_OK)
+                    return rc;
+                p.n_reports = n;
+                break;
+            }
+        }
         for (int attempt = 0; attempt < 4; attempt++) {
             p.bind();
             const int rc = peaks ? src_->poll_peaks(m, &p.r, wait) : src_->poll(m, &p.r, wait);
@@ -344,6 +420,7 @@ private:
     std::mutex mu_, peek_mu_;
     bool on_ = false;
     int row_columns_ = 0;
+    bool reports_on_ = false;
     std::vector<MemberBatch> parked_, peeked_;
 };
 

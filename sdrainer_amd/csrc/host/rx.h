@@ -254,11 +254,14 @@ public:
     void SetSilenceTimeout(double s) { silenceTimeout_ = s; }
     void SetAttachmentTimeout(double s) { attachmentTimeout_ = s; }
 
-    void Attach(const Peak &peak, int device_id)  // :84-94
+    // first_batch: the first device batch (sdr_results.batch_index) whose listener report is this attachment's
+    void Attach(const Peak &peak, int device_id, int64_t first_batch = 0)  // :84-94
     {
         peak_ = peak;
         attached_ = true;
         device_id_ = device_id;
+        ClearLevel();
+        levelFromBatch_ = first_batch;
         lastAttach_ = clock_->Now();
         textProcessor_.Restart();  // :89
         text_.clear();
@@ -270,10 +273,36 @@ public:
     {
         const int64_t f = peak_.signal_frequency;
         attached_ = false;
+        ClearLevel();
         if (reporter_)
             reporter_->ListenerDeactivated(id_, f);
     }
     const Peak &GetPeak() const { return peak_; }
+    // Listener reports (Receiver::EnableReports): this attachment's level totals over the polled segments - sums and counts
+    // added, the maximum, the last wpm (include/sdrainer_hip.h sdr_listener_report: reports of consecutive batches add up).
+    // A record of a batch that ran before this attachment (the slot's earlier listener, still in flight) is not its own.
+    void AddLevel(const sdr_listener_report &r, int64_t batch)
+    {
+        if (batch < levelFromBatch_)
+            return;
+        level_.band = r.band;
+        level_.listener = r.listener;
+        level_.bin = r.bin;
+        level_.ticks += r.ticks;
+        level_.ticks_on += r.ticks_on;
+        level_.ticks_off += r.ticks_off;
+        level_.on_max_q = std::max(level_.on_max_q, r.on_max_q);
+        level_.on_sum_q += r.on_sum_q;
+        level_.off_sum_q += r.off_sum_q;
+        level_.floor_sum_q += r.floor_sum_q;
+        level_.wpm = r.wpm;
+    }
+    const sdr_listener_report &Level() const { return level_; }
+    void ClearLevel()
+    {
+        level_ = sdr_listener_report{};
+        level_.on_max_q = INT32_MIN;
+    }
     int SignalBin() const { return attached_ ? peak_.signal_bin : 0; }  // :119-124
     int DeviceID() const { return device_id_; }
     bool TimeoutExceeded() const  // :126-136
@@ -376,6 +405,8 @@ private:
     Peak peak_{};
     bool attached_ = false;
     int device_id_ = -1;
+    sdr_listener_report level_{};  // (ClearLevel at Attach and Detach)
+    int64_t levelFromBatch_ = 0;
     double lastAttach_ = 0;
     double silenceTimeout_ = kDefaultSilenceTimeout, attachmentTimeout_ = kDefaultAttachmentTimeout;
     std::string text_;
@@ -672,6 +703,9 @@ public:
         resEdges_.resize(pool * (size_t)std::min(maxBatchFrames, 8192));
         resRunes_.resize(pool * 2048);
         resRuneFrames_.resize(pool * 2048);
+        resReports_.resize(pool);
+        if (reports_ && (rc = sdr_enable_reports(bank_, 1)) != SDR_OK)
+            return rc;
         peaks_.reset(new PeaksTable(blockSize, clock_));
         peaks_->SetRand(rand_);
         peaks_->SetPolicy(policy_);
@@ -783,6 +817,25 @@ public:
         return drain ? resolvePending() : SDR_OK;
     }
 
+    // Listener reports (sdr_enable_reports): from the next segment on every resolved segment adds each bound listener's
+    // record to its totals.  Before Start the wish is stored.  The Reporter interface and its call order stay as they are.
+    int EnableReports()
+    {
+        reports_ = true;
+        return bank_ ? sdr_enable_reports(bank_, 1) : SDR_OK;
+    }
+    // The totals of the listener `id` since its Attach, over the segments resolved so far (a record whose sums add up:
+    // ticks, ticks_on / _off, on_max_q, the three sums, the last wpm); false: no such listener, or it is not attached.
+    bool ListenerLevel(const std::string &id, sdr_listener_report *totals)
+    {
+        for (auto &l : listeners_.Listeners())
+            if (l->ID() == id && l->Attached()) {
+                *totals = l->Level();
+                return true;
+            }
+        return false;
+    }
+
     PeaksTable &Peaks() { return *peaks_; }
     ListenerPool &Listeners() { return listeners_; }
     sdr_bank *Bank() { return bank_; }
@@ -871,7 +924,9 @@ private:
                                                                       : sdr_attach(bank_, 0, peak.signal_bin, &dev);
         if (rc != SDR_OK)
             return rc;
-        listener->Attach(peak, dev);
+        // (a listener bound inside the segment whose listen half is pending is reported with that segment, any other with
+        // the next one to be launched)
+        listener->Attach(peak, dev, first_frame >= 0 && sdr_listen_pending(bank_) ? segmentsLaunched_ - 1 : segmentsLaunched_);
         return SDR_OK;
     }
     // (the stream clock's arithmetic is FrameTiming's: a frame advances it by hop / sampleRate)
@@ -928,6 +983,7 @@ private:
     {
         const int64_t start = framesProcessed_;
         framesProcessed_ += n;
+        segmentsLaunched_++;  // (= the bank's batch_index: every batch of the bank is a segment of this receiver)
         bool end_decided = false;
         if (speculative_) {
             // while the device runs the spectral half just enqueued: the results of everything older (their listeners
@@ -1016,9 +1072,23 @@ private:
     {
         sdr_results r = pollBuffers();
         const auto ts0 = std::chrono::steady_clock::now();
+        // the segment's listener reports first: a peek at the batch sdr_poll hands out next
+        int n_reports = 0;
+        int64_t report_batch = -1;
+        if (reports_) {
+            const int prc = sdr_poll_reports(bank_, resReports_.data(), (int)resReports_.size(), &n_reports, &report_batch, 1);
+            if (prc != SDR_OK)
+                return prc;
+        }
         const int rc = sdr_poll(bank_, &r, 1);
         if (rc != SDR_OK)
             return rc;
+        for (int i = 0; i < n_reports; i++)
+            for (auto &l : listeners_.Listeners())
+                if (l->Attached() && l->DeviceID() == resReports_[(size_t)i].listener) {
+                    l->AddLevel(resReports_[(size_t)i], report_batch);
+                    break;
+                }
         const auto ts1 = std::chrono::steady_clock::now();
         // runes -> the listeners' text processors, each Write stamped with the time of its frame.  A listener's text
         // processor is independent of every other's (in the reference each runs in a goroutine of its own,
@@ -1143,6 +1213,9 @@ private:
     PeaksTable::Policy policy_ = PeaksTable::ReferenceOrder;
     ListenerPool listeners_;
     int64_t framesProcessed_ = 0, reportFrames_ = -1;
+    int64_t segmentsLaunched_ = 0;
+    bool reports_ = false;
+    std::vector<sdr_listener_report> resReports_;
     double aheadTiming_[3] = {0, 0, 0}, segmentTiming_[3] = {0, 0, 0};
     int maxBatchFrames_ = 256;
     bool segExpiryAtEnd_ = false;

@@ -226,6 +226,13 @@ hipError_t launch_listen_decode(ListenerSlot *slots, const uint16_t *morse, cons
                                 uint64_t *deb_bits, uint32_t *text, uint32_t *text_frames, sdr_edge *edges,
                                 uint32_t *edge_counts, uint8_t *tr_deb, DropCounters *drops, const BatchCursor *cur, ListenGeom g,
                                 int n_frames, int n_bands, uint32_t *edge_pos, int pos_stride, LaunchAt at);
+// k_report.hip (sdr_enable_reports): a slot's start and tap marks inside this batch, clamped to [0, n_frames], taken in front
+// of the decoder; behind it one sdr_listener_report per slot (listener = -1: not active) into the batch's report block
+hipError_t launch_report_marks(const ListenerSlot *slots, const BatchCursor *cur, ListenGeom g, int n_frames, int n_bands, int32_t *marks,
+                               hipStream_t stream);
+hipError_t launch_listen_report(const float *tap, const float *psd, const sdr_frame_rec *recs, const ListenerSlot *slots, const void *db_tab,
+                                const uint64_t *deb_bits, const int32_t *marks, ListenGeom g, int n_frames, int n_slots, int n_bands,
+                                sdr_listener_report *out, hipStream_t stream);
 hipError_t launch_listener_stop(ListenerSlot *slot, const uint16_t *morse, uint32_t *text, uint32_t *text_frames, int text_cap,
                                 uint32_t frame, DropCounters *drops, hipStream_t stream);
 hipError_t launch_set_debounce(ListenerSlot *slots, int n, int threshold, hipStream_t stream);

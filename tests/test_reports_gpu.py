@@ -1,0 +1,418 @@
+"""Listener reports (sdr_enable_reports / sdr_poll_reports, csrc/k_report.hip): per batch and listener the key-down and
+key-up level, the noise floor under the key-down ticks and the decoder's speed, as counts, fixed-point sums and a maximum.
+
+The expected record is tests/reports_ref.py - numpy over the oracle's `values`, `deb` and frame records, oracle.Decoder for
+the speed - and every comparison is exact: integers, and the bits of wpm.  No listener is left out of any comparison.
+
+The base shape, (a): N = 512 at 48 kS/s, synth.make_band(330, 48000, 512, 24, seed=5), 70 listeners on the 24 carriers, their
+neighbours and the band's two end bins - two lane groups of slots - in batches of 130 and 200 frames: ragged 64-frame words,
+a word boundary inside a batch, state carried into the second."""
+import functools
+
+import numpy as np
+import pytest
+
+import reports_ref as ref
+from parity_case import Case
+from parity_tools import (RATES, GROUP_BANDS, Pair, capi, group_bands, listener_bins, make_stream,  # noqa: F401 (capi: the fixture)
+                          random_window, same_delivery)
+from sdrainer_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+A_STEPS = (130, 200)
+
+
+def case_a(steps=A_STEPS, debounce=1, defer=None, listeners=70):
+    """(a): the issue's band, listeners and batches (steps that hold fewer than the 330 frames take the stream's first ones:
+    the oracle's output for them is the head of its output for all).  defer: (bin index, frame) pairs bound by sdr_attach_at
+    inside one deferred batch of all the frames (the listed carriers are then left out of the first listeners)."""
+    iq, bins, _ = synth.make_band(330, 48000, 512, 24, seed=5)
+    iq = iq[:sum(steps)]
+    bins = [int(b) for b in bins]
+    first = listener_bins(512, bins, listeners)
+    st = [("batch", x) for x in steps]
+    if defer:
+        late = [bins[i] for i, _ in defer]
+        first = [b for b in first if b not in late]
+        st = [("defer", 330, [(0, bins[i], at) for i, at in defer])]
+    return Case(512, 1, None, 0, st, 5, rate=48000, max_listeners=listeners, bands=[(np.ascontiguousarray(iq, np.float32), None, bins)],
+                init_bins=[first], debounce=debounce)
+
+
+def streams_case(n, n_bands, steps, tones, listeners, seed, sc16=False, hop=None, windows=None, bands=None, path=None):
+    made = bands or [make_stream(n, hop or n, sum(steps), RATES[n], tones, seed + 17 * b, sc16) for b in range(n_bands)]
+    return Case(n, n_bands, None, 0, [("batch", x) for x in steps], seed, rate=RATES[n], max_listeners=listeners,
+                path=path or ("device_sc16" if sc16 else "device"), bands=made, init_bins=[listener_bins(n, m[2], listeners) for m in made],
+                hop=hop, windows=windows)
+
+
+@functools.lru_cache(maxsize=None)
+def base_case():
+    """(a) with its oracle run, shared by the tests that only read it."""
+    case = case_a()
+    case.run_oracle()
+    return case
+
+
+def wpm_table(case):
+    """{(band, lid): [Decoder.wpm behind each batch]} from the oracle's debounced bits: the decoder ticks once per hop from
+    the frame the listener was attached at."""
+    ends = [e for _, e in case.spans]
+    return {(b, lid): ref.wpm_at(case.outs[b]["deb"][:, lid], case.rate, case.step, ends, start=case.life[b][lid][0])
+            for b in range(case.n_bands) for lid in range(len(case.bins[b]))}
+
+
+def expected_batch(case, wpm, k):
+    a, e = case.spans[k]
+    return [ref.expected(case.outs[b], b, lid, case.bins[b][lid], a, e, case.life[b][lid][0], wpm[(b, lid)][k])
+            for b in range(case.n_bands) for lid in case.live(b, a, e)]
+
+
+def check_reports(got, want, what):
+    assert len(got) == len(want), f"{what}: {len(got)} records for {len(want)} listeners"
+    for r, w in zip(got, want):
+        assert int(r["reserved"]) == 0
+        bad = ref.same(ref.as_dict(r), w)
+        assert not bad, f"{what} band {w['band']} listener {w['listener']}: fields {bad} differ: {ref.as_dict(r)} != {w}"
+
+
+def assert_not_trivial(case, min_on=100):
+    """From the oracle alone: every carrier listener has at least `min_on` key-down ticks over the stream."""
+    for b in range(case.n_bands):
+        for lid, bn in enumerate(case.init_bins[b]):
+            if bn in case.carriers[b]:
+                on = int(case.outs[b]["deb"][:, lid].sum())
+                assert on >= min_on, f"band {b} listener {lid} (carrier bin {bn}): {on} key-down ticks"
+
+
+def run_reports(capi, case, check=True):
+    """Every batch of the case on a new bank with reports on: poll_reports (a peek, twice), then poll, which must hand out the
+    same batch.  Returns the bank and the totals {(band, listener): accumulated record}."""
+    case.run_oracle()
+    wpm = wpm_table(case)
+    bank = case.new_bank(capi)
+    bank.enable_reports(True)
+    assert bank.reports_enabled
+    totals = {}
+    for k, (a, e) in enumerate(case.spans):
+        case.set_window(bank, k)
+        keep = case._enqueue(bank, a, e)
+        peek = bank.poll_reports(wait=True)
+        assert peek is not None and peek[0] == k, f"batch {k}: poll_reports looked at {peek and peek[0]}"
+        again = bank.poll_reports(wait=False)
+        assert again[0] == k and again[1].tobytes() == peek[1].tobytes(), f"batch {k}: a second peek differs"
+        res = bank.poll(wait=True)
+        assert res["batch_index"] == k, f"batch {k}: poll delivered {res['batch_index']} after the peek"
+        if check:
+            check_reports(peek[1], expected_batch(case, wpm, k), f"batch {k}")
+        for r in peek[1]:
+            key = (int(r["band"]), int(r["listener"]))
+            totals[key] = ref.add(totals.get(key), ref.as_dict(r))
+        del keep
+    assert bank.poll_reports(wait=False) is None and bank.poll(wait=False) is None
+    return bank, totals
+
+
+# -- against the oracle ------------------------------------------------------------------------------------------------------
+def test_base_shape(capi):
+    case = base_case()
+    assert_not_trivial(case)
+    assert len(case.init_bins[0]) == 70 and len(set(case.init_bins[0])) == 70
+    bank, totals = run_reports(capi, case)
+    assert len(totals) == 70
+    snr = capi.report_snr_db(bank_records(totals))
+    carriers = [lid for lid, bn in enumerate(case.init_bins[0]) if bn in case.carriers[0]]
+    assert np.all(snr[carriers] > 20.0), snr[carriers]  # (the issue's 65 to 68 dB on the CPU oracle; any keyed carrier stands far above the floor)
+    bank.close()
+
+
+def bank_records(totals):
+    from sdrainer_amd import capi as c
+
+    out = np.zeros(len(totals), c.REPORT_DTYPE)
+    for i, key in enumerate(sorted(totals)):
+        for f in ref.FIELDS:
+            out[i][f] = totals[key][f]
+    return out
+
+
+def test_debounced_bits(capi):
+    """signal_debounce = 3: the report counts the DEBOUNCED bit - raw bits give other records."""
+    case = case_a(debounce=3)
+    case.run_oracle()
+    differ = int((case.outs[0]["deb"] != case.outs[0]["raw"]).sum())
+    assert differ >= 1000, f"debounced and raw bits differ in {differ} places only"
+    bank, _ = run_reports(capi, case)
+    bank.close()
+
+
+def test_three_bands(capi):
+    case = streams_case(512, 3, (130, 200), 8, 12, seed=5100)
+    case.run_oracle()
+    assert_not_trivial(case, 50)
+    bank, totals = run_reports(capi, case)
+    assert len(totals) == 3 * 12
+    bank.close()
+
+
+@functools.lru_cache(maxsize=None)
+def wide_streams():
+    """One band of N = 16384, 1100 frames, as sc16 words and as the float32 values they stand for: one oracle run for both."""
+    return make_stream(16384, 16384, 1100, RATES[16384], 96, 5200, sc16=True)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_oracle():
+    case = streams_case(16384, 1, (1100,), 96, 256, seed=5200, bands=[wide_streams()])
+    case.run_oracle()
+    return case.outs, case.refs
+
+
+@pytest.mark.parametrize("sc16", [False, True], ids=["f32", "sc16"])
+def test_r32_and_its_tap(capi, sc16):
+    """N = 16384, 1100 frames in one batch, 256 listeners: k_fft_r32 (1024 frames and more) and its tap."""
+    case = streams_case(16384, 1, (1100,), 96, 256, seed=5200, sc16=sc16, bands=[wide_streams()])
+    case.outs, case.refs = wide_oracle()  # (the same float32 values either way: the oracle runs once)
+    assert_not_trivial(case, 100)
+    bank, totals = run_reports(capi, case)
+    assert len(totals) == 256
+    bank.close()
+
+
+def test_overlapped_frames(capi):
+    """N = 4096 with hop 1024: the decoder, and so wpm, is timed by the hop."""
+    case = streams_case(4096, 1, (230, 130), 8, 24, seed=5300, hop=1024)
+    bank, totals = run_reports(capi, case)
+    assert len(totals) == 24
+    bank.close()
+
+
+def test_windowed(capi):
+    w = random_window(512, 78)
+    case = streams_case(512, 1, (130, 200), 8, 24, seed=5400, windows=[w, w])
+    bank, totals = run_reports(capi, case)
+    assert len(totals) == 24
+    bank.close()
+
+
+# -- batch cuts ---------------------------------------------------------------------------------------------------------------
+def test_batch_cuts(capi):
+    """(a)'s stream as one batch and in cuts of 1, 63, 64, 65 and 137 frames: the accumulated totals are equal field by field."""
+    whole = case_a(steps=(330,))
+    whole.outs, whole.refs = base_case().outs, base_case().refs
+    bank, one = run_reports(capi, whole)
+    bank.close()
+    cut = case_a(steps=(1, 63, 64, 65, 137))
+    cut.outs, cut.refs = base_case().outs, base_case().refs
+    bank, many = run_reports(capi, cut)
+    bank.close()
+    assert one.keys() == many.keys() and len(one) == 70
+    for key in one:
+        assert not ref.same(one[key], many[key]), f"listener {key}: {one[key]} != {many[key]}"
+
+
+# -- the deferred half --------------------------------------------------------------------------------------------------------
+def test_deferred_half(capi):
+    """sdr_attach_at at frames 101 and 164 of a deferred 330-frame batch: ticks count from the start frame, the values in
+    front of tapped_from come from the retained psd rows, and the batch shows no reports before sdr_process_listen."""
+    case = case_a(defer=[(3, 101), (7, 164)])
+    case.run_oracle()
+    wpm = wpm_table(case)
+    bank = case.new_bank(capi)
+    bank.enable_reports(True)
+    bank.defer_listen(True)
+    keep = case._enqueue(bank, 0, 330)
+    pk = bank.poll_peaks(wait=True)
+    assert pk["batch_index"] == 0
+    assert bank.poll_reports(wait=False) is None and bank.poll_reports(wait=True) is None, "reports of a batch whose listen half has not run"
+    with pytest.raises(capi.SdrError) as err:
+        bank.enable_reports(False)
+    assert err.value.code == capi.ERR_STATE  # a listen half is pending
+    n0 = len(case.init_bins[0])
+    for i, (_, bn, at) in enumerate(case.steps[0][2]):
+        assert bank.attach_at(0, int(bn), at) == n0 + i
+    bank.process_listen()
+    bank.defer_listen(False)
+    k, got = bank.poll_reports(wait=True)
+    want = expected_batch(case, wpm, 0)
+    assert k == 0 and len(want) == n0 + 2
+    assert [w["ticks"] for w in want[-2:]] == [330 - 101, 330 - 164]
+    assert all(w["ticks_on"] >= 50 for w in want[-2:]), "the late listeners' carriers are not keyed"
+    check_reports(got, want, "deferred batch")
+    assert bank.poll(wait=True)["batch_index"] == 0
+    del keep
+    bank.close()
+
+
+# -- non-finite ---------------------------------------------------------------------------------------------------------------
+def two_band_case(second, seed):
+    """Band 0: keyed carriers.  Band 1: band 0's frames changed by `second`.  130 frames in one batch, NaN by class."""
+    s, _, carriers = make_stream(512, 512, 130, RATES[512], 6, seed)
+    made = [(s, None, carriers), (second(s.copy()), None, carriers)]
+    return Case(512, 2, None, 0, [("batch", 130)], seed, rate=RATES[512], max_listeners=12, bands=made,
+                init_bins=[listener_bins(512, carriers, 12)] * 2, nan_ok=True)
+
+
+def test_zero_band(capi):
+    """An all-zero band: v and nf are -Inf and clamp at q = -262144 - for the first SDR_NOISE_WINDOW = 60 frames: then the
+    rolling mean of the noise floor takes -Inf out of a sum of -Inf and is NaN, and the ticks are unmeasured."""
+    case = two_band_case(lambda s: np.zeros_like(s), 5500)
+    case.run_oracle()
+    nf = case.outs[1]["frames"]["noise_floor"]
+    assert np.all(np.isneginf(case.outs[1]["values"])) and np.all(np.isneginf(nf[:60])) and np.all(np.isnan(nf[60:]))
+    bank, totals = run_reports(capi, case)
+    for lid in range(12):
+        t = totals[(1, lid)]
+        assert t["ticks"] == 130 and t["ticks_on"] + t["ticks_off"] == 60 and t["on_sum_q"] + t["off_sum_q"] == 60 * -262144, t
+    bank.close()
+
+
+def test_nan_sample(capi):
+    """One NaN sample at frame 40 of 130: from that frame on the band's ticks are unmeasured; the other band is untouched."""
+    def poison(s):
+        s[40 * 512 + 7, 0] = np.nan
+        return s
+
+    case = two_band_case(poison, 5600)
+    case.run_oracle()
+    nf = case.outs[1]["frames"]["noise_floor"]
+    assert not np.isnan(nf[:40]).any() and np.isnan(nf[40:]).all(), "the oracle's noise floor is not NaN from frame 40 on"
+    bank, totals = run_reports(capi, case)
+    for lid in range(12):
+        assert totals[(1, lid)]["ticks"] == 130 and totals[(1, lid)]["ticks_on"] + totals[(1, lid)]["ticks_off"] == 40
+        assert totals[(0, lid)]["ticks_on"] + totals[(0, lid)]["ticks_off"] == 130
+    bank.close()
+
+
+# -- the unchanged path -------------------------------------------------------------------------------------------------------
+def test_unchanged_path(capi):
+    """The same input through a bank with reports off and a bank with reports on: everything sdr_poll delivers is equal, and
+    so are the rows; reports off delivers no record and launches neither kernel."""
+    case = base_case()
+    off, on = case.new_bank(capi), case.new_bank(capi)
+    for b in (off, on):
+        b.enable_rows(64)
+        b.profile_enable(True)
+    on.enable_reports(True)
+    L = capi.load()
+    assert [L.sdr_kernel_name(i).decode() for i in range(8)] == list(capi.KERNELS) and L.sdr_kernel_name(8) == b"k_cum_rows"
+    assert (L.sdr_kernel_name(9), L.sdr_kernel_name(10)) == (b"k_listen_report", b"k_report_marks")
+    for k, (a, e) in enumerate(case.spans):
+        keep = [case._enqueue(b, a, e) for b in (off, on)]
+        none = off.poll_reports(wait=True)
+        assert none[0] == k and none[1].shape == (0,)
+        some = on.poll_reports(wait=True)
+        assert some[0] == k and some[1].shape == (70,)
+        rows = [b.poll_rows(wait=True) for b in (off, on)]
+        assert rows[0][0] == rows[1][0] == k and rows[0][1].tobytes() == rows[1][1].tobytes()
+        same_delivery(on.poll(wait=True), off.poll(wait=True))
+        del keep
+    prof = [b.profile_read() for b in (off, on)]
+    for name in capi.REPORT_KERNELS:
+        assert prof[0][name] == (0.0, 0) and prof[1][name][1] == len(case.spans), (name, prof[0][name], prof[1][name])
+    for name in capi.KERNELS + (capi.ROWS_KERNEL,):
+        assert prof[0][name][1] == prof[1][name][1], name
+    # switched off again: the next batch has none; results off switches reports off
+    on.enable_reports(False)
+    on.enable_results(False)
+    assert not on.reports_enabled
+    bare = capi.Bank(case.rate, 512, max_batch_frames=64)
+    with pytest.raises(capi.SdrError) as err:
+        bare.enable_reports(True)
+    assert err.value.code == capi.ERR_STATE  # needs sdr_enable_results
+    for b in (off, on, bare):
+        b.close()
+
+
+# -- capacity and peek --------------------------------------------------------------------------------------------------------
+def test_capacity_and_parked_batches(capi):
+    """cap too small: ERR_BAD_SIZE with the count needed, nothing consumed.  Eight batches processed before the first poll -
+    more than the six ring sets - each keep their reports."""
+    steps = (40,) * 7 + (50,)
+    case = case_a(steps=steps)
+    case.outs, case.refs = base_case().outs, base_case().refs
+    wpm = wpm_table(case)
+    bank = case.new_bank(capi)
+    bank.enable_reports(True)
+    keep = [case._enqueue(bank, a, e) for a, e in case.spans]
+    assert bank.results_pending == 8
+    for cap in (0, 69):
+        with pytest.raises(capi.SdrError) as err:
+            bank.poll_reports(wait=True, cap=cap)
+        assert err.value.code == capi.ERR_BAD_SIZE and err.value.n_out == 70
+    for k in range(8):
+        peek = bank.poll_reports(wait=True, cap=70)
+        assert peek[0] == k
+        check_reports(peek[1], expected_batch(case, wpm, k), f"batch {k}")
+        assert bank.poll_reports(wait=False)[1].tobytes() == peek[1].tobytes()
+        assert bank.poll(wait=True)["batch_index"] == k
+    assert bank.poll_reports(wait=False) is None
+    del keep
+    bank.close()
+
+
+# -- graph --------------------------------------------------------------------------------------------------------------------
+def test_graph(capi):
+    """Two replays of six 27-frame batches captured with reports on equal an eager bank's reports (and the oracle's); a launch
+    after sdr_enable_reports(0) is refused."""
+    import torch
+
+    per = 27
+    case = case_a(steps=(per,) * 12)
+    case.outs, case.refs = base_case().outs, base_case().refs
+    bank, want = run_reports(capi, case)
+    bank.close()
+    graph = case_a(steps=(per,) * 12)
+    graph.path = "graph"
+    graph.outs, graph.refs = case.outs, case.refs
+    wpm = wpm_table(graph)
+    bank = graph.new_bank(capi, torch.cuda.Stream())
+    bank.enable_reports(True)
+    bank.graph_capture(per)
+    got = {}
+    for replay in range(2):
+        batches = [graph.device_batch(a, e) for a, e in graph.spans[6 * replay:6 * replay + 6]]
+        torch.cuda.synchronize()
+        bank.graph_launch([x.data_ptr() for x in batches])
+        for k in range(6 * replay, 6 * replay + 6):
+            peek = bank.poll_reports(wait=True)
+            assert peek[0] == k
+            check_reports(peek[1], expected_batch(graph, wpm, k), f"replayed batch {k}")
+            assert bank.poll(wait=True)["batch_index"] == k
+            for r in peek[1]:
+                key = (int(r["band"]), int(r["listener"]))
+                got[key] = ref.add(got.get(key), ref.as_dict(r))
+        bank.sync()
+    assert got.keys() == want.keys() and all(not ref.same(got[key], want[key]) for key in got)
+    bank.enable_reports(False)
+    with pytest.raises(capi.SdrError) as err:
+        bank.graph_launch([x.data_ptr() for x in batches])
+    assert err.value.code == capi.ERR_STATE
+    bank.close()
+
+
+# -- group --------------------------------------------------------------------------------------------------------------------
+def test_group(capi):
+    """Two members on one GPU, five bands: the merged reports equal one bank's, with global band numbers."""
+    n, rate = 512, RATES[512]
+    iq, bins = group_bands(330, rate, n, 4, seed=5700)
+    pair = Pair(capi, [0, 0], rate, n, max_batch_frames=256, max_listeners=4)
+    for b in range(GROUP_BANDS):
+        for bn in bins[b]:
+            pair.attach(b, bn)
+    pair.bank.enable_results(True)
+    pair.group.enable_results(True)
+    pair.bank.enable_reports(True)
+    pair.group.enable_reports(True)
+    for k, (a, e) in enumerate([(0, 130), (130, 330)]):
+        pair.process(iq[:, a:e])
+        one, merged = pair.bank.poll_reports(wait=True), pair.group.poll_reports(wait=True)
+        assert one[0] == merged[0] == k and one[1].shape == merged[1].shape == (GROUP_BANDS * 4,)
+        assert [int(r["band"]) for r in merged[1]] == [b for b in range(GROUP_BANDS) for _ in range(4)]
+        assert one[1].tobytes() == merged[1].tobytes(), f"batch {k}: the group's reports differ from the bank's"
+        assert int(one[1]["ticks_on"].sum()) > 0
+        res = pair.polls()
+        assert res["batch_index"] == k
+    assert pair.group.poll_reports(wait=False) is None
+    pair.close()

@@ -3,7 +3,7 @@
 // filling (one listener bound per 100-frame cumulation, rx/receiver.go:409-426: the spectral half of a long segment
 // first, the boundary decisions next, the listeners last - rx.h discoverAhead; with SDR_RX_NO_SPECULATION=1 the
 // round-2 way, a 100-frame segment resolved on the host before the next) and once it is full (segments of max_batch
-// frames, up to four in flight).
+// frames, up to four in flight).  Listener reports are on: every spot is printed with its dB over noise and WPM.
 // Built as a shared library and driven by tools/strain_e2e.py, which owns the device buffer.
 #include <chrono>
 #include <cstdio>
@@ -16,7 +16,22 @@ struct CountingReporter : rx::Reporter {
     void ListenerActivated(const std::string &, int64_t) override { activated++; }
     void ListenerDeactivated(const std::string &, int64_t) override { deactivated++; }
     void CallsignDecoded(const std::string &, const std::string &, int64_t, int, int) override { decoded++; }
-    void CallsignSpotted(const std::string &, const std::string &, int64_t) override { spotted++; }
+    // a skimmer's spot line: call sign, frequency, dB over noise, WPM - the last two from the listener's level totals
+    // (rx::Receiver::ListenerLevel: the mean key-down level over the band's noise floor since the listener was bound, and
+    // its decoder's speed as of the last resolved segment); the first kSpotLines spots are printed
+    static constexpr long kSpotLines = 32;
+    rx::Receiver *receiver = nullptr;
+    void CallsignSpotted(const std::string &listener, const std::string &callsign, int64_t frequency) override
+    {
+        if (spotted++ >= kSpotLines || !receiver)
+            return;
+        sdr_listener_report t{};
+        if (receiver->ListenerLevel(listener, &t) && t.ticks_on > 0)
+            fprintf(stderr, "spot %-10s %10lld Hz %6.1f dB %5.1f WPM  (%s)\n", callsign.c_str(), (long long)frequency,
+                    (double)(t.on_sum_q - t.floor_sum_q) / (256.0 * t.ticks_on), t.wpm, listener.c_str());
+        else
+            fprintf(stderr, "spot %-10s %10lld Hz      - dB     - WPM  (%s)\n", callsign.c_str(), (long long)frequency, listener.c_str());
+    }
 };
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 }  // namespace
@@ -28,7 +43,9 @@ extern "C" int strain_e2e(const float *iq_dev, int frames, int rate, int n, int 
 {
     CountingReporter rep;
     rx::Receiver r("rx", rx::StrainMode, nullptr, pool);
+    rep.receiver = &r;
     r.AddReporter(&rep);
+    r.EnableReports();
     r.SetCenterFrequency(14000000);
     r.SetSelectionPolicy(rx::PeaksTable::StrongestFirst);
     r.SetSilenceTimeout(1e9);
