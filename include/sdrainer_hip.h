@@ -27,6 +27,7 @@
  *   sdr_read_frame_records          locals of Receiver.run (noise floor, thresholds)  rx/receiver.go:381-385
  *   sdr_push_kiwi_snd               decodeIQMessage + kiwi.Process.IQData       kiwi/client.go:284-308, kiwi/kiwi.go:94-105
  *   sdr_push_iq_sc16, *_sc16        Receiver.IQData fed by decodeIQBytes' complex int16 samples  kiwi/client.go:298-308
+ *   sdr_push_iq8, *_iq8             Receiver.IQData fed by an 8-bit receiver's bytes (cs8 / cu8), widened on the device
  *   sdr_audio_*                     cw.AudioDemodulator (Goertzel audio path)   cw/audio.go:37-211
  *   sdr_enable_results / sdr_poll   the consumer side in bulk: what Receiver.run hands to its listeners'
  *                                   io.Writer (rx/receiver.go:123, ChannelWriter :508-539) and to the
@@ -206,6 +207,26 @@ int sdr_process_device_stream_sc16(sdr_bank *bank, const int16_t *iq_dev, int n_
  *     kernels read the int16 values themselves (no float32 copy). */
 int sdr_push_iq_sc16(sdr_bank *bank, int band, int sample_rate, const int16_t *iq, size_t n_values);
 int sdr_process_device_sc16(sdr_bank *bank, const int16_t *iq_dev, int n_frames);
+/* Complex 8-bit input: one byte I, then one byte Q per sample, the format of the common wide-band receivers.  `format`:
+ *   SDR_IQ8_CS8  signed bytes (HackRF class):     value = float32(x) / 128
+ *   SDR_IQ8_CU8  unsigned bytes (RTL-SDR class):  value = (float32(x) - 127.5) / 128 = (2 x - 255) / 256
+ * Both are exact in float32 for all 256 inputs, so nothing is rounded and every result is bit-identical to the float32
+ * calls fed with those values - with a window (the operand is the converted value), with a hop, in a graph replay and
+ * through a group.  A caller who wants another convention (a measured DC offset such as 127.4, division by 127) converts
+ * to float32 itself and uses the float32 calls.  n_values counts bytes (2 per sample); statuses are the sc16 calls'; any
+ * other `format` is SDR_ERR_BAD_ARG.
+ *   sdr_push_iq8: as sdr_push_iq_sc16 (whole hops; only the new samples are uploaded): the bytes are staged and uploaded as
+ *     they are (a quarter of float32's bytes) and converted on the device.  A band's batch must not mix kinds - float32,
+ *     KiwiSDR, sc16, cs8, cu8 (SDR_ERR_STATE).
+ *   sdr_process_device_iq8: as sdr_process_device, layout [band][frame][block_size][2] bytes, 16-byte aligned; the FFT
+ *     kernels read the bytes themselves (no float32 copy).  SDR_ERR_STATE on a bank with hop < block_size.
+ *   sdr_process_device_stream_iq8: as sdr_process_device_stream_sc16, band_stride_samples a multiple of 8 samples (16
+ *     bytes). */
+#define SDR_IQ8_CS8 0
+#define SDR_IQ8_CU8 1
+int sdr_push_iq8(sdr_bank *bank, int band, int sample_rate, const void *iq, size_t n_values, int format);
+int sdr_process_device_iq8(sdr_bank *bank, const void *iq_dev, int n_frames, int format);
+int sdr_process_device_stream_iq8(sdr_bank *bank, const void *iq_dev, int n_frames, size_t band_stride_samples, int format);
 /* Blocks until everything queued on the bank's stream has finished. */
 int sdr_sync(sdr_bank *bank);
 
@@ -430,7 +451,7 @@ int sdr_read_drop_counters(sdr_bank *bank, uint64_t *runes_dropped, uint64_t *ed
  * listener, sdr_enable_results, sdr_enable_rows, sdr_enable_reports and sdr_set_find_peaks invalidate the capture (sdr_graph_launch returns SDR_ERR_STATE:
  * capture again).  Results are read / polled exactly as after sdr_process_device;
  * the "last batch" of the read calls is the last replay's last.  Not offered with overlapped frames yet:
- * sdr_graph_capture(_sc16) on a bank with hop < block_size returns SDR_ERR_STATE. */
+ * sdr_graph_capture(_sc16, _iq8) on a bank with hop < block_size returns SDR_ERR_STATE. */
 int sdr_graph_batches(sdr_bank *bank);
 int sdr_graph_capture(sdr_bank *bank, int n_frames);
 /* iq_dev: sdr_graph_batches() device pointers, one batch each, layout and alignment as sdr_process_device. */
@@ -439,6 +460,10 @@ int sdr_graph_launch(sdr_bank *bank, const float *const *iq_dev);
  * with the other call returns SDR_ERR_STATE. */
 int sdr_graph_capture_sc16(sdr_bank *bank, int n_frames);
 int sdr_graph_launch_sc16(sdr_bank *bank, const int16_t *const *iq_dev);
+/* The same for 8-bit input (sdr_process_device_iq8's layout and formats).  The graph remembers its format: a launch with
+ * another one (cs8 against cu8 included) returns SDR_ERR_STATE and names the right call. */
+int sdr_graph_capture_iq8(sdr_bank *bank, int n_frames, int format);
+int sdr_graph_launch_iq8(sdr_bank *bank, const void *const *iq_dev, int format);
 /* Back to sdr_process_*: drains the pipeline, moves what was not polled yet to the host-side queue (sdr_poll keeps
  * delivering it, oldest first) and frees the replays' buffer sets; what the last replay's last batch left on the device
  * goes with them - read it (sdr_read_*) before the release. */
@@ -481,6 +506,9 @@ int sdr_group_process_device(sdr_group *group, const float *const *iq_dev, int n
 /* sc16 input (sdr_push_iq_sc16 / sdr_process_device_sc16), routed exactly like the float32 calls. */
 int sdr_group_push_iq_sc16(sdr_group *group, int band, int sample_rate, const int16_t *iq, size_t n_values);
 int sdr_group_process_device_sc16(sdr_group *group, const int16_t *const *iq_dev, int n_frames);
+/* 8-bit input (sdr_push_iq8 / sdr_process_device_iq8), routed exactly like the float32 calls. */
+int sdr_group_push_iq8(sdr_group *group, int band, int sample_rate, const void *iq, size_t n_values, int format);
+int sdr_group_process_device_iq8(sdr_group *group, const void *const *iq_dev, int n_frames, int format);
 int sdr_group_sync(sdr_group *group);
 int sdr_group_set_peak_threshold(sdr_group *group, int band, float threshold);
 int sdr_group_set_signal_debounce(sdr_group *group, int band, int debounce);

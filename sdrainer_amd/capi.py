@@ -121,6 +121,15 @@ def _set_window(fn, handle, w):
     w = np.ascontiguousarray(w, np.float32).reshape(-1)
     return fn(handle, w.ctypes.data_as(C.POINTER(C.c_float)), int(w.size))
 
+# 8-bit input formats (SDR_IQ8_CS8 / SDR_IQ8_CU8)
+IQ8_CS8, IQ8_CU8 = 0, 1
+
+
+def _iq8_bytes(iq, fmt):
+    """The bytes of an 8-bit push: int8 for cs8, uint8 for cu8 (any other fmt goes to the library, which refuses it)."""
+    return np.ascontiguousarray(iq, dtype=np.int8 if fmt == IQ8_CS8 else np.uint8).reshape(-1)
+
+
 # every symbol include/sdrainer_hip.h declares (tests/test_capi_symbols.py checks the header against this)
 SYMBOLS = (
     "sdr_last_error sdr_abi_version sdr_create sdr_destroy sdr_self_check sdr_set_stream sdr_push_iq sdr_push_kiwi_snd sdr_staged_frames "
@@ -136,6 +145,8 @@ SYMBOLS = (
     "sdr_push_iq_sc16 sdr_process_device_sc16 sdr_graph_capture_sc16 sdr_graph_launch_sc16 "
     "sdr_group_push_iq_sc16 sdr_group_process_device_sc16 "
     "sdr_hop sdr_process_device_stream sdr_process_device_stream_sc16 "
+    "sdr_push_iq8 sdr_process_device_iq8 sdr_process_device_stream_iq8 sdr_graph_capture_iq8 sdr_graph_launch_iq8 "
+    "sdr_group_push_iq8 sdr_group_process_device_iq8 "
     "sdr_set_window sdr_group_set_window "
     "sdr_enable_rows sdr_row_columns sdr_poll_rows sdr_group_enable_rows sdr_group_poll_rows "
     "sdr_enable_reports sdr_reports_enabled sdr_poll_reports sdr_group_enable_reports sdr_group_poll_reports "
@@ -187,6 +198,9 @@ def load():
     sig("sdr_hop", C.c_int, vp)
     sig("sdr_process_device_stream", C.c_int, vp, vp, C.c_int, C.c_size_t)
     sig("sdr_process_device_stream_sc16", C.c_int, vp, vp, C.c_int, C.c_size_t)
+    sig("sdr_push_iq8", C.c_int, vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int)
+    sig("sdr_process_device_iq8", C.c_int, vp, vp, C.c_int, C.c_int)
+    sig("sdr_process_device_stream_iq8", C.c_int, vp, vp, C.c_int, C.c_size_t, C.c_int)
     sig("sdr_sync", C.c_int, vp)
     sig("sdr_attach", C.c_int, vp, C.c_int, C.c_int, ip)
     sig("sdr_detach", C.c_int, vp, C.c_int, C.c_int)
@@ -215,6 +229,8 @@ def load():
     sig("sdr_graph_launch", C.c_int, vp, C.POINTER(C.c_void_p))
     sig("sdr_graph_capture_sc16", C.c_int, vp, C.c_int)
     sig("sdr_graph_launch_sc16", C.c_int, vp, C.POINTER(C.c_void_p))
+    sig("sdr_graph_capture_iq8", C.c_int, vp, C.c_int, C.c_int)
+    sig("sdr_graph_launch_iq8", C.c_int, vp, C.POINTER(C.c_void_p), C.c_int)
     sig("sdr_graph_release", C.c_int, vp)
     sig("sdr_scope_active", C.c_int, vp)
     sig("sdr_scope_read_spectral", C.c_int, vp, C.c_int, C.c_int, C.POINTER(ScopeSpectralFrame), C.POINTER(C.c_double), C.c_int)
@@ -253,6 +269,8 @@ def load():
     sig("sdr_group_process_device", C.c_int, vp, C.POINTER(C.c_void_p), C.c_int)
     sig("sdr_group_push_iq_sc16", C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_int16), C.c_size_t)
     sig("sdr_group_process_device_sc16", C.c_int, vp, C.POINTER(C.c_void_p), C.c_int)
+    sig("sdr_group_push_iq8", C.c_int, vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int)
+    sig("sdr_group_process_device_iq8", C.c_int, vp, C.POINTER(C.c_void_p), C.c_int, C.c_int)
     sig("sdr_group_sync", C.c_int, vp)
     sig("sdr_group_set_peak_threshold", C.c_int, vp, C.c_int, C.c_float)
     sig("sdr_group_set_signal_debounce", C.c_int, vp, C.c_int, C.c_int)
@@ -433,6 +451,15 @@ class Bank:
             _check(rc)
         return rc
 
+    def push_iq8(self, band: int, sample_rate: int, iq: np.ndarray, fmt: int) -> int:
+        """iq: byte I,Q pairs, int8 for fmt = IQ8_CS8 (value x / 128) or uint8 for IQ8_CU8 (value (x - 127.5) / 128).  Status
+        code as push_iq."""
+        iq = _iq8_bytes(iq, fmt)
+        rc = self._L.sdr_push_iq8(self._h, band, sample_rate, C.c_void_p(iq.ctypes.data), iq.size, fmt)
+        if rc not in (OK, ERR_BAD_RATE, ERR_BAD_SIZE, ERR_WOULD_DROP, ERR_STATE):
+            _check(rc)
+        return rc
+
     def push_kiwi_snd(self, band: int, sample_rate: int, payload: bytes) -> int:
         """payload: body of one KiwiSDR SND message (17-byte header + big-endian int16 IQ)."""
         rc = self._L.sdr_push_kiwi_snd(self._h, band, sample_rate, payload, len(payload))
@@ -460,6 +487,10 @@ class Bank:
         """iq_dev_ptr: device memory [band][frame][2N] int16 (sc16), 16-byte aligned."""
         _check(self._L.sdr_process_device_sc16(self._h, C.c_void_p(iq_dev_ptr), n_frames))
 
+    def process_device_iq8(self, iq_dev_ptr: int, n_frames: int, fmt: int):
+        """iq_dev_ptr: device memory [band][frame][2N] bytes (cs8 or cu8 by fmt), 16-byte aligned."""
+        _check(self._L.sdr_process_device_iq8(self._h, C.c_void_p(iq_dev_ptr), n_frames, fmt))
+
     @property
     def hop(self) -> int:
         """The effective hop: block_size unless the bank was created with a smaller one."""
@@ -472,6 +503,10 @@ class Bank:
     def process_device_stream_sc16(self, iq_dev_ptr: int, n_frames: int, band_stride_samples: int):
         """The same for int16 I,Q pairs (sc16)."""
         _check(self._L.sdr_process_device_stream_sc16(self._h, C.c_void_p(iq_dev_ptr), n_frames, band_stride_samples))
+
+    def process_device_stream_iq8(self, iq_dev_ptr: int, n_frames: int, band_stride_samples: int, fmt: int):
+        """The same for byte I,Q pairs (cs8 or cu8 by fmt); band_stride_samples a multiple of 8."""
+        _check(self._L.sdr_process_device_stream_iq8(self._h, C.c_void_p(iq_dev_ptr), n_frames, band_stride_samples, fmt))
 
     def process_host(self, iq: np.ndarray) -> int:
         """iq: float32 [n_bands, n_frames, 2N] (or [n_frames, 2N] for one band) from host memory."""
@@ -625,6 +660,14 @@ class Bank:
         arr = (C.c_void_p * len(iq_dev_ptrs))(*[C.c_void_p(int(p)) for p in iq_dev_ptrs])
         assert len(iq_dev_ptrs) == self.graph_batches
         _check(self._L.sdr_graph_launch_sc16(self._h, arr))
+
+    def graph_capture_iq8(self, n_frames: int, fmt: int):
+        _check(self._L.sdr_graph_capture_iq8(self._h, n_frames, fmt))
+
+    def graph_launch_iq8(self, iq_dev_ptrs, fmt: int):
+        arr = (C.c_void_p * len(iq_dev_ptrs))(*[C.c_void_p(int(p)) for p in iq_dev_ptrs])
+        assert len(iq_dev_ptrs) == self.graph_batches
+        _check(self._L.sdr_graph_launch_iq8(self._h, arr, fmt))
 
     def graph_release(self):
         _check(self._L.sdr_graph_release(self._h))
@@ -811,6 +854,13 @@ class Group:
             _check(rc)
         return rc
 
+    def push_iq8(self, band: int, sample_rate: int, iq: np.ndarray, fmt: int) -> int:
+        iq = _iq8_bytes(iq, fmt)
+        rc = self._L.sdr_group_push_iq8(self._h, band, sample_rate, C.c_void_p(iq.ctypes.data), iq.size, fmt)
+        if rc not in (OK, ERR_BAD_RATE, ERR_BAD_SIZE, ERR_WOULD_DROP, ERR_STATE):
+            _check(rc)
+        return rc
+
     def push_kiwi_snd(self, band: int, sample_rate: int, payload: bytes) -> int:
         rc = self._L.sdr_group_push_kiwi_snd(self._h, band, sample_rate, payload, len(payload))
         if rc not in (OK, ERR_BAD_RATE, ERR_BAD_SIZE, ERR_WOULD_DROP, ERR_STATE):
@@ -836,6 +886,11 @@ class Group:
         """iq_dev_ptrs: one device pointer per member, each [local band][frame][2N] int16 (sc16)."""
         arr = (C.c_void_p * len(iq_dev_ptrs))(*[C.c_void_p(int(p)) for p in iq_dev_ptrs])
         _check(self._L.sdr_group_process_device_sc16(self._h, arr, n_frames))
+
+    def process_device_iq8(self, iq_dev_ptrs, n_frames: int, fmt: int):
+        """iq_dev_ptrs: one device pointer per member, each [local band][frame][2N] bytes (cs8 or cu8 by fmt)."""
+        arr = (C.c_void_p * len(iq_dev_ptrs))(*[C.c_void_p(int(p)) for p in iq_dev_ptrs])
+        _check(self._L.sdr_group_process_device_iq8(self._h, arr, n_frames, fmt))
 
     def sync(self):
         _check(self._L.sdr_group_sync(self._h))

@@ -214,7 +214,7 @@ struct sdr_bank {
     int64_t graph_replays = 0;  // launches since the capture
     bool graph_ready = false;
     int graph_frames = 0, graph_slots = 0;
-    sdr::InFormat graph_fmt = sdr::InFormat::F32;  // the input format the graphs were captured for (sdr_graph_capture / _sc16)
+    sdr::InFormat graph_fmt = sdr::InFormat::F32;  // the input format the graphs were captured for (sdr_graph_capture / _sc16 / _iq8)
     uint64_t attach_gen = 0, graph_attach_gen = 0;  // sdr_attach / sdr_detach calls so far; as of the capture
     // what the captured graphs have baked in besides the listeners: the packing kernels exist only if results were on, the
     // refinement / peak-scan nodes only if find_peaks was
@@ -256,7 +256,7 @@ struct sdr_bank {
         // pinned rows hold the samples pushed since the last batch; the device row holds the history (the last N - hop
         // samples of the frames the batch before consumed, none at hop = N) and the uploaded samples behind it.
         float *h_f32 = nullptr;        // pinned [band][stage_cap][2] float32 samples
-        uint8_t *h_raw = nullptr;      // pinned [band][stage_cap][2] int16: big-endian (KiwiSDR payloads) or sc16, on demand
+        uint8_t *h_raw = nullptr;      // pinned, [band] rows of stage_cap * 4 bytes: [2] int16 per sample, big-endian (KiwiSDR payloads) or sc16, or [2] bytes per sample (cs8 / cu8: half a row), on demand
         DevBuf<float> d_f32;           // [band][stage_cap][2]: what the FFT kernel reads
         DevBuf<uint8_t> d_raw;         // raw int16 bytes, unpacked on the device (k_unpack.hip)
         hipEvent_t uploaded = nullptr;  // the upload has left the pinned buffers (they may be overwritten)
@@ -268,7 +268,7 @@ struct sdr_bank {
     hipStream_t copy_stream = nullptr;
     std::vector<sdr::StreamStage> staged;  // per band: history and staged samples (host/overlap.h)
     size_t stage_cap() const { return sdr::span_samples(cfg.max_batch_frames, hop, cfg.block_size); }
-    std::vector<int> staged_kind;  // per band: 0 nothing staged, 1 float32 frames, 2 int16be frames, 3 sc16 frames
+    std::vector<int> staged_kind;  // per band: 0 nothing staged, 1 float32 frames, 2 int16be frames, 3 sc16 frames, 4 cs8 frames, 5 cu8 frames
 
     bool profiling = false;
     double prof_ms[sdr::K_PROFILE_SLOTS] = {};
@@ -320,7 +320,7 @@ int check_listener(sdr_bank *b, int band, int lid);
 hipError_t alloc_set(sdr_bank *b, BatchSet &S);
 // (capi_process.hip)
 int flush_late_attached(sdr_bank *b);
-// iq_dev: float32 frames, or sc16 frames with fmt = SC16 (only the FFT reads the input)
+// iq_dev: float32 frames, or sc16 / cs8 / cu8 frames with fmt = SC16 / CS8 / CU8 (only the FFT reads the input)
 // in_stride: samples from one band's stream to the next; frames start every b->hop samples (sdr_device.h launch_fft)
 int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in_stride, int capture_k = -1, int capture_stage = -1,
                         int parts = PART_ALL, sdr::InFormat fmt = sdr::InFormat::F32);

@@ -239,9 +239,14 @@ static int graph_launch(sdr_bank *b, const void *const *iq_dev, sdr::InFormat fm
         return fail(SDR_ERR_BAD_ARG, "null argument");
     if (!b->graph_ready)
         return fail(SDR_ERR_STATE, "no graph captured (sdr_graph_capture)");
-    if (fmt != b->graph_fmt)
-        return fail(SDR_ERR_STATE, fmt == sdr::InFormat::SC16 ? "the graph was captured for float32 input (sdr_graph_launch)"
-                                                               : "the graph was captured for sc16 input (sdr_graph_launch_sc16)");
+    if (fmt != b->graph_fmt) {
+        switch (b->graph_fmt) {
+        case sdr::InFormat::F32: return fail(SDR_ERR_STATE, "the graph was captured for float32 input (sdr_graph_launch)");
+        case sdr::InFormat::SC16: return fail(SDR_ERR_STATE, "the graph was captured for sc16 input (sdr_graph_launch_sc16)");
+        case sdr::InFormat::CS8: return fail(SDR_ERR_STATE, "the graph was captured for cs8 input (sdr_graph_launch_iq8 with SDR_IQ8_CS8)");
+        default: return fail(SDR_ERR_STATE, "the graph was captured for cu8 input (sdr_graph_launch_iq8 with SDR_IQ8_CU8)");
+        }
+    }
     if (b->failed)
         return fail(SDR_ERR_STATE, "an earlier process call failed half way; destroy the bank");
     int max_slots = 0;
@@ -278,7 +283,9 @@ static int graph_launch(sdr_bank *b, const void *const *iq_dev, sdr::InFormat fm
         if (!iq_dev[k] || (reinterpret_cast<uintptr_t>(iq_dev[k]) & 15))
             return fail(SDR_ERR_BAD_ARG, "every input pointer must be non-null and 16-byte aligned");
         cursor[k] = sdr::BatchCursor{};
-        if (fmt == sdr::InFormat::SC16)
+        if (sdr::is_iq8(fmt))
+            cursor[k].iq8 = static_cast<const uint8_t *>(iq_dev[k]);
+        else if (fmt == sdr::InFormat::SC16)
             cursor[k].iq_sc16 = static_cast<const int16_t *>(iq_dev[k]);
         else
             cursor[k].iq = static_cast<const float *>(iq_dev[k]);
@@ -399,6 +406,18 @@ static int graph_launch(sdr_bank *b, const void *const *iq_dev, sdr::InFormat fm
 
 int sdr_graph_capture(sdr_bank *b, int n_frames) { return graph_capture(b, n_frames, sdr::InFormat::F32); }
 int sdr_graph_capture_sc16(sdr_bank *b, int n_frames) { return graph_capture(b, n_frames, sdr::InFormat::SC16); }
+int sdr_graph_capture_iq8(sdr_bank *b, int n_frames, int format)
+{
+    if (format != SDR_IQ8_CS8 && format != SDR_IQ8_CU8)
+        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
+    return graph_capture(b, n_frames, format == SDR_IQ8_CU8 ? sdr::InFormat::CU8 : sdr::InFormat::CS8);
+}
+int sdr_graph_launch_iq8(sdr_bank *b, const void *const *iq_dev, int format)
+{
+    if (format != SDR_IQ8_CS8 && format != SDR_IQ8_CU8)
+        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
+    return graph_launch(b, iq_dev, format == SDR_IQ8_CU8 ? sdr::InFormat::CU8 : sdr::InFormat::CS8);
+}
 
 int sdr_graph_launch(sdr_bank *b, const float *const *iq_dev)
 {

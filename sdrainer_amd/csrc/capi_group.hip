@@ -183,6 +183,17 @@ int sdr_group_push_iq_sc16(sdr_group *g, int band, int sample_rate, const int16_
     return sdr_push_iq_sc16(b, local, sample_rate, iq, n_values);
 }
 
+int sdr_group_push_iq8(sdr_group *g, int band, int sample_rate, const void *iq, size_t n_values, int format)
+{
+    sdr_bank *b = nullptr;
+    int local = 0;
+    int rc = route(g, band, &b, &local);
+    if (rc)
+        return rc;
+    KeepDevice keep;
+    return sdr_push_iq8(b, local, sample_rate, iq, n_values, format);
+}
+
 int sdr_group_push_kiwi_snd(sdr_group *g, int band, int sample_rate, const uint8_t *payload, size_t n_bytes)
 {
     sdr_bank *b = nullptr;
@@ -231,8 +242,8 @@ int sdr_group_process_staged_limit(sdr_group *g, int max_frames, int *n_frames_o
 }
 
 namespace {
-// iq_dev: one pointer per member, float32 frames or (sc16) complex int16 frames
-static int group_process_device(sdr_group *g, const void *const *iq_dev, int n_frames, bool sc16)
+// iq_dev: one pointer per member, frames of one kind: 0 float32, 1 sc16, 2 + format 8-bit (SDR_IQ8_CS8 / SDR_IQ8_CU8)
+static int group_process_device(sdr_group *g, const void *const *iq_dev, int n_frames, int kind)
 {
     if (!g || !iq_dev)
         return fail(SDR_ERR_BAD_ARG, "null argument");
@@ -253,8 +264,9 @@ static int group_process_device(sdr_group *g, const void *const *iq_dev, int n_f
     // (sdr_process_device only enqueues: every member is launched before anything is waited for)
     for (int m = 0; m < g->rt.n_members; m++) {
         sdr_bank *b = g->banks[(size_t)m];
-        rc = sc16 ? sdr_process_device_sc16(b, static_cast<const int16_t *>(iq_dev[m]), n_frames)
-                  : sdr_process_device(b, static_cast<const float *>(iq_dev[m]), n_frames);
+        rc = kind >= 2   ? sdr_process_device_iq8(b, iq_dev[m], n_frames, kind - 2)
+             : kind == 1 ? sdr_process_device_sc16(b, static_cast<const int16_t *>(iq_dev[m]), n_frames)
+                         : sdr_process_device(b, static_cast<const float *>(iq_dev[m]), n_frames);
         if (rc)
             return member_failed(g, rc, m);
     }
@@ -264,12 +276,19 @@ static int group_process_device(sdr_group *g, const void *const *iq_dev, int n_f
 
 int sdr_group_process_device(sdr_group *g, const float *const *iq_dev, int n_frames)
 {
-    return group_process_device(g, reinterpret_cast<const void *const *>(iq_dev), n_frames, false);
+    return group_process_device(g, reinterpret_cast<const void *const *>(iq_dev), n_frames, 0);
 }
 
 int sdr_group_process_device_sc16(sdr_group *g, const int16_t *const *iq_dev, int n_frames)
 {
-    return group_process_device(g, reinterpret_cast<const void *const *>(iq_dev), n_frames, true);
+    return group_process_device(g, reinterpret_cast<const void *const *>(iq_dev), n_frames, 1);
+}
+
+int sdr_group_process_device_iq8(sdr_group *g, const void *const *iq_dev, int n_frames, int format)
+{
+    if (format != SDR_IQ8_CS8 && format != SDR_IQ8_CU8)
+        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
+    return group_process_device(g, iq_dev, n_frames, 2 + format);
 }
 
 int sdr_group_sync(sdr_group *g)

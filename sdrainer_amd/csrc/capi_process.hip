@@ -572,7 +572,8 @@ static int staging_ready(sdr_bank *b, bool raw)
 }
 
 // One push of `n_values` values (two per sample, `value_bytes` bytes each) of kind `kind` (sdr_bank::staged_kind) behind
-// what the band has staged.  The stream arrives in whole hops: at hop = block_size that is the reference's whole frames
+// what the band has staged.  A band's row of the pinned buffer is 8 bytes per sample (float32) or 4 (raw: int16 values
+// fill it, 8-bit values half of it).  The stream arrives in whole hops: at hop = block_size that is the reference's whole frames
 // (rx/receiver.go:323-326), below it a piece is any whole number of hops (host/overlap.h StreamStage).
 static int push_samples(sdr_bank *b, int band, int sample_rate, const void *iq, size_t n_values, int kind, size_t value_bytes,
                         const char *mixed)
@@ -600,7 +601,8 @@ static int push_samples(sdr_bank *b, int band, int sample_rate, const void *iq, 
     b->staged_kind[band] = kind;
     sdr_bank::Staging &st = b->stage[b->stage_cur];
     unsigned char *row = kind == 1 ? reinterpret_cast<unsigned char *>(st.h_f32) : st.h_raw;
-    staging_copy(row + ((size_t)band * b->stage_cap() + ss.staged) * 2 * value_bytes, iq,
+    const size_t row_sample_bytes = kind == 1 ? 2 * sizeof(float) : 4;
+    staging_copy(row + (size_t)band * b->stage_cap() * row_sample_bytes + ss.staged * 2 * value_bytes, iq,
                  n_values * value_bytes);  // copy on push: the caller may reuse its buffer (kiwi/client.go:203)
     ss.push(ns);
     return SDR_OK;
@@ -609,7 +611,7 @@ static int push_samples(sdr_bank *b, int band, int sample_rate, const void *iq, 
 
 int sdr_push_iq(sdr_bank *b, int band, int sample_rate, const float *iq, size_t n_floats)
 {
-    return push_samples(b, band, sample_rate, iq, n_floats, 1, sizeof(float), "band already holds int16 frames (KiwiSDR or sc16) in this batch");
+    return push_samples(b, band, sample_rate, iq, n_floats, 1, sizeof(float), "band already holds int16 (KiwiSDR or sc16) or 8-bit frames in this batch");
 }
 
 int sdr_push_kiwi_snd(sdr_bank *b, int band, int sample_rate, const uint8_t *payload, size_t n_bytes)
@@ -628,14 +630,25 @@ int sdr_push_kiwi_snd(sdr_bank *b, int band, int sample_rate, const uint8_t *pay
     if (n_bytes <= kHeader || (n_bytes - kHeader) % per != 0)  // kiwi/kiwi.go:96-98 panics on a partial block
         return fail(SDR_ERR_BAD_SIZE, "SND payload does not hold whole frames");
     return push_samples(b, band, sample_rate, payload + kHeader, (n_bytes - kHeader) / 2, 2, sizeof(int16_t),
-                        "band already holds float32 or sc16 frames in this batch");
+                        "band already holds float32, sc16 or 8-bit frames in this batch");
 }
 
 // sc16 frames from the host: staged raw like a KiwiSDR payload (half the bytes of float32 go over PCIe) and converted on
 // the device by k_unpack_sc16 into the float32 staging buffer the FFT reads
 int sdr_push_iq_sc16(sdr_bank *b, int band, int sample_rate, const int16_t *iq, size_t n_values)
 {
-    return push_samples(b, band, sample_rate, iq, n_values, 3, sizeof(int16_t), "band already holds float32 or KiwiSDR frames in this batch");
+    return push_samples(b, band, sample_rate, iq, n_values, 3, sizeof(int16_t), "band already holds float32, KiwiSDR or 8-bit frames in this batch");
+}
+
+// cs8 / cu8 frames from the host: staged raw (a quarter of the bytes of float32 go over PCIe) and converted on the device by
+// k_unpack_iq8 into the float32 staging buffer the FFT reads
+int sdr_push_iq8(sdr_bank *b, int band, int sample_rate, const void *iq, size_t n_values, int format)
+{
+    if (format != SDR_IQ8_CS8 && format != SDR_IQ8_CU8)
+        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
+    return push_samples(b, band, sample_rate, iq, n_values, format == SDR_IQ8_CU8 ? 5 : 4, 1,
+                        format == SDR_IQ8_CU8 ? "band already holds float32, int16 or cs8 frames in this batch"
+                                              : "band already holds float32, int16 or cu8 frames in this batch");
 }
 
 int sdr_staged_frames(sdr_bank *b, int band)
@@ -679,18 +692,22 @@ int sdr_process_staged_limit(sdr_bank *b, int max_frames, int *n_frames_out)
         const size_t up = sdr::span_samples(n, b->hop, c.block_size) - ss.history;  // samples
         float *dst = st.d_f32.p + ((size_t)band * cap + ss.history) * 2;
         if (b->staged_kind[band] >= 2) {
-            // raw int16 (KiwiSDR big-endian, or sc16): upload half the bytes, unpack in HBM (k_unpack.hip)
+            // raw int16 (KiwiSDR big-endian, or sc16) or bytes (cs8 / cu8): upload half or a quarter of the bytes, unpack in
+            // HBM (k_unpack.hip)
             if (!st.d_raw.p) {
                 hipError_t e = st.d_raw.alloc(4 * cap * (size_t)c.n_bands);
                 if (e != hipSuccess)
                     return fail(SDR_ERR_HIP, "hipMalloc raw staging failed");
             }
             uint8_t *rdst = st.d_raw.p + (size_t)band * cap * 4;
-            HIP_TRY(hipMemcpyAsync(rdst, st.h_raw + (size_t)band * cap * 4, 4 * up, hipMemcpyHostToDevice, b->copy_stream));
-            if (b->staged_kind[band] == 2)
+            const int kind = b->staged_kind[band];
+            HIP_TRY(hipMemcpyAsync(rdst, st.h_raw + (size_t)band * cap * 4, (kind >= 4 ? 2 : 4) * up, hipMemcpyHostToDevice, b->copy_stream));
+            if (kind == 2)
                 HIP_TRY(sdr::launch_unpack_be16(rdst, dst, 2 * up, b->copy_stream));
-            else
+            else if (kind == 3)
                 HIP_TRY(sdr::launch_unpack_sc16(reinterpret_cast<const int16_t *>(rdst), dst, 2 * up, b->copy_stream));
+            else
+                HIP_TRY(sdr::launch_unpack_iq8(rdst, dst, 2 * up, kind == 5, b->copy_stream));
         } else {
             HIP_TRY(hipMemcpyAsync(dst, st.h_f32 + (size_t)band * cap * 2, sizeof(float) * 2 * up, hipMemcpyHostToDevice, b->copy_stream));
         }
@@ -736,8 +753,10 @@ int sdr_process_staged_limit(sdr_bank *b, int max_frames, int *n_frames_out)
     for (int band = 0; band < c.n_bands; band++) {
         const sdr::StreamStage::Consumed &t = took[(size_t)band];
         if (t.left > 0) {
-            if (b->staged_kind[band] >= 2)
-                memcpy(b->stage[next].h_raw + (size_t)band * cap * 4, b->stage[prev].h_raw + ((size_t)band * cap + t.left_from) * 4, 4 * t.left);
+            if (b->staged_kind[band] >= 2) {
+                const size_t sb = b->staged_kind[band] >= 4 ? 2 : 4;  // bytes per raw sample
+                memcpy(b->stage[next].h_raw + (size_t)band * cap * 4, b->stage[prev].h_raw + (size_t)band * cap * 4 + t.left_from * sb, sb * t.left);
+            }
             else
                 memcpy(b->stage[next].h_f32 + (size_t)band * cap * 2, b->stage[prev].h_f32 + ((size_t)band * cap + t.left_from) * 2,
                        sizeof(float) * 2 * t.left);
@@ -771,8 +790,9 @@ static int process_device_stream(sdr_bank *b, const void *iq_dev, int n_frames, 
     const int rc = check_device_input(b, iq_dev);
     if (rc)
         return rc;
-    if (band_stride_samples % 4 != 0)
-        return fail(SDR_ERR_BAD_ARG, "band_stride_samples must be a multiple of 4 samples (every band's stream 16-byte aligned)");
+    if (band_stride_samples % (sdr::is_iq8(fmt) ? 8 : 4) != 0)
+        return fail(SDR_ERR_BAD_ARG, sdr::is_iq8(fmt) ? "band_stride_samples must be a multiple of 8 samples (every band's stream 16-byte aligned)"
+                                                      : "band_stride_samples must be a multiple of 4 samples (every band's stream 16-byte aligned)");
     if (band_stride_samples < sdr::span_samples(n_frames, b->hop, b->cfg.block_size) || band_stride_samples > 0xffffffffu)
         return fail(SDR_ERR_BAD_ARG, "band_stride_samples is smaller than (n_frames - 1) * hop + block_size (or beyond 2^32 - 1)");
     return process_device_impl(b, iq_dev, n_frames, band_stride_samples, fmt);
@@ -794,6 +814,31 @@ int sdr_process_device_stream(sdr_bank *b, const float *iq_dev, int n_frames, si
 int sdr_process_device_stream_sc16(sdr_bank *b, const int16_t *iq_dev, int n_frames, size_t band_stride_samples)
 {
     return process_device_stream(b, iq_dev, n_frames, band_stride_samples, sdr::InFormat::SC16);
+}
+
+// 8-bit input: format -> the FFT's InFormat (false: neither SDR_IQ8_CS8 nor SDR_IQ8_CU8)
+static bool iq8_format(int format, sdr::InFormat *fmt)
+{
+    if (format != SDR_IQ8_CS8 && format != SDR_IQ8_CU8)
+        return false;
+    *fmt = format == SDR_IQ8_CU8 ? sdr::InFormat::CU8 : sdr::InFormat::CS8;
+    return true;
+}
+
+int sdr_process_device_iq8(sdr_bank *b, const void *iq_dev, int n_frames, int format)
+{
+    sdr::InFormat fmt;
+    if (!iq8_format(format, &fmt))
+        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
+    return process_device_dense(b, iq_dev, n_frames, fmt);
+}
+
+int sdr_process_device_stream_iq8(sdr_bank *b, const void *iq_dev, int n_frames, size_t band_stride_samples, int format)
+{
+    sdr::InFormat fmt;
+    if (!iq8_format(format, &fmt))
+        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
+    return process_device_stream(b, iq_dev, n_frames, band_stride_samples, fmt);
 }
 
 int sdr_hop(sdr_bank *b) { return b ? b->hop : -1; }

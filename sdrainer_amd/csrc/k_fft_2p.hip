@@ -10,8 +10,16 @@
 
 #include "../../include/sdrainer_hip.h"
 #include "fft_2p.h"
+#include "iq8.h"
 #include "sc16.h"
 #include "sdr_device.h"
+
+// 8-bit input (iq8.h).  k_fft_2p_iq8.hip compiles this file again with SDR_FFT2P_IQ8 = 1: that unit holds phase A's
+// 8-bit instances (k_fft2p_a / k_fft2p_win_a<LOGN, CS8 / CU8>) and launch_fft_2p_iq8, which runs them in front of THIS
+// unit's phase B (launch_fft2p_b); this unit's kernels stay the four k_fft2p_a, the four k_fft2p_win_a and the two k_fft2p_b.
+#if !defined(SDR_FFT2P_IQ8)
+#define SDR_FFT2P_IQ8 0
+#endif
 
 namespace sdr {
 
@@ -28,6 +36,7 @@ __device__ __forceinline__ fft64::cplx tw_load(const fft64::cplx *__restrict__ t
 #include "k_fft_2p_a.h"
 #undef SDR_FFT2P_WIN
 
+#if !SDR_FFT2P_IQ8
 // Phase B of the same group: workgroup x = frame_local * WG_B + w takes the residues c = w G .. w G + G - 1, writes their
 // bins' psd (fft-shifted) and the tap of the listeners whose bins are among them (k_fft_psd.hip "The tap"): the row's
 // values of those residues go to LDS first, the tap reads them there.
@@ -101,6 +110,20 @@ __global__ __launch_bounds__(fft2p::T) void k_fft2p_b(const fft64::cplx *__restr
     }
 }
 
+// phase B of frames [f0, f0 + g) of a group, behind their phase A on the same stream
+hipError_t launch_fft2p_b(int logn, const fft64::cplx *tw, float *psd, int n_bands, int out_stride, int f0, int g, int group, FftTap tap, LaunchAt at)
+{
+    if (logn == 15)
+        launch_kernel((k_fft2p_b<15>), dim3(g * fft2p::Phases<15>::WG_B, n_bands), dim3(fft2p::T), 0, at, static_cast<const fft64::cplx *>(tap.scratch), tw,
+                      psd, out_stride, f0, group, tap.bins, tap.out, tap.n, tap.stride);
+    else if (logn == 16)
+        launch_kernel((k_fft2p_b<16>), dim3(g * fft2p::Phases<16>::WG_B, n_bands), dim3(fft2p::T), 0, at, static_cast<const fft64::cplx *>(tap.scratch), tw,
+                      psd, out_stride, f0, group, tap.bins, tap.out, tap.n, tap.stride);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 template <int LOGN>
 static hipError_t launch_fft2p_t(FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
                                  int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
@@ -137,11 +160,63 @@ static hipError_t launch_fft2p_t(FftChoice fft, InFormat fmt, const void *iq, co
 hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
 {
+    if (is_iq8(fmt))  // k_fft_2p_iq8.hip
+        return launch_fft_2p_iq8(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
     switch (logn) {
     case 15: return launch_fft2p_t<15>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
     case 16: return launch_fft2p_t<16>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
     default: return hipErrorInvalidValue;
     }
 }
+
+#else  // SDR_FFT2P_IQ8
+hipError_t launch_fft2p_b(int logn, const fft64::cplx *tw, float *psd, int n_bands, int out_stride, int f0, int g, int group, FftTap tap, LaunchAt at);
+
+template <int LOGN, InFormat FMT>
+static hipError_t launch_fft2p_iq8_t(FftChoice fft, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+                                     size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
+{
+    using PH = fft2p::Phases<LOGN>;
+    const hipStream_t stream = at.stream;
+    if (n_frames <= 0 || n_bands <= 0)
+        return hipSuccess;
+    if (!tap.scratch || fft.group_frames <= 0)
+        return hipErrorInvalidValue;
+    const int group = fft.group_frames;
+    // (at.done rides on the last frame group's phase B, the last launch)
+    for (int f0 = 0; f0 < n_frames; f0 += group) {
+        const int g = n_frames - f0 < group ? n_frames - f0 : group;
+        if (tap.window)
+            hipLaunchKernelGGL((k_fft2p_win_a<LOGN, FMT>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw, tap.scratch, in_stride,
+                               frame_stride, f0, group, tap.window);
+        else
+            hipLaunchKernelGGL((k_fft2p_a<LOGN, FMT>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw, tap.scratch, in_stride,
+                               frame_stride, f0, group);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess)
+            e = launch_fft2p_b(LOGN, tw, psd, n_bands, out_stride, f0, g, group, tap, f0 + group >= n_frames ? at : LaunchAt(stream));
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_fft_2p_iq8(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
+                             int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
+{
+    const bool cu8 = fmt == InFormat::CU8;
+    if (!is_iq8(fmt))
+        return hipErrorInvalidValue;
+    switch (logn) {
+    case 15:
+        return cu8 ? launch_fft2p_iq8_t<15, InFormat::CU8>(fft, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at)
+                   : launch_fft2p_iq8_t<15, InFormat::CS8>(fft, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 16:
+        return cu8 ? launch_fft2p_iq8_t<16, InFormat::CU8>(fft, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at)
+                   : launch_fft2p_iq8_t<16, InFormat::CS8>(fft, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    default: return hipErrorInvalidValue;
+    }
+}
+#endif  // SDR_FFT2P_IQ8
 
 }  // namespace sdr

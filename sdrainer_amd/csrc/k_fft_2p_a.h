@@ -5,7 +5,7 @@
 // k_fft_2p.hip includes this file twice.  SDR_FFT2P_WIN = 0: k_fft2p_a, whose tokens are what they were before the window
 // existed.  SDR_FFT2P_WIN = 1: k_fft2p_win_a, which multiplies sample i of the frame by win[i] (sdr_set_window) - one
 // correctly rounded float32 multiplication per component, of the converted value for sc16 input - where the plain kernel
-// widens it.
+// widens it.  FMT = CS8 / CU8 (iq8.h: two bytes per sample) is instantiated by k_fft_2p_iq8.hip only.
 #if SDR_FFT2P_WIN
 #define SDR_K_FFT2P_A k_fft2p_win_a
 #define SDR_FFT2P_WIN_PARAM , const float *__restrict__ win
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(fft2p::T) void SDR_K_FFT2P_A(const void *__restrict
                 xi[s] = (double)v.y;
 #endif
             }
-        } else {
+        } else if constexpr (FMT == InFormat::SC16) {
             const uint32_t *__restrict__ iq = reinterpret_cast<const uint32_t *>(cur ? cur->iq_sc16 : static_cast<const int16_t *>(iq_arg)) + frame_at;
 #pragma unroll
             for (int s = 0; s < fft2p::R; s++) {
@@ -58,6 +58,23 @@ __global__ __launch_bounds__(fft2p::T) void SDR_K_FFT2P_A(const void *__restrict
                 const uint32_t v = iq[fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s))];
                 xr[s] = (double)sc16::re_of(v);
                 xi[s] = (double)sc16::im_of(v);
+#endif
+            }
+        } else {
+            const uint16_t *__restrict__ iq = reinterpret_cast<const uint16_t *>(cur ? cur->iq8 : static_cast<const uint8_t *>(iq_arg)) + frame_at;
+            constexpr iq8::Format F8 = iq8::format_of(FMT == InFormat::CU8);
+#pragma unroll
+            for (int s = 0; s < fft2p::R; s++) {
+#if SDR_FFT2P_WIN
+                const int i = fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s));
+                const uint32_t v = iq[i];
+                const float wv = win[i];
+                xr[s] = (double)__fmul_rn(iq8::re_of(v, F8), wv);
+                xi[s] = (double)__fmul_rn(iq8::im_of(v, F8), wv);
+#else
+                const uint32_t v = iq[fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s))];
+                xr[s] = (double)iq8::re_of(v, F8);
+                xi[s] = (double)iq8::im_of(v, F8);
 #endif
             }
         }

@@ -14,6 +14,7 @@
 #include "fft_f64.h"
 #include "fft_r32.h"
 #include "gomath.h"
+#include "iq8.h"
 #include "sc16.h"
 #include "sdr_device.h"
 
@@ -24,6 +25,12 @@
 // multiplication is the plain kernels'.  A translation unit of its own keeps the plain kernels' code exactly what it was.
 #if !defined(SDR_FFT_WIN)
 #define SDR_FFT_WIN 0
+#endif
+// 8-bit input (iq8.h).  k_fft_psd_iq8.hip compiles this file a third time with SDR_FFT_IQ8 = 1 (and SDR_FFT_WIN = 1 for
+// load_window): that unit holds k_fft_psd_iq8<LOGN, WIN>, plain and windowed, and launch_fft_iq8 - and none of the kernels
+// and launchers of the other two units, whose code stays exactly what it was.
+#if !defined(SDR_FFT_IQ8)
+#define SDR_FFT_IQ8 0
 #endif
 #if SDR_FFT_WIN
 #define SDR_K_FFT_PSD k_fft_psd_win
@@ -336,6 +343,7 @@ __device__ __forceinline__ void store_psd(const double (&xr)[fft64::Plan<LOGN>::
     }
 }
 
+#if !SDR_FFT_IQ8
 // Where the time of a frame goes (N = 16384, tools/fft_bench.hip with -DSDR_FFT_CLOCK and the -DSDR_ABLATE
 // builds, MI355X at 2.3 GHz in-kernel): the phases of a frame run one after the other on its CU - all 16 waves
 // wait for the input, then all compute, then all exchange, ... - and each phase is bound by a different unit, so
@@ -647,6 +655,152 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
+#else  // SDR_FFT_IQ8
+constexpr int kMaxLdsTap = 4096;  // (as in the other units: listeners per band the LDS tap holds bins for)
+
+// k_fft_psd for 8-bit input (iq8.h: one byte I, one byte Q per sample, cs8 or cu8): the one-frame workgroup of
+// k_fft_psd_sc16 with two bytes per sample.  Its LDS-DMA moves 512 samples per 1 KB row - R / 8 rows per wave - into iq8.h's
+// staging image, pass 0 reads one 16-bit LDS word per register slot and converts where the float32 kernel widens (exact:
+// iq8::to_f32).  From the first butterfly on everything is the float32 kernel's (run_passes, store_psd, the LDS tap), so
+// the results are the float32 path's bits for the converted values.  flip / c: iq8::Format.  WIN: the windowed twin, one
+// correctly rounded float32 multiplication of the converted value per component (load_window).
+template <int LOGN, bool WIN>
+__global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 ? 4 : 1)) void k_fft_psd_iq8(const uint8_t *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
+                                                                       const fft64::cplx *__restrict__ tw, float *__restrict__ psd,
+                                                                       size_t in_stride, int frame_stride, int out_stride, const int *__restrict__ tap_bins,
+                                                                       float *__restrict__ tap_out, int n_tap, int tap_stride, unsigned flip, float c,
+                                                                       const float *__restrict__ win)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    using PL = fft64::Plan<LOGN>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double *lds = reinterpret_cast<double *>(smem);
+    Stamps st;
+#if defined(SDR_FFT_PHASES)
+    st.on = false;
+#endif
+    const uint8_t *__restrict__ iq = cur ? cur->iq8 : iq_arg;  // graph replay: the batch's input pointer lives in device memory
+    const int frame = blockIdx.x;
+    const size_t in_band = blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
+    const int t = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    {
+        // frame -> LDS: row r = wave * R/8 + j; lane p fetches granule iq8::granule(p, r) of the row (the swizzle lives in
+        // the source address, the DMA writes lane p's 16 bytes at row base + 16 p); the descriptor ends with the frame
+        constexpr int ROWS_PER_WAVE = iq8::kRowsPerWave<LOGN>;
+        static_assert(ROWS_PER_WAVE * (PL::T / 64) * 1024 == PL::N * 2, "the waves' rows are the frame");
+        const int lane = t & 63;
+        const rsrc_t xrs = make_rsrc(iq + input_sample_offset(in_band, frame, frame_stride) * 2, PL::N * 2u);
+#pragma unroll
+        for (int j = 0; j < ROWS_PER_WAVE; j++) {
+            const int r = wave * ROWS_PER_WAVE + j;
+            const int g = iq8::granule<LOGN>(lane, r);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void *)(smem + r * 1024), 16,
+                                                     (unsigned)g * 16u, r * 1024, 0, SDR_FFT_DMA_AUX);
+        }
+    }
+    // the listeners' bins into LDS (behind the exchange area) while the frame is on its way
+    int *lds_bins = reinterpret_cast<int *>(smem + fft64::kLdsBytes<LOGN>);
+    const bool lds_tap = n_tap > 0 && n_tap <= kMaxLdsTap;
+    if (lds_tap)
+        for (int l = threadIdx.x; l < n_tap; l += PL::T)
+            lds_bins[l] = tap_bins[(size_t)blockIdx.y * tap_stride + l];
+    float wv[WIN ? PL::R : 1];
+    if constexpr (WIN)
+        load_window<LOGN>(wv, t, win);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    double xr[PL::R], xi[PL::R];
+    {
+        // dsp/fft.go:59-69 setSamplesFromIQ: slot m <- sample input_sample(t, m), the image address linear over GF(2)
+        const iq8::Format fmt{flip, c};
+        const int thread_byte = iq8::lds_byte<LOGN>(fft64::input_sample<LOGN>(t, 0));
+#pragma unroll
+        for (int m = 0; m < PL::R; m++) {
+            const int slot_byte = iq8::lds_byte<LOGN>(fft64::input_sample<LOGN>(0, m));
+            const uint32_t w = *reinterpret_cast<const uint16_t *>(smem + (thread_byte ^ slot_byte));
+            if constexpr (WIN) {
+                xr[m] = (double)__fmul_rn(iq8::re_of(w, fmt), wv[m]);
+                xi[m] = (double)__fmul_rn(iq8::im_of(w, fmt), wv[m]);
+            } else {
+                xr[m] = (double)iq8::re_of(w, fmt);
+                xi[m] = (double)iq8::im_of(w, fmt);
+            }
+        }
+    }
+    __syncthreads();  // everyone has its samples: the exchange area may be written again
+    const fft64::cplx no_pre[kTwPreMax] = {};
+    run_passes<LOGN, 0>(xr, xi, t, make_rsrc(tw, (unsigned)(PL::TW_TOTAL * sizeof(fft64::cplx))), tw, lds, no_pre, st);
+    if constexpr (!last_lds_exchange_is_cross<LOGN>())
+        if (lds_tap)
+            __syncthreads();  // a wave-local last exchange fences only its own wave; the row goes everywhere
+    store_psd<LOGN, true>(xr, xi, t, psd + (out_band + frame) * PL::N, smem, lds_tap);
+    if (lds_tap) {
+        __syncthreads();  // the row is in LDS
+        const float *row = reinterpret_cast<const float *>(smem);
+        float *out = tap_out + (out_band + frame) * (size_t)tap_stride;
+        for (int l = threadIdx.x; l < n_tap; l += PL::T) {
+            const int bin = lds_bins[l];
+            out[l] = bin >= 0 ? row[bin] : 0.0f;
+        }
+    } else if (n_tap > 0) {
+        // more listeners than the LDS tap holds: re-read the stored row once it has reached memory
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        const float *row = psd + (out_band + frame) * PL::N;
+        float *out = tap_out + (out_band + frame) * (size_t)tap_stride;
+        const int *bins = tap_bins + (size_t)blockIdx.y * tap_stride;
+        for (int l = threadIdx.x; l < n_tap; l += PL::T) {
+            const int bin = bins[l];
+            out[l] = bin >= 0 ? row[bin] : 0.0f;
+        }
+    }
+#endif  // __HIP_DEVICE_COMPILE__
+}
+
+template <int LOGN>
+static hipError_t launch_fft_iq8_t(bool cu8, const uint8_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+                                   size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
+{
+    using PL = fft64::Plan<LOGN>;
+    static LdsLimitOnce lds_once;
+    const hipError_t attr_err = raise_lds_limit_once(
+        lds_once, {reinterpret_cast<const void *>(&k_fft_psd_iq8<LOGN, false>), reinterpret_cast<const void *>(&k_fft_psd_iq8<LOGN, true>)},
+        fft64::kLdsBytes<LOGN> + kMaxLdsTap * 4);
+    if (attr_err != hipSuccess)
+        return attr_err;
+    if (n_frames <= 0 || n_bands <= 0)
+        return hipSuccess;
+    const unsigned tap_lds = tap.n > 0 && tap.n <= kMaxLdsTap ? ((tap.n * 4 + 255) & ~255) : 0;
+    const iq8::Format f = iq8::format_of(cu8);
+    // one frame per workgroup, always (FftChoice::fpw is the float32 kernel's)
+    if (tap.window)
+        launch_kernel((k_fft_psd_iq8<LOGN, true>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at, iq, cur, tw, psd, in_stride,
+                      frame_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride, f.flip, f.c, tap.window);
+    else
+        launch_kernel((k_fft_psd_iq8<LOGN, false>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at, iq, cur, tw, psd, in_stride,
+                      frame_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride, f.flip, f.c, static_cast<const float *>(nullptr));
+    return hipGetLastError();
+}
+
+// N = 512 - 16384 from cs8 / cu8 frames, with tap.window (in window_layout's order) or without (launch_fft hands such a
+// launch on)
+hipError_t launch_fft_iq8(int logn, bool cu8, const uint8_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
+{
+    switch (logn) {
+    case 9: return launch_fft_iq8_t<9>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 10: return launch_fft_iq8_t<10>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 11: return launch_fft_iq8_t<11>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 12: return launch_fft_iq8_t<12>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 13: return launch_fft_iq8_t<13>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    case 14: return launch_fft_iq8_t<14>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    default: return hipErrorInvalidValue;
+    }
+}
+#endif  // SDR_FFT_IQ8
+
+#if !SDR_FFT_IQ8
 // frames per workgroup when the plan asks for none (FftChoice::fpw, SDR_FFT_FPW)
 // (LDS behind the exchange area: the one-frame workgroup's copy of its listeners' bins)
 constexpr int kDefaultFpw = 1;  // in the pipeline short-lived workgroups win: 0.250 (1) / 0.253 (2) / 0.291 (4) / 0.294 ms (8) per step, standalone the other way round (0.174 / 0.166 / 0.165 / 0.164 ms)
@@ -715,17 +869,26 @@ void window_layout(int logn, const float *w, float *out)
 hipError_t launch_fft_win(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
                           int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
 {
-    if (!tap.window || fft.r32 || fft.two_phase)
+    if (!tap.window || fft.r32 || fft.two_phase || is_iq8(fmt))
         return hipErrorInvalidValue;  // (host/batch_plan.h: a windowed batch is never planned onto k_fft_r32)
 #else
 // The bank's twiddle buffer for N = 16384 holds both kernels' tables, the 32-point kernel's behind the other.
 hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
                       int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
 {
-    if (fmt != InFormat::F32 && fmt != InFormat::SC16)
+    if (fmt != InFormat::F32 && fmt != InFormat::SC16 && !is_iq8(fmt))
         return hipErrorInvalidValue;
     if (fft.two_phase)  // (with tap.window: k_fft2p_win_a)
         return launch_fft_2p(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    if (is_iq8(fmt)) {  // k_fft_r32_iq8.hip / k_fft_psd_iq8.hip, plain or windowed
+        const uint8_t *iq8p = static_cast<const uint8_t *>(iq);
+        if (!fft.r32)
+            return launch_fft_iq8(logn, fmt == InFormat::CU8, iq8p, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+        if (logn != 14 || tap.window)
+            return hipErrorInvalidValue;
+        return launch_fft_r32_iq8(fmt == InFormat::CU8, iq8p, cur, tw + fft64::Plan<14>::TW_TOTAL, psd, n_frames, n_bands, in_stride, frame_stride, out_stride,
+                                  tap, fft.reserve_cus, fft.reserve_forced, at);
+    }
     if (tap.window)
         return launch_fft_win(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
     if (fft.r32) {
@@ -784,5 +947,7 @@ void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx 
     }
 }
 #endif  // !SDR_FFT_WIN
+
+#endif  // !SDR_FFT_IQ8
 
 }  // namespace sdr

@@ -31,10 +31,16 @@
 // - and the samples are converted (sc16::to_f32) where the float32 kernel widens.  Everything else is the float32
 // kernel's.  Its own translation unit keeps the float32 kernel's source, and so its code, exactly as it was.
 //
+// 8-bit input.  k_fft_r32_iq8.hip compiles this file again with SDR_R32_IQ8 = 1: the kernel k_fft_r32_iq8 reads cs8 / cu8
+// frames (iq8.h), one 16-bit word per slot - the sc16 variant's 32 registers and plan, 2 bytes per lane, 128 contiguous
+// bytes per wave instruction - and converts them exactly (iq8::to_f32) where the float32 kernel widens.  The format is a
+// launch argument, the XOR mask of a sample word; it, the constant it implies and 1/128 sit in three vector registers
+// through the frame loop (the loop has no scalar register to spare, and the 32-register prefetch leaves vector ones).
+//
 // Overlapped frames (a frame stride below N: host/overlap.h).  The frame loop has no scalar register left for a stride:
 // one more live SGPR, even packed into the word that holds the frame count, is one SGPR spilled.  So the kernels above
 // keep their dense frames (frame f at sample f * N of the band, a constant shift) and k_fft_r32_hop.hip /
-// k_fft_r32_hop_sc16.hip compile this file again with SDR_R32_HOP = 1: k_fft_r32_hop(_sc16) take the stride as a shift
+// k_fft_r32_hop_sc16.hip / k_fft_r32_hop_iq8.hip compile this file again with SDR_R32_HOP = 1: k_fft_r32_hop(_sc16, _iq8) take the stride as a shift
 // (every hop is a power of two) beside the frame count, fold it into the scalar base of the frame's buffer descriptor
 // and pay that one spilled SGPR (into a vector register's lane: no scratch).  launch_fft_r32(_sc16) hand a launch with
 // frame_stride != N on to them.
@@ -52,13 +58,35 @@
 #if !defined(SDR_R32_HOP)
 #define SDR_R32_HOP 0
 #endif
-#if SDR_R32_SC16
+#if !defined(SDR_R32_IQ8)
+#define SDR_R32_IQ8 0
+#endif
+// (the 8-bit forms' extra kernel parameter - the format's XOR mask - and their launchers' leading one)
+#if SDR_R32_IQ8
+#define SDR_R32_FMT_KPARAM , unsigned flip
+#define SDR_R32_FMT_LPARAM bool cu8,
+#define SDR_R32_FMT_LARG cu8,
+#else
+#define SDR_R32_FMT_KPARAM
+#define SDR_R32_FMT_LPARAM
+#define SDR_R32_FMT_LARG
+#endif
+#if SDR_R32_IQ8
+#include "iq8.h"
+#define SDR_R32_IN uint8_t
+#elif SDR_R32_SC16
 #include "sc16.h"
 #define SDR_R32_IN int16_t
 #else
 #define SDR_R32_IN float
 #endif
-#if SDR_R32_HOP && SDR_R32_SC16
+#if SDR_R32_HOP && SDR_R32_IQ8
+#define SDR_R32_KERNEL k_fft_r32_hop_iq8
+#define SDR_R32_LAUNCH launch_fft_r32_hop_iq8
+#elif SDR_R32_IQ8
+#define SDR_R32_KERNEL k_fft_r32_iq8
+#define SDR_R32_LAUNCH launch_fft_r32_iq8
+#elif SDR_R32_HOP && SDR_R32_SC16
 #define SDR_R32_KERNEL k_fft_r32_hop_sc16
 #define SDR_R32_LAUNCH launch_fft_r32_hop_sc16
 #elif SDR_R32_HOP
@@ -288,14 +316,16 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
                                                           int out_stride, unsigned frames_and_shift /* (dense: the frame count alone) */,
                                                           unsigned *__restrict__ steal, const int *__restrict__ tap_bins,
                                                           float *__restrict__ tap_out, int n_tap, int tap_stride,
-                                                          float *__restrict__ tap_wide, int *__restrict__ tap_used)
+                                                          float *__restrict__ tap_wide, int *__restrict__ tap_used SDR_R32_FMT_KPARAM)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     using namespace fft32;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *ex = reinterpret_cast<double *>(smem);
     const unsigned char *tw1_lds = smem + kExchangeBytes;
-#if SDR_R32_SC16
+#if SDR_R32_IQ8
+    const uint8_t *__restrict__ iq = cur ? cur->iq8 : iq_arg;  // graph replay: the batch's input pointer lives in device memory
+#elif SDR_R32_SC16
     const int16_t *__restrict__ iq = cur ? cur->iq_sc16 : iq_arg;  // graph replay: the batch's input pointer lives in device memory
 #else
     const float *__restrict__ iq = cur ? cur->iq : iq_arg;  // graph replay: the batch's input pointer lives in device memory
@@ -305,7 +335,7 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
     // the frame count; both are taken out of it with scalar temporaries where a frame is claimed or fetched (kFrameBits).
     const unsigned fr_sh = frames_and_shift;
     auto n_fr = [fr_sh] { return fr_sh & ((1u << kFrameBits) - 1); };
-    auto frame_at = [fr_sh](unsigned frame) { return ((size_t)frame << (fr_sh >> kFrameBits)) << 1; };  // (in floats / int16 values)
+    auto frame_at = [fr_sh](unsigned frame) { return ((size_t)frame << (fr_sh >> kFrameBits)) << 1; };  // (in floats / int16 values / bytes)
 #else
     const unsigned n_frames_u = frames_and_shift;
     auto n_fr = [n_frames_u] { return n_frames_u; };
@@ -322,7 +352,10 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
 
     // setSamplesFromIQ's reads, one frame ahead: slot m <- sample tid + 512 * brev5(m) (fft_r32.h: pass 0's thread part of
     // the sample number is the thread id), 8 bytes per lane, 512 contiguous bytes per wave instruction
-#if SDR_R32_SC16
+#if SDR_R32_IQ8
+    unsigned pf[R];  // (8-bit: one 16-bit word per sample, 128 contiguous bytes per wave instruction)
+    constexpr unsigned kSampleBytes = 2;
+#elif SDR_R32_SC16
     unsigned pf[R];  // (sc16: one word per sample, 256 contiguous bytes per wave instruction)
     constexpr unsigned kSampleBytes = 4;
 #else
@@ -332,7 +365,14 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
     // touching memory, and the frame's code stays free of branches
     auto fetch = [&](unsigned frame, int t, int m0, int m1) {
         const bool live = frame < n_fr();
-#if SDR_R32_SC16
+#if SDR_R32_IQ8
+        const rsrc_t xrs = make_rsrc(iq_b + frame_at(frame), live ? N * kSampleBytes : 0u);
+        const unsigned voff = (unsigned)thread_sample(t) * kSampleBytes;
+#pragma unroll
+        for (int m = 0; m < R; m++)
+            if (m >= m0 && m < m1)
+                pf[m] = __builtin_amdgcn_raw_buffer_load_b16(xrs, voff, slot_sample(m) * (int)kSampleBytes, SDR_R32_IN_AUX);
+#elif SDR_R32_SC16
         const rsrc_t xrs = make_rsrc(iq_b + frame_at(frame), live ? N * kSampleBytes : 0u);
         const unsigned voff = (unsigned)thread_sample(t) * kSampleBytes;
 #pragma unroll
@@ -433,6 +473,12 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
 #if SDR_R32_PRIO
     asm volatile("s_mov_b32 m0, %0" ::"s"(__builtin_amdgcn_readfirstlane(tid >> 8)) : "m0");  // waves 0-3 / 4-7: a SIMD has one of each
 #endif
+#if SDR_R32_IQ8
+    // the format, for the frame loop: in vector registers (see the file header), opaque so that they stay there
+    unsigned flip_v = flip;
+    float c_v = flip ? 1.0f : 255.0f / 256.0f, inv_v = 1.0f / 128.0f;
+    asm volatile("" : "+v"(flip_v), "+v"(c_v), "+v"(inv_v));
+#endif
     int it = 0;  // frames this workgroup has finished (the soft barriers' targets count in it)
 #pragma nounroll
     while (frame < n_fr()) {
@@ -450,7 +496,12 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
         double xr[R], xi[R];
 #pragma unroll
         for (int m = 0; m < R; m++) {  // dsp/fft.go:59-69 setSamplesFromIQ: widen, exact
-#if SDR_R32_SC16
+#if SDR_R32_IQ8
+            // (iq8::re_of / im_of with the three constants from their registers: u * (1/128) - c, one exact FMA)
+            const unsigned u = pf[m] ^ flip_v;
+            xr[m] = (double)__builtin_fmaf((float)(u & 0xffu), inv_v, -c_v);
+            xi[m] = (double)__builtin_fmaf((float)((u >> 8) & 0xffu), inv_v, -c_v);
+#elif SDR_R32_SC16
             xr[m] = (double)sc16::re_of(pf[m]);  // (sc16: converted first, float32(x) / 32767 rounded once)
             xi[m] = (double)sc16::im_of(pf[m]);
 #else
@@ -657,7 +708,7 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
 
 }  // namespace r32
 
-#if !SDR_R32_SC16 && !SDR_R32_HOP
+#if !SDR_R32_SC16 && !SDR_R32_HOP && !SDR_R32_IQ8
 int r32_twiddle_count() { return fft32::kTwTotal; }
 void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out) { fft32::build_twiddles(wre, wim, out); }
 #endif
@@ -665,7 +716,7 @@ void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out) 
 // Workgroups per band: one per CU, less the reserve_cus CUs the batch plan leaves to the other streams' kernels
 // (host/batch_plan.h fft_reserve_cus; the rule's value capped at a quarter of the device, a forced one taken as it is),
 // at least one, never more than there are frames.
-hipError_t SDR_R32_LAUNCH(const SDR_R32_IN *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+hipError_t SDR_R32_LAUNCH(SDR_R32_FMT_LPARAM const SDR_R32_IN *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
                           size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at)
 {
     constexpr int kMaxDevices = 64;
@@ -705,7 +756,9 @@ hipError_t SDR_R32_LAUNCH(const SDR_R32_IN *iq, const BatchCursor *cur, const ff
     const unsigned frames_and_shift = (unsigned)n_frames | (unsigned)shift << r32::kFrameBits;
 #else
     if (frame_stride != fft32::N)  // overlapped frames: the strided kernel (k_fft_r32_hop.hip)
-#if SDR_R32_SC16
+#if SDR_R32_IQ8
+        return launch_fft_r32_hop_iq8(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, at);
+#elif SDR_R32_SC16
         return launch_fft_r32_hop_sc16(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, at);
 #else
         return launch_fft_r32_hop(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, at);
@@ -716,8 +769,13 @@ hipError_t SDR_R32_LAUNCH(const SDR_R32_IN *iq, const BatchCursor *cur, const ff
     const int reserve = reserve_forced ? reserve_cus : std::min(reserve_cus, cu_count[dev] / kReserveDeviceShare);
     const int cus = std::max(1, cu_count[dev] - std::max(0, reserve));
     const int grid = std::min((cus + n_bands - 1) / n_bands, n_frames);
+#if SDR_R32_IQ8
+    launch_kernel(r32::SDR_R32_KERNEL, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, at, iq, cur, tw, psd, (unsigned)in_stride, out_stride,
+                  frames_and_shift, tap.steal, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used, iq8::format_of(cu8).flip);
+#else
     launch_kernel(r32::SDR_R32_KERNEL, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, at, iq, cur, tw, psd, (unsigned)in_stride, out_stride,
                   frames_and_shift, tap.steal, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used);
+#endif
     return hipGetLastError();
 }
 

@@ -73,10 +73,12 @@ struct BatchCursor {
     int32_t carry_in;     // which of the two carry buffers holds the cumulation carried in (0 / 1)
     int32_t reserved;
     const int16_t *iq_sc16;  // this batch's input frames (sc16 graphs: sdr_graph_capture_sc16)
+    const uint8_t *iq8;      // this batch's input frames (cs8 / cu8 graphs: sdr_graph_capture_iq8)
 };
 
-// What the FFT kernels read: interleaved float32 I,Q or complex int16 (sc16.h)
-enum class InFormat { F32 = 0, SC16 = 1 };
+// What the FFT kernels read: interleaved float32 I,Q, complex int16 (sc16.h) or complex 8-bit, signed or unsigned (iq8.h)
+enum class InFormat { F32 = 0, SC16 = 1, CS8 = 2, CU8 = 3 };
+constexpr bool is_iq8(InFormat f) { return f == InFormat::CS8 || f == InFormat::CU8; }
 
 struct ListenGeom {
     int n, stride, max_listeners, text_cap, edge_cap, bit_words, trace;
@@ -180,7 +182,7 @@ struct FftTap {
     const float *window = nullptr;
 };
 
-// iq: samples of format fmt (float32 pairs or sc16 words); band b's frame f is the N samples from sample b * in_stride +
+// iq: samples of format fmt (float32 pairs, sc16 words or cs8 / cu8 byte pairs); band b's frame f is the N samples from sample b * in_stride +
 // f * frame_stride on (host/overlap.h input_sample_offset; dense frames: frame_stride = N, in_stride = n_frames * N; overlapped
 // frames: frame_stride = hop < N); `fft` picks the kernel (host/batch_plan.h)
 hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
@@ -188,11 +190,18 @@ hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, con
 // k_fft_psd_win.hip: N = 512 - 16384 with tap.window set (launch_fft hands such a launch on; never k_fft_r32)
 hipError_t launch_fft_win(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
                           int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
+// k_fft_psd_iq8.hip: N = 512 - 16384 from 8-bit frames (cu8: unsigned, else cs8), with tap.window or without (launch_fft
+// hands such a launch on)
+hipError_t launch_fft_iq8(int logn, bool cu8, const uint8_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
 // ... and the order its kernels read the table in: out[N] from the caller's w[N] (sample order)
 void window_layout(int logn, const float *w, float *out);
 // k_fft_2p.hip: N = 32768 / 65536 as two phases over a scratch buffer (fft_2p.h), frame group by frame group
 hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
+// k_fft_2p_iq8.hip: the same from 8-bit frames, fmt = CS8 / CU8 (launch_fft_2p hands such a launch on)
+hipError_t launch_fft_2p_iq8(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
+                             int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
 int twiddle_count(int logn);
 void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx *out);
 // k_fft_r32.hip: N = 16384 as 512 threads x 32 points with the next frame prefetched into registers (own twiddle layout);
@@ -209,6 +218,12 @@ hipError_t launch_fft_r32_hop(const float *iq, const BatchCursor *cur, const fft
                               size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
 hipError_t launch_fft_r32_hop_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
                                    size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
+// k_fft_r32_iq8.hip / k_fft_r32_hop_iq8.hip: the same kernels reading 8-bit frames (cu8: unsigned, else cs8); the first hands a
+// launch with frame_stride < N on to the second
+hipError_t launch_fft_r32_iq8(bool cu8, const uint8_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+                              size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
+hipError_t launch_fft_r32_hop_iq8(bool cu8, const uint8_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
+                                  size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
 int r32_twiddle_count();
 void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out);
 // wpb_forced: windows per workgroup (0: the launcher's rule); mfma: the matrix-pipe variance kernel (host/batch_plan.h)
@@ -261,6 +276,7 @@ __host__ __device__ inline int chunks_completed(int count0, int n_frames)
 }
 hipError_t launch_unpack_be16(const uint8_t *raw, float *out, size_t n_values, hipStream_t stream);
 hipError_t launch_unpack_sc16(const int16_t *raw, float *out, size_t n_values, hipStream_t stream);  // little-endian int16 values
+hipError_t launch_unpack_iq8(const uint8_t *raw, float *out, size_t n_values, bool cu8, hipStream_t stream);  // cs8 / cu8 bytes (iq8.h)
 hipError_t launch_find_peaks(float *cum, const float *psd, const void *db_tab, const float *carry0, const float *carry1, int carry_in,
                              const sdr_frame_rec *recs, DevPeak *peaks, int *counts, const BatchCursor *cur, PeakGeom g, int n_frames,
                              int n_chunks, int n_bands, Refine refine, FftTap tap, LaunchAt at);  // tap: .wide / .used / .n / .stride of this batch's FFT (or null)

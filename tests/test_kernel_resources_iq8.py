@@ -1,0 +1,57 @@
+"""The 8-bit k_fft_r32 kernels' register budget, checked at compile time (no GPU), as tests/test_kernel_resources_sc16.py
+checks the sc16 kernel: k_fft_r32.hip compiled again with SDR_R32_IQ8 = 1 (k_fft_r32_iq8.hip, and k_fft_r32_hop_iq8.hip
+with SDR_R32_HOP = 1), device-only for gfx950 with the library's own flags, and the compiler's resource report read.  Each
+kernel must run at two waves per SIMD with nothing in scratch and no spilled vector register; the strided form may keep a
+scalar register in a vector register's lane, as k_fft_r32_hop does.  Each unit holds its 8-bit kernel and no other."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from sdrainer_amd.csrc import build as hip_build
+
+UNITS = {"k_fft_r32_iq8.hip": "k_fft_r32_iq8", "k_fft_r32_hop_iq8.hip": "k_fft_r32_hop_iq8"}
+
+
+@pytest.fixture(scope="module", params=sorted(UNITS))
+def usage(request, tmp_path_factory):
+    unit, kernel = request.param, UNITS[request.param]
+    try:
+        cc = hip_build.hipcc()
+    except RuntimeError as e:
+        pytest.fail(str(e))
+    assert unit in hip_build.SOURCES
+    assert hip_build.EXTRA_FLAGS[unit] == hip_build.EXTRA_FLAGS["k_fft_r32.hip"]
+    out = tmp_path_factory.mktemp("res") / unit.replace(".hip", ".o")
+    cmd = [cc] + hip_build.FLAGS + hip_build.EXTRA_FLAGS[unit] + ["--cuda-device-only", "-c", os.path.join(hip_build.HERE, unit), "-o", str(out),
+                                                               "-Rpass-analysis=kernel-resource-usage"]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-4000:]
+    names = re.findall(r"Function Name: (\S+)", p.stderr)
+    assert len(names) == 1 and kernel + "E" in names[0], names  # (the mangled name: ...k_fft_r32_iq8E<parameters>)
+    m = re.search(r"Function Name: \S*" + kernel + r"\S*(.*?)(?:Function Name:|\Z)", p.stderr, re.S)
+    assert m, "no resource report for " + kernel
+    u = {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", m.group(1))}
+    u["hop"] = "hop" in kernel
+    return u
+
+
+def _int(usage, key):
+    assert key in usage, f"{key!r} missing from the report: {sorted(usage)}"
+    return int(usage[key])
+
+
+def test_no_vector_spills(usage):
+    assert _int(usage, "VGPRs Spill") == 0
+    if not usage["hop"]:
+        assert _int(usage, "SGPRs Spill") == 0
+
+
+def test_no_scratch(usage):
+    assert _int(usage, "ScratchSize [bytes/lane]") == 0
+
+
+def test_vgprs_and_occupancy(usage):
+    assert _int(usage, "VGPRs") <= 256
+    assert _int(usage, "Occupancy [waves/SIMD]") == 2

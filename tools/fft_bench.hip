@@ -50,6 +50,15 @@ hipError_t launch_fft_r32_hop_sc16(const int16_t *, const BatchCursor *, const f
 {
     return hipErrorNotSupported;
 }
+// (nor the 8-bit kernels, k_fft_psd_iq8.hip / k_fft_r32_iq8.hip)
+hipError_t launch_fft_iq8(int, bool, const uint8_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, LaunchAt)
+{
+    return hipErrorNotSupported;
+}
+hipError_t launch_fft_r32_iq8(bool, const uint8_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
+{
+    return hipErrorNotSupported;
+}
 // (nor the two-phase kernels of N = 32768 / 65536, k_fft_2p.hip)
 hipError_t launch_fft_2p(int, FftChoice, InFormat, const void *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap,
                          LaunchAt)
