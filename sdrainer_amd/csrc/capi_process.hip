@@ -204,7 +204,7 @@ struct BatchIssue {
 // uses buffer set RING + capture_k, everything that differs from batch to batch comes from the device-side cursor of that
 // number instead of the launch parameters and grids cover the most chunks a batch of this length can complete.
 // Without PART_SPECTRA (the later listen half) set and first frame are the pending batch's (b->pend).
-BatchIssue prepare_batch(sdr_bank *b, int n_frames, int capture_k, int capture_stage, bool do_spectra, bool do_listen)
+BatchIssue prepare_batch(sdr_bank *b, int n_frames, int capture_k, int capture_stage, bool do_spectra, bool do_listen, sdr::InFormat fmt)
 {
     const sdr_config &c = b->cfg;
     BatchIssue is;
@@ -224,14 +224,14 @@ BatchIssue prepare_batch(sdr_bank *b, int n_frames, int capture_k, int capture_s
         is.max_slots = std::max(is.max_slots, b->n_slots[i]);
     is.count0 = b->cum_count;
     is.P = sdr::plan_batch(b->sw, sdr::BatchGeometry{c.n_bands, c.block_size, c.max_batch_frames, b->max_chunks, b->fft_queue_alone}, n_frames, is.count0,
-                           is.cap, is.max_slots, b->windowed, b->results_on ? b->row_columns : 0, b->results_on && b->reports_on);
+                           is.cap, is.max_slots, b->windowed, b->results_on ? b->row_columns : 0, b->results_on && b->reports_on, fmt, b->hop);
     is.deps = sdr::stage_deps(is.P, b->find_peaks && is.P.n_chunks > 0);
     is.cg = sdr::CumGeom{c.block_size, c.max_batch_frames, n_frames, is.count0, b->max_chunks};
     return is;
 }
 
 // The spectral half: FFT + PSD + tap, noise floor, thresholds.
-int issue_spectra(const BatchIssue &is, const void *iq_dev, size_t in_stride, sdr::InFormat fmt)
+int issue_spectra(const BatchIssue &is, const void *iq_dev, size_t in_stride)
 {
     sdr_bank *b = is.b;
     const sdr_config &c = b->cfg;
@@ -264,17 +264,12 @@ int issue_spectra(const BatchIssue &is, const void *iq_dev, size_t in_stride, sd
     }
     if (is.cap && is.on(sdr::K_FFT) && is.capture_k % RING == 0)  // the replay's cursors, in front of its first FFT
         HIP_TRY(launch_set_cursors(is.cur, CursorPack{}, is.stream(sdr::K_FFT)));
-    sdr::FftTap tap{b->tap_bins.p, S.tap.p, is.max_slots, c.max_listeners};
-    tap.wide = S.tapw.p;
-    tap.used = S.tap_used.p;
-    tap.steal = S.fft_ctr.p;
-    tap.scratch = S.fft_scratch.p;
-    tap.window = b->windowed ? b->window.p : nullptr;
+    const sdr::FftLaunch fl{b->logn, P.fft, iq_dev, is.cur, b->tw.p, S.psd.p, n_frames, B, in_stride, b->hop, stride,
+                            sdr::FftTap{b->tap_bins.p, S.tap.p, is.max_slots, c.max_listeners, S.tapw.p, S.tap_used.p},
+                            S.fft_ctr.p, S.fft_scratch.p, b->windowed ? b->window.p : nullptr};
     // (n_frames > 0, process_device_body: launch_fft and launch_psd_scan launch nothing for an empty batch and would leave
     // the event they are given unrecorded)
-    int rc = is.stage(sdr::K_FFT, BatchIssue::LAUNCH, true, [&](sdr::LaunchAt at) {
-        return sdr::launch_fft(b->logn, P.fft, fmt, iq_dev, is.cur, b->tw.p, S.psd.p, n_frames, B, in_stride, b->hop, stride, tap, at);
-    });
+    int rc = is.stage(sdr::K_FFT, BatchIssue::LAUNCH, true, [&](sdr::LaunchAt at) { return sdr::launch_fft(fl, at); });
     if (rc)
         return rc;
 
@@ -505,9 +500,9 @@ int process_device_body(sdr_bank *b, const void *iq_dev, int n_frames, size_t in
     if (!cap)
         if (const int rc = flush_late_attached(b))
             return rc;
-    const BatchIssue is = prepare_batch(b, n_frames, capture_k, capture_stage, do_spectra, do_listen);
+    const BatchIssue is = prepare_batch(b, n_frames, capture_k, capture_stage, do_spectra, do_listen, fmt);
     int rc;
-    if (do_spectra && (rc = issue_spectra(is, iq_dev, in_stride, fmt)))
+    if (do_spectra && (rc = issue_spectra(is, iq_dev, in_stride)))
         return rc;
     if (do_listen && (rc = issue_listen(is)))
         return rc;

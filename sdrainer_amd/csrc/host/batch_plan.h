@@ -119,15 +119,23 @@ inline bool var_mfma_at(const Switches &sw, int n, int n_frames)
 // may a bank of block size n launch the matrix-pipe variance kernel (then sdr_create probes it)?
 inline bool may_use_matrix_pipe(const Switches &sw, int n) { return !noise_scan_at(sw, n) && (sw.var_mfma == 1 || (sw.var_mfma < 0 && n <= 16384)); }
 
+// What the FFT kernels read: interleaved float32 I,Q, complex int16 (sc16.h) or complex 8-bit, signed or unsigned (iq8.h)
+enum class InFormat { F32 = 0, SC16 = 1, CS8 = 2, CU8 = 3 };
+constexpr bool is_iq8(InFormat f) { return f == InFormat::CS8 || f == InFormat::CU8; }
+
 // Which FFT kernel runs a batch, and how.
 struct FftChoice {
     bool r32 = false;       // N = 16384 on k_fft_r32 instead of the 16-point k_fft_psd<14>
-    int fpw = 0;            // the 16-point kernels: frames per workgroup asked for (0: the kernel's default, launch_fft_t)
+    int fpw = 0;            // the 16-point kernels: frames per workgroup asked for (0: kDefaultFpw; frames_per_wg is what runs)
     bool wide_tap = false;  // the kernel leaves the wide tap (psd at bin - 1, bin, bin + 1 of every listener: k_cum_refine reads it)
     bool two_phase = false;  // N = 32768 / 65536: the two kernels of k_fft_2p.hip, frame group by frame group
     int group_frames = 0;    // ... frames per group (the batch set's scratch holds one group's intermediate of every band)
     int reserve_cus = 0;     // k_fft_r32: CUs its grid leaves to the other streams' kernels (fft_reserve_cus; 0 for every other kernel)
     bool reserve_forced = false;  // ... as SDR_FFT_RESERVE gave it (the launcher caps the rule's value at kReserveDeviceShare of the device, not a forced one)
+    InFormat fmt = InFormat::F32;  // what the kernel reads
+    bool windowed = false;         // the windowed form of the kernel (the bank has a window: sdr_set_window)
+    bool strided = false;          // frames start every hop < N samples (host/overlap.h); k_fft_r32 has a kernel of its own for that
+    int frames_per_wg = 0;  // the 16-point kernels: frames per workgroup (fft_frames_per_wg; 1 for sc16 and 8-bit input); 0 for k_fft_r32 and k_fft_2p
 };
 
 // N = 32768 and 65536 (k_fft_2p.hip): frames per group of the two phases.  A group's float64 intermediate is 16 bytes per
@@ -146,6 +154,19 @@ inline int fft2p_group_frames(const Switches &sw, int n, int n_bands, int max_fr
     return (int)(f < 1 ? 1 : (f > max_frames ? max_frames : f));
 }
 
+// The 16-point kernels' float32 form (k_fft_psd, k_fft_psd_win) can give a workgroup several consecutive frames.
+// frames per workgroup when the plan asks for none (FftChoice::fpw, SDR_FFT_FPW)
+constexpr int kDefaultFpw = 1;  // in the pipeline short-lived workgroups win: 0.250 (1) / 0.253 (2) / 0.291 (4) / 0.294 ms (8) per step, standalone the other way round (0.174 / 0.166 / 0.165 / 0.164 ms)
+// a workgroup's frames are consecutive; never fewer workgroups than CUs can take (a short batch keeps one
+// frame per workgroup)
+inline int fft_frames_per_wg(int fpw_asked, int n_frames, int n_bands)
+{
+    int fpw = fpw_asked > 0 ? fpw_asked : kDefaultFpw;
+    while (fpw > 1 && (long)((n_frames + fpw - 1) / fpw) * n_bands < 256)
+        fpw /= 2;
+    return fpw;
+}
+
 // N = 16384 has two kernels: k_fft_psd.hip's 16-point one and k_fft_r32.hip (512 threads x 32 points, the next frame
 // prefetched into registers), whose workgroups - one per CU - claim frames from a counter.  By default the 32-point kernel
 // runs from 1024 frames per launch on (measured by batch size) and while the listener slots fit its tap (one per thread).
@@ -154,14 +175,83 @@ inline int fft2p_group_frames(const Switches &sw, int n, int n_bands, int max_fr
 // windowed: the bank has a window (sdr_set_window).  k_fft_r32 has no windowed form - it has no register left for a
 // thread's 32 window values beside its prefetched frame - so a windowed batch never takes it, SDR_FFT_R32=1 or not: N =
 // 16384 runs the 16-point kernel at every batch length, and k_cum_refine reads psd columns (no wide tap).
-inline FftChoice fft_choice(const Switches &sw, int n, int n_frames, int n_bands, int tap_n, bool windowed = false)
+// fmt, hop: the input format and the samples from one frame's start to the next (0 or n: dense frames).
+// What the launchers once refused at run time cannot be planned: k_fft_r32 with a window or at n != 16384, the two-phase
+// kernels at n <= 16384, a windowed 8-bit batch on the float32 / sc16 unit (tests/host/test_fft_kernel_choice.cpp).
+inline FftChoice fft_choice(const Switches &sw, int n, int n_frames, int n_bands, int tap_n, bool windowed = false, InFormat fmt = InFormat::F32,
+                            int hop = 0)
 {
     FftChoice c;
     c.r32 = !windowed && n == 16384 && tap_n <= kR32MaxTap && (sw.fft_r32 == 1 || (sw.fft_r32 < 0 && (long)n_frames * n_bands >= 1024));
     c.fpw = sw.fft_fpw;
     c.wide_tap = c.r32 && tap_n > 0;  // (never at N > 16384: k_cum_refine reads psd columns there)
     c.two_phase = n > 16384;
+    c.fmt = fmt;
+    c.windowed = windowed;
+    c.strided = hop != 0 && hop != n;
+    // sc16 and 8-bit input: one frame per workgroup, always (the multi-frame workgroup is float32-only)
+    c.frames_per_wg = c.r32 || c.two_phase ? 0 : fmt != InFormat::F32 ? 1 : fft_frames_per_wg(sw.fft_fpw, n_frames, n_bands);
     return c;
+}
+
+// One id per kernel symbol a batch can launch first (the two-phase ids name phase A; k_fft2p_b follows every one of them).
+enum class FftKernel {
+    // k_fft_psd.hip and its recompilations k_fft_psd_win.hip, k_fft_psd_iq8.hip (PSD_IQ8*: cs8 and cu8, a launch argument)
+    PSD, PSD_MULTI, PSD_SC16, PSD_IQ8, PSD_WIN, PSD_WIN_MULTI, PSD_SC16_WIN, PSD_IQ8_WIN,
+    // k_fft_r32.hip and its five recompilations (R32*_IQ8: cs8 and cu8, a launch argument)
+    R32, R32_SC16, R32_IQ8, R32_HOP, R32_HOP_SC16, R32_HOP_IQ8,
+    // k_fft_2p.hip (F32, SC16) and k_fft_2p_iq8.hip (CS8, CU8): phase A's instances
+    A2P_F32, A2P_SC16, A2P_CS8, A2P_CU8, A2P_WIN_F32, A2P_WIN_SC16, A2P_WIN_CS8, A2P_WIN_CU8,
+    COUNT
+};
+
+inline FftKernel fft_kernel(const FftChoice &c)
+{
+    using K = FftKernel;
+    const bool iq8 = is_iq8(c.fmt), sc16 = c.fmt == InFormat::SC16;
+    if (c.two_phase) {
+        switch (c.fmt) {
+        case InFormat::F32: return c.windowed ? K::A2P_WIN_F32 : K::A2P_F32;
+        case InFormat::SC16: return c.windowed ? K::A2P_WIN_SC16 : K::A2P_SC16;
+        case InFormat::CS8: return c.windowed ? K::A2P_WIN_CS8 : K::A2P_CS8;
+        default: return c.windowed ? K::A2P_WIN_CU8 : K::A2P_CU8;
+        }
+    }
+    if (c.r32) {
+        if (c.strided)
+            return iq8 ? K::R32_HOP_IQ8 : sc16 ? K::R32_HOP_SC16 : K::R32_HOP;
+        return iq8 ? K::R32_IQ8 : sc16 ? K::R32_SC16 : K::R32;
+    }
+    if (iq8)
+        return c.windowed ? K::PSD_IQ8_WIN : K::PSD_IQ8;
+    if (sc16)
+        return c.windowed ? K::PSD_SC16_WIN : K::PSD_SC16;
+    if (c.frames_per_wg > 1)
+        return c.windowed ? K::PSD_WIN_MULTI : K::PSD_MULTI;
+    return c.windowed ? K::PSD_WIN : K::PSD;
+}
+
+// the kernel symbol's base name, as the compiler's resource listings spell it (profiles/*_kernel_resources.txt)
+inline const char *fft_kernel_name(FftKernel k)
+{
+    using K = FftKernel;
+    switch (k) {
+    case K::PSD: case K::PSD_MULTI: return "k_fft_psd";
+    case K::PSD_SC16: return "k_fft_psd_sc16";
+    case K::PSD_IQ8: case K::PSD_IQ8_WIN: return "k_fft_psd_iq8";
+    case K::PSD_WIN: case K::PSD_WIN_MULTI: return "k_fft_psd_win";
+    case K::PSD_SC16_WIN: return "k_fft_psd_sc16_win";
+    case K::R32: return "k_fft_r32";
+    case K::R32_SC16: return "k_fft_r32_sc16";
+    case K::R32_IQ8: return "k_fft_r32_iq8";
+    case K::R32_HOP: return "k_fft_r32_hop";
+    case K::R32_HOP_SC16: return "k_fft_r32_hop_sc16";
+    case K::R32_HOP_IQ8: return "k_fft_r32_hop_iq8";
+    case K::A2P_F32: case K::A2P_SC16: case K::A2P_CS8: case K::A2P_CU8: return "k_fft2p_a";
+    case K::A2P_WIN_F32: case K::A2P_WIN_SC16: case K::A2P_WIN_CS8: case K::A2P_WIN_CU8: return "k_fft2p_win_a";
+    case K::COUNT: break;
+    }
+    return "";
 }
 
 // k_fft_r32's grid is one persistent workgroup per CU: 254 VGPRs at two waves per SIMD and about 160 KB of LDS, so nothing
@@ -246,9 +336,9 @@ struct BatchPlan {
 // One batch of n_frames frames that starts at cumulationCount count0, max_slots listener slots in use.  capturing: the
 // batch is being recorded into a graph (sdr_graph_capture), replayed later at whatever count0 and without stream changes.
 // windowed: the bank has a window (fft_choice).  row_columns: sdr_enable_rows' setting (0: rows off).  reports:
-// sdr_enable_reports' setting.
+// sdr_enable_reports' setting.  fmt, hop: the batch's input format and frame stride (fft_choice).
 inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_frames, int count0, bool capturing, int max_slots,
-                            bool windowed = false, int row_columns = 0, bool reports = false)
+                            bool windowed = false, int row_columns = 0, bool reports = false, InFormat fmt = InFormat::F32, int hop = 0)
 {
     BatchPlan p;
     // Which of the bank's four streams each kernel runs on.  The step is as long as the longest stream, and kernels that
@@ -269,7 +359,7 @@ inline BatchPlan plan_batch(const Switches &sw, const BatchGeometry &g, int n_fr
         if (sw.diag_plan[k] >= 0)
             p.stream[k] = sw.diag_plan[k];
 
-    p.fft = fft_choice(sw, g.n, n_frames, g.n_bands, max_slots, windowed);
+    p.fft = fft_choice(sw, g.n, n_frames, g.n_bands, max_slots, windowed, fmt, hop);
     p.fft.group_frames = fft2p_group_frames(sw, g.n, g.n_bands, g.max_batch_frames);
 
     // noise floor: the one-pass scan unless the chains are asked for or the windows are too wide for it (noise_scan_at)

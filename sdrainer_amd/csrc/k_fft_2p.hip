@@ -111,109 +111,106 @@ __global__ __launch_bounds__(fft2p::T) void k_fft2p_b(const fft64::cplx *__restr
 }
 
 // phase B of frames [f0, f0 + g) of a group, behind their phase A on the same stream
-hipError_t launch_fft2p_b(int logn, const fft64::cplx *tw, float *psd, int n_bands, int out_stride, int f0, int g, int group, FftTap tap, LaunchAt at)
+hipError_t launch_fft2p_b(const FftLaunch &l, int f0, int g, LaunchAt at)
 {
-    if (logn == 15)
-        launch_kernel((k_fft2p_b<15>), dim3(g * fft2p::Phases<15>::WG_B, n_bands), dim3(fft2p::T), 0, at, static_cast<const fft64::cplx *>(tap.scratch), tw,
-                      psd, out_stride, f0, group, tap.bins, tap.out, tap.n, tap.stride);
-    else if (logn == 16)
-        launch_kernel((k_fft2p_b<16>), dim3(g * fft2p::Phases<16>::WG_B, n_bands), dim3(fft2p::T), 0, at, static_cast<const fft64::cplx *>(tap.scratch), tw,
-                      psd, out_stride, f0, group, tap.bins, tap.out, tap.n, tap.stride);
+    const int group = l.fft.group_frames;
+    if (l.logn == 15)
+        launch_kernel((k_fft2p_b<15>), dim3(g * fft2p::Phases<15>::WG_B, l.n_bands), dim3(fft2p::T), 0, at, static_cast<const fft64::cplx *>(l.scratch), l.tw,
+                      l.psd, l.out_stride, f0, group, l.tap.bins, l.tap.out, l.tap.n, l.tap.stride);
+    else if (l.logn == 16)
+        launch_kernel((k_fft2p_b<16>), dim3(g * fft2p::Phases<16>::WG_B, l.n_bands), dim3(fft2p::T), 0, at, static_cast<const fft64::cplx *>(l.scratch), l.tw,
+                      l.psd, l.out_stride, f0, group, l.tap.bins, l.tap.out, l.tap.n, l.tap.stride);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();
 }
+#endif  // !SDR_FFT2P_IQ8
 
-template <int LOGN>
-static hipError_t launch_fft2p_t(FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                                 int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
+// A batch, frame group by frame group: launch_a(f0, g) launches phase A of frames [f0, f0 + g) on at.stream, phase B
+// (k_fft_2p.hip's, for both units) follows it.  at.done rides on the last frame group's phase B, the last launch, and on
+// nothing else.
+template <class A>
+static hipError_t launch_fft2p_groups(const FftLaunch &l, LaunchAt at, A launch_a)
 {
-    using PH = fft2p::Phases<LOGN>;
-    const hipStream_t stream = at.stream;
-    if (n_frames <= 0 || n_bands <= 0)
-        return hipSuccess;
-    if (!tap.scratch || fft.group_frames <= 0)
+    if (!l.fft.two_phase || l.fft.windowed != (l.window != nullptr))
         return hipErrorInvalidValue;
-    const int group = fft.group_frames;
-    // (at.done rides on the last frame group's phase B, the last launch)
-    for (int f0 = 0; f0 < n_frames; f0 += group) {
-        const int g = n_frames - f0 < group ? n_frames - f0 : group;
-        if (tap.window && fmt == InFormat::SC16)
-            hipLaunchKernelGGL((k_fft2p_win_a<LOGN, InFormat::SC16>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
-                               tap.scratch, in_stride, frame_stride, f0, group, tap.window);
-        else if (tap.window)
-            hipLaunchKernelGGL((k_fft2p_win_a<LOGN, InFormat::F32>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
-                               tap.scratch, in_stride, frame_stride, f0, group, tap.window);
-        else if (fmt == InFormat::SC16)
-            hipLaunchKernelGGL((k_fft2p_a<LOGN, InFormat::SC16>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
-                               tap.scratch, in_stride, frame_stride, f0, group);
-        else
-            hipLaunchKernelGGL((k_fft2p_a<LOGN, InFormat::F32>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw,
-                               tap.scratch, in_stride, frame_stride, f0, group);
-        const bool last = f0 + group >= n_frames;
-        launch_kernel((k_fft2p_b<LOGN>), dim3(g * PH::WG_B, n_bands), dim3(fft2p::T), 0, last ? at : LaunchAt(stream),
-                      static_cast<const fft64::cplx *>(tap.scratch), tw, psd, out_stride, f0, group, tap.bins, tap.out, tap.n, tap.stride);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                         int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
-{
-    if (is_iq8(fmt))  // k_fft_2p_iq8.hip
-        return launch_fft_2p_iq8(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    switch (logn) {
-    case 15: return launch_fft2p_t<15>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 16: return launch_fft2p_t<16>(fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-#else  // SDR_FFT2P_IQ8
-hipError_t launch_fft2p_b(int logn, const fft64::cplx *tw, float *psd, int n_bands, int out_stride, int f0, int g, int group, FftTap tap, LaunchAt at);
-
-template <int LOGN, InFormat FMT>
-static hipError_t launch_fft2p_iq8_t(FftChoice fft, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                                     size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
-{
-    using PH = fft2p::Phases<LOGN>;
-    const hipStream_t stream = at.stream;
-    if (n_frames <= 0 || n_bands <= 0)
+    if (l.n_frames <= 0 || l.n_bands <= 0)
         return hipSuccess;
-    if (!tap.scratch || fft.group_frames <= 0)
+    if (!l.scratch || l.fft.group_frames <= 0)
         return hipErrorInvalidValue;
-    const int group = fft.group_frames;
-    // (at.done rides on the last frame group's phase B, the last launch)
-    for (int f0 = 0; f0 < n_frames; f0 += group) {
-        const int g = n_frames - f0 < group ? n_frames - f0 : group;
-        if (tap.window)
-            hipLaunchKernelGGL((k_fft2p_win_a<LOGN, FMT>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw, tap.scratch, in_stride,
-                               frame_stride, f0, group, tap.window);
-        else
-            hipLaunchKernelGGL((k_fft2p_a<LOGN, FMT>), dim3(g * PH::WG_A, n_bands), dim3(fft2p::T), 0, stream, iq, cur, tw, tap.scratch, in_stride,
-                               frame_stride, f0, group);
+    const int group = l.fft.group_frames;
+    for (int f0 = 0; f0 < l.n_frames; f0 += group) {
+        const int g = l.n_frames - f0 < group ? l.n_frames - f0 : group;
+        launch_a(f0, g);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess)
-            e = launch_fft2p_b(LOGN, tw, psd, n_bands, out_stride, f0, g, group, tap, f0 + group >= n_frames ? at : LaunchAt(stream));
+            e = launch_fft2p_b(l, f0, g, f0 + group >= l.n_frames ? at : LaunchAt(at.stream));
         if (e != hipSuccess)
             return e;
     }
     return hipSuccess;
 }
 
-hipError_t launch_fft_2p_iq8(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                             int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
+#if !SDR_FFT2P_IQ8
+template <int LOGN>
+static hipError_t launch_fft2p_t(const FftLaunch &l, LaunchAt at)
 {
-    const bool cu8 = fmt == InFormat::CU8;
-    if (!is_iq8(fmt))
+    using PH = fft2p::Phases<LOGN>;
+    const int group = l.fft.group_frames;
+    const bool sc16 = l.fft.fmt == InFormat::SC16;
+    return launch_fft2p_groups(l, at, [&](int f0, int g) {
+        if (l.window && sc16)
+            hipLaunchKernelGGL((k_fft2p_win_a<LOGN, InFormat::SC16>), dim3(g * PH::WG_A, l.n_bands), dim3(fft2p::T), 0, at.stream, l.iq, l.cur, l.tw,
+                               l.scratch, l.in_stride, l.frame_stride, f0, group, l.window);
+        else if (l.window)
+            hipLaunchKernelGGL((k_fft2p_win_a<LOGN, InFormat::F32>), dim3(g * PH::WG_A, l.n_bands), dim3(fft2p::T), 0, at.stream, l.iq, l.cur, l.tw,
+                               l.scratch, l.in_stride, l.frame_stride, f0, group, l.window);
+        else if (sc16)
+            hipLaunchKernelGGL((k_fft2p_a<LOGN, InFormat::SC16>), dim3(g * PH::WG_A, l.n_bands), dim3(fft2p::T), 0, at.stream, l.iq, l.cur, l.tw,
+                               l.scratch, l.in_stride, l.frame_stride, f0, group);
+        else
+            hipLaunchKernelGGL((k_fft2p_a<LOGN, InFormat::F32>), dim3(g * PH::WG_A, l.n_bands), dim3(fft2p::T), 0, at.stream, l.iq, l.cur, l.tw,
+                               l.scratch, l.in_stride, l.frame_stride, f0, group);
+    });
+}
+
+// float32 and sc16 frames
+hipError_t launch_fft_2p(const FftLaunch &l, LaunchAt at)
+{
+    if (l.fft.fmt != InFormat::F32 && l.fft.fmt != InFormat::SC16)
+        return hipErrorInvalidValue;  // (k_fft_2p_iq8.hip's)
+    switch (l.logn) {
+    case 15: return launch_fft2p_t<15>(l, at);
+    case 16: return launch_fft2p_t<16>(l, at);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+#else  // SDR_FFT2P_IQ8
+template <int LOGN, InFormat FMT>
+static hipError_t launch_fft2p_t(const FftLaunch &l, LaunchAt at)
+{
+    using PH = fft2p::Phases<LOGN>;
+    const int group = l.fft.group_frames;
+    return launch_fft2p_groups(l, at, [&](int f0, int g) {
+        if (l.window)
+            hipLaunchKernelGGL((k_fft2p_win_a<LOGN, FMT>), dim3(g * PH::WG_A, l.n_bands), dim3(fft2p::T), 0, at.stream, l.iq, l.cur, l.tw, l.scratch,
+                               l.in_stride, l.frame_stride, f0, group, l.window);
+        else
+            hipLaunchKernelGGL((k_fft2p_a<LOGN, FMT>), dim3(g * PH::WG_A, l.n_bands), dim3(fft2p::T), 0, at.stream, l.iq, l.cur, l.tw, l.scratch, l.in_stride,
+                               l.frame_stride, f0, group);
+    });
+}
+
+// cs8 and cu8 frames
+hipError_t launch_fft_2p_iq8(const FftLaunch &l, LaunchAt at)
+{
+    const bool cu8 = l.fft.fmt == InFormat::CU8;
+    if (!is_iq8(l.fft.fmt))
         return hipErrorInvalidValue;
-    switch (logn) {
-    case 15:
-        return cu8 ? launch_fft2p_iq8_t<15, InFormat::CU8>(fft, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at)
-                   : launch_fft2p_iq8_t<15, InFormat::CS8>(fft, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 16:
-        return cu8 ? launch_fft2p_iq8_t<16, InFormat::CU8>(fft, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at)
-                   : launch_fft2p_iq8_t<16, InFormat::CS8>(fft, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
+    switch (l.logn) {
+    case 15: return cu8 ? launch_fft2p_t<15, InFormat::CU8>(l, at) : launch_fft2p_t<15, InFormat::CS8>(l, at);
+    case 16: return cu8 ? launch_fft2p_t<16, InFormat::CU8>(l, at) : launch_fft2p_t<16, InFormat::CS8>(l, at);
     default: return hipErrorInvalidValue;
     }
 }

@@ -21,14 +21,15 @@
 // A window on the frames.  k_fft_psd_win.hip compiles this file again with SDR_FFT_WIN = 1: the kernels k_fft_psd_win and
 // k_fft_psd_sc16_win take the bank's window table (N float32 in device memory, in the order load_window reads it) and
 // multiply sample i of every frame by its value - one correctly rounded float32 multiplication per component, where
-// the plain kernels widen the sample to float64 - and launch_fft_win launches them.  Everything behind the
+// the plain kernels widen the sample to float64 - and launch_fft_psd_win launches them.  Everything behind the
 // multiplication is the plain kernels'.  A translation unit of its own keeps the plain kernels' code exactly what it was.
 #if !defined(SDR_FFT_WIN)
 #define SDR_FFT_WIN 0
 #endif
 // 8-bit input (iq8.h).  k_fft_psd_iq8.hip compiles this file a third time with SDR_FFT_IQ8 = 1 (and SDR_FFT_WIN = 1 for
-// load_window): that unit holds k_fft_psd_iq8<LOGN, WIN>, plain and windowed, and launch_fft_iq8 - and none of the kernels
-// and launchers of the other two units, whose code stays exactly what it was.
+// load_window): that unit holds k_fft_psd_iq8<LOGN, WIN>, plain and windowed, and launch_fft_psd_iq8 - and none of the
+// kernels of the other two units, whose code stays exactly what it was.
+// Each unit exports one launcher, SDR_FFT_PSD_LAUNCH, for the kernels it holds (sdr_device.h).
 #if !defined(SDR_FFT_IQ8)
 #define SDR_FFT_IQ8 0
 #endif
@@ -37,11 +38,26 @@
 #define SDR_K_FFT_PSD_SC16 k_fft_psd_sc16_win
 #define SDR_WIN_PARAM , const float *__restrict__ win
 #define SDR_WIN_ARG , win
+#define SDR_WIN_LAUNCH_ARG , l.window
+#define SDR_ID_PSD FftKernel::PSD_WIN
+#define SDR_ID_PSD_MULTI FftKernel::PSD_WIN_MULTI
+#define SDR_ID_PSD_SC16 FftKernel::PSD_SC16_WIN
 #else
 #define SDR_K_FFT_PSD k_fft_psd
 #define SDR_K_FFT_PSD_SC16 k_fft_psd_sc16
 #define SDR_WIN_PARAM
 #define SDR_WIN_ARG
+#define SDR_WIN_LAUNCH_ARG
+#define SDR_ID_PSD FftKernel::PSD
+#define SDR_ID_PSD_MULTI FftKernel::PSD_MULTI
+#define SDR_ID_PSD_SC16 FftKernel::PSD_SC16
+#endif
+#if SDR_FFT_IQ8
+#define SDR_FFT_PSD_LAUNCH launch_fft_psd_iq8
+#elif SDR_FFT_WIN
+#define SDR_FFT_PSD_LAUNCH launch_fft_psd_win
+#else
+#define SDR_FFT_PSD_LAUNCH launch_fft_psd
 #endif
 
 #if !defined(SDR_FFT_PSD_AUX)
@@ -759,62 +775,45 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
 }
 
 template <int LOGN>
-static hipError_t launch_fft_iq8_t(bool cu8, const uint8_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                                   size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
+static hipError_t launch_fft_t(const FftLaunch &l, LaunchAt at)
 {
     using PL = fft64::Plan<LOGN>;
+    const FftTap &tap = l.tap;
     static LdsLimitOnce lds_once;
     const hipError_t attr_err = raise_lds_limit_once(
         lds_once, {reinterpret_cast<const void *>(&k_fft_psd_iq8<LOGN, false>), reinterpret_cast<const void *>(&k_fft_psd_iq8<LOGN, true>)},
         fft64::kLdsBytes<LOGN> + kMaxLdsTap * 4);
     if (attr_err != hipSuccess)
         return attr_err;
-    if (n_frames <= 0 || n_bands <= 0)
+    const FftKernel k = fft_kernel(l.fft);
+    if ((k != FftKernel::PSD_IQ8 && k != FftKernel::PSD_IQ8_WIN) || (k == FftKernel::PSD_IQ8_WIN) != (l.window != nullptr))
+        return hipErrorInvalidValue;
+    if (l.n_frames <= 0 || l.n_bands <= 0)
         return hipSuccess;
     const unsigned tap_lds = tap.n > 0 && tap.n <= kMaxLdsTap ? ((tap.n * 4 + 255) & ~255) : 0;
-    const iq8::Format f = iq8::format_of(cu8);
+    const iq8::Format f = iq8::format_of(l.fft.fmt == InFormat::CU8);
+    const uint8_t *iq = static_cast<const uint8_t *>(l.iq);
     // one frame per workgroup, always (FftChoice::fpw is the float32 kernel's)
-    if (tap.window)
-        launch_kernel((k_fft_psd_iq8<LOGN, true>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at, iq, cur, tw, psd, in_stride,
-                      frame_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride, f.flip, f.c, tap.window);
+    if (l.window)
+        launch_kernel((k_fft_psd_iq8<LOGN, true>), dim3(l.n_frames, l.n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at, iq, l.cur, l.tw, l.psd,
+                      l.in_stride, l.frame_stride, l.out_stride, tap.bins, tap.out, tap.n, tap.stride, f.flip, f.c, l.window);
     else
-        launch_kernel((k_fft_psd_iq8<LOGN, false>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at, iq, cur, tw, psd, in_stride,
-                      frame_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride, f.flip, f.c, static_cast<const float *>(nullptr));
+        launch_kernel((k_fft_psd_iq8<LOGN, false>), dim3(l.n_frames, l.n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at, iq, l.cur, l.tw, l.psd,
+                      l.in_stride, l.frame_stride, l.out_stride, tap.bins, tap.out, tap.n, tap.stride, f.flip, f.c, static_cast<const float *>(nullptr));
     return hipGetLastError();
-}
-
-// N = 512 - 16384 from cs8 / cu8 frames, with tap.window (in window_layout's order) or without (launch_fft hands such a
-// launch on)
-hipError_t launch_fft_iq8(int logn, bool cu8, const uint8_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
-{
-    switch (logn) {
-    case 9: return launch_fft_iq8_t<9>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 10: return launch_fft_iq8_t<10>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 11: return launch_fft_iq8_t<11>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 12: return launch_fft_iq8_t<12>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 13: return launch_fft_iq8_t<13>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 14: return launch_fft_iq8_t<14>(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    default: return hipErrorInvalidValue;
-    }
 }
 #endif  // SDR_FFT_IQ8
 
 #if !SDR_FFT_IQ8
-// frames per workgroup when the plan asks for none (FftChoice::fpw, SDR_FFT_FPW)
-// (LDS behind the exchange area: the one-frame workgroup's copy of its listeners' bins)
-constexpr int kDefaultFpw = 1;  // in the pipeline short-lived workgroups win: 0.250 (1) / 0.253 (2) / 0.291 (4) / 0.294 ms (8) per step, standalone the other way round (0.174 / 0.166 / 0.165 / 0.164 ms)
 static_assert(fft32::T == kR32MaxTap, "host/batch_plan.h: k_fft_r32 serves one listener slot per thread");
 
+// float32 and sc16 frames; with SDR_FFT_WIN the windowed kernels and l.window, in window_layout's order
 template <int LOGN>
-static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                               int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
+static hipError_t launch_fft_t(const FftLaunch &l, LaunchAt at)
 {
     using PL = fft64::Plan<LOGN>;
-    const float *iq = static_cast<const float *>(iq_in);
-#if SDR_FFT_WIN
-    const float *win = tap.window;
-#endif
+    const FftTap &tap = l.tap;
+    const float *iq = static_cast<const float *>(l.iq);
     static LdsLimitOnce lds_once;
     const hipError_t attr_err = raise_lds_limit_once(lds_once,
                                                      {reinterpret_cast<const void *>(&SDR_K_FFT_PSD<LOGN, false>), reinterpret_cast<const void *>(&SDR_K_FFT_PSD<LOGN, true>),
@@ -822,31 +821,42 @@ static hipError_t launch_fft_t(int fpw_asked, InFormat fmt, const void *iq_in, c
                                                      fft64::kLdsBytes<LOGN> + kMaxLdsTap * 4);
     if (attr_err != hipSuccess)
         return attr_err;
-    if (n_frames <= 0 || n_bands <= 0)
+    const FftKernel k = fft_kernel(l.fft);
+    if ((k != SDR_ID_PSD && k != SDR_ID_PSD_MULTI && k != SDR_ID_PSD_SC16) || (SDR_FFT_WIN != 0) != (l.window != nullptr))
+        return hipErrorInvalidValue;
+    if (l.n_frames <= 0 || l.n_bands <= 0)
         return hipSuccess;
     const unsigned tap_lds = tap.n > 0 && tap.n <= kMaxLdsTap ? ((tap.n * 4 + 255) & ~255) : 0;
-    if (fmt == InFormat::SC16) {
-        // one frame per workgroup, always (FftChoice::fpw is the float32 kernel's)
-        launch_kernel((SDR_K_FFT_PSD_SC16<LOGN>), dim3(n_frames, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at,
-                      static_cast<const int16_t *>(iq_in), cur, tw, psd, in_stride, frame_stride, out_stride, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_ARG);
-        return hipGetLastError();
-    }
-    // a workgroup's frames are consecutive; never fewer workgroups than CUs can take (a short batch keeps one
-    // frame per workgroup)
-    int fpw = fpw_asked > 0 ? fpw_asked : kDefaultFpw;
-    while (fpw > 1 && (long)((n_frames + fpw - 1) / fpw) * n_bands < 256)
-        fpw /= 2;
-    if (fpw > 1)
-        launch_kernel((SDR_K_FFT_PSD<LOGN, true>), dim3((n_frames + fpw - 1) / fpw, n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN>, at,
-                           iq, cur, tw, psd, in_stride, frame_stride, out_stride, n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_ARG);
+    const int fpw = l.fft.frames_per_wg;  // (host/batch_plan.h fft_frames_per_wg; a workgroup's frames are consecutive)
+    if (k == SDR_ID_PSD_SC16)
+        launch_kernel((SDR_K_FFT_PSD_SC16<LOGN>), dim3(l.n_frames, l.n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at,
+                      static_cast<const int16_t *>(l.iq), l.cur, l.tw, l.psd, l.in_stride, l.frame_stride, l.out_stride, tap.bins, tap.out, tap.n,
+                      tap.stride SDR_WIN_LAUNCH_ARG);
+    else if (k == SDR_ID_PSD_MULTI)
+        launch_kernel((SDR_K_FFT_PSD<LOGN, true>), dim3((l.n_frames + fpw - 1) / fpw, l.n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN>, at, iq, l.cur, l.tw,
+                      l.psd, l.in_stride, l.frame_stride, l.out_stride, l.n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_LAUNCH_ARG);
     else
-        launch_kernel((SDR_K_FFT_PSD<LOGN, false>), dim3(n_frames, n_bands), dim3(PL::T),
-                           fft64::kLdsBytes<LOGN> + tap_lds, at, iq, cur, tw, psd, in_stride,
-                           frame_stride, out_stride, n_frames, 1, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_ARG);
+        launch_kernel((SDR_K_FFT_PSD<LOGN, false>), dim3(l.n_frames, l.n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at, iq, l.cur, l.tw, l.psd,
+                      l.in_stride, l.frame_stride, l.out_stride, l.n_frames, 1, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_LAUNCH_ARG);
     return hipGetLastError();
 }
+#endif  // !SDR_FFT_IQ8
 
-#if SDR_FFT_WIN
+// N = 512 - 16384: this unit's kernels of fft_kernel(l.fft), any other id refused
+hipError_t SDR_FFT_PSD_LAUNCH(const FftLaunch &l, LaunchAt at)
+{
+    switch (l.logn) {
+    case 9: return launch_fft_t<9>(l, at);
+    case 10: return launch_fft_t<10>(l, at);
+    case 11: return launch_fft_t<11>(l, at);
+    case 12: return launch_fft_t<12>(l, at);
+    case 13: return launch_fft_t<13>(l, at);
+    case 14: return launch_fft_t<14>(l, at);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+#if SDR_FFT_WIN && !SDR_FFT_IQ8
 // The device image of a window table w[N] (sample order): the order the windowed kernel of that size reads it in (N = 512
 // - 16384: load_window above; N = 32768 / 65536: k_fft2p_win_a reads it in sample order beside the samples themselves).
 void window_layout(int logn, const float *w, float *out)
@@ -864,90 +874,6 @@ void window_layout(int logn, const float *w, float *out)
         break;
     }
 }
-
-// N = 512 - 16384 with the window table tap.window, in window_layout's order (launch_fft hands such a launch on)
-hipError_t launch_fft_win(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
-{
-    if (!tap.window || fft.r32 || fft.two_phase || is_iq8(fmt))
-        return hipErrorInvalidValue;  // (host/batch_plan.h: a windowed batch is never planned onto k_fft_r32)
-#else
-// The bank's twiddle buffer for N = 16384 holds both kernels' tables, the 32-point kernel's behind the other.
-hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                      int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at)
-{
-    if (fmt != InFormat::F32 && fmt != InFormat::SC16 && !is_iq8(fmt))
-        return hipErrorInvalidValue;
-    if (fft.two_phase)  // (with tap.window: k_fft2p_win_a)
-        return launch_fft_2p(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    if (is_iq8(fmt)) {  // k_fft_r32_iq8.hip / k_fft_psd_iq8.hip, plain or windowed
-        const uint8_t *iq8p = static_cast<const uint8_t *>(iq);
-        if (!fft.r32)
-            return launch_fft_iq8(logn, fmt == InFormat::CU8, iq8p, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-        if (logn != 14 || tap.window)
-            return hipErrorInvalidValue;
-        return launch_fft_r32_iq8(fmt == InFormat::CU8, iq8p, cur, tw + fft64::Plan<14>::TW_TOTAL, psd, n_frames, n_bands, in_stride, frame_stride, out_stride,
-                                  tap, fft.reserve_cus, fft.reserve_forced, at);
-    }
-    if (tap.window)
-        return launch_fft_win(logn, fft, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    if (fft.r32) {
-        if (logn != 14)
-            return hipErrorInvalidValue;
-        const fft64::cplx *tw32 = tw + fft64::Plan<14>::TW_TOTAL;
-        if (fmt == InFormat::SC16)
-            return launch_fft_r32_sc16(static_cast<const int16_t *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, fft.reserve_cus, fft.reserve_forced, at);
-        return launch_fft_r32(static_cast<const float *>(iq), cur, tw32, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, fft.reserve_cus, fft.reserve_forced, at);
-    }
 #endif
-    switch (logn) {
-    case 9: return launch_fft_t<9>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 10: return launch_fft_t<10>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 11: return launch_fft_t<11>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 12: return launch_fft_t<12>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 13: return launch_fft_t<13>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    case 14: return launch_fft_t<14>(fft.fpw, fmt, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, at);
-    default: return hipErrorInvalidValue;
-    }
-}
-#if !SDR_FFT_WIN
-int twiddle_count(int logn)
-{
-    switch (logn) {
-    case 9: return fft64::Plan<9>::TW_TOTAL;
-    case 10: return fft64::Plan<10>::TW_TOTAL;
-    case 11: return fft64::Plan<11>::TW_TOTAL;
-    case 12: return fft64::Plan<12>::TW_TOTAL;
-    case 13: return fft64::Plan<13>::TW_TOTAL;
-    case 14: return fft64::Plan<14>::TW_TOTAL + r32_twiddle_count();
-    case 15: return 1 << 14;  // k_fft_2p: go-dsp's table as it is, the N / 2 entries a radix-2 FFT reads
-    case 16: return 1 << 15;
-    default: return 0;
-    }
-}
-
-void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx *out)
-{
-    switch (logn) {
-    case 9: fft64::build_pass_twiddles<9>(wre, wim, out); break;
-    case 10: fft64::build_pass_twiddles<10>(wre, wim, out); break;
-    case 11: fft64::build_pass_twiddles<11>(wre, wim, out); break;
-    case 12: fft64::build_pass_twiddles<12>(wre, wim, out); break;
-    case 13: fft64::build_pass_twiddles<13>(wre, wim, out); break;
-    case 14:
-        fft64::build_pass_twiddles<14>(wre, wim, out);
-        r32_build_twiddles(wre, wim, out + fft64::Plan<14>::TW_TOTAL);
-        break;
-    case 15:
-    case 16:
-        for (int i = 0; i < 1 << (logn - 1); i++)
-            out[i] = fft64::cplx{wre[i], wim[i]};
-        break;
-    default: break;
-    }
-}
-#endif  // !SDR_FFT_WIN
-
-#endif  // !SDR_FFT_IQ8
 
 }  // namespace sdr

@@ -42,8 +42,8 @@
 // keep their dense frames (frame f at sample f * N of the band, a constant shift) and k_fft_r32_hop.hip /
 // k_fft_r32_hop_sc16.hip / k_fft_r32_hop_iq8.hip compile this file again with SDR_R32_HOP = 1: k_fft_r32_hop(_sc16, _iq8) take the stride as a shift
 // (every hop is a power of two) beside the frame count, fold it into the scalar base of the frame's buffer descriptor
-// and pay that one spilled SGPR (into a vector register's lane: no scratch).  launch_fft_r32(_sc16) hand a launch with
-// frame_stride != N on to them.
+// and pay that one spilled SGPR (into a vector register's lane: no scratch).  The batch plan picks them where the hop is
+// below N (FftChoice::strided); the dense units refuse such a launch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -64,11 +64,9 @@
 // (the 8-bit forms' extra kernel parameter - the format's XOR mask - and their launchers' leading one)
 #if SDR_R32_IQ8
 #define SDR_R32_FMT_KPARAM , unsigned flip
-#define SDR_R32_FMT_LPARAM bool cu8,
-#define SDR_R32_FMT_LARG cu8,
+#define SDR_R32_FMT_LARG , iq8::format_of(l.fft.fmt == InFormat::CU8).flip
 #else
 #define SDR_R32_FMT_KPARAM
-#define SDR_R32_FMT_LPARAM
 #define SDR_R32_FMT_LARG
 #endif
 #if SDR_R32_IQ8
@@ -83,21 +81,27 @@
 #if SDR_R32_HOP && SDR_R32_IQ8
 #define SDR_R32_KERNEL k_fft_r32_hop_iq8
 #define SDR_R32_LAUNCH launch_fft_r32_hop_iq8
+#define SDR_R32_ID FftKernel::R32_HOP_IQ8
 #elif SDR_R32_IQ8
 #define SDR_R32_KERNEL k_fft_r32_iq8
 #define SDR_R32_LAUNCH launch_fft_r32_iq8
+#define SDR_R32_ID FftKernel::R32_IQ8
 #elif SDR_R32_HOP && SDR_R32_SC16
 #define SDR_R32_KERNEL k_fft_r32_hop_sc16
 #define SDR_R32_LAUNCH launch_fft_r32_hop_sc16
+#define SDR_R32_ID FftKernel::R32_HOP_SC16
 #elif SDR_R32_HOP
 #define SDR_R32_KERNEL k_fft_r32_hop
 #define SDR_R32_LAUNCH launch_fft_r32_hop
+#define SDR_R32_ID FftKernel::R32_HOP
 #elif SDR_R32_SC16
 #define SDR_R32_KERNEL k_fft_r32_sc16
 #define SDR_R32_LAUNCH launch_fft_r32_sc16
+#define SDR_R32_ID FftKernel::R32_SC16
 #else
 #define SDR_R32_KERNEL k_fft_r32
 #define SDR_R32_LAUNCH launch_fft_r32
+#define SDR_R32_ID FftKernel::R32
 #endif
 
 #if !defined(SDR_R32_IN_AUX)
@@ -708,16 +712,10 @@ __global__ __launch_bounds__(fft32::T, 2) void SDR_R32_KERNEL(const SDR_R32_IN *
 
 }  // namespace r32
 
-#if !SDR_R32_SC16 && !SDR_R32_HOP && !SDR_R32_IQ8
-int r32_twiddle_count() { return fft32::kTwTotal; }
-void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out) { fft32::build_twiddles(wre, wim, out); }
-#endif
-
 // Workgroups per band: one per CU, less the reserve_cus CUs the batch plan leaves to the other streams' kernels
 // (host/batch_plan.h fft_reserve_cus; the rule's value capped at a quarter of the device, a forced one taken as it is),
 // at least one, never more than there are frames.
-hipError_t SDR_R32_LAUNCH(SDR_R32_FMT_LPARAM const SDR_R32_IN *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at)
+hipError_t SDR_R32_LAUNCH(const FftLaunch &l, LaunchAt at)
 {
     constexpr int kMaxDevices = 64;
     static std::once_flag setup_once[kMaxDevices];
@@ -738,44 +736,37 @@ hipError_t SDR_R32_LAUNCH(SDR_R32_FMT_LPARAM const SDR_R32_IN *iq, const BatchCu
     });
     if (setup_err[dev] != hipSuccess)
         return setup_err[dev];
+    if (fft_kernel(l.fft) != SDR_R32_ID || l.logn != 14)
+        return hipErrorInvalidValue;  // this unit holds one kernel
+    const FftTap &tap = l.tap;
+    const int n_frames = l.n_frames, n_bands = l.n_bands;
     if (n_frames <= 0 || n_bands <= 0)
         return hipSuccess;
     if (tap.n > fft32::T)
-        return hipErrorInvalidValue;  // (launch_fft never asks: one listener slot per thread)
-    if (!tap.steal)
+        return hipErrorInvalidValue;  // (the plan never asks: one listener slot per thread)
+    if (!l.steal)
         return hipErrorInvalidValue;  // the frame counters are the bank's (BatchSet::fft_ctr)
-    if (in_stride > 0xffffffffu)
+    if (l.in_stride > 0xffffffffu)
         return hipErrorInvalidValue;
 #if SDR_R32_HOP
     // the frame stride travels as a shift beside the frame count (see the kernel): a power of two, as every hop is
     int shift = 0;
-    while ((1 << shift) < frame_stride)
+    while ((1 << shift) < l.frame_stride)
         shift++;
-    if (frame_stride <= 0 || (1 << shift) != frame_stride || n_frames >= (1 << r32::kFrameBits))
+    if (l.frame_stride <= 0 || (1 << shift) != l.frame_stride || n_frames >= (1 << r32::kFrameBits))
         return hipErrorInvalidValue;
     const unsigned frames_and_shift = (unsigned)n_frames | (unsigned)shift << r32::kFrameBits;
 #else
-    if (frame_stride != fft32::N)  // overlapped frames: the strided kernel (k_fft_r32_hop.hip)
-#if SDR_R32_IQ8
-        return launch_fft_r32_hop_iq8(cu8, iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, at);
-#elif SDR_R32_SC16
-        return launch_fft_r32_hop_sc16(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, at);
-#else
-        return launch_fft_r32_hop(iq, cur, tw, psd, n_frames, n_bands, in_stride, frame_stride, out_stride, tap, reserve_cus, reserve_forced, at);
-#endif
+    if (l.frame_stride != fft32::N)  // overlapped frames are the strided unit's (k_fft_r32_hop.hip)
+        return hipErrorInvalidValue;
     const unsigned frames_and_shift = (unsigned)n_frames;
 #endif
     // the rule's value is sized on a 256-CU device: on a smaller one (or a partition) never more than a quarter of it
-    const int reserve = reserve_forced ? reserve_cus : std::min(reserve_cus, cu_count[dev] / kReserveDeviceShare);
+    const int reserve = l.fft.reserve_forced ? l.fft.reserve_cus : std::min(l.fft.reserve_cus, cu_count[dev] / kReserveDeviceShare);
     const int cus = std::max(1, cu_count[dev] - std::max(0, reserve));
     const int grid = std::min((cus + n_bands - 1) / n_bands, n_frames);
-#if SDR_R32_IQ8
-    launch_kernel(r32::SDR_R32_KERNEL, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, at, iq, cur, tw, psd, (unsigned)in_stride, out_stride,
-                  frames_and_shift, tap.steal, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used, iq8::format_of(cu8).flip);
-#else
-    launch_kernel(r32::SDR_R32_KERNEL, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, at, iq, cur, tw, psd, (unsigned)in_stride, out_stride,
-                  frames_and_shift, tap.steal, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used);
-#endif
+    launch_kernel(r32::SDR_R32_KERNEL, dim3(grid, n_bands), dim3(fft32::T), r32::kLdsBytes, at, static_cast<const SDR_R32_IN *>(l.iq), l.cur, l.tw, l.psd,
+                  (unsigned)l.in_stride, l.out_stride, frames_and_shift, l.steal, tap.bins, tap.out, tap.n, tap.stride, tap.wide, tap.used SDR_R32_FMT_LARG);
     return hipGetLastError();
 }
 

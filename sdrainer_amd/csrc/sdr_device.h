@@ -76,10 +76,6 @@ struct BatchCursor {
     const uint8_t *iq8;      // this batch's input frames (cs8 / cu8 graphs: sdr_graph_capture_iq8)
 };
 
-// What the FFT kernels read: interleaved float32 I,Q, complex int16 (sc16.h) or complex 8-bit, signed or unsigned (iq8.h)
-enum class InFormat { F32 = 0, SC16 = 1, CS8 = 2, CU8 = 3 };
-constexpr bool is_iq8(InFormat f) { return f == InFormat::CS8 || f == InFormat::CU8; }
-
 struct ListenGeom {
     int n, stride, max_listeners, text_cap, edge_cap, bit_words, trace;
     uint32_t frame_base;
@@ -172,6 +168,24 @@ struct FftTap {
     // and the bins those rows were taken at, [band][stride] (-1 = none): what k_cum_refine reads instead of psd columns
     float *wide = nullptr;
     int32_t *used = nullptr;
+};
+
+// One FFT launch: what every FFT launcher takes.  `fft` names the kernel (host/batch_plan.h fft_kernel); launch_fft
+// (fft_launch.hip) hands the launch to the unit that holds it, and a unit's entry refuses every kernel that is not its own.
+struct FftLaunch {
+    int logn;
+    FftChoice fft;
+    // samples of format fft.fmt (float32 pairs, sc16 words or cs8 / cu8 byte pairs); band b's frame f is the N samples from
+    // sample b * in_stride + f * frame_stride on (host/overlap.h input_sample_offset; dense frames: frame_stride = N,
+    // in_stride = n_frames * N; overlapped frames: frame_stride = hop < N, fft.strided)
+    const void *iq;
+    const BatchCursor *cur;
+    const fft64::cplx *tw;  // the bank's twiddle buffer (build_twiddles); the k_fft_r32 units' entries take their own table
+    float *psd;
+    int n_frames, n_bands;
+    size_t in_stride;
+    int frame_stride, out_stride;
+    FftTap tap;
     // k_fft_r32 only: its frame counters, [band][2] uint32, zero between launches (BatchSet::fft_ctr)
     uint32_t *steal = nullptr;
     // k_fft_2p only: one frame group's float64 intermediate, [band][FftChoice::group_frames][N] (BatchSet::fft_scratch)
@@ -182,50 +196,34 @@ struct FftTap {
     const float *window = nullptr;
 };
 
-// iq: samples of format fmt (float32 pairs, sc16 words or cs8 / cu8 byte pairs); band b's frame f is the N samples from sample b * in_stride +
-// f * frame_stride on (host/overlap.h input_sample_offset; dense frames: frame_stride = N, in_stride = n_frames * N; overlapped
-// frames: frame_stride = hop < N); `fft` picks the kernel (host/batch_plan.h)
-hipError_t launch_fft(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                      int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
-// k_fft_psd_win.hip: N = 512 - 16384 with tap.window set (launch_fft hands such a launch on; never k_fft_r32)
-hipError_t launch_fft_win(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                          int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
-// k_fft_psd_iq8.hip: N = 512 - 16384 from 8-bit frames (cu8: unsigned, else cs8), with tap.window or without (launch_fft
-// hands such a launch on)
-hipError_t launch_fft_iq8(int logn, bool cu8, const uint8_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
-// ... and the order its kernels read the table in: out[N] from the caller's w[N] (sample order)
-void window_layout(int logn, const float *w, float *out);
-// k_fft_2p.hip: N = 32768 / 65536 as two phases over a scratch buffer (fft_2p.h), frame group by frame group
-hipError_t launch_fft_2p(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                         int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
-// k_fft_2p_iq8.hip: the same from 8-bit frames, fmt = CS8 / CU8 (launch_fft_2p hands such a launch on)
-hipError_t launch_fft_2p_iq8(int logn, FftChoice fft, InFormat fmt, const void *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd,
-                             int n_frames, int n_bands, size_t in_stride, int frame_stride, int out_stride, FftTap tap, LaunchAt at);
+// fft_launch.hip: the one dispatch, a switch on fft_kernel(l.fft) over the units' entries below.  The bank's twiddle buffer
+// for N = 16384 holds both kernels' tables, the 32-point kernel's behind the other: the k_fft_r32 units get theirs from here.
+hipError_t launch_fft(const FftLaunch &l, LaunchAt at);
 int twiddle_count(int logn);
 void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx *out);
-// k_fft_r32.hip: N = 16384 as 512 threads x 32 points with the next frame prefetched into registers (own twiddle layout);
-// reserve_cus: CUs the grid leaves free (FftChoice::reserve_cus; unless reserve_forced at most CUs / kReserveDeviceShare) -
-// workgroups per band = max(1, ceil((CUs - reserve_cus) / n_bands)), at most n_frames
-hipError_t launch_fft_r32(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                          size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
-// k_fft_r32_sc16.hip: the same kernel reading sc16 frames
-hipError_t launch_fft_r32_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                               size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
-// k_fft_r32_hop.hip / k_fft_r32_hop_sc16.hip: the same kernels for frame_stride < N (a power of two); the two launchers
-// above hand such a launch on themselves
-hipError_t launch_fft_r32_hop(const float *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                              size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
-hipError_t launch_fft_r32_hop_sc16(const int16_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                                   size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
-// k_fft_r32_iq8.hip / k_fft_r32_hop_iq8.hip: the same kernels reading 8-bit frames (cu8: unsigned, else cs8); the first hands a
-// launch with frame_stride < N on to the second
-hipError_t launch_fft_r32_iq8(bool cu8, const uint8_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                              size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
-hipError_t launch_fft_r32_hop_iq8(bool cu8, const uint8_t *iq, const BatchCursor *cur, const fft64::cplx *tw, float *psd, int n_frames, int n_bands,
-                                  size_t in_stride, int frame_stride, int out_stride, FftTap tap, int reserve_cus, bool reserve_forced, LaunchAt at);
-int r32_twiddle_count();
-void r32_build_twiddles(const double *wre, const double *wim, fft64::cplx *out);
+// One entry per kernel unit: it launches the kernels of fft_kernel(l.fft) that the unit holds and returns
+// hipErrorInvalidValue for any other id.  k_fft_psd.hip and its recompilations, N = 512 - 16384: float32 and sc16 frames,
+// the same with a window, 8-bit frames with a window or without
+hipError_t launch_fft_psd(const FftLaunch &l, LaunchAt at);
+hipError_t launch_fft_psd_win(const FftLaunch &l, LaunchAt at);
+hipError_t launch_fft_psd_iq8(const FftLaunch &l, LaunchAt at);
+// k_fft_psd_win.hip: the order its kernels read the window table in: out[N] from the caller's w[N] (sample order)
+void window_layout(int logn, const float *w, float *out);
+// k_fft_r32.hip and its recompilations: N = 16384 as 512 threads x 32 points with the next frame prefetched into registers
+// (l.tw: their own twiddle layout), by format, dense frames and frame_stride < N (a power of two).  Workgroups per band =
+// max(1, ceil((CUs - fft.reserve_cus) / n_bands)), at most n_frames (unless fft.reserve_forced the reserve is at most
+// CUs / kReserveDeviceShare)
+hipError_t launch_fft_r32(const FftLaunch &l, LaunchAt at);
+hipError_t launch_fft_r32_sc16(const FftLaunch &l, LaunchAt at);
+hipError_t launch_fft_r32_iq8(const FftLaunch &l, LaunchAt at);
+hipError_t launch_fft_r32_hop(const FftLaunch &l, LaunchAt at);
+hipError_t launch_fft_r32_hop_sc16(const FftLaunch &l, LaunchAt at);
+hipError_t launch_fft_r32_hop_iq8(const FftLaunch &l, LaunchAt at);
+// k_fft_2p.hip (float32, sc16) and k_fft_2p_iq8.hip (cs8, cu8): N = 32768 / 65536 as two phases over l.scratch (fft_2p.h),
+// frame group by frame group; phase B of frames [f0, f0 + g) of a group is k_fft_2p.hip's for both
+hipError_t launch_fft_2p(const FftLaunch &l, LaunchAt at);
+hipError_t launch_fft_2p_iq8(const FftLaunch &l, LaunchAt at);
+hipError_t launch_fft2p_b(const FftLaunch &l, int f0, int g, LaunchAt at);
 // wpb_forced: windows per workgroup (0: the launcher's rule); mfma: the matrix-pipe variance kernel (host/batch_plan.h)
 hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, int n_frames, int n_bands, int stride, int wpb_forced,
                                LaunchAt at);

@@ -11,12 +11,14 @@ cumulation, and the number of runs it found), and drop counters of 0.
 The input reaches the bank by one of the paths of include/sdrainer_hip.h:
   "device"       float32 in device memory (sdr_process_device)
   "device_sc16"  complex int16 in device memory (sdr_process_device_sc16)
+  "device_cs8", "device_cu8"  complex 8-bit, signed / unsigned, in device memory (sdr_process_device_iq8)
   "staged"       float32 from the host (sdr_push_iq -> sdr_process_staged)
   "staged_sc16"  complex int16 from the host (sdr_push_iq_sc16)
   "kiwi"         KiwiSDR SND payloads, big-endian int16 (sdr_push_kiwi_snd), a batch's frames in several messages
   "graph"        hipGraph replays of float32 batches (sdr_graph_capture / sdr_graph_launch)
   "graph_sc16"   the same for sc16 (sdr_graph_capture_sc16 / sdr_graph_launch_sc16)
-The oracle always reads the float32 values the bank was given: for sc16 and KiwiSDR input float32(x) / 32767.
+The oracle always reads the float32 values the bank was given: for sc16 and KiwiSDR input float32(x) / 32767, for 8-bit
+input iq8_tools.to_f32.
 
 With a hop below the block size frame f of a band is stream[f * hop : f * hop + N]: the oracle is fed the materialised
 frames, the device paths go through sdr_process_device_stream(_sc16) with the pointer advanced by frames * hop, the staged
@@ -27,14 +29,16 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from iq8_tools import to_f32 as iq8_to_float32
 from oracle import oracle as orc
 from sdrainer_amd import synth
 from parity_tools import (RATES, bits_equal, check_batch_polled, check_device_batch, decode, frames_of, listener_bins, make_stream,
                           nan_equal_bits, sc16_to_float32, windowed)
 
 RATE = 2_000_000
-PATHS = ("device", "device_sc16", "staged", "staged_sc16", "kiwi", "graph", "graph_sc16")
+PATHS = ("device", "device_sc16", "device_cs8", "device_cu8", "staged", "staged_sc16", "kiwi", "graph", "graph_sc16")
 SC16_PATHS = ("device_sc16", "staged_sc16", "kiwi", "graph_sc16")
+IQ8_PATHS = {"device_cs8": 0, "device_cu8": 1}  # -> SDR_IQ8_CS8 / SDR_IQ8_CU8
 KIWI_HEADER = bytes([0x01] + [7] * 16)  # the 17 bytes in front of an SND message's samples (flags, sequence, smeter)
 
 
@@ -93,7 +97,7 @@ class Case:
         assert path in PATHS, path
         self.n, self.n_bands, self.rate, self.path, self.nan_ok = n, n_bands, rate, path, nan_ok
         self.hop, self.step, self.pad, self.trace = hop or 0, hop or n, pad, trace
-        assert self.step == n or path in ("device", "device_sc16", "staged", "staged_sc16"), f"{path} input takes no hop below N"
+        assert self.step == n or path.startswith("device") or path in ("staged", "staged_sc16"), f"{path} input takes no hop below N"
         assert not pad or (self.hop and path.startswith("device")), "a padded band stride is the device stream calls'"
         self.timed = bool(self.hop or trace)
         self.edge = synth.default_edge_width(n) if edge is None else edge
@@ -114,6 +118,8 @@ class Case:
                 assert f32.size == 2 * samples and f32.dtype == np.float32, f"band {b}: not {self.total} frames of float32"
                 if path in SC16_PATHS:
                     assert q is not None and bits_equal(sc16_to_float32(q), f32), f"band {b}: the float32 input is not its int16's value"
+                if path in IQ8_PATHS:
+                    assert q is not None and bits_equal(iq8_to_float32(q, IQ8_PATHS[path]), f32), f"band {b}: the float32 input is not its bytes' value"
                 self.stream.append(f32.reshape(-1, 2))
                 self.q.append(None if q is None else q.reshape(-1, 2))
             self.carriers.append([int(x) for x in bins])
@@ -333,7 +339,7 @@ class Case:
         import torch
 
         if not hasattr(self, "_dev"):
-            src = self.q if self.path in SC16_PATHS else self.stream
+            src = self.q if self.path in SC16_PATHS or self.path in IQ8_PATHS else self.stream
             host = np.zeros((self.n_bands, src[0].shape[0] + self.pad, 2), src[0].dtype)
             for b in range(self.n_bands):
                 host[b, :src[b].shape[0]] = src[b]
@@ -350,11 +356,17 @@ class Case:
         if self.path.startswith("device") and self.hop:
             dev = self._device_input()
             ptr = dev.data_ptr() + a * self.hop * 2 * dev.element_size()
-            (bank.process_device_stream_sc16 if sc16 else bank.process_device_stream)(ptr, e - a, dev.shape[1])
+            if self.path in IQ8_PATHS:
+                bank.process_device_stream_iq8(ptr, e - a, dev.shape[1], IQ8_PATHS[self.path])
+            else:
+                (bank.process_device_stream_sc16 if sc16 else bank.process_device_stream)(ptr, e - a, dev.shape[1])
             return dev
         if self.path.startswith("device"):
             batch = self.device_batch(a, e)
-            (bank.process_device_sc16 if sc16 else bank.process_device)(batch.data_ptr(), e - a)
+            if self.path in IQ8_PATHS:
+                bank.process_device_iq8(batch.data_ptr(), e - a, IQ8_PATHS[self.path])
+            else:
+                (bank.process_device_sc16 if sc16 else bank.process_device)(batch.data_ptr(), e - a)
             return batch
         lo, hi = (a - 1) * self.step + self.n if a else 0, (e - 1) * self.step + self.n  # the samples the batch adds
         for b in range(self.n_bands):

@@ -31,47 +31,10 @@ __device__ unsigned long long g_fft_wg[2048][4];
 }  // namespace sdr
 #endif
 #include "../sdrainer_amd/csrc/k_fft_psd.hip"
-#include "../sdrainer_amd/csrc/k_fft_r32.hip"  // (launch_fft routes N = 16384 to it; SDR_FFT_R32=0 keeps the 16-point kernel)
+#include "../sdrainer_amd/csrc/k_fft_r32.hip"  // (N = 16384 from 1024 frames on; SDR_FFT_R32=0 keeps the 16-point kernel)
+#define SDR_FFT_TABLES_ONLY  // twiddle_count / build_twiddles; this tool calls the entries of the two units above itself
+#include "../sdrainer_amd/csrc/fft_launch.hip"
 #include "../sdrainer_amd/csrc/twiddles.h"
-
-namespace sdr {
-// (this tool times float32 input only: launch_fft's sc16 branch is linked to nothing - k_fft_r32_sc16.hip is k_fft_r32.hip
-// compiled again and cannot share this translation unit)
-hipError_t launch_fft_r32_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-// (nor dense input's strided twins, k_fft_r32_hop.hip / k_fft_r32_hop_sc16.hip: this tool's frames do not overlap)
-hipError_t launch_fft_r32_hop(const float *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-hipError_t launch_fft_r32_hop_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-// (nor the 8-bit kernels, k_fft_psd_iq8.hip / k_fft_r32_iq8.hip)
-hipError_t launch_fft_iq8(int, bool, const uint8_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-hipError_t launch_fft_r32_iq8(bool, const uint8_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-// (nor the two-phase kernels of N = 32768 / 65536, k_fft_2p.hip)
-hipError_t launch_fft_2p(int, FftChoice, InFormat, const void *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap,
-                         LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-// (nor the windowed kernels, k_fft_psd_win.hip: this tool sets no window)
-hipError_t launch_fft_win(int, FftChoice, InFormat, const void *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap,
-                          LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-}  // namespace sdr
 
 static unsigned long long fnv(const void *p, size_t n)
 {
@@ -116,8 +79,9 @@ int main(int argc, char **argv)
     const int n_tap = getenv("SDR_TAP") ? atoi(getenv("SDR_TAP")) : 256;
     sdr::FftTap tap{nullptr, nullptr, n_tap, n_tap > 0 ? n_tap : 1};
     // k_fft_r32's frame counters (N = 16384 from 1024 frames on), a zeroed pair per band
-    CK(hipMalloc(&tap.steal, (size_t)bands * 2 * sizeof(uint32_t)));
-    CK(hipMemset(tap.steal, 0, (size_t)bands * 2 * sizeof(uint32_t)));
+    uint32_t *steal;
+    CK(hipMalloc(&steal, (size_t)bands * 2 * sizeof(uint32_t)));
+    CK(hipMemset(steal, 0, (size_t)bands * 2 * sizeof(uint32_t)));
     float *dout = nullptr;
     if (n_tap > 0) {
         std::vector<int32_t> bins((size_t)n_tap * bands);
@@ -142,7 +106,11 @@ int main(int argc, char **argv)
     }
     // the library's choice for this batch (SDR_FFT_R32 / SDR_FFT_FPW honoured as in the pipeline)
     const sdr::FftChoice choice = sdr::fft_choice(sdr::read_switches(), N, frames, bands, n_tap);
-    auto launch = [&](hipStream_t st) { return sdr::launch_fft(logn, choice, sdr::InFormat::F32, iq, nullptr, tw, pd, frames, bands, (size_t)frames * N, N, frames, tap, st); };
+    printf("# kernel: %s\n", sdr::fft_kernel_name(sdr::fft_kernel(choice)));
+    sdr::FftLaunch fl{logn, choice, iq, nullptr, tw, pd, frames, bands, (size_t)frames * N, N, frames, tap, steal};
+    if (choice.r32)  // (the second table of the N = 16384 buffer, as launch_fft hands it on)
+        fl.tw = tw + fft64::Plan<14>::TW_TOTAL;
+    auto launch = [&](hipStream_t st) { return choice.r32 ? sdr::launch_fft_r32(fl, st) : sdr::launch_fft_psd(fl, st); };
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));

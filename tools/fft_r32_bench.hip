@@ -23,46 +23,9 @@ __device__ unsigned g_r32_phases[8][16];
 #endif
 #include "../sdrainer_amd/csrc/k_fft_psd.hip"
 #include "../sdrainer_amd/csrc/k_fft_r32.hip"
+#define SDR_FFT_TABLES_ONLY  // twiddle_count / build_twiddles; this tool calls the entries of the two units above itself
+#include "../sdrainer_amd/csrc/fft_launch.hip"
 #include "../sdrainer_amd/csrc/twiddles.h"
-
-namespace sdr {
-// (this tool times float32 input only: launch_fft's sc16 branch is linked to nothing - k_fft_r32_sc16.hip is k_fft_r32.hip
-// compiled again and cannot share this translation unit)
-hipError_t launch_fft_r32_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-// (nor dense input's strided twins, k_fft_r32_hop.hip / k_fft_r32_hop_sc16.hip: this tool's frames do not overlap)
-hipError_t launch_fft_r32_hop(const float *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-hipError_t launch_fft_r32_hop_sc16(const int16_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-// (nor the 8-bit kernels, k_fft_psd_iq8.hip / k_fft_r32_iq8.hip)
-hipError_t launch_fft_iq8(int, bool, const uint8_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-hipError_t launch_fft_r32_iq8(bool, const uint8_t *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap, int, bool, LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-// (nor the two-phase kernels of N = 32768 / 65536, k_fft_2p.hip)
-hipError_t launch_fft_2p(int, FftChoice, InFormat, const void *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap,
-                         LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-// (nor the windowed kernels, k_fft_psd_win.hip: this tool sets no window)
-hipError_t launch_fft_win(int, FftChoice, InFormat, const void *, const BatchCursor *, const fft64::cplx *, float *, int, int, size_t, int, int, FftTap,
-                          LaunchAt)
-{
-    return hipErrorNotSupported;
-}
-}  // namespace sdr
 
 static unsigned long long fnv(const void *p, size_t n)
 {
@@ -92,9 +55,9 @@ int main(int argc, char **argv)
     std::vector<double> wre, wim;
     fft64::radix2_factors(N, wre, wim);
     // (the library's table for N = 16384 holds both kernels' twiddles; the tool launches each kernel on its own)
-    std::vector<fft64::cplx> h16((size_t)sdr::twiddle_count(logn)), h32((size_t)sdr::r32_twiddle_count());
+    std::vector<fft64::cplx> h16((size_t)sdr::twiddle_count(logn)), h32((size_t)fft32::kTwTotal);
     sdr::build_twiddles(logn, wre.data(), wim.data(), h16.data());
-    sdr::r32_build_twiddles(wre.data(), wim.data(), h32.data());
+    fft32::build_twiddles(wre.data(), wim.data(), h32.data());
     fft64::cplx *tw16, *tw32;
     float *iq, *pd16, *pd32;
     const size_t total = (size_t)frames * bands;
@@ -135,8 +98,9 @@ int main(int argc, char **argv)
         host_bins = bins;
     }
     // k_fft_r32's frame counters, a zeroed pair per band (each launch leaves them zero)
-    CK(hipMalloc(&tap32.steal, (size_t)bands * 2 * sizeof(uint32_t)));
-    CK(hipMemset(tap32.steal, 0, (size_t)bands * 2 * sizeof(uint32_t)));
+    uint32_t *steal;
+    CK(hipMalloc(&steal, (size_t)bands * 2 * sizeof(uint32_t)));
+    CK(hipMemset(steal, 0, (size_t)bands * 2 * sizeof(uint32_t)));
     {
         // wide dynamic range: a strong on-bin carrier, weak noise, a few zeros and subnormals
         std::vector<float> x(total * N * 2);
@@ -154,11 +118,16 @@ int main(int argc, char **argv)
         }
         CK(hipMemcpy(iq, x.data(), x.size() * 4, hipMemcpyHostToDevice));
     }
-    sdr::FftChoice c16;  // the 16-point kernel (SDR_FFT_FPW honoured as in the pipeline)
-    c16.fpw = sdr::read_switches().fft_fpw;
-    auto launch16 = [&](hipStream_t st) { return sdr::launch_fft(logn, c16, sdr::InFormat::F32, iq, nullptr, tw16, pd16, frames, bands, (size_t)frames * N, N, frames, tap16, st); };
-    const int reserve = std::max(0, sdr::read_switches().fft_reserve);  // SDR_FFT_RESERVE: CUs the 32-point kernel's grid leaves free
-    auto launch32 = [&](hipStream_t st) { return sdr::launch_fft_r32(iq, nullptr, tw32, pd32, frames, bands, (size_t)frames * N, N, frames, tap32, reserve, true, st); };
+    // each kernel as the plan would choose it with SDR_FFT_R32 = 0 / 1 (SDR_FFT_FPW honoured as in the pipeline)
+    sdr::Switches sw16 = sdr::read_switches(), sw32 = sw16;
+    sw16.fft_r32 = 0;
+    sw32.fft_r32 = 1;
+    sdr::FftLaunch l16{logn, sdr::fft_choice(sw16, N, frames, bands, n_tap), iq, nullptr, tw16, pd16, frames, bands, (size_t)frames * N, N, frames, tap16};
+    sdr::FftLaunch l32{logn, sdr::fft_choice(sw32, N, frames, bands, n_tap), iq, nullptr, tw32, pd32, frames, bands, (size_t)frames * N, N, frames, tap32, steal};
+    l32.fft.reserve_cus = std::max(0, sw32.fft_reserve);  // SDR_FFT_RESERVE: CUs the 32-point kernel's grid leaves free
+    l32.fft.reserve_forced = true;
+    auto launch16 = [&](hipStream_t st) { return sdr::launch_fft_psd(l16, st); };
+    auto launch32 = [&](hipStream_t st) { return sdr::launch_fft_r32(l32, st); };
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
