@@ -38,6 +38,7 @@ struct RefSink {
     void put(uint32_t r) { out.push_back({r, frame}); }
 };
 
+// (tests/keying_gen.py stream() mirrors kinds 0 - 3 for the GPU tests of the kernel itself: a kind added here belongs there)
 static std::vector<uint8_t> make_stream(int ticks, int kind)
 {
     std::vector<uint8_t> s;

@@ -85,7 +85,8 @@ class Case:
     trace=True, and every checked batch is also held to the oracle's traced values, raw and debounced bits
     (sdr_read_trace) and to the psd and dB rows of the frames spectrum_frames() names.  With a hop or with trace the
     expected text, decoder state and rune frames are the hop-timed decoder's over the oracle's debounced bits, and every
-    step is a batch.
+    step is a batch, a deferred batch or an attach (no detach): a late listener's decoder ticks from the frame it was attached
+    at, and its tap is compared from that frame on.
 
     Not run by any test yet, so not to be trusted before the first row that uses them: the staged paths with a hop below N
     (the sample range of _enqueue) and run_graph with windows (a window set before the capture, release and a new capture
@@ -139,7 +140,7 @@ class Case:
                 self.spans.append((pos, pos + s[1]))
                 pos += s[1]
         assert self.total == pos, f"the steps hold {pos} frames, not {self.total}"
-        assert not self.timed or len(self.spans) == len(steps), "with a hop or with trace every step is a batch"
+        assert not self.timed or all(s[0] != "detach" for s in steps), "with a hop or with trace no listener is detached"
         self.windows = [None] * len(self.spans) if windows is None else list(windows)
         assert len(self.windows) == len(self.spans), "one window (or None) per batch"
         self.max_frames = max(e - a for a, e in self.spans)
@@ -240,8 +241,12 @@ class Case:
             res = list(ex.map(run, range(self.n_bands)))
         self.refs = [r for r, _ in res]
         self.outs = [o for _, o in res]
-        if self.timed:  # (text, 12-value state, the tick that wrote each rune) of every listener
-            self.decs = [[decode(out["deb"][:, lid], self.rate, self.step) for lid in range(out["deb"].shape[1])] for out in self.outs]
+        if self.timed:  # (text, 12-value state, the frame that wrote each rune) of every listener, ticked from its first frame on
+            def timed(b, lid):
+                start = self.life[b][lid][0]
+                text, state, at = decode(self.outs[b]["deb"][start:, lid], self.rate, self.step)
+                return text, state, at + start
+            self.decs = [[timed(b, lid) for lid in range(out["deb"].shape[1])] for b, out in enumerate(self.outs)]
 
     def oracle_counts(self):
         """(edges, peaks) the oracle sees over the run: a row with none of either proves nothing."""
@@ -309,8 +314,9 @@ class Case:
             out = self.outs[b]
             for lid in self.live(b, a, e):
                 v, raw, deb = bank.read_trace(b, lid)
-                assert same(v, out["values"][a:e, lid].copy()), f"band {b} listener {lid} batch {k} tap values"
-                assert np.array_equal(raw, out["raw"][a:e, lid]), f"band {b} listener {lid} batch {k} raw bits"
+                s = max(self.life[b][lid][0] - a, 0)  # (a listener bound inside the batch: nothing was handed to it before)
+                assert same(v[s:], out["values"][a + s:e, lid].copy()), f"band {b} listener {lid} batch {k} tap values"
+                assert np.array_equal(raw[s:], out["raw"][a + s:e, lid]), f"band {b} listener {lid} batch {k} raw bits"
                 assert np.array_equal(deb, out["deb"][a:e, lid]), f"band {b} listener {lid} batch {k} debounced bits"
             for f in self.spectrum_frames(e - a):
                 sp, psd = bank.read_spectrum(b, f)

@@ -12,6 +12,7 @@ import functools
 import numpy as np
 import pytest
 
+import keying_gen
 import reports_ref as ref
 from parity_case import Case
 from parity_tools import (RATES, GROUP_BANDS, Pair, capi, group_bands, listener_bins, make_stream,  # noqa: F401 (capi: the fixture)
@@ -88,14 +89,24 @@ def assert_not_trivial(case, min_on=100):
 
 def run_reports(capi, case, check=True):
     """Every batch of the case on a new bank with reports on: poll_reports (a peek, twice), then poll, which must hand out the
-    same batch.  Returns the bank and the totals {(band, listener): accumulated record}."""
+    same batch; an ("attach", band, bin) step is taken in front of its batch.  Returns the bank and the totals
+    {(band, listener): accumulated record}."""
     case.run_oracle()
     wpm = wpm_table(case)
     bank = case.new_bank(capi)
     bank.enable_reports(True)
     assert bank.reports_enabled
     totals = {}
+    attach, n = {}, 0  # batch index -> the listeners attached in front of it
+    for s in case.steps:
+        if s[0] == "attach":
+            attach.setdefault(n, []).append(s[1:])
+        else:
+            assert s[0] == "batch", s
+            n += 1
     for k, (a, e) in enumerate(case.spans):
+        for band, bn in attach.get(k, []):
+            assert bank.attach(band, int(bn)) == len(case.live(band, a, e)) - 1
         case.set_window(bank, k)
         keep = case._enqueue(bank, a, e)
         peek = bank.poll_reports(wait=True)
@@ -135,6 +146,21 @@ def bank_records(totals):
         for f in ref.FIELDS:
             out[i][f] = totals[key][f]
     return out
+
+
+def test_hostile_keying(capi):
+    """Band 0 of tests/test_keying_gpu.py's base case (keying_gen.band0_case): speeds that change inside the stream, runs of
+    dahs, over-long marks, noise, idle listeners, batches of 1 to 1024 frames and a listener attached late - wpm by its bits,
+    the counts and the fixed-point sums, every listener, every batch."""
+    case = keying_gen.band0_case()
+    case.run_oracle()
+    table = wpm_table(case)
+    final = [w[-1] for w in table.values()]
+    assert min(final) <= 12 and max(final) >= 40, (min(final), max(final))
+    assert sum(len({np.float64(x).tobytes() for x in w}) >= 5 for w in table.values()) >= 12, "wpm moves in too few listeners"
+    bank, totals = run_reports(capi, case)
+    assert len(totals) == keying_gen.A_LISTENERS
+    bank.close()
 
 
 def test_debounced_bits(capi):
