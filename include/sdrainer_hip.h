@@ -129,7 +129,16 @@ typedef struct sdr_frame_rec {
     float pad;
 } sdr_frame_rec;
 
-/* one keying edge of a listener: debounced state changed at this frame (counted from bank start) */
+/* Frame numbering.  A bank counts its frames in 64 bits: sdr_total_frames, sdr_results.first_frame, sdr_chunk_result.frame
+ * and the scope frames are int64 bank frame indices (0 for the first frame of a new bank, or what sdr_set_first_frame
+ * gave it).  The two 32-bit fields, sdr_edge.frame and sdr_results.rune_frames, hold the bank frame index MODULO 2^32 (a
+ * record per keying edge has no room for more, and on the device frames are only ever compared as differences).  A
+ * consumer widens one against the first_frame of the batch that delivered it:
+ *     frame = first_frame + (int32_t)(f32 - (uint32_t)first_frame)
+ * (csrc/host/delivery.h widen_frame; exact while the frame lies within 2^31 of first_frame, and an edge or a rune lies in
+ * its batch or, a flushed rune, right before it). */
+
+/* one keying edge of a listener: debounced state changed at this frame (the bank frame index modulo 2^32, see above) */
 typedef struct sdr_edge {
     uint32_t frame;
     uint32_t state; /* 1 = key down */
@@ -158,6 +167,17 @@ int sdr_self_check(int device_id);
 /* Run on this hipStream_t (NULL = the null stream).  Must be called before the first process call
  * or while the bank is idle. */
 int sdr_set_stream(sdr_bank *bank, void *hip_stream);
+/* The bank's next frame gets the index `frame`: a host that restarts a bank inside a running stream keeps its frame
+ * numbering and, with it, the stream clock (sdr_total_frames returns `frame` at once; every first_frame, chunk frame,
+ * scope frame, edge frame and rune frame that follows counts from it, and sdr_attach_at takes start frames counted so).
+ * Nothing else changes: batch_index starts at 0 and cumulations complete at frames = 99 (mod SDR_CUMULATION_SIZE) as in
+ * any bank, which is why `frame` must be a multiple of SDR_CUMULATION_SIZE.
+ *   SDR_ERR_BAD_ARG: frame < 0, or not a multiple of SDR_CUMULATION_SIZE.
+ *   SDR_ERR_STATE: the bank has processed a frame, has input staged (sdr_push_*), holds or has held a listener, or has
+ *     a graph captured: call it right after sdr_create.
+ * sdr_group_set_first_frame (declared with the group): the same frame on every member, or on none (a member that refuses
+ * leaves the others as they were). */
+int sdr_set_first_frame(sdr_bank *bank, int64_t frame);
 
 /* producer side ------------------------------------------------------------------------------ */
 /* Copies n_floats/(2*block_size) interleaved I,Q float32 frames of `band` from host memory into the
@@ -514,6 +534,9 @@ int sdr_group_set_peak_threshold(sdr_group *group, int band, float threshold);
 int sdr_group_set_signal_debounce(sdr_group *group, int band, int debounce);
 int sdr_group_set_edge_width(sdr_group *group, int edge_width);
 int sdr_group_set_find_peaks(sdr_group *group, int on);
+/* sdr_set_first_frame on every member (arguments and statuses are its).  Members given different first frames by hand,
+ * through sdr_group_member, disagree on first_frame: sdr_group_poll returns SDR_ERR_STATE. */
+int sdr_group_set_first_frame(sdr_group *group, int64_t frame);
 /* sdr_set_window on every member, before the group's next process call: every band changes at the same frame, and the
  * members cannot come to disagree (what one would refuse is refused before any member's table changes). */
 int sdr_group_set_window(sdr_group *group, const float *window, int n);

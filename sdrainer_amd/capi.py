@@ -148,6 +148,7 @@ SYMBOLS = (
     "sdr_push_iq8 sdr_process_device_iq8 sdr_process_device_stream_iq8 sdr_graph_capture_iq8 sdr_graph_launch_iq8 "
     "sdr_group_push_iq8 sdr_group_process_device_iq8 "
     "sdr_set_window sdr_group_set_window "
+    "sdr_set_first_frame sdr_group_set_first_frame "
     "sdr_enable_rows sdr_row_columns sdr_poll_rows sdr_group_enable_rows sdr_group_poll_rows "
     "sdr_enable_reports sdr_reports_enabled sdr_poll_reports sdr_group_enable_reports sdr_group_poll_reports "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
@@ -201,6 +202,8 @@ def load():
     sig("sdr_push_iq8", C.c_int, vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int)
     sig("sdr_process_device_iq8", C.c_int, vp, vp, C.c_int, C.c_int)
     sig("sdr_process_device_stream_iq8", C.c_int, vp, vp, C.c_int, C.c_size_t, C.c_int)
+    sig("sdr_set_first_frame", C.c_int, vp, C.c_int64)
+    sig("sdr_group_set_first_frame", C.c_int, vp, C.c_int64)
     sig("sdr_sync", C.c_int, vp)
     sig("sdr_attach", C.c_int, vp, C.c_int, C.c_int, ip)
     sig("sdr_detach", C.c_int, vp, C.c_int, C.c_int)
@@ -434,6 +437,10 @@ class Bank:
     # producer ---------------------------------------------------------------------------------
     def set_stream(self, stream_ptr: int):
         _check(self._L.sdr_set_stream(self._h, C.c_void_p(stream_ptr)))
+
+    def set_first_frame(self, frame: int):
+        """sdr_set_first_frame: the bank's next frame gets this index (a multiple of CUMULATION_SIZE; a fresh bank only)."""
+        _check(self._L.sdr_set_first_frame(self._h, int(frame)))
 
     def push_iq(self, band: int, sample_rate: int, iq: np.ndarray) -> int:
         """Returns the status code (0 ok) instead of raising for the reference's log-and-drop cases."""
@@ -907,6 +914,10 @@ class Group:
 
     def set_find_peaks(self, on: bool):
         _check(self._L.sdr_group_set_find_peaks(self._h, int(on)))
+
+    def set_first_frame(self, frame: int):
+        """sdr_group_set_first_frame: Bank.set_first_frame on every member."""
+        _check(self._L.sdr_group_set_first_frame(self._h, int(frame)))
 
     def set_window(self, w):
         """sdr_group_set_window: the same window on every member, None removes it."""

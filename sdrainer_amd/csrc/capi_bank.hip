@@ -695,6 +695,29 @@ int sdr_last_batch_frames(sdr_bank *b) { return b ? b->last_frames : -1; }
 int64_t sdr_total_frames(sdr_bank *b) { return b ? b->total_frames : -1; }
 int sdr_last_batch_chunks(sdr_bank *b) { return b ? b->last_chunks : -1; }
 
+// Only total_frames changes: every 32-bit frame word (the slots' start_frame and tapped_from, the batches' frame_base)
+// is cut from it when a listener is attached or a batch is enqueued, and cum_count stays 0 - hence a multiple of the
+// cumulation size, so that cumulations still complete at frames = 99 (mod 100).
+int sdr_set_first_frame(sdr_bank *b, int64_t frame)
+{
+    if (!b)
+        return fail(SDR_ERR_BAD_ARG, "null bank");
+    if (frame < 0 || frame % SDR_CUMULATION_SIZE != 0)
+        return fail(SDR_ERR_BAD_ARG, "the first frame must be >= 0 and a multiple of SDR_CUMULATION_SIZE");
+    if (b->batch_index != 0 || b->listen_pending)
+        return fail(SDR_ERR_STATE, "the bank has processed frames already");
+    if (b->graph_ready)
+        return fail(SDR_ERR_STATE, "a graph is captured (sdr_graph_release first)");
+    for (int band = 0; band < b->cfg.n_bands; band++) {
+        if (b->n_slots[band] != 0)
+            return fail(SDR_ERR_STATE, "a listener is attached already (set the first frame before the first attach)");
+        if (b->staged[band].staged != 0 || b->staged[band].history != 0 || b->staged_kind[band] != 0)
+            return fail(SDR_ERR_STATE, "input is staged already (set the first frame before the first push)");
+    }
+    b->total_frames = frame;
+    return SDR_OK;
+}
+
 int sdr_profile_enable(sdr_bank *b, int on)
 {
     if (!b)

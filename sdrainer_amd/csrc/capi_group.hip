@@ -381,6 +381,25 @@ int sdr_group_set_find_peaks(sdr_group *g, int on)
     return SDR_OK;
 }
 
+// The members cannot come to disagree: where one refuses, those set before it (fresh banks, or they had refused) get
+// the frame they had back.
+int sdr_group_set_first_frame(sdr_group *g, int64_t frame)
+{
+    if (!g)
+        return fail(SDR_ERR_BAD_ARG, "null group");
+    std::vector<int64_t> before;
+    for (sdr_bank *b : g->banks) {
+        before.push_back(sdr_total_frames(b));
+        const int rc = sdr_set_first_frame(b, frame);
+        if (rc) {
+            for (size_t m = 0; m + 1 < before.size(); m++)
+                (void)sdr_set_first_frame(g->banks[m], before[m]);
+            return rc;  // (the member's message stands: a successful call leaves it alone)
+        }
+    }
+    return SDR_OK;
+}
+
 int sdr_group_enable_results(sdr_group *g, int on)
 {
     if (!g)

@@ -405,7 +405,7 @@ int sdr_scope_read_decode(sdr_bank *b, int band, int lid, sdr_scope_decode_frame
         return fail(SDR_ERR_STATE, "listener was not attached during the last batch");
     // a listener bound inside the batch (sdr_attach_at) ticks from its first frame on
     const int64_t first = b->total_frames - frames;
-    const int skip = (int)std::max<int64_t>(0, (int64_t)(int32_t)(slot.start_frame - (uint32_t)first));
+    const int skip = (int)std::max<int64_t>(0, host::widen_frame(slot.start_frame, first) - first);
     std::vector<uint16_t> table(cw::kMorseTableSize);
     cw::build_morse_table(table.data());
     struct NullSink {

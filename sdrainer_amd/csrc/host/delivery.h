@@ -28,6 +28,14 @@
 
 namespace host {
 
+// The 64-bit bank frame index of a 32-bit frame word (sdr_edge.frame, sdr_results.rune_frames: the index modulo 2^32),
+// against the first_frame of the batch that delivered it: the frame within 2^31 of first_frame that has these low bits.
+// The one place the host widens a frame; a plain cast falls 2^32 frames into the past once the bank has passed frame 2^32.
+inline int64_t widen_frame(uint32_t f32, int64_t first_frame)
+{
+    return first_frame + (int64_t)(int32_t)(f32 - (uint32_t)first_frame);
+}
+
 // what the host knows about the batch whose results sit in a block
 struct BatchMeta {
     int64_t batch = -1;  // -1: no undelivered batch here

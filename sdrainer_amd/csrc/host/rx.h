@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../../include/sdrainer_hip.h"
+#include "delivery.h"
 #include "frequency_mapping.h"
 #include "text_processor.h"
 
@@ -651,6 +652,9 @@ public:
             sdr_set_center_frequency(bank_, 0, f);
     }
     int64_t CenterFrequency() const { return centerFrequency_; }
+    // The bank frame index of the first frame (sdr_set_first_frame: a multiple of the cumulation size): a receiver that
+    // takes over a running stream keeps its frame numbering, and the stream clock with it.  Before Start only.
+    void SetFirstFrame(int64_t frame) { firstFrame_ = frame; }
     void SetSelectionPolicy(PeaksTable::Policy p)
     {
         policy_ = p;
@@ -686,10 +690,19 @@ public:
         int rc = sdr_create(&cfg, &bank_);
         if (rc != SDR_OK)
             return rc;
+        if (firstFrame_ != 0 && (rc = sdr_set_first_frame(bank_, firstFrame_)) != SDR_OK) {
+            Stop();
+            return rc;
+        }
         sampleRate_ = sampleRate;
         blockSize_ = blockSize;
         hop_ = sdr_hop(bank_);
         timing_ = FrameTiming{sampleRate, hop_};
+        // the receiver counts the bank's frames, and the stream clock starts where the frame before the first one ends
+        // (0 for a bank that starts at frame 0): time-outs and the once-a-second clean-ups measure from there
+        framesProcessed_ = sdr_total_frames(bank_);
+        streamClock_.Set(frameTime(framesProcessed_ - 1));
+        lastCleanup_ = lastPeaksCleanup_ = clock_ == &streamClock_ ? streamClock_.Now() : 0;
         maxBatchFrames_ = maxBatchFrames;
         sdr_set_center_frequency(bank_, 0, centerFrequency_);
         // results arrive in bulk, one sdr_poll per processed segment (no per-listener reads, no pipeline drain)
@@ -1112,7 +1125,7 @@ private:
             l->BeginFeed();
             for (int k = 0; k < lr.n_runes; k++) {
                 if (stream_clock)
-                    l->SetFeedTime(frameTime(r.rune_frames[lr.first_rune + k]));
+                    l->SetFeedTime(frameTime(host::widen_frame(r.rune_frames[lr.first_rune + k], r.first_frame)));
                 l->WriteRune(r.runes[lr.first_rune + k]);
             }
             l->EndFeed();
@@ -1212,7 +1225,7 @@ private:
     PeaksTable::RandFn rand_;
     PeaksTable::Policy policy_ = PeaksTable::ReferenceOrder;
     ListenerPool listeners_;
-    int64_t framesProcessed_ = 0, reportFrames_ = -1;
+    int64_t firstFrame_ = 0, framesProcessed_ = 0, reportFrames_ = -1;
     int64_t segmentsLaunched_ = 0;
     bool reports_ = false;
     std::vector<sdr_listener_report> resReports_;

@@ -7,6 +7,9 @@
 // Streams: Morse-like keying at random speeds with jitter, glitches, over-long marks, long silences (the abort check),
 // characters of more than eight symbols, plain noise; debounce thresholds 1 (pass-through), 2, 3, 5, 9, 70 and 200; the first batch of
 // every third stream starts inside the batch (sdr_attach_at's `first` > 0).
+// Then the same with the stream's first tick at bank frame 2^31 - 48 and at 2^32 - 96: the stages get the frame base as the
+// kernel does, modulo 2^32, the literal tick loop stamps every edge and rune with its 64-bit frame reduced likewise, and the
+// batches are cut on the crossing, one tick in front of it, one tick behind it, and at random around it.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -277,13 +280,16 @@ static void staged_batch(cw::Debouncer &deb, cw::DecoderState &dec, const std::v
         dec.lastState = state0 ^ ((n_edges - 1) & 1);
 }
 
-int main()
+// `streams` streams whose first tick is bank frame `origin`; returns the mismatches
+static long run(int64_t origin, int streams)
 {
     uint16_t table[cw::kMorseTableSize];
     cw::build_morse_table(table);
     static const int thresholds[] = {1, 2, 3, 5, 9, 70, 200, 3, 3, 2};
     long mismatches = 0, runes_total = 0, edges_total = 0, batches = 0;
-    for (int it = 0; it < 600; it++) {
+    long edges_before = 0, runes_before = 0, edges_behind = 0, runes_behind = 0;  // in front of / from the crossing on
+    const int crossing = (int)((((int64_t)1 << 31) - origin % ((int64_t)1 << 31)) % ((int64_t)1 << 31));  // the tick whose frame is a multiple of 2^31
+    for (int it = 0; it < streams; it++) {
         const int ticks = 3000 + (int)(rnd() % 20000);
         const std::vector<uint8_t> s = make_stream(ticks, it % 4);
         const int thr = thresholds[it % 10];
@@ -297,6 +303,17 @@ int main()
         bool first_batch = true;
         while (at < ticks) {
             int n = 1 + (int)(rnd() % ((it & 1) ? 700 : 9000));
+            if (origin && at < crossing + 2) {
+                // the cuts around the crossing, by stream: a batch ends on it and one of a single tick follows; a batch
+                // ends one tick in front of it and the next holds two; a batch ends one tick behind it; any cut
+                const int cut = (it >> 1) & 3;
+                if (cut == 0)
+                    n = at < crossing ? crossing - at : 1;
+                else if (cut == 1)
+                    n = at < crossing - 1 ? crossing - 1 - at : 2;
+                else if (cut == 2 && at <= crossing)
+                    n = crossing + 1 - at;
+            }
             if (n > ticks - at)
                 n = ticks - at;
             int first = 0;
@@ -313,15 +330,15 @@ int main()
                 if (e)
                     ref_eff[(size_t)(i >> 6)] |= 1ull << (i & 63);
                 if ((int32_t)e != rdec.lastState)
-                    ref_edges.push_back({(uint32_t)(at + i), e ? 1u : 0u});
-                rs.frame = (uint32_t)(at + i);
+                    ref_edges.push_back({(uint32_t)(origin + at + i), e ? 1u : 0u});
+                rs.frame = (uint32_t)(origin + at + i);
                 cw::decoder_tick(rdec, e, table, rs);
             }
             // the stages
             std::vector<uint64_t> eff;
             std::vector<Edge> edges;
             std::vector<Rec> runes;
-            staged_batch(sdeb, sdec, raw, first, (uint32_t)at, table, eff, edges, runes, ((it >> 2) & 1) != 0, ((it >> 3) & 1) != 0);
+            staged_batch(sdeb, sdec, raw, first, (uint32_t)(origin + at), table, eff, edges, runes, ((it >> 2) & 1) != 0, ((it >> 3) & 1) != 0);
             bool bad = false;
             if (eff != ref_eff) {
                 if (mismatches < 8)
@@ -363,10 +380,31 @@ int main()
             }
             runes_total += (long)rs.out.size();
             edges_total += (long)ref_edges.size();
+            for (const Edge &e : ref_edges)
+                ((int32_t)(e.frame - (uint32_t)(origin + crossing)) < 0 ? edges_before : edges_behind)++;
+            for (const Rec &r : rs.out)
+                ((int32_t)(r.frame - (uint32_t)(origin + crossing)) < 0 ? runes_before : runes_behind)++;
             batches++;
             at += n;
         }
     }
-    printf("%ld batches, %ld edges, %ld runes, mismatches %ld\n", batches, edges_total, runes_total, mismatches);
+    printf("from frame %lld: %ld batches, %ld edges, %ld runes, mismatches %ld\n", (long long)origin, batches, edges_total, runes_total, mismatches);
+    if (origin) {
+        printf("  crossing at tick %d: %ld edges and %ld runes in front of it, %ld and %ld from it on\n", crossing, edges_before, runes_before,
+               edges_behind, runes_behind);
+        if (!edges_before || !runes_before || !edges_behind || !runes_behind) {
+            printf("  a side of the crossing is empty\n");
+            mismatches++;
+        }
+    }
+    return mismatches;
+}
+
+int main()
+{
+    long mismatches = run(0, 600);
+    mismatches += run(((int64_t)1 << 31) - 48, 200);
+    mismatches += run(((int64_t)1 << 32) - 96, 200);
+    printf("in all: mismatches %ld\n", mismatches);
     return mismatches ? 1 : 0;
 }

@@ -1,6 +1,7 @@
 // Tests of the C++ host mirror (sdrainer_amd/csrc/host/rx.h), modelled on the reference's
 // rx/peaks_test.go and rx/listener_test.go.  `test_rx_host cpu` needs no GPU; `test_rx_host strain
-// <iq.f32> <rate> <N> <frames> <pool>` drives a strain-mode Receiver on the GPU and prints what it did
+// <iq.f32> <rate> <N> <frames> <pool> [policy silence attachment max_batch piece first_frame]` drives a strain-mode
+// Receiver on the GPU (from bank frame first_frame on: Receiver::SetFirstFrame -> sdr_set_first_frame) and prints what it did
 // as JSON for tests/test_host_mirror.py to compare with an oracle-driven simulation.
 #include <cassert>
 #include <cstdio>
@@ -244,7 +245,7 @@ struct PrintReporter : rx::Reporter {
 };
 
 static int run_strain(const char *path, int rate, int n, int frames, int pool, bool strongest = false, double silence = 1e9,
-                      double attachment = 1e9, int max_batch = 256, int piece = 0)
+                      double attachment = 1e9, int max_batch = 256, int piece = 0, long long origin = 0)
 {
     FILE *f = fopen(path, "rb");
     if (!f)
@@ -263,10 +264,15 @@ static int run_strain(const char *path, int rate, int n, int frames, int pool, b
     r.SetSilenceTimeout(silence);
     r.SetAttachmentTimeout(attachment);
     r.SetEdgeWidth(70 * n / 512);
+    // (argv[12]) the bank frame index of the first frame: Start hands it to sdr_set_first_frame before anything else
+    // touches the new bank, and every frame the receiver reports counts from it
+    r.SetFirstFrame(origin);
     if (r.Start(rate, n, max_batch) != SDR_OK) {
         fprintf(stderr, "Start failed: %s\n", sdr_last_error());
         return 3;
     }
+    if (sdr_total_frames(r.Bank()) != origin || r.FramesProcessed() != origin)
+        return 7;
     // error behaviour of IQData (rx/receiver.go:315-334)
     if (r.IQData(rate + 1, iq.data(), 2 * (size_t)n) != SDR_ERR_BAD_RATE || r.IQData(rate, iq.data(), 2 * (size_t)n - 2) != SDR_ERR_BAD_SIZE)
         return 4;
@@ -650,7 +656,8 @@ int main(int argc, char **argv)
     if (argc >= 7 && !strcmp(argv[1], "strain"))
         return run_strain(argv[2], atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), atoi(argv[6]),
                           argc >= 8 && !strcmp(argv[7], "strongest"), argc >= 9 ? atof(argv[8]) : 1e9,
-                          argc >= 10 ? atof(argv[9]) : 1e9, argc >= 11 ? atoi(argv[10]) : 256, argc >= 12 ? atoi(argv[11]) : 0);
+                          argc >= 10 ? atof(argv[9]) : 1e9, argc >= 11 ? atoi(argv[10]) : 256, argc >= 12 ? atoi(argv[11]) : 0,
+                          argc >= 13 ? atoll(argv[12]) : 0);
     if (argc >= 7 && !strcmp(argv[1], "decode"))
         return run_decode(argv[2], atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), atoll(argv[6]));
     fprintf(stderr, "usage: %s cpu | text | strain <iq.f32> <rate> <N> <frames> <pool>\n", argv[0]);

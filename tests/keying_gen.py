@@ -95,26 +95,28 @@ def stream(ticks, kind, rng, dits=None, symbols=None):
     return out
 
 
-def key_matrix(frames, kinds, seed, dits=None, symbols=None):
-    """uint8 [frames, len(kinds)]: LEAD silent frames, then every column its kind's stream (a generator per column, so that
+def key_matrix(frames, kinds, seed, dits=None, symbols=None, lead=LEAD):
+    """uint8 [frames, len(kinds)]: `lead` silent frames, then every column its kind's stream (a generator per column, so that
     a column does not depend on its neighbours)."""
     keys = np.zeros((frames, len(kinds)), np.uint8)
     for i, kind in enumerate(kinds):
-        keys[LEAD:, i] = stream(frames - LEAD, kind, np.random.default_rng([seed, i]), dits, symbols)
+        keys[lead:, i] = stream(frames - lead, kind, np.random.default_rng([seed, i]), dits, symbols)
     return keys
 
 
-def keyed_band(n, rate, keys, seed, amplitude=synth.TONE_AMPLITUDE, hop=None):
+def keyed_band(n, rate, keys, seed, amplitude=synth.TONE_AMPLITUDE, hop=None, lead=LEAD):
     """(float32 frames [F, 2N], None, the carriers' bins): what Case(bands=...) takes.  One carrier per column of keys [F, L]
     on synth.tone_bins (the last noise window kept free), hard-keyed per frame, built as synth.make_band builds its bands:
     the inverse FFT of a sparse spectrum plus synth.NOISE_SIGMA of noise.  The sample rate takes no part: the keying is given
     in frames.
     hop (below n, a divisor of it): keys has a row per hop; the rows are built at block size `hop` and flattened into one
     continuous stream float32 [F * hop, 2], as parity_tools.make_stream does - every carrier makes whole cycles per hop, and
-    bin i of the short transform is bin i * n / hop of the long one.  Frame f of the stream is rows f .. f + n / hop - 1."""
+    bin i of the short transform is bin i * n / hop of the long one.  Frame f of the stream is rows f .. f + n / hop - 1.
+    lead: the frames in front that must be silent (a caller that wants keying while the rolling means still fill - the
+    oracle and the bank agree there too, only the keying is not what was sent - passes 0 here and to key_matrix)."""
     del rate
     keys = np.asarray(keys, np.uint8)
-    assert not keys[:LEAD].any(), f"the first {LEAD} frames are silent"
+    assert not keys[:lead].any(), f"the first {lead} frames are silent"
     size = hop or n
     assert n % size == 0
     bins = synth.tone_bins(size, keys.shape[1], free_last_window=True)

@@ -32,8 +32,8 @@ import numpy as np
 from iq8_tools import to_f32 as iq8_to_float32
 from oracle import oracle as orc
 from sdrainer_amd import synth
-from parity_tools import (RATES, bits_equal, check_batch_polled, check_device_batch, decode, frames_of, listener_bins, make_stream,
-                          nan_equal_bits, sc16_to_float32, windowed)
+from parity_tools import (RATES, bits_equal, check_batch_polled, check_device_batch, decode, frames32, frames_of, listener_bins,
+                          make_stream, nan_equal_bits, sc16_to_float32, windowed)
 
 RATE = 2_000_000
 PATHS = ("device", "device_sc16", "device_cs8", "device_cu8", "staged", "staged_sc16", "kiwi", "graph", "graph_sc16")
@@ -66,6 +66,8 @@ class Case:
        ("batch", frames)                      an eager batch
        ("defer", frames, [(band, bin, s)])    a deferred batch; after its peaks, sdr_attach_at(band, bin, s) in order
        ("attach", band, bin) / ("detach", band, lid)   between batches
+       ("stop", band, lid)                    sdr_listener_stop between batches (with a hop or with trace: the hop-timed
+                                              decoder is stopped there, and what it writes is stamped with the frame before)
     (steps may also be a function of the carriers' bins per band, which exist once the input does)
 
     Per band (a value, or a list with one per band): peak threshold and centre frequency.  The sample rate, the edge width
@@ -90,12 +92,19 @@ class Case:
 
     Not run by any test yet, so not to be trusted before the first row that uses them: the staged paths with a hop below N
     (the sample range of _enqueue) and run_graph with windows (a window set before the capture, release and a new capture
-    when the next replay's window differs)."""
+    when the next replay's window differs).
+
+    first_frame: the bank frame index of the stream's first frame (sdr_set_first_frame before the first attach; a multiple
+    of 100).  Steps, spans and the oracle stay counted from 0; every frame number the bank hands out is expected shifted by
+    it - first_frame, chunk frames and total_frames as int64, edge and rune frames modulo 2^32 - and sdr_attach_at is given
+    shifted start frames.  frame_in_batch and whatever is no frame number are what they are at 0."""
 
     def __init__(self, n, n_bands, carriers, listeners, steps, seed, rate=RATE, free_last=True, max_listeners=None, total_frames=None,
                  *, edge=None, debounce=1, threshold=15.0, centers=None, path="device", bands=None, init_bins=None, max_peaks=1024,
-                 nan_ok=False, hop=None, pad=0, windows=None, trace=False):
+                 nan_ok=False, hop=None, pad=0, windows=None, trace=False, first_frame=0):
         assert path in PATHS, path
+        assert first_frame >= 0 and first_frame % 100 == 0, "the first frame is a multiple of the cumulation size"
+        self.first_frame = first_frame
         self.n, self.n_bands, self.rate, self.path, self.nan_ok = n, n_bands, rate, path, nan_ok
         self.hop, self.step, self.pad, self.trace = hop or 0, hop or n, pad, trace
         assert self.step == n or path.startswith("device") or path in ("staged", "staged_sc16"), f"{path} input takes no hop below N"
@@ -145,23 +154,49 @@ class Case:
         assert len(self.windows) == len(self.spans), "one window (or None) per batch"
         self.max_frames = max(e - a for a, e in self.spans)
         late = sum(1 for s in steps if s[0] == "attach") + sum(len(s[2]) for s in steps if s[0] == "defer")
-        self.max_listeners = max_listeners or max(1, max(len(b) for b in self.init_bins) + late)
+        self.max_listeners = max_listeners or max(1, max(len(b) for b in self.init_bins) + late)  # (a reused slot needs none: an upper bound)
         # every listener of every band: (attached at frame, detached at frame or None)
         self.life = [[(0, None) for _ in bins] for bins in self.init_bins]
         self.bins = [list(bins) for bins in self.init_bins]
+        # ... and the bank's id of each: the lowest free slot at its attach (ListenerPool.BindNext), so a listener attached
+        # behind a detach reuses an id, while the oracle numbers its listeners as they come; heir: the listener that took
+        # its slot over, or None
+        self.stops = {}  # (band, listener): the frames in front of which it is stopped
+        self.slot = [list(range(len(bins))) for bins in self.init_bins]
+        self.heir = [[None] * len(bins) for bins in self.init_bins]
+        free = [[] for _ in self.init_bins]
+
+        def bind(band, bn, at):
+            self.bins[band].append(bn)
+            self.life[band].append((at, None))
+            self.heir[band].append(None)
+            if free[band]:
+                sl = min(free[band])
+                free[band].remove(sl)
+                owner = max(i for i, x in enumerate(self.slot[band]) if x == sl)
+                self.heir[band][owner] = len(self.slot[band])
+            else:
+                sl = len(set(self.slot[band]))
+            self.slot[band].append(sl)
         pos = 0
         for s in steps:
             if s[0] == "attach":
-                self.bins[s[1]].append(s[2])
-                self.life[s[1]].append((pos, None))
+                bind(s[1], s[2], pos)
             elif s[0] == "detach":
                 self.life[s[1]][s[2]] = (self.life[s[1]][s[2]][0], pos)
+                free[s[1]].append(self.slot[s[1]][s[2]])
+            elif s[0] == "stop":
+                assert self.timed and pos > self.life[s[1]][s[2]][0], "a stop needs the hop-timed decoders, behind the listener's first frame"
+                self.stops.setdefault((s[1], s[2]), []).append(pos)
             else:
                 for band, bn, at in s[2] if s[0] == "defer" else []:
-                    assert pos <= at < pos + s[1], f"band {band}: attach_at frame {at} outside its batch"
-                    self.bins[band].append(bn)
-                    self.life[band].append((at, None))
+                    assert pos <= at <= pos + s[1], f"band {band}: attach_at frame {at} outside its batch (or the frame behind it)"
+                    bind(band, bn, at)
                 pos += s[1]
+        # While no attach follows a detach on a band - every caller from before slots were reused - the bank's ids are the
+        # oracle's and nobody has an heir: gone(), check_end and every attach and detach then do what they always did.
+        reused = any(h is not None for heirs in self.heir for h in heirs)
+        assert reused or all(sl == list(range(len(sl))) for sl in self.slot), "without a reused slot the ids are the oracle's"
 
     @classmethod
     def of_streams(cls, n, hop, calls, n_bands, tones, listeners, sc16, seed, windows=None, pad=0):
@@ -244,7 +279,7 @@ class Case:
         if self.timed:  # (text, 12-value state, the frame that wrote each rune) of every listener, ticked from its first frame on
             def timed(b, lid):
                 start = self.life[b][lid][0]
-                text, state, at = decode(self.outs[b]["deb"][start:, lid], self.rate, self.step)
+                text, state, at = decode(self.outs[b]["deb"][start:, lid], self.rate, self.step, [f - start for f in self.stops.get((b, lid), ())])
                 return text, state, at + start
             self.decs = [[timed(b, lid) for lid in range(out["deb"].shape[1])] for b, out in enumerate(self.outs)]
 
@@ -268,6 +303,9 @@ class Case:
                          hop=self.hop)
         assert bank.hop == self.step, f"the bank's hop is {bank.hop}, not {self.step}"
         bank.set_stream((stream or torch.cuda.current_stream()).cuda_stream)
+        if self.first_frame:
+            bank.set_first_frame(self.first_frame)
+        assert bank.total_frames == self.first_frame, f"a new bank at frame {bank.total_frames}, not {self.first_frame}"
         for b in range(self.n_bands):
             bank.set_center_frequency(b, self.centers[b])
             if self.threshold[b] != 15.0:
@@ -275,11 +313,16 @@ class Case:
             for i, bn in enumerate(self.init_bins[b]):
                 assert bank.attach(b, int(bn)) == i, f"band {b}: listener {i} got another id"
         bank.enable_results(True)
+        self.begin()
+        return bank
+
+    def begin(self):
+        """What check_polled collects, emptied: new_bank calls it; so does a test that feeds the stream to something else
+        (a group) and holds its deliveries to check_polled."""
         self.text = [["" for _ in bins] for bins in self.bins]
         self.rune_at = [[[] for _ in bins] for bins in self.bins]
         self.edges = self.peaks = 0
         self.window = None  # (a bank that never had a window is never told about one)
-        return bank
 
     def set_window(self, bank, k):
         """Batch k's window, if it is not the one the bank has."""
@@ -288,21 +331,22 @@ class Case:
             bank.set_window(self.window)
 
     def gone(self, a):
-        """(band, listener) pairs detached before frame a."""
-        return [(b, lid) for b in range(self.n_bands) for lid, (_, d) in enumerate(self.life[b]) if d is not None and d <= a]
+        """(band, listener) pairs detached before frame a whose slot nobody has taken over by then."""
+        return [(b, lid) for b in range(self.n_bands) for lid, (_, d) in enumerate(self.life[b])
+                if d is not None and d <= a and (self.heir[b][lid] is None or self.life[b][self.heir[b][lid]][0] > a)]
 
     def check_polled(self, res, a, e):
         """One delivered batch against the stitched oracle stream, for the listeners live in it; detached ones deliver nothing."""
         ne, npk = check_batch_polled(res, self.outs, a, e, None, self.text, self.n_bands,
                                      live=[self.live(b, a, e) for b in range(self.n_bands)], gone=self.gone(a), rune_at=self.rune_at,
-                                     max_peaks=self.max_peaks)
+                                     max_peaks=self.max_peaks, first_frame=self.first_frame, slot=self.slot)
         self.edges += ne
         self.peaks += npk
 
     def check_device(self, bank, a, e, k, cumulations=True):
         """What the last batch left on the device: frame records, keying bits, cumulation rows; with trace, the tap."""
         check_device_batch(bank, self.outs, a, e, self.n_bands, [self.live(b, a, e) for b in range(self.n_bands)], k, cumulations,
-                           same=nan_equal_bits if self.nan_ok else None, max_peaks=self.max_peaks)
+                           same=nan_equal_bits if self.nan_ok else None, max_peaks=self.max_peaks, slot=self.slot)
         if self.trace:
             self.check_trace(bank, a, e, k)
 
@@ -313,7 +357,7 @@ class Case:
         for b in range(self.n_bands):
             out = self.outs[b]
             for lid in self.live(b, a, e):
-                v, raw, deb = bank.read_trace(b, lid)
+                v, raw, deb = bank.read_trace(b, self.slot[b][lid])
                 s = max(self.life[b][lid][0] - a, 0)  # (a listener bound inside the batch: nothing was handed to it before)
                 assert same(v[s:], out["values"][a + s:e, lid].copy()), f"band {b} listener {lid} batch {k} tap values"
                 assert np.array_equal(raw[s:], out["raw"][a + s:e, lid]), f"band {b} listener {lid} batch {k} raw bits"
@@ -329,9 +373,12 @@ class Case:
             for lid in range(len(self.bins[b])):
                 text, state = self.decs[b][lid][:2] if self.timed else (self.refs[b].text(lid), self.refs[b].decoder_state(lid))
                 assert self.text[b][lid] == text, f"band {b} listener {lid} text"
-                assert np.array_equal(bank.read_decoder_state(b, lid), state), f"band {b} listener {lid} state"
+                if self.heir[b][lid] is None:  # (else the slot holds its heir's decoder)
+                    assert np.array_equal(bank.read_decoder_state(b, self.slot[b][lid]), state), f"band {b} listener {lid} state"
                 if self.timed:
-                    assert np.array_equal(np.array(self.rune_at[b][lid], np.int64), self.decs[b][lid][2]), f"band {b} listener {lid} rune frames"
+                    assert np.array_equal(np.array(self.rune_at[b][lid], np.int64), frames32(self.decs[b][lid][2], self.first_frame)), \
+                        f"band {b} listener {lid} rune frames"
+        assert bank.total_frames == self.first_frame + self.total, f"{bank.total_frames} frames after {self.total} from {self.first_frame}"
         assert bank.read_drop_counters() == (0, 0), "runes or edges dropped"
         if activity:
             n_carriers = sum(len(c) for c in self.carriers)
@@ -410,15 +457,18 @@ class Case:
             self.check_polled(res, a, e)
             if last:
                 self.check_device(bank, a, e, i)
-        slots = [len(bins) for bins in self.init_bins]  # (no attach follows a detach on a band: ids are the oracle's)
+        slots = [len(bins) for bins in self.init_bins]  # the next listener of each band, in the oracle's numbering
         for s in self.steps:
             if s[0] == "attach":
                 got = bank.attach(s[1], int(s[2]))
-                assert got == slots[s[1]], f"band {s[1]}: attach gave listener {got}"
+                assert got == self.slot[s[1]][slots[s[1]]], f"band {s[1]}: attach gave listener {got}"
                 slots[s[1]] += 1
                 continue
             if s[0] == "detach":
-                bank.detach(s[1], s[2])
+                bank.detach(s[1], self.slot[s[1]][s[2]])
+                continue
+            if s[0] == "stop":
+                bank.listener_stop(s[1], self.slot[s[1]][s[2]])
                 continue
             a, e = pos, pos + s[1]
             self.set_window(bank, k)
@@ -426,10 +476,10 @@ class Case:
                 bank.defer_listen(True)
                 batch = self._enqueue(bank, a, e)
                 pk = bank.poll_peaks(wait=True)
-                assert pk["first_frame"] == a, f"batch {k}: peaks of frame {pk['first_frame']}"
+                assert pk["first_frame"] == self.first_frame + a, f"batch {k}: peaks of frame {pk['first_frame']}"
                 for band, bn, at in s[2]:
-                    got = bank.attach_at(band, int(bn), at)
-                    assert got == slots[band], f"band {band}: attach_at gave listener {got}"
+                    got = bank.attach_at(band, int(bn), self.first_frame + at)
+                    assert got == self.slot[band][slots[band]], f"band {band}: attach_at gave listener {got}"
                     slots[band] += 1
                 bank.process_listen()
                 bank.defer_listen(False)
@@ -483,7 +533,7 @@ class Case:
                     self.check_polled(res, a, e)
                     k += 1
                 bank.sync()
-                assert bank.total_frames == pos, f"{bank.total_frames} frames after {pos}"
+                assert bank.total_frames == self.first_frame + pos, f"{bank.total_frames} frames after {pos} from {self.first_frame}"
                 self.check_device(bank, run[-1][0], run[-1][1], k - 1, cumulations=False)
                 run = []
                 continue
@@ -495,9 +545,9 @@ class Case:
                 captured = False
             if s[0] == "attach":
                 got = bank.attach(s[1], int(s[2]))
-                assert got == slots[s[1]], f"band {s[1]}: attach gave listener {got}"
+                assert got == self.slot[s[1]][slots[s[1]]], f"band {s[1]}: attach gave listener {got}"
                 slots[s[1]] += 1
             else:
-                bank.detach(s[1], s[2])
+                bank.detach(s[1], self.slot[s[1]][s[2]])
         self.check_end(bank, min_edges, activity)
         return bank

@@ -127,15 +127,21 @@ def listener_bins(n, carriers, count):
     return out[:count]
 
 
-def decode(deb_col, rate, hop):
+def decode(deb_col, rate, hop, stops=()):
     """oracle.Decoder(rate, hop) over one listener's debounced bits: text, state, and the tick that wrote each rune.  What
     means time follows the hop: the bank's decoders are cw.NewDecoder(sampleRate, hop), the oracle receiver's are built
-    from the block size."""
+    from the block size.  stops: ticks in front of which Decoder.stop() is called (sdr_listener_stop between two batches);
+    what it writes is stamped with the tick before, the last one the listener took."""
     d = orc.Decoder(rate, hop)
     d.reset()
     L, col = orc.lib(), np.ascontiguousarray(deb_col, np.uint8)
     at, have = [], 0
     for f in range(len(col)):
+        if f in stops:
+            d.stop()
+            now = L.orc_decoder_out_len(d._h)
+            at += [f - 1] * (now - have)
+            have = now
         L.orc_decoder_tick(d._h, int(col[f]))
         now = L.orc_decoder_out_len(d._h)
         at += [f] * (now - have)
@@ -175,31 +181,44 @@ def peaks_of(res, ch):
             for p in res["peaks"][ch["first_peak"]:ch["first_peak"] + ch["n_peaks"]]]
 
 
-def check_batch_polled(res, outs, a, e, tones, text, n_bands, live=None, gone=(), rune_at=None, max_peaks=None, edges_dropped=0):
+def frames32(frames, first_frame=0):
+    """Stream frames as a bank that started at first_frame hands them out in its 32-bit fields (sdr_edge.frame,
+    rune_frames): shifted, then reduced modulo 2^32.  int64, so that it compares with either."""
+    return (np.asarray(frames, np.int64) + int(first_frame)) & 0xFFFFFFFF
+
+
+def check_batch_polled(res, outs, a, e, tones, text, n_bands, live=None, gone=(), rune_at=None, max_peaks=None, edges_dropped=0,
+                       first_frame=0, slot=None):
     """One polled batch (sdr_poll: what bench.py's consumer thread receives) against the oracle's whole-run output.
     live[band]: the listener ids to check (default: 0 .. tones - 1); gone: (band, listener) pairs detached before the
     batch, which must deliver nothing.  The runes go to text[band][listener], their frames to rune_at (if given).
     max_peaks: the bank's (None: it holds every run) - a cumulation delivers the oracle's first max_peaks peaks and says in
-    peaks_found how many runs there were; every chunk's first_peak follows on the one before.  Returns the edges and peaks
-    delivered."""
+    peaks_found how many runs there were; every chunk's first_peak follows on the one before.  first_frame: the bank's
+    (sdr_set_first_frame); a, e and the oracle count from 0, the batch's first_frame and chunk frames are expected shifted
+    by it, edge frames shifted and modulo 2^32 (frames32), and rune_at collects the 32-bit rune frames as delivered.
+    slot[band][listener]: the bank's id of the oracle's listener (default: the same; they differ once an attach has reused a
+    detached listener's id).  Returns the edges and peaks delivered."""
     k = res["batch_index"]
-    assert res["first_frame"] == a and res["n_frames"] == e - a, f"batch {k}: frames {res['first_frame']} + {res['n_frames']}, not [{a}, {e})"
+    sl = (lambda band, lid: lid) if slot is None else (lambda band, lid: slot[band][lid])
+    assert res["first_frame"] == first_frame + a and res["n_frames"] == e - a, \
+        f"batch {k}: frames {res['first_frame']} + {res['n_frames']}, not [{a}, {e}) from {first_frame}"
     assert res["runes_dropped"] == 0 and res["edges_dropped"] == edges_dropped, f"batch {k}: runes or edges dropped"
     by = {(int(r["band"]), int(r["listener"])): r for r in res["listeners"]}
     for key in gone:
-        r = by.get(key)
+        r = by.get((key[0], sl(*key)))
         assert r is None or (r["n_edges"] == 0 and r["n_runes"] == 0), f"band {key[0]} listener {key[1]} batch {k}: delivers after its detach"
     n_edges = 0
     for band in range(n_bands):
         out = outs[band]
         for lid in (range(tones) if live is None else live[band]):
             trans, states = transitions(out["deb"][:, lid], a, e)
-            r = by.get((band, lid))
+            r = by.get((band, sl(band, lid)))
             if r is None:
                 assert len(trans) == 0, f"band {band} listener {lid} batch {k}: edges missing"
                 continue
             ed = res["edges"][r["first_edge"]:r["first_edge"] + r["n_edges"]]
-            assert np.array_equal(ed["frame"], trans) and np.array_equal(ed["state"], states), f"band {band} listener {lid} batch {k} edges"
+            assert np.array_equal(ed["frame"].astype(np.int64), frames32(trans, first_frame)) and np.array_equal(ed["state"], states), \
+                f"band {band} listener {lid} batch {k} edges"
             n_edges += len(trans)
             runes = slice(r["first_rune"], r["first_rune"] + r["n_runes"])
             text[band][lid] += "".join(chr(int(x)) for x in res["runes"][runes])
@@ -210,7 +229,8 @@ def check_batch_polled(res, outs, a, e, tones, text, n_bands, live=None, gone=()
     for ch in res["chunks"]:
         band = int(ch["band"])
         out = outs[band]
-        gc = list(out["peak_frames"]).index(int(ch["frame"]))
+        assert ch["frame"].dtype == np.int64, "sdr_chunk_result.frame is 64-bit"
+        gc = list(out["peak_frames"]).index(int(ch["frame"]) - first_frame)
         got, want = peaks_of(res, ch), out["peaks"][gc]
         stored = len(want) if max_peaks is None else min(len(want), max_peaks)
         assert ch["first_peak"] == n_peaks, f"band {band} batch {k} cumulation {gc}: first_peak {ch['first_peak']} after {n_peaks} peaks"
@@ -225,11 +245,12 @@ def check_batch_polled(res, outs, a, e, tones, text, n_bands, live=None, gone=()
     return n_edges, n_peaks
 
 
-def check_device_batch(bank, outs, a, e, n_bands, live, k, cumulations=True, same=None, max_peaks=None):
+def check_device_batch(bank, outs, a, e, n_bands, live, k, cumulations=True, same=None, max_peaks=None, slot=None):
     """What the last batch [a, e) left on the device against the oracle: frame records, the keying bits of the listeners
     live[band], and (cumulations) every cumulation row it completed with its peaks (max_peaks: the bank's, by default read
     from it - sdr_read_peaks hands out the oracle's first max_peaks peaks and the number of runs found).  same: how two
-    float arrays compare (default: bit for bit; streams that hold NaN pass one that lets NaN equal NaN)."""
+    float arrays compare (default: bit for bit; streams that hold NaN pass one that lets NaN equal NaN).  slot: as in
+    check_batch_polled."""
     same = same or bits_equal
     max_peaks = bank.cfg.max_peaks if max_peaks is None else max_peaks
     for b in range(n_bands):
@@ -237,7 +258,8 @@ def check_device_batch(bank, outs, a, e, n_bands, live, k, cumulations=True, sam
         for f in REC_FIELDS:
             assert same(recs[f], outs[b]["frames"][f][a:e].copy()), f"band {b} batch {k} field {f}"
         for lid in live[b]:
-            assert np.array_equal(bank.read_keying_bits(b, lid), outs[b]["deb"][a:e, lid]), f"band {b} listener {lid} batch {k}"
+            assert np.array_equal(bank.read_keying_bits(b, lid if slot is None else slot[b][lid]), outs[b]["deb"][a:e, lid]), \
+                f"band {b} listener {lid} batch {k}"
         if not cumulations:
             continue
         for c in range(bank.last_batch_chunks):

@@ -273,6 +273,42 @@ def test_strain_mode_finite_timeouts_per_frame(exe, tmp_path):
 
 
 @pytest.mark.gpu
+def test_strain_mode_across_frame_2_to_the_32(exe, tmp_path):
+    """The same scenario on a bank whose first frame is 2^32 - 96 (Receiver::SetFirstFrame -> sdr_set_first_frame), with the
+    stream clock: rune frames arrive modulo 2^32 and are widened against the batch's first_frame (host/delivery.h
+    widen_frame) before they become feed times.  The silence time-out, 2.5 s, is shorter than the run and longer than the
+    gaps between a station's runes: a rune stamped 2^32 ticks in the past would time its listener out at once.  Listeners,
+    spots, time-outs and attachments are those of the run from frame 0 - and of the per-frame simulation on the oracle -
+    with every reported frame shifted."""
+    from sdrainer_amd import synth
+
+    origin = 2 ** 32 - 96
+    rate, n, pool, tones = 48000, 512, 2, 4
+    frames = 1900
+    iq, bins, _ = synth.make_band(frames, rate, n, tones, seed=31)
+    quiet, _, _ = synth.make_band(frames, rate, n, 0, seed=32)
+    iq[1200:] = quiet[1200:]
+    silence, attachment = 2.5, 6.3
+    path = tmp_path / "iq.f32"
+    iq.astype(np.float32).tofile(path)
+    runs = []
+    for first in (0, origin):
+        out = subprocess.run([exe, "strain", str(path), str(rate), str(n), str(frames), str(pool), "linear", str(silence),
+                              str(attachment), "256", "0", str(first)], capture_output=True, text=True)
+        assert out.returncode == 0, out.stdout + out.stderr
+        runs.append(json.loads(out.stdout))
+    plain, moved = runs
+    events, event_frames, live, sessions = _simulate_strain(iq, rate, n, pool, silence, attachment, 70)
+    assert len([e for e in events if e[0] == "-"]) >= 3 and sum(len(l["text"]) for l in live + sessions) > 20, events
+    assert plain["frames"] == frames and plain["events"] == events and plain["event_frames"] == event_frames
+    assert moved["frames"] == origin + frames
+    assert moved["events"] == events, f"first event that differs: {next(((i, a, b) for i, (a, b) in enumerate(zip(moved['events'] + [None] * len(events), events + [None] * len(moved['events']))) if a != b), None)}"
+    assert moved["event_frames"] == [origin + f for f in event_frames]
+    assert moved["listeners"] == plain["listeners"] and moved["callsigns"] == plain["callsigns"]
+    assert any(f > 96 for f in event_frames)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("silence,attachment", [(1e9, 1e9), (2.5, 6.3)])
 def test_strain_mode_long_segments_decide_like_one_cumulation_at_a_time(exe, tmp_path, silence, attachment):
     """Discovery over long segments (rx.h discoverAhead: the spectral half of up to 1024 frames first, the decisions of

@@ -331,7 +331,9 @@ def test_staged_listener_chain_matches_literal_ticks(tmp_path):
     on the CPU, tick by tick: same debounced bits, edges, runes, rune frames, and the same debouncer and decoder state at
     the end of every batch - 600 streams (keyed with jitter, glitches, over-long marks, long silences, over-long
     characters, plain noise) cut into batches of random length, debounce thresholds 1 ... 200, listeners that start
-    inside a batch."""
+    inside a batch.  Then 200 streams each whose first tick is bank frame 2^31 - 48 and 2^32 - 96, the frame base handed to the
+    stages modulo 2^32 as the kernel gets it, batches cut on and around the crossing: the edges' and runes' frames equal the
+    literal loop's modulo 2^32, with edges and runes on both sides."""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -341,6 +343,9 @@ def test_staged_listener_chain_matches_literal_ticks(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "mismatches 0" in out.stdout and " 0 runes" not in out.stdout and " 0 edges" not in out.stdout
+    assert out.stdout.count("mismatches 0\n") == 4 and "in all: mismatches 0" in out.stdout, out.stdout
+    assert "from frame 2147483600:" in out.stdout and "crossing at tick 48:" in out.stdout
+    assert "from frame 4294967200:" in out.stdout and "crossing at tick 96:" in out.stdout
 
 
 def test_cumulation_bound_is_an_upper_bound(tmp_path):
