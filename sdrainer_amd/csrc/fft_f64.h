@@ -494,77 +494,101 @@ SDR_HD inline int input_sample(int t, int m)
 // Input staging through LDS.  Pass 0 wants lane neighbours 32 bytes apart in memory at best (make_layout),
 // which costs the texture unit four times the cache-line look-ups of a contiguous read.  So the frame is
 // first copied global -> LDS by LDS-DMA (global_load_lds_dwordx4: no registers, each wave instruction one
-// contiguous 1 KB row of 128 samples) and then read from LDS in the pass-0 layout.  LDS-DMA writes lane l's
-// 16 bytes at row base + 16*l, so the image is shaped through the SOURCE address: lane p of row r fetches
-// granule g = in_granule(p, r) (a granule = 2 samples = 16 bytes); the XOR swizzle spreads the rows and
-// row halves that the 32 lanes of a ds_read_b64 group touch over the LDS banks.
-//   sample n  ->  row r = n >> 7, granule g = (n >> 1) & 63, byte address r*1024 + in_pos(g, r)*16 + (n & 1)*8
+// contiguous 1 KB row) and then read from LDS in the pass-0 layout.  LDS-DMA writes lane l's 16 bytes at row
+// base + 16*l, so the image is shaped through the SOURCE address: lane p of row r fetches granule
+// g = granule(p, r) (a granule = 16 bytes = 2^LOGS samples); the XOR swizzle spreads the rows and row parts that
+// the 32 lanes of an LDS read group touch over the LDS banks.
+//   sample n  ->  row r = n >> (6 + LOGS), granule g = (n >> LOGS) & 63,
+//                 byte address r*1024 + pos(g, r)*16 + (n & (2^LOGS - 1)) * (16 >> LOGS)
+// One image per input format, InImage<LOGN, LOGS, RULE>: float32 here (LOGS = 1: 128 samples per row, read with
+// ds_read_b64, 32 lanes over 32 eight-byte bank pairs), sc16.h (LOGS = 2) and iq8.h (LOGS = 3), each with what its reads
+// need from the banks.  RULE::make() says which bit each of three position bits is XORed with.
 // ---------------------------------------------------------------------------------------------
 struct InSwz {
-    int src[3];  // position bit 1+k is XORed with: -1 nothing, 0..5 granule bit, 8+j row bit j
+    int first;   // the swizzled position bits are first, first + 1, first + 2
+    int src[3];  // position bit first + k is XORed with: -1 nothing, 0..5 granule bit, 8+j row bit j
 };
 
-template <int LOGN>
-SDR_HD constexpr InSwz make_in_swz()
-{
-    const Layout L0 = make_layout<LOGN>(0);
-    InSwz z{{-1, -1, -1}};
-    for (int k = 0; k < 3; k++) {
-        const int nb = LOGN - 1 - L0.tbit[2 + k];  // sample-number bit behind lane bit 2+k
-        if (nb >= 7)
-            z.src[k] = 8 + (nb - 7);
-        else if (nb - 1 != 1 + k)
-            z.src[k] = nb - 1;
+// The rule of the float32 and sc16 images.  Pass 0's lane bits 0 and 1 are sample bits 0 and 1, which lie inside the
+// granule or (float32: sample bit 1) on position bit 0; position bit first + k pairs with lane bit 2 + k and is XORed
+// with the sample bit behind it, unless that is the bit a linear image has there.
+template <int LOGN, int LOGS>
+struct PairedSwz {
+    static_assert(LOGS == 1 || LOGS == 2, "sample bits 0 and 1 must end below position bit `first`");
+    SDR_HD static constexpr InSwz make()
+    {
+        const Layout L0 = make_layout<LOGN>(0);
+        InSwz z{2 - LOGS, {-1, -1, -1}};
+        for (int k = 0; k < 3; k++) {
+            const int nb = LOGN - 1 - L0.tbit[2 + k];  // sample-number bit behind lane bit 2+k
+            if (nb >= 6 + LOGS)
+                z.src[k] = 8 + (nb - (6 + LOGS));
+            else if (nb - LOGS != z.first + k)
+                z.src[k] = nb - LOGS;
+        }
+        return z;
     }
-    return z;
-}
+};
 
-template <int LOGN>
-SDR_HD constexpr bool in_swz_solvable()
-{
-    const InSwz z = make_in_swz<LOGN>();
-    for (int k = 0; k < 3; k++)
-        if (z.src[k] >= 0 && z.src[k] < 8 && z.src[k] <= 1 + k)
-            return false;  // a position bit may only depend on higher granule bits (in_granule solves downwards)
-    return true;
-}
+template <int LOGN, int LOGS, class RULE = PairedSwz<LOGN, LOGS>>
+struct InImage {
+    static constexpr int SAMPLE_BYTES = 16 >> LOGS;
+    static constexpr int ROW_SAMPLES = 64 << LOGS;                // one 1 KB row
+    static constexpr int ROWS = (1 << LOGN) / ROW_SAMPLES;        // of the image
+    static constexpr int ROWS_PER_WAVE = Plan<LOGN>::R >> LOGS;   // each wave of the workgroup fetches (N = 512: one wave)
+    static_assert(ROWS_PER_WAVE >= 1 && ROWS_PER_WAVE * (Plan<LOGN>::T / 64) == ROWS, "the waves' rows cover the frame exactly");
 
-template <int LOGN>
-SDR_HD inline int in_pos(int g, int r)
-{
-    constexpr InSwz Z = make_in_swz<LOGN>();
-    int p = g;
-    for (int k = 0; k < 3; k++) {
-        if (Z.src[k] >= 8)
-            p ^= ((r >> (Z.src[k] - 8)) & 1) << (1 + k);
-        else if (Z.src[k] >= 0)
-            p ^= ((g >> Z.src[k]) & 1) << (1 + k);
+    SDR_HD static constexpr bool solvable()
+    {
+        const InSwz z = RULE::make();
+        for (int k = 0; k < 3; k++)
+            if (z.src[k] >= 0 && z.src[k] < 8 && z.src[k] <= z.first + k)
+                return false;  // a position bit may only depend on higher granule bits (granule() solves downwards)
+        return true;
     }
-    return p;
-}
 
-template <int LOGN>
-SDR_HD inline int in_granule(int p, int r)
-{
-    static_assert(in_swz_solvable<LOGN>(), "input swizzle is not triangular");
-    constexpr InSwz Z = make_in_swz<LOGN>();
-    int g = p;
-    for (int k = 2; k >= 0; k--) {
-        if (Z.src[k] >= 8)
-            g ^= ((r >> (Z.src[k] - 8)) & 1) << (1 + k);
-        else if (Z.src[k] >= 0)
-            g ^= ((g >> Z.src[k]) & 1) << (1 + k);  // bit src[k] > 1+k is final already
+    SDR_HD static inline int pos(int g, int r)
+    {
+        constexpr InSwz Z = RULE::make();
+        int p = g;
+        for (int k = 0; k < 3; k++) {
+            if (Z.src[k] >= 8)
+                p ^= ((r >> (Z.src[k] - 8)) & 1) << (Z.first + k);
+            else if (Z.src[k] >= 0)
+                p ^= ((g >> Z.src[k]) & 1) << (Z.first + k);
+        }
+        return p;
     }
-    return g;
-}
 
-// byte address in the staging image of sample n
+    // the granule lane p of row r fetches (the inverse of pos)
+    SDR_HD static inline int granule(int p, int r)
+    {
+        static_assert(solvable(), "input swizzle is not triangular");
+        constexpr InSwz Z = RULE::make();
+        int g = p;
+        for (int k = 2; k >= 0; k--) {
+            if (Z.src[k] >= 8)
+                g ^= ((r >> (Z.src[k] - 8)) & 1) << (Z.first + k);
+            else if (Z.src[k] >= 0)
+                g ^= ((g >> Z.src[k]) & 1) << (Z.first + k);  // bit src[k] > first + k is final already
+        }
+        return g;
+    }
+
+    // byte address of sample n in the image (linear over GF(2): thread and slot parts of n combine by XOR)
+    SDR_HD static inline int lds_byte(int n)
+    {
+        const int r = n >> (6 + LOGS), g = (n >> LOGS) & 63;
+        return r * 1024 + pos(g, r) * 16 + (n & ((1 << LOGS) - 1)) * SAMPLE_BYTES;
+    }
+};
 template <int LOGN>
-SDR_HD inline int in_lds_byte(int n)
-{
-    const int r = n >> 7, g = (n >> 1) & 63;
-    return r * 1024 + in_pos<LOGN>(g, r) * 16 + (n & 1) * 8;
-}
+using InImageF32 = InImage<LOGN, 1>;
+// the float32 image's functions by the names tests/emu audits them under
+template <int LOGN>
+SDR_HD inline int in_granule(int p, int r) { return InImageF32<LOGN>::granule(p, r); }
+template <int LOGN>
+SDR_HD inline int in_lds_byte(int n) { return InImageF32<LOGN>::lds_byte(n); }
 
 // Pass 0 input: slot m <- x[input_sample(t, m)], widened to float64
 // (dsp/fft.go:59-69 setSamplesFromIQ).

@@ -42,93 +42,48 @@ SDR_HD inline float im_of(uint32_t w, Format f) { return to_f32(((w ^ f.flip) >>
 // + 16 l, so the swizzle is applied through the SOURCE address.
 //   sample n  ->  row r = n >> 9, granule g = (n >> 3) & 63, byte r*1024 + pos(g, r)*16 + (n & 7)*2
 // Every source bit is a granule bit above 2 (N <= 16384: the highest lane-held sample bit is 8, granule bit 5), so the map
-// is triangular and its own inverse is found downwards, as in sc16.h.
+// is triangular and its own inverse is found downwards: pos, granule and lds_byte are fft64::InImage's (fft_f64.h "Input
+// staging"), with eight samples per granule and the rule below in place of the other two images' pairing.
 // ---------------------------------------------------------------------------------------------
-struct Swz {
-    int src[3];  // position bit k is XORed with: -1 nothing, 0..5 granule bit, 8+j row bit j
+// The rule: which bit each position bit is XORed with (fft64::InSwz).
+template <int LOGN>
+struct FirstFreeSwz {
+    SDR_HD static constexpr fft64::InSwz make()
+    {
+        const fft64::Layout L0 = fft64::make_layout<LOGN>(0);
+        fft64::InSwz z{0, {-1, -1, -1}};
+        bool taken[3] = {false, false, false};
+        int nbs[3] = {0, 0, 0};
+        for (int k = 0; k < 3; k++) {
+            nbs[k] = LOGN - 1 - L0.tbit[2 + k];  // sample-number bit behind lane bit 2+k
+            if (nbs[k] >= 3 && nbs[k] <= 5)
+                taken[nbs[k] - 3] = true;  // sits on a position bit of the linear image already
+        }
+        for (int k = 0; k < 3; k++) {
+            if (nbs[k] <= 5)
+                continue;  // (2: dword bit 1, inside the granule)
+            int j = 0;
+            while (j < 3 && taken[j])
+                j++;
+            if (j == 3)
+                continue;  // (cannot happen: three lane bits, three position bits)
+            taken[j] = true;
+            z.src[j] = nbs[k] >= 9 ? 8 + (nbs[k] - 9) : nbs[k] - 3;
+        }
+        return z;
+    }
 };
 
 template <int LOGN>
-SDR_HD constexpr Swz make_swz()
-{
-    const fft64::Layout L0 = fft64::make_layout<LOGN>(0);
-    Swz z{{-1, -1, -1}};
-    bool taken[3] = {false, false, false};
-    int nbs[3] = {0, 0, 0};
-    for (int k = 0; k < 3; k++) {
-        nbs[k] = LOGN - 1 - L0.tbit[2 + k];  // sample-number bit behind lane bit 2+k
-        if (nbs[k] >= 3 && nbs[k] <= 5)
-            taken[nbs[k] - 3] = true;  // sits on a position bit of the linear image already
-    }
-    for (int k = 0; k < 3; k++) {
-        if (nbs[k] <= 5)
-            continue;  // (2: dword bit 1, inside the granule)
-        int j = 0;
-        while (j < 3 && taken[j])
-            j++;
-        if (j == 3)
-            continue;  // (cannot happen: three lane bits, three position bits)
-        taken[j] = true;
-        z.src[j] = nbs[k] >= 9 ? 8 + (nbs[k] - 9) : nbs[k] - 3;
-    }
-    return z;
-}
-
+using Image = fft64::InImage<LOGN, 3, FirstFreeSwz<LOGN>>;
+// the image's functions and row counts by the format's own names (the kernel and the host audits call either)
 template <int LOGN>
-SDR_HD constexpr bool swz_solvable()
-{
-    const Swz z = make_swz<LOGN>();
-    for (int k = 0; k < 3; k++)
-        if (z.src[k] >= 0 && z.src[k] < 8 && z.src[k] <= k)
-            return false;  // a position bit may only depend on higher granule bits (granule() solves downwards)
-    return true;
-}
-
+SDR_HD inline int granule(int p, int r) { return Image<LOGN>::granule(p, r); }
 template <int LOGN>
-SDR_HD inline int pos(int g, int r)
-{
-    constexpr Swz Z = make_swz<LOGN>();
-    int p = g;
-    for (int k = 0; k < 3; k++) {
-        if (Z.src[k] >= 8)
-            p ^= ((r >> (Z.src[k] - 8)) & 1) << k;
-        else if (Z.src[k] >= 0)
-            p ^= ((g >> Z.src[k]) & 1) << k;
-    }
-    return p;
-}
-
-// the granule lane p of row r fetches (the inverse of pos)
+SDR_HD inline int lds_byte(int n) { return Image<LOGN>::lds_byte(n); }
 template <int LOGN>
-SDR_HD inline int granule(int p, int r)
-{
-    static_assert(swz_solvable<LOGN>(), "iq8 input swizzle is not triangular");
-    constexpr Swz Z = make_swz<LOGN>();
-    int g = p;
-    for (int k = 2; k >= 0; k--) {
-        if (Z.src[k] >= 8)
-            g ^= ((r >> (Z.src[k] - 8)) & 1) << k;
-        else if (Z.src[k] >= 0)
-            g ^= ((g >> Z.src[k]) & 1) << k;  // bit src[k] > k is final already
-    }
-    return g;
-}
-
-// byte address of sample n in the image (linear over GF(2): thread and slot parts of n combine by XOR)
+constexpr int kRows = Image<LOGN>::ROWS;
 template <int LOGN>
-SDR_HD inline int lds_byte(int n)
-{
-    const int r = n >> 9, g = (n >> 3) & 63;
-    return r * 1024 + pos<LOGN>(g, r) * 16 + (n & 7) * 2;
-}
-
-// rows of the image, and rows each wave of the workgroup fetches (N = 512: one wave, one row)
-template <int LOGN>
-constexpr int kRows = (1 << LOGN) / 512;
-template <int LOGN>
-constexpr int kRowsPerWave = fft64::Plan<LOGN>::R / 8;
-static_assert(kRowsPerWave<9> == 1 && kRowsPerWave<10> * (fft64::Plan<10>::T / 64) == kRows<10> &&
-                  kRowsPerWave<14> * (fft64::Plan<14>::T / 64) == kRows<14>,
-              "the waves' rows cover the frame exactly");
+constexpr int kRowsPerWave = Image<LOGN>::ROWS_PER_WAVE;
 
 }  // namespace iq8

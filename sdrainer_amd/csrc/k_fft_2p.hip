@@ -10,9 +10,7 @@
 
 #include "../../include/sdrainer_hip.h"
 #include "fft_2p.h"
-#include "iq8.h"
-#include "sc16.h"
-#include "sdr_device.h"
+#include "fft_input.h"
 
 // 8-bit input (iq8.h).  k_fft_2p_iq8.hip compiles this file again with SDR_FFT2P_IQ8 = 1: that unit holds phase A's
 // 8-bit instances (k_fft2p_a / k_fft2p_win_a<LOGN, CS8 / CU8>) and launch_fft_2p_iq8, which runs them in front of THIS

@@ -5,7 +5,8 @@
 // k_fft_2p.hip includes this file twice.  SDR_FFT2P_WIN = 0: k_fft2p_a, whose tokens are what they were before the window
 // existed.  SDR_FFT2P_WIN = 1: k_fft2p_win_a, which multiplies sample i of the frame by win[i] (sdr_set_window) - one
 // correctly rounded float32 multiplication per component, of the converted value for sc16 input - where the plain kernel
-// widens it.  FMT = CS8 / CU8 (iq8.h: two bytes per sample) is instantiated by k_fft_2p_iq8.hip only.
+// widens it.  One input loop serves every format (fft_input.h).  FMT = CS8 / CU8 (iq8.h: two bytes per sample) is
+// instantiated by k_fft_2p_iq8.hip only.
 #if SDR_FFT2P_WIN
 #define SDR_K_FFT2P_A k_fft2p_win_a
 #define SDR_FFT2P_WIN_PARAM , const float *__restrict__ win
@@ -28,55 +29,22 @@ __global__ __launch_bounds__(fft2p::T) void SDR_K_FFT2P_A(const void *__restrict
     double xr[fft2p::R], xi[fft2p::R];
     {
         const int gl = fft2p::p0_sub<MB>(t), p = w * S::G + gl;
-        if constexpr (FMT == InFormat::F32) {
-            const float2 *__restrict__ iq = reinterpret_cast<const float2 *>(cur ? cur->iq : static_cast<const float *>(iq_arg)) + frame_at;
+        // the format's word per sample, converted (fft_input.h) where the float32 frames are widened
+        using IN = decltype(input_of<FMT>());
+        constexpr IN in = input_of<FMT>();
+        const typename IN::word *__restrict__ iq = input_frames<IN>(iq_arg, cur) + frame_at;
 #pragma unroll
-            for (int s = 0; s < fft2p::R; s++) {
+        for (int s = 0; s < fft2p::R; s++) {
+            const int i = fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s));
+            const typename IN::word v = iq[i];
 #if SDR_FFT2P_WIN
-                const int i = fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s));
-                const float2 v = iq[i];
-                const float wv = win[i];
-                xr[s] = (double)__fmul_rn(v.x, wv);
-                xi[s] = (double)__fmul_rn(v.y, wv);
+            const float wv = win[i];
+            xr[s] = (double)__fmul_rn(in.re(v), wv);
+            xi[s] = (double)__fmul_rn(in.im(v), wv);
 #else
-                const float2 v = iq[fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s))];
-                xr[s] = (double)v.x;
-                xi[s] = (double)v.y;
+            xr[s] = (double)in.re(v);
+            xi[s] = (double)in.im(v);
 #endif
-            }
-        } else if constexpr (FMT == InFormat::SC16) {
-            const uint32_t *__restrict__ iq = reinterpret_cast<const uint32_t *>(cur ? cur->iq_sc16 : static_cast<const int16_t *>(iq_arg)) + frame_at;
-#pragma unroll
-            for (int s = 0; s < fft2p::R; s++) {
-#if SDR_FFT2P_WIN
-                const int i = fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s));
-                const uint32_t v = iq[i];
-                const float wv = win[i];
-                xr[s] = (double)__fmul_rn(sc16::re_of(v), wv);
-                xi[s] = (double)__fmul_rn(sc16::im_of(v), wv);
-#else
-                const uint32_t v = iq[fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s))];
-                xr[s] = (double)sc16::re_of(v);
-                xi[s] = (double)sc16::im_of(v);
-#endif
-            }
-        } else {
-            const uint16_t *__restrict__ iq = reinterpret_cast<const uint16_t *>(cur ? cur->iq8 : static_cast<const uint8_t *>(iq_arg)) + frame_at;
-            constexpr iq8::Format F8 = iq8::format_of(FMT == InFormat::CU8);
-#pragma unroll
-            for (int s = 0; s < fft2p::R; s++) {
-#if SDR_FFT2P_WIN
-                const int i = fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s));
-                const uint32_t v = iq[i];
-                const float wv = win[i];
-                xr[s] = (double)__fmul_rn(iq8::re_of(v, F8), wv);
-                xi[s] = (double)__fmul_rn(iq8::im_of(v, F8), wv);
-#else
-                const uint32_t v = iq[fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s))];
-                xr[s] = (double)iq8::re_of(v, F8);
-                xi[s] = (double)iq8::im_of(v, F8);
-#endif
-            }
         }
         fft2p::pass0<MB>(xr, xi, LOGN, 0, 0, t, W);
 #pragma unroll

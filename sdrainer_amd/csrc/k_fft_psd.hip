@@ -12,10 +12,9 @@
 #include "../../include/sdrainer_hip.h"
 #include "cw_decoder.h"
 #include "fft_f64.h"
+#include "fft_input.h"
 #include "fft_r32.h"
 #include "gomath.h"
-#include "iq8.h"
-#include "sc16.h"
 #include "sdr_device.h"
 
 // A window on the frames.  k_fft_psd_win.hip compiles this file again with SDR_FFT_WIN = 1: the kernels k_fft_psd_win and
@@ -26,9 +25,9 @@
 #if !defined(SDR_FFT_WIN)
 #define SDR_FFT_WIN 0
 #endif
-// 8-bit input (iq8.h).  k_fft_psd_iq8.hip compiles this file a third time with SDR_FFT_IQ8 = 1 (and SDR_FFT_WIN = 1 for
-// load_window): that unit holds k_fft_psd_iq8<LOGN, WIN>, plain and windowed, and launch_fft_psd_iq8 - and none of the
-// kernels of the other two units, whose code stays exactly what it was.
+// 8-bit input (iq8.h).  k_fft_psd_iq8.hip compiles this file a third time with SDR_FFT_IQ8 = 1: that unit holds
+// k_fft_psd_iq8<LOGN, WIN>, plain and windowed, and launch_fft_psd_iq8 - and none of the kernels of the other two units.
+// The sc16 and the 8-bit kernels are one body (fft_psd_one_frame) over their formats' traits (fft_input.h).
 // Each unit exports one launcher, SDR_FFT_PSD_LAUNCH, for the kernels it holds (sdr_device.h).
 #if !defined(SDR_FFT_IQ8)
 #define SDR_FFT_IQ8 0
@@ -37,7 +36,7 @@
 #define SDR_K_FFT_PSD k_fft_psd_win
 #define SDR_K_FFT_PSD_SC16 k_fft_psd_sc16_win
 #define SDR_WIN_PARAM , const float *__restrict__ win
-#define SDR_WIN_ARG , win
+#define SDR_WIN_OR_NULL win
 #define SDR_WIN_LAUNCH_ARG , l.window
 #define SDR_ID_PSD FftKernel::PSD_WIN
 #define SDR_ID_PSD_MULTI FftKernel::PSD_WIN_MULTI
@@ -46,7 +45,7 @@
 #define SDR_K_FFT_PSD k_fft_psd
 #define SDR_K_FFT_PSD_SC16 k_fft_psd_sc16
 #define SDR_WIN_PARAM
-#define SDR_WIN_ARG
+#define SDR_WIN_OR_NULL nullptr
 #define SDR_WIN_LAUNCH_ARG
 #define SDR_ID_PSD FftKernel::PSD
 #define SDR_ID_PSD_MULTI FftKernel::PSD_MULTI
@@ -290,7 +289,6 @@ __device__ __forceinline__ void run_passes(double (&xr)[fft64::Plan<LOGN>::R], d
     }
 }
 
-#if SDR_FFT_WIN
 // The window values of thread t's register slots (slot m holds sample input_sample(t, m)).  In sample order a wave's
 // lanes would read them 32 bytes and more apart - what the frame itself avoids by going through LDS; measured, sixteen
 // such dword loads per thread made the kernel 13 % slower per launch.  So the bank keeps the table in THIS kernel's order
@@ -318,6 +316,7 @@ __device__ __forceinline__ void load_window(float (&wv)[fft64::Plan<LOGN>::R], i
         wv[4 * j + 3] = __uint_as_float(v.w);
     }
 }
+#if SDR_FFT_WIN && !SDR_FFT_IQ8
 template <int LOGN>
 static void window_layout_t(const float *w, float *out)
 {
@@ -359,7 +358,6 @@ __device__ __forceinline__ void store_psd(const double (&xr)[fft64::Plan<LOGN>::
     }
 }
 
-#if !SDR_FFT_IQ8
 // Where the time of a frame goes (N = 16384, tools/fft_bench.hip with -DSDR_FFT_CLOCK and the -DSDR_ABLATE
 // builds, MI355X at 2.3 GHz in-kernel): the phases of a frame run one after the other on its CU - all 16 waves
 // wait for the input, then all compute, then all exchange, ... - and each phase is bound by a different unit, so
@@ -385,6 +383,104 @@ __device__ __forceinline__ void store_psd(const double (&xr)[fft64::Plan<LOGN>::
 // its epilogue also writes the psd row into LDS (the exchange area is free by then; LDS stores cost no vector ALU
 // time) and the tap reads its bins from there behind one barrier: no wait on memory at all.
 constexpr int kMaxLdsTap = 4096;  // listeners per band the LDS tap holds bins for (16 KB); more fall back to the drain
+
+// the tap of one finished frame: slot l <- the row's value at the slot's bin, thread l takes slot l
+template <int T>
+__device__ __forceinline__ void tap_row(const float *row, const int *bins, float *out, int n_tap)
+{
+    for (int l = threadIdx.x; l < n_tap; l += T) {
+        const int bin = bins[l];
+        out[l] = bin >= 0 ? row[bin] : 0.0f;
+    }
+}
+
+// The one-frame workgroup of k_fft_psd<LOGN, false> for the narrow input formats (fft_input.h: IN = InSc16, InIq8), the
+// body of k_fft_psd_sc16, k_fft_psd_sc16_win and k_fft_psd_iq8<LOGN, WIN>.  Its LDS-DMA moves sizeof(IN::word) bytes per
+// sample - R / 4 or R / 8 rows of 1 KB per wave - into the format's staging image, pass 0 reads one word per register
+// slot and converts where the float32 kernel widens; WIN: one correctly rounded float32 multiplication of the converted
+// value per component (load_window).  From the first butterfly on everything is the float32 kernel's (run_passes,
+// store_psd, the LDS tap), so the results are the float32 path's bits for the converted values.  Only this one form
+// exists for these formats: the multi-frame workgroup and the timing-only builds stay float32-only (launch_fft_t).
+template <class IN, int LOGN, bool WIN>
+__device__ __forceinline__ void fft_psd_one_frame(const IN in, const void *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
+                                                  const fft64::cplx *__restrict__ tw, float *__restrict__ psd, size_t in_stride,
+                                                  int frame_stride, int out_stride, const int *__restrict__ tap_bins,
+                                                  float *__restrict__ tap_out, int n_tap, int tap_stride, const float *__restrict__ win)
+{
+    using PL = fft64::Plan<LOGN>;
+    using IM = typename IN::template Image<LOGN>;
+    using word = typename IN::word;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double *lds = reinterpret_cast<double *>(smem);
+    Stamps st;
+#if defined(SDR_FFT_PHASES)
+    st.on = false;
+#endif
+    const int frame = blockIdx.x;
+    const size_t in_band = blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
+    const int t = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    {
+        // frame -> LDS: row r = wave * ROWS_PER_WAVE + j; lane p fetches granule IM::granule(p, r) of the row (the swizzle
+        // lives in the source address, the DMA writes lane p's 16 bytes at row base + 16 p); the descriptor ends with the frame
+        const int lane = t & 63;
+        const rsrc_t xrs = make_rsrc(input_frames<IN>(iq_arg, cur) + input_sample_offset(in_band, frame, frame_stride), PL::N * (unsigned)sizeof(word));
+#pragma unroll
+        for (int j = 0; j < IM::ROWS_PER_WAVE; j++) {
+            const int r = wave * IM::ROWS_PER_WAVE + j;
+            const int g = IM::granule(lane, r);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void *)(smem + r * 1024), 16,
+                                                     (unsigned)g * 16u, r * 1024, 0, SDR_FFT_DMA_AUX);
+        }
+    }
+    // the listeners' bins into LDS (behind the exchange area) while the frame is on its way
+    int *lds_bins = reinterpret_cast<int *>(smem + fft64::kLdsBytes<LOGN>);
+    const bool lds_tap = n_tap > 0 && n_tap <= kMaxLdsTap;
+    if (lds_tap)
+        for (int l = threadIdx.x; l < n_tap; l += PL::T)
+            lds_bins[l] = tap_bins[(size_t)blockIdx.y * tap_stride + l];
+    float wv[WIN ? PL::R : 1];
+    if constexpr (WIN)
+        load_window<LOGN>(wv, t, win);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    double xr[PL::R], xi[PL::R];
+    {
+        // dsp/fft.go:59-69 setSamplesFromIQ: slot m <- sample input_sample(t, m), the image address linear over GF(2)
+        const int thread_byte = IM::lds_byte(fft64::input_sample<LOGN>(t, 0));
+#pragma unroll
+        for (int m = 0; m < PL::R; m++) {
+            const int slot_byte = IM::lds_byte(fft64::input_sample<LOGN>(0, m));
+            const word w = *reinterpret_cast<const word *>(smem + (thread_byte ^ slot_byte));
+            if constexpr (WIN) {
+                xr[m] = (double)__fmul_rn(in.re(w), wv[m]);
+                xi[m] = (double)__fmul_rn(in.im(w), wv[m]);
+            } else {
+                xr[m] = (double)in.re(w);
+                xi[m] = (double)in.im(w);
+            }
+        }
+    }
+    __syncthreads();  // everyone has its samples: the exchange area may be written again
+    const fft64::cplx no_pre[kTwPreMax] = {};
+    run_passes<LOGN, 0>(xr, xi, t, make_rsrc(tw, (unsigned)(PL::TW_TOTAL * sizeof(fft64::cplx))), tw, lds, no_pre, st);
+    if constexpr (!last_lds_exchange_is_cross<LOGN>())
+        if (lds_tap)
+            __syncthreads();  // a wave-local last exchange fences only its own wave; the row goes everywhere
+    store_psd<LOGN, true>(xr, xi, t, psd + (out_band + frame) * PL::N, smem, lds_tap);
+    float *out = tap_out + (out_band + frame) * (size_t)tap_stride;
+    if (lds_tap) {
+        __syncthreads();  // the row is in LDS
+        tap_row<PL::T>(reinterpret_cast<const float *>(smem), lds_bins, out, n_tap);
+    } else if (n_tap > 0) {
+        // more listeners than the LDS tap holds: re-read the stored row once it has reached memory
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        tap_row<PL::T>(psd + (out_band + frame) * PL::N, tap_bins + (size_t)blockIdx.y * tap_stride, out, n_tap);
+    }
+}
+
+#if !SDR_FFT_IQ8
 // (second launch bound = waves per SIMD the register allocation must leave room for: four, i.e. one 1024-thread
 // workgroup or two 512-thread ones per CU)
 template <int LOGN, bool MULTI>
@@ -426,7 +522,7 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
         if (frame >= 0)  // timing-only build: no input DMA at all - what a perfectly hidden input would leave
             return;
 #endif
-        constexpr int ROWS_PER_WAVE = PL::R / 2;
+        constexpr int ROWS_PER_WAVE = InF32::Image<LOGN>::ROWS_PER_WAVE;
         const int lane = t & 63;
 #if defined(SDR_ABLATE) && (SDR_ABLATE == 8)
         const size_t fr = (size_t)((blockIdx.y * (in_stride / PL::N) + frame) & 15) * PL::N;  // timing-only: 16 frames, L2-resident
@@ -438,20 +534,15 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
 #pragma unroll
         for (int j = 0; j < ROWS_PER_WAVE; j++) {
             const int r = wave * ROWS_PER_WAVE + j;
-            const int g = fft64::in_granule<LOGN>(lane, r);
+            const int g = InF32::Image<LOGN>::granule(lane, r);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void *)(smem + r * 1024), 16,
                                                      (unsigned)g * 16u, r * 1024, 0, SDR_FFT_DMA_AUX);
         }
     };
     // tap of one finished frame (its psd stores are known to be complete, see above)
     auto tap_frame = [&](int frame) {
-        const float *row = psd + (out_band + frame) * PL::N;
-        float *out = tap_out + (out_band + frame) * (size_t)tap_stride;
-        const int *bins = tap_bins + (size_t)blockIdx.y * tap_stride;
-        for (int l = threadIdx.x; l < n_tap; l += PL::T) {
-            const int bin = bins[l];
-            out[l] = bin >= 0 ? row[bin] : 0.0f;
-        }
+        tap_row<PL::T>(psd + (out_band + frame) * PL::N, tap_bins + (size_t)blockIdx.y * tap_stride,
+                       tap_out + (out_band + frame) * (size_t)tap_stride, n_tap);
     };
     stage_frame(frame0, tid);
     // one-frame workgroup: its listeners' bins into LDS (behind the exchange area) while the frame is on its way
@@ -487,7 +578,7 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
         __syncthreads();
         SDR_STAMP(st, ST_ALL_LANDED);  // everybody's have
 
-        const int thread_byte = fft64::in_lds_byte<LOGN>(fft64::input_sample<LOGN>(t, 0));
+        const int thread_byte = InF32::Image<LOGN>::lds_byte(fft64::input_sample<LOGN>(t, 0));
 #pragma unroll
         for (int m = 0; m < PL::R; m++) {
 #if defined(SDR_ABLATE) && (SDR_ABLATE == 1 || SDR_ABLATE == 7)
@@ -495,7 +586,7 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
 #else
             // sample number -> image address is linear over GF(2): thread part and slot part combine by XOR, and the
             // slot part is a compile-time constant
-            const int slot_byte = fft64::in_lds_byte<LOGN>(fft64::input_sample<LOGN>(0, m));
+            const int slot_byte = InF32::Image<LOGN>::lds_byte(fft64::input_sample<LOGN>(0, m));
             const float2 v = *reinterpret_cast<const float2 *>(smem + (thread_byte ^ slot_byte));
 #endif
 #if SDR_FFT_WIN
@@ -533,6 +624,7 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
     }
     if (lds_tap) {
         __syncthreads();  // the row is in LDS (and lds_bins has been for a long time)
+        // (not tap_row: through it the compiler orders two instructions of this loop differently at N >= 4096)
         const float *row = reinterpret_cast<const float *>(smem);
         float *out = tap_out + (out_band + frame0) * (size_t)tap_stride;
         for (int l = threadIdx.x; l < n_tap; l += PL::T) {
@@ -573,12 +665,8 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-// k_fft_psd for sc16 input (sc16.h: int16 I, int16 Q per sample): the one-frame workgroup of k_fft_psd<LOGN, false> with
-// half the input bytes.  Its LDS-DMA moves 4 bytes per sample - 256 samples per 1 KB row, R / 4 rows per wave - into
-// sc16.h's staging image, pass 0 reads one ds_read_b32 per register slot and converts where the float32 kernel widens.
-// From the first butterfly on everything is the float32 kernel's (run_passes, store_psd, the LDS tap), so the results
-// are the float32 path's bits for the converted values.  Only this one form exists for sc16: the multi-frame workgroup
-// and the timing-only builds stay float32-only (launch_fft_t).
+// k_fft_psd for sc16 input (sc16.h: int16 I, int16 Q per sample): fft_psd_one_frame over InSc16, windowed by recompilation
+// like the float32 kernel beside it.
 template <int LOGN>
 __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 ? 4 : 1)) void SDR_K_FFT_PSD_SC16(const int16_t *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
                                                                        const fft64::cplx *__restrict__ tw, float *__restrict__ psd,
@@ -586,100 +674,14 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
                                                                        float *__restrict__ tap_out, int n_tap, int tap_stride SDR_WIN_PARAM)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    using PL = fft64::Plan<LOGN>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *lds = reinterpret_cast<double *>(smem);
-    Stamps st;
-#if defined(SDR_FFT_PHASES)
-    st.on = false;
-#endif
-    const int16_t *__restrict__ iq = cur ? cur->iq_sc16 : iq_arg;  // graph replay: the batch's input pointer lives in device memory
-    const int frame = blockIdx.x;
-    const size_t in_band = blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
-    const int t = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    {
-        // frame -> LDS: row r = wave * R/4 + j; lane p fetches granule sc16::granule(p, r) of the row (the swizzle lives in
-        // the source address, the DMA writes lane p's 16 bytes at row base + 16 p)
-        constexpr int ROWS_PER_WAVE = PL::R / 4;
-        const int lane = t & 63;
-        const rsrc_t xrs = make_rsrc(iq + input_sample_offset(in_band, frame, frame_stride) * 2, PL::N * 4u);
-#pragma unroll
-        for (int j = 0; j < ROWS_PER_WAVE; j++) {
-            const int r = wave * ROWS_PER_WAVE + j;
-            const int g = sc16::granule<LOGN>(lane, r);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void *)(smem + r * 1024), 16,
-                                                     (unsigned)g * 16u, r * 1024, 0, SDR_FFT_DMA_AUX);
-        }
-    }
-    // the listeners' bins into LDS (behind the exchange area) while the frame is on its way
-    int *lds_bins = reinterpret_cast<int *>(smem + fft64::kLdsBytes<LOGN>);
-    const bool lds_tap = n_tap > 0 && n_tap <= kMaxLdsTap;
-    if (lds_tap)
-        for (int l = threadIdx.x; l < n_tap; l += PL::T)
-            lds_bins[l] = tap_bins[(size_t)blockIdx.y * tap_stride + l];
-#if SDR_FFT_WIN
-    float wv[PL::R];
-    load_window<LOGN>(wv, t, win);
-#endif
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    double xr[PL::R], xi[PL::R];
-    {
-        // dsp/fft.go:59-69 setSamplesFromIQ: slot m <- sample input_sample(t, m), the image address linear over GF(2)
-        const int thread_byte = sc16::lds_byte<LOGN>(fft64::input_sample<LOGN>(t, 0));
-#pragma unroll
-        for (int m = 0; m < PL::R; m++) {
-            const int slot_byte = sc16::lds_byte<LOGN>(fft64::input_sample<LOGN>(0, m));
-            const uint32_t w = *reinterpret_cast<const uint32_t *>(smem + (thread_byte ^ slot_byte));
-#if SDR_FFT_WIN
-            xr[m] = (double)__fmul_rn(sc16::re_of(w), wv[m]);
-            xi[m] = (double)__fmul_rn(sc16::im_of(w), wv[m]);
-#else
-            xr[m] = (double)sc16::re_of(w);
-            xi[m] = (double)sc16::im_of(w);
-#endif
-        }
-    }
-    __syncthreads();  // everyone has its samples: the exchange area may be written again
-    const fft64::cplx no_pre[kTwPreMax] = {};
-    run_passes<LOGN, 0>(xr, xi, t, make_rsrc(tw, (unsigned)(PL::TW_TOTAL * sizeof(fft64::cplx))), tw, lds, no_pre, st);
-    if constexpr (!last_lds_exchange_is_cross<LOGN>())
-        if (lds_tap)
-            __syncthreads();  // a wave-local last exchange fences only its own wave; the row goes everywhere
-    store_psd<LOGN, true>(xr, xi, t, psd + (out_band + frame) * PL::N, smem, lds_tap);
-    if (lds_tap) {
-        __syncthreads();  // the row is in LDS
-        const float *row = reinterpret_cast<const float *>(smem);
-        float *out = tap_out + (out_band + frame) * (size_t)tap_stride;
-        for (int l = threadIdx.x; l < n_tap; l += PL::T) {
-            const int bin = lds_bins[l];
-            out[l] = bin >= 0 ? row[bin] : 0.0f;
-        }
-    } else if (n_tap > 0) {
-        // more listeners than the LDS tap holds: re-read the stored row once it has reached memory
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        const float *row = psd + (out_band + frame) * PL::N;
-        float *out = tap_out + (out_band + frame) * (size_t)tap_stride;
-        const int *bins = tap_bins + (size_t)blockIdx.y * tap_stride;
-        for (int l = threadIdx.x; l < n_tap; l += PL::T) {
-            const int bin = bins[l];
-            out[l] = bin >= 0 ? row[bin] : 0.0f;
-        }
-    }
+    fft_psd_one_frame<InSc16, LOGN, SDR_FFT_WIN != 0>(InSc16{}, iq_arg, cur, tw, psd, in_stride, frame_stride, out_stride, tap_bins, tap_out, n_tap, tap_stride,
+                                                      SDR_WIN_OR_NULL);
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
 #else  // SDR_FFT_IQ8
-constexpr int kMaxLdsTap = 4096;  // (as in the other units: listeners per band the LDS tap holds bins for)
-
-// k_fft_psd for 8-bit input (iq8.h: one byte I, one byte Q per sample, cs8 or cu8): the one-frame workgroup of
-// k_fft_psd_sc16 with two bytes per sample.  Its LDS-DMA moves 512 samples per 1 KB row - R / 8 rows per wave - into iq8.h's
-// staging image, pass 0 reads one 16-bit LDS word per register slot and converts where the float32 kernel widens (exact:
-// iq8::to_f32).  From the first butterfly on everything is the float32 kernel's (run_passes, store_psd, the LDS tap), so
-// the results are the float32 path's bits for the converted values.  flip / c: iq8::Format.  WIN: the windowed twin, one
-// correctly rounded float32 multiplication of the converted value per component (load_window).
+// k_fft_psd for 8-bit input (iq8.h: one byte I, one byte Q per sample, cs8 or cu8): fft_psd_one_frame over InIq8.
+// flip / c: iq8::Format.  WIN: the windowed twin (win is null without).
 template <int LOGN, bool WIN>
 __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 ? 4 : 1)) void k_fft_psd_iq8(const uint8_t *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
                                                                        const fft64::cplx *__restrict__ tw, float *__restrict__ psd,
@@ -688,159 +690,67 @@ __global__ __launch_bounds__(fft64::Plan<LOGN>::T, (fft64::Plan<LOGN>::T >= 512 
                                                                        const float *__restrict__ win)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    using PL = fft64::Plan<LOGN>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *lds = reinterpret_cast<double *>(smem);
-    Stamps st;
-#if defined(SDR_FFT_PHASES)
-    st.on = false;
-#endif
-    const uint8_t *__restrict__ iq = cur ? cur->iq8 : iq_arg;  // graph replay: the batch's input pointer lives in device memory
-    const int frame = blockIdx.x;
-    const size_t in_band = blockIdx.y * in_stride, out_band = (size_t)blockIdx.y * out_stride;
-    const int t = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    {
-        // frame -> LDS: row r = wave * R/8 + j; lane p fetches granule iq8::granule(p, r) of the row (the swizzle lives in
-        // the source address, the DMA writes lane p's 16 bytes at row base + 16 p); the descriptor ends with the frame
-        constexpr int ROWS_PER_WAVE = iq8::kRowsPerWave<LOGN>;
-        static_assert(ROWS_PER_WAVE * (PL::T / 64) * 1024 == PL::N * 2, "the waves' rows are the frame");
-        const int lane = t & 63;
-        const rsrc_t xrs = make_rsrc(iq + input_sample_offset(in_band, frame, frame_stride) * 2, PL::N * 2u);
-#pragma unroll
-        for (int j = 0; j < ROWS_PER_WAVE; j++) {
-            const int r = wave * ROWS_PER_WAVE + j;
-            const int g = iq8::granule<LOGN>(lane, r);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void *)(smem + r * 1024), 16,
-                                                     (unsigned)g * 16u, r * 1024, 0, SDR_FFT_DMA_AUX);
-        }
-    }
-    // the listeners' bins into LDS (behind the exchange area) while the frame is on its way
-    int *lds_bins = reinterpret_cast<int *>(smem + fft64::kLdsBytes<LOGN>);
-    const bool lds_tap = n_tap > 0 && n_tap <= kMaxLdsTap;
-    if (lds_tap)
-        for (int l = threadIdx.x; l < n_tap; l += PL::T)
-            lds_bins[l] = tap_bins[(size_t)blockIdx.y * tap_stride + l];
-    float wv[WIN ? PL::R : 1];
-    if constexpr (WIN)
-        load_window<LOGN>(wv, t, win);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    double xr[PL::R], xi[PL::R];
-    {
-        // dsp/fft.go:59-69 setSamplesFromIQ: slot m <- sample input_sample(t, m), the image address linear over GF(2)
-        const iq8::Format fmt{flip, c};
-        const int thread_byte = iq8::lds_byte<LOGN>(fft64::input_sample<LOGN>(t, 0));
-#pragma unroll
-        for (int m = 0; m < PL::R; m++) {
-            const int slot_byte = iq8::lds_byte<LOGN>(fft64::input_sample<LOGN>(0, m));
-            const uint32_t w = *reinterpret_cast<const uint16_t *>(smem + (thread_byte ^ slot_byte));
-            if constexpr (WIN) {
-                xr[m] = (double)__fmul_rn(iq8::re_of(w, fmt), wv[m]);
-                xi[m] = (double)__fmul_rn(iq8::im_of(w, fmt), wv[m]);
-            } else {
-                xr[m] = (double)iq8::re_of(w, fmt);
-                xi[m] = (double)iq8::im_of(w, fmt);
-            }
-        }
-    }
-    __syncthreads();  // everyone has its samples: the exchange area may be written again
-    const fft64::cplx no_pre[kTwPreMax] = {};
-    run_passes<LOGN, 0>(xr, xi, t, make_rsrc(tw, (unsigned)(PL::TW_TOTAL * sizeof(fft64::cplx))), tw, lds, no_pre, st);
-    if constexpr (!last_lds_exchange_is_cross<LOGN>())
-        if (lds_tap)
-            __syncthreads();  // a wave-local last exchange fences only its own wave; the row goes everywhere
-    store_psd<LOGN, true>(xr, xi, t, psd + (out_band + frame) * PL::N, smem, lds_tap);
-    if (lds_tap) {
-        __syncthreads();  // the row is in LDS
-        const float *row = reinterpret_cast<const float *>(smem);
-        float *out = tap_out + (out_band + frame) * (size_t)tap_stride;
-        for (int l = threadIdx.x; l < n_tap; l += PL::T) {
-            const int bin = lds_bins[l];
-            out[l] = bin >= 0 ? row[bin] : 0.0f;
-        }
-    } else if (n_tap > 0) {
-        // more listeners than the LDS tap holds: re-read the stored row once it has reached memory
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        const float *row = psd + (out_band + frame) * PL::N;
-        float *out = tap_out + (out_band + frame) * (size_t)tap_stride;
-        const int *bins = tap_bins + (size_t)blockIdx.y * tap_stride;
-        for (int l = threadIdx.x; l < n_tap; l += PL::T) {
-            const int bin = bins[l];
-            out[l] = bin >= 0 ? row[bin] : 0.0f;
-        }
-    }
+    fft_psd_one_frame<InIq8, LOGN, WIN>(InIq8{{flip, c}}, iq_arg, cur, tw, psd, in_stride, frame_stride, out_stride, tap_bins, tap_out, n_tap, tap_stride, win);
 #endif  // __HIP_DEVICE_COMPILE__
-}
-
-template <int LOGN>
-static hipError_t launch_fft_t(const FftLaunch &l, LaunchAt at)
-{
-    using PL = fft64::Plan<LOGN>;
-    const FftTap &tap = l.tap;
-    static LdsLimitOnce lds_once;
-    const hipError_t attr_err = raise_lds_limit_once(
-        lds_once, {reinterpret_cast<const void *>(&k_fft_psd_iq8<LOGN, false>), reinterpret_cast<const void *>(&k_fft_psd_iq8<LOGN, true>)},
-        fft64::kLdsBytes<LOGN> + kMaxLdsTap * 4);
-    if (attr_err != hipSuccess)
-        return attr_err;
-    const FftKernel k = fft_kernel(l.fft);
-    if ((k != FftKernel::PSD_IQ8 && k != FftKernel::PSD_IQ8_WIN) || (k == FftKernel::PSD_IQ8_WIN) != (l.window != nullptr))
-        return hipErrorInvalidValue;
-    if (l.n_frames <= 0 || l.n_bands <= 0)
-        return hipSuccess;
-    const unsigned tap_lds = tap.n > 0 && tap.n <= kMaxLdsTap ? ((tap.n * 4 + 255) & ~255) : 0;
-    const iq8::Format f = iq8::format_of(l.fft.fmt == InFormat::CU8);
-    const uint8_t *iq = static_cast<const uint8_t *>(l.iq);
-    // one frame per workgroup, always (FftChoice::fpw is the float32 kernel's)
-    if (l.window)
-        launch_kernel((k_fft_psd_iq8<LOGN, true>), dim3(l.n_frames, l.n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at, iq, l.cur, l.tw, l.psd,
-                      l.in_stride, l.frame_stride, l.out_stride, tap.bins, tap.out, tap.n, tap.stride, f.flip, f.c, l.window);
-    else
-        launch_kernel((k_fft_psd_iq8<LOGN, false>), dim3(l.n_frames, l.n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at, iq, l.cur, l.tw, l.psd,
-                      l.in_stride, l.frame_stride, l.out_stride, tap.bins, tap.out, tap.n, tap.stride, f.flip, f.c, static_cast<const float *>(nullptr));
-    return hipGetLastError();
 }
 #endif  // SDR_FFT_IQ8
 
 #if !SDR_FFT_IQ8
 static_assert(fft32::T == kR32MaxTap, "host/batch_plan.h: k_fft_r32 serves one listener slot per thread");
+#endif
 
-// float32 and sc16 frames; with SDR_FFT_WIN the windowed kernels and l.window, in window_layout's order
+// This unit's kernels of one size.  float32 and sc16 frames - with SDR_FFT_WIN the windowed kernels and l.window, in
+// window_layout's order - or, in the 8-bit unit, cs8 and cu8 frames with a window or without.
 template <int LOGN>
 static hipError_t launch_fft_t(const FftLaunch &l, LaunchAt at)
 {
     using PL = fft64::Plan<LOGN>;
     const FftTap &tap = l.tap;
-    const float *iq = static_cast<const float *>(l.iq);
+    const FftKernel k = fft_kernel(l.fft);
+#if SDR_FFT_IQ8
+    const std::initializer_list<const void *> kernels = {reinterpret_cast<const void *>(&k_fft_psd_iq8<LOGN, false>),
+                                                         reinterpret_cast<const void *>(&k_fft_psd_iq8<LOGN, true>)};
+    const bool mine = (k == FftKernel::PSD_IQ8 || k == FftKernel::PSD_IQ8_WIN) && (k == FftKernel::PSD_IQ8_WIN) == (l.window != nullptr);
+#else
+    const std::initializer_list<const void *> kernels = {reinterpret_cast<const void *>(&SDR_K_FFT_PSD<LOGN, false>),
+                                                         reinterpret_cast<const void *>(&SDR_K_FFT_PSD<LOGN, true>),
+                                                         reinterpret_cast<const void *>(&SDR_K_FFT_PSD_SC16<LOGN>)};
+    const bool mine = (k == SDR_ID_PSD || k == SDR_ID_PSD_MULTI || k == SDR_ID_PSD_SC16) && (SDR_FFT_WIN != 0) == (l.window != nullptr);
+#endif
     static LdsLimitOnce lds_once;
-    const hipError_t attr_err = raise_lds_limit_once(lds_once,
-                                                     {reinterpret_cast<const void *>(&SDR_K_FFT_PSD<LOGN, false>), reinterpret_cast<const void *>(&SDR_K_FFT_PSD<LOGN, true>),
-                                                      reinterpret_cast<const void *>(&SDR_K_FFT_PSD_SC16<LOGN>)},
-                                                     fft64::kLdsBytes<LOGN> + kMaxLdsTap * 4);
+    const hipError_t attr_err = raise_lds_limit_once(lds_once, kernels, fft64::kLdsBytes<LOGN> + kMaxLdsTap * 4);
     if (attr_err != hipSuccess)
         return attr_err;
-    const FftKernel k = fft_kernel(l.fft);
-    if ((k != SDR_ID_PSD && k != SDR_ID_PSD_MULTI && k != SDR_ID_PSD_SC16) || (SDR_FFT_WIN != 0) != (l.window != nullptr))
+    if (!mine)
         return hipErrorInvalidValue;
     if (l.n_frames <= 0 || l.n_bands <= 0)
         return hipSuccess;
     const unsigned tap_lds = tap.n > 0 && tap.n <= kMaxLdsTap ? ((tap.n * 4 + 255) & ~255) : 0;
+    // the narrow formats' kernels: one frame per workgroup, always (FftChoice::frames_per_wg is the float32 kernel's)
+    const auto one_frame = [&](auto kernel, auto iq, auto... more) {
+        launch_kernel(kernel, dim3(l.n_frames, l.n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at, iq, l.cur, l.tw, l.psd, l.in_stride,
+                      l.frame_stride, l.out_stride, tap.bins, tap.out, tap.n, tap.stride, more...);
+    };
+#if SDR_FFT_IQ8
+    const iq8::Format f = iq8::format_of(l.fft.fmt == InFormat::CU8);
+    if (l.window)
+        one_frame(k_fft_psd_iq8<LOGN, true>, static_cast<const uint8_t *>(l.iq), f.flip, f.c, l.window);
+    else
+        one_frame(k_fft_psd_iq8<LOGN, false>, static_cast<const uint8_t *>(l.iq), f.flip, f.c, static_cast<const float *>(nullptr));
+#else
+    const float *iq = static_cast<const float *>(l.iq);
     const int fpw = l.fft.frames_per_wg;  // (host/batch_plan.h fft_frames_per_wg; a workgroup's frames are consecutive)
     if (k == SDR_ID_PSD_SC16)
-        launch_kernel((SDR_K_FFT_PSD_SC16<LOGN>), dim3(l.n_frames, l.n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at,
-                      static_cast<const int16_t *>(l.iq), l.cur, l.tw, l.psd, l.in_stride, l.frame_stride, l.out_stride, tap.bins, tap.out, tap.n,
-                      tap.stride SDR_WIN_LAUNCH_ARG);
+        one_frame(SDR_K_FFT_PSD_SC16<LOGN>, static_cast<const int16_t *>(l.iq) SDR_WIN_LAUNCH_ARG);
     else if (k == SDR_ID_PSD_MULTI)
         launch_kernel((SDR_K_FFT_PSD<LOGN, true>), dim3((l.n_frames + fpw - 1) / fpw, l.n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN>, at, iq, l.cur, l.tw,
                       l.psd, l.in_stride, l.frame_stride, l.out_stride, l.n_frames, fpw, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_LAUNCH_ARG);
     else
         launch_kernel((SDR_K_FFT_PSD<LOGN, false>), dim3(l.n_frames, l.n_bands), dim3(PL::T), fft64::kLdsBytes<LOGN> + tap_lds, at, iq, l.cur, l.tw, l.psd,
                       l.in_stride, l.frame_stride, l.out_stride, l.n_frames, 1, tap.bins, tap.out, tap.n, tap.stride SDR_WIN_LAUNCH_ARG);
+#endif
     return hipGetLastError();
 }
-#endif  // !SDR_FFT_IQ8
 
 // N = 512 - 16384: this unit's kernels of fft_kernel(l.fft), any other id refused
 hipError_t SDR_FFT_PSD_LAUNCH(const FftLaunch &l, LaunchAt at)

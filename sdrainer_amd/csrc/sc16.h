@@ -36,75 +36,17 @@ SDR_HD inline float im_of(uint32_t w) { return to_f32((int16_t)(uint16_t)(w >> 1
 // lane, and read back in the pass-0 layout with one ds_read_b32 per register slot.  A ds_read_b32 is served in two
 // groups of 32 lanes over 32 four-byte banks: the 32 lanes' words must differ mod 32, i.e. in word-address bits 0-4.
 // Pass 0's lane bits 0 and 1 are sample bits 0 and 1 (word bits 0-1 of a linear image); lane bits 2-4 are higher sample
-// bits in general, so granule-position bit k (word bit 2 + k) is XORed with the sample bit behind lane bit 2 + k.  The
-// DMA writes lane l's granule at row base + 16 l, so the swizzle is applied through the SOURCE address.
+// bits in general, so granule-position bit k (word bit 2 + k) is XORed with the sample bit behind lane bit 2 + k
+// (fft64::PairedSwz).  The DMA writes lane l's granule at row base + 16 l, so the swizzle is applied through the SOURCE
+// address; pos, granule and lds_byte are fft64::InImage's (fft_f64.h "Input staging"), with four samples per granule.
 //   sample n  ->  row r = n >> 8, granule g = (n >> 2) & 63, byte r*1024 + pos(g, r)*16 + (n & 3)*4
 // ---------------------------------------------------------------------------------------------
-struct Swz {
-    int src[3];  // position bit k is XORed with: -1 nothing, 0..5 granule bit, 8+j row bit j
-};
-
 template <int LOGN>
-SDR_HD constexpr Swz make_swz()
-{
-    const fft64::Layout L0 = fft64::make_layout<LOGN>(0);
-    Swz z{{-1, -1, -1}};
-    for (int k = 0; k < 3; k++) {
-        const int nb = LOGN - 1 - L0.tbit[2 + k];  // sample-number bit behind lane bit 2+k
-        if (nb >= 8)
-            z.src[k] = 8 + (nb - 8);
-        else if (nb != 2 + k)
-            z.src[k] = nb - 2;
-    }
-    return z;
-}
-
+using Image = fft64::InImage<LOGN, 2>;
+// the image's functions by the format's own names (the kernel and the host audits call either)
 template <int LOGN>
-SDR_HD constexpr bool swz_solvable()
-{
-    const Swz z = make_swz<LOGN>();
-    for (int k = 0; k < 3; k++)
-        if (z.src[k] >= 0 && z.src[k] < 8 && z.src[k] <= k)
-            return false;  // a position bit may only depend on higher granule bits (granule() solves downwards)
-    return true;
-}
-
+SDR_HD inline int granule(int p, int r) { return Image<LOGN>::granule(p, r); }
 template <int LOGN>
-SDR_HD inline int pos(int g, int r)
-{
-    constexpr Swz Z = make_swz<LOGN>();
-    int p = g;
-    for (int k = 0; k < 3; k++) {
-        if (Z.src[k] >= 8)
-            p ^= ((r >> (Z.src[k] - 8)) & 1) << k;
-        else if (Z.src[k] >= 0)
-            p ^= ((g >> Z.src[k]) & 1) << k;
-    }
-    return p;
-}
-
-// the granule lane p of row r fetches (the inverse of pos)
-template <int LOGN>
-SDR_HD inline int granule(int p, int r)
-{
-    static_assert(swz_solvable<LOGN>(), "sc16 input swizzle is not triangular");
-    constexpr Swz Z = make_swz<LOGN>();
-    int g = p;
-    for (int k = 2; k >= 0; k--) {
-        if (Z.src[k] >= 8)
-            g ^= ((r >> (Z.src[k] - 8)) & 1) << k;
-        else if (Z.src[k] >= 0)
-            g ^= ((g >> Z.src[k]) & 1) << k;  // bit src[k] > k is final already
-    }
-    return g;
-}
-
-// byte address of sample n in the image (linear over GF(2): thread and slot parts of n combine by XOR)
-template <int LOGN>
-SDR_HD inline int lds_byte(int n)
-{
-    const int r = n >> 8, g = (n >> 2) & 63;
-    return r * 1024 + pos<LOGN>(g, r) * 16 + (n & 3) * 4;
-}
+SDR_HD inline int lds_byte(int n) { return Image<LOGN>::lds_byte(n); }
 
 }  // namespace sc16

@@ -1,0 +1,145 @@
+"""The one-frame FFT body the narrow input formats share (sdrainer_amd/csrc/k_fft_psd.hip fft_psd_one_frame: k_fft_psd_sc16,
+k_fft_psd_sc16_win, k_fft_psd_iq8<LOGN, false / true>) over the full product of its branches at the smallest shapes:
+formats sc16, cs8, cu8; window off and on; every N it is instantiated for; two bands, three frames; no listener, a few
+listeners with bins 0 and N - 1 among them (the LDS tap) and, at N = 1024, more than kMaxLdsTap (the tap that re-reads
+the stored row); one graph replay per format (the format's trait names the BatchCursor field).
+
+The library's contract is the expectation: a bank fed the narrow samples gives, bit for bit, what a bank fed their
+float32 values through the float32 call gives - every psd and spectrum row, every listener's tapped value (the traced
+value is a function of it alone), frame record and delivery.  The samples are uniform over the format's whole range."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+import iq8_tools as t8  # noqa: E402
+from parity_tools import capi, random_window, sc16_to_float32  # noqa: E402, F401 (capi: the fixture)
+
+RATE = t8.RATE
+BANDS, FRAMES = 2, 3
+FORMATS = ["sc16", "cs8", "cu8"]
+SIZES = [512, 1024, 2048, 4096, 8192, 16384]
+
+
+def samples(fmt, shape, seed):
+    """Uniform over every value of the format: int16, int8 or uint8 of the given shape."""
+    rng = np.random.default_rng(seed)
+    if fmt == "sc16":
+        return rng.integers(-32768, 32768, shape, dtype=np.int16)
+    x = rng.integers(0, 256, shape, dtype=np.uint8)
+    return x.view(np.int8) if fmt == "cs8" else x
+
+
+def to_f32(fmt, q):
+    return sc16_to_float32(q) if fmt == "sc16" else t8.to_f32(q, t8.FORMAT_IDS.index(fmt))
+
+
+class Pair:
+    """Bank a takes the float32 values through the float32 calls, bank b the narrow samples through their format's."""
+
+    def __init__(self, capi, n, fmt, window, listeners=8):
+        self.n, self.fmt, self.lids = n, fmt, [[] for _ in range(BANDS)]
+        mk = lambda: capi.Bank(RATE[n], n, n_bands=BANDS, max_batch_frames=FRAMES, max_listeners=listeners, trace=True)
+        self.a, self.b = mk(), mk()
+        for bk in (self.a, self.b):
+            bk.enable_results(True)
+            if window:
+                bk.set_window(random_window(n, 4000 + n))
+
+    def attach(self, bins):
+        for band in range(BANDS):
+            for bin_ in bins:
+                ia, ib = self.a.attach(band, int(bin_)), self.b.attach(band, int(bin_))
+                assert ia == ib >= 0
+                self.lids[band].append(ia)
+
+    def device(self, q):
+        ta, tb = torch.from_numpy(to_f32(self.fmt, q)).cuda(), torch.from_numpy(np.ascontiguousarray(q)).cuda()
+        torch.cuda.synchronize()
+        return ta, tb
+
+    def run(self, seed, traced=None):
+        ta, tb = self.device(samples(self.fmt, (BANDS, FRAMES, 2 * self.n), seed))
+        self.a.process_device(ta.data_ptr(), FRAMES)
+        if self.fmt == "sc16":
+            self.b.process_device_sc16(tb.data_ptr(), FRAMES)
+        else:
+            self.b.process_device_iq8(tb.data_ptr(), FRAMES, t8.FORMAT_IDS.index(self.fmt))
+        self.check(traced)
+
+    def check(self, traced=None):
+        """traced: positions in the attach order whose traces are compared (default: every listener)."""
+        self.a.sync()
+        self.b.sync()
+        for band in range(BANDS):
+            for f in range(FRAMES):
+                (sa, pa), (sb, pb) = self.a.read_spectrum(band, f), self.b.read_spectrum(band, f)
+                assert pa.tobytes() == pb.tobytes(), f"band {band} frame {f}: psd row differs"
+                assert sa.tobytes() == sb.tobytes(), f"band {band} frame {f}: spectrum row differs"
+                assert np.all(np.isfinite(pb)) and pb.max() > 0
+            assert self.a.read_frame_records(band).tobytes() == self.b.read_frame_records(band).tobytes(), f"band {band}: frame records"
+            lids = self.lids[band] if traced is None else [self.lids[band][k] for k in traced]
+            for lid in lids:
+                va, vb = self.a.read_trace(band, lid), self.b.read_trace(band, lid)
+                assert len(va[0]) == FRAMES
+                for x, y, what in zip(va, vb, ("tapped value", "raw bit", "debounced bit")):
+                    assert x.tobytes() == y.tobytes(), f"band {band} listener {lid}: {what} differs"
+        assert t8.same_deliveries(self.a, self.b) > 0
+
+    def close(self):
+        self.a.close()
+        self.b.close()
+
+
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("window", [False, True], ids=["plain", "win"])
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_no_listener_then_lds_tap(capi, fmt, window, n):
+    """One batch without a listener (no tap), then one with five, bins 0 and N - 1 among them (the tap out of LDS)."""
+    p = Pair(capi, n, fmt, window)
+    p.run(n + 1)
+    p.attach([0, n - 1, n // 2, 37, n - 70])
+    p.run(n + 2)
+    p.close()
+
+
+@pytest.mark.parametrize("window", [False, True], ids=["plain", "win"])
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_drain_tap(capi, fmt, window):
+    """N = 1024 with 4100 listeners, more than kMaxLdsTap: the tap re-reads the stored psd row.  Every row, record and
+    delivery is compared; the traces of the first listeners (bins 0 and N - 1), of those around slot 4096 and of the last."""
+    n, count = 1024, 4100
+    p = Pair(capi, n, fmt, window, listeners=count)
+    p.attach([0, n - 1] + [(k * 7919) % n for k in range(2, count)])
+    p.run(5000, traced=[0, 1, 2, 4094, 4095, 4096, 4097, count - 1])
+    p.close()
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_graph_replay(capi, fmt):
+    """The narrow format's graph against the float32 graph, N = 2048, one replay of sdr_graph_batches() batches with their own
+    inputs: the kernel takes each batch's pointer from the cursor field of its format."""
+    n = 2048
+    p = Pair(capi, n, fmt, False)
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    p.a.set_stream(streams[0].cuda_stream)
+    p.b.set_stream(streams[1].cuda_stream)
+    p.attach([0, n - 1, 300])
+    K = p.a.graph_batches
+    p.a.graph_capture(FRAMES)
+    if fmt == "sc16":
+        p.b.graph_capture_sc16(FRAMES)
+    else:
+        p.b.graph_capture_iq8(FRAMES, t8.FORMAT_IDS.index(fmt))
+    dev = [p.device(samples(fmt, (BANDS, FRAMES, 2 * n), 6000 + k)) for k in range(K)]
+    p.a.graph_launch([ta.data_ptr() for ta, _ in dev])
+    if fmt == "sc16":
+        p.b.graph_launch_sc16([tb.data_ptr() for _, tb in dev])
+    else:
+        p.b.graph_launch_iq8([tb.data_ptr() for _, tb in dev], t8.FORMAT_IDS.index(fmt))
+    p.check()  # (the read calls see the replay's last batch, the deliveries every batch)
+    p.a.graph_release()
+    p.b.graph_release()
+    p.close()
