@@ -260,6 +260,28 @@ int sdr_listener_count(sdr_bank *bank, int band);
 int sdr_listener_stop(sdr_bank *bank, int band, int listener_id);
 
 /* control ------------------------------------------------------------------------------------ */
+/* The reference applies each control between two frames (Receiver.do, rx/receiver.go:217-253); the bank applies it between
+ * two batches: a call takes effect from the next batch enqueued (the next replay of a captured graph) and leaves every
+ * batch enqueued before it - finished or not - as it was, what the read calls hand out of the last one included.
+ *   sdr_set_peak_threshold   the band's threshold in dB over the noise floor, from the next batch's first frame on - the
+ *                            cumulation that completes behind the call is searched with the new value, as in the
+ *                            reference.  Any float (+Inf: no peak).  Accepted with a listen half pending (it reaches the
+ *                            batch behind the pending one) and with a graph captured.  Drains the bank.
+ *   sdr_set_edge_width       FindNoiseFloor's edge width, the whole bank's, from the next batch on; SDR_ERR_BAD_ARG if
+ *                            negative or if fewer than 10 bins are left.  Accepted with a listen half pending.  With a
+ *                            graph captured a different value invalidates the capture (sdr_graph_launch returns
+ *                            SDR_ERR_STATE: release, capture again); the value the capture has leaves it valid.
+ *                            sdr_read_frame_records of the batch before the call still reads with the width it ran with.
+ *   sdr_set_signal_debounce  the debounce threshold of the band's listeners attached at the call (dsp/dsp.go:154-156: the
+ *                            threshold and nothing else of the debouncer - below 2 it passes the raw state through and
+ *                            keeps its count and states as they were, and a later threshold >= 2 picks them up again).  A
+ *                            listener attached later starts from sdr_config.signal_debounce.  SDR_ERR_STATE while a
+ *                            listen half is pending (sdr_process_listen first): its frames lie before the call.
+ *                            Accepted with a graph captured (the next replay runs with it).
+ *   sdr_set_find_peaks       whether completed cumulations are searched, from the next batch on (a cumulation that is
+ *                            not searched is delivered with no peaks).  Accepted with a listen half pending; with a graph
+ *                            captured a different value invalidates the capture.
+ * A band out of range is SDR_ERR_BAD_ARG and changes nothing. */
 int sdr_set_peak_threshold(sdr_bank *bank, int band, float threshold);
 int sdr_set_edge_width(sdr_bank *bank, int edge_width);
 int sdr_set_signal_debounce(sdr_bank *bank, int band, int debounce);
@@ -468,7 +490,8 @@ int sdr_read_drop_counters(sdr_bank *bank, uint64_t *runes_dropped, uint64_t *ed
  * their own (allocated at capture), so that consecutive replays overlap stage by stage like consecutive eager batches.
  * Needs a bank on a real stream (sdr_set_stream with a non-null stream) and, once captured, all processing to go
  * through sdr_graph_launch (sdr_process_* return SDR_ERR_STATE until sdr_graph_release).  Attaching or detaching a
- * listener, sdr_enable_results, sdr_enable_rows, sdr_enable_reports and sdr_set_find_peaks invalidate the capture (sdr_graph_launch returns SDR_ERR_STATE:
+ * listener, sdr_enable_results, sdr_enable_rows, sdr_enable_reports, sdr_set_find_peaks and sdr_set_edge_width with a
+ * value other than the capture's invalidate the capture (sdr_graph_launch returns SDR_ERR_STATE:
  * capture again).  Results are read / polled exactly as after sdr_process_device;
  * the "last batch" of the read calls is the last replay's last.  Not offered with overlapped frames yet:
  * sdr_graph_capture(_sc16, _iq8) on a bank with hop < block_size returns SDR_ERR_STATE. */
@@ -501,7 +524,8 @@ int sdr_graph_release(sdr_bank *bank);
  *   - sdr_group_process_device takes one device pointer per member, each laid out as sdr_process_device's over the
  *     member's local bands; every member is enqueued before the call waits for anything;
  *   - the setters apply to every member before the next process call: every band changes at the same frame
- *     (band = -1: every band);
+ *     (band = -1: every band); timing and refusals are the bank's (sdr_set_*), and sdr_group_set_signal_debounce with a
+ *     batch waiting for its listen half returns SDR_ERR_STATE before any member changes;
  *   - sdr_group_poll delivers batch k once every member has finished it, merged into one sdr_results with global band
  *     numbers in exactly one bank's order (chunks by band, then chunk; listeners by band, then slot), first_peak /
  *     first_edge / first_rune renumbered, drop counters summed.  A member batch already taken from its bank is kept by

@@ -104,6 +104,8 @@ def lib():
     sig("orc_debouncer_new", C.c_void_p, C.c_int)
     sig("orc_debouncer_debounce", C.c_int, C.c_void_p, C.c_int)
     sig("orc_debouncer_free", None, C.c_void_p)
+    sig("orc_debouncer_set_threshold", None, C.c_void_p, C.c_int)
+    sig("orc_debouncer_state", None, C.c_void_p, ip)
     sig("orc_goertzel_blocksize", C.c_int, C.c_double, C.c_int, C.c_double)
     sig("orc_morse_count", C.c_int)
     sig("orc_morse_rune", C.c_uint32, C.c_int)
@@ -150,6 +152,8 @@ def lib():
     sig("orc_receiver_set_peak_threshold", None, C.c_void_p, C.c_float)
     sig("orc_receiver_set_edge_width", None, C.c_void_p, C.c_int)
     sig("orc_receiver_set_find_peaks", None, C.c_void_p, C.c_int)
+    sig("orc_receiver_set_signal_debounce", None, C.c_void_p, C.c_int)
+    sig("orc_receiver_debouncer_state", None, C.c_void_p, C.c_int, ip)
     sig("orc_receiver_attach", C.c_int, C.c_void_p, C.c_int)
     sig("orc_receiver_detach", None, C.c_void_p, C.c_int)
     sig("orc_receiver_text_len", C.c_int, C.c_void_p, C.c_int)
@@ -368,6 +372,17 @@ class Receiver:
 
     def set_find_peaks(self, on: bool):
         lib().orc_receiver_set_find_peaks(self._h, int(on))
+
+    def set_signal_debounce(self, d: int):
+        """The debounce threshold of the listeners attached now (dsp/dsp.go:154-156 on each: the threshold and nothing
+        else); a listener attached later starts from the constructor's value."""
+        lib().orc_receiver_set_signal_debounce(self._h, int(d))
+
+    def debouncer_state(self, lid: int):
+        """(threshold, effectiveState, lastRawState, stateCount) of listener lid's debouncer."""
+        out = (C.c_int * 4)()
+        lib().orc_receiver_debouncer_state(self._h, lid, out)
+        return tuple(out)
 
     def text(self, lid: int) -> str:
         return runes_to_str(lib().orc_receiver_text(self._h, lid), lib().orc_receiver_text_len(self._h, lid))

@@ -1414,6 +1414,32 @@ ORC_API void orc_receiver_free(void *h)
 ORC_API void orc_receiver_set_peak_threshold(void *h, float t) { ((orc_receiver *)h)->peakThreshold = t; }
 ORC_API void orc_receiver_set_edge_width(void *h, int e) { ((orc_receiver *)h)->edgeWidth = e; }
 ORC_API void orc_receiver_set_find_peaks(void *h, int on) { ((orc_receiver *)h)->find_peaks_enabled = on; }
+/* rx/receiver.go:212-216 -> rx/listener.go -> dsp/dsp.go:154-156 SetThreshold: the threshold of every listener attached
+ * at the call, and nothing else - stateCount, lastRawState and effectiveState stay what they are (stale while the
+ * threshold is below 2, picked up again by a later threshold >= 2).  The receiver's own value is left alone: a listener
+ * attached later starts from the constructor's (the bank's rule, include/sdrainer_hip.h sdr_set_signal_debounce). */
+ORC_API void orc_receiver_set_signal_debounce(void *h, int debounce)
+{
+    orc_receiver *r = (orc_receiver *)h;
+    for (int i = 0; i < r->n_listeners; i++)
+        if (r->listeners[i].attached)
+            r->listeners[i].deb.threshold = debounce;
+}
+/* dsp/dsp.go:154-156 on a bare debouncer */
+ORC_API void orc_debouncer_set_threshold(void *h, int threshold) { ((orc_debouncer *)h)->threshold = threshold; }
+/* (threshold, effectiveState, lastRawState, stateCount) of a bare debouncer / of listener id's */
+ORC_API void orc_debouncer_state(void *h, int *out4)
+{
+    const orc_debouncer *d = (const orc_debouncer *)h;
+    out4[0] = d->threshold;
+    out4[1] = d->effectiveState;
+    out4[2] = d->lastRawState;
+    out4[3] = d->stateCount;
+}
+ORC_API void orc_receiver_debouncer_state(void *h, int id, int *out4)
+{
+    orc_debouncer_state(&((orc_receiver *)h)->listeners[id].deb, out4);
+}
 
 /* Attach a fresh listener to `bin` (rx/listener.go:84-94 Attach on a newly
  * bound listener: new SpectralDemodulator => new debouncer (threshold =

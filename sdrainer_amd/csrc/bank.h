@@ -200,6 +200,7 @@ struct sdr_bank {
     int last_set = 0, last_frames = 0, last_chunks = 0, last_count0 = 0;
     int last_carry_in = 0;  // which carry buffer the last batch's first cumulation started from (exact rows on demand)
     int edge_width = 0;
+    int last_edge_width = 0;  // the edge width the last batch ran with (sdr_set_edge_width may have moved edge_width since)
     int find_peaks = 1;
     bool failed = false;  // a HIP call failed in the middle of a launch sequence: device state is unknown
     DevBuf<sdr::DropCounters> drops;
@@ -220,6 +221,7 @@ struct sdr_bank {
     // refinement / peak-scan nodes only if find_peaks was
     bool graph_results_on = false;
     int graph_find_peaks = 0;
+    int graph_edge_width = 0;  // ... and the noise geometry is an argument of the captured noise kernels
     int graph_rows = 0;  // ... and the rows kernel only if rows were on, with the column count of the capture
     int graph_reports = 0;  // ... and the report kernels only if reports were (-1: the capture holds report blocks that are gone)
     // deferred listen half (sdr_defer_listen): the batch whose spectra exist and whose listeners have not run yet
@@ -275,7 +277,8 @@ struct sdr_bank {
     int prof_n[sdr::K_PROFILE_SLOTS] = {};
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
 
-    sdr::NoiseGeom noise_geom() const
+    sdr::NoiseGeom noise_geom() const { return noise_geom(edge_width); }
+    sdr::NoiseGeom noise_geom(int edge_width) const
     {
         sdr::NoiseGeom g;
         g.n = cfg.block_size;

@@ -665,6 +665,10 @@ int sdr_set_signal_debounce(sdr_bank *b, int band, int debounce)
     int rc = check_band(b, band);
     if (rc)
         return rc;
+    // The kernel runs on the listen stream, where the pending half's decoders have not run yet: it would reach frames that
+    // lie before the call (the reference applies a control between two frames, rx/receiver.go:217-253).
+    if (b->listen_pending)
+        return fail(SDR_ERR_STATE, "the listen half of a deferred batch is pending (sdr_process_listen first)");
     if (b->n_slots[band] == 0)
         return SDR_OK;
     HIP_TRY(hipSetDevice(b->device));

@@ -227,6 +227,7 @@ static int graph_capture(sdr_bank *b, int n_frames, sdr::InFormat fmt)
     b->graph_attach_gen = b->attach_gen;
     b->graph_results_on = b->results_on;
     b->graph_find_peaks = b->find_peaks;
+    b->graph_edge_width = b->edge_width;
     b->graph_rows = b->row_columns;
     b->graph_reports = b->reports_on ? 1 : 0;
     return SDR_OK;
@@ -259,6 +260,9 @@ static int graph_launch(sdr_bank *b, const void *const *iq_dev, sdr::InFormat fm
     if (b->results_on != b->graph_results_on || b->find_peaks != b->graph_find_peaks || b->row_columns != b->graph_rows ||
         (b->reports_on ? 1 : 0) != b->graph_reports)
         return fail(SDR_ERR_STATE, "sdr_enable_results / sdr_set_find_peaks / sdr_enable_rows / sdr_enable_reports changed since the capture: capture again");
+    // ... and the noise geometry is an argument of the captured noise kernels: a replay would run with the capture's
+    if (b->edge_width != b->graph_edge_width)
+        return fail(SDR_ERR_STATE, "sdr_set_edge_width changed the edge width since the capture: capture again");
     HIP_TRY(hipSetDevice(b->device));
     const bool dbg = b->sw.graph_debug;
     double tdbg[8] = {};
@@ -392,6 +396,7 @@ static int graph_launch(sdr_bank *b, const void *const *iq_dev, sdr::InFormat fm
         b->last_chunks = meta[k].chunks;
         b->last_count0 = meta[k].count0;
         b->last_carry_in = pack.c[k].carry_in;
+        b->last_edge_width = b->graph_edge_width;
         b->batch_index++;
     }
     if (!b->results_on)

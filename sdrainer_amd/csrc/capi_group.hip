@@ -327,6 +327,9 @@ int sdr_group_set_signal_debounce(sdr_group *g, int band, int debounce)
         return fail(SDR_ERR_BAD_ARG, "null group");
     if (band < -1 || band >= g->rt.n_bands)
         return fail(SDR_ERR_BAD_ARG, "band out of range (-1: every band)");
+    for (sdr_bank *b : g->banks)  // (refused before any member changes, as sdr_group_set_window is)
+        if (sdr_listen_pending(b))
+            return fail(SDR_ERR_STATE, "a batch waits for its listen half (sdr_group_process_listen)");
     KeepDevice keep;
     for (int b = band < 0 ? 0 : band; b < (band < 0 ? g->rt.n_bands : band + 1); b++) {
         const int rc = sdr_set_signal_debounce(g->banks[(size_t)g->rt.member_of(b)], g->rt.local_of(b), debounce);

@@ -463,6 +463,7 @@ void commit_batch(const BatchIssue &is)
     b->last_frames = is.n_frames;
     b->last_chunks = is.P.n_chunks;
     b->last_count0 = is.count0;
+    b->last_edge_width = b->edge_width;
     if (!is.do_listen) {
         b->pend.set = is.si;
         b->pend.frames = is.n_frames;

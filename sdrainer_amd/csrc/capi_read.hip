@@ -201,12 +201,13 @@ int sdr_read_frame_records(sdr_bank *b, int band, sdr_frame_rec *out, int max)
         // The hot path (k_noise_scan.hip) produces FindNoiseFloor's CONSUMED values and only brackets the float64 variance,
         // which nothing consumes.  A read gets the reference's variance - the literal loops run here, for every frame of
         // the batch - and the same pass compares the consumed values with the literal ones: a difference is an error.
+        // The geometry is the one the batch ran with: sdr_set_edge_width since then is the next batch's.
         if (sdr::noise_scan_at(b->sw, b->cfg.block_size)) {
             unsigned *mism = nullptr, h = 0;
             HIP_TRY(hipMalloc(&mism, sizeof(unsigned)));
             hipError_t e = hipMemset(mism, 0, sizeof(unsigned));
             if (e == hipSuccess)
-                e = sdr::launch_noise_exact_check(S.psd.p + (size_t)band * b->cfg.max_batch_frames * b->cfg.block_size, recs, b->noise_geom(),
+                e = sdr::launch_noise_exact_check(S.psd.p + (size_t)band * b->cfg.max_batch_frames * b->cfg.block_size, recs, b->noise_geom(b->last_edge_width),
                                                   b->last_frames, mism, nullptr);
             if (e == hipSuccess)
                 e = hipMemcpy(&h, mism, sizeof h, hipMemcpyDeviceToHost);

@@ -367,6 +367,82 @@ static int run_decode(const char *path, int rate, int n, int frames, long long v
     return 0;
 }
 
+// Receiver::SetSignalDebounce / SetPeakThreshold / SetEdgeWidth after Start, between batches (DecodeMode, one listener on
+// the VFO's bin).  The batches are `cuts` frames long, one IQData + Process each; behind batch i the controls of row i of
+// the table below are set.  Prints the listener's text and, per batch, the bits of the bank's min_mean, peak_thr and
+// listen_thr records of the last segment the batch ran as (a batch may run as several).
+static int run_setters(const char *path, int rate, int n, long long vfo_offset, int n_cuts, char **cuts)
+{
+    struct Row {
+        int debounce;
+        float threshold;
+        int edge;
+    };
+    const Row rows[] = {{3, 9.0f, 1}, {0, 21.5f, (n - 10 * (n / 16)) / 2}, {5, -3.0f, (n - 10) / 2}, {2, 15.0f, 70 * n / 512}};
+    int frames = 0;
+    for (int i = 0; i < n_cuts; i++)
+        frames += atoi(cuts[i]);
+    FILE *f = fopen(path, "rb");
+    if (!f)
+        return 2;
+    std::vector<float> iq((size_t)frames * 2 * n);
+    if (fread(iq.data(), sizeof(float), iq.size(), f) != iq.size())
+        return 2;
+    fclose(f);
+    PrintReporter rep;
+    rx::Receiver r("rx", rx::DecodeMode);
+    r.AddReporter(&rep);
+    r.SetCenterFrequency(7020000);
+    r.SetEdgeWidth(70 * n / 512);
+    if (r.Start(rate, n, 256) != SDR_OK)
+        return 3;
+    if (r.SetVFOOffset(vfo_offset) != SDR_OK)
+        return 4;
+    printf("{\"batches\": [");
+    int pos = 0;
+    for (int i = 0; i < n_cuts; i++) {
+        const int m = atoi(cuts[i]);
+        if (r.IQData(rate, iq.data() + (size_t)pos * 2 * n, (size_t)m * 2 * n) != SDR_OK || r.Process() != SDR_OK)
+            return 5;
+        pos += m;
+        if (i < (int)(sizeof rows / sizeof rows[0])) {
+            r.SetSignalDebounce(rows[i].debounce);
+            r.SetPeakThreshold(rows[i].threshold);
+            r.SetEdgeWidth(rows[i].edge);
+        }
+        // (behind the setters: the read is of the batch before them)
+        const int last = sdr_last_batch_frames(r.Bank());
+        std::vector<sdr_frame_rec> recs((size_t)std::max(last, 1));
+        if (sdr_read_frame_records(r.Bank(), 0, recs.data(), last) != SDR_OK)
+            return 6;
+        printf("%s{\"end\": %d, \"min_mean\": [", i ? ", " : "", pos);
+        for (int k = 0; k < last; k++) {
+            uint32_t u;
+            memcpy(&u, &recs[(size_t)k].min_mean, 4);
+            printf("%s%u", k ? ", " : "", u);
+        }
+        printf("], \"peak_thr\": [");
+        for (int k = 0; k < last; k++) {
+            uint32_t u;
+            memcpy(&u, &recs[(size_t)k].peak_thr, 4);
+            printf("%s%u", k ? ", " : "", u);
+        }
+        printf("], \"listen_thr\": [");
+        for (int k = 0; k < last; k++) {
+            uint32_t u;
+            memcpy(&u, &recs[(size_t)k].listen_thr, 4);
+            printf("%s%u", k ? ", " : "", u);
+        }
+        printf("]}");
+    }
+    const auto l = r.Listeners().First();
+    printf("], \"frames\": %lld, \"bin\": %d, \"text\": \"", (long long)r.FramesProcessed(), l ? l->SignalBin() : -1);
+    for (unsigned char c : (l ? l->Text() : std::string()))
+        printf("\\u%04x", c);
+    printf("\"}\n");
+    return 0;
+}
+
 // ---- rx/text_processor_test.go ---------------------------------------------------------------
 static void TestTextWindow_Write()  // :10-69
 {
@@ -660,6 +736,8 @@ int main(int argc, char **argv)
                           argc >= 13 ? atoll(argv[12]) : 0);
     if (argc >= 7 && !strcmp(argv[1], "decode"))
         return run_decode(argv[2], atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), atoll(argv[6]));
+    if (argc >= 7 && !strcmp(argv[1], "setters"))
+        return run_setters(argv[2], atoi(argv[3]), atoi(argv[4]), atoll(argv[5]), argc - 6, argv + 6);
     fprintf(stderr, "usage: %s cpu | text | strain <iq.f32> <rate> <N> <frames> <pool>\n", argv[0]);
     return 2;
 }

@@ -104,10 +104,10 @@ def key_matrix(frames, kinds, seed, dits=None, symbols=None, lead=LEAD):
     return keys
 
 
-def keyed_band(n, rate, keys, seed, amplitude=synth.TONE_AMPLITUDE, hop=None, lead=LEAD):
+def keyed_band(n, rate, keys, seed, amplitude=synth.TONE_AMPLITUDE, hop=None, lead=LEAD, sigma=synth.NOISE_SIGMA):
     """(float32 frames [F, 2N], None, the carriers' bins): what Case(bands=...) takes.  One carrier per column of keys [F, L]
     on synth.tone_bins (the last noise window kept free), hard-keyed per frame, built as synth.make_band builds its bands:
-    the inverse FFT of a sparse spectrum plus synth.NOISE_SIGMA of noise.  The sample rate takes no part: the keying is given
+    the inverse FFT of a sparse spectrum plus `sigma` (synth.NOISE_SIGMA) of noise.  The sample rate takes no part: the keying is given
     in frames.
     hop (below n, a divisor of it): keys has a row per hop; the rows are built at block size `hop` and flattened into one
     continuous stream float32 [F * hop, 2], as parity_tools.make_stream does - every carrier makes whole cycles per hop, and
@@ -128,7 +128,7 @@ def keyed_band(n, rate, keys, seed, amplitude=synth.TONE_AMPLITUDE, hop=None, le
         spec = np.zeros((k.shape[0], size), np.complex128)
         spec[:, fft_bins] = amplitude * size * k.astype(np.float64)
         x = np.fft.ifft(spec, axis=1)
-        x += synth.NOISE_SIGMA * (rng.standard_normal(x.shape) + 1j * rng.standard_normal(x.shape))
+        x += sigma * (rng.standard_normal(x.shape) + 1j * rng.standard_normal(x.shape))
         iq[a:a + 4096, 0::2] = x.real
         iq[a:a + 4096, 1::2] = x.imag
     if hop:

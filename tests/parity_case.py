@@ -32,13 +32,14 @@ import numpy as np
 from iq8_tools import to_f32 as iq8_to_float32
 from oracle import oracle as orc
 from sdrainer_amd import synth
-from parity_tools import (RATES, bits_equal, check_batch_polled, check_device_batch, decode, frames32, frames_of, listener_bins,
+from parity_tools import (RATES, REC_FIELDS, bits_equal, check_batch_polled, check_device_batch, decode, frames32, frames_of, listener_bins,
                           make_stream, nan_equal_bits, sc16_to_float32, windowed)
 
 RATE = 2_000_000
 PATHS = ("device", "device_sc16", "device_cs8", "device_cu8", "staged", "staged_sc16", "kiwi", "graph", "graph_sc16")
 SC16_PATHS = ("device_sc16", "staged_sc16", "kiwi", "graph_sc16")
 IQ8_PATHS = {"device_cs8": 0, "device_cu8": 1}  # -> SDR_IQ8_CS8 / SDR_IQ8_CU8
+SETTERS = ("peak_threshold", "edge_width", "signal_debounce", "find_peaks")
 KIWI_HEADER = bytes([0x01] + [7] * 16)  # the 17 bytes in front of an SND message's samples (flags, sequence, smeter)
 
 
@@ -61,6 +62,11 @@ def _per_band(v, n_bands):
     return list(v) if isinstance(v, (list, tuple)) else [v] * n_bands
 
 
+def _refused(s):
+    """A ("set", ...) step whose value is ("bad", value): the bank must refuse it."""
+    return isinstance(s[3], tuple) and s[3][0] == "bad"
+
+
 class Case:
     """One bank's stream: bands of keyed carriers, the listeners attached before the first frame, then a list of steps
        ("batch", frames)                      an eager batch
@@ -68,6 +74,16 @@ class Case:
        ("attach", band, bin) / ("detach", band, lid)   between batches
        ("stop", band, lid)                    sdr_listener_stop between batches (with a hop or with trace: the hop-timed
                                               decoder is stopped there, and what it writes is stamped with the frame before)
+       ("set", name, band, value)             a control between two batches, on the bank and on the oracle(s): name is
+                                              "peak_threshold" or "signal_debounce" (band: the band), "edge_width" or
+                                              "find_peaks" (band: None, the bank's).  A value the bank must refuse is
+                                              ("bad", value): SDR_ERR_BAD_ARG is expected and the oracle is not told.
+                                              After every accepted "edge_width", and before the next batch,
+                                              sdr_read_frame_records of the batch just finished must return SDR_OK and
+                                              the oracle's records - those of the width the batch ran with
+    A deferred batch takes a fourth element, a list of ("set", ...) steps called while its listen half is pending: the
+    bank must refuse "signal_debounce" there (SDR_ERR_STATE, the oracle is not told) and accept the others, which reach the
+    next batch only (the oracle is told behind the deferred batch's last frame).
     (steps may also be a function of the carriers' bins per band, which exist once the input does)
 
     Per band (a value, or a list with one per band): peak threshold and centre frequency.  The sample rate, the edge width
@@ -77,7 +93,10 @@ class Case:
     (float32 stream [samples, 2] or its dense frames [total, 2N], int16 of the same shape or None, carrier bins) per band -
     the int16 array is what the sc16 and KiwiSDR paths send, and the float32 one must then be its value (sc16_to_float32).
     Graph paths take batches of one length, sdr_graph_batches() of them per replay, with attach, detach and a new window
-    only between replays (each one is followed by a release and a new capture); no deferred batches.  nan_ok: the oracle's
+    only between replays (each one is followed by a release and a new capture); no deferred batches.  A "set" between
+    replays is called with the capture in place: the next replay runs without a new capture, except behind an "edge_width"
+    or "find_peaks" that changed the value - then sdr_graph_launch must refuse (SDR_ERR_STATE) and a release and a new
+    capture follow.  nan_ok: the oracle's
     stream holds NaN (a silent run: -Inf and then NaN in the rolling means and thresholds), and NaN compares by class in
     the float fields.
 
@@ -188,6 +207,8 @@ class Case:
             elif s[0] == "stop":
                 assert self.timed and pos > self.life[s[1]][s[2]][0], "a stop needs the hop-timed decoders, behind the listener's first frame"
                 self.stops.setdefault((s[1], s[2]), []).append(pos)
+            elif s[0] == "set":
+                assert s[1] in SETTERS and (s[2] is None) == (s[1] in ("edge_width", "find_peaks")), f"no such control: {s}"
             else:
                 for band, bn, at in s[2] if s[0] == "defer" else []:
                     assert pos <= at <= pos + s[1], f"band {band}: attach_at frame {at} outside its batch (or the frame behind it)"
@@ -240,11 +261,16 @@ class Case:
                     ev.append((pos, "attach", s[2]))
                 elif s[0] == "detach" and s[1] == b:
                     ev.append((pos, "detach", s[2]))
+                elif s[0] == "set" and s[2] in (None, b) and not _refused(s):
+                    ev.append((pos, "set", (s[1], s[3])))
                 elif s[0] == "defer":
                     ev += [(at, "attach", bn) for band, bn, at in s[2] if band == b]
+                    # (controls called while the listen half is pending: behind the batch's last frame, behind its attaches)
+                    ev += [(pos + s[1], "set", (t[1], t[3])) for t in (s[3] if len(s) > 3 else [])
+                           if t[2] in (None, b) and t[1] != "signal_debounce" and not _refused(t)]
                 if s[0] in ("batch", "defer"):
                     pos += s[1]
-            return ev
+            return sorted(ev, key=lambda x: x[0])  # (stable: the call order within a frame)
 
         def run(b):
             r = orc.Receiver(self.rate, self.n, self.edge, self.threshold[b], self.debounce, center_frequency=self.centers[b])
@@ -252,7 +278,9 @@ class Case:
                 r.attach(int(bn))
             L = len(self.bins[b])
             st = {"frames": [], "deb": np.zeros((self.total, L), np.uint8), "raw": np.zeros((self.total, L), np.uint8),
-                  "values": np.zeros((self.total, L), np.float32), "peaks": [], "peak_frames": [], "cumulation": []}
+                  "values": np.zeros((self.total, L), np.float32), "peaks": [], "peak_frames": [], "cumulation": [],
+                  # (frame, name, value, every listener's debouncer (threshold, effective, last raw, count) before the call)
+                  "sets": []}
             pos = 0
             for at, kind, arg in band_events(b) + [(self.total, None, None)]:
                 if at > pos:
@@ -268,6 +296,9 @@ class Case:
                     r.attach(int(arg))
                 elif kind == "detach":
                     r.detach(int(arg))
+                elif kind == "set":
+                    st["sets"].append((at, arg[0], arg[1], [r.debouncer_state(l) for l in range(r.n_listeners)]))
+                    getattr(r, "set_" + arg[0])(arg[1])
             st["frames"] = np.concatenate(st["frames"])
             st["peak_frames"] = np.array(st["peak_frames"], np.int64)
             return r, st
@@ -323,12 +354,40 @@ class Case:
         self.rune_at = [[[] for _ in bins] for bins in self.bins]
         self.edges = self.peaks = 0
         self.window = None  # (a bank that never had a window is never told about one)
+        self.controls = {"edge_width": self.edge, "find_peaks": True}
 
     def set_window(self, bank, k):
         """Batch k's window, if it is not the one the bank has."""
         if self.windows[k] is not self.window:
             self.window = self.windows[k]
             bank.set_window(self.window)
+
+    def apply_set(self, capi, bank, s, last, pending=False):
+        """One ("set", ...) step on the bank.  last: (a, e, k) of the batch just enqueued, or None; pending: its listen
+        half is pending.  self.controls follows the two controls a captured graph has baked in."""
+        _, name, band, value = s
+        call = {"peak_threshold": lambda v: bank.set_peak_threshold(band, v), "edge_width": bank.set_edge_width,
+                "signal_debounce": lambda v: bank.set_signal_debounce(band, v), "find_peaks": bank.set_find_peaks}[name]
+        refuse = capi.ERR_BAD_ARG if _refused(s) else capi.ERR_STATE if pending and name == "signal_debounce" else None
+        if refuse is not None:
+            try:
+                call(value[1] if _refused(s) else value)
+            except capi.SdrError as err:
+                assert err.code == refuse, f"{s}: refused with {err.code}, not {refuse}"
+                return
+            raise AssertionError(f"{s}: accepted, SDR_ERR {refuse} expected")
+        call(value)
+        if name in self.controls:
+            self.controls[name] = value
+        if name == "edge_width" and last is not None:
+            # the batch before ran with the width before: its records are still the oracle's, its variance included, and
+            # the read's own comparison with the literal FindNoiseFloor (an error if it fails) uses that width too
+            a, e, k = last
+            for b in range(self.n_bands):
+                recs = bank.read_frame_records(b)
+                same = nan_equal_bits if self.nan_ok else bits_equal
+                for f in REC_FIELDS:
+                    assert same(recs[f], self.outs[b]["frames"][f][a:e].copy()), f"band {b} batch {k} field {f}, read behind {s}"
 
     def gone(self, a):
         """(band, listener) pairs detached before frame a whose slot nobody has taken over by then."""
@@ -439,19 +498,25 @@ class Case:
         return None
 
     # -- runs --------------------------------------------------------------------------------------------------------------
-    def run(self, capi, min_edges=20, lag=False, activity=True):
+    def run(self, capi, min_edges=20, lag=False, activity=True, prepare=None, before_poll=None):
         """Every step on one bank, each batch checked when it is delivered.  lag: a batch is polled only once the next one
         is enqueued (the listen stream may then still run one batch while the next batch's spectral stages start), and
-        what stays on the device is checked for the last batch only."""
+        what stays on the device is checked for the last batch only.  prepare(bank): called on the new bank, in front of
+        the first step; before_poll(bank, k): called in front of the sdr_poll that delivers batch k (neither on the graph
+        paths)."""
         if self.path.startswith("graph"):
             return self.run_graph(capi, min_edges, activity)
         self.run_oracle()
         bank = self.new_bank(capi)
+        if prepare:
+            prepare(bank)
         pos, k = 0, 0
         pending = []  # (first frame, end, batch index, input) enqueued and not yet polled
 
         def deliver(last):
             a, e, i, _ = pending.pop(0)
+            if before_poll:
+                before_poll(bank, i)
             res = bank.poll(wait=True)
             assert res["batch_index"] == i, f"batch {i} delivered as {res['batch_index']}"
             self.check_polled(res, a, e)
@@ -470,6 +535,9 @@ class Case:
             if s[0] == "stop":
                 bank.listener_stop(s[1], self.slot[s[1]][s[2]])
                 continue
+            if s[0] == "set":
+                self.apply_set(capi, bank, s, (self.spans[k - 1] + (k - 1,)) if k else None)
+                continue
             a, e = pos, pos + s[1]
             self.set_window(bank, k)
             if s[0] == "defer":
@@ -481,6 +549,8 @@ class Case:
                     got = bank.attach_at(band, int(bn), self.first_frame + at)
                     assert got == self.slot[band][slots[band]], f"band {band}: attach_at gave listener {got}"
                     slots[band] += 1
+                for t in s[3] if len(s) > 3 else []:
+                    self.apply_set(capi, bank, t, (a, e, k), pending=True)
                 bank.process_listen()
                 bank.defer_listen(False)
             else:
@@ -500,7 +570,7 @@ class Case:
         device after the last batch of every replay."""
         import torch
 
-        assert all(s[0] in ("batch", "attach", "detach") for s in self.steps), "graph mode takes no deferred batch"
+        assert all(s[0] in ("batch", "attach", "detach", "set") for s in self.steps), "graph mode takes no deferred batch"
         per = {s[1] for s in self.steps if s[0] == "batch"}
         assert len(per) == 1, "graph mode: batches of one length"
         per = per.pop()
@@ -509,7 +579,7 @@ class Case:
         K = bank.graph_batches
         sc16 = self.path == "graph_sc16"
         slots = [len(bins) for bins in self.init_bins]
-        pos, k, captured, run = 0, 0, False, []
+        pos, k, captured, run, baked = 0, 0, False, [], None  # baked: self.controls as of the capture
         for s in self.steps + [("end",)]:
             if s[0] == "batch":
                 run.append((pos, pos + per))
@@ -521,12 +591,25 @@ class Case:
                     bank.graph_release()
                     captured = False
                 self.set_window(bank, k)
-                if not captured:
-                    (bank.graph_capture_sc16 if sc16 else bank.graph_capture)(per)
-                    captured = True
                 batches = [self.device_batch(a, e) for a, e in run]
                 torch.cuda.synchronize()  # (the input is written on torch's stream, the bank reads it on its own)
-                (bank.graph_launch_sc16 if sc16 else bank.graph_launch)([x.data_ptr() for x in batches])
+
+                def launch():
+                    (bank.graph_launch_sc16 if sc16 else bank.graph_launch)([x.data_ptr() for x in batches])
+                if captured and baked != self.controls:  # a control the capture has baked in changed: the replay is refused, nothing has run
+                    try:
+                        launch()
+                    except capi.SdrError as err:
+                        assert err.code == capi.ERR_STATE, f"replay behind a changed control: refused with {err.code}"
+                    else:
+                        raise AssertionError("a replay behind a changed edge width or find_peaks was accepted")
+                    assert bank.total_frames == self.first_frame + run[0][0], "a refused replay moved the bank"
+                    bank.graph_release()
+                    captured = False
+                if not captured:
+                    (bank.graph_capture_sc16 if sc16 else bank.graph_capture)(per)
+                    captured, baked = True, dict(self.controls)
+                launch()
                 for a, e in run:
                     res = bank.poll(wait=True)
                     assert res["batch_index"] == k, f"batch {k} delivered as {res['batch_index']}"
@@ -540,6 +623,9 @@ class Case:
             assert not run, "graph mode: listener changes only between replays"
             if s[0] == "end":
                 break
+            if s[0] == "set":  # (with the capture in place)
+                self.apply_set(capi, bank, s, (self.spans[k - 1] + (k - 1,)) if k else None)
+                continue
             if captured:  # a listener change invalidates the capture (capi_graph.hip): release, capture again later
                 bank.graph_release()
                 captured = False

@@ -402,3 +402,45 @@ def test_decode_mode_vfo_listener(exe, tmp_path):
     assert bytes(ord(ch) for ch in got["text1"]).decode("utf-8") == ref.text(b) != ""
     f = center + offset
     assert got["events"] == [f"+rx1@{f}", f"-rx1@{f}", f"+rx1@{f}"]
+
+
+@pytest.mark.gpu
+def test_decode_mode_setters_between_batches(exe, tmp_path):
+    """Receiver::SetSignalDebounce, SetPeakThreshold and SetEdgeWidth after Start, between batches, against the oracle with
+    the same calls at the same frames: the listener's text (glitching raw states under debounce 1 -> 3 -> 0 -> 5 -> 2) and,
+    read behind each round of setters, the last segment's min_mean, peak_thr and listen_thr records - those of the width
+    and threshold the batch ran with.  (rx.h runs the listen half of a deferred segment inside the Process call that
+    enqueued it - discoverAhead ends with sdr_process_listen - so no setter of a caller between two calls can meet a
+    pending half, which sdr_set_signal_debounce would refuse.)"""
+    import setters_gen as gen
+    from oracle import oracle as orc
+
+    rate, n, cuts = gen.RATE, gen.N, (180, 150, 1, 170, 149)
+    iq, _, bins = gen.band_input(n, sum(cuts), gen.PATH_KINDS, 9100)
+    sb = bins[1]  # (a "jitter" carrier)
+    offset = int((sb - n // 2) * rate / n) + 20
+    path = tmp_path / "iq.f32"
+    iq.tofile(path)
+    out = subprocess.run([exe, "setters", str(path), str(rate), str(n), str(offset)] + [str(c) for c in cuts], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    got = json.loads(out.stdout)
+    assert got["frames"] == sum(cuts) and got["bin"] == sb
+    rows = [(3, 9.0, 1), (0, 21.5, gen.nine_window_edge(n)), (5, -3.0, gen.one_bin_edge(n)), (2, 15.0, gen.EDGE)]
+    ref = orc.Receiver(rate, n, gen.EDGE, 15.0, 1, center_frequency=7020000)
+    lid = ref.attach(sb)
+    pos, differ = 0, 0
+    for i, c in enumerate(cuts):
+        want = ref.process(iq[pos:pos + c])
+        pos += c
+        differ += int((want["raw"][:, lid] != want["deb"][:, lid]).sum())
+        if i < len(rows):
+            ref.set_signal_debounce(rows[i][0])
+            ref.set_peak_threshold(rows[i][1])
+            ref.set_edge_width(rows[i][2])
+        b = got["batches"][i]
+        k = len(b["min_mean"])
+        assert b["end"] == pos and 1 <= k <= c
+        for f in ("min_mean", "peak_thr", "listen_thr"):
+            assert b[f] == want["frames"][f][c - k:].view(np.uint32).tolist(), (i, f)
+    assert differ >= 20, "the debouncer changes too little"
+    assert bytes(ord(ch) for ch in got["text"]).decode("utf-8") == ref.text(lid) != ""

@@ -425,3 +425,59 @@ def test_kiwi_iq_bytes_decode():
     want = vals.astype(np.float32) / np.float32(32767)
     assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), want.view(np.uint32))
     assert got[3] == 1.0 and got[4] < -1.0  # -32768/32767: the reference does not clamp
+
+
+def test_debouncer_under_a_changing_threshold():
+    """dsp/dsp.go:154-182: SetThreshold changes the threshold and nothing else.  Below 2 the debouncer passes the raw state
+    through and leaves stateCount, lastRawState and effectiveState as they were; a later threshold >= 2 picks them up
+    again.  The oracle's debouncer against a literal Python re-reading (setters_gen.Debouncer), state by state, over
+    glitching runs while the threshold goes 3 -> 1 -> 5 -> 70 -> 2 -> 0 -> 3 -> 1 -> 4."""
+    import ctypes as C
+
+    import setters_gen
+
+    L = orc.lib()
+    rng = np.random.default_rng(154)
+    h, d = L.orc_debouncer_new(1), setters_gen.Debouncer(1)
+    stale = resumed = 0
+    try:
+        for threshold in (3, 1, 5, 70, 2, 0, 3, 1, 4):
+            before = d.state()
+            L.orc_debouncer_set_threshold(h, threshold)
+            d.set_threshold(threshold)
+            got = (C.c_int * 4)()
+            L.orc_debouncer_state(h, got)
+            assert tuple(got) == (threshold,) + before[1:] == d.state(), "SetThreshold touched the state"
+            raw = np.repeat(rng.integers(0, 2, 120), rng.integers(1, 9, 120))[:257 if threshold != 70 else 400]
+            if threshold == 70:
+                raw[150:330] = 1  # (a run that reaches 70)
+            for i, r in enumerate(raw):
+                assert L.orc_debouncer_debounce(h, int(r)) == int(d.debounce(r)), (threshold, i)
+                L.orc_debouncer_state(h, got)
+                assert tuple(got) == d.state(), (threshold, i)
+            if threshold < 2:
+                assert d.state()[1:] == before[1:], "the pass-through moved the state"
+                stale += d.state()[2] != int(raw[-1]) or d.state()[1] != int(raw[-1])
+            elif before[0] < 2:
+                resumed += 1
+    finally:
+        L.orc_debouncer_free(h)
+    assert stale >= 1 and resumed >= 3, (stale, resumed)
+
+
+def test_receiver_set_signal_debounce_reaches_the_attached_listeners_only():
+    """orc.Receiver.set_signal_debounce: the threshold of the listeners attached at the call and nothing else of them; a
+    detached listener keeps its own, and one attached later starts from the constructor's value."""
+    r = orc.Receiver(48000, 512, 70, 15.0, 2)
+    for b in (100, 200, 300):
+        r.attach(b)
+    rng = np.random.default_rng(5)
+    iq = (1e-3 * rng.standard_normal((40, 1024))).astype(np.float32)
+    iq[:, 0] += np.float32(0.1)  # (bin 256 carries the DC line: it takes no part)
+    r.process(iq)
+    before = [r.debouncer_state(l) for l in range(3)]
+    assert any(s[3] > 0 for s in before)
+    r.detach(1)
+    r.set_signal_debounce(7)
+    assert [r.debouncer_state(l) for l in range(3)] == [(7,) + before[0][1:], before[1], (7,) + before[2][1:]]
+    assert r.attach(150) == 3 and r.debouncer_state(3) == (2, 0, 0, 0)
