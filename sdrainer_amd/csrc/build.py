@@ -13,7 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libsdrainer_hip.so")
 SOURCES = ["k_fft_psd.hip", "k_fft_psd_win.hip", "k_fft_psd_iq8.hip", "k_fft_r32.hip", "k_fft_r32_sc16.hip", "k_fft_r32_hop.hip", "k_fft_r32_hop_sc16.hip", "k_fft_r32_iq8.hip", "k_fft_r32_hop_iq8.hip", "k_fft_2p.hip", "k_fft_2p_iq8.hip", "fft_launch.hip", "k_noise.hip", "k_noise_scan.hip", "k_listen.hip", "k_report.hip", "k_peaks.hip", "k_unpack.hip", "k_results.hip", "capi_bank.hip", "capi_process.hip", "capi_results.hip", "capi_graph.hip", "capi_read.hip", "capi_group.hip", "sdr_audio.hip"]
-HEADERS = ["sdr_device.h", "bank.h", "host/batch_plan.h", "host/delivery.h", "host/group.h", "host/overlap.h", "fft_f64.h", "fft_r32.h", "fft_2p.h", "k_fft_2p_a.h", "fft_input.h", "sc16.h", "iq8.h", "noise_cert.h", "gomath.h", "cw_decoder.h", "cw_stages.h", "twiddles.h", "host/frequency_mapping.h",
+HEADERS = ["sdr_device.h", "bank.h", "host/batch_plan.h", "host/delivery.h", "host/group.h", "host/overlap.h", "fft_f64.h", "fft_r32.h", "k_fft_r32.h", "fft_2p.h", "k_fft_2p_a.h", "fft_input.h", "sc16.h", "iq8.h", "noise_cert.h", "gomath.h", "cw_decoder.h", "cw_stages.h", "twiddles.h", "host/frequency_mapping.h",
            "../../include/sdrainer_hip.h"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
@@ -25,15 +25,9 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=o
          "-DSDR_SAFE_FENCES"]
 # k_fft_psd: machine-LICM parks literal constants in VGPRs for the whole kernel; the FFT needs all 128
 # registers a 1024-thread workgroup leaves it, and four parked constants are four spilled data registers.
-EXTRA_FLAGS = {"k_fft_psd.hip": ["-mllvm", "-disable-machine-licm", "-Wno-unused-lambda-capture"],
-               "k_fft_psd_win.hip": ["-mllvm", "-disable-machine-licm", "-Wno-unused-lambda-capture"],
-               "k_fft_psd_iq8.hip": ["-mllvm", "-disable-machine-licm", "-Wno-unused-lambda-capture"],
-               "k_fft_r32.hip": ["-mllvm", "-disable-machine-licm", "-Wno-unused-lambda-capture"],
-               "k_fft_r32_sc16.hip": ["-mllvm", "-disable-machine-licm", "-Wno-unused-lambda-capture"],
-               "k_fft_r32_hop.hip": ["-mllvm", "-disable-machine-licm", "-Wno-unused-lambda-capture"],
-               "k_fft_r32_hop_sc16.hip": ["-mllvm", "-disable-machine-licm", "-Wno-unused-lambda-capture"],
-               "k_fft_r32_iq8.hip": ["-mllvm", "-disable-machine-licm", "-Wno-unused-lambda-capture"],
-               "k_fft_r32_hop_iq8.hip": ["-mllvm", "-disable-machine-licm", "-Wno-unused-lambda-capture"]}
+# (k_fft_r32 likewise: every one of its 256 is in use)
+EXTRA_FLAGS = {s: ["-mllvm", "-disable-machine-licm", "-Wno-unused-lambda-capture"]
+               for s in SOURCES if s.startswith(("k_fft_psd", "k_fft_r32"))}
 
 
 def hipcc() -> str:

@@ -56,12 +56,12 @@ hipError_t launch_fft(const FftLaunch &l, LaunchAt at)
     case K::PSD: case K::PSD_MULTI: case K::PSD_SC16: return launch_fft_psd(l, at);
     case K::PSD_WIN: case K::PSD_WIN_MULTI: case K::PSD_SC16_WIN: return launch_fft_psd_win(l, at);
     case K::PSD_IQ8: case K::PSD_IQ8_WIN: return launch_fft_psd_iq8(l, at);
-    case K::R32: return launch_fft_r32(r32, at);
-    case K::R32_SC16: return launch_fft_r32_sc16(r32, at);
-    case K::R32_IQ8: return launch_fft_r32_iq8(r32, at);
-    case K::R32_HOP: return launch_fft_r32_hop(r32, at);
-    case K::R32_HOP_SC16: return launch_fft_r32_hop_sc16(r32, at);
-    case K::R32_HOP_IQ8: return launch_fft_r32_hop_iq8(r32, at);
+    case K::R32: return launch_fft_r32<InF32, false>(r32, at);
+    case K::R32_SC16: return launch_fft_r32<InSc16, false>(r32, at);
+    case K::R32_IQ8: return launch_fft_r32<InIq8, false>(r32, at);
+    case K::R32_HOP: return launch_fft_r32<InF32, true>(r32, at);
+    case K::R32_HOP_SC16: return launch_fft_r32<InSc16, true>(r32, at);
+    case K::R32_HOP_IQ8: return launch_fft_r32<InIq8, true>(r32, at);
     case K::A2P_F32: case K::A2P_SC16: case K::A2P_WIN_F32: case K::A2P_WIN_SC16: return launch_fft_2p(l, at);
     case K::A2P_CS8: case K::A2P_CU8: case K::A2P_WIN_CS8: case K::A2P_WIN_CU8: return launch_fft_2p_iq8(l, at);
     case K::COUNT: break;

@@ -167,7 +167,7 @@ inline int fft_frames_per_wg(int fpw_asked, int n_frames, int n_bands)
     return fpw;
 }
 
-// N = 16384 has two kernels: k_fft_psd.hip's 16-point one and k_fft_r32.hip (512 threads x 32 points, the next frame
+// N = 16384 has two kernels: k_fft_psd.hip's 16-point one and k_fft_r32.h (512 threads x 32 points, the next frame
 // prefetched into registers), whose workgroups - one per CU - claim frames from a counter.  By default the 32-point kernel
 // runs from 1024 frames per launch on (measured by batch size) and while the listener slots fit its tap (one per thread).
 // sc16 input takes the same choice (k_fft_r32_sc16 or k_fft_psd_sc16<14>): the rule does not look at the format.
@@ -198,7 +198,7 @@ inline FftChoice fft_choice(const Switches &sw, int n, int n_frames, int n_bands
 enum class FftKernel {
     // k_fft_psd.hip and its recompilations k_fft_psd_win.hip, k_fft_psd_iq8.hip (PSD_IQ8*: cs8 and cu8, a launch argument)
     PSD, PSD_MULTI, PSD_SC16, PSD_IQ8, PSD_WIN, PSD_WIN_MULTI, PSD_SC16_WIN, PSD_IQ8_WIN,
-    // k_fft_r32.hip and its five recompilations (R32*_IQ8: cs8 and cu8, a launch argument)
+    // k_fft_r32.h, one instance per k_fft_r32*.hip unit (R32*_IQ8: cs8 and cu8, a launch argument)
     R32, R32_SC16, R32_IQ8, R32_HOP, R32_HOP_SC16, R32_HOP_IQ8,
     // k_fft_2p.hip (F32, SC16) and k_fft_2p_iq8.hip (CS8, CU8): phase A's instances
     A2P_F32, A2P_SC16, A2P_CS8, A2P_CU8, A2P_WIN_F32, A2P_WIN_SC16, A2P_WIN_CS8, A2P_WIN_CU8,

@@ -1,5 +1,4 @@
-// k_fft_r32_hop_iq8.hip — k_fft_r32_iq8 for overlapped frames (a frame stride below N): k_fft_r32.hip compiled again, see
-// that file's header.
-#define SDR_R32_IQ8 1
-#define SDR_R32_HOP 1
-#include "k_fft_r32.hip"
+// k_fft_r32_hop_iq8.hip — k_fft_r32 (k_fft_r32.h) for 8-bit input (cs8 / cu8), overlapped frames (a frame stride below N).
+#include "k_fft_r32.h"
+
+template hipError_t sdr::launch_fft_r32<sdr::InIq8, true>(const sdr::FftLaunch &, sdr::LaunchAt);

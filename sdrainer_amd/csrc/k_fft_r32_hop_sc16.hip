@@ -1,4 +1,4 @@
-// k_fft_r32_hop_sc16.hip — k_fft_r32_sc16 for overlapped frames: k_fft_r32.hip compiled once more (see that file's header).
-#define SDR_R32_HOP 1
-#define SDR_R32_SC16 1
-#include "k_fft_r32.hip"
+// k_fft_r32_hop_sc16.hip — k_fft_r32 (k_fft_r32.h) for sc16 input, overlapped frames (a frame stride below N).
+#include "k_fft_r32.h"
+
+template hipError_t sdr::launch_fft_r32<sdr::InSc16, true>(const sdr::FftLaunch &, sdr::LaunchAt);

@@ -1,4 +1,4 @@
-// k_fft_r32_iq8.hip — k_fft_r32 reading 8-bit frames (cs8 / cu8, iq8.h): k_fft_r32.hip compiled again, in a translation
-// unit of its own so that the other kernels' code stays exactly what it was (see that file's header).
-#define SDR_R32_IQ8 1
-#include "k_fft_r32.hip"
+// k_fft_r32_iq8.hip — k_fft_r32 (k_fft_r32.h) for 8-bit input (cs8 / cu8, iq8.h), dense frames.
+#include "k_fft_r32.h"
+
+template hipError_t sdr::launch_fft_r32<sdr::InIq8, false>(const sdr::FftLaunch &, sdr::LaunchAt);

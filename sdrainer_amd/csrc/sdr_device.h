@@ -209,16 +209,15 @@ hipError_t launch_fft_psd_win(const FftLaunch &l, LaunchAt at);
 hipError_t launch_fft_psd_iq8(const FftLaunch &l, LaunchAt at);
 // k_fft_psd_win.hip: the order its kernels read the window table in: out[N] from the caller's w[N] (sample order)
 void window_layout(int logn, const float *w, float *out);
-// k_fft_r32.hip and its recompilations: N = 16384 as 512 threads x 32 points with the next frame prefetched into registers
-// (l.tw: their own twiddle layout), by format, dense frames and frame_stride < N (a power of two).  Workgroups per band =
-// max(1, ceil((CUs - fft.reserve_cus) / n_bands)), at most n_frames (unless fft.reserve_forced the reserve is at most
-// CUs / kReserveDeviceShare)
+// k_fft_r32.h, one instance per k_fft_r32*.hip unit: N = 16384 as 512 threads x 32 points with the next frame prefetched
+// into registers (l.tw: their own twiddle layout), by input format (fft_input.h: InF32, InSc16, InIq8), dense frames (HOP =
+// false) and frame_stride < N (a power of two; HOP = true).  Workgroups per band = max(1, ceil((CUs - fft.reserve_cus) /
+// n_bands)), at most n_frames (unless fft.reserve_forced the reserve is at most CUs / kReserveDeviceShare)
+struct InF32;
+struct InSc16;
+struct InIq8;
+template <class IN, bool HOP>
 hipError_t launch_fft_r32(const FftLaunch &l, LaunchAt at);
-hipError_t launch_fft_r32_sc16(const FftLaunch &l, LaunchAt at);
-hipError_t launch_fft_r32_iq8(const FftLaunch &l, LaunchAt at);
-hipError_t launch_fft_r32_hop(const FftLaunch &l, LaunchAt at);
-hipError_t launch_fft_r32_hop_sc16(const FftLaunch &l, LaunchAt at);
-hipError_t launch_fft_r32_hop_iq8(const FftLaunch &l, LaunchAt at);
 // k_fft_2p.hip (float32, sc16) and k_fft_2p_iq8.hip (cs8, cu8): N = 32768 / 65536 as two phases over l.scratch (fft_2p.h),
 // frame group by frame group; phase B of frames [f0, f0 + g) of a group is k_fft_2p.hip's for both
 hipError_t launch_fft_2p(const FftLaunch &l, LaunchAt at);

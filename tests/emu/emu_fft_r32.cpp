@@ -204,11 +204,12 @@ static int transform(const std::vector<float> &iq, const std::vector<cplx> &tw, 
     }
     for (int t = 0; t < T; t++) {
         const int p0 = tw2_pos(t, 0), p1 = tw2_pos(t, 1);
-        // (as the kernel runs it: twiddles requested two chunks ahead of their butterflies)
+        // (as the kernel runs it: the first chunk of four twiddles requested ahead of the pass - in the kernel, in front of
+        // E1 - and every later chunk one chunk ahead of its butterflies)
         auto tw2 = [twp, p0, p1](int row, int u) { return twp[kTw2 + row * 1024 + (u ? p1 : p0)]; };
-        FirstChunks2<4, 4> first;
-        first_chunks2<4, false, 4>(tw2, first);
-        run_pass2_with<4, false, 4>(&xr[(size_t)t * R], &xi[(size_t)t * R], first, tw2);
+        FirstChunk<4, 4> first;
+        first_chunk<4, false, 4>(tw2, first);
+        run_pass_with<4, false, 4>(&xr[(size_t)t * R], &xi[(size_t)t * R], first, tw2);
     }
     std::vector<char> seen((size_t)N, 0);
     for (int t = 0; t < T; t++)

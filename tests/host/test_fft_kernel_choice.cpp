@@ -129,7 +129,7 @@ sdr::FftChoice choose(const Case &c)
     return sdr::fft_choice(sdr::read_switches(), c.n, c.frames, c.bands, c.slots, c.windowed, c.fmt, c.hop);
 }
 
-// what a unit's entry checks before it launches (k_fft_psd.hip, k_fft_r32.hip, k_fft_2p.hip): none may refuse a planned choice
+// what a unit's entry checks before it launches (k_fft_psd.hip, k_fft_r32.h, k_fft_2p.hip): none may refuse a planned choice
 bool a_unit_takes(const sdr::FftChoice &c, int n, int slots, int frame_stride)
 {
     switch (sdr::fft_kernel(c)) {

@@ -43,6 +43,22 @@ def capi():
     return c
 
 
+@pytest.fixture(scope="module")
+def planned(tmp_path_factory):
+    """(kernel name, FftKernel id, frames per workgroup) the batch plan picks, with the switches of the environment: the host
+    helper tests/host/iq8_plan.cpp, asked for (n, frames, listener slots, windowed, format name, hop or 0)."""
+    import subprocess
+
+    exe = str(tmp_path_factory.mktemp("fft_plan") / "iq8_plan")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(os.path.dirname(os.path.abspath(__file__)), "host", "iq8_plan.cpp")])
+
+    def ask(n, frames, slots, windowed, fmt, hop):
+        w = subprocess.check_output([exe, str(n), str(frames), "1", str(slots), str(int(windowed)), fmt, str(hop)], text=True).split()
+        got = dict(zip(w[0::2], w[1::2]))
+        return got["kernel"], int(got["id"]), int(got["frames_per_wg"])
+    return ask
+
+
 @contextlib.contextmanager
 def environment(**kw):
     """Switches the library reads when a bank is created (host/batch_plan.h read_switches) or while it reads back."""

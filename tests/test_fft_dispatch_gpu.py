@@ -8,9 +8,6 @@ The shapes are the smallest at which an arm can go wrong: three frames and two l
 k_fft_r32 (forced with SDR_FFT_R32=1: by itself it starts at 1024 frames), two frames of 32768 points for the two phases,
 and 515 frames of 512 points at SDR_FFT_FPW=2 for the multi-frame workgroup - 258 workgroups, so the halving rule keeps 2,
 and the odd count leaves the last workgroup one frame."""
-import os
-import subprocess
-
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,25 +16,11 @@ torch = pytest.importorskip("torch")
 
 import iq8_tools as t8  # noqa: E402
 from parity_case import Case  # noqa: E402
-from parity_tools import RATES, capi, environment, listener_bins, make_stream, random_window  # noqa: E402, F401 (capi: the fixture)
+from parity_tools import RATES, capi, environment, listener_bins, make_stream, planned, random_window  # noqa: E402, F401 (capi, planned: fixtures)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FORMATS = ("f32", "sc16", "cs8", "cu8")
 PATH = {"f32": "device", "sc16": "device_sc16", "cs8": "device_cs8", "cu8": "device_cu8"}
 IQ8 = {"cs8": t8.CS8, "cu8": t8.CU8}
-
-
-@pytest.fixture(scope="module")
-def planned(tmp_path_factory):
-    """(kernel name, FftKernel id, frames per workgroup) the batch plan picks, with the switches of the environment."""
-    exe = str(tmp_path_factory.mktemp("fft_plan") / "iq8_plan")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(ROOT, "tests", "host", "iq8_plan.cpp")])
-
-    def ask(n, frames, slots, windowed, fmt, hop):
-        w = subprocess.check_output([exe, str(n), str(frames), "1", str(slots), str(int(windowed)), fmt, str(hop)], text=True).split()
-        got = dict(zip(w[0::2], w[1::2]))
-        return got["kernel"], int(got["id"]), int(got["frames_per_wg"])
-    return ask
 
 
 def run_case(capi, n, frames, listeners, fmt, hop, windowed, seed):

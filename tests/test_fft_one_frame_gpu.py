@@ -2,7 +2,8 @@
 k_fft_psd_sc16_win, k_fft_psd_iq8<LOGN, false / true>) over the full product of its branches at the smallest shapes:
 formats sc16, cs8, cu8; window off and on; every N it is instantiated for; two bands, three frames; no listener, a few
 listeners with bins 0 and N - 1 among them (the LDS tap) and, at N = 1024, more than kMaxLdsTap (the tap that re-reads
-the stored row); one graph replay per format (the format's trait names the BatchCursor field).
+the stored row); one graph replay per format (the format's trait names the BatchCursor field) - and one more per format
+through k_fft_r32 (k_fft_r32.h), which takes its replayed pointer from the same trait.
 
 The library's contract is the expectation: a bank fed the narrow samples gives, bit for bit, what a bank fed their
 float32 values through the float32 call gives - every psd and spectrum row, every listener's tapped value (the traced
@@ -15,7 +16,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import iq8_tools as t8  # noqa: E402
-from parity_tools import capi, random_window, sc16_to_float32  # noqa: E402, F401 (capi: the fixture)
+from parity_tools import capi, environment, planned, random_window, sc16_to_float32  # noqa: E402, F401 (capi, planned: fixtures)
 
 RATE = t8.RATE
 BANDS, FRAMES = 2, 3
@@ -39,9 +40,9 @@ def to_f32(fmt, q):
 class Pair:
     """Bank a takes the float32 values through the float32 calls, bank b the narrow samples through their format's."""
 
-    def __init__(self, capi, n, fmt, window, listeners=8):
-        self.n, self.fmt, self.lids = n, fmt, [[] for _ in range(BANDS)]
-        mk = lambda: capi.Bank(RATE[n], n, n_bands=BANDS, max_batch_frames=FRAMES, max_listeners=listeners, trace=True)
+    def __init__(self, capi, n, fmt, window, listeners=8, bands=BANDS):
+        self.n, self.fmt, self.bands, self.lids = n, fmt, bands, [[] for _ in range(bands)]
+        mk = lambda: capi.Bank(RATE[n], n, n_bands=bands, max_batch_frames=FRAMES, max_listeners=listeners, trace=True)
         self.a, self.b = mk(), mk()
         for bk in (self.a, self.b):
             bk.enable_results(True)
@@ -49,7 +50,7 @@ class Pair:
                 bk.set_window(random_window(n, 4000 + n))
 
     def attach(self, bins):
-        for band in range(BANDS):
+        for band in range(self.bands):
             for bin_ in bins:
                 ia, ib = self.a.attach(band, int(bin_)), self.b.attach(band, int(bin_))
                 assert ia == ib >= 0
@@ -61,7 +62,7 @@ class Pair:
         return ta, tb
 
     def run(self, seed, traced=None):
-        ta, tb = self.device(samples(self.fmt, (BANDS, FRAMES, 2 * self.n), seed))
+        ta, tb = self.device(samples(self.fmt, (self.bands, FRAMES, 2 * self.n), seed))
         self.a.process_device(ta.data_ptr(), FRAMES)
         if self.fmt == "sc16":
             self.b.process_device_sc16(tb.data_ptr(), FRAMES)
@@ -73,7 +74,7 @@ class Pair:
         """traced: positions in the attach order whose traces are compared (default: every listener)."""
         self.a.sync()
         self.b.sync()
-        for band in range(BANDS):
+        for band in range(self.bands):
             for f in range(FRAMES):
                 (sa, pa), (sb, pb) = self.a.read_spectrum(band, f), self.b.read_spectrum(band, f)
                 assert pa.tobytes() == pb.tobytes(), f"band {band} frame {f}: psd row differs"
@@ -87,6 +88,29 @@ class Pair:
                 for x, y, what in zip(va, vb, ("tapped value", "raw bit", "debounced bit")):
                     assert x.tobytes() == y.tobytes(), f"band {band} listener {lid}: {what} differs"
         assert t8.same_deliveries(self.a, self.b) > 0
+
+    def replay(self, bins, seed):
+        """One replay of sdr_graph_batches() captured batches, each with its own input, on both banks."""
+        streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+        self.a.set_stream(streams[0].cuda_stream)
+        self.b.set_stream(streams[1].cuda_stream)
+        self.attach(bins)
+        K = self.a.graph_batches
+        fmt_id = None if self.fmt == "sc16" else t8.FORMAT_IDS.index(self.fmt)
+        self.a.graph_capture(FRAMES)
+        if self.fmt == "sc16":
+            self.b.graph_capture_sc16(FRAMES)
+        else:
+            self.b.graph_capture_iq8(FRAMES, fmt_id)
+        dev = [self.device(samples(self.fmt, (self.bands, FRAMES, 2 * self.n), seed + k)) for k in range(K)]
+        self.a.graph_launch([ta.data_ptr() for ta, _ in dev])
+        if self.fmt == "sc16":
+            self.b.graph_launch_sc16([tb.data_ptr() for _, tb in dev])
+        else:
+            self.b.graph_launch_iq8([tb.data_ptr() for _, tb in dev], fmt_id)
+        self.check()  # (the read calls see the replay's last batch, the deliveries every batch)
+        self.a.graph_release()
+        self.b.graph_release()
 
     def close(self):
         self.a.close()
@@ -123,23 +147,24 @@ def test_graph_replay(capi, fmt):
     inputs: the kernel takes each batch's pointer from the cursor field of its format."""
     n = 2048
     p = Pair(capi, n, fmt, False)
-    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
-    p.a.set_stream(streams[0].cuda_stream)
-    p.b.set_stream(streams[1].cuda_stream)
-    p.attach([0, n - 1, 300])
-    K = p.a.graph_batches
-    p.a.graph_capture(FRAMES)
-    if fmt == "sc16":
-        p.b.graph_capture_sc16(FRAMES)
-    else:
-        p.b.graph_capture_iq8(FRAMES, t8.FORMAT_IDS.index(fmt))
-    dev = [p.device(samples(fmt, (BANDS, FRAMES, 2 * n), 6000 + k)) for k in range(K)]
-    p.a.graph_launch([ta.data_ptr() for ta, _ in dev])
-    if fmt == "sc16":
-        p.b.graph_launch_sc16([tb.data_ptr() for _, tb in dev])
-    else:
-        p.b.graph_launch_iq8([tb.data_ptr() for _, tb in dev], t8.FORMAT_IDS.index(fmt))
-    p.check()  # (the read calls see the replay's last batch, the deliveries every batch)
-    p.a.graph_release()
-    p.b.graph_release()
+    p.replay([0, n - 1, 300], 6000)
     p.close()
+
+
+# FftKernel (host/batch_plan.h) of the dense k_fft_r32 instance of each format, by the plan's name for it
+R32_IDS = {"f32": ("k_fft_r32", 8), "sc16": ("k_fft_r32_sc16", 9), "cs8": ("k_fft_r32_iq8", 10), "cu8": ("k_fft_r32_iq8", 10)}
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_graph_replay_r32(capi, planned, fmt):
+    """The same through k_fft_r32 (forced with SDR_FFT_R32=1: by itself it starts at 1024 frames): N = 16384, dense, one
+    band, two listeners, three frames per batch, one replay.  Both graphs run the k_fft_r32 instance of their format, and
+    the narrow one takes each batch's pointer from the cursor field its trait names.  (Hopped banks refuse graph capture:
+    the strided instances have no cursor path.)"""
+    n = 16384
+    with environment(SDR_FFT_R32=1):
+        for f in ("f32", fmt):
+            assert planned(n, FRAMES, 2, False, f, 0) == R32_IDS[f] + (0,)
+        p = Pair(capi, n, fmt, False, bands=1)
+        p.replay([0, n - 1], 6100)
+        p.close()

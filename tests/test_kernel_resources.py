@@ -24,9 +24,10 @@ def usage(tmp_path_factory):
     cmd = [cc] + flags + ["--cuda-device-only", "-c", SRC, "-o", str(out), "-Rpass-analysis=kernel-resource-usage"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]
-    # the remarks of the function whose name holds k_fft_r32, up to the next function's
-    m = re.search(r"Function Name: \S*k_fft_r32\S*(.*?)(?:Function Name:|\Z)", p.stderr, re.S)
-    assert m, "no resource report for k_fft_r32"
+    # the remarks of the instance k_fft_r32<InF32, false> (its mangled name: ...k_fft_r32INS_5InF32ELb0E...), up to the
+    # next function's
+    m = re.search(r"Function Name: \S*k_fft_r32INS_5InF32ELb0E\S*(.*?)(?:Function Name:|\Z)", p.stderr, re.S)
+    assert m, "no resource report for k_fft_r32<InF32, false>"
     return {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", m.group(1))}
 
 
@@ -51,7 +52,7 @@ def test_vgprs_and_occupancy(usage):
 
 def test_lds_fits():
     """The LDS is dynamic (the report says 0): the kernel's own constant kLdsBytes, evaluated by the compiler."""
-    probe = ('#include "k_fft_r32.hip"\n'
+    probe = ('#include "k_fft_r32.h"\n'
              'static_assert(sdr::r32::kLdsBytes <= 160 * 1024, "k_fft_r32 needs more LDS than a CU has");\n')
     cc = hip_build.hipcc()
     p = subprocess.run([cc] + hip_build.FLAGS + hip_build.EXTRA_FLAGS.get("k_fft_r32.hip", []) +

@@ -1,6 +1,6 @@
 """The 8-bit k_fft_r32 kernels' register budget, checked at compile time (no GPU), as tests/test_kernel_resources_sc16.py
-checks the sc16 kernel: k_fft_r32.hip compiled again with SDR_R32_IQ8 = 1 (k_fft_r32_iq8.hip, and k_fft_r32_hop_iq8.hip
-with SDR_R32_HOP = 1), device-only for gfx950 with the library's own flags, and the compiler's resource report read.  Each
+checks the sc16 kernel: the instances k_fft_r32<InIq8, false> (k_fft_r32_iq8.hip) and k_fft_r32<InIq8, true>
+(k_fft_r32_hop_iq8.hip) of k_fft_r32.h, device-only for gfx950 with the library's own flags, and the compiler's resource report read.  Each
 kernel must run at two waves per SIMD with nothing in scratch and no spilled vector register; the strided form may keep a
 scalar register in a vector register's lane, as k_fft_r32_hop does.  Each unit holds its 8-bit kernel and no other."""
 import os
@@ -11,7 +11,8 @@ import pytest
 
 from sdrainer_amd.csrc import build as hip_build
 
-UNITS = {"k_fft_r32_iq8.hip": "k_fft_r32_iq8", "k_fft_r32_hop_iq8.hip": "k_fft_r32_hop_iq8"}
+# (the mangled names of the two instances: ...k_fft_r32INS_5InIq8ELb0E<argument pack and parameters>)
+UNITS = {"k_fft_r32_iq8.hip": "k_fft_r32INS_5InIq8ELb0E", "k_fft_r32_hop_iq8.hip": "k_fft_r32INS_5InIq8ELb1E"}
 
 
 @pytest.fixture(scope="module", params=sorted(UNITS))
@@ -29,11 +30,11 @@ def usage(request, tmp_path_factory):
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]
     names = re.findall(r"Function Name: (\S+)", p.stderr)
-    assert len(names) == 1 and kernel + "E" in names[0], names  # (the mangled name: ...k_fft_r32_iq8E<parameters>)
+    assert len(names) == 1 and kernel in names[0], names
     m = re.search(r"Function Name: \S*" + kernel + r"\S*(.*?)(?:Function Name:|\Z)", p.stderr, re.S)
     assert m, "no resource report for " + kernel
     u = {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", m.group(1))}
-    u["hop"] = "hop" in kernel
+    u["hop"] = "hop" in unit
     return u
 
 

@@ -1,5 +1,5 @@
 """k_fft_r32_sc16's register budget, checked at compile time (no GPU), as tests/test_kernel_resources.py checks the
-float32 kernel: k_fft_r32.hip compiled again with SDR_R32_SC16 = 1 (k_fft_r32_sc16.hip), device-only for gfx950 with the
+float32 kernel: the instance k_fft_r32<InSc16, false> of k_fft_r32.h (k_fft_r32_sc16.hip), device-only for gfx950 with the
 library's own flags, and the compiler's resource report read.  The sc16 kernel must run at two waves per SIMD with
 nothing in scratch, like the float32 one; its prefetched frame is 32 registers instead of 64."""
 import os
@@ -11,6 +11,7 @@ import pytest
 from sdrainer_amd.csrc import build as hip_build
 
 SRC = os.path.join(hip_build.HERE, "k_fft_r32_sc16.hip")
+KERNEL = "k_fft_r32INS_6InSc16ELb0E"  # (the mangled name of k_fft_r32<InSc16, false>: ...k_fft_r32INS_6InSc16ELb0E...)
 
 
 @pytest.fixture(scope="module")
@@ -27,8 +28,8 @@ def usage(tmp_path_factory):
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]
     names = re.findall(r"Function Name: (\S+)", p.stderr)
-    assert not any("k_fft_r32E" in n or ("k_fft_r32" in n and "sc16" not in n) for n in names), names
-    m = re.search(r"Function Name: \S*k_fft_r32_sc16\S*(.*?)(?:Function Name:|\Z)", p.stderr, re.S)
+    assert not any("k_fft_r32" in n and KERNEL not in n for n in names), names
+    m = re.search(r"Function Name: \S*" + KERNEL + r"\S*(.*?)(?:Function Name:|\Z)", p.stderr, re.S)
     assert m, "no resource report for k_fft_r32_sc16"
     return {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", m.group(1))}
 
