@@ -582,6 +582,87 @@ int sdr_group_poll_peaks(sdr_group *group, sdr_results *results, int wait);
 int sdr_group_process_listen(sdr_group *group);
 int sdr_group_read_drop_counters(sdr_group *group, uint64_t *runes_dropped, uint64_t *edges_dropped);
 
+/* down-converter ----------------------------------------------------------------------------- */
+/* A digital down-converter (DDC) in front of a bank: one WIDE stream - a HackRF's 8-20 MS/s, an RTL-SDR's 2.4 MS/s - goes in
+ * once, in any of the four input formats, and n_bands narrow float32 streams come out in device memory, laid out as
+ * sdr_process_device_stream reads them.  Each band is mixed to 0 Hz, low-pass filtered and decimated by one kernel.  An
+ * sdr_ddc is an object of its own beside the bank; a process that never creates one runs exactly what it ran.  Like the
+ * window and the hop it has no counterpart in the reference: its arithmetic is defined here to the bit (DESIGN.md section
+ * 1; tests/ddc_ref.py restates it in NumPy), and everything behind it is the reference fed with these float32 samples.
+ *
+ * The wide stream is x[k], k a 64-bit sample index counted from the DDC's start (or from sdr_ddc_set_first_sample);
+ * x[k] = 0 for k below the first sample.  A sample's float32 value (re, im) is what the bank's calls make of that format:
+ * exact for cs8 / cu8, float32(x) / 32767 correctly rounded for sc16.  L = SDR_DDC_NCO_SIZE = 65536.  Per band b:
+ *   NCO     step_b in [-32768, 32767] tunes the band: a signal step_b * input_rate / L Hz from the wide stream's centre
+ *           lands on 0 Hz.  p = (k * step_b) mod L from the full 64-bit k (two's complement for negative steps; the phase
+ *           is never truncated: no phase-truncation spurs), c = COS[p], s = SIN[p] from the float32 table of
+ *           sdr_ddc_nco_table.
+ *   mix     yre = (re * c) + (im * s),  yim = (im * c) - (re * s)  in float32, every operation rounded on its own.
+ *   filter  the n_taps float32 taps h are the caller's (as the window is) and the same for every band; with decimation D,
+ *           output n is  acc = +0.0f; for j = 0 .. n_taps - 1, in this order: acc = acc + (h[j] * y[n * D - j])
+ *           for re and im separately, each product and each sum rounded once in float32; subnormals are kept.
+ *   count   a call that brings m * D new samples produces exactly m outputs per band, n = K / D .. K / D + m - 1 for K
+ *           samples seen before it.  The DDC keeps the last n_taps - 1 RAW samples on the device between calls and mixes
+ *           them again from their absolute index: any cut of a stream into calls gives the same bits, and a retune
+ *           between two calls is well defined - an output uses, for all its taps, the step current in the call that
+ *           produces it.
+ * Calls and statuses (a refused call changes nothing):
+ *   sdr_ddc_create       taps: n_taps float32 values, nco_steps: n_bands steps, both copied.  SDR_ERR_BAD_ARG: a null
+ *                        pointer, a wrong struct_size, n_bands outside 1..64, decimation outside 1..256, n_taps outside
+ *                        1..4096, an unknown in_format, max_in_samples < decimation or not a multiple of it, a non-zero
+ *                        reserved word, a step outside [-32768, 32767].
+ *   sdr_ddc_set_stream   run on this hipStream_t (NULL = the null stream): the stream the bank's FFT runs on
+ *                        (sdr_set_stream), so that a DDC call and the bank call behind it need no synchronisation.
+ *   sdr_ddc_set_first_sample  the next sample gets index k0 (k0 >= 0 and a multiple of the decimation, SDR_ERR_BAD_ARG
+ *                        otherwise); before the first process call only, SDR_ERR_STATE afterwards.  Mirrors
+ *                        sdr_set_first_frame.
+ *   sdr_ddc_total_samples  the index of the next sample.
+ *   sdr_ddc_set_nco_step from the next process call on.  SDR_ERR_BAD_ARG: band or step out of range.
+ *   sdr_ddc_process_device  asynchronous on the DDC's stream.  in_dev: n_in_samples samples of in_format in device memory;
+ *                        out_dev: float32 I,Q in device memory, band b's m outputs from sample b * band_stride_samples on.
+ *                        Both 16-byte aligned, band_stride_samples a multiple of 4 and >= m (SDR_ERR_BAD_ARG otherwise).
+ *                        n_in_samples is a positive multiple of the decimation, at most max_in_samples (SDR_ERR_BAD_SIZE
+ *                        otherwise).  Placement in a ring and continuity are the caller's business, as for
+ *                        sdr_process_device_stream: the next call's out_dev is where this call's outputs ended.
+ *   sdr_ddc_process_host the same with the wide stream in host memory (borrowed for the call), uploaded raw: one byte per
+ *                        value for the 8-bit formats.
+ *   sdr_ddc_nco_table    host only, needs no handle and no GPU: COS and SIN, SDR_DDC_NCO_SIZE float32 values each (either
+ *                        pointer may be null).  Built in float64 from one quarter wave and extended by exact symmetry:
+ *                        SIN[i] == COS[(i - L/4) mod L], COS[i] == COS[L - i], COS[i] == -COS[L/2 - i]; exactly 0 and
+ *                        +-1 at the multiples of L/4.
+ * Not offered: per-band taps, resampling by a ratio, DDC launches inside a captured graph, DDCs in an sdr_group. */
+#define SDR_DDC_F32 0
+#define SDR_DDC_SC16 1
+#define SDR_DDC_CS8 2
+#define SDR_DDC_CU8 3
+#define SDR_DDC_NCO_SIZE 65536
+/* outputs of one band that one workgroup of the kernel computes (csrc/ddc.h): where the tests put their output counts */
+#define SDR_DDC_TILE_OUTPUTS 512
+
+typedef struct sdr_ddc sdr_ddc;
+
+typedef struct sdr_ddc_config {
+    int32_t struct_size;    /* = sizeof(sdr_ddc_config), ABI guard                    */
+    int32_t n_bands;        /* 1 .. 64                                                */
+    int32_t decimation;     /* D, 1 .. 256                                            */
+    int32_t n_taps;         /* T, 1 .. 4096                                           */
+    int32_t in_format;      /* SDR_DDC_F32 / _SC16 / _CS8 / _CU8                      */
+    int32_t max_in_samples; /* capacity: input samples per call, a multiple of D      */
+    int32_t device_id;      /* HIP device ordinal                                     */
+    int32_t reserved;       /* 0                                                      */
+} sdr_ddc_config;
+
+int sdr_ddc_create(const sdr_ddc_config *cfg, const float *taps, const int32_t *nco_steps, sdr_ddc **out);
+int sdr_ddc_destroy(sdr_ddc *ddc);
+int sdr_ddc_sync(sdr_ddc *ddc);
+int sdr_ddc_set_stream(sdr_ddc *ddc, void *hip_stream);
+int sdr_ddc_set_first_sample(sdr_ddc *ddc, int64_t k0);
+int64_t sdr_ddc_total_samples(sdr_ddc *ddc);
+int sdr_ddc_set_nco_step(sdr_ddc *ddc, int band, int step);
+int sdr_ddc_process_device(sdr_ddc *ddc, const void *in_dev, size_t n_in_samples, float *out_dev, size_t band_stride_samples);
+int sdr_ddc_process_host(sdr_ddc *ddc, const void *in_host, size_t n_in_samples, float *out_dev, size_t band_stride_samples);
+int sdr_ddc_nco_table(float *cos_out, float *sin_out);
+
 /* scope tap ---------------------------------------------------------------------------------- */
 /* The reference shows its inner workings through scope.Scope (scope/scope.go:33-37); NullScope is the default
  * and so is "no tap" here: the two reads below need a bank created with trace = 1 (that is scope.Active()).

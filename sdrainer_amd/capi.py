@@ -125,6 +125,18 @@ def _set_window(fn, handle, w):
 IQ8_CS8, IQ8_CU8 = 0, 1
 
 
+# the down-converter (sdr_ddc_*): input formats, the NCO table's size, the outputs of one band per workgroup
+DDC_F32, DDC_SC16, DDC_CS8, DDC_CU8 = range(4)
+DDC_NCO_SIZE = 65536
+DDC_TILE_OUTPUTS = 512
+
+
+class DdcConfig(C.Structure):
+    """sdr_ddc_config (include/sdrainer_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_bands", C.c_int32), ("decimation", C.c_int32), ("n_taps", C.c_int32),
+                ("in_format", C.c_int32), ("max_in_samples", C.c_int32), ("device_id", C.c_int32), ("reserved", C.c_int32)]
+
+
 def _iq8_bytes(iq, fmt):
     """The bytes of an 8-bit push: int8 for cs8, uint8 for cu8 (any other fmt goes to the library, which refuses it)."""
     return np.ascontiguousarray(iq, dtype=np.int8 if fmt == IQ8_CS8 else np.uint8).reshape(-1)
@@ -151,6 +163,8 @@ SYMBOLS = (
     "sdr_set_first_frame sdr_group_set_first_frame "
     "sdr_enable_rows sdr_row_columns sdr_poll_rows sdr_group_enable_rows sdr_group_poll_rows "
     "sdr_enable_reports sdr_reports_enabled sdr_poll_reports sdr_group_enable_reports sdr_group_poll_reports "
+    "sdr_ddc_create sdr_ddc_destroy sdr_ddc_sync sdr_ddc_set_stream sdr_ddc_set_first_sample sdr_ddc_total_samples "
+    "sdr_ddc_set_nco_step sdr_ddc_process_device sdr_ddc_process_host sdr_ddc_nco_table "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -296,6 +310,16 @@ def load():
     sig("sdr_poll_reports", C.c_int, vp, vp, C.c_int, ip, C.POINTER(C.c_int64), C.c_int)
     sig("sdr_group_enable_reports", C.c_int, vp, C.c_int)
     sig("sdr_group_poll_reports", C.c_int, vp, vp, C.c_int, ip, C.POINTER(C.c_int64), C.c_int)
+    sig("sdr_ddc_create", C.c_int, C.POINTER(DdcConfig), fp, C.POINTER(C.c_int32), C.POINTER(vp))
+    sig("sdr_ddc_destroy", C.c_int, vp)
+    sig("sdr_ddc_sync", C.c_int, vp)
+    sig("sdr_ddc_set_stream", C.c_int, vp, vp)
+    sig("sdr_ddc_set_first_sample", C.c_int, vp, C.c_int64)
+    sig("sdr_ddc_total_samples", C.c_int64, vp)
+    sig("sdr_ddc_set_nco_step", C.c_int, vp, C.c_int, C.c_int)
+    sig("sdr_ddc_process_device", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
+    sig("sdr_ddc_process_host", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
+    sig("sdr_ddc_nco_table", C.c_int, fp, fp)
     _lib = L
     return L
 
@@ -972,6 +996,70 @@ class Group:
         a, b = C.c_uint64(), C.c_uint64()
         _check(self._L.sdr_group_read_drop_counters(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+
+def ddc_nco_table():
+    """sdr_ddc_nco_table: (COS, SIN), float32 [DDC_NCO_SIZE] each - the table the down-converter mixes with.  Needs no GPU."""
+    co, si = np.empty(DDC_NCO_SIZE, np.float32), np.empty(DDC_NCO_SIZE, np.float32)
+    _check(load().sdr_ddc_nco_table(co.ctypes.data_as(C.POINTER(C.c_float)), si.ctypes.data_as(C.POINTER(C.c_float))))
+    return co, si
+
+
+class Ddc:
+    """sdr_ddc: one wide stream in, n_bands narrow float32 streams out in device memory (see include/sdrainer_hip.h).
+    taps: the low-pass, float32, the same for every band; nco_steps: one step per band, the band's centre offset is
+    step * input_rate / DDC_NCO_SIZE Hz."""
+
+    def __init__(self, decimation: int, taps, nco_steps, in_format: int = DDC_F32, max_in_samples: int = 1 << 20,
+                 device_id: int = 0):
+        L = load()
+        taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        steps = np.ascontiguousarray(nco_steps, np.int32).reshape(-1)
+        self.cfg = DdcConfig(C.sizeof(DdcConfig), int(steps.size), decimation, int(taps.size), in_format, max_in_samples, device_id, 0)
+        self.n_bands, self.decimation, self.n_taps, self.in_format = int(steps.size), decimation, int(taps.size), in_format
+        h = C.c_void_p()
+        _check(L.sdr_ddc_create(C.byref(self.cfg), taps.ctypes.data_as(C.POINTER(C.c_float)),
+                                steps.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h)))
+        self._h, self._L = h, L
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sdr_ddc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr: int):
+        _check(self._L.sdr_ddc_set_stream(self._h, C.c_void_p(stream_ptr)))
+
+    def set_first_sample(self, k0: int):
+        """The next sample gets index k0 (>= 0, a multiple of the decimation); before the first process call only."""
+        _check(self._L.sdr_ddc_set_first_sample(self._h, int(k0)))
+
+    @property
+    def total_samples(self) -> int:
+        return self._L.sdr_ddc_total_samples(self._h)
+
+    def set_nco_step(self, band: int, step: int):
+        _check(self._L.sdr_ddc_set_nco_step(self._h, band, int(step)))
+
+    def process_device(self, in_dev_ptr: int, n_in_samples: int, out_dev_ptr: int, band_stride_samples: int):
+        """Asynchronous on the DDC's stream: band b's n_in_samples / decimation outputs go to float32 I,Q sample
+        b * band_stride_samples of out_dev_ptr on."""
+        _check(self._L.sdr_ddc_process_device(self._h, C.c_void_p(in_dev_ptr), n_in_samples, C.c_void_p(out_dev_ptr), band_stride_samples))
+
+    def process_host(self, samples: np.ndarray, out_dev_ptr: int, band_stride_samples: int):
+        """samples: the wide stream's raw samples in host memory, [n, 2] of float32, int16, int8 or uint8 by in_format."""
+        dt = {DDC_F32: np.float32, DDC_SC16: np.int16, DDC_CS8: np.int8, DDC_CU8: np.uint8}[self.in_format]
+        s = np.ascontiguousarray(samples, dt).reshape(-1, 2)
+        _check(self._L.sdr_ddc_process_host(self._h, C.c_void_p(s.ctypes.data), s.shape[0], C.c_void_p(out_dev_ptr), band_stride_samples))
+
+    def sync(self):
+        _check(self._L.sdr_ddc_sync(self._h))
 
 
 class AudioBank:

@@ -120,6 +120,42 @@ def make_band(n_frames: int, sample_rate: int, block_size: int, n_tones: int, se
     return iq, bins, key
 
 
+def lowpass_taps(decimation: int, taps_per_phase: int = 8) -> np.ndarray:
+    """A Hann-windowed sinc for the down-converter (capi.Ddc), for tests and tools only - the caller owns the filter's shape,
+    as it owns the window's: decimation * taps_per_phase float32 taps, cut-off at half the output rate, unit gain at 0 Hz
+    (the float64 taps sum to 1 before they are rounded)."""
+    t = decimation * taps_per_phase
+    x = np.arange(t, dtype=np.float64) - (t - 1) / 2.0
+    h = np.sinc(x / decimation) * (0.5 - 0.5 * np.cos(2.0 * np.pi * (np.arange(t) + 0.5) / t))
+    return (h / h.sum()).astype(np.float32)
+
+
+def wide_stream(n_samples: int, sample_rate: float, carriers, noise_sigma: float = NOISE_SIGMA, seed: int = 0,
+                quantise: str | None = None) -> np.ndarray:
+    """A wide IQ stream, [n_samples, 2]: complex white noise plus one complex exponential per carrier.  carriers: tuples
+    (offset_hz, amplitude, key), key None (unkeyed) or a 0/1 array with one state per sample (shorter: padded with 0).
+    quantise: None (float32), "cs8" (int8, x * 128 rounded and clipped to [-128, 127]) or "cu8" (uint8, x * 128 + 127.5
+    rounded and clipped to [0, 255]) - the inverses of the values the library gives those bytes (include/sdrainer_hip.h)."""
+    rng = np.random.default_rng(seed)
+    x = noise_sigma * (rng.standard_normal(n_samples) + 1j * rng.standard_normal(n_samples))
+    k = np.arange(n_samples, dtype=np.float64)
+    for offset_hz, amplitude, key in carriers:
+        c = amplitude * np.exp(2j * np.pi * ((offset_hz / sample_rate * k) % 1.0))
+        if key is not None:
+            on = np.zeros(n_samples)
+            on[:min(len(key), n_samples)] = np.asarray(key[:n_samples], np.float64)
+            c *= on
+        x += c
+    s = np.stack([x.real, x.imag], axis=1)
+    if quantise is None:
+        return s.astype(np.float32)
+    if quantise == "cs8":
+        return np.clip(np.rint(s * 128.0), -128, 127).astype(np.int8)
+    if quantise == "cu8":
+        return np.clip(np.rint(s * 128.0 + 127.5), 0, 255).astype(np.uint8)
+    raise ValueError("quantise must be None, 'cs8' or 'cu8'")
+
+
 def make_band_torch(n_frames: int, sample_rate: int, block_size: int, n_tones: int, seed: int, device,
                     edge_width: int | None = None, text: str = TEXT, free_last_window: bool = False):
     """Same signal model generated directly in HBM with torch (benchmark input; not bit-identical to
