@@ -14,9 +14,11 @@ The input reaches the bank by one of the paths of include/sdrainer_hip.h:
   "device_cs8", "device_cu8"  complex 8-bit, signed / unsigned, in device memory (sdr_process_device_iq8)
   "staged"       float32 from the host (sdr_push_iq -> sdr_process_staged)
   "staged_sc16"  complex int16 from the host (sdr_push_iq_sc16)
+  "staged_cs8", "staged_cu8"  complex 8-bit from the host (sdr_push_iq8)
   "kiwi"         KiwiSDR SND payloads, big-endian int16 (sdr_push_kiwi_snd), a batch's frames in several messages
   "graph"        hipGraph replays of float32 batches (sdr_graph_capture / sdr_graph_launch)
   "graph_sc16"   the same for sc16 (sdr_graph_capture_sc16 / sdr_graph_launch_sc16)
+  "graph_cs8", "graph_cu8"  the same for 8-bit input (sdr_graph_capture_iq8 / sdr_graph_launch_iq8)
 The oracle always reads the float32 values the bank was given: for sc16 and KiwiSDR input float32(x) / 32767, for 8-bit
 input iq8_tools.to_f32.
 
@@ -36,9 +38,10 @@ from parity_tools import (RATES, REC_FIELDS, bits_equal, check_batch_polled, che
                           make_stream, nan_equal_bits, sc16_to_float32, windowed)
 
 RATE = 2_000_000
-PATHS = ("device", "device_sc16", "device_cs8", "device_cu8", "staged", "staged_sc16", "kiwi", "graph", "graph_sc16")
+PATHS = ("device", "device_sc16", "device_cs8", "device_cu8", "staged", "staged_sc16", "staged_cs8", "staged_cu8", "kiwi", "graph",
+         "graph_sc16", "graph_cs8", "graph_cu8")
 SC16_PATHS = ("device_sc16", "staged_sc16", "kiwi", "graph_sc16")
-IQ8_PATHS = {"device_cs8": 0, "device_cu8": 1}  # -> SDR_IQ8_CS8 / SDR_IQ8_CU8
+IQ8_PATHS = {"device_cs8": 0, "device_cu8": 1, "staged_cs8": 0, "staged_cu8": 1, "graph_cs8": 0, "graph_cu8": 1}  # -> SDR_IQ8_CS8 / SDR_IQ8_CU8
 SETTERS = ("peak_threshold", "edge_width", "signal_debounce", "find_peaks")
 KIWI_HEADER = bytes([0x01] + [7] * 16)  # the 17 bytes in front of an SND message's samples (flags, sequence, smeter)
 
@@ -109,9 +112,9 @@ class Case:
     step is a batch, a deferred batch or an attach (no detach): a late listener's decoder ticks from the frame it was attached
     at, and its tap is compared from that frame on.
 
-    Not run by any test yet, so not to be trusted before the first row that uses them: the staged paths with a hop below N
-    (the sample range of _enqueue) and run_graph with windows (a window set before the capture, release and a new capture
-    when the next replay's window differs).
+    The staged paths with a hop below N (the sample range of _enqueue) are run by tests/test_gpu_fuzz_features.py's default
+    seeds 5, 6, 12, 14, 19, 24 and 28, one per format and kernel family at least; run_graph with windows (a window set before
+    the capture, release and a new capture when the next replay's window differs) by its seeds 16, 18 and 21.
 
     first_frame: the bank frame index of the stream's first frame (sdr_set_first_frame before the first attach; a multiple
     of 100).  Steps, spans and the oracle stay counted from 0; every frame number the bank hands out is expected shifted by
@@ -126,7 +129,7 @@ class Case:
         self.first_frame = first_frame
         self.n, self.n_bands, self.rate, self.path, self.nan_ok = n, n_bands, rate, path, nan_ok
         self.hop, self.step, self.pad, self.trace = hop or 0, hop or n, pad, trace
-        assert self.step == n or path.startswith("device") or path in ("staged", "staged_sc16"), f"{path} input takes no hop below N"
+        assert self.step == n or path.startswith("device") or path.startswith("staged"), f"{path} input takes no hop below N"
         assert not pad or (self.hop and path.startswith("device")), "a padded band stride is the device stream calls'"
         self.timed = bool(self.hop or trace)
         self.edge = synth.default_edge_width(n) if edge is None else edge
@@ -486,6 +489,8 @@ class Case:
                 assert bank.push_iq(b, self.rate, self.stream[b][lo:hi].reshape(-1)) == 0, f"band {b}: push refused"
             elif self.path == "staged_sc16":
                 assert bank.push_iq_sc16(b, self.rate, self.q[b][lo:hi].reshape(-1)) == 0, f"band {b}: push refused"
+            elif self.path in IQ8_PATHS:
+                assert bank.push_iq8(b, self.rate, self.q[b][lo:hi].reshape(-1), IQ8_PATHS[self.path]) == 0, f"band {b}: push refused"
             else:  # KiwiSDR: the batch's frames in messages of up to 1, 2, 5, 12 ... frames, as the websocket delivers them
                 f, sizes, n = a, (1, 2, 5, 12, 40), self.n
                 while f < e:
@@ -577,7 +582,7 @@ class Case:
         self.run_oracle()
         bank = self.new_bank(capi, torch.cuda.Stream())
         K = bank.graph_batches
-        sc16 = self.path == "graph_sc16"
+        sc16, iq8 = self.path == "graph_sc16", IQ8_PATHS.get(self.path)
         slots = [len(bins) for bins in self.init_bins]
         pos, k, captured, run, baked = 0, 0, False, [], None  # baked: self.controls as of the capture
         for s in self.steps + [("end",)]:
@@ -595,7 +600,11 @@ class Case:
                 torch.cuda.synchronize()  # (the input is written on torch's stream, the bank reads it on its own)
 
                 def launch():
-                    (bank.graph_launch_sc16 if sc16 else bank.graph_launch)([x.data_ptr() for x in batches])
+                    ptrs = [x.data_ptr() for x in batches]
+                    if iq8 is not None:
+                        bank.graph_launch_iq8(ptrs, iq8)
+                    else:
+                        (bank.graph_launch_sc16 if sc16 else bank.graph_launch)(ptrs)
                 if captured and baked != self.controls:  # a control the capture has baked in changed: the replay is refused, nothing has run
                     try:
                         launch()
@@ -607,7 +616,10 @@ class Case:
                     bank.graph_release()
                     captured = False
                 if not captured:
-                    (bank.graph_capture_sc16 if sc16 else bank.graph_capture)(per)
+                    if iq8 is not None:
+                        bank.graph_capture_iq8(per, iq8)
+                    else:
+                        (bank.graph_capture_sc16 if sc16 else bank.graph_capture)(per)
                     captured, baked = True, dict(self.controls)
                 launch()
                 for a, e in run:
