@@ -1,7 +1,7 @@
 // fft_input.h — what an FFT kernel needs from an input format, stated once per format: the word a sample is read as (its
 // size is the bytes per sample), the BatchCursor field that carries a replayed graph's pointer, the staging image of the
-// one-frame kernels (fft_f64.h "Input staging") and the float32 value of a word's two components.  k_fft_psd.hip's one-frame
-// body and k_fft_2p_a.h's input loop are written over these; the conversions themselves are sc16.h's and iq8.h's.
+// one-frame kernels (fft_f64.h "Input staging") and the float32 value of a word's two components.  k_fft_psd.h's one-frame
+// body and k_fft_2p_a.h's input loop are written over these, and the kernel templates take them as template arguments; the conversions themselves are sc16.h's and iq8.h's.
 #pragma once
 #include "iq8.h"
 #include "sc16.h"

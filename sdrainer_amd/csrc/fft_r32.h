@@ -5,7 +5,7 @@
 //
 //   * A thread's 32 complex128 points are 128 VGPRs; at two waves per SIMD a wave has 256, so the NEXT frame's samples
 //     (32 complex64 = 64 VGPRs) are fetched into registers while the current frame computes - the input wait that is a
-//     third of a frame in the 16-point kernel (k_fft_psd.hip) overlaps the arithmetic, without any LDS for it.
+//     third of a frame in the 16-point kernel (k_fft_psd.h) overlaps the arithmetic, without any LDS for it.
 //   * Pass 0's slots are the five highest sample-number bits, its lanes the six lowest: every wave instruction of the
 //     prefetch reads 512 contiguous bytes, each 128-byte line is asked for by exactly one wave.
 //   * The cross-wave exchange sits behind pass 0 (E0); passes 1 and 2 share their wave bits, E1 stays inside a wave's own

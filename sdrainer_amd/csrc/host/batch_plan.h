@@ -154,7 +154,7 @@ inline int fft2p_group_frames(const Switches &sw, int n, int n_bands, int max_fr
     return (int)(f < 1 ? 1 : (f > max_frames ? max_frames : f));
 }
 
-// The 16-point kernels' float32 form (k_fft_psd, k_fft_psd_win) can give a workgroup several consecutive frames.
+// The 16-point kernels' float32 form (k_fft_psd<LOGN, MULTI, WIN...>, plain and windowed) can give a workgroup several consecutive frames.
 // frames per workgroup when the plan asks for none (FftChoice::fpw, SDR_FFT_FPW)
 constexpr int kDefaultFpw = 1;  // in the pipeline short-lived workgroups win: 0.250 (1) / 0.253 (2) / 0.291 (4) / 0.294 ms (8) per step, standalone the other way round (0.174 / 0.166 / 0.165 / 0.164 ms)
 // a workgroup's frames are consecutive; never fewer workgroups than CUs can take (a short batch keeps one
@@ -167,10 +167,10 @@ inline int fft_frames_per_wg(int fpw_asked, int n_frames, int n_bands)
     return fpw;
 }
 
-// N = 16384 has two kernels: k_fft_psd.hip's 16-point one and k_fft_r32.h (512 threads x 32 points, the next frame
+// N = 16384 has two kernels: k_fft_psd.h's 16-point one and k_fft_r32.h (512 threads x 32 points, the next frame
 // prefetched into registers), whose workgroups - one per CU - claim frames from a counter.  By default the 32-point kernel
 // runs from 1024 frames per launch on (measured by batch size) and while the listener slots fit its tap (one per thread).
-// sc16 input takes the same choice (k_fft_r32_sc16 or k_fft_psd_sc16<14>): the rule does not look at the format.
+// sc16 input takes the same choice (k_fft_r32<InSc16, .> or k_fft_psd_narrow<InSc16, 14, .>): the rule does not look at the format.
 // (bench.py restates the frame-count rule to name the kernel in its report.)
 // windowed: the bank has a window (sdr_set_window).  k_fft_r32 has no windowed form - it has no register left for a
 // thread's 32 window values beside its prefetched frame - so a windowed batch never takes it, SDR_FFT_R32=1 or not: N =
@@ -196,11 +196,11 @@ inline FftChoice fft_choice(const Switches &sw, int n, int n_frames, int n_bands
 
 // One id per kernel symbol a batch can launch first (the two-phase ids name phase A; k_fft2p_b follows every one of them).
 enum class FftKernel {
-    // k_fft_psd.hip and its recompilations k_fft_psd_win.hip, k_fft_psd_iq8.hip (PSD_IQ8*: cs8 and cu8, a launch argument)
+    // k_fft_psd.h, instantiated by k_fft_psd.hip, k_fft_psd_win.hip and k_fft_psd_iq8.hip (PSD_IQ8*: cs8 and cu8, a launch argument)
     PSD, PSD_MULTI, PSD_SC16, PSD_IQ8, PSD_WIN, PSD_WIN_MULTI, PSD_SC16_WIN, PSD_IQ8_WIN,
     // k_fft_r32.h, one instance per k_fft_r32*.hip unit (R32*_IQ8: cs8 and cu8, a launch argument)
     R32, R32_SC16, R32_IQ8, R32_HOP, R32_HOP_SC16, R32_HOP_IQ8,
-    // k_fft_2p.hip (F32, SC16) and k_fft_2p_iq8.hip (CS8, CU8): phase A's instances
+    // k_fft_2p_a.h: phase A's instances, in k_fft_2p.hip (F32, SC16) and k_fft_2p_iq8.hip (CS8, CU8)
     A2P_F32, A2P_SC16, A2P_CS8, A2P_CU8, A2P_WIN_F32, A2P_WIN_SC16, A2P_WIN_CS8, A2P_WIN_CU8,
     COUNT
 };
@@ -231,7 +231,9 @@ inline FftKernel fft_kernel(const FftChoice &c)
     return c.windowed ? K::PSD_WIN : K::PSD;
 }
 
-// the kernel symbol's base name, as the compiler's resource listings spell it (profiles/*_kernel_resources.txt)
+// The kernel's label: what tests and tools read through the plan, and the symbol's base name in the resource listings taken
+// while each kernel had a name of its own (profiles/*_kernel_resources.txt).  The k_fft_r32, k_fft_psd and k_fft2p_a
+// kernels are template instances now; their labels stay.
 inline const char *fft_kernel_name(FftKernel k)
 {
     using K = FftKernel;

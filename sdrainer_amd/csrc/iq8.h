@@ -31,7 +31,7 @@ SDR_HD inline float re_of(uint32_t w, Format f) { return to_f32((w ^ f.flip) & 0
 SDR_HD inline float im_of(uint32_t w, Format f) { return to_f32(((w ^ f.flip) >> 8) & 0xffu, f.c); }
 
 // ---------------------------------------------------------------------------------------------
-// The staging image of k_fft_psd_iq8 (the float32 kernel's is fft_f64.h "Input staging", the sc16 kernel's sc16.h): the
+// The staging image of k_fft_psd_narrow<InIq8, ..> (the float32 kernel's is fft_f64.h "Input staging", the sc16 kernel's sc16.h): the
 // frame is copied global -> LDS by LDS-DMA, one contiguous 1 KB row of 512 samples per wave instruction, 16 bytes (a
 // granule of eight samples) per lane, and read back in the pass-0 layout with one 16-bit LDS read per register slot.  Such
 // a read is served in two groups of 32 lanes over 32 four-byte banks; two lanes that read the two halves of ONE dword do

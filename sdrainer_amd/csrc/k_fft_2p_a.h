@@ -1,24 +1,39 @@
-// k_fft_2p_a.h — phase A of the two-phase FFT (k_fft_2p.hip), plain and windowed: no include guard, see below.
+// k_fft_2p_a.h — phase A of the two-phase FFT (k_fft_2p.hip) as one kernel template over block size, input format and
+// window, and the launcher of a batch's frame groups.
 // Phase A of frames [frame0, frame0 + group) of band blockIdx.y: workgroup x = frame_local * WG_A + w takes the sub-FFTs
 // p = w G .. w G + G - 1 (blocks k = brev_B(p)).  Y: [band][group frames][N].
 //
-// k_fft_2p.hip includes this file twice.  SDR_FFT2P_WIN = 0: k_fft2p_a, whose tokens are what they were before the window
-// existed.  SDR_FFT2P_WIN = 1: k_fft2p_win_a, which multiplies sample i of the frame by win[i] (sdr_set_window) - one
-// correctly rounded float32 multiplication per component, of the converted value for sc16 input - where the plain kernel
-// widens it.  One input loop serves every format (fft_input.h).  FMT = CS8 / CU8 (iq8.h: two bytes per sample) is
-// instantiated by k_fft_2p_iq8.hip only.
-#if SDR_FFT2P_WIN
-#define SDR_K_FFT2P_A k_fft2p_win_a
-#define SDR_FFT2P_WIN_PARAM , const float *__restrict__ win
-#else
-#define SDR_K_FFT2P_A k_fft2p_a
-#define SDR_FFT2P_WIN_PARAM
-#endif
-template <int LOGN, InFormat FMT>
-__global__ __launch_bounds__(fft2p::T) void SDR_K_FFT2P_A(const void *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
-                                                      const fft64::cplx *__restrict__ tw, fft64::cplx *__restrict__ y, size_t in_stride,
-                                                      int frame_stride, int frame0, int group SDR_FFT2P_WIN_PARAM)
+// WIN... is empty or the bank's window table (sdr_set_window).  With it the kernel multiplies sample i of the frame by
+// win[i] - one correctly rounded float32 multiplication per component, of the converted value for the narrow formats -
+// where the plain kernel widens it.  One input loop serves every format (fft_input.h).  k_fft_2p.hip instantiates the
+// launcher for F32 and SC16, k_fft_2p_iq8.hip for CS8 and CU8 (iq8.h: two bytes per sample); phase B is k_fft_2p.hip's
+// for all of them (launch_fft2p_b).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/sdrainer_hip.h"
+#include "fft_2p.h"
+#include "fft_input.h"
+
+namespace sdr {
+
+__device__ __forceinline__ fft64::cplx tw_load(const fft64::cplx *__restrict__ tw, int i)
 {
+    return tw[i];
+}
+
+// the window's value for sample i (called with the kernel's WIN... pack, which holds the table)
+__device__ __forceinline__ float window_value(const float *__restrict__ win, int i)
+{
+    return win[i];
+}
+
+template <int LOGN, InFormat FMT, class... WIN>
+__global__ __launch_bounds__(fft2p::T) void k_fft2p_a(const void *__restrict__ iq_arg, const BatchCursor *__restrict__ cur,
+                                                      const fft64::cplx *__restrict__ tw, fft64::cplx *__restrict__ y, size_t in_stride,
+                                                      int frame_stride, int frame0, int group, WIN... win)
+{
+    static_assert(sizeof...(WIN) <= 1, "the window table or nothing");
     using PH = fft2p::Phases<LOGN>;
     using S = typename PH::SA;
     constexpr int N = PH::N, MB = PH::A;
@@ -37,14 +52,14 @@ __global__ __launch_bounds__(fft2p::T) void SDR_K_FFT2P_A(const void *__restrict
         for (int s = 0; s < fft2p::R; s++) {
             const int i = fft2p::a_sample<LOGN>(p, fft2p::p0_index<MB>(t, s));
             const typename IN::word v = iq[i];
-#if SDR_FFT2P_WIN
-            const float wv = win[i];
-            xr[s] = (double)__fmul_rn(in.re(v), wv);
-            xi[s] = (double)__fmul_rn(in.im(v), wv);
-#else
-            xr[s] = (double)in.re(v);
-            xi[s] = (double)in.im(v);
-#endif
+            if constexpr (sizeof...(WIN) == 1) {
+                const float wv = window_value(win..., i);
+                xr[s] = (double)__fmul_rn(in.re(v), wv);
+                xi[s] = (double)__fmul_rn(in.im(v), wv);
+            } else {
+                xr[s] = (double)in.re(v);
+                xi[s] = (double)in.im(v);
+            }
         }
         fft2p::pass0<MB>(xr, xi, LOGN, 0, 0, t, W);
 #pragma unroll
@@ -69,5 +84,58 @@ __global__ __launch_bounds__(fft2p::T) void SDR_K_FFT2P_A(const void *__restrict
     for (int s = 0; s < fft2p::R; s++)
         out[fft2p::p1_index<MB, true>(t, s)] = fft64::cplx{xr[s], xi[s]};
 }
-#undef SDR_K_FFT2P_A
-#undef SDR_FFT2P_WIN_PARAM
+
+// A batch, frame group by frame group: launch_a(f0, g) launches phase A of frames [f0, f0 + g) on at.stream, phase B
+// (k_fft_2p.hip's, for every format) follows it.  at.done rides on the last frame group's phase B, the last launch, and on
+// nothing else.
+template <class A>
+static hipError_t launch_fft2p_groups(const FftLaunch &l, LaunchAt at, A launch_a)
+{
+    if (!l.fft.two_phase || l.fft.windowed != (l.window != nullptr))
+        return hipErrorInvalidValue;
+    if (l.n_frames <= 0 || l.n_bands <= 0)
+        return hipSuccess;
+    if (!l.scratch || l.fft.group_frames <= 0)
+        return hipErrorInvalidValue;
+    const int group = l.fft.group_frames;
+    for (int f0 = 0; f0 < l.n_frames; f0 += group) {
+        const int g = l.n_frames - f0 < group ? l.n_frames - f0 : group;
+        launch_a(f0, g);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess)
+            e = launch_fft2p_b(l, f0, g, f0 + group >= l.n_frames ? at : LaunchAt(at.stream));
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+template <int LOGN, InFormat FMT>
+static hipError_t launch_fft2p_t(const FftLaunch &l, LaunchAt at)
+{
+    using PH = fft2p::Phases<LOGN>;
+    const int group = l.fft.group_frames;
+    return launch_fft2p_groups(l, at, [&](int f0, int g) {
+        if (l.window)
+            hipLaunchKernelGGL((k_fft2p_a<LOGN, FMT, const float *__restrict__>), dim3(g * PH::WG_A, l.n_bands), dim3(fft2p::T), 0, at.stream, l.iq, l.cur, l.tw,
+                               l.scratch, l.in_stride, l.frame_stride, f0, group, l.window);
+        else
+            hipLaunchKernelGGL((k_fft2p_a<LOGN, FMT>), dim3(g * PH::WG_A, l.n_bands), dim3(fft2p::T), 0, at.stream, l.iq, l.cur, l.tw, l.scratch, l.in_stride,
+                               l.frame_stride, f0, group);
+    });
+}
+
+// N = 32768 / 65536, frames of format FMT with a window or without; any other format refused
+template <InFormat FMT>
+hipError_t launch_fft_2p(const FftLaunch &l, LaunchAt at)
+{
+    if (l.fft.fmt != FMT)
+        return hipErrorInvalidValue;
+    switch (l.logn) {
+    case 15: return launch_fft2p_t<15, FMT>(l, at);
+    case 16: return launch_fft2p_t<16, FMT>(l, at);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace sdr

@@ -1,4 +1,5 @@
-// k_fft_psd_iq8.hip — k_fft_psd for 8-bit input (cs8 / cu8, iq8.h), plain and windowed: k_fft_psd.hip compiled a third
-// time, in a translation unit of its own beside the float32 and sc16 kernels' (see that file's header).  Holds k_fft_psd_iq8<9..14, false / true> and launch_fft_psd_iq8 only.
-#define SDR_FFT_IQ8 1
-#include "k_fft_psd.hip"
+// k_fft_psd_iq8.hip — k_fft_psd (k_fft_psd.h) for 8-bit input (cs8 / cu8, iq8.h), without a window and with one.
+#include "k_fft_psd.h"
+
+template hipError_t sdr::launch_fft_psd<sdr::InIq8, false>(const sdr::FftLaunch &, sdr::LaunchAt);
+template hipError_t sdr::launch_fft_psd<sdr::InIq8, true>(const sdr::FftLaunch &, sdr::LaunchAt);

@@ -1,5 +1,5 @@
-// k_fft_psd_win.hip — k_fft_psd and k_fft_psd_sc16 with a window on the frames (sdr_set_window): k_fft_psd.hip compiled
-// again, in a translation unit of its own so that the plain kernels' code stays exactly what it was (see that file's
-// header).
-#define SDR_FFT_WIN 1
-#include "k_fft_psd.hip"
+// k_fft_psd_win.hip — k_fft_psd (k_fft_psd.h) for float32 and sc16 input with a window on the frames (sdr_set_window).
+#include "k_fft_psd.h"
+
+template hipError_t sdr::launch_fft_psd<sdr::InF32, true>(const sdr::FftLaunch &, sdr::LaunchAt);
+template hipError_t sdr::launch_fft_psd<sdr::InSc16, true>(const sdr::FftLaunch &, sdr::LaunchAt);

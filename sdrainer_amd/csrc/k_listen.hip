@@ -20,7 +20,7 @@
 namespace sdr {
 
 // One lane per listener slot, one wave per 64 frames: lane l reads tap[f][l] for the wave's frames (the FFT kernel
-// wrote the psd value of the slot's bin there, k_fft_psd.hip "The tap"; neighbouring lanes read neighbouring
+// wrote the psd value of the slot's bin there, k_fft_psd.h "The tap"; neighbouring lanes read neighbouring
 // words), projects it to dB - the certified table shortcut of gomath.h, the literal Go algorithm where its
 // certificate fails - and collects its own 64 comparison results into one word.  Sixteen waves to a workgroup: round
 // 2's one-wave workgroups with the literal logarithm (0.031 ms) went to 128 different CUs and kept an FFT workgroup,

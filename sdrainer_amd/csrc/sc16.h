@@ -1,5 +1,5 @@
 // sc16.h — complex int16 input ("sc16": int16 I, then int16 Q, little-endian), read by the FFT kernels themselves
-// (k_fft_psd.hip k_fft_psd_sc16, k_fft_r32_sc16.hip) and unpacked by k_unpack.hip for the staged host path.
+// (k_fft_psd.h k_fft_psd_narrow<InSc16, ..>, k_fft_r32_sc16.hip) and unpacked by k_unpack.hip for the staged host path.
 //
 // A sample's value is float32(x) / 32767, correctly rounded: the reference's float32(int16(v)) / float32(math.MaxInt16)
 // (kiwi/client.go:298-308), and what k_unpack.hip's be16_to_f32 computes with a division.  Everything after the
@@ -31,7 +31,7 @@ SDR_HD inline float re_of(uint32_t w) { return to_f32((int16_t)(uint16_t)(w & 0x
 SDR_HD inline float im_of(uint32_t w) { return to_f32((int16_t)(uint16_t)(w >> 16)); }
 
 // ---------------------------------------------------------------------------------------------
-// The staging image of k_fft_psd_sc16 (the float32 kernel's is fft_f64.h "Input staging"): the frame is copied global ->
+// The staging image of k_fft_psd_narrow<InSc16, ..> (the float32 kernel's is fft_f64.h "Input staging"): the frame is copied global ->
 // LDS by LDS-DMA, one contiguous 1 KB row of 256 samples per wave instruction, 16 bytes (a granule of four samples) per
 // lane, and read back in the pass-0 layout with one ds_read_b32 per register slot.  A ds_read_b32 is served in two
 // groups of 32 lanes over 32 four-byte banks: the 32 lanes' words must differ mod 32, i.e. in word-address bits 0-4.

@@ -33,7 +33,7 @@ struct ListenerSlot {
     uint32_t text_count;    // runes in the text buffer not yet read by the host
     uint32_t text_dropped;  // runes dropped because the buffer was full (since attach)
     // Bank frame index (32 bits, wrapping like every frame number on the device) from which the listener listens, and
-    // from which the FFT kernel has tapped its bin (k_fft_psd.hip "The tap").  Equal for a listener attached between
+    // from which the FFT kernel has tapped its bin (k_fft_psd.h "The tap").  Equal for a listener attached between
     // batches.  A listener bound to a batch whose spectra already exist (sdr_attach_at: strain-mode discovery without a
     // host round trip per cumulation) starts inside that batch - frames before start_frame do not reach its debouncer
     // or decoder - and reads its bin from the retained psd rows up to tapped_from.
@@ -158,7 +158,7 @@ inline hipError_t raise_lds_limit_once(LdsLimitOnce &once, std::initializer_list
     return attr_err;
 }
 
-// The listeners' bins of every band and where their psd values go (k_fft_psd.hip "The tap").
+// The listeners' bins of every band and where their psd values go (k_fft_psd.h "The tap").
 struct FftTap {
     const int32_t *bins;  // [band][stride], -1 = free slot
     float *out;           // [band][out_stride frames][stride]
@@ -191,8 +191,8 @@ struct FftLaunch {
     // k_fft_2p only: one frame group's float64 intermediate, [band][FftChoice::group_frames][N] (BatchSet::fft_scratch)
     fft64::cplx *scratch = nullptr;
     // the bank's window table, [N] float32 in window_layout's order (sdr_set_window), null = none: sample i of every frame
-    // is multiplied by its value in float32 before it is widened, by the windowed forms of the kernels (k_fft_psd_win.hip,
-    // k_fft2p_win_a)
+    // is multiplied by its value in float32 before it is widened, by the windowed instances of the kernels (k_fft_psd.h,
+    // k_fft_2p_a.h)
     const float *window = nullptr;
 };
 
@@ -201,27 +201,28 @@ struct FftLaunch {
 hipError_t launch_fft(const FftLaunch &l, LaunchAt at);
 int twiddle_count(int logn);
 void build_twiddles(int logn, const double *wre, const double *wim, fft64::cplx *out);
-// One entry per kernel unit: it launches the kernels of fft_kernel(l.fft) that the unit holds and returns
-// hipErrorInvalidValue for any other id.  k_fft_psd.hip and its recompilations, N = 512 - 16384: float32 and sc16 frames,
-// the same with a window, 8-bit frames with a window or without
-hipError_t launch_fft_psd(const FftLaunch &l, LaunchAt at);
-hipError_t launch_fft_psd_win(const FftLaunch &l, LaunchAt at);
-hipError_t launch_fft_psd_iq8(const FftLaunch &l, LaunchAt at);
-// k_fft_psd_win.hip: the order its kernels read the window table in: out[N] from the caller's w[N] (sample order)
-void window_layout(int logn, const float *w, float *out);
-// k_fft_r32.h, one instance per k_fft_r32*.hip unit: N = 16384 as 512 threads x 32 points with the next frame prefetched
-// into registers (l.tw: their own twiddle layout), by input format (fft_input.h: InF32, InSc16, InIq8), dense frames (HOP =
-// false) and frame_stride < N (a power of two; HOP = true).  Workgroups per band = max(1, ceil((CUs - fft.reserve_cus) /
-// n_bands)), at most n_frames (unless fft.reserve_forced the reserve is at most CUs / kReserveDeviceShare)
+// The launchers are templates, instantiated by the kernel units (fft_input.h: InF32, InSc16, InIq8).  An instance launches
+// the kernels of fft_kernel(l.fft) that are its own and returns hipErrorInvalidValue for any other id.
 struct InF32;
 struct InSc16;
 struct InIq8;
+// k_fft_psd.h, N = 512 - 16384, by input format and window: k_fft_psd.hip holds float32 and sc16 frames, k_fft_psd_win.hip
+// the same with a window, k_fft_psd_iq8.hip 8-bit frames with a window and without
+template <class IN, bool WIN>
+hipError_t launch_fft_psd(const FftLaunch &l, LaunchAt at);
+// fft_launch.hip: the order the windowed kernels read the window table in: out[N] from the caller's w[N] (sample order)
+void window_layout(int logn, const float *w, float *out);
+// k_fft_r32.h, one instance per k_fft_r32*.hip unit: N = 16384 as 512 threads x 32 points with the next frame prefetched
+// into registers (l.tw: their own twiddle layout), dense frames (HOP = false) and frame_stride < N (a power of two; HOP =
+// true).  Workgroups per band = max(1, ceil((CUs - fft.reserve_cus) / n_bands)), at most n_frames (unless
+// fft.reserve_forced the reserve is at most CUs / kReserveDeviceShare)
 template <class IN, bool HOP>
 hipError_t launch_fft_r32(const FftLaunch &l, LaunchAt at);
-// k_fft_2p.hip (float32, sc16) and k_fft_2p_iq8.hip (cs8, cu8): N = 32768 / 65536 as two phases over l.scratch (fft_2p.h),
-// frame group by frame group; phase B of frames [f0, f0 + g) of a group is k_fft_2p.hip's for both
+// k_fft_2p_a.h, by input format, with a window or without: N = 32768 / 65536 as two phases over l.scratch (fft_2p.h), frame
+// group by frame group.  k_fft_2p.hip holds F32 and SC16, k_fft_2p_iq8.hip CS8 and CU8; phase B of frames [f0, f0 + g) of a
+// group is k_fft_2p.hip's for all of them
+template <InFormat FMT>
 hipError_t launch_fft_2p(const FftLaunch &l, LaunchAt at);
-hipError_t launch_fft_2p_iq8(const FftLaunch &l, LaunchAt at);
 hipError_t launch_fft2p_b(const FftLaunch &l, int f0, int g, LaunchAt at);
 // wpb_forced: windows per workgroup (0: the launcher's rule); mfma: the matrix-pipe variance kernel (host/batch_plan.h)
 hipError_t launch_window_means(const float *psd, double *win_mean, NoiseGeom g, int n_frames, int n_bands, int stride, int wpb_forced,

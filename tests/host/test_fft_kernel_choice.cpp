@@ -100,7 +100,8 @@ FftKernel old_chain(const Case &c, bool *refused)
     return old_fpw(c) > 1 ? K::PSD_MULTI : K::PSD;
 }
 
-// the kernel symbols' base names, as profiles/*_kernel_resources.txt spell them
+// the kernels' labels: the base names their symbols had when each kernel was a function of its own, as
+// profiles/*_kernel_resources.txt spell them (today k_fft_psd.h, k_fft_r32.h and k_fft_2p_a.h hold templates; the labels stay)
 const char *old_name(FftKernel k)
 {
     static const char *const names[(int)FftKernel::COUNT] = {
@@ -129,7 +130,7 @@ sdr::FftChoice choose(const Case &c)
     return sdr::fft_choice(sdr::read_switches(), c.n, c.frames, c.bands, c.slots, c.windowed, c.fmt, c.hop);
 }
 
-// what a unit's entry checks before it launches (k_fft_psd.hip, k_fft_r32.h, k_fft_2p.hip): none may refuse a planned choice
+// what a launcher instance checks before it launches (k_fft_psd.h, k_fft_r32.h, k_fft_2p_a.h): none may refuse a planned choice
 bool a_unit_takes(const sdr::FftChoice &c, int n, int slots, int frame_stride)
 {
     switch (sdr::fft_kernel(c)) {

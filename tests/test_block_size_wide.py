@@ -61,7 +61,13 @@ def usage(tmp_path_factory):
 
 def test_two_phase_kernels_resources(usage):
     names = sorted(usage)
-    assert sum("k_fft2p_a" in n for n in names) == 4 and sum("k_fft2p_b" in n for n in names) == 2, names
+    # phase A is one template, k_fft2p_a<LOGN, FMT, WIN...>: the pack is mangled J..E, empty (JE) for the plain instances
+    # and the window table's type for the windowed ones; N = 32768 / 65536 x float32 / sc16 of each
+    phase_a = [n for n in names if "k_fft2p_a" in n]
+    plain = [n for n in phase_a if re.search(r"InFormatE\dEJEE", n)]
+    windowed = [n for n in phase_a if re.search(r"InFormatE\dEJ\w*PKfEE", n)]
+    assert len(plain) == 4 and len(windowed) == 4 and len(phase_a) == 8, names
+    assert sum("k_fft2p_b" in n for n in names) == 2 and len(names) == 10, names
     for name, u in usage.items():
         assert int(u["VGPRs Spill"]) == 0 and int(u["SGPRs Spill"]) == 0, name
         assert int(u["ScratchSize [bytes/lane]"]) == 0, name

@@ -184,7 +184,7 @@ def test_stream_wide_block(capi, fmt):
 @both
 def test_windowed(capi, fmt):
     """A random asymmetric window: N = 1024 dense (k_fft_psd_iq8's windowed twin) and N = 32768 with hop 4096
-    (k_fft2p_win_a's 8-bit instances), against bank A with the same table and the oracle on the windowed frames."""
+    (k_fft2p_a's windowed 8-bit instances), against bank A with the same table and the oracle on the windowed frames."""
     n, tones, frames = 1024, 6, 45
     w = random_window(n, 900)
     p = Pair(capi, n, 2, frames, tones, fmt)

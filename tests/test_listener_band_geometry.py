@@ -68,7 +68,7 @@ def test_crossing_512_slots_inside_a_deferred_batch(capi):
 @pytest.mark.parametrize("n,listeners", [(8192, 4096), (8192, 4097), (16384, 4100)])
 def test_lds_tap_capacity(capi, n, listeners):
     """The one-frame FFT kernel (host/batch_plan.h kDefaultFpw = 1) keeps its listeners' bins in LDS while
-    n_tap <= kMaxLdsTap (k_fft_psd.hip:519 `lds_tap`, and the dynamic LDS size at :1003) and drains the tap from the
+    n_tap <= kMaxLdsTap (k_fft_psd.h `lds_tap`, and the dynamic LDS size in launch_fft_t) and drains the tap from the
     stored psd row past it (:635, tap_frame).  4096 and 4097 listeners on one band of N = 8192 in two 512-frame batches,
     and 4100 at N = 16384 in two 1024-frame batches: the frame count would select k_fft_r32 there, and it is the slot
     count (fft_choice, tap_n > kR32MaxTap) that puts the tap on k_fft_psd<14> instead.  64 or 65 gather rows."""

@@ -1,5 +1,5 @@
 """The places where a kernel could rely on documented-by-measurement hardware ordering rather than on the memory model -
-k_noise.hip's LDS flags ordered against data by program order only, k_fft_psd.hip's counted vmcnt - have a formally fenced
+k_noise.hip's LDS flags ordered against data by program order only, k_fft_psd.h's counted vmcnt - have a formally fenced
 form (-DSDR_SAFE_FENCES: workgroup-scope fences, acquire / release flags, full waits).  Round 5 priced it (under a percent)
 and made it the PRODUCT; the program-order form is kept as a variant (__graft_entry__.build() makes it beside the product)
 so that the price stays measurable.  Both must give the same bits: the parity tests that exercise the chain kernels

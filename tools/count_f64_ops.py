@@ -33,7 +33,8 @@ with tempfile.TemporaryDirectory() as tmp:
 
 out = {}
 for logn in range(9, 15):
-    m = re.search(r"^(_ZN3sdr9k_fft_psdILi%dELb0E\w*):[^\n]*\n(.*?)s_endpgm" % logn, asm, re.S | re.M)
+    # k_fft_psd<LOGN, false> with an empty WIN... pack (k_fft_psd.h): float32 frames, one per workgroup, no window
+    m = re.search(r"^(_ZN3sdr9k_fft_psdILi%dELb0EJEEEv\w*):[^\n]*\n(.*?)s_endpgm" % logn, asm, re.S | re.M)
     body = m.group(2)
     counts = {op: len(re.findall(r"^\s+%s\b" % op, body, re.M)) for op in
               ("v_add_f64", "v_mul_f64", "v_fma_f64", "v_fmac_f64_e32")}

@@ -110,7 +110,7 @@ int main(int argc, char **argv)
     sdr::FftLaunch fl{logn, choice, iq, nullptr, tw, pd, frames, bands, (size_t)frames * N, N, frames, tap, steal};
     if (choice.r32)  // (the second table of the N = 16384 buffer, as launch_fft hands it on)
         fl.tw = tw + fft64::Plan<14>::TW_TOTAL;
-    auto launch = [&](hipStream_t st) { return choice.r32 ? sdr::launch_fft_r32<sdr::InF32, false>(fl, st) : sdr::launch_fft_psd(fl, st); };
+    auto launch = [&](hipStream_t st) { return choice.r32 ? sdr::launch_fft_r32<sdr::InF32, false>(fl, st) : sdr::launch_fft_psd<sdr::InF32, false>(fl, st); };
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));

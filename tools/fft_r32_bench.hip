@@ -126,7 +126,7 @@ int main(int argc, char **argv)
     sdr::FftLaunch l32{logn, sdr::fft_choice(sw32, N, frames, bands, n_tap), iq, nullptr, tw32, pd32, frames, bands, (size_t)frames * N, N, frames, tap32, steal};
     l32.fft.reserve_cus = std::max(0, sw32.fft_reserve);  // SDR_FFT_RESERVE: CUs the 32-point kernel's grid leaves free
     l32.fft.reserve_forced = true;
-    auto launch16 = [&](hipStream_t st) { return sdr::launch_fft_psd(l16, st); };
+    auto launch16 = [&](hipStream_t st) { return sdr::launch_fft_psd<sdr::InF32, false>(l16, st); };
     auto launch32 = [&](hipStream_t st) { return sdr::launch_fft_r32<sdr::InF32, false>(l32, st); };
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
