@@ -2,8 +2,9 @@
 // translation units that implement it share.
 //   capi_bank.hip     create / destroy / control calls (attach, detach, setters), profiling
 //   capi_process.hip  the scheduler: one batch's kernels over the bank's four streams (eager, captured, deferred listen
-//                     half), the staged host input
-//   capi_results.hip  bulk delivery (sdr_enable_results / sdr_poll / sdr_poll_peaks, rows, listener reports) over host/delivery.h
+//                     half), the device-input entry points
+//   capi_staged.hip   the host-fed input: sdr_push_* into pinned staging sets, sdr_process_staged (rows and kinds: host/staging.h)
+//   capi_results.hip bulk delivery (sdr_enable_results / sdr_poll / sdr_poll_peaks, rows, listener reports) over host/delivery.h
 //   capi_graph.hip    graph mode (sdr_graph_*)
 //   capi_read.hip     per-listener / per-batch reads and the scope tap (they synchronise)
 #pragma once
@@ -25,6 +26,7 @@
 #include "../../include/sdrainer_hip.h"
 #include "host/delivery.h"
 #include "host/frequency_mapping.h"
+#include "host/staging.h"
 #include "sdr_device.h"
 
 namespace sdrcapi {
@@ -42,6 +44,15 @@ inline int fail(int code, const std::string &msg)
         if (_e != hipSuccess)                                                                          \
             return fail(SDR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));               \
     } while (0)
+
+// The ABI's 8-bit format number (the *_iq8 calls) -> the FFT's InFormat; anything else is refused.
+inline int iq8_format(int format, sdr::InFormat *fmt)
+{
+    if (format != SDR_IQ8_CS8 && format != SDR_IQ8_CU8)
+        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
+    *fmt = format == SDR_IQ8_CU8 ? sdr::InFormat::CU8 : sdr::InFormat::CS8;
+    return SDR_OK;
+}
 
 template <class T>
 struct DevBuf {
@@ -250,27 +261,30 @@ struct sdr_bank {
     std::unique_ptr<host::Delivery> results;
     std::mutex center_mu;  // center_frequency: written by sdr_set_center_frequency, snapshot per batch
 
-    // Host-fed input (sdr_push_iq / sdr_push_kiwi_snd -> sdr_process_staged).  Three staging sets rotate, so the
-    // caller's copy into pinned memory, the upload (its own stream) and the FFT of consecutive batches overlap:
+    // Host-fed input (sdr_push_iq / sdr_push_kiwi_snd -> sdr_process_staged, capi_staged.hip).  Three staging sets rotate,
+    // so the caller's copy into pinned memory, the upload (its own stream) and the FFT of consecutive batches overlap:
     // nothing on this path waits for the device unless the ring has wrapped around onto work still in flight.
-    struct Staging {
-        // A band's row holds `stage_cap` samples: what max_batch_frames frames span, (max_batch_frames - 1) * hop + N.  The
-        // pinned rows hold the samples pushed since the last batch; the device row holds the history (the last N - hop
-        // samples of the frames the batch before consumed, none at hop = N) and the uploaded samples behind it.
-        float *h_f32 = nullptr;        // pinned [band][stage_cap][2] float32 samples
-        uint8_t *h_raw = nullptr;      // pinned, [band] rows of stage_cap * 4 bytes: [2] int16 per sample, big-endian (KiwiSDR payloads) or sc16, or [2] bytes per sample (cs8 / cu8: half a row), on demand
-        DevBuf<float> d_f32;           // [band][stage_cap][2]: what the FFT kernel reads
-        DevBuf<uint8_t> d_raw;         // raw int16 bytes, unpacked on the device (k_unpack.hip)
-        hipEvent_t uploaded = nullptr;  // the upload has left the pinned buffers (they may be overwritten)
-        hipEvent_t consumed = nullptr;  // the FFT has read d_f32 (it may be overwritten)
-    };
-    static constexpr int STAGE_RING = 3;
-    Staging stage[STAGE_RING];
-    int stage_cur = 0;  // the set sdr_push_* currently fills
-    hipStream_t copy_stream = nullptr;
-    std::vector<sdr::StreamStage> staged;  // per band: history and staged samples (host/overlap.h)
-    size_t stage_cap() const { return sdr::span_samples(cfg.max_batch_frames, hop, cfg.block_size); }
-    std::vector<int> staged_kind;  // per band: 0 nothing staged, 1 float32 frames, 2 int16be frames, 3 sc16 frames, 4 cs8 frames, 5 cu8 frames
+    struct StagedInput {
+        struct Staging {
+            // A band's row holds `stage_cap` samples: what max_batch_frames frames span, (max_batch_frames - 1) * hop + N.  The
+            // pinned rows hold the samples pushed since the last batch; the device row holds the history (the last N - hop
+            // samples of the frames the batch before consumed, none at hop = N) and the uploaded samples behind it.
+            // Which bytes of a row a kind of frames fills is host/staging.h's.
+            float *h_f32 = nullptr;        // pinned [band][stage_cap][2] float32 samples, on demand
+            uint8_t *h_raw = nullptr;      // pinned, [band] rows of stage_cap * 4 bytes: [2] int16 per sample, big-endian (KiwiSDR payloads) or sc16, or [2] bytes per sample (cs8 / cu8: half a row), on demand
+            DevBuf<float> d_f32;           // [band][stage_cap][2]: what the FFT kernel reads
+            DevBuf<uint8_t> d_raw;         // raw int16 bytes, unpacked on the device (k_unpack.hip)
+            hipEvent_t uploaded = nullptr;  // the upload has left the pinned buffers (they may be overwritten)
+            hipEvent_t consumed = nullptr;  // the FFT has read d_f32 (it may be overwritten)
+        };
+        static constexpr int STAGE_RING = 3;
+        Staging stage[STAGE_RING];
+        int stage_cur = 0;  // the set sdr_push_* currently fills
+        hipStream_t copy_stream = nullptr;
+        std::vector<sdr::StreamStage> staged;  // per band: history and staged samples (host/overlap.h)
+        std::vector<sdr::StagedKind> staged_kind;  // per band: what its staged frames are (host/staging.h)
+    } in;
+    size_t stage_cap() const { return sdr::span_samples(cfg.max_batch_frames, hop, cfg.block_size); }  // (needs the bank's geometry)
 
     bool profiling = false;
     double prof_ms[sdr::K_PROFILE_SLOTS] = {};

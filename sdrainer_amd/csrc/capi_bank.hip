@@ -1,7 +1,8 @@
 // capi_bank.hip — the bank behind the C ABI (include/sdrainer_hip.h): creation and destruction of its HBM-resident
 // state, the control calls that touch state owned by a pipeline stage (attach / detach / setters: applied between
 // batches, as the reference applies them between frames, rx/receiver.go:166-172), profiling.  The scheduler is
-// capi_process.hip, delivery capi_results.hip, graph mode capi_graph.hip, reads capi_read.hip (see bank.h).
+// capi_process.hip, the host-fed input capi_staged.hip, delivery capi_results.hip, graph mode capi_graph.hip, reads
+// capi_read.hip (see bank.h).
 #include "bank.h"
 #include "twiddles.h"
 
@@ -386,8 +387,8 @@ int sdr_create(const sdr_config *cfg, sdr_bank **out)
     b->h_slots.assign(B * L, sdr::ListenerSlot{});
     b->n_slots.assign(B, 0);
     b->center_frequency.assign(B, 0);
-    b->staged.assign(B, sdr::StreamStage{N, b->hop, 0, 0});
-    b->staged_kind.assign(B, 0);
+    b->in.staged.assign(B, sdr::StreamStage{N, b->hop, 0, 0});
+    b->in.staged_kind.assign(B, sdr::StagedKind::None);
     {
         const int prc = probe_fft_queue(b);  // (the null stream's queue against the bank's; sdr_set_stream looks again)
         if (prc) {
@@ -437,11 +438,11 @@ int sdr_destroy(sdr_bank *b)
     for (int s = 0; s < N_STAGES; s++)
         if (b->own_stream[s] && b->stream[s])
             (void)hipStreamDestroy(b->stream[s]);
-    if (b->copy_stream) {
-        (void)hipStreamSynchronize(b->copy_stream);
-        (void)hipStreamDestroy(b->copy_stream);
+    if (b->in.copy_stream) {
+        (void)hipStreamSynchronize(b->in.copy_stream);
+        (void)hipStreamDestroy(b->in.copy_stream);
     }
-    for (auto &st : b->stage) {
+    for (auto &st : b->in.stage) {
         if (st.h_f32)
             (void)hipHostFree(st.h_f32);
         if (st.h_raw)
@@ -715,7 +716,7 @@ int sdr_set_first_frame(sdr_bank *b, int64_t frame)
     for (int band = 0; band < b->cfg.n_bands; band++) {
         if (b->n_slots[band] != 0)
             return fail(SDR_ERR_STATE, "a listener is attached already (set the first frame before the first attach)");
-        if (b->staged[band].staged != 0 || b->staged[band].history != 0 || b->staged_kind[band] != 0)
+        if (b->in.staged[band].staged != 0 || b->in.staged[band].history != 0 || b->in.staged_kind[band] != sdr::StagedKind::None)
             return fail(SDR_ERR_STATE, "input is staged already (set the first frame before the first push)");
     }
     b->total_frames = frame;

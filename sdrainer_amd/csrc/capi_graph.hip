@@ -413,15 +413,17 @@ int sdr_graph_capture(sdr_bank *b, int n_frames) { return graph_capture(b, n_fra
 int sdr_graph_capture_sc16(sdr_bank *b, int n_frames) { return graph_capture(b, n_frames, sdr::InFormat::SC16); }
 int sdr_graph_capture_iq8(sdr_bank *b, int n_frames, int format)
 {
-    if (format != SDR_IQ8_CS8 && format != SDR_IQ8_CU8)
-        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
-    return graph_capture(b, n_frames, format == SDR_IQ8_CU8 ? sdr::InFormat::CU8 : sdr::InFormat::CS8);
+    sdr::InFormat fmt;
+    if (const int rc = iq8_format(format, &fmt))
+        return rc;
+    return graph_capture(b, n_frames, fmt);
 }
 int sdr_graph_launch_iq8(sdr_bank *b, const void *const *iq_dev, int format)
 {
-    if (format != SDR_IQ8_CS8 && format != SDR_IQ8_CU8)
-        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
-    return graph_launch(b, iq_dev, format == SDR_IQ8_CU8 ? sdr::InFormat::CU8 : sdr::InFormat::CS8);
+    sdr::InFormat fmt;
+    if (const int rc = iq8_format(format, &fmt))
+        return rc;
+    return graph_launch(b, iq_dev, fmt);
 }
 
 int sdr_graph_launch(sdr_bank *b, const float *const *iq_dev)

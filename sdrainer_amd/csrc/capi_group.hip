@@ -100,6 +100,48 @@ int member_failed(sdr_group *g, int rc, int member)
     return rc;
 }
 
+// One band's push: the band's member and local band, the caller's device kept, then the member's call.
+template <class Push>
+int push_to_member(sdr_group *g, int band, Push &&push)
+{
+    sdr_bank *b = nullptr;
+    int local = 0;
+    const int rc = route(g, band, &b, &local);
+    if (rc)
+        return rc;
+    KeepDevice keep;
+    return push(b, local);
+}
+
+// iq_dev: one pointer per member, frames of one kind; process: the member call that takes them
+template <class Process>
+int group_process_device(sdr_group *g, const void *const *iq_dev, int n_frames, Process &&process)
+{
+    if (!g || !iq_dev)
+        return fail(SDR_ERR_BAD_ARG, "null argument");
+    for (int m = 0; m < g->rt.n_members; m++) {
+        if (!iq_dev[m])
+            return fail(SDR_ERR_BAD_ARG, "null iq_dev of a member");
+        if (reinterpret_cast<uintptr_t>(iq_dev[m]) & 15)
+            return fail(SDR_ERR_BAD_ARG, "iq_dev must be 16-byte aligned (frames are copied to LDS 16 bytes per lane)");
+    }
+    if (n_frames > g->cfg.max_batch_frames)
+        return fail(SDR_ERR_BAD_ARG, "n_frames exceeds max_batch_frames");
+    KeepDevice keep;
+    int rc = check_members(g);
+    if (rc)
+        return rc;
+    if (n_frames <= 0)
+        return SDR_OK;
+    // (sdr_process_device only enqueues: every member is launched before anything is waited for)
+    for (int m = 0; m < g->rt.n_members; m++) {
+        rc = process(g->banks[(size_t)m], iq_dev[m], n_frames);
+        if (rc)
+            return member_failed(g, rc, m);
+    }
+    return SDR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -163,46 +205,22 @@ int sdr_group_member(sdr_group *g, int band, sdr_bank **bank, int *local_band)
 
 int sdr_group_push_iq(sdr_group *g, int band, int sample_rate, const float *iq, size_t n_floats)
 {
-    sdr_bank *b = nullptr;
-    int local = 0;
-    int rc = route(g, band, &b, &local);
-    if (rc)
-        return rc;
-    KeepDevice keep;
-    return sdr_push_iq(b, local, sample_rate, iq, n_floats);
+    return push_to_member(g, band, [&](sdr_bank *b, int local) { return sdr_push_iq(b, local, sample_rate, iq, n_floats); });
 }
 
 int sdr_group_push_iq_sc16(sdr_group *g, int band, int sample_rate, const int16_t *iq, size_t n_values)
 {
-    sdr_bank *b = nullptr;
-    int local = 0;
-    int rc = route(g, band, &b, &local);
-    if (rc)
-        return rc;
-    KeepDevice keep;
-    return sdr_push_iq_sc16(b, local, sample_rate, iq, n_values);
+    return push_to_member(g, band, [&](sdr_bank *b, int local) { return sdr_push_iq_sc16(b, local, sample_rate, iq, n_values); });
 }
 
 int sdr_group_push_iq8(sdr_group *g, int band, int sample_rate, const void *iq, size_t n_values, int format)
 {
-    sdr_bank *b = nullptr;
-    int local = 0;
-    int rc = route(g, band, &b, &local);
-    if (rc)
-        return rc;
-    KeepDevice keep;
-    return sdr_push_iq8(b, local, sample_rate, iq, n_values, format);
+    return push_to_member(g, band, [&](sdr_bank *b, int local) { return sdr_push_iq8(b, local, sample_rate, iq, n_values, format); });
 }
 
 int sdr_group_push_kiwi_snd(sdr_group *g, int band, int sample_rate, const uint8_t *payload, size_t n_bytes)
 {
-    sdr_bank *b = nullptr;
-    int local = 0;
-    int rc = route(g, band, &b, &local);
-    if (rc)
-        return rc;
-    KeepDevice keep;
-    return sdr_push_kiwi_snd(b, local, sample_rate, payload, n_bytes);
+    return push_to_member(g, band, [&](sdr_bank *b, int local) { return sdr_push_kiwi_snd(b, local, sample_rate, payload, n_bytes); });
 }
 
 int sdr_group_process_staged(sdr_group *g, int *n_frames_out)
@@ -241,54 +259,23 @@ int sdr_group_process_staged_limit(sdr_group *g, int max_frames, int *n_frames_o
     return SDR_OK;
 }
 
-namespace {
-// iq_dev: one pointer per member, frames of one kind: 0 float32, 1 sc16, 2 + format 8-bit (SDR_IQ8_CS8 / SDR_IQ8_CU8)
-static int group_process_device(sdr_group *g, const void *const *iq_dev, int n_frames, int kind)
-{
-    if (!g || !iq_dev)
-        return fail(SDR_ERR_BAD_ARG, "null argument");
-    for (int m = 0; m < g->rt.n_members; m++) {
-        if (!iq_dev[m])
-            return fail(SDR_ERR_BAD_ARG, "null iq_dev of a member");
-        if (reinterpret_cast<uintptr_t>(iq_dev[m]) & 15)
-            return fail(SDR_ERR_BAD_ARG, "iq_dev must be 16-byte aligned (frames are copied to LDS 16 bytes per lane)");
-    }
-    if (n_frames > g->cfg.max_batch_frames)
-        return fail(SDR_ERR_BAD_ARG, "n_frames exceeds max_batch_frames");
-    KeepDevice keep;
-    int rc = check_members(g);
-    if (rc)
-        return rc;
-    if (n_frames <= 0)
-        return SDR_OK;
-    // (sdr_process_device only enqueues: every member is launched before anything is waited for)
-    for (int m = 0; m < g->rt.n_members; m++) {
-        sdr_bank *b = g->banks[(size_t)m];
-        rc = kind >= 2   ? sdr_process_device_iq8(b, iq_dev[m], n_frames, kind - 2)
-             : kind == 1 ? sdr_process_device_sc16(b, static_cast<const int16_t *>(iq_dev[m]), n_frames)
-                         : sdr_process_device(b, static_cast<const float *>(iq_dev[m]), n_frames);
-        if (rc)
-            return member_failed(g, rc, m);
-    }
-    return SDR_OK;
-}
-}  // namespace
-
 int sdr_group_process_device(sdr_group *g, const float *const *iq_dev, int n_frames)
 {
-    return group_process_device(g, reinterpret_cast<const void *const *>(iq_dev), n_frames, 0);
+    return group_process_device(g, reinterpret_cast<const void *const *>(iq_dev), n_frames,
+                                [](sdr_bank *b, const void *iq, int n) { return sdr_process_device(b, static_cast<const float *>(iq), n); });
 }
 
 int sdr_group_process_device_sc16(sdr_group *g, const int16_t *const *iq_dev, int n_frames)
 {
-    return group_process_device(g, reinterpret_cast<const void *const *>(iq_dev), n_frames, 1);
+    return group_process_device(g, reinterpret_cast<const void *const *>(iq_dev), n_frames,
+                                [](sdr_bank *b, const void *iq, int n) { return sdr_process_device_sc16(b, static_cast<const int16_t *>(iq), n); });
 }
 
 int sdr_group_process_device_iq8(sdr_group *g, const void *const *iq_dev, int n_frames, int format)
 {
     if (format != SDR_IQ8_CS8 && format != SDR_IQ8_CU8)
         return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
-    return group_process_device(g, iq_dev, n_frames, 2 + format);
+    return group_process_device(g, iq_dev, n_frames, [format](sdr_bank *b, const void *iq, int n) { return sdr_process_device_iq8(b, iq, n, format); });
 }
 
 int sdr_group_sync(sdr_group *g)

@@ -26,8 +26,8 @@
 //
 // The same body is driven three more ways: recorded into graphs (capi_graph.hip: capture_k / capture_stage), as the
 // deferred listen half (sdr_defer_listen ...: the spectral stages of a batch first, listeners bound to frames inside it,
-// then the listen stages) and from the staged host input (sdr_push_* / sdr_process_staged: three pinned staging sets,
-// uploads on a copy stream).
+// then the listen stages) and by the staged host input (capi_staged.hip, through process_device_impl).  The file ends
+// with the entry points for input that is on the device already and the deferred-listen calls.
 #include <string>
 
 #include "bank.h"
@@ -526,244 +526,6 @@ extern "C" {
 #pragma GCC visibility push(default)
 
 namespace {
-// the staging set the caller is filling, with its buffers in place (allocated on first use)
-// Copy into pinned staging memory.  One core moves about 12 GB/s into write-combined-free pinned pages; a large push
-// (a whole batch at once) is split over a few threads so that the copy keeps up with the PCIe upload behind it.
-static void staging_copy(void *dst, const void *src, size_t bytes)
-{
-    constexpr size_t kChunk = 8u << 20;
-    const size_t parts = std::min<size_t>(bytes / kChunk, 6);
-    if (parts < 2) {
-        memcpy(dst, src, bytes);
-        return;
-    }
-    std::vector<std::thread> th;
-    const size_t step = ((bytes / parts) + 4095) & ~(size_t)4095;
-    for (size_t i = 1; i < parts; i++) {
-        const size_t off = i * step, len = (i + 1 == parts) ? bytes - off : step;
-        th.emplace_back([=] { memcpy(static_cast<char *>(dst) + off, static_cast<const char *>(src) + off, len); });
-    }
-    memcpy(dst, src, step);
-    for (auto &t : th)
-        t.join();
-}
-
-static int staging_ready(sdr_bank *b, bool raw)
-{
-    const sdr_config &c = b->cfg;
-    sdr_bank::Staging &st = b->stage[b->stage_cur];
-    const size_t samples = b->stage_cap() * (size_t)c.n_bands;
-    HIP_TRY(hipSetDevice(b->device));
-    if (!b->copy_stream)
-        HIP_TRY(hipStreamCreateWithFlags(&b->copy_stream, hipStreamNonBlocking));
-    if (!st.uploaded) {
-        HIP_TRY(hipEventCreateWithFlags(&st.uploaded, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&st.consumed, hipEventDisableTiming));
-    }
-    if (!raw && !st.h_f32)
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&st.h_f32), sizeof(float) * 2 * samples, hipHostMallocDefault));
-    if (raw && !st.h_raw)
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&st.h_raw), sizeof(int16_t) * 2 * samples, hipHostMallocDefault));
-    return SDR_OK;
-}
-
-// One push of `n_values` values (two per sample, `value_bytes` bytes each) of kind `kind` (sdr_bank::staged_kind) behind
-// what the band has staged.  A band's row of the pinned buffer is 8 bytes per sample (float32) or 4 (raw: int16 values
-// fill it, 8-bit values half of it).  The stream arrives in whole hops: at hop = block_size that is the reference's whole frames
-// (rx/receiver.go:323-326), below it a piece is any whole number of hops (host/overlap.h StreamStage).
-static int push_samples(sdr_bank *b, int band, int sample_rate, const void *iq, size_t n_values, int kind, size_t value_bytes,
-                        const char *mixed)
-{
-    int rc = check_band(b, band);
-    if (rc)
-        return rc;
-    if (!iq)
-        return fail(SDR_ERR_BAD_ARG, "null iq");
-    const sdr_config &c = b->cfg;
-    if (sample_rate != c.sample_rate)  // rx/receiver.go:319-322
-        return fail(SDR_ERR_BAD_RATE, "wrong incoming sample rate");
-    const size_t per = 2 * (size_t)b->hop;
-    if (n_values == 0 || n_values % per != 0)  // rx/receiver.go:323-326
-        return fail(SDR_ERR_BAD_SIZE, b->hop == c.block_size ? "wrong incoming block size" : "a push must hold a whole number of hops");
-    const size_t ns = n_values / 2;
-    sdr::StreamStage &ss = b->staged[band];
-    if (ss.would_drop(ns, c.max_batch_frames))  // rx/receiver.go:328-333
-        return fail(SDR_ERR_WOULD_DROP, "IQ data skipped: staging queue full");
-    if (ss.staged > 0 && b->staged_kind[band] != kind)
-        return fail(SDR_ERR_STATE, mixed);
-    rc = staging_ready(b, kind != 1);
-    if (rc)
-        return rc;
-    b->staged_kind[band] = kind;
-    sdr_bank::Staging &st = b->stage[b->stage_cur];
-    unsigned char *row = kind == 1 ? reinterpret_cast<unsigned char *>(st.h_f32) : st.h_raw;
-    const size_t row_sample_bytes = kind == 1 ? 2 * sizeof(float) : 4;
-    staging_copy(row + (size_t)band * b->stage_cap() * row_sample_bytes + ss.staged * 2 * value_bytes, iq,
-                 n_values * value_bytes);  // copy on push: the caller may reuse its buffer (kiwi/client.go:203)
-    ss.push(ns);
-    return SDR_OK;
-}
-}  // namespace
-
-int sdr_push_iq(sdr_bank *b, int band, int sample_rate, const float *iq, size_t n_floats)
-{
-    return push_samples(b, band, sample_rate, iq, n_floats, 1, sizeof(float), "band already holds int16 (KiwiSDR or sc16) or 8-bit frames in this batch");
-}
-
-int sdr_push_kiwi_snd(sdr_bank *b, int band, int sample_rate, const uint8_t *payload, size_t n_bytes)
-{
-    int rc = check_band(b, band);
-    if (rc)
-        return rc;
-    if (b->hop != b->cfg.block_size)
-        return fail(SDR_ERR_STATE, "sdr_push_kiwi_snd is not offered on a bank with hop < block_size (overlapped frames)");
-    if (!payload)
-        return fail(SDR_ERR_BAD_ARG, "null payload");
-    if (sample_rate != b->cfg.sample_rate)
-        return fail(SDR_ERR_BAD_RATE, "wrong incoming sample rate");
-    constexpr size_t kHeader = 17;  // flags, sequence, S-meter, GPS (kiwi/client.go:285-290)
-    const size_t per = 2 * (size_t)b->cfg.block_size * 2;  // bytes per frame: 2N int16
-    if (n_bytes <= kHeader || (n_bytes - kHeader) % per != 0)  // kiwi/kiwi.go:96-98 panics on a partial block
-        return fail(SDR_ERR_BAD_SIZE, "SND payload does not hold whole frames");
-    return push_samples(b, band, sample_rate, payload + kHeader, (n_bytes - kHeader) / 2, 2, sizeof(int16_t),
-                        "band already holds float32, sc16 or 8-bit frames in this batch");
-}
-
-// sc16 frames from the host: staged raw like a KiwiSDR payload (half the bytes of float32 go over PCIe) and converted on
-// the device by k_unpack_sc16 into the float32 staging buffer the FFT reads
-int sdr_push_iq_sc16(sdr_bank *b, int band, int sample_rate, const int16_t *iq, size_t n_values)
-{
-    return push_samples(b, band, sample_rate, iq, n_values, 3, sizeof(int16_t), "band already holds float32, KiwiSDR or 8-bit frames in this batch");
-}
-
-// cs8 / cu8 frames from the host: staged raw (a quarter of the bytes of float32 go over PCIe) and converted on the device by
-// k_unpack_iq8 into the float32 staging buffer the FFT reads
-int sdr_push_iq8(sdr_bank *b, int band, int sample_rate, const void *iq, size_t n_values, int format)
-{
-    if (format != SDR_IQ8_CS8 && format != SDR_IQ8_CU8)
-        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
-    return push_samples(b, band, sample_rate, iq, n_values, format == SDR_IQ8_CU8 ? 5 : 4, 1,
-                        format == SDR_IQ8_CU8 ? "band already holds float32, int16 or cs8 frames in this batch"
-                                              : "band already holds float32, int16 or cu8 frames in this batch");
-}
-
-int sdr_staged_frames(sdr_bank *b, int band)
-{
-    if (check_band(b, band))
-        return -1;
-    return b->staged[band].frames();
-}
-
-int sdr_process_staged(sdr_bank *b, int *n_frames_out)
-{
-    return sdr_process_staged_limit(b, b ? b->cfg.max_batch_frames : 0, n_frames_out);
-}
-
-int sdr_process_staged_limit(sdr_bank *b, int max_frames, int *n_frames_out)
-{
-    if (!b)
-        return fail(SDR_ERR_BAD_ARG, "null bank");
-    const sdr_config &c = b->cfg;
-    int n = std::min(c.max_batch_frames, std::max(max_frames, 0));
-    for (const sdr::StreamStage &ss : b->staged)
-        n = std::min(n, ss.frames());
-    if (n_frames_out)
-        *n_frames_out = n;
-    if (n == 0)
-        return SDR_OK;
-    HIP_TRY(hipSetDevice(b->device));
-    const size_t cap = b->stage_cap();  // samples per band row, pinned and device alike
-    const size_t overlap = (size_t)(c.block_size - b->hop);
-    sdr_bank::Staging &st = b->stage[b->stage_cur];
-    if (!st.d_f32.p) {
-        hipError_t e = st.d_f32.alloc(2 * cap * (size_t)c.n_bands);
-        if (e != hipSuccess)
-            return fail(SDR_ERR_HIP, "hipMalloc iq staging failed");
-    }
-    // upload on the copy stream, once the FFT of this set's previous batch has read the device buffer.  Only what was
-    // pushed goes up: the first `history` samples of a band's device row are already there (the batch before left them)
-    HIP_TRY(hipStreamWaitEvent(b->copy_stream, st.consumed, 0));
-    for (int band = 0; band < c.n_bands; band++) {
-        const sdr::StreamStage &ss = b->staged[band];
-        const size_t up = sdr::span_samples(n, b->hop, c.block_size) - ss.history;  // samples
-        float *dst = st.d_f32.p + ((size_t)band * cap + ss.history) * 2;
-        if (b->staged_kind[band] >= 2) {
-            // raw int16 (KiwiSDR big-endian, or sc16) or bytes (cs8 / cu8): upload half or a quarter of the bytes, unpack in
-            // HBM (k_unpack.hip)
-            if (!st.d_raw.p) {
-                hipError_t e = st.d_raw.alloc(4 * cap * (size_t)c.n_bands);
-                if (e != hipSuccess)
-                    return fail(SDR_ERR_HIP, "hipMalloc raw staging failed");
-            }
-            uint8_t *rdst = st.d_raw.p + (size_t)band * cap * 4;
-            const int kind = b->staged_kind[band];
-            HIP_TRY(hipMemcpyAsync(rdst, st.h_raw + (size_t)band * cap * 4, (kind >= 4 ? 2 : 4) * up, hipMemcpyHostToDevice, b->copy_stream));
-            if (kind == 2)
-                HIP_TRY(sdr::launch_unpack_be16(rdst, dst, 2 * up, b->copy_stream));
-            else if (kind == 3)
-                HIP_TRY(sdr::launch_unpack_sc16(reinterpret_cast<const int16_t *>(rdst), dst, 2 * up, b->copy_stream));
-            else
-                HIP_TRY(sdr::launch_unpack_iq8(rdst, dst, 2 * up, kind == 5, b->copy_stream));
-        } else {
-            HIP_TRY(hipMemcpyAsync(dst, st.h_f32 + (size_t)band * cap * 2, sizeof(float) * 2 * up, hipMemcpyHostToDevice, b->copy_stream));
-        }
-    }
-    HIP_TRY(hipEventRecord(st.uploaded, b->copy_stream));
-    HIP_TRY(hipStreamWaitEvent(b->stream[S_FFT], st.uploaded, 0));
-    int rc = process_device_impl(b, st.d_f32.p, n, cap);
-    if (rc)
-        return rc;
-    const int next = (b->stage_cur + 1) % sdr_bank::STAGE_RING;
-    const int prev = b->stage_cur;
-    if (overlap > 0) {
-        // The next batch's history: the last block_size - hop samples of the frames just consumed, from sample n * hop of
-        // every band's row to the front of the next set's - on the FFT stream, behind this batch's FFT (which reads this
-        // set) and behind the next set's last FFT (which read the rows written here; its later uploads write behind the
-        // history only).
-        sdr_bank::Staging &nx = b->stage[next];
-        if (!nx.d_f32.p) {
-            hipError_t e = nx.d_f32.alloc(2 * cap * (size_t)c.n_bands);
-            if (e != hipSuccess)
-                return fail(SDR_ERR_HIP, "hipMalloc iq staging failed");
-        }
-        HIP_TRY(hipMemcpy2DAsync(nx.d_f32.p, cap * 2 * sizeof(float), st.d_f32.p + (size_t)n * (size_t)b->hop * 2, cap * 2 * sizeof(float),
-                                 overlap * 2 * sizeof(float), (size_t)c.n_bands, hipMemcpyDeviceToDevice, b->stream[S_FFT]));
-    }
-    HIP_TRY(hipEventRecord(st.consumed, b->stream[S_FFT]));  // (behind the FFT launch and the history copy: the only readers of d_f32)
-    // the caller goes on filling the next set; what this batch did not take moves to its front
-    b->stage_cur = next;
-    std::vector<sdr::StreamStage::Consumed> took((size_t)c.n_bands);
-    bool raw = false, f32 = false;
-    for (int band = 0; band < c.n_bands; band++) {
-        took[(size_t)band] = b->staged[band].consume(n);
-        if (took[(size_t)band].left > 0)
-            (b->staged_kind[band] >= 2 ? raw : f32) = true;
-    }
-    if (f32 && (rc = staging_ready(b, false)))
-        return rc;
-    if (raw && (rc = staging_ready(b, true)))
-        return rc;
-    // the pinned buffers of the next set are free once ITS last upload has completed (two batches ago: a formality)
-    if (b->stage[next].uploaded)
-        HIP_TRY(hipEventSynchronize(b->stage[next].uploaded));
-    for (int band = 0; band < c.n_bands; band++) {
-        const sdr::StreamStage::Consumed &t = took[(size_t)band];
-        if (t.left > 0) {
-            if (b->staged_kind[band] >= 2) {
-                const size_t sb = b->staged_kind[band] >= 4 ? 2 : 4;  // bytes per raw sample
-                memcpy(b->stage[next].h_raw + (size_t)band * cap * 4, b->stage[prev].h_raw + (size_t)band * cap * 4 + t.left_from * sb, sb * t.left);
-            }
-            else
-                memcpy(b->stage[next].h_f32 + (size_t)band * cap * 2, b->stage[prev].h_f32 + ((size_t)band * cap + t.left_from) * 2,
-                       sizeof(float) * 2 * t.left);
-        } else {
-            b->staged_kind[band] = 0;
-        }
-    }
-    return SDR_OK;
-}
-
-namespace {
 static int check_device_input(sdr_bank *b, const void *iq_dev)
 {
     if (!b || !iq_dev)
@@ -812,28 +574,19 @@ int sdr_process_device_stream_sc16(sdr_bank *b, const int16_t *iq_dev, int n_fra
     return process_device_stream(b, iq_dev, n_frames, band_stride_samples, sdr::InFormat::SC16);
 }
 
-// 8-bit input: format -> the FFT's InFormat (false: neither SDR_IQ8_CS8 nor SDR_IQ8_CU8)
-static bool iq8_format(int format, sdr::InFormat *fmt)
-{
-    if (format != SDR_IQ8_CS8 && format != SDR_IQ8_CU8)
-        return false;
-    *fmt = format == SDR_IQ8_CU8 ? sdr::InFormat::CU8 : sdr::InFormat::CS8;
-    return true;
-}
-
 int sdr_process_device_iq8(sdr_bank *b, const void *iq_dev, int n_frames, int format)
 {
     sdr::InFormat fmt;
-    if (!iq8_format(format, &fmt))
-        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
+    if (const int rc = iq8_format(format, &fmt))
+        return rc;
     return process_device_dense(b, iq_dev, n_frames, fmt);
 }
 
 int sdr_process_device_stream_iq8(sdr_bank *b, const void *iq_dev, int n_frames, size_t band_stride_samples, int format)
 {
     sdr::InFormat fmt;
-    if (!iq8_format(format, &fmt))
-        return fail(SDR_ERR_BAD_ARG, "format must be SDR_IQ8_CS8 or SDR_IQ8_CU8");
+    if (const int rc = iq8_format(format, &fmt))
+        return rc;
     return process_device_stream(b, iq_dev, n_frames, band_stride_samples, fmt);
 }
 

@@ -3,7 +3,7 @@ the float32 values those bytes stand for produces: every psd and spectrum row, e
 (peaks, edges, runes, with listeners attached), over the kernels the formats reach - k_fft_psd_iq8<9..14> plain and
 windowed, k_fft_r32_iq8 and its strided form, k_fft2p_a's 8-bit instances, k_unpack_iq8 - and over streams with a hop,
 graph replay, staged host input, a group, waterfall rows and listener reports.  Band 0's psd rows also equal the CPU
-oracle's.  Every test runs for both formats.
+oracle's.  Every test runs for both formats (test_staged_kinds_side_by_side holds both, and the other staged kinds, in one bank).
 
 The input is tests/iq8_tools.py's (tests/test_iq8_inputs.py shows that the oracle hears it).  As in
 tests/test_sc16_input_gpu.py, frame f of a dense batch is frame f % P of a pool of P frames (a fresh pool per batch), so
@@ -22,7 +22,7 @@ torch = pytest.importorskip("torch")
 import iq8_tools as t8  # noqa: E402
 from iq8_tools import RATE, Pair, batch, check_oracle, pool, to_f32  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
-from parity_tools import capi, frames_of, random_window, windowed  # noqa: E402, F401 (capi: the fixture)
+from parity_tools import capi, frames_of, random_window, sc16_to_float32, windowed  # noqa: E402, F401 (capi: the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 both = pytest.mark.parametrize("fmt", t8.FORMATS, ids=t8.FORMAT_IDS)
@@ -238,6 +238,69 @@ def test_staged_push(capi, fmt, overlapped):
     want = orc.iq_to_spectrum_and_psd(frames_of(s, n, hop)[-1])[1].view(np.uint32)
     assert np.array_equal(p.b.read_spectrum(0, left - 1)[1].view(np.uint32), want)
     p.close()
+
+
+@pytest.mark.parametrize("overlapped", [False, True], ids=["dense", "hop"])
+def test_staged_kinds_side_by_side(capi, overlapped):
+    """Every kind of staged frames in one batch, a band each: float32, KiwiSDR payloads (dense frames only: sdr_push_kiwi_snd
+    is refused with a hop), sc16, cs8, cu8, at N = 512 and max_batch_frames = 8 - the smallest shapes at which a wrong row
+    offset of one kind lands in another kind's bytes.  Bank B gets each band in its own kind, bank A sdr_push_iq of the
+    converted values; uneven pieces, every batch cut by sdr_process_staged_limit so that frames stay staged, seven batches
+    (each of the three staging sets is reused).  After each batch every psd row of every band is the same float32 bits."""
+    c = capi
+    n, frames = 512, 8
+    hop = n // 4 if overlapped else n
+    kinds = ["f32", "sc16", "cs8", "cu8"] if overlapped else ["f32", "kiwi", "sc16", "cs8", "cu8"]
+    pieces = (8 if overlapped else 5, 4, 6, 3, 5, 2)  # (in hops; two frames stay staged behind every batch)
+    samples = sum(pieces) * hop
+    rng = np.random.default_rng(660 + overlapped)
+    mk = lambda: c.Bank(RATE[n], n, n_bands=len(kinds), max_batch_frames=frames, hop=hop if overlapped else 0)
+    a, b = mk(), mk()
+    raw = {"f32": rng.standard_normal((samples, 2)).astype(np.float32),
+           "kiwi": rng.integers(-32768, 32768, size=(samples, 2)).astype(np.int16),
+           "sc16": rng.integers(-32768, 32768, size=(samples, 2)).astype(np.int16),
+           "cs8": rng.integers(-128, 128, size=(samples, 2)).astype(np.int8),
+           "cu8": rng.integers(0, 256, size=(samples, 2)).astype(np.uint8)}
+
+    def push(band, kind, x):
+        """x [samples, 2] of the band's kind into bank B as it is, into bank A as the float32 values it stands for."""
+        if kind == "f32":
+            rc, ref = b.push_iq(band, RATE[n], x), x
+        elif kind == "kiwi":
+            payload = bytes([0x01] + [7] * 16) + x.astype(">i2").tobytes()
+            rc, ref = b.push_kiwi_snd(band, RATE[n], payload), orc.decode_iq_message(payload)
+        elif kind == "sc16":
+            rc, ref = b.push_iq_sc16(band, RATE[n], x), sc16_to_float32(x)
+        else:
+            fmt = t8.CS8 if kind == "cs8" else t8.CU8
+            rc, ref = b.push_iq8(band, RATE[n], x, fmt), to_f32(x, fmt)
+        assert rc == c.OK and a.push_iq(band, RATE[n], ref) == c.OK, f"{kind}: push refused"
+
+    def same_rows(count):
+        a.sync()
+        b.sync()
+        for band, kind in enumerate(kinds):
+            for f in range(count):
+                pa, pb = a.read_spectrum(band, f)[1], b.read_spectrum(band, f)[1]
+                assert np.array_equal(pa.view(np.uint32), pb.view(np.uint32)), f"band {band} ({kind}) frame {f} of the batch: psd differs"
+            assert np.all(np.isfinite(pb)) and np.any(pb > 0)
+
+    at = batches = 0
+    for piece in pieces:
+        for band, kind in enumerate(kinds):
+            push(band, kind, raw[kind][at * hop:(at + piece) * hop])
+        at += piece
+        staged = [bk.staged_frames(band) for bk in (a, b) for band in range(len(kinds))]
+        assert min(staged) == max(staged) >= 3
+        want = staged[0] - 2
+        assert a.process_staged_limit(want) == b.process_staged_limit(want) == want
+        same_rows(want)
+        batches += 1
+    assert a.process_staged() == b.process_staged() == 2
+    same_rows(2)
+    assert batches + 1 >= 5 and a.staged_frames(0) == b.staged_frames(0) == 0
+    a.close()
+    b.close()
 
 
 @both

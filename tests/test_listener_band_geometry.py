@@ -32,7 +32,7 @@ pytestmark = pytest.mark.gpu
 def test_fft_r32_slot_limit(capi, slots):
     """N = 16384, 256 keyed carriers and `slots` listeners, two 1024-frame batches (n_frames * n_bands >= 1024, so the
     frame count alone would pick k_fft_r32).  fft_choice (host/batch_plan.h, `tap_n <= kR32MaxTap`) selects k_fft_r32 at
-    512 slots - register tap, wide tap and tap_used written, and k_cum_refine reading them (capi_process.hip:439,
+    512 slots - register tap, wide tap and tap_used written, and k_cum_refine reading them (capi_process.hip issue_cumulation,
     FftChoice::wide_tap) - and the one-frame k_fft_psd<14> with its LDS tap at 513, where k_cum_refine reads the psd.
     max_listeners is 600 in both, so tap_stride > 512 and the tap_used entries past 512 exist.  513 slots also need a
     ninth gather row (k_listen.hip:709, grid.y = (n_slots + 63) / 64)."""
@@ -130,12 +130,12 @@ def test_fft_r32_claim_counters_beyond_8_bands(capi):
 
 @pytest.mark.parametrize("n,n_bands,rate,early,late", [(8192, 1, RATE, 32, 320), (4096, 2, 192_000, 16, 200)])
 def test_small_plan_many_late_attaches(capi, n, n_bands, rate, early, late):
-    """B * N <= 8192 (capi_process.hip:168: the gather on the peaks stream): one deferred 1000-frame batch in which
-    sdr_attach_at binds `late` listeners per band at the nine cumulation boundaries inside it - dozens of k_put_slots
-    launches on the listen stream (capi_process.hip:149, flush_late_attached) - then two eager batches with every
+    """B * N <= 8192 (host/batch_plan.h plan_batch's gather stream: the gather on the peaks stream): one deferred 1000-frame
+    batch in which sdr_attach_at binds `late` listeners per band at the nine cumulation boundaries inside it - dozens of
+    k_put_slots launches on the listen stream (capi_process.hip flush_late_attached) - then two eager batches with every
     listener carried.  Each batch is polled only after the next one is enqueued, so the listen stream may still be
     behind when the next gather is issued on the peaks stream; every such gather waits for the last put until the host
-    has seen it done (capi_process.hip:358, slots_put_ev).  The oracle attaches each listener at its frame."""
+    has seen it done (slots_put_ev in capi_process.hip issue_listen).  The oracle attaches each listener at its frame."""
     boundaries = list(range(100, 1000, 100))
 
     def steps(carriers):

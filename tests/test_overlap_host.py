@@ -1,5 +1,6 @@
 """Overlapped frames (sdr_config.hop < block_size) without a GPU: the ABI (symbols, the header from plain C, where the hop
-lies in sdr_config), the arithmetic of the staged host input (sdrainer_amd/csrc/host/overlap.h) and the host mirror's
+lies in sdr_config), the arithmetic of the staged host input (sdrainer_amd/csrc/host/overlap.h: samples and frames;
+sdrainer_amd/csrc/host/staging.h: the kinds of staged frames and the bytes of their rows) and the host mirror's
 clock, which one frame advances by hop / sample_rate (sdrainer_amd/csrc/host/rx.h FrameTiming)."""
 import ctypes as C
 import os
@@ -64,6 +65,23 @@ def test_staging_arithmetic(tmp_path, sanitizer):
     run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0 and "FAILED" not in run.stdout, run.stdout + run.stderr
     assert run.stdout.split() == ["hops", "ok", "index", "ok", "staging", "ok"]
+
+
+@pytest.mark.parametrize("sanitizer", [None, "address,undefined"])
+def test_staging_rows(tmp_path, sanitizer):
+    """sdrainer_amd/csrc/host/staging.h: the kind table, and real bytes of all five kinds moved through the planned push,
+    upload, history and leftover ranges of three staging sets, at N = 512 (hops 512, 256, 32) and 16384 (hops 16384, 1024),
+    max_batch_frames 8 and 64: every batch's device rows hold the stream, every range lies inside its buffer."""
+    exe = str(tmp_path / "test_staging_rows")
+    flags = [f"-fsanitize={sanitizer}", "-fno-sanitize-recover=all"] if sanitizer else []
+    cc = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags +
+                        ["-o", exe, os.path.join(HOST, "test_staging_rows.cpp")], capture_output=True, text=True)
+    if sanitizer and cc.returncode != 0 and "sanitize" in cc.stderr and "error:" not in cc.stderr.replace("-Werror", ""):
+        pytest.skip("this compiler has no -fsanitize=" + sanitizer)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0 and "FAILED" not in run.stdout, run.stdout[-4000:] + run.stderr[-4000:]
+    assert run.stdout.split() == ["kinds", "ok", "rows", "ok"]
 
 
 @pytest.mark.parametrize("rate, n, silence", [(2_000_000, 65536, 20.0), (2_000_000, 16384, 1.0), (48_000, 512, 20.0), (192_000, 4096, 0.37)])
