@@ -1,14 +1,16 @@
 """The down-converter on the GPU (sdr_ddc_*, csrc/k_ddc.hip) against its NumPy restatement tests/ddc_ref.py, bit for bit:
 every input format over the decimations and tap counts at which the kernel's tile takes another shape, cuts of the stream
 into calls, sample indices across 2^31 and 2^32, a retune between calls, subnormal products, the host entry point, every
-refusal, and the chain - one cu8 wide stream through the DDC into a bank on the same HIP stream - against the oracle
-receiver fed with the reference's narrow streams."""
+refusal, and the chain - one cu8 wide stream through the DDC into a bank on the same HIP stream, cut into whole hops, cut
+raggedly, and cut raggedly with a padded band stride - against the oracle receiver fed with the reference's narrow streams.
+The seeded fuzz over every tile shape is tests/test_ddc_fuzz_gpu.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import ddc_ref as R
+from ddc_run import run_gpu
 from parity_tools import bits_equal, capi, check_batch_polled, run_oracle  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -24,39 +26,6 @@ def table(capi):
 
 def random_taps(t, seed):
     return np.random.default_rng(seed).uniform(-1, 1, t).astype(np.float32)
-
-
-def run_gpu(capi, fmt, d, taps, steps, pieces, first_sample=None, between=None, host=False):
-    """One DDC over the raw pieces, one call each, every call with device tensors of its own (a call's pointers are 16-byte
-    aligned whatever the pieces' lengths); between(ddc, i) runs in front of call i.  Returns float32 [bands, outputs, 2].
-    The words behind a band's outputs, up to the band stride, must be left alone."""
-    import torch
-
-    ddc = capi.Ddc(d, taps, steps, in_format=fmt, max_in_samples=max(len(p) for p in pieces))
-    ddc.set_stream(torch.cuda.current_stream().cuda_stream)
-    if first_sample is not None:
-        ddc.set_first_sample(first_sample)
-    start = ddc.total_samples
-    outs = []
-    for i, raw in enumerate(pieces):
-        if between:
-            between(ddc, i)
-        m = len(raw) // d
-        stride = (m + 3) // 4 * 4 + 4
-        out = torch.full((len(steps), stride, 2), float("nan"), dtype=torch.float32, device="cuda")
-        if host:
-            ddc.process_host(raw, out.data_ptr(), stride)
-        else:
-            dev = torch.from_numpy(np.ascontiguousarray(raw)).cuda()
-            ddc.process_device(dev.data_ptr(), len(raw), out.data_ptr(), stride)
-        outs.append((out, m))
-    ddc.sync()
-    assert ddc.total_samples == start + sum(len(p) for p in pieces)
-    ddc.close()
-    got = [o.cpu().numpy() for o, _ in outs]
-    for g, (_, m) in zip(got, outs):
-        assert np.isnan(g[:, m:]).all(), "the kernel wrote behind a band's outputs"
-    return np.concatenate([g[:, :m] for g, (_, m) in zip(got, outs)], axis=1)
 
 
 @pytest.mark.parametrize("fmt", R.FORMATS, ids=R.FORMAT_IDS)
@@ -224,9 +193,26 @@ def test_refusals_change_nothing(capi, table):
     ddc.close()
 
 
-def test_end_to_end_with_a_bank_on_one_stream(capi, table):
+def ragged_lengths(narrow, hop):
+    """DDC call lengths in outputs, drawn with a fixed seed, as a receiver's are: each even (the next call's output pointer
+    stays 16-byte aligned), none a multiple of the hop, a third of them shorter than a hop - after which the bank often has
+    no whole new frame."""
+    rng = np.random.default_rng(20_241)
+    lens, left = [], narrow
+    while left > 0:
+        m = 2 * int(rng.integers(1, hop // 2) if rng.random() < 0.35 else rng.integers(hop, 100 * hop))
+        m += 2 * (m % hop == 0)
+        lens.append(min(m, left))
+        left -= lens[-1]
+    assert all(m % 2 == 0 for m in lens) and all(m % hop for m in lens[:-1]) and sum(lens) == narrow
+    return lens
+
+
+def chain(capi, table, lens=None, gap=0):
     """cu8 wide stream -> DDC (D = 8, T = 64) -> bank (N = 512, hop 128, sdr_process_device_stream), both on one HIP stream,
-    call pairs back to back with no host synchronisation between a pair's two calls and one at the end."""
+    call pairs back to back with no host synchronisation between a pair's two calls and one at the end.  lens: the DDC
+    calls' outputs (by default 512 frames' worth each); the bank takes whatever whole frames exist behind each and is
+    skipped where there is none.  gap: words between one band's narrow stream and the next, which stay as they were."""
     import torch
 
     e = R.E2E
@@ -239,12 +225,17 @@ def test_end_to_end_with_a_bank_on_one_stream(capi, table):
     bins = [[b] for b in e["bins"]]
     _, outs, decs = run_oracle(rate, n, e["edge"], bins, list(ref), centers, hop)
 
+    per = 512  # frames' worth of samples per DDC call, at the most
+    if lens is None:
+        lens = [min(per * hop, narrow - a) for a in range(0, narrow, per * hop)]
+    assert sum(lens) == narrow and max(lens) <= per * hop
+    stride = narrow + gap
+    assert stride % 4 == 0
     stream = torch.cuda.Stream()
     with torch.cuda.stream(stream):
         wide = torch.from_numpy(raw).cuda()
-        out = torch.zeros((2, narrow, 2), dtype=torch.float32, device="cuda")
+        out = torch.full((2, stride, 2), float("nan"), dtype=torch.float32, device="cuda")
     stream.synchronize()
-    per = 512  # frames' worth of samples per DDC call
     bank = capi.Bank(rate, n, n_bands=2, edge_width=e["edge"], max_batch_frames=per, max_listeners=2, hop=hop)
     ddc = capi.Ddc(d, taps, e["steps"], in_format=capi.DDC_CU8, max_in_samples=per * hop * d)
     bank.set_stream(stream.cuda_stream)
@@ -253,20 +244,24 @@ def test_end_to_end_with_a_bank_on_one_stream(capi, table):
         bank.set_center_frequency(b, centers[b])
         assert bank.attach(b, e["bins"][b]) == 0
     bank.enable_results(True)
-    have = done = 0  # narrow samples produced, frames processed
+    have = done = skipped = 0  # narrow samples produced, frames processed, DDC calls behind which the bank had no new frame
     batches = []
-    while have < narrow:
-        m = min(per * hop, narrow - have)
-        ddc.process_device(wide.data_ptr() + have * d * 2, m * d, out.data_ptr() + have * 8, narrow)
+    for m in lens:
+        ddc.process_device(wide.data_ptr() + have * d * 2, m * d, out.data_ptr() + have * 8, stride)
         have += m
-        k = (have - n) // hop + 1 - done
-        bank.process_device_stream(out.data_ptr() + done * hop * 8, k, narrow)
+        k = (have - n) // hop + 1 - done if have >= n else 0
+        if k == 0:
+            skipped += 1
+            continue
+        bank.process_device_stream(out.data_ptr() + done * hop * 8, k, stride)
         batches.append((done, done + k))
         done += k
     ddc.sync()
     bank.sync()
-    assert done == frames and len(batches) >= 3 and bank.total_frames == frames
-    assert bits_equal(out.cpu().numpy(), ref)
+    assert have == narrow and done == frames and len(batches) >= 3 and bank.total_frames == frames
+    got = out.cpu().numpy()
+    assert bits_equal(got[:, :narrow], ref)
+    assert np.isnan(got[:, narrow:]).all(), "the words between the bands were written"
     text = [[""], [""]]
     n_peaks = 0
     for a, z in batches:
@@ -278,3 +273,21 @@ def test_end_to_end_with_a_bank_on_one_stream(capi, table):
         assert text[b][0] == decs[b][0][0] and call in text[b][0], text[b][0]
     ddc.close()
     bank.close()
+    return skipped
+
+
+def test_end_to_end_with_a_bank_on_one_stream(capi, table):
+    """Every DDC call makes a whole number of hops."""
+    assert chain(capi, table) == 0
+
+
+def test_end_to_end_with_ragged_calls(capi, table):
+    """The same stream cut as a receiver cuts it (ragged_lengths): the same samples, peaks, edges and text."""
+    lens = ragged_lengths(R.e2e_wide()[1], R.E2E["hop"])
+    assert len(lens) >= 8
+    assert chain(capi, table, lens) >= 2  # (calls behind which the bank was skipped)
+
+
+def test_end_to_end_with_ragged_calls_and_a_band_stride(capi, table):
+    """And with the band stride larger than the narrow length: the words between the bands stay untouched."""
+    assert chain(capi, table, ragged_lengths(R.e2e_wide()[1], R.E2E["hop"]), gap=64) >= 2
