@@ -584,7 +584,7 @@ int sdr_group_read_drop_counters(sdr_group *group, uint64_t *runes_dropped, uint
 
 /* down-converter ----------------------------------------------------------------------------- */
 /* A digital down-converter (DDC) in front of a bank: one WIDE stream - a HackRF's 8-20 MS/s, an RTL-SDR's 2.4 MS/s - goes in
- * once, in any of the four input formats, and n_bands narrow float32 streams come out in device memory, laid out as
+ * once, in any of the four complex input formats or as real samples (below), and n_bands narrow float32 streams come out in device memory, laid out as
  * sdr_process_device_stream reads them.  Each band is mixed to 0 Hz, low-pass filtered and decimated by one kernel.  An
  * sdr_ddc is an object of its own beside the bank; a process that never creates one runs exactly what it ran.  Like the
  * window and the hop it has no counterpart in the reference: its arithmetic is defined here to the bit (DESIGN.md section
@@ -630,11 +630,32 @@ int sdr_group_read_drop_counters(sdr_group *group, uint64_t *runes_dropped, uint
  *                        pointer may be null).  Built in float64 from one quarter wave and extended by exact symmetry:
  *                        SIN[i] == COS[(i - L/4) mod L], COS[i] == COS[L - i], COS[i] == -COS[L/2 - i]; exactly 0 and
  *                        +-1 at the multiples of L/4.
- * Not offered: per-band taps, resampling by a ratio, DDC launches inside a captured graph, DDCs in an sdr_group. */
+ *
+ * Real input (SDR_DDC_REAL), for direct-sampling receivers whose ADC delivers one value per sample: a real stream v[k] is
+ * the complex stream x[k] = (v[k], +0.0f) through the arithmetic above, bit for bit - the same NCO, the same two mix
+ * formulas with im = +0.0f, the same filter order, zeros below the first sample, the same carry of n_taps - 1 RAW samples;
+ * signs of zero, NaN and Inf follow from that.  The value of a raw word is what the complex format of the same sample
+ * type gives that word: float32 as it is (RF32), float32(x) / 32767 (RS16), x / 128 (RS8), (2 x - 255) / 256 (RU8).
+ * Calls, statuses and alignment are unchanged; n_in_samples counts samples, so a call of n samples reads 4 n, 2 n or n
+ * bytes, and sdr_ddc_process_host uploads exactly those.
+ *   tuning  for a real stream sampled at fs, a signal at f Hz, 0 < f < fs / 2, lands on 0 Hz with
+ *           step = round(f * L / fs), which lies in [0, 32767].  A carrier A cos(..) comes out as a complex carrier of
+ *           amplitude A / 2 (-6.02 dB); the bank's thresholds are relative to the noise floor and need no change.
+ *   mirror  a negative step selects the mirror image of the same signal: the band's spectrum comes out reversed.  That
+ *           is what an inverting Nyquist zone needs; otherwise use positive steps.
+ *   image   the other half of the real spectrum lies 2 f away after the mix: the caller's taps must reject it, as the
+ *           filter's shape is the caller's business throughout.
+ * Not offered: per-band taps, resampling by a ratio, DDC launches inside a captured graph, DDCs in an sdr_group, packed
+ * 12-bit samples. */
 #define SDR_DDC_F32 0
 #define SDR_DDC_SC16 1
 #define SDR_DDC_CS8 2
 #define SDR_DDC_CU8 3
+#define SDR_DDC_REAL 16 /* flag: one value per sample, no imaginary part */
+#define SDR_DDC_RF32 16 /* SDR_DDC_REAL | SDR_DDC_F32 : float32                          */
+#define SDR_DDC_RS16 17 /* SDR_DDC_REAL | SDR_DDC_SC16: int16, value float32(x) / 32767  */
+#define SDR_DDC_RS8 18  /* SDR_DDC_REAL | SDR_DDC_CS8 : int8,  value x / 128             */
+#define SDR_DDC_RU8 19  /* SDR_DDC_REAL | SDR_DDC_CU8 : uint8, value (2 x - 255) / 256   */
 #define SDR_DDC_NCO_SIZE 65536
 /* outputs of one band that one workgroup of the kernel computes (csrc/ddc.h): where the tests put their output counts */
 #define SDR_DDC_TILE_OUTPUTS 512
@@ -646,7 +667,7 @@ typedef struct sdr_ddc_config {
     int32_t n_bands;        /* 1 .. 64                                                */
     int32_t decimation;     /* D, 1 .. 256                                            */
     int32_t n_taps;         /* T, 1 .. 4096                                           */
-    int32_t in_format;      /* SDR_DDC_F32 / _SC16 / _CS8 / _CU8                      */
+    int32_t in_format;      /* SDR_DDC_F32 / _SC16 / _CS8 / _CU8, _RF32 .. _RU8 real  */
     int32_t max_in_samples; /* capacity: input samples per call, a multiple of D      */
     int32_t device_id;      /* HIP device ordinal                                     */
     int32_t reserved;       /* 0                                                      */

@@ -127,6 +127,9 @@ IQ8_CS8, IQ8_CU8 = 0, 1
 
 # the down-converter (sdr_ddc_*): input formats, the NCO table's size, the outputs of one band per workgroup
 DDC_F32, DDC_SC16, DDC_CS8, DDC_CU8 = range(4)
+# real input, one value per sample: the flag, and the flag with each sample type
+DDC_REAL = 16
+DDC_RF32, DDC_RS16, DDC_RS8, DDC_RU8 = (DDC_REAL | f for f in (DDC_F32, DDC_SC16, DDC_CS8, DDC_CU8))
 DDC_NCO_SIZE = 65536
 DDC_TILE_OUTPUTS = 512
 
@@ -1053,9 +1056,15 @@ class Ddc:
         _check(self._L.sdr_ddc_process_device(self._h, C.c_void_p(in_dev_ptr), n_in_samples, C.c_void_p(out_dev_ptr), band_stride_samples))
 
     def process_host(self, samples: np.ndarray, out_dev_ptr: int, band_stride_samples: int):
-        """samples: the wide stream's raw samples in host memory, [n, 2] of float32, int16, int8 or uint8 by in_format."""
-        dt = {DDC_F32: np.float32, DDC_SC16: np.int16, DDC_CS8: np.int8, DDC_CU8: np.uint8}[self.in_format]
-        s = np.ascontiguousarray(samples, dt).reshape(-1, 2)
+        """samples: the wide stream's raw samples in host memory, float32, int16, int8 or uint8 by in_format: [n, 2] for a
+        complex format, [n] for a real one."""
+        dt = {DDC_F32: np.float32, DDC_SC16: np.int16, DDC_CS8: np.int8, DDC_CU8: np.uint8}[self.in_format & ~DDC_REAL]
+        s = np.ascontiguousarray(samples, dt)
+        if self.in_format & DDC_REAL:
+            if s.ndim != 1:
+                raise ValueError("a real in_format takes a one-dimensional array, one value per sample")
+        else:
+            s = s.reshape(-1, 2)
         _check(self._L.sdr_ddc_process_host(self._h, C.c_void_p(s.ctypes.data), s.shape[0], C.c_void_p(out_dev_ptr), band_stride_samples))
 
     def sync(self):

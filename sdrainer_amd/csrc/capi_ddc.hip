@@ -1,5 +1,6 @@
 // capi_ddc.hip — the down-converter behind the C ABI (include/sdrainer_hip.h "down-converter"): an object of its own beside
-// the bank, with the taps, the NCO table and the carry of n_taps - 1 raw samples in device memory.  The kernel is k_ddc.hip.
+// the bank, with the taps, the NCO table and the carry of n_taps - 1 raw samples in device memory.  The kernel is k_ddc.h, instantiated by
+// k_ddc.hip (complex formats) and k_ddc_real.hip (real formats); a sample's size is host/ddc_format.h's.
 //
 // The carry is double-buffered: a call's kernel reads carry[cur] and a second small kernel behind it forms carry[1 - cur]
 // from carry[cur] and the call's input - also where the call is shorter than n_taps - 1 samples and part of the old carry
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "ddc.h"
+#include "host/ddc_format.h"
 
 namespace sdr {
 int set_error(int code, const char *msg);  // capi_bank.hip: feeds sdr_last_error()
@@ -27,7 +29,7 @@ int dfail(int code, const std::string &msg) { return sdr::set_error(code, msg.c_
             return dfail(SDR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
     } while (0)
 
-size_t sample_bytes(int fmt) { return fmt == SDR_DDC_F32 ? 8 : fmt == SDR_DDC_SC16 ? 4 : 2; }
+size_t sample_bytes(int fmt) { return (size_t)sdr::ddc_sample_bytes(fmt); }  // 8, 4, 2 complex; 4, 2, 1 real
 
 // COS over one period from the quarter wave q[0 .. L/4] = cos(2 pi i / L), evaluated in float64 and rounded once, with the
 // two ends set exactly; every other entry is a copy of one of these or its negation (both zeros are +0).
@@ -153,8 +155,8 @@ int sdr_ddc_create(const sdr_ddc_config *cfg, const float *taps, const int32_t *
         return dfail(SDR_ERR_BAD_ARG, "decimation must be 1 .. 256");
     if (cfg->n_taps < 1 || cfg->n_taps > sdr::kDdcMaxTaps)
         return dfail(SDR_ERR_BAD_ARG, "n_taps must be 1 .. 4096");
-    if (cfg->in_format < SDR_DDC_F32 || cfg->in_format > SDR_DDC_CU8)
-        return dfail(SDR_ERR_BAD_ARG, "in_format must be SDR_DDC_F32, _SC16, _CS8 or _CU8");
+    if (!sdr::ddc_format_valid(cfg->in_format))
+        return dfail(SDR_ERR_BAD_ARG, "in_format must be SDR_DDC_F32, _SC16, _CS8, _CU8 or SDR_DDC_RF32, _RS16, _RS8, _RU8");
     if (cfg->max_in_samples < cfg->decimation || cfg->max_in_samples % cfg->decimation != 0)
         return dfail(SDR_ERR_BAD_ARG, "max_in_samples must be a positive multiple of the decimation");
     if (cfg->reserved != 0)

@@ -156,6 +156,34 @@ def wide_stream(n_samples: int, sample_rate: float, carriers, noise_sigma: float
     raise ValueError("quantise must be None, 'cs8' or 'cu8'")
 
 
+def wide_stream_real(n_samples: int, sample_rate: float, carriers, noise_sigma: float = NOISE_SIGMA, seed: int = 0,
+                     quantise: str | None = None) -> np.ndarray:
+    """A wide REAL stream, [n_samples], as a direct-sampling receiver's ADC delivers it: real white noise plus
+    amplitude * cos(2 pi f k / sample_rate) per carrier.  carriers: tuples (frequency_hz, amplitude, key) with
+    0 < frequency_hz < sample_rate / 2, keyed like wide_stream's.  quantise: None (float32), "s16" (int16, x * 32767 rounded
+    and clipped to [-32768, 32767]), "s8" (int8, x * 128 rounded and clipped) or "u8" (uint8, x * 128 + 127.5 rounded and
+    clipped) - the inverses of the values the library gives those words (include/sdrainer_hip.h)."""
+    rng = np.random.default_rng(seed)
+    x = noise_sigma * rng.standard_normal(n_samples)
+    k = np.arange(n_samples, dtype=np.float64)
+    for frequency_hz, amplitude, key in carriers:
+        c = amplitude * np.cos(2.0 * np.pi * ((frequency_hz / sample_rate * k) % 1.0))
+        if key is not None:
+            on = np.zeros(n_samples)
+            on[:min(len(key), n_samples)] = np.asarray(key[:n_samples], np.float64)
+            c *= on
+        x += c
+    if quantise is None:
+        return x.astype(np.float32)
+    if quantise == "s16":
+        return np.clip(np.rint(x * 32767.0), -32768, 32767).astype(np.int16)
+    if quantise == "s8":
+        return np.clip(np.rint(x * 128.0), -128, 127).astype(np.int8)
+    if quantise == "u8":
+        return np.clip(np.rint(x * 128.0 + 127.5), 0, 255).astype(np.uint8)
+    raise ValueError("quantise must be None, 's16', 's8' or 'u8'")
+
+
 def make_band_torch(n_frames: int, sample_rate: int, block_size: int, n_tones: int, seed: int, device,
                     edge_width: int | None = None, text: str = TEXT, free_last_window: bool = False):
     """Same signal model generated directly in HBM with torch (benchmark input; not bit-identical to

@@ -9,7 +9,12 @@
 (b) The chain: the DDC (cu8, D = 8, T = 64) plus a bank of 8 bands at N = 16384 on the same stream, against the same bank
     fed the precomputed DDC output through sdr_process_device_stream - as interleaved pairs in one run.
 
+(c) With --real, instead of (a) and (b): a real format against the complex format of the same sample type (rs16 against
+    sc16, ru8 against cu8), the same number of input samples per call, as interleaved pairs in one run - the real form reads
+    half the bytes and mixes with im = +0.0f, everything behind the mix is the same kernel body.
+
     python tools/ddc_rate.py [--out profiles/ddc_rate.json] [--calls 200]
+    python tools/ddc_rate.py --real [--out profiles/ddc_real_rate.json] [--calls 200]
 """
 from __future__ import annotations
 
@@ -41,16 +46,34 @@ def timed(stream, fn, reps):
     return a.elapsed_time(b) * 1e-3 / reps
 
 
+def format_of(capi, fmt_name):
+    """(in_format, values per sample, torch dtype) of a format by name: f32 sc16 cs8 cu8, and rf32 rs16 rs8 ru8 real."""
+    import torch
+
+    fmt = getattr(capi, "DDC_" + fmt_name.upper())
+    dtype = {capi.DDC_F32: torch.float32, capi.DDC_SC16: torch.int16, capi.DDC_CS8: torch.int8, capi.DDC_CU8: torch.uint8}[fmt & ~capi.DDC_REAL]
+    return fmt, 1 if fmt & capi.DDC_REAL else 2, dtype
+
+
+def random_input(capi, fmt_name, seed):
+    """N_IN raw samples of the format in device memory, over the format's whole range: [N_IN, 2] complex, [N_IN] real."""
+    import torch
+
+    _, values, dtype = format_of(capi, fmt_name)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    shape = (N_IN, 2) if values == 2 else (N_IN,)
+    if dtype == torch.float32:
+        return torch.rand(shape, dtype=torch.float32, device="cuda", generator=g) * 2 - 1
+    info = torch.iinfo(dtype)
+    return torch.randint(info.min, info.max + 1, shape, dtype=dtype, device="cuda", generator=g)
+
+
 def ddc_alone(capi, synth, stream, fmt_name, d, t, calls):
     import torch
 
-    fmt = {"cu8": capi.DDC_CU8, "f32": capi.DDC_F32}[fmt_name]
-    g = torch.Generator(device="cuda")
-    g.manual_seed(1)
-    if fmt_name == "cu8":
-        x = torch.randint(0, 256, (N_IN, 2), dtype=torch.uint8, device="cuda", generator=g)
-    else:
-        x = torch.rand((N_IN, 2), dtype=torch.float32, device="cuda", generator=g) * 2 - 1
+    fmt, values, _ = format_of(capi, fmt_name)
+    x = random_input(capi, fmt_name, 1)
     m = N_IN // d
     out = torch.empty((BANDS, m, 2), dtype=torch.float32, device="cuda")
     steps = [(-28000 + 8000 * b) for b in range(BANDS)]
@@ -61,7 +84,7 @@ def ddc_alone(capi, synth, stream, fmt_name, d, t, calls):
     runs = [timed(stream, call, calls // 4) for _ in range(4)]
     ddc.close()
     s = float(np.median(runs))
-    in_bytes = N_IN * x.element_size() * 2
+    in_bytes = N_IN * x.element_size() * values
     need_bytes = in_bytes + out.numel() * 4
     flops = 4.0 * t / d * BANDS * N_IN
     t_mem, t_alu = need_bytes / HBM_PEAK, flops / FP32_PEAK
@@ -71,6 +94,45 @@ def ddc_alone(capi, synth, stream, fmt_name, d, t, calls):
         "needed_bytes_per_call": need_bytes, "needed_bytes_per_s": need_bytes / s, "share_of_hbm_peak": t_mem / s,
         "float32_ops_per_call": flops, "float32_ops_per_s": flops / s, "share_of_fp32_vector_peak": t_alu / s,
         "bound": "float32 vector peak" if t_alu > t_mem else "HBM",
+    }
+
+
+REAL_PAIRS = (("rs16", "sc16", 8, 64), ("rs16", "sc16", 64, 512), ("rs16", "sc16", 256, 2048), ("ru8", "cu8", 8, 64))
+
+
+def real_pair(capi, synth, stream, real_name, complex_name, d, t, calls):
+    """Interleaved timings of one real format and its complex counterpart: the same geometry, bands and samples per call."""
+    import torch
+
+    m = N_IN // d
+    out = torch.empty((BANDS, m, 2), dtype=torch.float32, device="cuda")
+    steps = [(-28000 + 8000 * b) for b in range(BANDS)]
+    taps = synth.lowpass_taps(d, t // d)
+    side = {}
+    for name in (real_name, complex_name):
+        x = random_input(capi, name, 3)
+        ddc = capi.Ddc(d, taps, steps, in_format=format_of(capi, name)[0], max_in_samples=N_IN)
+        ddc.set_stream(stream.cuda_stream)
+        side[name] = (ddc, x, lambda ddc=ddc, x=x: ddc.process_device(x.data_ptr(), N_IN, out.data_ptr(), m))
+    reps, pairs = 10, max(1, calls // 10)
+    for name in side:
+        timed(stream, side[name][2], 20)  # warm-up
+    runs = {name: [] for name in side}
+    for _ in range(pairs):
+        for name in side:
+            runs[name].append(timed(stream, side[name][2], reps))
+    for ddc, _, _ in side.values():
+        ddc.close()
+    med = {name: float(np.median(r)) for name, r in runs.items()}
+    return {
+        "real": real_name, "complex": complex_name, "bands": BANDS, "decimation": d, "taps": t, "input_samples_per_call": N_IN,
+        "pairs": pairs, "calls_per_timing": reps,
+        "real_seconds_per_call": med[real_name], "complex_seconds_per_call": med[complex_name],
+        "real_input_msps": N_IN / med[real_name] / 1e6, "complex_input_msps": N_IN / med[complex_name] / 1e6,
+        "real_input_bytes_per_call": side[real_name][1].numel() * side[real_name][1].element_size(),
+        "complex_input_bytes_per_call": side[complex_name][1].numel() * side[complex_name][1].element_size(),
+        "real_over_complex_time": med[real_name] / med[complex_name],
+        "real_runs": runs[real_name], "complex_runs": runs[complex_name],
     }
 
 
@@ -130,9 +192,12 @@ def chain(capi, synth, stream, calls):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ddc_rate.json"))
+    ap.add_argument("--real", action="store_true", help="measure the real formats against their complex counterparts, in pairs")
+    ap.add_argument("--out", default=None, help="default: profiles/ddc_rate.json, with --real profiles/ddc_real_rate.json")
     ap.add_argument("--calls", type=int, default=200, help="calls per figure (at least 200 for a figure that is quoted)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "ddc_real_rate.json" if args.real else "ddc_rate.json")
     import torch
 
     if not torch.cuda.is_available():
@@ -142,19 +207,28 @@ def main():
     from sdrainer_amd import capi, synth
 
     stream = torch.cuda.Stream()
-    res = {"device": torch.cuda.get_device_name(0), "hbm_peak_bytes_per_s": HBM_PEAK, "fp32_vector_peak_ops_per_s": FP32_PEAK,
-           "timing": "device events around back-to-back calls on one stream, behind a warm-up; medians", "ddc_alone": [], "chain": None}
+    res = {"device": torch.cuda.get_device_name(0), "hbm_peak_bytes_per_s": HBM_PEAK, "fp32_vector_peak_ops_per_s": FP32_PEAK}
     with torch.cuda.stream(stream):
-        for fmt in ("cu8", "f32"):
-            for d, t in ((8, 64), (64, 512)):
-                r = ddc_alone(capi, synth, stream, fmt, d, t, args.calls)
-                res["ddc_alone"].append(r)
-                print(f"ddc alone {fmt} D={d} T={t}: {r['seconds_per_call'] * 1e3:.3f} ms/call, {r['input_msps']:.0f} MS/s in, "
-                      f"{r['share_of_hbm_peak'] * 100:.1f} % of HBM peak, {r['share_of_fp32_vector_peak'] * 100:.1f} % of fp32 vector peak "
-                      f"(bound: {r['bound']})", flush=True)
-        res["chain"] = c = chain(capi, synth, stream, args.calls)
-        print(f"chain: ddc + bank {c['ddc_and_bank_seconds_per_call'] * 1e3:.3f} ms/call, bank alone {c['bank_alone_seconds_per_call'] * 1e3:.3f} ms/call",
-              flush=True)
+        if args.real:
+            res["timing"] = "device events around 10 back-to-back calls on one stream, behind a warm-up; real and complex alternate; medians"
+            res["real_pairs"] = []
+            for real_name, complex_name, d, t in REAL_PAIRS:
+                r = real_pair(capi, synth, stream, real_name, complex_name, d, t, args.calls)
+                res["real_pairs"].append(r)
+                print(f"{real_name} vs {complex_name} D={d} T={t}: {r['real_seconds_per_call'] * 1e3:.3f} / {r['complex_seconds_per_call'] * 1e3:.3f} ms/call, "
+                      f"{r['real_input_msps']:.0f} / {r['complex_input_msps']:.0f} MS/s in, time ratio {r['real_over_complex_time']:.3f}", flush=True)
+        else:
+            res.update({"timing": "device events around back-to-back calls on one stream, behind a warm-up; medians", "ddc_alone": [], "chain": None})
+            for fmt in ("cu8", "f32"):
+                for d, t in ((8, 64), (64, 512)):
+                    r = ddc_alone(capi, synth, stream, fmt, d, t, args.calls)
+                    res["ddc_alone"].append(r)
+                    print(f"ddc alone {fmt} D={d} T={t}: {r['seconds_per_call'] * 1e3:.3f} ms/call, {r['input_msps']:.0f} MS/s in, "
+                          f"{r['share_of_hbm_peak'] * 100:.1f} % of HBM peak, {r['share_of_fp32_vector_peak'] * 100:.1f} % of fp32 vector peak "
+                          f"(bound: {r['bound']})", flush=True)
+            res["chain"] = c = chain(capi, synth, stream, args.calls)
+            print(f"chain: ddc + bank {c['ddc_and_bank_seconds_per_call'] * 1e3:.3f} ms/call, bank alone {c['bank_alone_seconds_per_call'] * 1e3:.3f} ms/call",
+                  flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
