@@ -646,7 +646,7 @@ int sdr_group_read_drop_counters(sdr_group *group, uint64_t *runes_dropped, uint
  *   image   the other half of the real spectrum lies 2 f away after the mix: the caller's taps must reject it, as the
  *           filter's shape is the caller's business throughout.
  * Not offered: per-band taps, resampling by a ratio, DDC launches inside a captured graph, DDCs in an sdr_group, packed
- * 12-bit samples. */
+ * 12-bit samples.  (Many equally spaced bands: the channelizer below.) */
 #define SDR_DDC_F32 0
 #define SDR_DDC_SC16 1
 #define SDR_DDC_CS8 2
@@ -683,6 +683,70 @@ int sdr_ddc_set_nco_step(sdr_ddc *ddc, int band, int step);
 int sdr_ddc_process_device(sdr_ddc *ddc, const void *in_dev, size_t n_in_samples, float *out_dev, size_t band_stride_samples);
 int sdr_ddc_process_host(sdr_ddc *ddc, const void *in_host, size_t n_in_samples, float *out_dev, size_t band_stride_samples);
 int sdr_ddc_nco_table(float *cos_out, float *sin_out);
+
+/* channelizer -------------------------------------------------------------------------------- */
+/* A polyphase channelizer: one wide stream into M EQUALLY SPACED bands, fs / M apart, all with the same prototype filter,
+ * for T multiply-adds and one M-point FFT per output time where the DDC spends n_bands * T.  It is an object of its own
+ * beside the DDC and the bank and mirrors sdr_ddc_* call for call; a process that never creates one runs exactly what it
+ * ran.  Like the DDC it has no counterpart in the reference: its arithmetic is defined here to the bit (tests/chan_ref.py
+ * restates it in NumPy), and everything behind it is the reference fed with these float32 streams.
+ *
+ * L = SDR_DDC_NCO_SIZE, COS and SIN the tables of sdr_ddc_nco_table.  M = n_channels, D = decimation, T = n_taps = P * M,
+ * h[0 .. T-1] the caller's float32 taps.  x[k] is the float32 complex value of stream sample k, exactly what the DDC makes
+ * of each SDR_DDC_* input format (a real format is (v, +0.0f)), and (+0, +0) below the first sample; k is a 64-bit index
+ * and output time n is absolute, n = k / D.  Per output time n, three steps in this order:
+ *   branch sums  for r = 0 .. M-1, for re and im separately: acc = +0.0f; for p = 0 .. P-1, in this order:
+ *                acc = acc + (h[r + p * M] * x[n * D - r - p * M]); u[r] = acc.  Every product and every sum is rounded
+ *                once in float32; subnormals are kept.
+ *   rotation     v[r] = u[(r + n * D) mod M], n * D from the full 64-bit index: the exact replacement of the phase factor
+ *                e^{-j 2 pi c n D / M}, without arithmetic.
+ *   FFT          M points, kernel e^{+j 2 pi c r / M}, radix 2, decimation in time, unnormalised: a[i] = v[bitrev(i)]; for
+ *                len = 2, 4, .. M, every block start s (a multiple of len) and q = 0 .. len/2 - 1:
+ *                    w = (COS[q * L / len], SIN[q * L / len]),  lo = a[s + q],  hi = a[s + q + len/2]
+ *                    t.re = (w.re * hi.re) - (w.im * hi.im),  t.im = (w.re * hi.im) + (w.im * hi.re)
+ *                    a[s + q] = lo + t,  a[s + q + len/2] = lo - t
+ *                every operation rounded on its own and no product skipped: the twiddles (1, 0) and (0, 1) are multiplied
+ *                like any other (skipping them changes zero signs and what Inf and NaN do).  Channel c's output is a[c].
+ * In exact arithmetic channel c is the DDC's band with step = c * L / M (steps above 32767 wrap by -L: channel M/2 is step
+ * -32768), the same D and taps: channel c is centred c * fs / M above the wide stream's centre for c < M/2 and
+ * (c - M) * fs / M for c >= M/2.  The prototype filter must cut off at half the OUTPUT rate fs / D, as with the DDC.
+ * Limits (SDR_ERR_BAD_ARG otherwise): M a power of two in 2 .. 256; D one of M, M/2, M/4 (critically sampled, 2x and 4x
+ * oversampled) and at least 1; T = P * M with 1 <= P <= 64 and T <= 4096; n_out in 1 .. M; the channels distinct and in
+ * 0 .. M-1 (NULL: channels 0 .. n_out-1).
+ * Output stream i is channel channels[i], from float32 I,Q sample i * band_stride_samples of out_dev on: the layout
+ * sdr_process_device_stream reads.  Only the listed channels are written: a caller with real input asks for channels
+ * 0 .. M/2 only, and nobody pays the HBM writes of channels he does not read.
+ * Everything else is the DDC's: the alignment and stride rules, n_in_samples a positive multiple of D and at most
+ * max_in_samples (SDR_ERR_BAD_SIZE), sdr_chan_set_first_sample (k0 >= 0, a multiple of D, before the first process call
+ * only), a refused call changes nothing, the carry of T - 1 RAW samples on the device, and any cut of the stream into calls
+ * gives the same bits.
+ *   sdr_chan_tile_outputs  host only, needs no handle and no GPU: the output times one workgroup of the kernel computes for
+ *                        this geometry (where the tests put their output counts); negative for a geometry outside the limits.
+ * Not offered: per-channel taps, M not a power of two, a channelizer inside a captured graph or an sdr_group, feeding
+ * sdr_push_*, library-designed prototype filters, retuning (a channelizer has no NCO: fine tuning between channel centres
+ * stays the DDC's job). */
+typedef struct sdr_chan sdr_chan;
+
+typedef struct sdr_chan_config {
+    int32_t struct_size;    /* = sizeof(sdr_chan_config), ABI guard                   */
+    int32_t n_channels;     /* M, a power of two, 2 .. 256                            */
+    int32_t decimation;     /* D: M, M/2 or M/4, at least 1                           */
+    int32_t n_taps;         /* T = P * M, 1 <= P <= 64, T <= 4096                     */
+    int32_t in_format;      /* SDR_DDC_F32 / _SC16 / _CS8 / _CU8, _RF32 .. _RU8 real  */
+    int32_t max_in_samples; /* capacity: input samples per call, a multiple of D      */
+    int32_t device_id;      /* HIP device ordinal                                     */
+    int32_t n_out;          /* output streams written, 1 .. M                         */
+} sdr_chan_config;
+
+int sdr_chan_create(const sdr_chan_config *cfg, const float *taps, const int32_t *channels, sdr_chan **out);
+int sdr_chan_destroy(sdr_chan *chan);
+int sdr_chan_sync(sdr_chan *chan);
+int sdr_chan_set_stream(sdr_chan *chan, void *hip_stream);
+int sdr_chan_set_first_sample(sdr_chan *chan, int64_t k0);
+int64_t sdr_chan_total_samples(sdr_chan *chan);
+int sdr_chan_process_device(sdr_chan *chan, const void *in_dev, size_t n_in_samples, float *out_dev, size_t band_stride_samples);
+int sdr_chan_process_host(sdr_chan *chan, const void *in_host, size_t n_in_samples, float *out_dev, size_t band_stride_samples);
+int sdr_chan_tile_outputs(int n_channels, int decimation, int n_taps);
 
 /* scope tap ---------------------------------------------------------------------------------- */
 /* The reference shows its inner workings through scope.Scope (scope/scope.go:33-37); NullScope is the default

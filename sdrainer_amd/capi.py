@@ -140,6 +140,12 @@ class DdcConfig(C.Structure):
                 ("in_format", C.c_int32), ("max_in_samples", C.c_int32), ("device_id", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ChanConfig(C.Structure):
+    """sdr_chan_config (include/sdrainer_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_channels", C.c_int32), ("decimation", C.c_int32), ("n_taps", C.c_int32),
+                ("in_format", C.c_int32), ("max_in_samples", C.c_int32), ("device_id", C.c_int32), ("n_out", C.c_int32)]
+
+
 def _iq8_bytes(iq, fmt):
     """The bytes of an 8-bit push: int8 for cs8, uint8 for cu8 (any other fmt goes to the library, which refuses it)."""
     return np.ascontiguousarray(iq, dtype=np.int8 if fmt == IQ8_CS8 else np.uint8).reshape(-1)
@@ -168,6 +174,8 @@ SYMBOLS = (
     "sdr_enable_reports sdr_reports_enabled sdr_poll_reports sdr_group_enable_reports sdr_group_poll_reports "
     "sdr_ddc_create sdr_ddc_destroy sdr_ddc_sync sdr_ddc_set_stream sdr_ddc_set_first_sample sdr_ddc_total_samples "
     "sdr_ddc_set_nco_step sdr_ddc_process_device sdr_ddc_process_host sdr_ddc_nco_table "
+    "sdr_chan_create sdr_chan_destroy sdr_chan_sync sdr_chan_set_stream sdr_chan_set_first_sample sdr_chan_total_samples "
+    "sdr_chan_process_device sdr_chan_process_host sdr_chan_tile_outputs "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -323,6 +331,15 @@ def load():
     sig("sdr_ddc_process_device", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
     sig("sdr_ddc_process_host", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
     sig("sdr_ddc_nco_table", C.c_int, fp, fp)
+    sig("sdr_chan_create", C.c_int, C.POINTER(ChanConfig), fp, C.POINTER(C.c_int32), C.POINTER(vp))
+    sig("sdr_chan_destroy", C.c_int, vp)
+    sig("sdr_chan_sync", C.c_int, vp)
+    sig("sdr_chan_set_stream", C.c_int, vp, vp)
+    sig("sdr_chan_set_first_sample", C.c_int, vp, C.c_int64)
+    sig("sdr_chan_total_samples", C.c_int64, vp)
+    sig("sdr_chan_process_device", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
+    sig("sdr_chan_process_host", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
+    sig("sdr_chan_tile_outputs", C.c_int, C.c_int, C.c_int, C.c_int)
     _lib = L
     return L
 
@@ -1069,6 +1086,74 @@ class Ddc:
 
     def sync(self):
         _check(self._L.sdr_ddc_sync(self._h))
+
+
+def chan_tile_outputs(n_channels: int, decimation: int, n_taps: int) -> int:
+    """sdr_chan_tile_outputs: the output times one workgroup of the channelizer's kernel computes; negative for a geometry
+    outside the limits.  Needs no GPU."""
+    return load().sdr_chan_tile_outputs(int(n_channels), int(decimation), int(n_taps))
+
+
+class Chan:
+    """sdr_chan: one wide stream in, the listed channels of an n_channels-band polyphase filter bank out as float32 streams in
+    device memory (see include/sdrainer_hip.h).  taps: the prototype low-pass, float32, n_channels * P of them; channels: the
+    channel of each output stream (None: all of them, 0 .. n_channels - 1).  Channel c is centred c * input_rate / n_channels
+    above the wide stream's centre, (c - n_channels) * input_rate / n_channels for c >= n_channels / 2."""
+
+    def __init__(self, n_channels: int, decimation: int, taps, channels=None, in_format: int = DDC_F32,
+                 max_in_samples: int = 1 << 20, device_id: int = 0):
+        L = load()
+        taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        chans = np.arange(n_channels, dtype=np.int32) if channels is None else np.ascontiguousarray(channels, np.int32).reshape(-1)
+        self.cfg = ChanConfig(C.sizeof(ChanConfig), n_channels, decimation, int(taps.size), in_format, max_in_samples, device_id, int(chans.size))
+        self.n_channels, self.decimation, self.n_taps, self.in_format = n_channels, decimation, int(taps.size), in_format
+        self.channels = tuple(int(c) for c in chans)
+        h = C.c_void_p()
+        _check(L.sdr_chan_create(C.byref(self.cfg), taps.ctypes.data_as(C.POINTER(C.c_float)),
+                                 chans.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h)))
+        self._h, self._L = h, L
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sdr_chan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr: int):
+        _check(self._L.sdr_chan_set_stream(self._h, C.c_void_p(stream_ptr)))
+
+    def set_first_sample(self, k0: int):
+        """The next sample gets index k0 (>= 0, a multiple of the decimation); before the first process call only."""
+        _check(self._L.sdr_chan_set_first_sample(self._h, int(k0)))
+
+    @property
+    def total_samples(self) -> int:
+        return self._L.sdr_chan_total_samples(self._h)
+
+    def process_device(self, in_dev_ptr: int, n_in_samples: int, out_dev_ptr: int, band_stride_samples: int):
+        """Asynchronous on the channelizer's stream: output stream i's n_in_samples / decimation outputs go to float32 I,Q
+        sample i * band_stride_samples of out_dev_ptr on."""
+        _check(self._L.sdr_chan_process_device(self._h, C.c_void_p(in_dev_ptr), n_in_samples, C.c_void_p(out_dev_ptr), band_stride_samples))
+
+    def process_host(self, samples: np.ndarray, out_dev_ptr: int, band_stride_samples: int):
+        """samples: the wide stream's raw samples in host memory, float32, int16, int8 or uint8 by in_format: [n, 2] for a
+        complex format, [n] for a real one."""
+        dt = {DDC_F32: np.float32, DDC_SC16: np.int16, DDC_CS8: np.int8, DDC_CU8: np.uint8}[self.in_format & ~DDC_REAL]
+        s = np.ascontiguousarray(samples, dt)
+        if self.in_format & DDC_REAL:
+            if s.ndim != 1:
+                raise ValueError("a real in_format takes a one-dimensional array, one value per sample")
+        else:
+            s = s.reshape(-1, 2)
+        _check(self._L.sdr_chan_process_host(self._h, C.c_void_p(s.ctypes.data), s.shape[0], C.c_void_p(out_dev_ptr), band_stride_samples))
+
+    def sync(self):
+        _check(self._L.sdr_chan_sync(self._h))
 
 
 class AudioBank:

@@ -14,6 +14,7 @@
 
 #include "ddc.h"
 #include "host/ddc_format.h"
+#include "host/nco_table.h"
 
 namespace sdr {
 int set_error(int code, const char *msg);  // capi_bank.hip: feeds sdr_last_error()
@@ -31,27 +32,7 @@ int dfail(int code, const std::string &msg) { return sdr::set_error(code, msg.c_
 
 size_t sample_bytes(int fmt) { return (size_t)sdr::ddc_sample_bytes(fmt); }  // 8, 4, 2 complex; 4, 2, 1 real
 
-// COS over one period from the quarter wave q[0 .. L/4] = cos(2 pi i / L), evaluated in float64 and rounded once, with the
-// two ends set exactly; every other entry is a copy of one of these or its negation (both zeros are +0).
-void build_nco(float *cos_out, float *sin_out)
-{
-    constexpr int L = sdr::kDdcNco, Q = L / 4;
-    std::vector<float> c((size_t)L);
-    for (int i = 0; i <= Q; i++)
-        c[(size_t)i] = (float)std::cos(3.14159265358979323846264338327950288 * (double)i / (double)(L / 2));
-    c[0] = 1.0f;
-    c[(size_t)Q] = 0.0f;
-    for (int i = Q + 1; i <= L / 2; i++)
-        c[(size_t)i] = -c[(size_t)(L / 2 - i)];
-    for (int i = L / 2 + 1; i < L; i++)
-        c[(size_t)i] = c[(size_t)(L - i)];
-    for (int i = 0; i < L; i++) {
-        if (cos_out)
-            cos_out[i] = c[(size_t)i];
-        if (sin_out)
-            sin_out[i] = c[(size_t)((i - Q + L) % L)];
-    }
-}
+using sdr::build_nco;  // host/nco_table.h: the channelizer builds the same table
 
 }  // namespace
 

@@ -1,6 +1,6 @@
 // k_ddc_real.hip — the down-converter's kernel over the real input formats (include/sdrainer_hip.h SDR_DDC_REAL): one value
 // per sample, as a direct-sampling receiver's ADC delivers it.  A real sample v is the complex sample (v, +0.0f) through
-// k_ddc.h's arithmetic, bit for bit: the traits below give im = +0.0f and nothing else differs - the same two mix formulas
+// k_ddc.h's arithmetic, bit for bit: the traits (ddc_input_real.h) give im = +0.0f and nothing else differs - the same two mix formulas
 // (no product is dropped: 0 * s carries s's sign into the sum, and a NaN or Inf sample reaches both outputs), the same
 // filter, the same image.  A value's float32 is what the complex format of the same sample type makes of that word
 // (sc16.h, iq8.h).  The traits ask for 16-byte loads of 4, 8 or 16 samples (kWide, k_ddc.h ddc_mix_wide): with one word
@@ -8,34 +8,12 @@
 // ahead at D = 64 and 256 and 9 % behind at D = 8 (profiles/ddc_real_rate.json).
 #include "k_ddc.h"
 
+#include "ddc_input_real.h"
 #include "host/ddc_format.h"
-#include "iq8.h"
-#include "sc16.h"
 
 namespace sdr {
 
-struct InRealF32 {
-    using word = float;
-    static constexpr int kWide = 4;  // samples per 16-byte load (k_ddc.h ddc_mix_wide)
-    __device__ __forceinline__ float re(word w) const { return w; }
-    __device__ __forceinline__ float im(word) const { return 0.f; }
-};
-
-struct InRealS16 {
-    using word = uint16_t;
-    static constexpr int kWide = 8;  // samples per 16-byte load (k_ddc.h ddc_mix_wide)
-    __device__ __forceinline__ float re(word w) const { return sc16::re_of(w); }
-    __device__ __forceinline__ float im(word) const { return 0.f; }
-};
-
-// rs8 and ru8: which of the two is the trait's state, as InIq8 has it
-struct InReal8 {
-    using word = uint8_t;
-    static constexpr int kWide = 16;  // samples per 16-byte load (k_ddc.h ddc_mix_wide)
-    iq8::Format fmt;
-    __device__ __forceinline__ float re(word w) const { return iq8::re_of(w, fmt); }
-    __device__ __forceinline__ float im(word) const { return 0.f; }
-};
+// (the traits InRealF32, InRealS16 and InReal8 are ddc_input_real.h's: the channelizer converts with them too)
 
 hipError_t launch_ddc_real(const DdcLaunch &l, hipStream_t stream)
 {
