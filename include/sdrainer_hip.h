@@ -748,6 +748,75 @@ int sdr_chan_process_device(sdr_chan *chan, const void *in_dev, size_t n_in_samp
 int sdr_chan_process_host(sdr_chan *chan, const void *in_host, size_t n_in_samples, float *out_dev, size_t band_stride_samples);
 int sdr_chan_tile_outputs(int n_channels, int decimation, int n_taps);
 
+/* IQ correction ------------------------------------------------------------------------------ */
+/* A zero-IF receiver's wide stream has a DC offset (an unkeyed carrier on the stream's centre) and an I/Q gain and phase
+ * imbalance (a mirror image of every station at minus its offset, about 30 dB down for 5 % and 3 degrees).  Both are taken
+ * out where the DDC's and the channelizer's kernels convert a raw sample, and the values are computed from exact sums of
+ * the raw stream.  Everything here is additive: an object that never calls these launches exactly the kernels it launched.
+ * The entry points share the prefix sdr_iq_ and take the handle of either object (sdr_iq_ddc_*, sdr_iq_chan_*): the sets of
+ * sdr_ddc_* and sdr_chan_* calls stay the ten and nine they were.
+ *
+ * The correction.  Let (re0, im0) be what the input format makes of a raw word (above).  Each line is one float32
+ * operation, rounded on its own:
+ *     re1 = re0 - dc_re          im1 = im0 - dc_im
+ *     re  = re1                  im  = (gain_im * im1) + (cross * re1)
+ * A corrected stream is the stream of these (re, im) through the arithmetic of the DDC or the channelizer as stated above,
+ * bit for bit (tests/ddc_ref.py and tests/chan_ref.py fed the corrected float32 values; tests/iqc_ref.py restates the four
+ * lines).  Samples below the first sample stay (+0, +0): they are not -dc.
+ *   sdr_iq_ddc_set_correction, sdr_iq_chan_set_correction   the four values are copied by the call and hold from the next
+ *                        process call on, for every sample that call converts - the n_taps - 1 carried RAW samples
+ *                        included, which are read again with the new values.  With constant values any cut of the stream
+ *                        into calls gives the same bits.  A change between two calls is well defined: an output uses, for all
+ *                        its taps, the values current in the call that produces it (as for sdr_ddc_set_nco_step), so the
+ *                        n_taps - 1 samples around a change are seen once with the old and once with the new values.
+ *                        NULL: no correction, the kernels and the bits of an object that never set one.  The identity
+ *                        (0, 0, 1, 0) is NOT "none": it runs the corrected kernels, and its bits differ for a sample that is
+ *                        -0 (-0 - 0 is -0 but 0 * re1 may turn a sum's zero sign) or not finite (0 * Inf is NaN).
+ *                        SDR_ERR_BAD_ARG: a null handle, a field that is not finite, an object with a real input format
+ *                        (SDR_DDC_REAL).  A refused call changes nothing.
+ *
+ * The sums.  For SDR_DDC_CS8, _CU8 and _SC16 (SDR_ERR_BAD_ARG for _F32 - such a caller has floats in hand - and for the real
+ * formats) an object can sum the raw stream in integer units u: cs8 x, cu8 2 x - 255, sc16 x.
+ *   sdr_iq_*_enable_sums on != 0: from the next process call on, every accepted call also sums its own n_in_samples raw
+ *                        samples, each sample of the stream once; the carry is never summed and a correction is ignored.
+ *                        Off in a new object; switching off, and switching on, clear the sums.
+ *   sdr_iq_*_read_sums   waits for the object's stream, returns the sums since the last read (or since they were switched
+ *                        on) and clears them.  SDR_ERR_STATE while the sums are off.
+ * All six values are exact integers: any kernel schedule and any cut of the stream into calls give the same bits.  A call
+ * that would take n past 2^32 since the last read is not summed; its samples are counted in `skipped` (so sum_ii and sum_qq
+ * stay within 2^62).
+ *   sdr_iq_correction_from_sums   host only, needs no handle and no GPU.  Defined operation by operation in float64, each
+ *                        rounded once (NumPy reproduces its bits); S = 128 (cs8), 256 (cu8), 32767 (sc16):
+ *                            N = (double)n;  mi = (double)sum_i / N;  mq = (double)sum_q / N
+ *                            vi = (double)sum_ii / N - mi * mi;  vq = (double)sum_qq / N - mq * mq
+ *                            c = (double)sum_iq / N - mi * mq
+ *                            r = vq - (c * c) / vi;  g = sqrt(vi / r);  x = -(g * (c / vi))
+ *                            dc_re = (float)(mi / S);  dc_im = (float)(mq / S);  gain_im = (float)g;  cross = (float)x
+ *                        SDR_ERR_BAD_ARG, with *out untouched: a null pointer, n < 2, vi <= 0, r <= 0, an intermediate that
+ *                        is not finite, any other in_format.
+ * What the estimate assumes: a stream whose TRUE I and Q are uncorrelated and of equal power.  Noise and any sum of
+ * stations at different offsets satisfy that; a single strong carrier exactly on the centre does not.  The estimate is
+ * blind and per call of read: smooth the values on the host before setting them.
+ * Not offered: corrections per band or per frequency, a tracking loop on the device, sums of float32 or real streams, DC
+ * removal for real formats, a correction for the bank's own *_iq8 / *_sc16 calls. */
+typedef struct sdr_iq_correction {
+    float dc_re, dc_im, gain_im, cross;
+} sdr_iq_correction; /* 16 bytes */
+
+typedef struct sdr_iq_sums { /* 64 bytes; raw integer units u: cs8 x, cu8 2 x - 255, sc16 x */
+    int64_t n, sum_i, sum_q, sum_ii, sum_qq, sum_iq;
+    int64_t skipped;  /* samples of calls that were not summed (n would have passed 2^32) */
+    int64_t reserved; /* 0 */
+} sdr_iq_sums;
+
+int sdr_iq_ddc_set_correction(sdr_ddc *ddc, const sdr_iq_correction *c);
+int sdr_iq_ddc_enable_sums(sdr_ddc *ddc, int on);
+int sdr_iq_ddc_read_sums(sdr_ddc *ddc, sdr_iq_sums *out);
+int sdr_iq_chan_set_correction(sdr_chan *chan, const sdr_iq_correction *c);
+int sdr_iq_chan_enable_sums(sdr_chan *chan, int on);
+int sdr_iq_chan_read_sums(sdr_chan *chan, sdr_iq_sums *out);
+int sdr_iq_correction_from_sums(const sdr_iq_sums *s, int in_format, sdr_iq_correction *out);
+
 /* scope tap ---------------------------------------------------------------------------------- */
 /* The reference shows its inner workings through scope.Scope (scope/scope.go:33-37); NullScope is the default
  * and so is "no tap" here: the two reads below need a bank created with trace = 1 (that is scope.Active()).

@@ -146,6 +146,44 @@ class ChanConfig(C.Structure):
                 ("in_format", C.c_int32), ("max_in_samples", C.c_int32), ("device_id", C.c_int32), ("n_out", C.c_int32)]
 
 
+class IqCorrection(C.Structure):
+    """sdr_iq_correction (include/sdrainer_hip.h): re = re0 - dc_re, im = gain_im * (im0 - dc_im) + cross * re."""
+    _fields_ = [("dc_re", C.c_float), ("dc_im", C.c_float), ("gain_im", C.c_float), ("cross", C.c_float)]
+
+    def astuple(self):
+        return (self.dc_re, self.dc_im, self.gain_im, self.cross)
+
+
+IQ_SUMS_FIELDS = ("n", "sum_i", "sum_q", "sum_ii", "sum_qq", "sum_iq", "skipped", "reserved")
+
+
+class IqSums(C.Structure):
+    """sdr_iq_sums (include/sdrainer_hip.h): exact sums of the raw stream in integer units (cs8 x, cu8 2 x - 255, sc16 x)."""
+    _fields_ = [(f, C.c_int64) for f in IQ_SUMS_FIELDS]
+
+    def asdict(self) -> dict:
+        return {f: int(getattr(self, f)) for f in IQ_SUMS_FIELDS}
+
+
+def _iq_correction(c):
+    """None, an IqCorrection or four numbers (dc_re, dc_im, gain_im, cross) -> the pointer argument."""
+    if c is None:
+        return None
+    return C.byref(c if isinstance(c, IqCorrection) else IqCorrection(*[float(v) for v in c]))
+
+
+def _iq_sums(s) -> IqSums:
+    return s if isinstance(s, IqSums) else IqSums(**{f: int(s.get(f, 0)) for f in IQ_SUMS_FIELDS})
+
+
+def iq_correction_from_sums(sums, in_format: int) -> IqCorrection:
+    """sdr_iq_correction_from_sums: the blind estimate of DC offset and imbalance from a stream's sums (an IqSums or a dict
+    of its fields).  Needs no GPU.  SdrError(ERR_BAD_ARG) where the sums give none."""
+    out = IqCorrection()
+    _check(load().sdr_iq_correction_from_sums(C.byref(_iq_sums(sums)), int(in_format), C.byref(out)))
+    return out
+
+
 def _iq8_bytes(iq, fmt):
     """The bytes of an 8-bit push: int8 for cs8, uint8 for cu8 (any other fmt goes to the library, which refuses it)."""
     return np.ascontiguousarray(iq, dtype=np.int8 if fmt == IQ8_CS8 else np.uint8).reshape(-1)
@@ -176,6 +214,8 @@ SYMBOLS = (
     "sdr_ddc_set_nco_step sdr_ddc_process_device sdr_ddc_process_host sdr_ddc_nco_table "
     "sdr_chan_create sdr_chan_destroy sdr_chan_sync sdr_chan_set_stream sdr_chan_set_first_sample sdr_chan_total_samples "
     "sdr_chan_process_device sdr_chan_process_host sdr_chan_tile_outputs "
+    "sdr_iq_ddc_set_correction sdr_iq_ddc_enable_sums sdr_iq_ddc_read_sums "
+    "sdr_iq_chan_set_correction sdr_iq_chan_enable_sums sdr_iq_chan_read_sums sdr_iq_correction_from_sums "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -340,6 +380,11 @@ def load():
     sig("sdr_chan_process_device", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
     sig("sdr_chan_process_host", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
     sig("sdr_chan_tile_outputs", C.c_int, C.c_int, C.c_int, C.c_int)
+    for obj in ("ddc", "chan"):
+        sig(f"sdr_iq_{obj}_set_correction", C.c_int, vp, C.POINTER(IqCorrection))
+        sig(f"sdr_iq_{obj}_enable_sums", C.c_int, vp, C.c_int)
+        sig(f"sdr_iq_{obj}_read_sums", C.c_int, vp, C.POINTER(IqSums))
+    sig("sdr_iq_correction_from_sums", C.c_int, C.POINTER(IqSums), C.c_int, C.POINTER(IqCorrection))
     _lib = L
     return L
 
@@ -1087,6 +1132,19 @@ class Ddc:
     def sync(self):
         _check(self._L.sdr_ddc_sync(self._h))
 
+    def set_iq_correction(self, c):
+        """c: None (no correction), an IqCorrection or (dc_re, dc_im, gain_im, cross); from the next process call on."""
+        _check(self._L.sdr_iq_ddc_set_correction(self._h, _iq_correction(c)))
+
+    def enable_iq_sums(self, on: bool = True):
+        _check(self._L.sdr_iq_ddc_enable_sums(self._h, int(bool(on))))
+
+    def read_iq_sums(self) -> dict:
+        """Waits for the stream; the sums since the last read as a dict of sdr_iq_sums' fields, and clears them."""
+        s = IqSums()
+        _check(self._L.sdr_iq_ddc_read_sums(self._h, C.byref(s)))
+        return s.asdict()
+
 
 def chan_tile_outputs(n_channels: int, decimation: int, n_taps: int) -> int:
     """sdr_chan_tile_outputs: the output times one workgroup of the channelizer's kernel computes; negative for a geometry
@@ -1154,6 +1212,19 @@ class Chan:
 
     def sync(self):
         _check(self._L.sdr_chan_sync(self._h))
+
+    def set_iq_correction(self, c):
+        """c: None (no correction), an IqCorrection or (dc_re, dc_im, gain_im, cross); from the next process call on."""
+        _check(self._L.sdr_iq_chan_set_correction(self._h, _iq_correction(c)))
+
+    def enable_iq_sums(self, on: bool = True):
+        _check(self._L.sdr_iq_chan_enable_sums(self._h, int(bool(on))))
+
+    def read_iq_sums(self) -> dict:
+        """Waits for the stream; the sums since the last read as a dict of sdr_iq_sums' fields, and clears them."""
+        s = IqSums()
+        _check(self._L.sdr_iq_chan_read_sums(self._h, C.byref(s)))
+        return s.asdict()
 
 
 class AudioBank:

@@ -3,9 +3,11 @@
 // raw samples in device memory.  The kernel is k_chan.h, instantiated by k_chan.hip; a sample's size is host/ddc_format.h's.
 //
 // The carry is the down-converter's (capi_ddc.hip): double-buffered, formed by launch_ddc_carry behind each call's kernel,
-// everything ordered by the channelizer's one stream.
+// everything ordered by the channelizer's one stream.  The IQ correction and the raw stream's sums are the down-converter's
+// too: k_chan_iqc.hip's instance while a correction is set, k_iq_sums.hip behind the carry's kernel with the sums on.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -13,6 +15,7 @@
 #include "chan.h"
 #include "ddc.h"
 #include "host/ddc_format.h"
+#include "iq_sums_dev.h"
 #include "host/nco_table.h"
 
 namespace sdr {
@@ -47,6 +50,10 @@ struct sdr_chan {
     // sdr_chan_process_host: the upload, through pinned memory (allocated by the first such call)
     void *h_pin = nullptr, *d_in = nullptr;
     hipEvent_t uploaded = nullptr;
+    // the IQ correction (launch_chan_iqc while one is set) and the raw stream's sums (iq_sums_dev.h)
+    bool corrected = false;
+    sdr_iq_correction corr{};
+    sdr::IqSums sums;
 };
 
 namespace {
@@ -84,8 +91,10 @@ int run(sdr_chan *c, const void *in_dev, size_t n_in, float *out_dev, size_t str
     l.n_channels = g.n_channels;
     l.decimation = g.decimation;
     l.n_taps = g.n_taps;
-    CHIP(sdr::launch_chan(l, c->stream));
+    CHIP(c->corrected ? sdr::launch_chan_iqc(l, c->corr, c->stream) : sdr::launch_chan(l, c->stream));
     CHIP(sdr::launch_ddc_carry(g.in_format, c->d_carry[c->cur], in_dev, (int)n_in, g.n_taps, c->d_carry[1 - c->cur], c->stream));
+    if (c->sums.on)
+        CHIP(sdr::iq_sums_add(c->sums, g.in_format, in_dev, (int)n_in, c->stream));
     c->cur = 1 - c->cur;
     c->total += (int64_t)n_in;
     c->started = true;
@@ -115,6 +124,7 @@ int sdr_chan_destroy(sdr_chan *c)
     (void)hipFree(c->d_carry[0]);
     (void)hipFree(c->d_carry[1]);
     (void)hipFree(c->d_in);
+    sdr::iq_sums_free(c->sums);
     if (c->h_pin)
         (void)hipHostFree(c->h_pin);
     if (c->uploaded)
@@ -243,6 +253,41 @@ int sdr_chan_process_host(sdr_chan *c, const void *in_host, size_t n_in_samples,
     CHIP(hipMemcpyAsync(c->d_in, c->h_pin, bytes, hipMemcpyHostToDevice, c->stream));
     CHIP(hipEventRecord(c->uploaded, c->stream));
     return run(c, c->d_in, n_in_samples, out_dev, band_stride_samples);
+}
+
+int sdr_iq_chan_set_correction(sdr_chan *c, const sdr_iq_correction *v)
+{
+    if (!c)
+        return cfail(SDR_ERR_BAD_ARG, "null channelizer");
+    if (sdr::ddc_is_real(c->cfg.in_format))
+        return cfail(SDR_ERR_BAD_ARG, "sdr_iq_chan_set_correction: a real input format has no IQ correction");
+    if (v && !(std::isfinite(v->dc_re) && std::isfinite(v->dc_im) && std::isfinite(v->gain_im) && std::isfinite(v->cross)))
+        return cfail(SDR_ERR_BAD_ARG, "sdr_iq_chan_set_correction: every field must be finite");
+    c->corrected = v != nullptr;
+    c->corr = v ? *v : sdr_iq_correction{};
+    return SDR_OK;
+}
+
+int sdr_iq_chan_enable_sums(sdr_chan *c, int on)
+{
+    if (!c)
+        return cfail(SDR_ERR_BAD_ARG, "null channelizer");
+    if (!sdr::iq_sums_format(c->cfg.in_format))
+        return cfail(SDR_ERR_BAD_ARG, "sdr_iq_chan_enable_sums: sums are offered for SDR_DDC_CS8, _CU8 and _SC16");
+    CHIP(hipSetDevice(c->cfg.device_id));
+    CHIP(sdr::iq_sums_enable(c->sums, c->cfg.in_format, c->cfg.max_in_samples, on != 0, c->stream));
+    return SDR_OK;
+}
+
+int sdr_iq_chan_read_sums(sdr_chan *c, sdr_iq_sums *out)
+{
+    if (!c || !out)
+        return cfail(SDR_ERR_BAD_ARG, "null channelizer or output");
+    if (!c->sums.on)
+        return cfail(SDR_ERR_STATE, "sdr_iq_chan_read_sums: the sums are off (sdr_iq_chan_enable_sums)");
+    CHIP(hipSetDevice(c->cfg.device_id));
+    CHIP(sdr::iq_sums_read(c->sums, out, c->stream));
+    return SDR_OK;
 }
 
 #pragma GCC visibility pop

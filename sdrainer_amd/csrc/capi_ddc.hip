@@ -5,6 +5,9 @@
 // The carry is double-buffered: a call's kernel reads carry[cur] and a second small kernel behind it forms carry[1 - cur]
 // from carry[cur] and the call's input - also where the call is shorter than n_taps - 1 samples and part of the old carry
 // survives.  Everything is ordered by the DDC's one stream.
+//
+// While an IQ correction is set (sdr_iq_ddc_set_correction) a call launches k_ddc_iqc.hip's instance in place of k_ddc.hip's;
+// with the sums on (iq_sums_dev.h) k_iq_sums.hip's reduction over the call's input follows the carry's kernel.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,6 +17,7 @@
 
 #include "ddc.h"
 #include "host/ddc_format.h"
+#include "iq_sums_dev.h"
 #include "host/nco_table.h"
 
 namespace sdr {
@@ -50,6 +54,10 @@ struct sdr_ddc {
     // sdr_ddc_process_host: the upload, through pinned memory (allocated by the first such call)
     void *h_pin = nullptr, *d_in = nullptr;
     hipEvent_t uploaded = nullptr;
+    // the IQ correction (launch_ddc_iqc while one is set) and the raw stream's sums (iq_sums_dev.h)
+    bool corrected = false;
+    sdr_iq_correction corr{};
+    sdr::IqSums sums;
 };
 
 namespace {
@@ -86,8 +94,10 @@ int run(sdr_ddc *d, const void *in_dev, size_t n_in, float *out_dev, size_t stri
     l.decimation = c.decimation;
     l.n_taps = c.n_taps;
     l.steps = d->steps;
-    DHIP(sdr::launch_ddc(l, d->stream));
+    DHIP(d->corrected ? sdr::launch_ddc_iqc(l, d->corr, d->stream) : sdr::launch_ddc(l, d->stream));
     DHIP(sdr::launch_ddc_carry(c.in_format, d->d_carry[d->cur], in_dev, (int)n_in, c.n_taps, d->d_carry[1 - d->cur], d->stream));
+    if (d->sums.on)
+        DHIP(sdr::iq_sums_add(d->sums, c.in_format, in_dev, (int)n_in, d->stream));
     d->cur = 1 - d->cur;
     d->total += (int64_t)n_in;
     d->started = true;
@@ -116,6 +126,7 @@ int sdr_ddc_destroy(sdr_ddc *d)
     (void)hipFree(d->d_carry[0]);
     (void)hipFree(d->d_carry[1]);
     (void)hipFree(d->d_in);
+    sdr::iq_sums_free(d->sums);
     if (d->h_pin)
         (void)hipHostFree(d->h_pin);
     if (d->uploaded)
@@ -253,6 +264,51 @@ int sdr_ddc_process_host(sdr_ddc *d, const void *in_host, size_t n_in_samples, f
     DHIP(hipMemcpyAsync(d->d_in, d->h_pin, bytes, hipMemcpyHostToDevice, d->stream));
     DHIP(hipEventRecord(d->uploaded, d->stream));
     return run(d, d->d_in, n_in_samples, out_dev, band_stride_samples);
+}
+
+int sdr_iq_ddc_set_correction(sdr_ddc *d, const sdr_iq_correction *c)
+{
+    if (!d)
+        return dfail(SDR_ERR_BAD_ARG, "null ddc");
+    if (sdr::ddc_is_real(d->cfg.in_format))
+        return dfail(SDR_ERR_BAD_ARG, "sdr_iq_ddc_set_correction: a real input format has no IQ correction");
+    if (c && !(std::isfinite(c->dc_re) && std::isfinite(c->dc_im) && std::isfinite(c->gain_im) && std::isfinite(c->cross)))
+        return dfail(SDR_ERR_BAD_ARG, "sdr_iq_ddc_set_correction: every field must be finite");
+    d->corrected = c != nullptr;
+    d->corr = c ? *c : sdr_iq_correction{};
+    return SDR_OK;
+}
+
+int sdr_iq_ddc_enable_sums(sdr_ddc *d, int on)
+{
+    if (!d)
+        return dfail(SDR_ERR_BAD_ARG, "null ddc");
+    if (!sdr::iq_sums_format(d->cfg.in_format))
+        return dfail(SDR_ERR_BAD_ARG, "sdr_iq_ddc_enable_sums: sums are offered for SDR_DDC_CS8, _CU8 and _SC16");
+    DHIP(hipSetDevice(d->cfg.device_id));
+    DHIP(sdr::iq_sums_enable(d->sums, d->cfg.in_format, d->cfg.max_in_samples, on != 0, d->stream));
+    return SDR_OK;
+}
+
+int sdr_iq_ddc_read_sums(sdr_ddc *d, sdr_iq_sums *out)
+{
+    if (!d || !out)
+        return dfail(SDR_ERR_BAD_ARG, "null ddc or output");
+    if (!d->sums.on)
+        return dfail(SDR_ERR_STATE, "sdr_iq_ddc_read_sums: the sums are off (sdr_iq_ddc_enable_sums)");
+    DHIP(hipSetDevice(d->cfg.device_id));
+    DHIP(sdr::iq_sums_read(d->sums, out, d->stream));
+    return SDR_OK;
+}
+
+int sdr_iq_correction_from_sums(const sdr_iq_sums *s, int in_format, sdr_iq_correction *out)
+{
+    if (!s || !out)
+        return dfail(SDR_ERR_BAD_ARG, "null sums or output");
+    if (!sdr::iq_correction_from_sums(*s, in_format, out))
+        return dfail(SDR_ERR_BAD_ARG, "sdr_iq_correction_from_sums: a format without sums, n < 2, no variance of I, a Q that is a "
+                                      "multiple of I, or a value that is not finite");
+    return SDR_OK;
 }
 
 #pragma GCC visibility pop

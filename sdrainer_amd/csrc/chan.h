@@ -72,5 +72,7 @@ struct ChanLaunch {
 };
 
 hipError_t launch_chan(const ChanLaunch &l, hipStream_t stream);
+// k_chan_iqc.hip: the same kernel over the corrected traits (iq_correct.h), for the four complex formats only
+hipError_t launch_chan_iqc(const ChanLaunch &l, const sdr_iq_correction &c, hipStream_t stream);
 
 }  // namespace sdr

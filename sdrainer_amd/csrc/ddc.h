@@ -71,6 +71,8 @@ struct DdcLaunch {
 };
 
 hipError_t launch_ddc(const DdcLaunch &l, hipStream_t stream);
+// k_ddc_iqc.hip: the same kernel over the corrected traits (iq_correct.h), for the four complex formats only
+hipError_t launch_ddc_iqc(const DdcLaunch &l, const sdr_iq_correction &c, hipStream_t stream);
 // carry_out = the last n_taps - 1 samples of (carry_in, in[0 .. n_in)); carry_out != carry_in
 hipError_t launch_ddc_carry(int fmt, const void *carry_in, const void *in, int n_in, int n_taps, void *carry_out, hipStream_t stream);
 

@@ -156,6 +156,28 @@ def wide_stream(n_samples: int, sample_rate: float, carriers, noise_sigma: float
     raise ValueError("quantise must be None, 'cs8' or 'cu8'")
 
 
+def impair_iq(x, gain: float, phase: float, dc) -> np.ndarray:
+    """What a zero-IF receiver makes of a float stream x [n, 2]: i' = i + dc[0], q' = gain * (q cos(phase) + i sin(phase))
+    + dc[1], in float64 (phase in radians).  The imbalance puts an image of every carrier at minus its offset, the offset
+    a carrier on the stream's centre.  Quantise the result with quantise_iq."""
+    x = np.asarray(x, np.float64).reshape(-1, 2)
+    i, q = x[:, 0], x[:, 1]
+    return np.stack([i + float(dc[0]), gain * (q * np.cos(phase) + i * np.sin(phase)) + float(dc[1])], axis=1)
+
+
+def quantise_iq(x, fmt: str) -> np.ndarray:
+    """A float stream [n, 2] as raw samples: "cs8" (int8, x * 128), "cu8" (uint8, x * 128 + 127.5) or "sc16" (int16,
+    x * 32767), rounded and clipped to the type's range - the inverses of the values the library gives those words."""
+    x = np.asarray(x, np.float64).reshape(-1, 2)
+    if fmt == "cs8":
+        return np.clip(np.rint(x * 128.0), -128, 127).astype(np.int8)
+    if fmt == "cu8":
+        return np.clip(np.rint(x * 128.0 + 127.5), 0, 255).astype(np.uint8)
+    if fmt == "sc16":
+        return np.clip(np.rint(x * 32767.0), -32768, 32767).astype(np.int16)
+    raise ValueError("fmt must be 'cs8', 'cu8' or 'sc16'")
+
+
 def wide_stream_real(n_samples: int, sample_rate: float, carriers, noise_sigma: float = NOISE_SIGMA, seed: int = 0,
                      quantise: str | None = None) -> np.ndarray:
     """A wide REAL stream, [n_samples], as a direct-sampling receiver's ADC delivers it: real white noise plus
