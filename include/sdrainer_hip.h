@@ -817,6 +817,91 @@ int sdr_iq_chan_enable_sums(sdr_chan *chan, int on);
 int sdr_iq_chan_read_sums(sdr_chan *chan, sdr_iq_sums *out);
 int sdr_iq_correction_from_sums(const sdr_iq_sums *s, int in_format, sdr_iq_correction *out);
 
+/* impulse noise blanker ---------------------------------------------------------------------- */
+/* Impulse noise (power lines, ignition, electric fences, switching supplies) is a burst of a few samples at the wide rate,
+ * tens of dB above the band; behind the DDC's or the channelizer's filter it is that filter's impulse response in every
+ * band.  The blanker removes it before any narrow filter has seen it: raw samples in, raw samples of the SAME format out,
+ * both in device memory.  Its output goes to sdr_ddc_process_device, sdr_chan_process_device or, for a receiver that feeds
+ * the bank directly, sdr_process_device_stream_sc16 / _iq8.  An sdr_nb is an object of its own (a sample's fate depends on
+ * its neighbourhood, so it is no per-word input trait as the IQ correction is); a process that never creates one launches
+ * exactly what it launched.  It has no counterpart in the reference: its arithmetic is defined here in integers, to the bit
+ * (tests/nb_ref.py restates it), and everything behind it is the existing path fed with the blanked samples.
+ *
+ *   formats   SDR_DDC_SC16, _CS8, _CU8, _RS16, _RS8, _RU8.
+ *   unit      a raw value's integer unit u is the one of sdr_iq_sums: x for int8 and int16, 2 x - 255 for uint8.  A sample's
+ *             squared magnitude is m[k] = uI^2 + uQ^2 (complex), u^2 (real).
+ *   index     k is a 64-bit sample index counted from the object's start (or from sdr_nb_set_first_sample).
+ *   config    block B: a power of two, 64 .. 4096; window W: a power of two, 1 .. 64; B * W <= 65536.
+ *   power     block j holds samples j B .. j B + B - 1;  P[j] = sum of m[k] over the block, an exact integer (<= 2^43).
+ *   level     R[j] = P[j-W] + .. + P[j-1].  Only blocks with W full blocks of this stream behind them are judged: samples of
+ *             the first W blocks after the start are never impulses.
+ *   impulse   sample k of a judged block j is an impulse iff   m[k] * (B * W) * 16 > ratio_q4 * R[j]   in unsigned 64-bit
+ *             integers.  ratio_q4 is the power ratio over the window's mean, in sixteenths, 16 .. 16384; the left side stays
+ *             below 2^52 and the right side below 2^62 (static assertions in csrc/host/nb_rule.h).  ratio_q4 = 0 switches
+ *             judging off: nothing is an impulse, powers are still tracked.  R[j] = 0 needs no rule: the inequality decides.
+ *   gate      sample k is blanked iff some impulse i has i <= k <= i + hold, 0 <= hold <= B.  The gate crosses block ends
+ *             and call ends.  An impulse is judged with the R of its own block and with the ratio_q4 current in the call
+ *             that brought it; a gate that runs into the next call keeps the length it had.
+ *   blank     a blanked sample is written as: 0 in both parts for int8 and int16; I = 127 + (k & 1), Q = 128 - (k & 1) for
+ *             cu8; 127 + (k & 1) for ru8 (u = -+1, +-1: zero on average, since uint8 has no zero).  Every other sample is
+ *             copied byte for byte.
+ *   calls     n_in_samples is a positive multiple of B, at most max_in_samples.  The object keeps the last W block powers
+ *             and the open gate's remaining length on the device between calls; no call waits for the device.  Any cut of
+ *             a stream into calls gives the same output bytes and the same statistics.
+ *   stats     `impulses` (samples judged impulses) and `blanked` (samples replaced) are exact 64-bit totals counted on the
+ *             device, `samples` the host's count of samples seen; sdr_nb_read_stats waits for the stream, returns all three
+ *             since the last read and clears them.  The blanked share is how a user sets ratio_q4.
+ * Calls and statuses (a refused call changes nothing):
+ *   sdr_nb_create        SDR_ERR_BAD_ARG: a null pointer, a wrong struct_size, a format, block, window, ratio_q4 or hold
+ *                        outside the above, max_in_samples < B or not a multiple of it.
+ *   sdr_nb_set_stream    the stream of the DDC and the bank, so that no synchronisation is needed between them.
+ *   sdr_nb_set_first_sample  k0 >= 0 and a multiple of B (SDR_ERR_BAD_ARG), before the first process call only
+ *                        (SDR_ERR_STATE).  The warm-up of W blocks starts at k0.
+ *   sdr_nb_set_threshold ratio_q4 and hold from the next process call on.  SDR_ERR_BAD_ARG outside the ranges.
+ *   sdr_nb_process_device  asynchronous on the blanker's stream.  in_dev and out_dev: n_in_samples samples of in_format, both
+ *                        16-byte aligned, and the two ranges must not overlap (SDR_ERR_BAD_ARG: the gate reads samples in
+ *                        front of the ones it writes, so operation in place is undefined).  SDR_ERR_BAD_SIZE: a length that
+ *                        is not a positive multiple of B, or above max_in_samples.
+ *   sdr_nb_process_host  the same with the input in host memory (borrowed for the call), uploaded raw through pinned memory.
+ *   sdr_nb_tile_samples  host only, needs no handle and no GPU: the samples one workgroup of the gate kernel writes (where
+ *                        the tests put their lengths); negative for a format or block outside the above.
+ *   sdr_nb_blank_host    host only, needs no GPU: the definition over one whole stream from k = 0, in plain C++ with
+ *                        integers; cfg as for sdr_nb_create (device_id is ignored, n_in_samples may exceed max_in_samples),
+ *                        in and out in host memory and not overlapping, stats may be null.
+ * Not offered: float32 streams (SDR_DDC_F32, _RF32: SDR_ERR_BAD_ARG), a reference level that excludes blanked samples,
+ * median or minimum references, per-band blanking behind the DDC, interpolation across the gap instead of the blank word, a
+ * gate that opens before the impulse (it would cost latency), lengths that are not multiples of B, blanker launches inside a
+ * captured graph or in an sdr_group, an automatic threshold. */
+typedef struct sdr_nb sdr_nb;
+
+typedef struct sdr_nb_config {
+    int32_t struct_size;    /* = sizeof(sdr_nb_config), ABI guard                     */
+    int32_t in_format;      /* SDR_DDC_SC16 / _CS8 / _CU8 / _RS16 / _RS8 / _RU8       */
+    int32_t block;          /* B, a power of two, 64 .. 4096                          */
+    int32_t window;         /* W, a power of two, 1 .. 64, B * W <= 65536             */
+    int32_t ratio_q4;       /* 16 .. 16384 (sixteenths of the window's mean), 0: off  */
+    int32_t hold;           /* 0 .. B: samples blanked behind an impulse              */
+    int32_t max_in_samples; /* capacity: input samples per call, a multiple of B      */
+    int32_t device_id;      /* HIP device ordinal                                     */
+} sdr_nb_config; /* 32 bytes */
+
+typedef struct sdr_nb_stats {
+    int64_t samples, impulses, blanked, reserved;
+} sdr_nb_stats; /* 32 bytes */
+
+int sdr_nb_create(const sdr_nb_config *cfg, sdr_nb **out);
+int sdr_nb_destroy(sdr_nb *nb);
+int sdr_nb_sync(sdr_nb *nb);
+int sdr_nb_set_stream(sdr_nb *nb, void *hip_stream);
+int sdr_nb_set_first_sample(sdr_nb *nb, int64_t k0);
+int64_t sdr_nb_total_samples(sdr_nb *nb);
+int sdr_nb_set_threshold(sdr_nb *nb, int ratio_q4, int hold);
+int sdr_nb_process_device(sdr_nb *nb, const void *in_dev, size_t n_in_samples, void *out_dev);
+int sdr_nb_process_host(sdr_nb *nb, const void *in_host, size_t n_in_samples, void *out_dev);
+int sdr_nb_read_stats(sdr_nb *nb, sdr_nb_stats *out);
+int sdr_nb_tile_samples(int in_format, int block);
+int sdr_nb_blank_host(const sdr_nb_config *cfg, const void *in, size_t n_in_samples, void *out, sdr_nb_stats *stats);
+
 /* scope tap ---------------------------------------------------------------------------------- */
 /* The reference shows its inner workings through scope.Scope (scope/scope.go:33-37); NullScope is the default
  * and so is "no tap" here: the two reads below need a bank created with trace = 1 (that is scope.Active()).

@@ -184,6 +184,23 @@ def iq_correction_from_sums(sums, in_format: int) -> IqCorrection:
     return out
 
 
+class NbConfig(C.Structure):
+    """sdr_nb_config (include/sdrainer_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("in_format", C.c_int32), ("block", C.c_int32), ("window", C.c_int32),
+                ("ratio_q4", C.c_int32), ("hold", C.c_int32), ("max_in_samples", C.c_int32), ("device_id", C.c_int32)]
+
+
+NB_STATS_FIELDS = ("samples", "impulses", "blanked", "reserved")
+
+
+class NbStats(C.Structure):
+    """sdr_nb_stats (include/sdrainer_hip.h): samples seen, samples judged impulses, samples replaced."""
+    _fields_ = [(f, C.c_int64) for f in NB_STATS_FIELDS]
+
+    def asdict(self) -> dict:
+        return {f: int(getattr(self, f)) for f in NB_STATS_FIELDS}
+
+
 def _iq8_bytes(iq, fmt):
     """The bytes of an 8-bit push: int8 for cs8, uint8 for cu8 (any other fmt goes to the library, which refuses it)."""
     return np.ascontiguousarray(iq, dtype=np.int8 if fmt == IQ8_CS8 else np.uint8).reshape(-1)
@@ -216,6 +233,8 @@ SYMBOLS = (
     "sdr_chan_process_device sdr_chan_process_host sdr_chan_tile_outputs "
     "sdr_iq_ddc_set_correction sdr_iq_ddc_enable_sums sdr_iq_ddc_read_sums "
     "sdr_iq_chan_set_correction sdr_iq_chan_enable_sums sdr_iq_chan_read_sums sdr_iq_correction_from_sums "
+    "sdr_nb_create sdr_nb_destroy sdr_nb_sync sdr_nb_set_stream sdr_nb_set_first_sample sdr_nb_total_samples sdr_nb_set_threshold "
+    "sdr_nb_process_device sdr_nb_process_host sdr_nb_read_stats sdr_nb_tile_samples sdr_nb_blank_host "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -385,6 +404,18 @@ def load():
         sig(f"sdr_iq_{obj}_enable_sums", C.c_int, vp, C.c_int)
         sig(f"sdr_iq_{obj}_read_sums", C.c_int, vp, C.POINTER(IqSums))
     sig("sdr_iq_correction_from_sums", C.c_int, C.POINTER(IqSums), C.c_int, C.POINTER(IqCorrection))
+    sig("sdr_nb_create", C.c_int, C.POINTER(NbConfig), C.POINTER(vp))
+    sig("sdr_nb_destroy", C.c_int, vp)
+    sig("sdr_nb_sync", C.c_int, vp)
+    sig("sdr_nb_set_stream", C.c_int, vp, vp)
+    sig("sdr_nb_set_first_sample", C.c_int, vp, C.c_int64)
+    sig("sdr_nb_total_samples", C.c_int64, vp)
+    sig("sdr_nb_set_threshold", C.c_int, vp, C.c_int, C.c_int)
+    sig("sdr_nb_process_device", C.c_int, vp, vp, C.c_size_t, vp)
+    sig("sdr_nb_process_host", C.c_int, vp, vp, C.c_size_t, vp)
+    sig("sdr_nb_read_stats", C.c_int, vp, C.POINTER(NbStats))
+    sig("sdr_nb_tile_samples", C.c_int, C.c_int, C.c_int)
+    sig("sdr_nb_blank_host", C.c_int, C.POINTER(NbConfig), vp, C.c_size_t, vp, C.POINTER(NbStats))
     _lib = L
     return L
 
@@ -1143,6 +1174,92 @@ class Ddc:
         """Waits for the stream; the sums since the last read as a dict of sdr_iq_sums' fields, and clears them."""
         s = IqSums()
         _check(self._L.sdr_iq_ddc_read_sums(self._h, C.byref(s)))
+        return s.asdict()
+
+
+def _raw_samples(samples, in_format: int) -> np.ndarray:
+    """Raw integer samples of a DDC format as a C array: [n, 2] for a complex format, [n] for a real one."""
+    dt = {DDC_SC16: np.int16, DDC_CS8: np.int8, DDC_CU8: np.uint8}[in_format & ~DDC_REAL]
+    s = np.ascontiguousarray(samples, dt)
+    if in_format & DDC_REAL:
+        if s.ndim != 1:
+            raise ValueError("a real in_format takes a one-dimensional array, one value per sample")
+        return s
+    return s.reshape(-1, 2)
+
+
+def nb_tile_samples(in_format: int, block: int) -> int:
+    """sdr_nb_tile_samples: the samples one workgroup of the blanker's gate kernel writes; negative for a format or block
+    outside the limits.  Needs no GPU."""
+    return load().sdr_nb_tile_samples(int(in_format), int(block))
+
+
+def nb_blank_host(samples, in_format: int, block: int, window: int, ratio_q4: int, hold: int):
+    """sdr_nb_blank_host: the blanker's definition over one whole stream from k = 0, on the host.  Needs no GPU.
+    Returns (the blanked samples, shaped and typed as the input, and a dict of sdr_nb_stats' fields)."""
+    s = _raw_samples(samples, in_format)
+    out = np.empty_like(s)
+    cfg = NbConfig(C.sizeof(NbConfig), int(in_format), int(block), int(window), int(ratio_q4), int(hold), int(block), 0)
+    st = NbStats()
+    _check(load().sdr_nb_blank_host(C.byref(cfg), C.c_void_p(s.ctypes.data), s.shape[0], C.c_void_p(out.ctypes.data), C.byref(st)))
+    return out, st.asdict()
+
+
+class Nb:
+    """sdr_nb: the impulse noise blanker - raw samples in, raw samples of the same format out in device memory, in front of
+    a Ddc, a Chan or the bank's raw-format calls (see include/sdrainer_hip.h)."""
+
+    def __init__(self, in_format: int, block: int, window: int, ratio_q4: int, hold: int, max_in_samples: int = 1 << 20,
+                 device_id: int = 0):
+        L = load()
+        self.cfg = NbConfig(C.sizeof(NbConfig), in_format, block, window, ratio_q4, hold, max_in_samples, device_id)
+        self.in_format, self.block, self.window = in_format, block, window
+        h = C.c_void_p()
+        _check(L.sdr_nb_create(C.byref(self.cfg), C.byref(h)))
+        self._h, self._L = h, L
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sdr_nb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr: int):
+        _check(self._L.sdr_nb_set_stream(self._h, C.c_void_p(stream_ptr)))
+
+    def set_first_sample(self, k0: int):
+        """The next sample gets index k0 (>= 0, a multiple of block); before the first process call only."""
+        _check(self._L.sdr_nb_set_first_sample(self._h, int(k0)))
+
+    @property
+    def total_samples(self) -> int:
+        return self._L.sdr_nb_total_samples(self._h)
+
+    def set_threshold(self, ratio_q4: int, hold: int):
+        """From the next process call on; ratio_q4 = 0 switches judging off."""
+        _check(self._L.sdr_nb_set_threshold(self._h, int(ratio_q4), int(hold)))
+
+    def process_device(self, in_dev_ptr: int, n_in_samples: int, out_dev_ptr: int):
+        """Asynchronous on the blanker's stream: n_in_samples raw samples from in_dev_ptr, blanked, to out_dev_ptr."""
+        _check(self._L.sdr_nb_process_device(self._h, C.c_void_p(in_dev_ptr), n_in_samples, C.c_void_p(out_dev_ptr)))
+
+    def process_host(self, samples: np.ndarray, out_dev_ptr: int):
+        """samples: raw samples in host memory, int16, int8 or uint8 by in_format: [n, 2] complex, [n] real."""
+        s = _raw_samples(samples, self.in_format)
+        _check(self._L.sdr_nb_process_host(self._h, C.c_void_p(s.ctypes.data), s.shape[0], C.c_void_p(out_dev_ptr)))
+
+    def sync(self):
+        _check(self._L.sdr_nb_sync(self._h))
+
+    def read_stats(self) -> dict:
+        """Waits for the stream; samples, impulses and blanked since the last read as a dict, and clears them."""
+        s = NbStats()
+        _check(self._L.sdr_nb_read_stats(self._h, C.byref(s)))
         return s.asdict()
 
 
