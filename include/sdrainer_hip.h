@@ -724,7 +724,7 @@ int sdr_ddc_nco_table(float *cos_out, float *sin_out);
  *                        this geometry (where the tests put their output counts); negative for a geometry outside the limits.
  * Not offered: per-channel taps, M not a power of two, a channelizer inside a captured graph or an sdr_group, feeding
  * sdr_push_*, library-designed prototype filters, retuning (a channelizer has no NCO: fine tuning between channel centres
- * stays the DDC's job). */
+ * is the fine converter's job, sdr_fine_* below, which reads the channelizer's outputs where they lie). */
 typedef struct sdr_chan sdr_chan;
 
 typedef struct sdr_chan_config {
@@ -901,6 +901,81 @@ int sdr_nb_process_host(sdr_nb *nb, const void *in_host, size_t n_in_samples, vo
 int sdr_nb_read_stats(sdr_nb *nb, sdr_nb_stats *out);
 int sdr_nb_tile_samples(int in_format, int block);
 int sdr_nb_blank_host(const sdr_nb_config *cfg, const void *in, size_t n_in_samples, void *out, sdr_nb_stats *stats);
+
+/* fine converter ----------------------------------------------------------------------------- */
+/* A second stage behind the channelizer or a first DDC: n_bands output bands in one launch, each band reading its OWN
+ * stage-one output stream, tuned with the DDC's NCO and decimated again.  Chained behind a channelizer it puts bands anywhere
+ * in the wide stream at the channelizer's cost; behind a DDC it reaches total decimations up to 65536; a station that drifts
+ * across a channel edge is followed by re-pointing its band.  An sdr_fine is an object of its own beside the DDC, the
+ * channelizer and the bank; a process that never creates one launches exactly what it launched (no existing launcher is
+ * touched).  Its arithmetic is the down-converter's, bit for bit (tests/fine_ref.py restates it over tests/ddc_ref.py).
+ *
+ *   input    n_inputs streams of float32 I,Q in device memory, stream i from sample i * in_stride_samples of in_dev on: the
+ *            layout sdr_chan_process_device and sdr_ddc_process_device write, so stage one's band_stride_samples is stage
+ *            two's in_stride_samples and nothing is copied.  All inputs share one 64-bit sample index k, counted from the
+ *            object's start (or from sdr_fine_set_first_sample); every stream is zero below the first sample.
+ *   band     band b is the down-converter's arithmetic above applied to stream inputs[b] with step nco_steps[b]: the same
+ *            table and phase p = (k * step) mod L from the full k, the same two mix formulas, acc = +0.0f and
+ *            acc = acc + (h[j] * y[n * D - j]) for j = 0 .. n_taps - 1 with every product and sum rounded once, subnormals
+ *            kept.  It is exactly what a one-band SDR_DDC_F32 sdr_ddc gives when fed that stream.  A step tunes by
+ *            step * (input rate) / 65536 Hz.  Several bands may read one input; an input may go unread.
+ *   state    the device keeps the last n_taps - 1 raw samples of EVERY input between calls (double-buffered, as the DDC's
+ *            carry is), whether a band reads that input or not: any cut of the streams into calls gives the same bits, and a
+ *            band moved to another input finds that input's history.  sdr_fine_set_nco_step and sdr_fine_set_input hold
+ *            from the next process call on; an output uses, for all its taps, the step and the input current in the call that
+ *            produces it.
+ * Calls and statuses (these mirror sdr_ddc_*; a refused call changes nothing):
+ *   sdr_fine_create      taps: n_taps float32 values; nco_steps: n_bands steps; inputs: n_bands input indices, or NULL for
+ *                        band b reads input b (which needs n_bands <= n_inputs); all copied.  SDR_ERR_BAD_ARG: a null
+ *                        config, taps, steps or output, a wrong struct_size, n_bands outside 1..64, n_inputs outside 1..256,
+ *                        decimation outside 1..256, n_taps outside 1..4096, max_in_samples < decimation or not a multiple of
+ *                        it, a non-zero reserved word, a step outside [-32768, 32767], an input outside 0 .. n_inputs - 1.
+ *   sdr_fine_set_stream  the stream stage one and the bank run on, so that the three calls need no synchronisation.
+ *   sdr_fine_set_first_sample  k0 >= 0 and a multiple of the decimation (SDR_ERR_BAD_ARG), before the first process call
+ *                        only (SDR_ERR_STATE).  Behind a stage one that started at K0 with decimation D1 it is K0 / D1.
+ *   sdr_fine_total_samples  the index of the next sample (of every input).
+ *   sdr_fine_set_nco_step, sdr_fine_set_input   SDR_ERR_BAD_ARG: band, step or input out of range.
+ *   sdr_fine_process_device  asynchronous on the object's stream.  n_in_samples new samples of every input; band b's
+ *                        m = n_in_samples / decimation outputs go to float32 I,Q sample b * band_stride_samples of out_dev
+ *                        on.  in_dev and out_dev 16-byte aligned, in_stride_samples a multiple of 4 and >= n_in_samples,
+ *                        band_stride_samples a multiple of 4 and >= m (SDR_ERR_BAD_ARG otherwise); n_in_samples a positive
+ *                        multiple of the decimation, at most max_in_samples (SDR_ERR_BAD_SIZE otherwise).  out_dev must not
+ *                        overlap in_dev: the kernel reads the inputs while it writes the outputs, and this cannot be checked.
+ *   sdr_fine_tune        host only, needs no handle and no GPU, exact in integers: where to point a band behind a channelizer
+ *                        of M = n_channels channels with decimation D.  target is the wanted band centre in units of
+ *                        wide_rate / (65536 * D), the fine step's own unit.  With q = 65536 * D / M (an integer), c is
+ *                        target / q rounded to nearest, ties toward the even channel, and step = target - c * q; a step of
+ *                        32768 (possible only at D = M) becomes channel c + 1 and step -32768.  *channel = c mod M in
+ *                        0 .. M - 1, *step = the step.  SDR_ERR_BAD_ARG with the outputs untouched: a null output, M not a
+ *                        power of two in 2 .. 256 or D not one of M, M/2, M/4 and at least 1 (the channelizer's limits),
+ *                        |target| > 32768 * D (outside the wide stream).  In exact arithmetic channel c followed by this
+ *                        step equals one DDC of the wide stream whose total mix is target / (65536 * D) cycles per sample.
+ * Not offered: input formats other than float32, a host entry point (the input is device-resident by construction), per-band
+ * taps or decimations, IQ correction and sums on this object, launches inside a captured graph, sdr_group. */
+typedef struct sdr_fine sdr_fine;
+
+typedef struct sdr_fine_config {
+    int32_t struct_size;    /* = sizeof(sdr_fine_config), ABI guard                   */
+    int32_t n_bands;        /* 1 .. 64 output bands                                   */
+    int32_t n_inputs;       /* 1 .. 256 input streams (a channelizer's n_out, a DDC's n_bands) */
+    int32_t decimation;     /* D, 1 .. 256                                            */
+    int32_t n_taps;         /* T, 1 .. 4096, one filter for every band                */
+    int32_t max_in_samples; /* per input stream and call, a multiple of D             */
+    int32_t device_id;      /* HIP device ordinal                                     */
+    int32_t reserved;       /* 0                                                      */
+} sdr_fine_config; /* 32 bytes */
+
+int sdr_fine_create(const sdr_fine_config *cfg, const float *taps, const int32_t *nco_steps, const int32_t *inputs, sdr_fine **out);
+int sdr_fine_destroy(sdr_fine *f);
+int sdr_fine_sync(sdr_fine *f);
+int sdr_fine_set_stream(sdr_fine *f, void *hip_stream);
+int sdr_fine_set_first_sample(sdr_fine *f, int64_t k0);
+int64_t sdr_fine_total_samples(sdr_fine *f);
+int sdr_fine_set_nco_step(sdr_fine *f, int band, int step);
+int sdr_fine_set_input(sdr_fine *f, int band, int input);
+int sdr_fine_process_device(sdr_fine *f, const float *in_dev, size_t in_stride_samples, size_t n_in_samples,
+                            float *out_dev, size_t band_stride_samples);
+int sdr_fine_tune(int n_channels, int decimation, int64_t target, int32_t *channel, int32_t *step);
 
 /* scope tap ---------------------------------------------------------------------------------- */
 /* The reference shows its inner workings through scope.Scope (scope/scope.go:33-37); NullScope is the default

@@ -190,6 +190,12 @@ class NbConfig(C.Structure):
                 ("ratio_q4", C.c_int32), ("hold", C.c_int32), ("max_in_samples", C.c_int32), ("device_id", C.c_int32)]
 
 
+class FineConfig(C.Structure):
+    """sdr_fine_config (include/sdrainer_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_bands", C.c_int32), ("n_inputs", C.c_int32), ("decimation", C.c_int32),
+                ("n_taps", C.c_int32), ("max_in_samples", C.c_int32), ("device_id", C.c_int32), ("reserved", C.c_int32)]
+
+
 NB_STATS_FIELDS = ("samples", "impulses", "blanked", "reserved")
 
 
@@ -235,6 +241,8 @@ SYMBOLS = (
     "sdr_iq_chan_set_correction sdr_iq_chan_enable_sums sdr_iq_chan_read_sums sdr_iq_correction_from_sums "
     "sdr_nb_create sdr_nb_destroy sdr_nb_sync sdr_nb_set_stream sdr_nb_set_first_sample sdr_nb_total_samples sdr_nb_set_threshold "
     "sdr_nb_process_device sdr_nb_process_host sdr_nb_read_stats sdr_nb_tile_samples sdr_nb_blank_host "
+    "sdr_fine_create sdr_fine_destroy sdr_fine_sync sdr_fine_set_stream sdr_fine_set_first_sample sdr_fine_total_samples "
+    "sdr_fine_set_nco_step sdr_fine_set_input sdr_fine_process_device sdr_fine_tune "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -416,6 +424,16 @@ def load():
     sig("sdr_nb_read_stats", C.c_int, vp, C.POINTER(NbStats))
     sig("sdr_nb_tile_samples", C.c_int, C.c_int, C.c_int)
     sig("sdr_nb_blank_host", C.c_int, C.POINTER(NbConfig), vp, C.c_size_t, vp, C.POINTER(NbStats))
+    sig("sdr_fine_create", C.c_int, C.POINTER(FineConfig), fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(vp))
+    sig("sdr_fine_destroy", C.c_int, vp)
+    sig("sdr_fine_sync", C.c_int, vp)
+    sig("sdr_fine_set_stream", C.c_int, vp, vp)
+    sig("sdr_fine_set_first_sample", C.c_int, vp, C.c_int64)
+    sig("sdr_fine_total_samples", C.c_int64, vp)
+    sig("sdr_fine_set_nco_step", C.c_int, vp, C.c_int, C.c_int)
+    sig("sdr_fine_set_input", C.c_int, vp, C.c_int, C.c_int)
+    sig("sdr_fine_process_device", C.c_int, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t)
+    sig("sdr_fine_tune", C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
     _lib = L
     return L
 
@@ -1175,6 +1193,76 @@ class Ddc:
         s = IqSums()
         _check(self._L.sdr_iq_ddc_read_sums(self._h, C.byref(s)))
         return s.asdict()
+
+
+def fine_tune(n_channels: int, decimation: int, target: int):
+    """sdr_fine_tune: (channel, step) for a band centred `target` units of wide_rate / (65536 * decimation) from the wide
+    stream's centre, behind a channelizer of n_channels channels with that decimation.  Exact in integers, needs no GPU.
+    SdrError(ERR_BAD_ARG) for an illegal geometry or a target outside the wide stream."""
+    ch, st = C.c_int32(), C.c_int32()
+    _check(load().sdr_fine_tune(int(n_channels), int(decimation), int(target), C.byref(ch), C.byref(st)))
+    return ch.value, st.value
+
+
+class Fine:
+    """sdr_fine: n_inputs float32 streams in device memory in (a channelizer's or a DDC's outputs), n_bands narrower float32
+    streams out, each band tuned and decimated from the input it points at (see include/sdrainer_hip.h "fine converter").
+    taps: the low-pass, the same for every band; nco_steps: one step per band, step * input_rate / DDC_NCO_SIZE Hz;
+    inputs: the input each band reads (None: band b reads input b)."""
+
+    def __init__(self, n_inputs: int, decimation: int, taps, nco_steps, inputs=None, max_in_samples: int = 1 << 20,
+                 device_id: int = 0):
+        L = load()
+        taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        steps = np.ascontiguousarray(nco_steps, np.int32).reshape(-1)
+        ins = None if inputs is None else np.ascontiguousarray(inputs, np.int32).reshape(-1)
+        if ins is not None and ins.size != steps.size:
+            raise ValueError("one input index per band")
+        self.cfg = FineConfig(C.sizeof(FineConfig), int(steps.size), n_inputs, decimation, int(taps.size), max_in_samples, device_id, 0)
+        self.n_bands, self.n_inputs, self.decimation, self.n_taps = int(steps.size), n_inputs, decimation, int(taps.size)
+        h = C.c_void_p()
+        _check(L.sdr_fine_create(C.byref(self.cfg), taps.ctypes.data_as(C.POINTER(C.c_float)), steps.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 None if ins is None else ins.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h)))
+        self._h, self._L = h, L
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sdr_fine_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr: int):
+        _check(self._L.sdr_fine_set_stream(self._h, C.c_void_p(stream_ptr)))
+
+    def set_first_sample(self, k0: int):
+        """The next sample of every input gets index k0 (>= 0, a multiple of the decimation); before the first process call only."""
+        _check(self._L.sdr_fine_set_first_sample(self._h, int(k0)))
+
+    @property
+    def total_samples(self) -> int:
+        return self._L.sdr_fine_total_samples(self._h)
+
+    def set_nco_step(self, band: int, step: int):
+        _check(self._L.sdr_fine_set_nco_step(self._h, band, int(step)))
+
+    def set_input(self, band: int, input_: int):
+        """Band `band` reads input `input_` from the next process call on (that input's history is on the device)."""
+        _check(self._L.sdr_fine_set_input(self._h, band, int(input_)))
+
+    def process_device(self, in_dev_ptr: int, in_stride_samples: int, n_in_samples: int, out_dev_ptr: int, band_stride_samples: int):
+        """Asynchronous on the object's stream: input i's n_in_samples float32 I,Q samples are read from sample
+        i * in_stride_samples of in_dev_ptr on, band b's n_in_samples / decimation outputs go to sample
+        b * band_stride_samples of out_dev_ptr on.  The two ranges must not overlap."""
+        _check(self._L.sdr_fine_process_device(self._h, C.c_void_p(in_dev_ptr), in_stride_samples, n_in_samples,
+                                               C.c_void_p(out_dev_ptr), band_stride_samples))
+
+    def sync(self):
+        _check(self._L.sdr_fine_sync(self._h))
 
 
 def _raw_samples(samples, in_format: int) -> np.ndarray:
