@@ -977,6 +977,118 @@ int sdr_fine_process_device(sdr_fine *f, const float *in_dev, size_t in_stride_s
                             float *out_dev, size_t band_stride_samples);
 int sdr_fine_tune(int n_channels, int decimation, int64_t target, int32_t *channel, int32_t *step);
 
+/* receive chain ------------------------------------------------------------------------------ */
+/* One call from raw samples to bank batches.  An sdr_chain joins objects the caller created and still owns,
+ *     [sdr_nb] -> sdr_ddc | sdr_chan -> [sdr_fine] -> sdr_bank        (the parts in brackets are optional)
+ * and does what INTEGRATION.md's hand-written loops leave to the integrator: pushes of ANY length, a bounded ring in device
+ * memory, the carry between calls, the pointers' alignment and the frame arithmetic.  It launches no DSP kernel of its own:
+ * the hot path is the five launchers above (sdr_nb_process_device, sdr_ddc_ / sdr_chan_process_device,
+ * sdr_fine_process_device, sdr_process_device_stream), and the chain only decides pointers and counts and moves a carry.  A
+ * process that never creates a chain calls exactly what it called.  Every narrow sample and every result is what the
+ * hand-written sequence gives for the same stream, bit for bit, whatever the push lengths are.
+ *
+ * The plan (csrc/host/chain_plan.h; tests/chain_ref.py restates it).  D1 is stage one's decimation, Dtot = D1 times the fine
+ * converter's decimation (Dtot = D1 without one).  WIDE samples are the raw stream's, NARROW samples one band's at the bank.
+ *   granule   G = lcm(2 * Dtot, the blanker's block (1 without a blanker), 16).  The factor 2 makes every piece produce an
+ *             even number of narrow samples, which keeps every stage's float32 I,Q output pointer 16-byte aligned; the 16
+ *             keeps a piece's first sample 16-byte aligned for one-byte real formats.  sdr_chain_granule returns it.
+ *   piece     the largest multiple of G that fits every member's max_in_samples (the blanker's, stage one's, and the fine
+ *             converter's counted times D1).
+ *   ring      linear, per band: band b's samples start at b * ring_samples; it holds narrow samples [base, have) of the
+ *             chain's stream (indices count from the chain's creation).  ring_samples >= 2 * block_size + piece / Dtot
+ *             rounded up to a multiple of 4 (sdr_chain_min_ring; 0 in the configuration selects that minimum).
+ *   push_host takes ANY n_samples in 1 .. max_in_samples, borrowed for the call only.  The samples go through the chain's
+ *             pinned memory into its raw device buffer, behind the `pending` samples (always fewer than G) a former push
+ *             left.  The largest multiple of G now there is processed in pieces of at most `piece`; the rest stays pending
+ *             and is moved to the buffer's front by a device copy (which cannot overlap: what was processed is at least G,
+ *             what moves is less).
+ *   push_device  reads the caller's device memory in place: n_samples a positive multiple of G, at most max_in_samples
+ *             (SDR_ERR_BAD_SIZE), raw_dev 16-byte aligned (SDR_ERR_BAD_ARG), and nothing pending (SDR_ERR_STATE).  The
+ *             memory must stay untouched until the work enqueued has run (sdr_chain_sync, or the stream's own order).
+ *   a piece   of p wide samples: the blanker writes it into a chain-owned buffer; stage one writes its p / D1 outputs per
+ *             stream to the front of a chain-owned buffer, or straight into the ring when there is no fine converter; the
+ *             fine converter writes into the ring.  m = p / Dtot new narrow samples per band land behind the ones there.
+ *   carry     before a piece, if have - base + m > ring_samples, the unconsumed samples [next, have), next = frames * hop
+ *             with `frames` the frames processed so far - fewer than block_size of them - are moved to the ring's front
+ *             by one strided device-to-device copy on the stream, and base = next.
+ *   batches   after each piece, while have - next >= block_size: one sdr_process_device_stream of
+ *             min((have - next - block_size) / hop + 1, max_batch_frames) frames at ring offset next - base.
+ *             *n_batches (may be null) is the number of bank batches the push enqueued: what sdr_poll will deliver.
+ * Which batches a push enqueues is thereby a function of the geometry and the push lengths alone.  Everything is
+ * asynchronous on ONE stream; a push returns without a device synchronisation, except that push_host waits until its own
+ * pinned buffer is free, as sdr_ddc_process_host does.
+ *
+ * Members stay usable.  sdr_fine_set_nco_step / sdr_fine_set_input, sdr_ddc_set_nco_step, sdr_iq_*, sdr_nb_set_threshold /
+ * sdr_nb_read_stats, every setter of the bank, sdr_attach / sdr_detach and sdr_poll* are called on the member handles
+ * between pushes and hold "from the next process call on": from the first wide sample not yet processed, pending samples
+ * included (sdr_chain_stats says how many are pending).  Driving a member's PROCESS call directly while it is in a chain is
+ * an error the chain notices: it remembers every member's *_total_samples / sdr_total_frames behind its own calls, and a
+ * push that finds one changed returns SDR_ERR_STATE and does nothing.
+ * Calls and statuses (a refused call changes nothing):
+ *   sdr_chain_create     SDR_ERR_BAD_ARG: a null pointer, a wrong struct_size, a non-zero reserved word, max_in_samples < 1, no
+ *                        bank, both or neither of ddc and chan, a blanker whose in_format is not stage one's, a fine
+ *                        converter whose n_inputs is not stage one's output count (a DDC's n_bands, a channelizer's n_out),
+ *                        a last stage whose band count is not the bank's n_bands, members on different devices or on
+ *                        different streams (the chain runs on the stream its members share), piece < G, a ring_samples
+ *                        that is neither 0 nor a multiple of 4 of at least sdr_chain_min_ring.  SDR_ERR_STATE: a bank with
+ *                        a graph captured, with input staged (sdr_push_*), or with sdr_defer_listen on.
+ *   sdr_chain_destroy    waits for the stream and frees the chain's buffers; the members stay the caller's, in the state
+ *                        the chain left them, and can be driven by hand from then on.
+ *   sdr_chain_set_stream the chain's stream and, through their own set_stream calls, every member's.
+ *   sdr_chain_sync       every member's sync.
+ *   sdr_chain_push_host, sdr_chain_push_device   SDR_ERR_BAD_SIZE: n_samples 0 or above max_in_samples (and the rule
+ *                        above); SDR_ERR_STATE: a member was driven directly, or a member's call failed half way through
+ *                        an earlier push (destroy the chain).
+ *   sdr_chain_read_narrow  for recording and for tests: waits for the stream and copies narrow samples [from, from + n) of
+ *                        `band` to out_host (2 n floats).  SDR_ERR_BAD_ARG unless base <= from, n >= 1 and
+ *                        from + n <= have: only resident samples can be read.
+ *   sdr_chain_stats      counters kept on the host; it does not wait for the device.
+ *   sdr_chain_granule, sdr_chain_min_ring   host only, need no handle and no GPU; negative for an argument below 1, a hop
+ *                        above block_size or a piece that is no multiple of total_decimation.
+ * Not offered: chains in a captured graph or an sdr_group; a bank fed in raw sc16 or iq8 without a stage one; deferred
+ * listening; a call that inserts zeros for samples the receiver dropped; an IQ-correction or blanker-threshold loop run by
+ * the chain; several chains into one bank; set_first_sample through the chain (set it on the members before creating the
+ * chain). */
+typedef struct sdr_chain sdr_chain;
+
+typedef struct sdr_chain_config {
+    int32_t struct_size;     /* = sizeof(sdr_chain_config), ABI guard                    */
+    int32_t max_in_samples;  /* per push, wide samples                                   */
+    int32_t ring_samples;    /* narrow samples per band held in HBM; 0 = the minimum     */
+    int32_t reserved;        /* 0                                                        */
+    sdr_nb *nb;              /* or NULL                                                  */
+    sdr_ddc *ddc;            /* exactly one of ddc / chan                                */
+    sdr_chan *chan;
+    sdr_fine *fine;          /* or NULL                                                  */
+    sdr_bank *bank;
+} sdr_chain_config; /* 56 bytes with 8-byte pointers */
+
+typedef struct sdr_chain_counts { /* 96 bytes */
+    int64_t accepted;     /* wide samples taken by pushes                             */
+    int64_t processed;    /* ... of which went through the stages                     */
+    int64_t pending;      /* ... of which wait in the raw buffer: accepted - processed */
+    int64_t narrow;       /* narrow samples produced per band (`have`)                */
+    int64_t frames;       /* frames the bank was given                                */
+    int64_t batches;      /* bank batches enqueued                                    */
+    int64_t carry_moves;  /* times the ring's unconsumed samples moved to its front   */
+    int64_t granule;      /* G                                                        */
+    int64_t piece;        /* wide samples per piece at the most                       */
+    int64_t ring_samples; /* the ring size in use                                     */
+    int64_t resident_from; /* `base`: the first narrow sample sdr_chain_read_narrow can still read */
+    int64_t reserved;     /* 0                                                        */
+} sdr_chain_counts;
+
+int sdr_chain_create(const sdr_chain_config *cfg, sdr_chain **out);
+int sdr_chain_destroy(sdr_chain *chain);
+int sdr_chain_set_stream(sdr_chain *chain, void *hip_stream);
+int sdr_chain_sync(sdr_chain *chain);
+int sdr_chain_push_host(sdr_chain *chain, const void *raw, size_t n_samples, int *n_batches);
+int sdr_chain_push_device(sdr_chain *chain, const void *raw_dev, size_t n_samples, int *n_batches);
+int sdr_chain_read_narrow(sdr_chain *chain, int band, int64_t from, int n, float *out_host);
+int sdr_chain_stats(sdr_chain *chain, sdr_chain_counts *out);
+int64_t sdr_chain_granule(int total_decimation, int nb_block);
+int64_t sdr_chain_min_ring(int block_size, int hop, int64_t piece, int total_decimation);
+
 /* scope tap ---------------------------------------------------------------------------------- */
 /* The reference shows its inner workings through scope.Scope (scope/scope.go:33-37); NullScope is the default
  * and so is "no tap" here: the two reads below need a bank created with trace = 1 (that is scope.Active()).

@@ -196,6 +196,24 @@ class FineConfig(C.Structure):
                 ("n_taps", C.c_int32), ("max_in_samples", C.c_int32), ("device_id", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ChainConfig(C.Structure):
+    """sdr_chain_config (include/sdrainer_hip.h): the handles are borrowed."""
+    _fields_ = [("struct_size", C.c_int32), ("max_in_samples", C.c_int32), ("ring_samples", C.c_int32), ("reserved", C.c_int32),
+                ("nb", C.c_void_p), ("ddc", C.c_void_p), ("chan", C.c_void_p), ("fine", C.c_void_p), ("bank", C.c_void_p)]
+
+
+CHAIN_COUNT_FIELDS = ("accepted", "processed", "pending", "narrow", "frames", "batches", "carry_moves", "granule", "piece",
+                      "ring_samples", "resident_from", "reserved")
+
+
+class ChainCounts(C.Structure):
+    """sdr_chain_counts (include/sdrainer_hip.h): what sdr_chain_stats reports."""
+    _fields_ = [(f, C.c_int64) for f in CHAIN_COUNT_FIELDS]
+
+    def asdict(self) -> dict:
+        return {f: int(getattr(self, f)) for f in CHAIN_COUNT_FIELDS}
+
+
 NB_STATS_FIELDS = ("samples", "impulses", "blanked", "reserved")
 
 
@@ -243,6 +261,8 @@ SYMBOLS = (
     "sdr_nb_process_device sdr_nb_process_host sdr_nb_read_stats sdr_nb_tile_samples sdr_nb_blank_host "
     "sdr_fine_create sdr_fine_destroy sdr_fine_sync sdr_fine_set_stream sdr_fine_set_first_sample sdr_fine_total_samples "
     "sdr_fine_set_nco_step sdr_fine_set_input sdr_fine_process_device sdr_fine_tune "
+    "sdr_chain_create sdr_chain_destroy sdr_chain_set_stream sdr_chain_sync sdr_chain_push_host sdr_chain_push_device "
+    "sdr_chain_read_narrow sdr_chain_stats sdr_chain_granule sdr_chain_min_ring "
     "sdr_audio_destroy sdr_audio_blocksize sdr_audio_set_scale sdr_audio_set_debounce "
     "sdr_audio_set_magnitude_threshold sdr_audio_write sdr_audio_close sdr_audio_read_text sdr_audio_read_trace"
 ).split()
@@ -434,6 +454,16 @@ def load():
     sig("sdr_fine_set_input", C.c_int, vp, C.c_int, C.c_int)
     sig("sdr_fine_process_device", C.c_int, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t)
     sig("sdr_fine_tune", C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+    sig("sdr_chain_create", C.c_int, C.POINTER(ChainConfig), C.POINTER(vp))
+    sig("sdr_chain_destroy", C.c_int, vp)
+    sig("sdr_chain_set_stream", C.c_int, vp, vp)
+    sig("sdr_chain_sync", C.c_int, vp)
+    sig("sdr_chain_push_host", C.c_int, vp, vp, C.c_size_t, ip)
+    sig("sdr_chain_push_device", C.c_int, vp, vp, C.c_size_t, ip)
+    sig("sdr_chain_read_narrow", C.c_int, vp, C.c_int, C.c_int64, C.c_int, fp)
+    sig("sdr_chain_stats", C.c_int, vp, C.POINTER(ChainCounts))
+    sig("sdr_chain_granule", C.c_int64, C.c_int, C.c_int)
+    sig("sdr_chain_min_ring", C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int)
     _lib = L
     return L
 
@@ -1429,6 +1459,82 @@ class Chan:
         """Waits for the stream; the sums since the last read as a dict of sdr_iq_sums' fields, and clears them."""
         s = IqSums()
         _check(self._L.sdr_iq_chan_read_sums(self._h, C.byref(s)))
+        return s.asdict()
+
+
+def chain_granule(total_decimation: int, nb_block: int = 1) -> int:
+    """sdr_chain_granule: G = lcm(2 * total_decimation, nb_block, 16); negative for an argument below 1.  Needs no GPU."""
+    return load().sdr_chain_granule(int(total_decimation), int(nb_block))
+
+
+def chain_min_ring(block_size: int, hop: int, piece: int, total_decimation: int) -> int:
+    """sdr_chain_min_ring: 2 * block_size + piece / total_decimation rounded up to 4; negative for an illegal argument.
+    Needs no GPU."""
+    return load().sdr_chain_min_ring(int(block_size), int(hop), int(piece), int(total_decimation))
+
+
+class Chain:
+    """sdr_chain: [Nb] -> Ddc | Chan -> [Fine] -> Bank joined into one object that takes raw samples in pushes of any length
+    and enqueues bank batches (see include/sdrainer_hip.h "receive chain").  The members are borrowed: they stay usable for
+    their setters and for Bank.poll, and they outlive the chain.  ring_samples = 0 takes the minimum ring."""
+
+    def __init__(self, bank: "Bank", ddc=None, chan=None, nb=None, fine=None, max_in_samples: int = 1 << 20, ring_samples: int = 0):
+        L = load()
+        self.members = (nb, ddc, chan, fine, bank)  # (kept alive as long as the chain is)
+        stage = ddc if ddc is not None else chan
+        self.in_format = stage.cfg.in_format if stage is not None else DDC_F32
+        self.cfg = ChainConfig(C.sizeof(ChainConfig), max_in_samples, ring_samples, 0, *[m._h if m is not None else None for m in self.members])
+        h = C.c_void_p()
+        _check(L.sdr_chain_create(C.byref(self.cfg), C.byref(h)))
+        self._h, self._L = h, L
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sdr_chain_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr: int):
+        """The chain's stream and every member's."""
+        _check(self._L.sdr_chain_set_stream(self._h, C.c_void_p(stream_ptr)))
+
+    def sync(self):
+        _check(self._L.sdr_chain_sync(self._h))
+
+    def push_host(self, samples: np.ndarray) -> int:
+        """samples: raw samples in host memory, typed by stage one's in_format, [n, 2] for a complex format and [n] for a real
+        one; any n in 1 .. max_in_samples.  Returns the bank batches the push enqueued (Bank.poll delivers them)."""
+        dt = {DDC_F32: np.float32, DDC_SC16: np.int16, DDC_CS8: np.int8, DDC_CU8: np.uint8}[self.in_format & ~DDC_REAL]
+        s = np.ascontiguousarray(samples, dt)
+        if not self.in_format & DDC_REAL:
+            s = s.reshape(-1, 2)
+        elif s.ndim != 1:
+            raise ValueError("a real in_format takes a one-dimensional array, one value per sample")
+        nb = C.c_int()
+        _check(self._L.sdr_chain_push_host(self._h, C.c_void_p(s.ctypes.data), s.shape[0], C.byref(nb)))
+        return nb.value
+
+    def push_device(self, raw_dev_ptr: int, n_samples: int) -> int:
+        """n_samples (a multiple of the granule) raw samples in device memory, 16-byte aligned, read in place."""
+        nb = C.c_int()
+        _check(self._L.sdr_chain_push_device(self._h, C.c_void_p(raw_dev_ptr), n_samples, C.byref(nb)))
+        return nb.value
+
+    def read_narrow(self, band: int, start: int, n: int) -> np.ndarray:
+        """Narrow samples [start, start + n) of `band`, float32 [n, 2]; they must still be resident in the ring.  Waits for
+        the stream."""
+        out = np.empty((n, 2), np.float32)
+        _check(self._L.sdr_chain_read_narrow(self._h, band, int(start), int(n), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def stats(self) -> dict:
+        s = ChainCounts()
+        _check(self._L.sdr_chain_stats(self._h, C.byref(s)))
         return s.asdict()
 
 

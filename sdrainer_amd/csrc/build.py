@@ -15,11 +15,13 @@ LIB = os.path.join(HERE, "libsdrainer_hip.so")
 SOURCES = ["k_fft_psd.hip", "k_fft_psd_win.hip", "k_fft_psd_iq8.hip", "k_fft_r32.hip", "k_fft_r32_sc16.hip", "k_fft_r32_hop.hip", "k_fft_r32_hop_sc16.hip", "k_fft_r32_iq8.hip", "k_fft_r32_hop_iq8.hip", "k_fft_2p.hip", "k_fft_2p_iq8.hip", "fft_launch.hip", "k_noise.hip", "k_noise_scan.hip", "k_listen.hip", "k_report.hip", "k_peaks.hip", "k_unpack.hip", "k_results.hip", "capi_bank.hip", "capi_process.hip", "capi_staged.hip", "capi_results.hip", "capi_graph.hip", "capi_read.hip", "capi_group.hip", "sdr_audio.hip", "k_ddc.hip", "k_ddc_real.hip", "capi_ddc.hip", "k_chan.hip", "capi_chan.hip",
            "k_ddc_iqc.hip", "k_chan_iqc.hip", "k_iq_sums.hip",
            "k_nb.hip", "capi_nb.hip",
-           "k_fine.hip", "capi_fine.hip"]
+           "k_fine.hip", "capi_fine.hip",
+           "capi_chain.hip"]
 HEADERS = ["sdr_device.h", "bank.h", "host/batch_plan.h", "host/delivery.h", "host/group.h", "host/overlap.h", "host/staging.h", "fft_f64.h", "fft_r32.h", "k_fft_psd.h", "k_fft_r32.h", "fft_2p.h", "k_fft_2p_a.h", "fft_input.h", "sc16.h", "iq8.h", "noise_cert.h", "gomath.h", "cw_decoder.h", "cw_stages.h", "twiddles.h", "host/frequency_mapping.h", "ddc.h", "k_ddc.h", "host/ddc_format.h", "ddc_input_real.h", "host/nco_table.h", "chan.h", "k_chan.h",
            "iq_correct.h", "iq_sums_dev.h", "host/iq_sums.h",
            "nb.h", "host/nb_rule.h",
            "fine.h", "host/fine_tune.h",
+           "chain.h", "host/chain_plan.h",
            "../../include/sdrainer_hip.h"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fvisibility=hidden", "-Wall", "-Wno-unused-function",

@@ -4,12 +4,31 @@
 // capi_process.hip, the host-fed input capi_staged.hip, delivery capi_results.hip, graph mode capi_graph.hip, reads
 // capi_read.hip (see bank.h).
 #include "bank.h"
+#include "chain.h"
 #include "twiddles.h"
 
 using namespace sdrcapi;
 
 namespace sdr {
 int set_error(int code, const char *msg) { return fail(code, msg); }
+
+// what an sdr_chain reads of the bank it borrows (chain.h): the geometry and the three states it refuses at creation
+ChainBankView chain_bank_view(const sdr_bank *b)
+{
+    ChainBankView v{};
+    v.n_bands = b->cfg.n_bands;
+    v.block_size = b->cfg.block_size;
+    v.hop = b->hop;
+    v.max_batch_frames = b->cfg.max_batch_frames;
+    v.device_id = b->cfg.device_id;
+    v.stream = b->stream[S_FFT];
+    v.graph_captured = b->graph_ready;
+    v.defer_listen = b->defer_listen || b->listen_pending;
+    for (int band = 0; band < b->cfg.n_bands; band++)
+        if (b->in.staged[band].staged != 0 || b->in.staged[band].history != 0 || b->in.staged_kind[band] != sdr::StagedKind::None)
+            v.input_staged = true;
+    return v;
+}
 }  // namespace sdr
 
 namespace sdrcapi {

@@ -56,6 +56,11 @@ struct sdr_chan {
     sdr::IqSums sums;
 };
 
+namespace sdr {
+const sdr_chan_config &chan_config(const sdr_chan *chan) { return chan->cfg; }  // chain.h
+hipStream_t chan_stream(const sdr_chan *chan) { return chan->stream; }
+}
+
 namespace {
 
 int check_call(sdr_chan *c, const void *in, size_t n_in, const float *out, size_t stride, bool in_on_device)

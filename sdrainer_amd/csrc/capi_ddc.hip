@@ -60,6 +60,11 @@ struct sdr_ddc {
     sdr::IqSums sums;
 };
 
+namespace sdr {
+const sdr_ddc_config &ddc_config(const sdr_ddc *ddc) { return ddc->cfg; }  // chain.h
+hipStream_t ddc_stream(const sdr_ddc *ddc) { return ddc->stream; }
+}
+
 namespace {
 
 int check_call(sdr_ddc *d, const void *in, size_t n_in, const float *out, size_t stride, bool in_on_device)

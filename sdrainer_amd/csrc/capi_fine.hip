@@ -46,6 +46,11 @@ struct sdr_fine {
     bool started = false;   // a process call has been accepted
 };
 
+namespace sdr {
+const sdr_fine_config &fine_config(const sdr_fine *f) { return f->cfg; }  // chain.h
+hipStream_t fine_stream(const sdr_fine *f) { return f->stream; }
+}
+
 extern "C" {
 #pragma GCC visibility push(default)
 

@@ -63,6 +63,11 @@ struct sdr_nb {
     hipEvent_t uploaded = nullptr;
 };
 
+namespace sdr {
+const sdr_nb_config &nb_config(const sdr_nb *nb) { return nb->cfg; }  // chain.h
+hipStream_t nb_stream(const sdr_nb *nb) { return nb->stream; }
+}
+
 namespace {
 
 int check_call(sdr_nb *nb, const void *in, size_t n_in, const void *out, bool in_on_device)
