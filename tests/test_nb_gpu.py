@@ -3,7 +3,9 @@ with equal statistics: every format at lengths around the gate kernel's tile, fu
 tile and a call begin and end and where judging begins, the gate's limits hold = 0 and hold = B, one stream cut into calls
 shorter than the window, thresholds changed between calls with a gate open, both entry points, a restart above 2^32, every
 refusal with a good call behind it, and one cu8 stream through blanker, DDC and bank on one HIP stream against the oracle
-receiver fed ddc_ref(nb_ref(raw))."""
+receiver fed ddc_ref(nb_ref(raw)).  Every case here has B = 64 (the chain: 256) and W = 2 or 8; the block sizes up to 4096,
+and with them every branch the kernels take on the block's size, W = 1 and 64, holds above 256 samples and above a wave's
+4 KB, equality in the inequality and the saturated threshold are covered by the seeded fuzz, tests/test_nb_fuzz_gpu.py."""
 import ctypes as C
 
 import numpy as np
