@@ -408,22 +408,18 @@ def load():
     sig("sdr_poll_reports", C.c_int, vp, vp, C.c_int, ip, C.POINTER(C.c_int64), C.c_int)
     sig("sdr_group_enable_reports", C.c_int, vp, C.c_int)
     sig("sdr_group_poll_reports", C.c_int, vp, vp, C.c_int, ip, C.POINTER(C.c_int64), C.c_int)
+    for obj in ("ddc", "chan", "nb", "fine"):  # what every front-end object has (_Front)
+        sig(f"sdr_{obj}_destroy", C.c_int, vp)
+        sig(f"sdr_{obj}_sync", C.c_int, vp)
+        sig(f"sdr_{obj}_set_stream", C.c_int, vp, vp)
+        sig(f"sdr_{obj}_set_first_sample", C.c_int, vp, C.c_int64)
+        sig(f"sdr_{obj}_total_samples", C.c_int64, vp)
     sig("sdr_ddc_create", C.c_int, C.POINTER(DdcConfig), fp, C.POINTER(C.c_int32), C.POINTER(vp))
-    sig("sdr_ddc_destroy", C.c_int, vp)
-    sig("sdr_ddc_sync", C.c_int, vp)
-    sig("sdr_ddc_set_stream", C.c_int, vp, vp)
-    sig("sdr_ddc_set_first_sample", C.c_int, vp, C.c_int64)
-    sig("sdr_ddc_total_samples", C.c_int64, vp)
     sig("sdr_ddc_set_nco_step", C.c_int, vp, C.c_int, C.c_int)
     sig("sdr_ddc_process_device", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
     sig("sdr_ddc_process_host", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
     sig("sdr_ddc_nco_table", C.c_int, fp, fp)
     sig("sdr_chan_create", C.c_int, C.POINTER(ChanConfig), fp, C.POINTER(C.c_int32), C.POINTER(vp))
-    sig("sdr_chan_destroy", C.c_int, vp)
-    sig("sdr_chan_sync", C.c_int, vp)
-    sig("sdr_chan_set_stream", C.c_int, vp, vp)
-    sig("sdr_chan_set_first_sample", C.c_int, vp, C.c_int64)
-    sig("sdr_chan_total_samples", C.c_int64, vp)
     sig("sdr_chan_process_device", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
     sig("sdr_chan_process_host", C.c_int, vp, vp, C.c_size_t, vp, C.c_size_t)
     sig("sdr_chan_tile_outputs", C.c_int, C.c_int, C.c_int, C.c_int)
@@ -433,11 +429,6 @@ def load():
         sig(f"sdr_iq_{obj}_read_sums", C.c_int, vp, C.POINTER(IqSums))
     sig("sdr_iq_correction_from_sums", C.c_int, C.POINTER(IqSums), C.c_int, C.POINTER(IqCorrection))
     sig("sdr_nb_create", C.c_int, C.POINTER(NbConfig), C.POINTER(vp))
-    sig("sdr_nb_destroy", C.c_int, vp)
-    sig("sdr_nb_sync", C.c_int, vp)
-    sig("sdr_nb_set_stream", C.c_int, vp, vp)
-    sig("sdr_nb_set_first_sample", C.c_int, vp, C.c_int64)
-    sig("sdr_nb_total_samples", C.c_int64, vp)
     sig("sdr_nb_set_threshold", C.c_int, vp, C.c_int, C.c_int)
     sig("sdr_nb_process_device", C.c_int, vp, vp, C.c_size_t, vp)
     sig("sdr_nb_process_host", C.c_int, vp, vp, C.c_size_t, vp)
@@ -445,11 +436,6 @@ def load():
     sig("sdr_nb_tile_samples", C.c_int, C.c_int, C.c_int)
     sig("sdr_nb_blank_host", C.c_int, C.POINTER(NbConfig), vp, C.c_size_t, vp, C.POINTER(NbStats))
     sig("sdr_fine_create", C.c_int, C.POINTER(FineConfig), fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(vp))
-    sig("sdr_fine_destroy", C.c_int, vp)
-    sig("sdr_fine_sync", C.c_int, vp)
-    sig("sdr_fine_set_stream", C.c_int, vp, vp)
-    sig("sdr_fine_set_first_sample", C.c_int, vp, C.c_int64)
-    sig("sdr_fine_total_samples", C.c_int64, vp)
     sig("sdr_fine_set_nco_step", C.c_int, vp, C.c_int, C.c_int)
     sig("sdr_fine_set_input", C.c_int, vp, C.c_int, C.c_int)
     sig("sdr_fine_process_device", C.c_int, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t)
@@ -1149,10 +1135,86 @@ def ddc_nco_table():
     return co, si
 
 
-class Ddc:
+def _raw_samples(samples, in_format: int) -> np.ndarray:
+    """Raw samples of a DDC format as a C array: [n, 2] for a complex format, [n] for a real one."""
+    dt = {DDC_F32: np.float32, DDC_SC16: np.int16, DDC_CS8: np.int8, DDC_CU8: np.uint8}[in_format & ~DDC_REAL]
+    s = np.ascontiguousarray(samples, dt)
+    if in_format & DDC_REAL:
+        if s.ndim != 1:
+            raise ValueError("a real in_format takes a one-dimensional array, one value per sample")
+        return s
+    return s.reshape(-1, 2)
+
+
+class _Front:
+    """What the front-end objects share (csrc/front.h): a handle of sdr_<object>_create on one stream, with a sample clock.
+    A subclass names its entry points' prefix and sets _h and _L."""
+
+    _prefix = ""  # "sdr_ddc", "sdr_chan", "sdr_fine", "sdr_nb"
+
+    def _entry(self, name: str):
+        return getattr(self._L, f"{self._prefix}_{name}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._entry("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr: int):
+        _check(self._entry("set_stream")(self._h, C.c_void_p(stream_ptr)))
+
+    def set_first_sample(self, k0: int):
+        """The next sample (of every input) gets index k0, >= 0 and a multiple of the decimation - the blanker: of block;
+        before the first process call only."""
+        _check(self._entry("set_first_sample")(self._h, int(k0)))
+
+    @property
+    def total_samples(self) -> int:
+        return self._entry("total_samples")(self._h)
+
+    def sync(self):
+        _check(self._entry("sync")(self._h))
+
+
+class _StageOne(_Front):
+    """A down-converter or a channelizer: one wide raw stream in, from host memory too, with the IQ correction and the raw
+    stream's sums (sdr_iq_<ddc|chan>_*)."""
+
+    def _iq(self, name: str):
+        return getattr(self._L, f"sdr_iq_{self._prefix[4:]}_{name}")
+
+    def process_host(self, samples: np.ndarray, out_dev_ptr: int, band_stride_samples: int):
+        """samples: the wide stream's raw samples in host memory, float32, int16, int8 or uint8 by in_format: [n, 2] for a
+        complex format, [n] for a real one."""
+        s = _raw_samples(samples, self.in_format)
+        _check(self._entry("process_host")(self._h, C.c_void_p(s.ctypes.data), s.shape[0], C.c_void_p(out_dev_ptr), band_stride_samples))
+
+    def set_iq_correction(self, c):
+        """c: None (no correction), an IqCorrection or (dc_re, dc_im, gain_im, cross); from the next process call on."""
+        _check(self._iq("set_correction")(self._h, _iq_correction(c)))
+
+    def enable_iq_sums(self, on: bool = True):
+        _check(self._iq("enable_sums")(self._h, int(bool(on))))
+
+    def read_iq_sums(self) -> dict:
+        """Waits for the stream; the sums since the last read as a dict of sdr_iq_sums' fields, and clears them."""
+        s = IqSums()
+        _check(self._iq("read_sums")(self._h, C.byref(s)))
+        return s.asdict()
+
+
+class Ddc(_StageOne):
     """sdr_ddc: one wide stream in, n_bands narrow float32 streams out in device memory (see include/sdrainer_hip.h).
     taps: the low-pass, float32, the same for every band; nco_steps: one step per band, the band's centre offset is
     step * input_rate / DDC_NCO_SIZE Hz."""
+
+    _prefix = "sdr_ddc"
 
     def __init__(self, decimation: int, taps, nco_steps, in_format: int = DDC_F32, max_in_samples: int = 1 << 20,
                  device_id: int = 0):
@@ -1166,28 +1228,6 @@ class Ddc:
                                 steps.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h)))
         self._h, self._L = h, L
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sdr_ddc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr: int):
-        _check(self._L.sdr_ddc_set_stream(self._h, C.c_void_p(stream_ptr)))
-
-    def set_first_sample(self, k0: int):
-        """The next sample gets index k0 (>= 0, a multiple of the decimation); before the first process call only."""
-        _check(self._L.sdr_ddc_set_first_sample(self._h, int(k0)))
-
-    @property
-    def total_samples(self) -> int:
-        return self._L.sdr_ddc_total_samples(self._h)
-
     def set_nco_step(self, band: int, step: int):
         _check(self._L.sdr_ddc_set_nco_step(self._h, band, int(step)))
 
@@ -1195,34 +1235,6 @@ class Ddc:
         """Asynchronous on the DDC's stream: band b's n_in_samples / decimation outputs go to float32 I,Q sample
         b * band_stride_samples of out_dev_ptr on."""
         _check(self._L.sdr_ddc_process_device(self._h, C.c_void_p(in_dev_ptr), n_in_samples, C.c_void_p(out_dev_ptr), band_stride_samples))
-
-    def process_host(self, samples: np.ndarray, out_dev_ptr: int, band_stride_samples: int):
-        """samples: the wide stream's raw samples in host memory, float32, int16, int8 or uint8 by in_format: [n, 2] for a
-        complex format, [n] for a real one."""
-        dt = {DDC_F32: np.float32, DDC_SC16: np.int16, DDC_CS8: np.int8, DDC_CU8: np.uint8}[self.in_format & ~DDC_REAL]
-        s = np.ascontiguousarray(samples, dt)
-        if self.in_format & DDC_REAL:
-            if s.ndim != 1:
-                raise ValueError("a real in_format takes a one-dimensional array, one value per sample")
-        else:
-            s = s.reshape(-1, 2)
-        _check(self._L.sdr_ddc_process_host(self._h, C.c_void_p(s.ctypes.data), s.shape[0], C.c_void_p(out_dev_ptr), band_stride_samples))
-
-    def sync(self):
-        _check(self._L.sdr_ddc_sync(self._h))
-
-    def set_iq_correction(self, c):
-        """c: None (no correction), an IqCorrection or (dc_re, dc_im, gain_im, cross); from the next process call on."""
-        _check(self._L.sdr_iq_ddc_set_correction(self._h, _iq_correction(c)))
-
-    def enable_iq_sums(self, on: bool = True):
-        _check(self._L.sdr_iq_ddc_enable_sums(self._h, int(bool(on))))
-
-    def read_iq_sums(self) -> dict:
-        """Waits for the stream; the sums since the last read as a dict of sdr_iq_sums' fields, and clears them."""
-        s = IqSums()
-        _check(self._L.sdr_iq_ddc_read_sums(self._h, C.byref(s)))
-        return s.asdict()
 
 
 def fine_tune(n_channels: int, decimation: int, target: int):
@@ -1234,11 +1246,13 @@ def fine_tune(n_channels: int, decimation: int, target: int):
     return ch.value, st.value
 
 
-class Fine:
+class Fine(_Front):
     """sdr_fine: n_inputs float32 streams in device memory in (a channelizer's or a DDC's outputs), n_bands narrower float32
     streams out, each band tuned and decimated from the input it points at (see include/sdrainer_hip.h "fine converter").
     taps: the low-pass, the same for every band; nco_steps: one step per band, step * input_rate / DDC_NCO_SIZE Hz;
     inputs: the input each band reads (None: band b reads input b)."""
+
+    _prefix = "sdr_fine"
 
     def __init__(self, n_inputs: int, decimation: int, taps, nco_steps, inputs=None, max_in_samples: int = 1 << 20,
                  device_id: int = 0):
@@ -1255,28 +1269,6 @@ class Fine:
                                  None if ins is None else ins.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h)))
         self._h, self._L = h, L
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sdr_fine_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr: int):
-        _check(self._L.sdr_fine_set_stream(self._h, C.c_void_p(stream_ptr)))
-
-    def set_first_sample(self, k0: int):
-        """The next sample of every input gets index k0 (>= 0, a multiple of the decimation); before the first process call only."""
-        _check(self._L.sdr_fine_set_first_sample(self._h, int(k0)))
-
-    @property
-    def total_samples(self) -> int:
-        return self._L.sdr_fine_total_samples(self._h)
-
     def set_nco_step(self, band: int, step: int):
         _check(self._L.sdr_fine_set_nco_step(self._h, band, int(step)))
 
@@ -1290,20 +1282,6 @@ class Fine:
         b * band_stride_samples of out_dev_ptr on.  The two ranges must not overlap."""
         _check(self._L.sdr_fine_process_device(self._h, C.c_void_p(in_dev_ptr), in_stride_samples, n_in_samples,
                                                C.c_void_p(out_dev_ptr), band_stride_samples))
-
-    def sync(self):
-        _check(self._L.sdr_fine_sync(self._h))
-
-
-def _raw_samples(samples, in_format: int) -> np.ndarray:
-    """Raw integer samples of a DDC format as a C array: [n, 2] for a complex format, [n] for a real one."""
-    dt = {DDC_SC16: np.int16, DDC_CS8: np.int8, DDC_CU8: np.uint8}[in_format & ~DDC_REAL]
-    s = np.ascontiguousarray(samples, dt)
-    if in_format & DDC_REAL:
-        if s.ndim != 1:
-            raise ValueError("a real in_format takes a one-dimensional array, one value per sample")
-        return s
-    return s.reshape(-1, 2)
 
 
 def nb_tile_samples(in_format: int, block: int) -> int:
@@ -1323,9 +1301,11 @@ def nb_blank_host(samples, in_format: int, block: int, window: int, ratio_q4: in
     return out, st.asdict()
 
 
-class Nb:
+class Nb(_Front):
     """sdr_nb: the impulse noise blanker - raw samples in, raw samples of the same format out in device memory, in front of
     a Ddc, a Chan or the bank's raw-format calls (see include/sdrainer_hip.h)."""
+
+    _prefix = "sdr_nb"
 
     def __init__(self, in_format: int, block: int, window: int, ratio_q4: int, hold: int, max_in_samples: int = 1 << 20,
                  device_id: int = 0):
@@ -1335,28 +1315,6 @@ class Nb:
         h = C.c_void_p()
         _check(L.sdr_nb_create(C.byref(self.cfg), C.byref(h)))
         self._h, self._L = h, L
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sdr_nb_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr: int):
-        _check(self._L.sdr_nb_set_stream(self._h, C.c_void_p(stream_ptr)))
-
-    def set_first_sample(self, k0: int):
-        """The next sample gets index k0 (>= 0, a multiple of block); before the first process call only."""
-        _check(self._L.sdr_nb_set_first_sample(self._h, int(k0)))
-
-    @property
-    def total_samples(self) -> int:
-        return self._L.sdr_nb_total_samples(self._h)
 
     def set_threshold(self, ratio_q4: int, hold: int):
         """From the next process call on; ratio_q4 = 0 switches judging off."""
@@ -1371,9 +1329,6 @@ class Nb:
         s = _raw_samples(samples, self.in_format)
         _check(self._L.sdr_nb_process_host(self._h, C.c_void_p(s.ctypes.data), s.shape[0], C.c_void_p(out_dev_ptr)))
 
-    def sync(self):
-        _check(self._L.sdr_nb_sync(self._h))
-
     def read_stats(self) -> dict:
         """Waits for the stream; samples, impulses and blanked since the last read as a dict, and clears them."""
         s = NbStats()
@@ -1387,11 +1342,13 @@ def chan_tile_outputs(n_channels: int, decimation: int, n_taps: int) -> int:
     return load().sdr_chan_tile_outputs(int(n_channels), int(decimation), int(n_taps))
 
 
-class Chan:
+class Chan(_StageOne):
     """sdr_chan: one wide stream in, the listed channels of an n_channels-band polyphase filter bank out as float32 streams in
     device memory (see include/sdrainer_hip.h).  taps: the prototype low-pass, float32, n_channels * P of them; channels: the
     channel of each output stream (None: all of them, 0 .. n_channels - 1).  Channel c is centred c * input_rate / n_channels
     above the wide stream's centre, (c - n_channels) * input_rate / n_channels for c >= n_channels / 2."""
+
+    _prefix = "sdr_chan"
 
     def __init__(self, n_channels: int, decimation: int, taps, channels=None, in_format: int = DDC_F32,
                  max_in_samples: int = 1 << 20, device_id: int = 0):
@@ -1406,60 +1363,10 @@ class Chan:
                                  chans.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h)))
         self._h, self._L = h, L
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sdr_chan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_ptr: int):
-        _check(self._L.sdr_chan_set_stream(self._h, C.c_void_p(stream_ptr)))
-
-    def set_first_sample(self, k0: int):
-        """The next sample gets index k0 (>= 0, a multiple of the decimation); before the first process call only."""
-        _check(self._L.sdr_chan_set_first_sample(self._h, int(k0)))
-
-    @property
-    def total_samples(self) -> int:
-        return self._L.sdr_chan_total_samples(self._h)
-
     def process_device(self, in_dev_ptr: int, n_in_samples: int, out_dev_ptr: int, band_stride_samples: int):
         """Asynchronous on the channelizer's stream: output stream i's n_in_samples / decimation outputs go to float32 I,Q
         sample i * band_stride_samples of out_dev_ptr on."""
         _check(self._L.sdr_chan_process_device(self._h, C.c_void_p(in_dev_ptr), n_in_samples, C.c_void_p(out_dev_ptr), band_stride_samples))
-
-    def process_host(self, samples: np.ndarray, out_dev_ptr: int, band_stride_samples: int):
-        """samples: the wide stream's raw samples in host memory, float32, int16, int8 or uint8 by in_format: [n, 2] for a
-        complex format, [n] for a real one."""
-        dt = {DDC_F32: np.float32, DDC_SC16: np.int16, DDC_CS8: np.int8, DDC_CU8: np.uint8}[self.in_format & ~DDC_REAL]
-        s = np.ascontiguousarray(samples, dt)
-        if self.in_format & DDC_REAL:
-            if s.ndim != 1:
-                raise ValueError("a real in_format takes a one-dimensional array, one value per sample")
-        else:
-            s = s.reshape(-1, 2)
-        _check(self._L.sdr_chan_process_host(self._h, C.c_void_p(s.ctypes.data), s.shape[0], C.c_void_p(out_dev_ptr), band_stride_samples))
-
-    def sync(self):
-        _check(self._L.sdr_chan_sync(self._h))
-
-    def set_iq_correction(self, c):
-        """c: None (no correction), an IqCorrection or (dc_re, dc_im, gain_im, cross); from the next process call on."""
-        _check(self._L.sdr_iq_chan_set_correction(self._h, _iq_correction(c)))
-
-    def enable_iq_sums(self, on: bool = True):
-        _check(self._L.sdr_iq_chan_enable_sums(self._h, int(bool(on))))
-
-    def read_iq_sums(self) -> dict:
-        """Waits for the stream; the sums since the last read as a dict of sdr_iq_sums' fields, and clears them."""
-        s = IqSums()
-        _check(self._L.sdr_iq_chan_read_sums(self._h, C.byref(s)))
-        return s.asdict()
 
 
 def chain_granule(total_decimation: int, nb_block: int = 1) -> int:
@@ -1509,12 +1416,7 @@ class Chain:
     def push_host(self, samples: np.ndarray) -> int:
         """samples: raw samples in host memory, typed by stage one's in_format, [n, 2] for a complex format and [n] for a real
         one; any n in 1 .. max_in_samples.  Returns the bank batches the push enqueued (Bank.poll delivers them)."""
-        dt = {DDC_F32: np.float32, DDC_SC16: np.int16, DDC_CS8: np.int8, DDC_CU8: np.uint8}[self.in_format & ~DDC_REAL]
-        s = np.ascontiguousarray(samples, dt)
-        if not self.in_format & DDC_REAL:
-            s = s.reshape(-1, 2)
-        elif s.ndim != 1:
-            raise ValueError("a real in_format takes a one-dimensional array, one value per sample")
+        s = _raw_samples(samples, self.in_format)
         nb = C.c_int()
         _check(self._L.sdr_chain_push_host(self._h, C.c_void_p(s.ctypes.data), s.shape[0], C.byref(nb)))
         return nb.value

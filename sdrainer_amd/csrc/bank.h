@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/sdrainer_hip.h"
+#include "front.h"
 #include "host/delivery.h"
 #include "host/frequency_mapping.h"
 #include "host/staging.h"
@@ -31,19 +32,9 @@
 
 namespace sdrcapi {
 
-inline thread_local std::string g_last_error;
+inline thread_local std::string g_last_error;  // written by sdr::set_error (capi_bank.hip) alone
 
-inline int fail(int code, const std::string &msg)
-{
-    g_last_error = msg;
-    return code;
-}
-#define HIP_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess)                                                                          \
-            return fail(SDR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));               \
-    } while (0)
+using sdr::fail;  // and HIP_TRY: front.h's, the library's one failure function and one HIP-error macro
 
 // The ABI's 8-bit format number (the *_iq8 calls) -> the FFT's InFormat; anything else is refused.
 inline int iq8_format(int format, sdr::InFormat *fmt)

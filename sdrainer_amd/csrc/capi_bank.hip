@@ -10,7 +10,11 @@
 using namespace sdrcapi;
 
 namespace sdr {
-int set_error(int code, const char *msg) { return fail(code, msg); }
+int set_error(int code, const char *msg)  // front.h: what fail and HIP_TRY report through
+{
+    g_last_error = msg;
+    return code;
+}
 
 // what an sdr_chain reads of the bank it borrows (chain.h): the geometry and the three states it refuses at creation
 ChainBankView chain_bank_view(const sdr_bank *b)

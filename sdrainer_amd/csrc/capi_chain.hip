@@ -6,31 +6,13 @@
 //
 // A push plans on a copy of the state and commits it once every action has been enqueued.  A member that refuses or fails
 // half way leaves the members out of step with each other: the chain is marked failed and refuses further pushes.
-#include <hip/hip_runtime.h>
-
-#include <cstring>
-#include <string>
-#include <vector>
-
+// The failure function, the HIP-error macro, the guard of a half-built chain and push_host's upload are front.h's, the
+// members' own.
 #include "chain.h"
+#include "front.h"
 #include "host/chain_plan.h"
-#include "host/ddc_format.h"
 
-namespace sdr {
-int set_error(int code, const char *msg);  // capi_bank.hip: feeds sdr_last_error()
-}
-
-namespace {
-
-int hfail(int code, const std::string &msg) { return sdr::set_error(code, msg.c_str()); }
-#define HHIP(expr)                                                                          \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess)                                                               \
-            return hfail(SDR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
-    } while (0)
-
-}  // namespace
+using sdr::fail;
 
 struct sdr_chain {
     sdr_chain_config cfg{};
@@ -46,8 +28,7 @@ struct sdr_chain {
     char *d_clean = nullptr; // the blanker's output, one piece
     float *d_mid = nullptr;  // [n_mid][mid_stride] float32 I,Q: stage one's output in front of the fine converter
     float *d_ring = nullptr; // [n_bands][ring] float32 I,Q
-    void *h_pin = nullptr;   // push_host's upload (allocated by the first such call)
-    hipEvent_t uploaded = nullptr;
+    sdr::HostUpload upload;  // push_host's way into d_raw (front.h; allocated by the first such call)
     // the members' counters behind the chain's own calls: a push that finds one changed was overtaken by a direct call
     int64_t seen_nb = 0, seen_one = 0, seen_fine = 0, seen_frames = 0;
     bool failed = false;
@@ -100,9 +81,9 @@ int execute(sdr_chain *c, const std::vector<sdr::ChainAction> &actions, const ch
             break;
         }
         case sdr::ChainOp::Move:
-            HHIP(hipSetDevice(c->device));
+            HIP_TRY(hipSetDevice(c->device));
             if (a.c > 0)
-                HHIP(hipMemcpy2DAsync(c->d_ring + 2 * (size_t)a.b, ring * sizeof(float2), c->d_ring + 2 * (size_t)a.a, ring * sizeof(float2),
+                HIP_TRY(hipMemcpy2DAsync(c->d_ring + 2 * (size_t)a.b, ring * sizeof(float2), c->d_ring + 2 * (size_t)a.a, ring * sizeof(float2),
                                       (size_t)a.c * sizeof(float2), (size_t)c->n_bands, hipMemcpyDeviceToDevice, c->stream));
             break;
         case sdr::ChainOp::Batch:
@@ -112,8 +93,8 @@ int execute(sdr_chain *c, const std::vector<sdr::ChainAction> &actions, const ch
                 ++*n_batches;
             break;
         case sdr::ChainOp::Keep:
-            HHIP(hipSetDevice(c->device));
-            HHIP(hipMemcpyAsync(c->d_raw + (size_t)a.b * sb, c->d_raw + (size_t)a.a * sb, (size_t)a.c * sb, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipSetDevice(c->device));
+            HIP_TRY(hipMemcpyAsync(c->d_raw + (size_t)a.b * sb, c->d_raw + (size_t)a.a * sb, (size_t)a.c * sb, hipMemcpyDeviceToDevice, c->stream));
             break;
         }
     }
@@ -123,35 +104,29 @@ int execute(sdr_chain *c, const std::vector<sdr::ChainAction> &actions, const ch
 int push(sdr_chain *c, const void *raw, size_t n_samples, int *n_batches, bool host)
 {
     if (!c || !raw)
-        return hfail(SDR_ERR_BAD_ARG, "null chain or input");
+        return fail(SDR_ERR_BAD_ARG, "null chain or input");
     if (c->failed)
-        return hfail(SDR_ERR_STATE, "a member's call failed half way through an earlier push; destroy the chain");
+        return fail(SDR_ERR_STATE, "a member's call failed half way through an earlier push; destroy the chain");
     const int64_t n = n_samples > (size_t)c->plan.g.max_in ? c->plan.g.max_in + 1 : (int64_t)n_samples;  // (either is refused)
     const sdr::ChainPlan::Refusal why = c->plan.check(n, host);
     if (why == sdr::ChainPlan::BadSize)
-        return hfail(SDR_ERR_BAD_SIZE, host ? "n_samples must lie in 1 .. max_in_samples"
+        return fail(SDR_ERR_BAD_SIZE, host ? "n_samples must lie in 1 .. max_in_samples"
                                             : "n_samples must be a positive multiple of the granule, at most max_in_samples");
-    if (!host && ((uintptr_t)raw & 15u))
-        return hfail(SDR_ERR_BAD_ARG, "raw_dev must be 16-byte aligned");
+    if (!host && !sdr::aligned16(raw))
+        return fail(SDR_ERR_BAD_ARG, "raw_dev must be 16-byte aligned");
     if (why == sdr::ChainPlan::State)
-        return hfail(SDR_ERR_STATE, "sdr_chain_push_device: samples of a host push are pending (push_host until sdr_chain_stats says 0)");
+        return fail(SDR_ERR_STATE, "sdr_chain_push_device: samples of a host push are pending (push_host until sdr_chain_stats says 0)");
     if (!untouched(c))
-        return hfail(SDR_ERR_STATE, "a member's process call was driven directly while it is in the chain");
+        return fail(SDR_ERR_STATE, "a member's process call was driven directly while it is in the chain");
     sdr::ChainPlan next = c->plan;
     std::vector<sdr::ChainAction> actions;
     next.push(n, host, actions);
-    HHIP(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     if (host) {
-        if (!c->h_pin)
-            HHIP(hipHostMalloc(&c->h_pin, c->sample_bytes * (size_t)c->plan.g.max_in, hipHostMallocDefault));
-        if (!c->uploaded)
-            HHIP(hipEventCreateWithFlags(&c->uploaded, hipEventDisableTiming));
-        else
-            HHIP(hipEventSynchronize(c->uploaded));  // the pinned buffer is free once the last upload has left it
-        const size_t bytes = c->sample_bytes * n_samples;
-        memcpy(c->h_pin, raw, bytes);
-        HHIP(hipMemcpyAsync(c->d_raw + (size_t)c->plan.pending * c->sample_bytes, c->h_pin, bytes, hipMemcpyHostToDevice, c->stream));
-        HHIP(hipEventRecord(c->uploaded, c->stream));
+        const int rc = c->upload.stage(raw, c->sample_bytes * n_samples, c->sample_bytes * (size_t)c->plan.g.max_in,
+                                       c->d_raw + (size_t)c->plan.pending * c->sample_bytes, c->stream);
+        if (rc)
+            return rc;
     }
     if (n_batches)
         *n_batches = 0;
@@ -187,10 +162,7 @@ int sdr_chain_destroy(sdr_chain *c)
     (void)hipFree(c->d_clean);
     (void)hipFree(c->d_mid);
     (void)hipFree(c->d_ring);
-    if (c->h_pin)
-        (void)hipHostFree(c->h_pin);
-    if (c->uploaded)
-        (void)hipEventDestroy(c->uploaded);
+    c->upload.release();
     delete c;
     return SDR_OK;
 }
@@ -198,17 +170,17 @@ int sdr_chain_destroy(sdr_chain *c)
 int sdr_chain_create(const sdr_chain_config *cfg, sdr_chain **out)
 {
     if (!cfg || !out)
-        return hfail(SDR_ERR_BAD_ARG, "null config or output");
+        return fail(SDR_ERR_BAD_ARG, "null config or output");
     if (cfg->struct_size != (int32_t)sizeof(sdr_chain_config))
-        return hfail(SDR_ERR_BAD_ARG, "sdr_chain_config.struct_size mismatch");
+        return fail(SDR_ERR_BAD_ARG, "sdr_chain_config.struct_size mismatch");
     if (cfg->reserved != 0)
-        return hfail(SDR_ERR_BAD_ARG, "sdr_chain_config.reserved must be 0");
+        return fail(SDR_ERR_BAD_ARG, "sdr_chain_config.reserved must be 0");
     if (cfg->max_in_samples < 1)
-        return hfail(SDR_ERR_BAD_ARG, "max_in_samples must be at least 1");
+        return fail(SDR_ERR_BAD_ARG, "max_in_samples must be at least 1");
     if (!cfg->bank)
-        return hfail(SDR_ERR_BAD_ARG, "a chain ends in a bank");
+        return fail(SDR_ERR_BAD_ARG, "a chain ends in a bank");
     if ((cfg->ddc != nullptr) == (cfg->chan != nullptr))
-        return hfail(SDR_ERR_BAD_ARG, "exactly one of ddc and chan is stage one");
+        return fail(SDR_ERR_BAD_ARG, "exactly one of ddc and chan is stage one");
     // stage one, as the chain sees either kind
     int fmt, d1, n_one, dev_one;
     int64_t limit;
@@ -229,7 +201,7 @@ int sdr_chain_create(const sdr_chain_config *cfg, sdr_chain **out)
     if (cfg->nb) {
         const sdr_nb_config &o = sdr::nb_config(cfg->nb);
         if (o.in_format != fmt)
-            return hfail(SDR_ERR_BAD_ARG, "the blanker's in_format is not stage one's");
+            return fail(SDR_ERR_BAD_ARG, "the blanker's in_format is not stage one's");
         nb_block = o.block;
         limit = o.max_in_samples < limit ? o.max_in_samples : limit;
         one_device = one_device && o.device_id == dev_one;
@@ -238,7 +210,7 @@ int sdr_chain_create(const sdr_chain_config *cfg, sdr_chain **out)
     if (cfg->fine) {
         const sdr_fine_config &o = sdr::fine_config(cfg->fine);
         if (o.n_inputs != n_one)
-            return hfail(SDR_ERR_BAD_ARG, "the fine converter's n_inputs is not stage one's output count");
+            return fail(SDR_ERR_BAD_ARG, "the fine converter's n_inputs is not stage one's output count");
         dtot *= o.decimation;
         n_last = o.n_bands;
         const int64_t wide = (int64_t)o.max_in_samples * d1;
@@ -247,17 +219,17 @@ int sdr_chain_create(const sdr_chain_config *cfg, sdr_chain **out)
         one_stream = one_stream && sdr::fine_stream(cfg->fine) == stream;
     }
     if (n_last != bank.n_bands)
-        return hfail(SDR_ERR_BAD_ARG, "the last stage's band count is not the bank's n_bands");
+        return fail(SDR_ERR_BAD_ARG, "the last stage's band count is not the bank's n_bands");
     if (!one_device)
-        return hfail(SDR_ERR_BAD_ARG, "the members are on different devices");
+        return fail(SDR_ERR_BAD_ARG, "the members are on different devices");
     if (!one_stream)
-        return hfail(SDR_ERR_BAD_ARG, "the members are on different streams (set one stream on every member, or sdr_chain_set_stream later)");
+        return fail(SDR_ERR_BAD_ARG, "the members are on different streams (set one stream on every member, or sdr_chain_set_stream later)");
     sdr::ChainGeometry g{};
     g.total_decimation = dtot;
     g.granule = sdr::chain_granule(dtot, nb_block);
     g.piece = sdr::chain_piece(g.granule, limit);
     if (g.granule < 1 || g.piece < g.granule)
-        return hfail(SDR_ERR_BAD_ARG, "not one granule (lcm(2 * total decimation, blanker block, 16)) fits every member's max_in_samples");
+        return fail(SDR_ERR_BAD_ARG, "not one granule (lcm(2 * total decimation, blanker block, 16)) fits every member's max_in_samples");
     g.block_size = bank.block_size;
     g.hop = bank.hop;
     g.max_batch_frames = bank.max_batch_frames;
@@ -265,15 +237,15 @@ int sdr_chain_create(const sdr_chain_config *cfg, sdr_chain **out)
     const int64_t min_ring = sdr::chain_min_ring(g.block_size, g.hop, g.piece, dtot);
     g.ring = cfg->ring_samples == 0 ? min_ring : cfg->ring_samples;
     if (min_ring < 1 || g.ring < min_ring || g.ring % 4 != 0 || g.ring > 0xffffffffll)
-        return hfail(SDR_ERR_BAD_ARG, "ring_samples must be 0 or a multiple of 4 of at least sdr_chain_min_ring");
+        return fail(SDR_ERR_BAD_ARG, "ring_samples must be 0 or a multiple of 4 of at least sdr_chain_min_ring");
     if (bank.graph_captured)
-        return hfail(SDR_ERR_STATE, "the bank has a graph captured (sdr_graph_release first)");
+        return fail(SDR_ERR_STATE, "the bank has a graph captured (sdr_graph_release first)");
     if (bank.input_staged)
-        return hfail(SDR_ERR_STATE, "the bank has input staged (a bank in a chain is fed by the chain alone)");
+        return fail(SDR_ERR_STATE, "the bank has input staged (a bank in a chain is fed by the chain alone)");
     if (bank.defer_listen)
-        return hfail(SDR_ERR_STATE, "the bank defers its listen half (sdr_defer_listen): not offered in a chain");
-    HHIP(hipSetDevice(bank.device_id));
-    sdr_chain *c = new sdr_chain();
+        return fail(SDR_ERR_STATE, "the bank defers its listen half (sdr_defer_listen): not offered in a chain");
+    HIP_TRY(hipSetDevice(bank.device_id));
+    sdr::Building<sdr_chain, sdr_chain_destroy> c(new sdr_chain());
     c->cfg = *cfg;
     c->plan.g = g;
     c->stream = stream;
@@ -285,33 +257,23 @@ int sdr_chain_create(const sdr_chain_config *cfg, sdr_chain **out)
     // the most one piece ever holds: a push processes at most the whole granules of pending + max_in_samples
     const int64_t most = (g.granule - 1 + g.max_in) / g.granule * g.granule, p_cap = most < g.piece ? most : g.piece;
     c->mid_stride = ((size_t)(p_cap / d1) + 3) / 4 * 4;
-#define HCREATE(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            const std::string _msg = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            sdr_chain_destroy(c);                                                           \
-            return hfail(SDR_ERR_HIP, _msg);                                                \
-        }                                                                                   \
-    } while (0)
-    HCREATE(hipMalloc((void **)&c->d_raw, c->sample_bytes * (size_t)(g.granule + g.max_in)));
+    HIP_TRY(hipMalloc((void **)&c->d_raw, c->sample_bytes * (size_t)(g.granule + g.max_in)));
     if (cfg->nb)
-        HCREATE(hipMalloc((void **)&c->d_clean, c->sample_bytes * (size_t)p_cap));
+        HIP_TRY(hipMalloc((void **)&c->d_clean, c->sample_bytes * (size_t)p_cap));
     if (cfg->fine)
-        HCREATE(hipMalloc((void **)&c->d_mid, sizeof(float2) * c->mid_stride * (size_t)n_one));
-    HCREATE(hipMalloc((void **)&c->d_ring, sizeof(float2) * (size_t)g.ring * (size_t)bank.n_bands));
-#undef HCREATE
-    remember(c);
-    *out = c;
+        HIP_TRY(hipMalloc((void **)&c->d_mid, sizeof(float2) * c->mid_stride * (size_t)n_one));
+    HIP_TRY(hipMalloc((void **)&c->d_ring, sizeof(float2) * (size_t)g.ring * (size_t)bank.n_bands));
+    remember(c.get());
+    *out = c.release();
     return SDR_OK;
 }
 
 int sdr_chain_set_stream(sdr_chain *c, void *hip_stream)
 {
     if (!c)
-        return hfail(SDR_ERR_BAD_ARG, "null chain");
-    HHIP(hipSetDevice(c->device));
-    HHIP(hipStreamSynchronize(c->stream));  // (the ring and the pending samples are ordered by the old stream)
+        return fail(SDR_ERR_BAD_ARG, "null chain");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (the ring and the pending samples are ordered by the old stream)
     const sdr_chain_config &m = c->cfg;
     int rc = SDR_OK;
     if (m.nb && (rc = sdr_nb_set_stream(m.nb, hip_stream)))
@@ -329,7 +291,7 @@ int sdr_chain_set_stream(sdr_chain *c, void *hip_stream)
 int sdr_chain_sync(sdr_chain *c)
 {
     if (!c)
-        return hfail(SDR_ERR_BAD_ARG, "null chain");
+        return fail(SDR_ERR_BAD_ARG, "null chain");
     const sdr_chain_config &m = c->cfg;
     int rc = SDR_OK;
     if (m.nb && (rc = sdr_nb_sync(m.nb)))
@@ -338,8 +300,8 @@ int sdr_chain_sync(sdr_chain *c)
         return rc;
     if (m.fine && (rc = sdr_fine_sync(m.fine)))
         return rc;
-    HHIP(hipSetDevice(c->device));
-    HHIP(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return sdr_sync(m.bank);
 }
 
@@ -353,22 +315,22 @@ int sdr_chain_push_device(sdr_chain *c, const void *raw_dev, size_t n_samples, i
 int sdr_chain_read_narrow(sdr_chain *c, int band, int64_t from, int n, float *out_host)
 {
     if (!c || !out_host)
-        return hfail(SDR_ERR_BAD_ARG, "null chain or output");
+        return fail(SDR_ERR_BAD_ARG, "null chain or output");
     if (band < 0 || band >= c->n_bands)
-        return hfail(SDR_ERR_BAD_ARG, "band out of range");
+        return fail(SDR_ERR_BAD_ARG, "band out of range");
     if (n < 1 || from < c->plan.base || from > c->plan.have - n)
-        return hfail(SDR_ERR_BAD_ARG, "sdr_chain_read_narrow: the samples are not resident in the ring (sdr_chain_stats: resident_from .. narrow)");
-    HHIP(hipSetDevice(c->device));
-    HHIP(hipStreamSynchronize(c->stream));
+        return fail(SDR_ERR_BAD_ARG, "sdr_chain_read_narrow: the samples are not resident in the ring (sdr_chain_stats: resident_from .. narrow)");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     const float *src = c->d_ring + 2 * ((size_t)band * (size_t)c->plan.g.ring + (size_t)(from - c->plan.base));
-    HHIP(hipMemcpy(out_host, src, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_host, src, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost));
     return SDR_OK;
 }
 
 int sdr_chain_stats(sdr_chain *c, sdr_chain_counts *out)
 {
     if (!c || !out)
-        return hfail(SDR_ERR_BAD_ARG, "null chain or output");
+        return fail(SDR_ERR_BAD_ARG, "null chain or output");
     const sdr::ChainPlan &p = c->plan;
     *out = sdr_chain_counts{};
     out->accepted = p.accepted;
