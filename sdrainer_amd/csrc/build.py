@@ -22,7 +22,7 @@ HEADERS = ["sdr_device.h", "bank.h", "host/batch_plan.h", "host/delivery.h", "ho
            "nb.h", "host/nb_rule.h",
            "fine.h", "host/fine_tune.h",
            "chain.h", "host/chain_plan.h",
-           "front.h", "host/front_rules.h",
+           "front.h", "host/front_rules.h", "front_input.h",
            "../../include/sdrainer_hip.h"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fvisibility=hidden", "-Wall", "-Wno-unused-function",

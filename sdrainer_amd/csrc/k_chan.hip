@@ -3,25 +3,14 @@
 // the arithmetic's contract are k_chan.h.
 #include "k_chan.h"
 
-#include "ddc_input_real.h"
-#include "fft_input.h"
-#include "host/ddc_format.h"
+#include "front_input.h"
 
 namespace sdr {
 
 hipError_t launch_chan(const ChanLaunch &l, hipStream_t stream)
 {
-    switch (l.fmt) {
-    case SDR_DDC_F32: return launch_chan_as(InF32{}, l, stream);
-    case SDR_DDC_SC16: return launch_chan_as(InSc16{}, l, stream);
-    case SDR_DDC_CS8:
-    case SDR_DDC_CU8: return launch_chan_as(InIq8{iq8::format_of(l.fmt == SDR_DDC_CU8)}, l, stream);
-    case SDR_DDC_RF32: return launch_chan_as(InRealF32{}, l, stream);
-    case SDR_DDC_RS16: return launch_chan_as(InRealS16{}, l, stream);
-    case SDR_DDC_RS8:
-    case SDR_DDC_RU8: return launch_chan_as(InReal8{iq8::format_of(ddc_complex_base(l.fmt) == SDR_DDC_CU8)}, l, stream);
-    }
-    return hipErrorInvalidValue;
+    const auto launch = [&](auto in) { return launch_chan_as(in, l, stream); };
+    return !ddc_is_real(l.fmt) ? with_complex_input(l.fmt, launch) : with_real_input(l.fmt, launch);
 }
 
 }  // namespace sdr

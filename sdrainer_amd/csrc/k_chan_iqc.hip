@@ -3,20 +3,14 @@
 // body and the arithmetic's contract are k_chan.h; k_chan.hip keeps exactly the kernels it holds.
 #include "k_chan.h"
 
-#include "fft_input.h"
+#include "front_input.h"
 #include "iq_correct.h"
 
 namespace sdr {
 
 hipError_t launch_chan_iqc(const ChanLaunch &l, const sdr_iq_correction &c, hipStream_t stream)
 {
-    switch (l.fmt) {
-    case SDR_DDC_F32: return launch_chan_as(corrected(InF32{}, c), l, stream);
-    case SDR_DDC_SC16: return launch_chan_as(corrected(InSc16{}, c), l, stream);
-    case SDR_DDC_CS8:
-    case SDR_DDC_CU8: return launch_chan_as(corrected(InIq8{iq8::format_of(l.fmt == SDR_DDC_CU8)}, c), l, stream);
-    }
-    return hipErrorInvalidValue;  // (a real format has no correction)
+    return with_complex_input(l.fmt, [&](auto in) { return launch_chan_as(corrected(in, c), l, stream); });  // (no real format)
 }
 
 }  // namespace sdr

@@ -2,20 +2,14 @@
 // format.  The kernel bodies and the arithmetic's contract are k_ddc.h; the real formats' instances are k_ddc_real.hip.
 #include "k_ddc.h"
 
-#include "fft_input.h"
-#include "host/ddc_format.h"
+#include "front_input.h"
 
 namespace sdr {
 
 hipError_t launch_ddc(const DdcLaunch &l, hipStream_t stream)
 {
-    switch (l.fmt) {
-    case SDR_DDC_F32: return launch_ddc_as(InF32{}, l, stream);
-    case SDR_DDC_SC16: return launch_ddc_as(InSc16{}, l, stream);
-    case SDR_DDC_CS8: return launch_ddc_as(InIq8{iq8::format_of(false)}, l, stream);
-    case SDR_DDC_CU8: return launch_ddc_as(InIq8{iq8::format_of(true)}, l, stream);
-    }
-    return ddc_format_valid(l.fmt) && ddc_is_real(l.fmt) ? launch_ddc_real(l, stream) : hipErrorInvalidValue;
+    const auto launch = [&](auto in) { return launch_ddc_as(in, l, stream); };
+    return ddc_is_real(l.fmt) ? launch_ddc_real(l, stream) : with_complex_input(l.fmt, launch);
 }
 
 // the carry moves raw words: the kernel is chosen by the sample's size alone

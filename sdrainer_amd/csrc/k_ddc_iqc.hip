@@ -3,20 +3,14 @@
 // body and the arithmetic's contract are k_ddc.h; k_ddc.hip and k_ddc_real.hip keep exactly the kernels they hold.
 #include "k_ddc.h"
 
-#include "fft_input.h"
+#include "front_input.h"
 #include "iq_correct.h"
 
 namespace sdr {
 
 hipError_t launch_ddc_iqc(const DdcLaunch &l, const sdr_iq_correction &c, hipStream_t stream)
 {
-    switch (l.fmt) {
-    case SDR_DDC_F32: return launch_ddc_as(corrected(InF32{}, c), l, stream);
-    case SDR_DDC_SC16: return launch_ddc_as(corrected(InSc16{}, c), l, stream);
-    case SDR_DDC_CS8: return launch_ddc_as(corrected(InIq8{iq8::format_of(false)}, c), l, stream);
-    case SDR_DDC_CU8: return launch_ddc_as(corrected(InIq8{iq8::format_of(true)}, c), l, stream);
-    }
-    return hipErrorInvalidValue;  // (a real format has no correction)
+    return with_complex_input(l.fmt, [&](auto in) { return launch_ddc_as(corrected(in, c), l, stream); });  // (no real format)
 }
 
 }  // namespace sdr

@@ -8,8 +8,7 @@
 // ahead at D = 64 and 256 and 9 % behind at D = 8 (profiles/ddc_real_rate.json).
 #include "k_ddc.h"
 
-#include "ddc_input_real.h"
-#include "host/ddc_format.h"
+#include "front_input.h"
 
 namespace sdr {
 
@@ -17,13 +16,7 @@ namespace sdr {
 
 hipError_t launch_ddc_real(const DdcLaunch &l, hipStream_t stream)
 {
-    switch (l.fmt) {
-    case SDR_DDC_RF32: return launch_ddc_as(InRealF32{}, l, stream);
-    case SDR_DDC_RS16: return launch_ddc_as(InRealS16{}, l, stream);
-    case SDR_DDC_RS8:
-    case SDR_DDC_RU8: return launch_ddc_as(InReal8{iq8::format_of(ddc_complex_base(l.fmt) == SDR_DDC_CU8)}, l, stream);
-    }
-    return hipErrorInvalidValue;
+    return with_real_input(l.fmt, [&](auto in) { return launch_ddc_as(in, l, stream); });
 }
 
 hipError_t launch_ddc_carry_byte(const void *carry_in, const void *in, int n_in, int keep, void *carry_out, hipStream_t stream)

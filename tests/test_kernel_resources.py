@@ -3,32 +3,20 @@ register in use, and a toolchain or source change that pushes its prefetched sam
 the kernel without changing a single result.  The kernel is compiled device-only for gfx950 with the library's own
 flags (sdrainer_amd/csrc/build.py) and the compiler's resource report is read."""
 import os
-import re
 import subprocess
 
 import pytest
 
+from kernel_report import kernel_report, only_kernel
 from sdrainer_amd.csrc import build as hip_build
 
-SRC = os.path.join(hip_build.HERE, "k_fft_r32.hip")
+UNIT = "k_fft_r32.hip"
 
 
 @pytest.fixture(scope="module")
 def usage(tmp_path_factory):
-    try:
-        cc = hip_build.hipcc()
-    except RuntimeError as e:
-        pytest.fail(str(e))
-    out = tmp_path_factory.mktemp("res") / "k_fft_r32.o"
-    flags = hip_build.FLAGS + hip_build.EXTRA_FLAGS.get("k_fft_r32.hip", [])
-    cmd = [cc] + flags + ["--cuda-device-only", "-c", SRC, "-o", str(out), "-Rpass-analysis=kernel-resource-usage"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-4000:]
-    # the remarks of the instance k_fft_r32<InF32, false> (its mangled name: ...k_fft_r32INS_5InF32ELb0E...), up to the
-    # next function's
-    m = re.search(r"Function Name: \S*k_fft_r32INS_5InF32ELb0E\S*(.*?)(?:Function Name:|\Z)", p.stderr, re.S)
-    assert m, "no resource report for k_fft_r32<InF32, false>"
-    return {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", m.group(1))}
+    # the instance k_fft_r32<InF32, false> (its mangled name: ...k_fft_r32INS_5InF32ELb0E...)
+    return only_kernel(kernel_report(UNIT, tmp_path_factory), "k_fft_r32INS_5InF32ELb0E")
 
 
 def _int(usage, key):

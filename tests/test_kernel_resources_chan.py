@@ -5,10 +5,10 @@ The LDS is dynamic (span and image, csrc/chan.h): the report's static LDS and th
 the 160 KB of a CU for every legal geometry, sdr_chan_tile_outputs is what the restated shape says, and it is at least 16."""
 import os
 import re
-import subprocess
 
 import pytest
 
+from kernel_report import kernel_report
 from sdrainer_amd.csrc import build as hip_build
 
 UNIT = "k_chan.hip"
@@ -18,21 +18,9 @@ LDS_LIMIT = 160 * 1024
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
-    try:
-        cc = hip_build.hipcc()
-    except RuntimeError as e:
-        pytest.fail(str(e))
     assert UNIT in hip_build.SOURCES and "capi_chan.hip" in hip_build.SOURCES
-    assert all(h in hip_build.HEADERS for h in ("chan.h", "k_chan.h", "ddc_input_real.h", "host/nco_table.h"))
-    out = tmp_path_factory.mktemp("res") / UNIT.replace(".hip", ".o")
-    cmd = [cc] + hip_build.FLAGS + hip_build.EXTRA_FLAGS.get(UNIT, []) + ["--cuda-device-only", "-c", os.path.join(hip_build.HERE, UNIT), "-o", str(out),
-                                                                        "-Rpass-analysis=kernel-resource-usage"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-4000:]
-    usage = {}
-    for name, body in re.findall(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", p.stderr, re.S):
-        usage[name] = {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", body)}
-    return usage
+    assert all(h in hip_build.HEADERS for h in ("chan.h", "k_chan.h", "ddc_input_real.h", "front_input.h", "host/nco_table.h"))
+    return kernel_report(UNIT, tmp_path_factory)
 
 
 def test_the_unit_holds_exactly_the_channelizer_kernels(report):

@@ -6,10 +6,10 @@ LDS and the largest image the launcher may ask for both stay within the 160 KB o
 header, the binding and the kernel agree."""
 import os
 import re
-import subprocess
 
 import pytest
 
+from kernel_report import kernel_report
 from sdrainer_amd.csrc import build as hip_build
 
 UNIT = "k_ddc.hip"
@@ -19,20 +19,8 @@ LDS_LIMIT = 160 * 1024
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
-    try:
-        cc = hip_build.hipcc()
-    except RuntimeError as e:
-        pytest.fail(str(e))
-    assert UNIT in hip_build.SOURCES and "capi_ddc.hip" in hip_build.SOURCES and "ddc.h" in hip_build.HEADERS
-    out = tmp_path_factory.mktemp("res") / UNIT.replace(".hip", ".o")
-    cmd = [cc] + hip_build.FLAGS + hip_build.EXTRA_FLAGS.get(UNIT, []) + ["--cuda-device-only", "-c", os.path.join(hip_build.HERE, UNIT), "-o", str(out),
-                                                                        "-Rpass-analysis=kernel-resource-usage"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-4000:]
-    usage = {}
-    for name, body in re.findall(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", p.stderr, re.S):
-        usage[name] = {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", body)}
-    return usage
+    assert UNIT in hip_build.SOURCES and "capi_ddc.hip" in hip_build.SOURCES and "ddc.h" in hip_build.HEADERS and "front_input.h" in hip_build.HEADERS
+    return kernel_report(UNIT, tmp_path_factory)
 
 
 def test_the_unit_holds_exactly_the_ddc_kernels(report):

@@ -5,11 +5,10 @@ int16 and byte word) and k_ddc_carry over the one-byte word - each with no spill
 within the 160 KB of a CU (the image is dynamic: tests/test_kernel_resources_ddc.py restates its size) and registers that
 leave room for at least four waves per SIMD."""
 import os
-import re
-import subprocess
 
 import pytest
 
+from kernel_report import kernel_report
 from sdrainer_amd.csrc import build as hip_build
 
 UNIT = "k_ddc_real.hip"
@@ -19,20 +18,8 @@ LDS_LIMIT = 160 * 1024
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
-    try:
-        cc = hip_build.hipcc()
-    except RuntimeError as e:
-        pytest.fail(str(e))
     assert UNIT in hip_build.SOURCES and "k_ddc.h" in hip_build.HEADERS and "host/ddc_format.h" in hip_build.HEADERS
-    out = tmp_path_factory.mktemp("res") / UNIT.replace(".hip", ".o")
-    cmd = [cc] + hip_build.FLAGS + hip_build.EXTRA_FLAGS.get(UNIT, []) + ["--cuda-device-only", "-c", os.path.join(hip_build.HERE, UNIT), "-o", str(out),
-                                                                        "-Rpass-analysis=kernel-resource-usage"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-4000:]
-    usage = {}
-    for name, body in re.findall(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", p.stderr, re.S):
-        usage[name] = {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", body)}
-    return usage
+    return kernel_report(UNIT, tmp_path_factory)
 
 
 def test_the_unit_holds_exactly_the_real_ddc_kernels(report):

@@ -3,12 +3,9 @@ checks the sc16 kernel: the instances k_fft_r32<InIq8, false> (k_fft_r32_iq8.hip
 (k_fft_r32_hop_iq8.hip) of k_fft_r32.h, device-only for gfx950 with the library's own flags, and the compiler's resource report read.  Each
 kernel must run at two waves per SIMD with nothing in scratch and no spilled vector register; the strided form may keep a
 scalar register in a vector register's lane, as k_fft_r32_hop does.  Each unit holds its 8-bit kernel and no other."""
-import os
-import re
-import subprocess
-
 import pytest
 
+from kernel_report import kernel_report, only_kernel
 from sdrainer_amd.csrc import build as hip_build
 
 # (the mangled names of the two instances: ...k_fft_r32INS_5InIq8ELb0E<argument pack and parameters>)
@@ -18,22 +15,11 @@ UNITS = {"k_fft_r32_iq8.hip": "k_fft_r32INS_5InIq8ELb0E", "k_fft_r32_hop_iq8.hip
 @pytest.fixture(scope="module", params=sorted(UNITS))
 def usage(request, tmp_path_factory):
     unit, kernel = request.param, UNITS[request.param]
-    try:
-        cc = hip_build.hipcc()
-    except RuntimeError as e:
-        pytest.fail(str(e))
     assert unit in hip_build.SOURCES
     assert hip_build.EXTRA_FLAGS[unit] == hip_build.EXTRA_FLAGS["k_fft_r32.hip"]
-    out = tmp_path_factory.mktemp("res") / unit.replace(".hip", ".o")
-    cmd = [cc] + hip_build.FLAGS + hip_build.EXTRA_FLAGS[unit] + ["--cuda-device-only", "-c", os.path.join(hip_build.HERE, unit), "-o", str(out),
-                                                               "-Rpass-analysis=kernel-resource-usage"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-4000:]
-    names = re.findall(r"Function Name: (\S+)", p.stderr)
-    assert len(names) == 1 and kernel in names[0], names
-    m = re.search(r"Function Name: \S*" + kernel + r"\S*(.*?)(?:Function Name:|\Z)", p.stderr, re.S)
-    assert m, "no resource report for " + kernel
-    u = {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", m.group(1))}
+    report = kernel_report(unit, tmp_path_factory)
+    assert len(report) == 1, sorted(report)
+    u = dict(only_kernel(report, kernel))
     u["hop"] = "hop" in unit
     return u
 

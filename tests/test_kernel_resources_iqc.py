@@ -3,12 +3,9 @@ k_ddc_iqc.hip, k_chan_iqc.hip and k_iq_sums.hip compiled device-only for gfx950 
 compiler's resource report read.  Each unit holds exactly its instances - k_ddc and k_chan over the three corrected traits,
 the two sums kernels and their finishing pass - with no spilled register and nothing in scratch; the corrected kernels keep
 the occupancy of the uncorrected ones, and the sums kernels' static LDS is the four waves' totals."""
-import os
-import re
-import subprocess
-
 import pytest
 
+from kernel_report import kernel_report
 from sdrainer_amd.csrc import build as hip_build
 
 UNITS = {
@@ -21,24 +18,9 @@ CASES = [(u, k) for u, ks in UNITS.items() for k in ks]
 
 @pytest.fixture(scope="module")
 def reports(tmp_path_factory):
-    try:
-        cc = hip_build.hipcc()
-    except RuntimeError as e:
-        pytest.fail(str(e))
     assert all(u in hip_build.SOURCES for u in UNITS)
     assert all(h in hip_build.HEADERS for h in ("iq_correct.h", "iq_sums_dev.h", "host/iq_sums.h"))
-    tmp = tmp_path_factory.mktemp("res")
-    out = {}
-    for unit in UNITS:
-        cmd = [cc] + hip_build.FLAGS + hip_build.EXTRA_FLAGS.get(unit, []) + ["--cuda-device-only", "-c", os.path.join(hip_build.HERE, unit), "-o",
-                                                                             str(tmp / unit.replace(".hip", ".o")), "-Rpass-analysis=kernel-resource-usage"]
-        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, p.stderr[-4000:]
-        usage = {}
-        for name, body in re.findall(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", p.stderr, re.S):
-            usage[name] = {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", body)}
-        out[unit] = usage
-    return out
+    return {unit: kernel_report(unit, tmp_path_factory) for unit in UNITS}
 
 
 @pytest.mark.parametrize("unit", list(UNITS))

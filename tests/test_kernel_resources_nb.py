@@ -7,11 +7,10 @@ format, the carry pass - with no spilled register and nothing in scratch.  The e
 the carry pass its two 8-byte totals; both streaming passes are memory-bound and want every wave slot, which 64 VGPRs or
 fewer and a 256-thread workgroup give: 8 waves per SIMD."""
 import os
-import re
-import subprocess
 
 import pytest
 
+from kernel_report import kernel_report
 from sdrainer_amd.csrc import build as hip_build
 
 UNIT = "k_nb.hip"
@@ -25,21 +24,9 @@ TILE_BLOCKS = TILE_BYTES // MIN_BLOCK_BYTES
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
-    try:
-        cc = hip_build.hipcc()
-    except RuntimeError as e:
-        pytest.fail(str(e))
     assert UNIT in hip_build.SOURCES and "capi_nb.hip" in hip_build.SOURCES
     assert all(h in hip_build.HEADERS for h in ("nb.h", "host/nb_rule.h"))
-    tmp = tmp_path_factory.mktemp("res")
-    cmd = [cc] + hip_build.FLAGS + hip_build.EXTRA_FLAGS.get(UNIT, []) + ["--cuda-device-only", "-c", os.path.join(hip_build.HERE, UNIT), "-o",
-                                                                         str(tmp / UNIT.replace(".hip", ".o")), "-Rpass-analysis=kernel-resource-usage"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-4000:]
-    usage = {}
-    for name, body in re.findall(r"Function Name: (\S+)(.*?)(?=Function Name:|\Z)", p.stderr, re.S):
-        usage[name] = {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", body)}
-    return usage
+    return kernel_report(UNIT, tmp_path_factory)
 
 
 def test_the_unit_holds_exactly_its_kernels(report):

@@ -2,36 +2,22 @@
 float32 kernel: the instance k_fft_r32<InSc16, false> of k_fft_r32.h (k_fft_r32_sc16.hip), device-only for gfx950 with the
 library's own flags, and the compiler's resource report read.  The sc16 kernel must run at two waves per SIMD with
 nothing in scratch, like the float32 one; its prefetched frame is 32 registers instead of 64."""
-import os
-import re
-import subprocess
-
 import pytest
 
+from kernel_report import kernel_report, only_kernel
 from sdrainer_amd.csrc import build as hip_build
 
-SRC = os.path.join(hip_build.HERE, "k_fft_r32_sc16.hip")
+UNIT = "k_fft_r32_sc16.hip"
 KERNEL = "k_fft_r32INS_6InSc16ELb0E"  # (the mangled name of k_fft_r32<InSc16, false>: ...k_fft_r32INS_6InSc16ELb0E...)
 
 
 @pytest.fixture(scope="module")
 def usage(tmp_path_factory):
-    try:
-        cc = hip_build.hipcc()
-    except RuntimeError as e:
-        pytest.fail(str(e))
-    assert "k_fft_r32_sc16.hip" in hip_build.SOURCES
-    out = tmp_path_factory.mktemp("res") / "k_fft_r32_sc16.o"
-    flags = hip_build.FLAGS + hip_build.EXTRA_FLAGS["k_fft_r32_sc16.hip"]
-    assert hip_build.EXTRA_FLAGS["k_fft_r32_sc16.hip"] == hip_build.EXTRA_FLAGS["k_fft_r32.hip"]
-    cmd = [cc] + flags + ["--cuda-device-only", "-c", SRC, "-o", str(out), "-Rpass-analysis=kernel-resource-usage"]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-4000:]
-    names = re.findall(r"Function Name: (\S+)", p.stderr)
-    assert not any("k_fft_r32" in n and KERNEL not in n for n in names), names
-    m = re.search(r"Function Name: \S*" + KERNEL + r"\S*(.*?)(?:Function Name:|\Z)", p.stderr, re.S)
-    assert m, "no resource report for k_fft_r32_sc16"
-    return {k.strip(): v for k, v in re.findall(r"remark: +([A-Za-z][A-Za-z /\[\]]*?): (\S+)", m.group(1))}
+    assert UNIT in hip_build.SOURCES
+    assert hip_build.EXTRA_FLAGS[UNIT] == hip_build.EXTRA_FLAGS["k_fft_r32.hip"]
+    report = kernel_report(UNIT, tmp_path_factory)
+    assert not any("k_fft_r32" in n and KERNEL not in n for n in report), sorted(report)
+    return only_kernel(report, KERNEL)
 
 
 def _int(usage, key):
